@@ -11,15 +11,27 @@ fwd+bwd+update and student fwd+bwd+update) on one batch of B=256 videos x 300
 frames x 1152 features PER GPU (weak scaling).  Inputs are resident in HBM when
 the timed region starts.  Rank 0 prints ONE JSON line.
 
-The headline (`value`, `ms_per_step`, `roofline`) is BASELINE cfg 3 in plain bf16 (one MFMA product per
-contraction, as north_star prescribes).  At N=1 the same line also carries, each timed the same way on a short run:
+The headline (`value`, `ms_per_step`) is BASELINE cfg 3 in plain bf16 (one MFMA product per contraction, as north_star
+prescribes).  A plain run does only that: set up, warm up, time the K steps, write the outputs (--dump-outputs) and print
+the line.  Everything else runs only with `--full`: the in-step `roofline` / `rooflines` of the headline, and at N=1
+the same line also carries, each timed the same way on a short run:
   precision_modes   the same step in the "high" forward mode (IEEE f16 operands + low-order corrections on the MX-scaled MFMA,
                     DESIGN.md 7: the mode that holds the 1e-3 logit tolerance on trained-magnitude weights,
                     tests/test_gpu_step.py) next to the bf16 figure;
   other_configs     BASELINE cfg 2 (teacher only), cfg 5 (student only, every_n=30, B=1024), cfg 4 (DBoF + MoE,
                     B=512, with the roofline of its cluster GEMM) and the all-300-frames worst case;
   cpu_baseline      the PyTorch-CPU float32 restatement of the reference graph (oracle/torch_cpu.py) on the host cores.
-`--config dbof` makes cfg 4 the timed workload of the line instead (its own metric string).
+`--config dbof` makes cfg 4 the timed workload of the line instead (its own metric string; `--full` adds its roofline).
+
+`--dump-outputs DIR` writes what the last timed step computed, as a caller of the step receives it (predictions, states,
+losses) plus a fixed, seeded sample of each tower's updated f32 weights, as DIR/<name>.npy (float32; float64 for integer
+outputs), at most 64 MB in all.  The inputs and the initial weights are seeded: with the same arguments two builds can be
+compared output for output.  With --dump-outputs bench.py runs the library with EVC_DETERMINISTIC=1 unless the environment says
+otherwise: no floating-point atomics on the training path, so what the timed steps compute is the same on every run (the dumps
+of two runs are bit-identical but for the pred_loss scalar, which takes one atomic per video row).  With the atomic split-K joins
+of a plain run two runs differ in the last bits of the gradient sums, and the training steps before the dump (settle pass,
+warm-up, timed steps) amplify that through Adam far beyond rounding; the atomic joins make the step about 5 % faster, so the
+plain run keeps them.  The line says which path was timed (schedule.deterministic).
 
 Every timed figure carries `ms_per_step` (mean over the K timed steps: wall clock between the two barriers, what the
 driver's own clock checks), `ms_per_step_median` / `ms_per_step_max` (HIP events on the caller's stream after every step) and
@@ -92,6 +104,48 @@ class StepClock:
         return self.ev[0].elapsed_time(getattr(self, "end", self.ev[-1]))
 
 
+def ops_deterministic():
+    from efficientvideoclassification_youtube8m_amd import ops
+    return bool(ops.DETERMINISTIC)
+
+
+DUMP_MAX_ELEMS = 1 << 21           # --dump-outputs: a larger array is written as a fixed, seeded sample of at most this many of its elements
+DUMP_MAX_BYTES = 64 << 20
+
+
+def step_outputs(out, towers):
+    """The arrays of one training step's result dict (tensors and numbers, as the caller of step() receives them) plus the
+    updated f32 weights of each tower (flat master buffer, sampled by dump_outputs)."""
+    arrays = {k: v for k, v in out.items() if torch.is_tensor(v) or isinstance(v, (int, float))}
+    for name, tw in towers:
+        if tw is not None:
+            arrays["%s_weights" % name] = tw.store.master
+    return arrays
+
+
+def dump_outputs(directory, arrays):
+    """Writes every array as <directory>/<name>.npy: float32 (float64 stays float64, integers and booleans become float64).  An
+    array of more than DUMP_MAX_ELEMS elements is written as the same seeded sample of its flattened elements in every run (the
+    indices depend only on its size; the sample is gathered on the device).  Returns {name: "full [shape]" | "sample n of N"}."""
+    os.makedirs(directory, exist_ok=True)
+    what, total = {}, 0
+    for name, v in arrays.items():
+        t = v.detach() if torch.is_tensor(v) else torch.as_tensor(v)
+        n = t.numel()
+        if n > DUMP_MAX_ELEMS:       # DUMP_MAX_ELEMS seeded draws, duplicates dropped (sorted): no permutation of all n indices
+            idx = np.unique(np.random.default_rng(0).integers(0, n, size=DUMP_MAX_ELEMS, dtype=np.int64))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            what[name] = "sample %d of %d (seeded)" % (idx.size, n)
+        else:
+            what[name] = "full %s" % list(t.shape)
+        a = (t.double() if t.dtype == torch.float64 or not t.is_floating_point() else t.float()).cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise RuntimeError("--dump-outputs: more than %d bytes (at %s)" % (DUMP_MAX_BYTES, name))
+        np.save(os.path.join(directory, name + ".npy"), a)
+    return what
+
+
 def synthetic_inputs(B, T, F, V, seed, device, all_full, as_uint8=False):
     """uint8-uniform features dequantised as cs/utils.py:22-25,
     n ~ U{120..300} with padded rows zeroed, ~3 positives per video (+class 0 w.p. 0.3).
@@ -149,9 +203,10 @@ def hlstm_gflop(n_host, mode, every_n, B, row_plans=True):
 
 
 def run_hlstm(device, rank, world, B, mode, every_n, steps, warmup, all_full=False, precision="bf16", pool=8,
-              overlap=True, fused_moe=True, student_forward_early=False, roofline=False, input_u8=False):
+              overlap=True, fused_moe=True, student_forward_early=False, roofline=False, input_u8=False, dump=None):
     """Times `steps` training iterations of one DistillGraph configuration (after `warmup`), inputs resident in HBM.
-    Returns a dict; with roofline=True also the live timing of the teacher's L1 forward step launches."""
+    Returns a dict; with roofline=True also the live timing of the teacher's L1 forward step launches; with dump=DIR
+    (rank 0) the last timed step's outputs are written there (dump_outputs)."""
     from efficientvideoclassification_youtube8m_amd.distill import DistillGraph
     pool_in = [synthetic_inputs(B, T_FRAMES, F_FEAT, V_CLS, 1234 + rank + 1000 * i, device, all_full, as_uint8=input_u8) for i in range(pool)]
     # the frame counts also live on the host, as an input pipeline has them before the H2D copy (the launch
@@ -199,7 +254,7 @@ def run_hlstm(device, rank, world, B, mode, every_n, steps, warmup, all_full=Fal
     t0 = time.perf_counter()
     for _ in range(steps):
         x, n, labels = pool_in[it % pool]
-        graph.step(x, labels, n, num_frames_host=n_host[it % pool])
+        out = graph.step(x, labels, n, num_frames_host=n_host[it % pool])
         it += 1
         clock.tick()
     graph.flush()              # defer_updates: the last step's MoE / L2-level updates are enqueued and joined INSIDE the timed region
@@ -209,6 +264,9 @@ def run_hlstm(device, rank, world, B, mode, every_n, steps, warmup, all_full=Fal
     barrier()
     dt = time.perf_counter() - t0
     per_step = clock.per_step_ms()
+    dumped = None
+    if dump and rank == 0:     # before anything below launches more work on the graph's buffers
+        dumped = dump_outputs(dump, step_outputs(out, (("teacher", graph.teacher), ("student", graph.student))))
     if os.environ.get("EVC_BENCH_STEP_EVENTS") == "1":
         sys.stderr.write("[bench] per-step ms (events on the caller's stream): %s\n" % " ".join("%.1f" % v for v in per_step))
     if world > 1:
@@ -221,8 +279,11 @@ def run_hlstm(device, rank, world, B, mode, every_n, steps, warmup, all_full=Fal
            "executed_tflop_per_step": round(float(np.mean([g[1] for g in gf])) / 1e3, 3),
            "losses": {k: round(v, 4) for k, v in graph.loss_report().items()},
            "schedule": {"defer_updates": bool(graph.defer_updates and not graph.dp), "student_forward_early": bool(graph.student_forward_early),
-                        "student_forward_after_l1": bool(graph.student_forward_after_l1), "opt_cu_mask": os.environ.get("EVC_OPT_CU_MASK")}}
+                        "student_forward_after_l1": bool(graph.student_forward_after_l1), "opt_cu_mask": os.environ.get("EVC_OPT_CU_MASK"),
+                        "deterministic": ops_deterministic()}}
     res["executed_tflops"] = round(res["executed_tflop_per_step"] / (res["ms_per_step"] * 1e-3), 1)
+    if dumped is not None:
+        res["dumped_outputs"] = dumped
     if precision != "bf16":
         res["high_layout"] = {tw.scope: tw.precision_layout() for tw in (graph.teacher, graph.student) if tw is not None}
     if dp_on:
@@ -352,9 +413,10 @@ def run_hlstm(device, rank, world, B, mode, every_n, steps, warmup, all_full=Fal
     return res
 
 
-def run_dbof(device, rank, world, B, steps, warmup, pool=4, precision="bf16"):
+def run_dbof(device, rank, world, B, steps, warmup, pool=4, precision="bf16", roofline=True, dump=None):
     """BASELINE cfg 4: DbofModel (cluster 8192, hidden 1024, 30 sampled frames) + MoE(2), one training step per
-    batch of B videos (cs/frame_level_models.py:108-195).  uint8 inputs resident in HBM."""
+    batch of B videos (cs/frame_level_models.py:108-195).  uint8 inputs resident in HBM.  roofline: live timing of the
+    cluster GEMM launches; dump=DIR (rank 0): the last timed step's outputs (dump_outputs)."""
     from efficientvideoclassification_youtube8m_amd.distill import SingleTowerGraph
     from efficientvideoclassification_youtube8m_amd.towers import DbofTower
     g = torch.Generator(device=device)
@@ -381,14 +443,14 @@ def run_dbof(device, rank, world, B, steps, warmup, pool=4, precision="bf16"):
     if world > 1:
         torch.distributed.barrier()
     torch.cuda.synchronize()
-    if hasattr(tw, "timing"):
+    if roofline and hasattr(tw, "timing"):
         tw.timing = []
     clock = StepClock()
     clock.tick()
     t0 = time.perf_counter()
     for i in range(steps):
         x, n, labels, u = pool_in[(warmup + i) % pool]
-        graph.step(x, labels, n, uniform=u)
+        out = graph.step(x, labels, n, uniform=u)
         clock.tick()
     clock.close()
     torch.cuda.synchronize()
@@ -398,6 +460,7 @@ def run_dbof(device, rank, world, B, steps, warmup, pool=4, precision="bf16"):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     per_step = clock.per_step_ms()
+    dumped = dump_outputs(dump, step_outputs(out, (("dbof", tw),))) if dump and rank == 0 else None
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=device)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
@@ -408,6 +471,8 @@ def run_dbof(device, rank, world, B, steps, warmup, pool=4, precision="bf16"):
            **step_stats(per_step, dt_local / steps * 1e3, clock.span_ms() / steps),
            "nominal_tflop_per_step": round(3 * gflop_fwd / 1e3, 4), "loss": round(float(graph.losses[0]), 4)}
     res["nominal_tflops"] = round(res["nominal_tflop_per_step"] / (res["ms_per_step"] * 1e-3), 1)
+    if dumped is not None:
+        res["dumped_outputs"] = dumped
     timing = getattr(tw, "timing", None)
     if timing:
         ms = sum(e0.elapsed_time(e1) for e0, e1 in timing) / len(timing)
@@ -623,7 +688,18 @@ def main():
     ap.add_argument("--student_forward_early", action="store_true", help="A/B: student forward next to the teacher forward")
     ap.add_argument("--no_overlap", action="store_true", help="debug: everything on one stream (solo kernel times for profiling)")
     ap.add_argument("--pool", type=int, default=8, help="distinct synthetic batches cycled through (HBM resident)")
+    ap.add_argument("--full", action="store_true", help="also the in-step rooflines and, at N=1, precision_modes / other_configs and the "
+                    "cpu_baseline leg (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64, <= 64 MB; larger arrays as a seeded sample)")
     args = ap.parse_args()
+    if args.dump_outputs:
+        # A run that writes its outputs computes the same ones on every run: no floating-point atomics on the training path (the library
+        # and ops read the switch once, at their first use, after this line).  Under the atomic split-K joins two runs differ in the last
+        # bits of the gradient sums, and Adam turns the flipped sign of a near-zero gradient into a whole step: the dumps of two runs
+        # would differ far beyond rounding.  A plain run keeps the atomic joins (about 5 % faster); an explicit EVC_DETERMINISTIC in the
+        # environment wins either way.
+        os.environ.setdefault("EVC_DETERMINISTIC", "1")
 
     if args.cpu_baseline_only:
         print(json.dumps({"cpu_baseline": cpu_baseline(args.every_n, args.cpu_videos, args.cpu_budget, args.cpu_threads)}))
@@ -667,7 +743,7 @@ def main():
 
     if args.config == "dbof":
         B = args.batch or 512
-        r = run_dbof(device, rank, world, B, args.steps, args.warmup, precision=args.precision)
+        r = run_dbof(device, rank, world, B, args.steps, args.warmup, precision=args.precision, roofline=args.full, dump=args.dump_outputs)
         if rank == 0:
             res = {"metric": "frames/sec (whole node) DBoF(8192,1024)+MoE(2) training step B=512x300x1152 (BASELINE cfg 4)",
                    "value": r["frames_per_sec"], "unit": "frames/sec", "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
@@ -676,8 +752,9 @@ def main():
                    "config": {"workload": "DbofModel cluster 8192, hidden 1024, 30 sampled frames, MoE(2), batch %d x 300 x 1152 per GPU" % B,
                               "global_batch": B * n_gpus, "frames_per_video": T_FRAMES, "parallelism": "dp%d" % n_gpus},
                    "videos_per_sec": r["videos_per_sec"], "nominal_tflop_per_step": r["nominal_tflop_per_step"], "loss": r["loss"]}
-            if "roofline" in r:
-                res["roofline"] = r["roofline"]
+            for k in ("roofline", "dumped_outputs"):
+                if k in r:
+                    res[k] = r[k]
             print(json.dumps(res))
         if world > 1 or one_rank_dp:
             torch.distributed.destroy_process_group()
@@ -689,9 +766,10 @@ def main():
             raise SystemExit("--global_batch %d must be a multiple of --gpus %d (and excludes --batch)" % (args.global_batch, n_gpus))
         B = args.global_batch // n_gpus
     head = run_hlstm(device, rank, world, B, args.mode, args.every_n, args.steps, args.warmup, args.all_full, args.precision,
-                     args.pool, not args.no_overlap, not args.no_fused_moe, args.student_forward_early, roofline=True, input_u8=args.input == "uint8")
+                     args.pool, not args.no_overlap, not args.no_fused_moe, args.student_forward_early, roofline=args.full, input_u8=args.input == "uint8",
+                     dump=args.dump_outputs)
     _log("headline done: %.2f ms/step" % head["ms_per_step"])
-    secondary = n_gpus == 1 and not args.no_secondary and not one_rank_dp
+    secondary = args.full and n_gpus == 1 and not args.no_secondary and not one_rank_dp
     extra = {}
     if secondary:
         s_steps, s_warm = 5, 2
@@ -776,8 +854,9 @@ def main():
             "losses": head["losses"], "gap_at_20_last_batch": head["gap_at_20_last_batch"],
             "roofline": head.get("roofline"), "rooflines": head.get("rooflines"), "schedule": head.get("schedule"),
         }
-        if "dp" in head:
-            res["dp"] = head["dp"]
+        for k in ("dp", "dumped_outputs"):
+            if k in head:
+                res[k] = head[k]
         res.update(extra)
     # The CPU leg runs on rank 0 AFTER the process group is gone (no peer waits inside a collective while rank 0 spends a minute on the
     # host cores; the other ranks have exited by then and left the cores to it), so the N > 1 line carries cpu_baseline next to roofline too.
@@ -785,7 +864,7 @@ def main():
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
     if rank == 0:
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(args.every_n, args.cpu_videos, args.cpu_budget, args.cpu_threads)
             if n_gpus > 1:
                 res["cpu_baseline"]["sample"] += "; timed on rank 0 after destroy_process_group() (the other ranks have exited)"

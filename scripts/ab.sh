@@ -7,7 +7,7 @@ mkdir -p gpurun_out; : > $OUT
 for round in $(seq 1 ${ROUNDS:-2}); do
   for spec in "$@"; do
     label=${spec%%:*}; envs=${spec#*:}
-    line=$(env $(echo $envs | tr ',' ' ') X_=1 timeout 300 python bench.py --no_secondary --no_cpu_baseline --steps ${STEPS:-20} --warmup 3 ${BENCH_ARGS:-} 2>/dev/null | tail -1)
+    line=$(env $(echo $envs | tr ',' ' ') X_=1 timeout 300 python bench.py --full --no_secondary --no_cpu_baseline --steps ${STEPS:-20} --warmup 3 ${BENCH_ARGS:-} 2>/dev/null | tail -1)
     python - "$label" "$line" >> $OUT <<'PY'
 import json, sys
 label, line = sys.argv[1], sys.argv[2]

@@ -4,8 +4,8 @@
 set -u
 O=gpurun_out/r03
 mkdir -p $O
-timeout 900 python bench.py > $O/bench_final.json 2> $O/bench_final.err
-timeout 300 python bench.py --config dbof --no_cpu_baseline > $O/bench_dbof.json 2> /dev/null
+timeout 900 python bench.py --full > $O/bench_final.json 2> $O/bench_final.err
+timeout 300 python bench.py --full --config dbof --no_cpu_baseline > $O/bench_dbof.json 2> /dev/null
 bash scripts/prof.sh r03/prof_default --no_cpu_baseline --no_secondary > $O/digest_default.txt 2>&1
 bash scripts/prof.sh r03/prof_no_overlap --no_cpu_baseline --no_secondary --no_overlap > $O/digest_no_overlap.txt 2>&1
 bash scripts/prof.sh r03/prof_high_no_overlap --no_cpu_baseline --no_secondary --no_overlap --precision high > $O/digest_high_no_overlap.txt 2>&1

@@ -5,8 +5,8 @@
 set -u
 O=gpurun_out/r04
 mkdir -p $O
-timeout 900 python bench.py > $O/bench_final.json 2> $O/bench_final.err
-timeout 300 python bench.py --config dbof --no_cpu_baseline > $O/bench_dbof.json 2> /dev/null
+timeout 900 python bench.py --full > $O/bench_final.json 2> $O/bench_final.err
+timeout 300 python bench.py --full --config dbof --no_cpu_baseline > $O/bench_dbof.json 2> /dev/null
 prof() {   # name, bench args / env through the caller
   local name=$1; shift
   bash scripts/prof.sh r04/prof_$name --no_cpu_baseline --no_secondary "$@" > $O/digest_$name.txt 2>&1
@@ -29,7 +29,7 @@ python scripts/pmc_kernels.py $O/pmc_high $O/pmc_kernels_high.json "lstm_fwd_ste
 bash scripts/pmc_collect.sh $O/pmc_dbof --config dbof --steps 3 --warmup 2 --no_cpu_baseline > /dev/null 2>&1
 python scripts/pmc_kernels.py $O/pmc_dbof $O/pmc_kernels_dbof.json > /dev/null 2>&1
 STEPS=10 bash scripts/rccl_one_rank.sh $O/rccl_one_rank.txt > /dev/null 2>&1
-for v in 0 1; do EVC_DETERMINISTIC=$v python bench.py --no_secondary --no_cpu_baseline --steps 20 2>/dev/null | python -c "import json,sys; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('EVC_DETERMINISTIC=$v bf16 %.3f ms/step' % r['ms_per_step'], r['losses'])"; done > $O/deterministic_cost.txt 2>&1
+for v in 0 1; do EVC_DETERMINISTIC=$v python bench.py --full --no_secondary --no_cpu_baseline --steps 20 2>/dev/null | python -c "import json,sys; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('EVC_DETERMINISTIC=$v bf16 %.3f ms/step' % r['ms_per_step'], r['losses'])"; done > $O/deterministic_cost.txt 2>&1
 # keep the merged output small: the raw traces and counter dumps stay on the box
 rm -rf $O/pmc/*/ $O/pmc_dbof/*/ $O/pmc_high/*/ 2>/dev/null
 find $O -name "run_kernel_trace.csv" -delete

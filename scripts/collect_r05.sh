@@ -5,9 +5,9 @@
 set -u
 O=gpurun_out/r05
 mkdir -p $O
-timeout 900 python bench.py > $O/bench_final.json 2> $O/bench_final.err
-timeout 300 python bench.py --config dbof --no_cpu_baseline > $O/bench_dbof.json 2> /dev/null
-timeout 300 python bench.py --config dbof --no_cpu_baseline --precision high > $O/bench_dbof_high.json 2> /dev/null
+timeout 900 python bench.py --full > $O/bench_final.json 2> $O/bench_final.err
+timeout 300 python bench.py --full --config dbof --no_cpu_baseline > $O/bench_dbof.json 2> /dev/null
+timeout 300 python bench.py --full --config dbof --no_cpu_baseline --precision high > $O/bench_dbof_high.json 2> /dev/null
 prof() {   # name, bench args / env through the caller
   local name=$1; shift
   bash scripts/prof.sh r05/prof_$name --no_cpu_baseline --no_secondary "$@" > $O/digest_$name.txt 2>&1

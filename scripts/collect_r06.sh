@@ -5,10 +5,10 @@
 set -u
 O=gpurun_out/r06f
 mkdir -p $O
-timeout 1200 python bench.py > $O/bench_final.json 2> $O/bench_final.err
-timeout 300 python bench.py --config dbof --no_cpu_baseline > $O/bench_dbof.json 2> /dev/null
-timeout 300 python bench.py --input uint8 --no_cpu_baseline --no_secondary --steps 20 > $O/bench_uint8_bf16.json 2> /dev/null
-timeout 300 python bench.py --input uint8 --precision high --no_cpu_baseline --no_secondary --steps 20 > $O/bench_uint8_high.json 2> /dev/null
+timeout 1200 python bench.py --full > $O/bench_final.json 2> $O/bench_final.err
+timeout 300 python bench.py --full --config dbof --no_cpu_baseline > $O/bench_dbof.json 2> /dev/null
+timeout 300 python bench.py --full --input uint8 --no_cpu_baseline --no_secondary --steps 20 > $O/bench_uint8_bf16.json 2> /dev/null
+timeout 300 python bench.py --full --input uint8 --precision high --no_cpu_baseline --no_secondary --steps 20 > $O/bench_uint8_high.json 2> /dev/null
 prof() {   # name, bench args / env through the caller
   local name=$1; shift
   bash scripts/prof.sh r06f/prof_$name --no_cpu_baseline --no_secondary "$@" > $O/digest_$name.txt 2>&1

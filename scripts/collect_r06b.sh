@@ -14,8 +14,8 @@ EVC_HIGH_DITHER_LAYERS= timeout 600 python scripts/long_horizon.py eval $O/long 
 EVC_HIGH_DITHER_LAYERS= EVC_HIGH_STUDENT_LIGHT=0 timeout 600 python scripts/long_horizon.py eval $O/long high > $O/long_eval_no_dither_student_full.txt 2>&1
 rm -f $O/long/*.pt
 for i in 1 2; do
-  timeout 300 python bench.py --mode student --every_n 30 --batch 1024 --no_cpu_baseline --no_secondary --steps 20 > $O/cfg5_default_$i.json 2> /dev/null
-  EVC_HOIST_BELOW=1025 timeout 300 python bench.py --mode student --every_n 30 --batch 1024 --no_cpu_baseline --no_secondary --steps 20 > $O/cfg5_hoist_$i.json 2> /dev/null
+  timeout 300 python bench.py --full --mode student --every_n 30 --batch 1024 --no_cpu_baseline --no_secondary --steps 20 > $O/cfg5_default_$i.json 2> /dev/null
+  EVC_HOIST_BELOW=1025 timeout 300 python bench.py --full --mode student --every_n 30 --batch 1024 --no_cpu_baseline --no_secondary --steps 20 > $O/cfg5_hoist_$i.json 2> /dev/null
 done
 tail -3 $O/pytest_kernels.txt $O/pytest_cfg.txt
 grep -h "high\|steps" $O/long_eval_*.txt | cut -c1-260

@@ -16,10 +16,10 @@ rm -rf $D
 bash scripts/dp_sim_world.sh $O/dp_sim_world.txt > /dev/null 2>&1
 for i in 1 2; do
   for v in 0 1; do
-    EVC_OPT_SPARE_STREAM=$v timeout 300 python bench.py --mode student --every_n 30 --batch 1024 --no_cpu_baseline --no_secondary --steps 20 2>/dev/null | python3 -c "
+    EVC_OPT_SPARE_STREAM=$v timeout 300 python bench.py --full --mode student --every_n 30 --batch 1024 --no_cpu_baseline --no_secondary --steps 20 2>/dev/null | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); print('cfg5 single GPU, EVC_OPT_SPARE_STREAM=$v: %.3f ms/step (median %.3f)' % (d['ms_per_step'], d['ms_per_step_median']))" >> $O/cfg5_spare_ab.txt
-    EVC_OPT_SPARE_STREAM=$v timeout 300 python bench.py --mode teacher --no_cpu_baseline --no_secondary --steps 20 2>/dev/null | python3 -c "
+    EVC_OPT_SPARE_STREAM=$v timeout 300 python bench.py --full --mode teacher --no_cpu_baseline --no_secondary --steps 20 2>/dev/null | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); print('cfg2 single GPU, EVC_OPT_SPARE_STREAM=$v: %.3f ms/step (median %.3f)' % (d['ms_per_step'], d['ms_per_step_median']))" >> $O/cfg5_spare_ab.txt
   done

@@ -16,9 +16,9 @@ for seed in 5 7 8 3 4 6; do
 done
 rm -rf $D
 for i in 1 2; do
-  timeout 300 python bench.py --precision high --no_cpu_baseline --no_secondary --steps 20 > $O/high_actlo_$i.json 2> /dev/null
-  EVC_HIGH_ACT_LO=0 timeout 300 python bench.py --precision high --no_cpu_baseline --no_secondary --steps 20 > $O/high_noactlo_$i.json 2> /dev/null
-  timeout 300 python bench.py --no_cpu_baseline --no_secondary --steps 20 > $O/bf16_$i.json 2> /dev/null
+  timeout 300 python bench.py --full --precision high --no_cpu_baseline --no_secondary --steps 20 > $O/high_actlo_$i.json 2> /dev/null
+  EVC_HIGH_ACT_LO=0 timeout 300 python bench.py --full --precision high --no_cpu_baseline --no_secondary --steps 20 > $O/high_noactlo_$i.json 2> /dev/null
+  timeout 300 python bench.py --full --no_cpu_baseline --no_secondary --steps 20 > $O/bf16_$i.json 2> /dev/null
 done
 tail -4 $O/pytest_kernels.txt; tail -4 $O/pytest_step.txt
 cat $O/long_draws.txt | cut -c1-230

@@ -15,10 +15,10 @@ for seed in 5 7 8 3 4 6; do
 done
 rm -rf $D
 for i in 1 2; do
-  timeout 300 python bench.py --input uint8 --precision high --no_cpu_baseline --no_secondary --steps 20 > $O/u8_high_int_$i.json 2> /dev/null
-  EVC_HIGH_X_INT=0 timeout 300 python bench.py --input uint8 --precision high --no_cpu_baseline --no_secondary --steps 20 > $O/u8_high_noint_$i.json 2> /dev/null
-  timeout 300 python bench.py --input uint8 --no_cpu_baseline --no_secondary --steps 20 > $O/u8_bf16_$i.json 2> /dev/null
-  timeout 300 python bench.py --precision high --no_cpu_baseline --no_secondary --steps 20 > $O/f32_high_$i.json 2> /dev/null
+  timeout 300 python bench.py --full --input uint8 --precision high --no_cpu_baseline --no_secondary --steps 20 > $O/u8_high_int_$i.json 2> /dev/null
+  EVC_HIGH_X_INT=0 timeout 300 python bench.py --full --input uint8 --precision high --no_cpu_baseline --no_secondary --steps 20 > $O/u8_high_noint_$i.json 2> /dev/null
+  timeout 300 python bench.py --full --input uint8 --no_cpu_baseline --no_secondary --steps 20 > $O/u8_bf16_$i.json 2> /dev/null
+  timeout 300 python bench.py --full --precision high --no_cpu_baseline --no_secondary --steps 20 > $O/f32_high_$i.json 2> /dev/null
 done
 tail -4 $O/pytest_kernels.txt; tail -4 $O/pytest_step.txt
 cat $O/long_draws.txt | cut -c1-230

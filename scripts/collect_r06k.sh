@@ -4,9 +4,9 @@
 set -u
 O=gpurun_out/r06k
 mkdir -p $O
-timeout 1200 python bench.py > $O/bench_final.json 2> $O/bench_final.err
-timeout 300 python bench.py --input uint8 --no_cpu_baseline --no_secondary --steps 20 > $O/bench_uint8_bf16.json 2> /dev/null
-timeout 300 python bench.py --input uint8 --precision high --no_cpu_baseline --no_secondary --steps 20 > $O/bench_uint8_high.json 2> /dev/null
+timeout 1200 python bench.py --full > $O/bench_final.json 2> $O/bench_final.err
+timeout 300 python bench.py --full --input uint8 --no_cpu_baseline --no_secondary --steps 20 > $O/bench_uint8_bf16.json 2> /dev/null
+timeout 300 python bench.py --full --input uint8 --precision high --no_cpu_baseline --no_secondary --steps 20 > $O/bench_uint8_high.json 2> /dev/null
 C5="--mode student --every_n 30 --batch 1024"
 bash scripts/pmc_collect.sh $O/pmc_cfg5 --steps 3 --warmup 2 --no_cpu_baseline --no_secondary $C5 > /dev/null 2>&1
 python scripts/pmc_kernels.py $O/pmc_cfg5 $O/pmc_kernels_cfg5.json "gemm_tn 256x256 (cfg 5: weight gradients of the student's L1 / L2 levels)=gemm_tn_kernel<TileCfg2<256" \

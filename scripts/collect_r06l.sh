@@ -8,7 +8,7 @@ timeout 900 python -m pytest tests/test_gpu_kernels.py -x -q -k "clip_norm_from_
 timeout 900 python -m pytest tests/test_gpu_configs.py tests/test_gpu_step.py -x -q -k "cfg5 or small_step or three_iterations or fused_moe" > $O/pytest_cfg.txt 2>&1
 for i in 1 2 3; do
   for v in 1 0; do
-    EVC_FUSED_GRAD_NORM=$v timeout 300 python bench.py --mode student --every_n 30 --batch 1024 --no_cpu_baseline --no_secondary --steps 20 2>/dev/null | python3 -c "
+    EVC_FUSED_GRAD_NORM=$v timeout 300 python bench.py --full --mode student --every_n 30 --batch 1024 --no_cpu_baseline --no_secondary --steps 20 2>/dev/null | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); print('cfg5 EVC_FUSED_GRAD_NORM=$v: %.3f ms/step (median %.3f) losses %s' % (d['ms_per_step'], d['ms_per_step_median'], d['losses']))" >> $O/cfg5_fused_norm_ab.txt
   done

@@ -10,7 +10,7 @@ tail -3 $O/pytest_step.txt
 for i in 1 2 3; do
   for v in 1 0; do
     for inp in uint8 f32; do
-      EVC_FWD_WALK2_HIGH=$v timeout 300 python bench.py --precision high --input $inp --no_cpu_baseline --no_secondary --steps 20 2>/dev/null | python3 -c "
+      EVC_FWD_WALK2_HIGH=$v timeout 300 python bench.py --full --precision high --input $inp --no_cpu_baseline --no_secondary --steps 20 2>/dev/null | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); print('high $inp EVC_FWD_WALK2_HIGH=$v: %.3f ms/step (median %.3f) fwd_step %s' % (d['ms_per_step'], d['ms_per_step_median'], json.dumps(d.get('rooflines', {}).get('fwd_step', {}))[:160]))" >> $O/walk2_high_ab.txt
     done

@@ -22,7 +22,7 @@ done
 echo "== cfg 4 training step (bench.py --config dbof --steps 30), alternating" >> "$OUT"
 for round in 1 2 3; do
   for pin in cols rows; do
-    EVC_DBOF_PIN=$pin timeout 300 python3 bench.py --config dbof --no_cpu_baseline --steps 30 --warmup 6 2>/dev/null | python3 -c "
+    EVC_DBOF_PIN=$pin timeout 300 python3 bench.py --full --config dbof --no_cpu_baseline --steps 30 --warmup 6 2>/dev/null | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('pin %-5s %.3f ms/step (median %.3f)  cluster kernel %.1f us = %.3f of peak' % ('$pin', d['ms_per_step'], d['ms_per_step_median'], d['roofline']['avg_launch_ms'] * 1e3, d['roofline']['frac']))" >> "$OUT"

@@ -10,7 +10,7 @@ for round in 1 2; do
   for v in shipped 1_0 8_1 16_1; do
     lib=$PWD/build_ab/libevc_dact_$v.so; [ $v = shipped ] && lib=$PWD/efficientvideoclassification_youtube8m_amd/libevc_hip.so
     k=$(EVC_LIB=$lib timeout 200 python3 scripts/dbof_bench.py dact 2>/dev/null | head -1 | cut -c1-70)
-    s=$(EVC_LIB=$lib timeout 300 python3 bench.py --config dbof --no_cpu_baseline --steps 30 --warmup 6 2>/dev/null | python3 -c "
+    s=$(EVC_LIB=$lib timeout 300 python3 bench.py --full --config dbof --no_cpu_baseline --steps 30 --warmup 6 2>/dev/null | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); print('step %.3f ms (median %.3f)' % (d['ms_per_step'], d['ms_per_step_median']))")
     echo "rows_nt $v (round $round): $k | $s" >> "$OUT"

@@ -16,7 +16,7 @@ run() {   # label, env...
   local label=$1; shift
   PORT=$((PORT + 1))
   env "$@" python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port $PORT \
-      bench.py --gpus 1 --steps ${STEPS:-10} --warmup 3 --no_cpu_baseline --no_secondary 2>/dev/null | python3 -c "
+      bench.py --gpus 1 --full --steps ${STEPS:-10} --warmup 3 --no_cpu_baseline --no_secondary 2>/dev/null | python3 -c "
 import json, sys
 for l in sys.stdin:
     if l.startswith('{'):
@@ -24,7 +24,7 @@ for l in sys.stdin:
         print('%-64s %7.2f ms/step  wire %6.0f MB  collective events %6.2f ms  fwd step %5.1f us' % ('$label', d['ms_per_step'],
               dp.get('wire_mb_per_rank_per_step', 0), dp.get('collective_event_ms_per_step', 0), d['roofline']['avg_launch_ms'] * 1e3))" | tee -a "$OUT"
 }
-python3 bench.py --no_cpu_baseline --no_secondary --steps ${STEPS:-10} --warmup 3 2>/dev/null | python3 -c "
+python3 bench.py --full --no_cpu_baseline --no_secondary --steps ${STEPS:-10} --warmup 3 2>/dev/null | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read()); print('%-64s %7.2f ms/step' % ('no process group (plain single-GPU step)', d['ms_per_step']))" | tee -a "$OUT"
 run "one-rank RCCL, no stand-in" EVC_DP_FORCE=1

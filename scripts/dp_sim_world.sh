@@ -24,7 +24,7 @@ for l in sys.stdin:
               dp.get("wire_mb_per_rank_per_step", 0), kinds, d["roofline"]["avg_launch_ms"] * 1e3))'
 plain() {   # label, bench args...
   local label=$1; shift
-  python3 bench.py --no_cpu_baseline --no_secondary --steps ${STEPS:-12} --warmup 3 "$@" 2>/dev/null | python3 -c "$show" "$label" | tee -a "$OUT"
+  python3 bench.py --full --no_cpu_baseline --no_secondary --steps ${STEPS:-12} --warmup 3 "$@" 2>/dev/null | python3 -c "$show" "$label" | tee -a "$OUT"
 }
 run() {   # label, "ENV=..." assignments ..., -- , bench args...
   local label=$1; shift
@@ -33,7 +33,7 @@ run() {   # label, "ENV=..." assignments ..., -- , bench args...
   [ $# -gt 0 ] && shift
   PORT=$((PORT + 1))
   env EVC_DP_FORCE=1 "${envs[@]}" python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port $PORT \
-      bench.py --gpus 1 --steps ${STEPS:-12} --warmup 3 --no_cpu_baseline --no_secondary "$@" 2>/dev/null | python3 -c "$show" "$label" | tee -a "$OUT"
+      bench.py --gpus 1 --full --steps ${STEPS:-12} --warmup 3 --no_cpu_baseline --no_secondary "$@" 2>/dev/null | python3 -c "$show" "$label" | tee -a "$OUT"
 }
 echo "== BASELINE cfg 3 (teacher + student, B = 256 per rank)" | tee -a "$OUT"
 plain "no process group (plain single-GPU step)"

@@ -10,10 +10,10 @@ shift || true
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p "$OUT"
 ARGS="${*:---steps 2 --warmup 1 --no_cpu_baseline --no_secondary}"
-echo "python3 bench.py $ARGS" > "$OUT/command.txt"
+echo "python3 bench.py --full $ARGS" > "$OUT/command.txt"
 pass() {   # name, counters...
   local name=$1; shift
-  timeout 600 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d "$OUT/$name" -o run -- python3 bench.py $ARGS > "$OUT/$name.log" 2>&1
+  timeout 600 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d "$OUT/$name" -o run -- python3 bench.py --full $ARGS > "$OUT/$name.log" 2>&1
 }
 pass fetch FETCH_SIZE
 pass write WRITE_SIZE

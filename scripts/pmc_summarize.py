@@ -47,7 +47,7 @@ fetch_kb, write_kb = avg(fetch, "FETCH_SIZE"), avg(write, "WRITE_SIZE")
 busy, gui = avg(mfma, "SQ_VALU_MFMA_BUSY_CYCLES"), avg(mfma, "GRBM_GUI_ACTIVE")
 res = {
     "source": "rocprofv3 --pmc passes (FETCH_SIZE | WRITE_SIZE | SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE; each with "
-              "--kernel-trace only) of `python3 bench.py --steps 2 --warmup 1 --no_cpu_baseline` on MI355X (scripts/pmc_collect.sh)",
+              "--kernel-trace only) of `python3 bench.py --full --steps 2 --warmup 1 --no_cpu_baseline` on MI355X (scripts/pmc_collect.sh)",
     "kernel": ("lstm_fwd_walk2_kernel<TileCfg3<BM,4,64,2,4,2>> (two tiles per workgroup and launch: layer 0's step s + layer 1's step s-1; bytes and cycles are per LAUNCH = "
                "two step tiles) - the ring tile heights the row plans select, launches per variant: " if IS_WALK else
                "lstm_fwd_step_kernel<TileCfg3<BM,4,64,2,4,2>> (TileCfg2 for 288/320 rows) - the ring tile heights the row plans select, launches per variant: ")

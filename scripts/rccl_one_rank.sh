@@ -27,7 +27,7 @@ for l in sys.stdin:
         print('LOSSES ' + json.dumps(d['losses'], sort_keys=True))
 sys.exit(0 if seen == 1 else 3)" | tee -a "$OUT"      # a crashed run prints no JSON line: fail here (pipefail), not silently
 }
-ARGS="bench.py --gpus 1 --steps ${STEPS:-10} --warmup 3 --no_cpu_baseline --no_secondary"
+ARGS="bench.py --full --gpus 1 --steps ${STEPS:-10} --warmup 3 --no_cpu_baseline --no_secondary"
 run "one-rank RCCL, collectives in stream order, student on its own communicator (default)" EVC_DP_FORCE=1 \
     python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 $ARGS
 run "one-rank RCCL, EVC_DP_SERIAL_COMM=1 (one communicator, one collective at a time)" EVC_DP_FORCE=1 EVC_DP_SERIAL_COMM=1 \

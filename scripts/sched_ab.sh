@@ -8,7 +8,7 @@ mkdir -p gpurun_out
 run() {   # label, env...
   local label=$1; shift
   local line
-  line=$(env "$@" timeout 300 python bench.py --no_secondary --no_cpu_baseline --steps 20 --warmup 3 ${BENCH_ARGS:-} 2>/dev/null | tail -1)
+  line=$(env "$@" timeout 300 python bench.py --full --no_secondary --no_cpu_baseline --steps 20 --warmup 3 ${BENCH_ARGS:-} 2>/dev/null | tail -1)
   python - "$label" "$line" >> $OUT <<'PY'
 import json, sys
 label, line = sys.argv[1], sys.argv[2]

@@ -432,6 +432,44 @@ def test_bench_figures_flag_a_stall_in_the_timed_window():
     assert len(runs) == 1 and "retimed_after_stall" not in r
 
 
+def test_bench_dump_outputs_writes_float_arrays_and_a_fixed_sample(tmp_path):
+    """--dump-outputs: every output of the step as <name>.npy in float32 (float64 for float64 / integer outputs), an array of more
+    than DUMP_MAX_ELEMS elements as the same seeded sample in every run, the whole dump within DUMP_MAX_BYTES."""
+    bench = _load_bench()
+
+    class Store:
+        master = torch.arange(4 * bench.DUMP_MAX_ELEMS, dtype=torch.float32)
+
+    class Tower:
+        store = Store()
+
+    g = torch.Generator().manual_seed(3)
+    out = {"predictions": torch.rand((4, 7), generator=g), "state_bf16": torch.rand((4, 3), generator=g).to(torch.bfloat16),
+           "loss": torch.tensor(0.25, dtype=torch.float64), "num_frames": torch.tensor([3, 5, 7, 9], dtype=torch.int32), "global_step": 12,
+           "note": "not an array"}
+    arrays = bench.step_outputs(out, (("teacher", Tower()), ("student", None)))
+    assert set(arrays) == {"predictions", "state_bf16", "loss", "num_frames", "global_step", "teacher_weights"}
+    what = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(k + ".npy" for k in arrays) and set(what) == set(arrays)
+    p = np.load(tmp_path / "a" / "predictions.npy")
+    assert p.dtype == np.float32 and np.array_equal(p, out["predictions"].numpy())
+    assert np.load(tmp_path / "a" / "state_bf16.npy").dtype == np.float32
+    assert np.load(tmp_path / "a" / "loss.npy").dtype == np.float64
+    assert np.load(tmp_path / "a" / "num_frames.npy").tolist() == [3.0, 5.0, 7.0, 9.0]
+    assert float(np.load(tmp_path / "a" / "global_step.npy")) == 12.0
+    w = np.load(tmp_path / "a" / "teacher_weights.npy")
+    assert 0.8 * bench.DUMP_MAX_ELEMS < w.size <= bench.DUMP_MAX_ELEMS and w.dtype == np.float32 and what["teacher_weights"].startswith("sample")
+    assert np.all(np.diff(w) > 0) and w.max() < Store.master.numel()        # sorted distinct elements of the flat buffer
+    assert np.array_equal(w, np.load(tmp_path / "b" / "teacher_weights.npy"))
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in files)
+    assert total <= bench.DUMP_MAX_BYTES
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                       text=True, timeout=300)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+
+
 def test_bench_gpus_flag_means_n(tmp_path):
     """`--gpus N` is the number of ranks in the line: under a launcher it must equal WORLD_SIZE (exit 2 with the reason otherwise);
     without one, N > 1 makes bench.py start N rank processes itself - fresh children with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*

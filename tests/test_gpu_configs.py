@@ -399,3 +399,46 @@ def test_cfg4_dbof_train_main_on_tfrecords(tmp_path):
     print("cfg4 through train.main: loss %.4f vs oracle %.4f, pred err %.2e" % (res["history"][0][1]["loss"], want, err))
     assert abs(res["history"][0][1]["loss"] - want) < 2e-3 * want
     assert err < 5e-3                               # bf16 operands on O(1) batch-normalised activations
+
+
+def test_bench_plain_run_times_the_headline_and_dumps_its_outputs(tmp_path):
+    """A plain bench.py run times exactly --steps steps of the headline and nothing else (no roofline, secondary configurations or
+    CPU leg: those are --full's); --dump-outputs writes the last timed step's outputs as finite float arrays within 64 MB, and a second
+    run with the same arguments writes the same bits (no floating-point atomics on the timed path)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k != "EVC_DETERMINISTIC"}
+    lines = []
+    for run in ("out", "again"):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "16", "--pool", "2",
+               "--dump-outputs", str(tmp_path / run)]
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, cwd=root, env=env)
+        assert r.returncode == 0, r.stderr.decode()[-3000:]
+        lines += [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
+    assert len(lines) == 2
+    d = json.loads(lines[0])
+    assert d["schedule"]["deterministic"] is True        # (--dump-outputs selects the path without floating-point atomics)
+    r = subprocess.run(cmd[:-2], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, cwd=root, env=env)
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    plain = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1])
+    assert plain["schedule"]["deterministic"] is False and "dumped_outputs" not in plain     # a plain run times the atomic joins
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["unit"] == "frames/sec" and d["higher_is_better"] is True and d["dtype"] == "bf16"
+    assert abs(d["value"] - 16 * 300 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    assert d["roofline"] is None and not any(k in d for k in ("cpu_baseline", "precision_modes", "other_configs"))
+    files = sorted(os.listdir(tmp_path / "out"))
+    assert set(files) == {k + ".npy" for k in d["dumped_outputs"]}
+    for k in ("predictions", "student_predictions", "teacher_weights", "student_weights"):
+        assert k + ".npy" in files
+    assert sum(os.path.getsize(tmp_path / "out" / f) for f in files) <= 64 << 20
+    for f in files:
+        a = np.load(tmp_path / "out" / f)
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), f
+        b = np.load(tmp_path / "again" / f)
+        if f == "pred_loss.npy":            # (the one scalar that still sums with atomics: one per video row)
+            assert np.allclose(a, b, rtol=1e-5, atol=0), (a, b)
+        else:
+            assert np.array_equal(a, b), f
+    assert np.load(tmp_path / "out" / "predictions.npy").shape == (16, 4716)

@@ -217,7 +217,7 @@ def test_bench_multi_rank_path_runs(tmp_path):
     env = dict(os.environ, EVC_BENCH_SHARED_GPU="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29631", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--batch", "16", "--pool", "2", "--cpu_videos", "2", "--cpu_budget", "8"]
+           "--batch", "16", "--pool", "2", "--cpu_videos", "2", "--cpu_budget", "8", "--full"]
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
