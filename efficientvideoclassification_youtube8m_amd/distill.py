@@ -735,12 +735,18 @@ class EvalGraph:
     """Forward-only graph of cs/validate.py:109-189 (teacher built too, so that the
     student_state_loss ||teacher_state - student_state||^2 can be logged) and of
     cs/eval_finetune.py:108-175 (``student_only``).  Towers are built with
-    training=False (no backward tape); ``restore`` takes a TF-named state dict."""
+    training=False (no backward tape); ``restore`` takes a TF-named state dict.
+    ``teacher_only``: the teacher alone (no student allocated) - the forward the inference binary serves from a
+    train.py checkpoint (cs/train.py:338 puts the teacher's predictions in "predictions"); step() then returns
+    predictions / teacher_state / teacher_predictions and computes no loss."""
 
     def __init__(self, batch_size, every_n=10, student_only=False, feature_size=1152, vocab_size=4716, max_frames=300,
                  num_inputs_to_lstm=20, num_inputs_l1_student=5, lstm_cells=1024, lstm_layers=2, num_mixtures=2,
-                 device="cuda:0", precision="bf16"):
-        validate_every_n(every_n, num_inputs_l1_student, max_frames)
+                 device="cuda:0", precision="bf16", teacher_only=False):
+        if student_only and teacher_only:
+            raise ValueError("EvalGraph: student_only and teacher_only exclude each other")
+        if not teacher_only:
+            validate_every_n(every_n, num_inputs_l1_student, max_frames)
         self.every_n, self.max_frames, self.C1, self.C2 = every_n, max_frames, num_inputs_to_lstm, num_inputs_l1_student
         self.S = max_frames // every_n
         self.device = torch.device(device)
@@ -748,8 +754,10 @@ class EvalGraph:
         if not student_only:
             self.teacher = HLstmTower(batch_size, max_frames, num_inputs_to_lstm, feature_size, vocab_size, lstm_cells,
                                       lstm_layers, num_mixtures, device, False, "model", 7)
-        self.student = HLstmTower(batch_size, self.S, num_inputs_l1_student, feature_size, vocab_size, lstm_cells,
-                                  lstm_layers, num_mixtures, device, False, "model_student", 8)
+        self.student = None
+        if not teacher_only:
+            self.student = HLstmTower(batch_size, self.S, num_inputs_l1_student, feature_size, vocab_size, lstm_cells,
+                                      lstm_layers, num_mixtures, device, False, "model_student", 8)
         self.precision = precision
         student_light(self.student, precision)
         if precision != "bf16":
@@ -783,6 +791,8 @@ class EvalGraph:
     def _step(self, x_raw, labels_u8, num_frames, nh):
         """Returns predictions (student), student_label_loss, student_state_loss (teacher_student only) - the
         tensors cs/validate.py:240 fetches.  The two towers are independent: they run on two streams."""
+        if self.student is None:
+            return self._step_teacher(x_raw, num_frames, nh)
         main = torch.cuda.current_stream(self.device)
         split = self.student.input_split()
         u8 = x_raw.dtype == torch.uint8
@@ -813,6 +823,14 @@ class EvalGraph:
         out.update(predictions=s_pred, student_state=s_state, num_frames=n_s, student_label_loss=self.losses[0],
                    loss=self.losses[0])
         return out
+
+    def _step_teacher(self, x_raw, num_frames, nh):
+        """teacher_only: the teacher's forward alone (same input views, row plans and precision handling as _step)."""
+        tp, _ = frame_counts_and_plans(self, num_frames, nh, True, False)
+        xt, _ = input_views(self, x_raw, num_frames, tp, None, False)
+        l1, l2, plan_t = tp
+        t_state, t_pred = self.teacher.forward(xt, l1, l2, plan_t)
+        return dict(predictions=t_pred, teacher_state=t_state, teacher_predictions=t_pred)
 
 
 class SingleTowerGraph:

@@ -75,6 +75,9 @@ _define("num_hidden_units", 1024, int)
 _define("eval_data_pattern", "", str)
 _define("run_once", False, _bool)
 _define("top_k", 20, int)
+# ---- cs/inference_ensemble.py:28-61 (inference binary; train_dir, top_k and the model / input flags as above) -------------
+_define("output_file", "", str, "the file to save the predictions to")
+_define("input_data_pattern", "", str, "glob of the tf.SequenceExample records to predict (labels not needed)")
 # ---- additions of this build (not in the reference) --------------------------------
 _define("max_steps", 0, int, "stop after this many iterations (0 = until the data ends)")
 _define("synthetic_videos", 2048, int, "videos per epoch when train_data_pattern is synthetic")

@@ -582,6 +582,24 @@ def lstm_stack2_bwd(w_il0, w_il1, lens, T, M, Kin0, H, gates, c_all, dS, dc_ws, 
               *_plan_args(plan), _stream())
 
 
+TOPK_MAX_K = 256         # evc_topk_rows: 1 <= k <= min(cols, 256), cols <= 32768
+
+
+def topk_rows(x, k):
+    """Per-row top-k of a 2-D f32 tensor (rows contiguous, any row stride) on the current stream (evc_topk_rows): (values [B, k] f32,
+    indices [B, k] int32), value descending and column ascending - -0 ties with +0, NaN above +inf, ties at the k-th place admit the
+    lowest columns; the values are the input's own bits.  The selection of the inference binary (cs/inference_ensemble.py:63-74)."""
+    if x.dtype != F32 or x.dim() != 2 or (x.shape[0] > 0 and x.shape[1] > 1 and x.stride(1) != 1):
+        raise _lib.EvcError("topk_rows: needs a 2-D float32 tensor with contiguous rows (got %s %s)" % (x.dtype, tuple(x.shape)))
+    B, cols = x.shape
+    kk = max(int(k), 0)
+    values = torch.empty((B, kk), dtype=F32, device=x.device)
+    indices = torch.empty((B, kk), dtype=torch.int32, device=x.device)
+    ld = x.stride(0) if B > 1 else cols
+    _lib.call("evc_topk_rows", _p(x), ld, B, cols, int(k), _p(values), _p(indices), _stream())
+    return values, indices
+
+
 # ---------------------------------------------------------------------------
 def moe_tail_fwd(gate_logits, expert_logits, B, V, M, pred, rowsum):
     _lib.call("evc_moe_tail_fwd", _p(gate_logits), _p(expert_logits), B, V, M, _p(pred), _p(rowsum), _stream())
