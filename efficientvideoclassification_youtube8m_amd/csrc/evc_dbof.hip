@@ -299,10 +299,8 @@ extern "C" int evc_dbof_input_bn_apply_f16fp8(const float* r, int B, int S, int 
 // ---------------------------------------------------------------------------------------------------------------
 // K4: the cluster GEMM with the statistics / max-pool epilogue
 // ---------------------------------------------------------------------------------------------------------------
-#ifndef EVC_DBOF_ACT_POLICY
-#define EVC_DBOF_ACT_POLICY 2     // the 268 MB bf16 tape as non-temporal stores (round 6; profiles/r06_dbof_act_policy_ab.txt, same box, alternating: the cluster kernel
-                                   // in the cfg-4 step 317 -> 300 us, the step 1.70 -> 1.67 ms; sc1 write-through: no change; 0 = plain stores)
-#endif
+constexpr int DBOF_ACT_POLICY = 2;    // the 268 MB bf16 tape as non-temporal stores (round 6; profiles/r06_dbof_act_policy_ab.txt, same box, alternating: the cluster kernel
+                                      // in the cfg-4 step 317 -> 300 us, the step 1.70 -> 1.67 ms; sc1 write-through: no change)
 struct DbofPoolParams {
   bf16_t* act; long ld_act;        // [Mp][C] bf16 (training tape) or null
   float* part;                     // [2 * tiles_m][2][C] column partial sums or null (evaluation: moving statistics)
@@ -312,13 +310,10 @@ struct DbofPoolParams {
   int B, S, C;
 };
 
-#ifdef EVC_DBOF_V2_LOOP
-typedef TileCfg2<256, 1, 256, 2, 4, 5, true> CfgDbof;      // 256 frame rows (8 videos) x 256 clusters, 8 waves (2 x 4)
-#else
-struct CfgDbof : TileCfg3<256, 1, 256, 2, 4, 2> {};        // the same tile on two 64-wide K stages (gemm_core_v3.h: 128 KB = the epilogue's eight 16 KB transpose slices)
+// 256 frame rows (8 videos) x 256 clusters, 8 waves (2 x 4), two 64-wide K stages (gemm_core_v3.h: 128 KB = the epilogue's eight 16 KB transpose slices)
+struct CfgDbof : TileCfg3<256, 1, 256, 2, 4, 2> {};
 template <> struct is_v2<CfgDbof> { static constexpr bool value = true; };
 template <> struct is_v3<CfgDbof> { static constexpr bool value = true; };
-#endif
 
 template <class Cfg, bool INIT, int EXTRA = 0>
 __device__ __forceinline__ void dbof_mainloop(const GemmOperands& p, int m0, int u0, f32x4 (&acc)[Cfg::MI][1][Cfg::NI]) {
@@ -339,17 +334,6 @@ __device__ __forceinline__ void dbof_tile_epilogue(const GemmOperands& p, const 
   const int rbase = m0 + wr * Cfg::WM;                         // first row of this wave: a multiple of 128 = 4 videos
   const int b = (rbase >> 5) + (l >> 2);                       // this lane's video
   const int lim = b < e.B ? (e.S - j + 3) >> 2 : 0;            // accumulator blocks mi < lim hold sampled frames (slot mi*4 + j < S)
-#ifdef EVC_ABLATE_DBOF_EPILOGUE      // timing ablation (profiles/r06_dbof_ablation.txt): the main loop alone, one store per lane keeps the accumulators alive
-  {
-    float keep = 0.f;                                            // (every accumulator feeds the never-taken store: no MFMA is dead code)
-#pragma unroll
-    for (int mi = 0; mi < Cfg::MI; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < Cfg::NI; ++ni) keep += acc[mi][0][ni][0] + acc[mi][0][ni][1] + acc[mi][0][ni][2] + acc[mi][0][ni][3];
-    if (e.S == 0x7fffffff) e.xsel[threadIdx.x] = keep;
-    return;
-  }
-#endif
   if (e.act) {
     // bf16 activation for the backward pass.  The accumulator layout gives a lane 4 consecutive columns of 16 different
     // rows per block: stored directly, every wave-instruction touches 16 lines with 32 bytes each (measured: +0.21 ms on
@@ -382,12 +366,8 @@ __device__ __forceinline__ void dbof_tile_epilogue(const GemmOperands& p, const 
           const uint4 q = *(const uint4*)(wl + rl * RS + (((lane & 7) ^ (rl & 7)) << 4));
           const int row = rbase + r0 + rl;
           if (row < p.M) {
-#if EVC_DBOF_ACT_POLICY      // A/B (round 6): the 268 MB bf16 tape leaves with a cache policy (1 = sc1 write-through, 2 = nt) instead of staying dirty in the XCD's L2
-            const u32x4_t qv = {q.x, q.y, q.z, q.w};
-            store16<EVC_DBOF_ACT_POLICY>(e.act, (uint32_t)(((long)row * e.ld_act + colw + (lane & 7) * 8) * 2), qv);
-#else
-            *(uint4*)(e.act + (long)row * e.ld_act + colw + (lane & 7) * 8) = q;
-#endif
+            const u32x4_t qv = {q.x, q.y, q.z, q.w};      // (the tape leaves with a cache policy instead of staying dirty in the XCD's L2)
+            store16<DBOF_ACT_POLICY>(e.act, (uint32_t)(((long)row * e.ld_act + colw + (lane & 7) * 8) * 2), qv);
           }
         }
       }
@@ -410,21 +390,14 @@ __device__ __forceinline__ void dbof_tile_epilogue(const GemmOperands& p, const 
       for (int mi = 0; mi < Cfg::MI; ++mi) {
         if (mi < lim) {
           const float v = acc[mi][0][ni][r];
-#ifndef EVC_ABLATE_DBOF_STATS
           sum += v;
           sq += v * v;
-#endif
-#ifndef EVC_ABLATE_DBOF_SELECT
           const float t = sgn * v;
           if (t > best) { best = t; bi = mi; }                 // strict: the first maximum wins
-#else
-          best = fmaxf(best, v);                               // (timing ablation: keeps the accumulators alive, no index / sign / tie logic)
-#endif
         }
       }
       int sidx = bi * 4 + j;
       // the video's other three lanes (same quad): maximum, ties to the smaller frame slot
-#ifndef EVC_ABLATE_DBOF_SELECT
       {
         const float ob = dpp_f<QP_XOR1>(best);
         const int oi = dpp_i<QP_XOR1>(sidx);
@@ -435,7 +408,6 @@ __device__ __forceinline__ void dbof_tile_epilogue(const GemmOperands& p, const 
         const int oi = dpp_i<QP_XOR2>(sidx);
         if (ob > best || (ob == best && oi < sidx)) { best = ob; sidx = oi; }
       }
-#endif
       xs[r] = sgn * best;
       args |= (uint32_t)(sidx & 0xff) << (8 * r);
       ssum[r] = row16_sum(sum);                                // the wave's 128 rows (4 videos) of this column
@@ -528,7 +500,6 @@ extern "C" int evc_dbof_cluster_pool_fwd(const evc_bf16* r_bn, const evc_bf16* r
   p.A1lo = r_bn_lo; p.A2lo = nullptr; p.Blo = wT_lo;
   DbofPoolParams e{act, (long)C, part, gamma, xsel, arg, B, S, C};
   const int tm = ceil_div(Mp, CfgDbof::BM), tn = ceil_div(C, CfgDbof::BU);
-#ifndef EVC_DBOF_V2_LOOP
   // tile walk: plain bf16 operands and enough tiles to give 256 workgroups several each (EVC_DBOF_WALK=0: one tile per workgroup, A/B)
   const char* wenv = getenv("EVC_DBOF_WALK");                    // (read per call: the tests switch it; 2 = also below 512 tiles)
   const int walk_on = wenv ? atoi(wenv) : 1;
@@ -549,13 +520,11 @@ extern "C" int evc_dbof_cluster_pool_fwd(const evc_bf16* r_bn, const evc_bf16* r
     EVC_LAUNCH_CHECK();
     return EVC_OK;
   }
-#endif
   launch_cfg<CfgDbof>(dbof_cluster_pool_kernel<false>, tm * tn, (hipStream_t)stream, p, e, tm, tn);
   EVC_LAUNCH_CHECK();
   return EVC_OK;
 }
 
-#ifndef EVC_DBOF_V2_LOOP
 // The cluster GEMM on f16 operands with both operands' low-order corrections as e4m3 operands behind the f16 stages of the same launch
 // (evc_gemm_nt_f16_fp8's arithmetic with this kernel's epilogue): r_rows from evc_dbof_input_bn_apply_f16fp8 (rows of 4F bytes), wT16 [C][F]
 // f16, wT8 [C][2F] = [e4m3((W - f16(W)) 2^w_lo_exp) | e4m3(W 2^w_hi_exp)] (evc_cast_f32_to_fp8_lo, hi_cols = F); scale_exp = -(x_hi_exp +
@@ -582,15 +551,6 @@ extern "C" int evc_dbof_cluster_pool_fwd_f16fp8(const evc_f16* r_rows, const evc
   EVC_LAUNCH_CHECK();
   return EVC_OK;
 }
-#else
-// (A/B build on the 32-wide K stages: the e4m3 tail exists in the 64-wide ring loop only.  The symbol stays exported - the ctypes
-//  table binds every entry point of include/evc.h at import - and says so when called.)
-extern "C" int evc_dbof_cluster_pool_fwd_f16fp8(const evc_f16*, const evc_f16*, const uint8_t*, int, int, int, int, int, const float*, evc_bf16*, float*,
-                                                float*, uint8_t*, void*) {
-  evc_set_error("evc_dbof_cluster_pool_fwd_f16fp8: this library was built with -DEVC_DBOF_V2_LOOP (no e4m3 stages); set EVC_HIGH_FP8_LO=0");
-  return EVC_ERR_UNSUPPORTED_ARCH;
-}
-#endif
 
 // ---------------------------------------------------------------------------------------------------------------
 // K6: pooled = relu6(gamma * (x_sel - mean) * rsqrt(var + eps) + beta)   [B][C]
@@ -628,12 +588,6 @@ extern "C" int evc_dbof_pool_finish(const float* xsel, int B, int C, const float
 // data parallelism); empty frame slots get 0.  A workgroup owns one video x 2048 clusters: its per-column constants
 // and the video's (d, arg) stay in registers while it walks the video's 32 rows.
 // ---------------------------------------------------------------------------------------------------------------
-#ifndef EVC_DBOF_DACT_ROWS
-#define EVC_DBOF_DACT_ROWS 32
-#endif
-#ifndef EVC_DBOF_DACT_NT
-#define EVC_DBOF_DACT_NT 1
-#endif
 __global__ __launch_bounds__(256) void dbof_dact_kernel(bf16_t* __restrict__ act, const float* __restrict__ dpooled,
                                                         const float* __restrict__ pooled, const uint8_t* __restrict__ arg,
                                                         const float* __restrict__ mean, const float* __restrict__ var,
@@ -670,7 +624,7 @@ __global__ __launch_bounds__(256) void dbof_dact_kernel(bf16_t* __restrict__ act
   }
   // The walk is in place: written as load -> store per row, hipcc keeps each row's load behind the previous row's store (one 16-byte load in flight per lane:
   // 3.5 TB/s).  DACT_ROWS rows are loaded before the first of them is stored (round 6; all 32 = the whole video in registers, nt loads: 0.154 -> 0.126 ms, 4.3 TB/s, profiles/r06_dbof_dact_ab.txt).
-  constexpr int DACT_ROWS = EVC_DBOF_DACT_ROWS;
+  constexpr int DACT_ROWS = 32;
   static_assert(SP % DACT_ROWS == 0, "whole row groups");
   for (int s0 = 0; s0 < SP; s0 += DACT_ROWS) {
     uint4 q[DACT_ROWS];
@@ -678,11 +632,7 @@ __global__ __launch_bounds__(256) void dbof_dact_kernel(bf16_t* __restrict__ act
     for (int j = 0; j < DACT_ROWS; ++j) {
       q[j] = make_uint4(0u, 0u, 0u, 0u);
       if (live && s0 + j < S) {
-#if EVC_DBOF_DACT_NT
         const u32x4_t t = __builtin_nontemporal_load((const u32x4_t*)(act + dbof_row(b, s0 + j) * C + c0));   // the tape is read once
-#else
-        const u32x4_t t = *(const u32x4_t*)(act + dbof_row(b, s0 + j) * C + c0);
-#endif
         q[j] = make_uint4(t[0], t[1], t[2], t[3]);
       }
     }

@@ -40,9 +40,6 @@ __device__ __forceinline__ float block_sum(float v, float* sh) {
 // ---------------------------------------------------------------------------
 // a1 + a2: l2-normalise, sub-sample, cast, re-layout.  One wave per frame.
 // ---------------------------------------------------------------------------
-#ifndef EVC_INPUT_NT
-#define EVC_INPUT_NT 0
-#endif
 template <bool U8>
 __global__ __launch_bounds__(256) void l2norm_chunk_kernel(const float* __restrict__ x, const uint8_t* __restrict__ xq,
                                                            const int* __restrict__ nfr, int B, int T, int F, int C1,
@@ -100,12 +97,7 @@ __global__ __launch_bounds__(256) void l2norm_chunk_kernel(const float* __restri
           v[i] = make_float4(q.x * sc + bs, q.y * sc + bs, q.z * sc + bs, q.w * sc + bs);
         }
       } else {
-#if EVC_INPUT_NT       // (A/B: the f32 frame tensor - 354 MB at the headline's batch, read once at the head of every step - as non-temporal loads)
-        const f32x4 t4 = __builtin_nontemporal_load((const f32x4*)(x + row * F) + j);
-        v[i] = make_float4(t4[0], t4[1], t4[2], t4[3]);
-#else
         v[i] = ((const float4*)(x + row * F))[j];
-#endif
       }
       ss += v[i].x * v[i].x + v[i].y * v[i].y + v[i].z * v[i].z + v[i].w * v[i].w;
     }
@@ -1791,19 +1783,12 @@ extern "C" int evc_framepool_max_bwd(const float* dpooled, const int32_t* argmax
   return EVC_OK;
 }
 
-#ifndef EVC_FILL_NT
-#define EVC_FILL_NT 0
-#endif
 __global__ void fill_kernel(float* p, long n, float v) {
   const long stride = (long)gridDim.x * blockDim.x, tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if ((((uintptr_t)p) & 15) == 0) {      // 16-byte stores over the aligned body, scalar tail
     const long n4 = n >> 2;
     const float4 v4 = make_float4(v, v, v, v);
-#if EVC_FILL_NT      // (A/B: the zero fills of the gradient buffers - 372 MB per step, next touched by the split-K atomics - as non-temporal stores)
-    for (long i = tid; i < n4; i += stride) __builtin_nontemporal_store(f32x4{v, v, v, v}, (f32x4*)p + i);
-#else
     for (long i = tid; i < n4; i += stride) ((float4*)p)[i] = v4;
-#endif
     for (long i = (n4 << 2) + tid; i < n; i += stride) p[i] = v;
   } else {
     for (long i = tid; i < n; i += stride) p[i] = v;

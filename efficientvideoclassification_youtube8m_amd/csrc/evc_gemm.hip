@@ -30,18 +30,16 @@ __global__ __launch_bounds__(Cfg::NT) void gemm_nt_kernel(GemmOperands p, StoreP
   // loop options (gemm_core_v2.h): producer waves + LDS-DMA first + no priority flips for every ring tile but the 320-row one
   // (same box: L1 dX 477 -> 431 us, 1280 x 4096 x 4096 63 -> 56.5 us, MoE gates forward 48.3 -> 46 us; 5120 x 4096 x 4096 on
   // the 320-row tile 153 -> 162 us with them)
-#ifndef EVC_TALL_B_NT
-#define EVC_TALL_B_NT 1      // the weight rows of the batch-row products (256 x 64 tiles: every weight row is read by ONE workgroup) as non-temporal LDS-DMA loads
-                             // (round 5; same box, alternated three times: the MoE gates product ALONE 42.9 -> 49.3 us, the training step 9.96 -> 9.92 ms -
-                             // 193 MB of weights per product no longer evict what the other streams' kernels re-read; 0 = default policy)
-#endif
+  // the weight rows of the batch-row products (256 x 64 tiles: every weight row is read by ONE workgroup) as non-temporal LDS-DMA loads
+  // (round 5; same box, alternated three times: the MoE gates product ALONE 42.9 -> 49.3 us, the training step 9.96 -> 9.92 ms -
+  // 193 MB of weights per product no longer evict what the other streams' kernels re-read)
   constexpr int NT_MODE = (Cfg::BM == 320 ? 0 : (LOOP_PRODUCER | LOOP_DMA_FIRST | LOOP_NO_PRIO)) | (F16 ? LOOP_F16 : 0) | (FP8 ? LOOP_FP8_TAIL : 0) |
-                          ((EVC_TALL_B_NT && is_v3<Cfg>::value && Cfg::BM == 256 && Cfg::BU == 64) ? LOOP_B_NT : 0);
+                          ((is_v3<Cfg>::value && Cfg::BM == 256 && Cfg::BU == 64) ? LOOP_B_NT : 0);
   run_mainloop<Cfg, Cfg::G, V2, true, NT_MODE>(p, m0, u0, acc);     // ring tiles: transposed accumulators (lane = one row, 4 consecutive columns)
   if constexpr (V2) {
     // plain overwrite with 16-byte-aligned rows, or the split-K join: through LDS (kernel-uniform conditions: one barrier)
     const int es = s.out_bf16 ? 2 : 4;
-    const bool lds_store = s.splits == 1 && !s.accumulate && (s.ldc * es) % 16 == 0 && ((uintptr_t)s.C % 16) == 0 &&
+    const bool via_lds = s.splits == 1 && !s.accumulate && (s.ldc * es) % 16 == 0 && ((uintptr_t)s.C % 16) == 0 &&
                            (!s.bias || ((uintptr_t)s.bias % 16) == 0);
     const int wave = threadIdx.x >> 6, wc = wave % Cfg::WC;
     const bool wave_cols_in = u0 + wc * Cfg::WU + Cfg::WU <= s.N;         // this wave's column span lies inside C
@@ -52,7 +50,7 @@ __global__ __launch_bounds__(Cfg::NT) void gemm_nt_kernel(GemmOperands p, StoreP
         return;
       }
     }
-    if (lds_store) {
+    if (via_lds) {
       __syncthreads();
       if (wave_cols_in) {
         if (s.out_bf16) store_tile_via_lds<Cfg, 2>(acc, lds_dyn, s.C, s.ldc, s.M, s.N, m0, u0, s.bias);
@@ -153,9 +151,7 @@ static int gemm_nt_impl(const evc_bf16* A, int64_t lda, const evc_bf16* B, int64
     if (splits > K / 1024) splits = K / 1024;
     if (splits < 1 || evc_deterministic()) splits = 1;
     if (splits > 1 && !accumulate) EVC_CHECK_HIP(hipMemset2DAsync(C, ldc * sizeof(float), 0, (size_t)N * sizeof(float), M, st));
-    static const bool tall_v2 = getenv("EVC_TALL_V2") != nullptr;      // A/B: the 32-wide K stages
-    if (tall_v2) launch_gemm<CfgTallV2>(p, s, K, splits, st);
-    else launch_gemm<TileCfg3<256, 1, 64, 2, 4, 4>>(p, s, K, splits, st);   // 64-wide K stages: the [256][K] row operand is re-read from L2 by every workgroup
+    launch_gemm<TileCfg3<256, 1, 64, 2, 4, 4>>(p, s, K, splits, st);   // 64-wide K stages: the [256][K] row operand is re-read from L2 by every workgroup
     EVC_LAUNCH_CHECK();
     return EVC_OK;
   }
@@ -216,20 +212,12 @@ static int gemm_nt_impl(const evc_bf16* A, int64_t lda, const evc_bf16* B, int64
   if (pick == 2 && K >= 2048 && (long)ceil_div(M, 128) * ceil_div(N, 128) <= 256) pick = 5;
   if (sq_out && (pick == 2 || pick == 3)) pick = ring;            // (the fused norm lives in the ring tiles' LDS store)
   if (forced_tile()) pick = forced_tile();
-  static const bool nt_v3 = getenv("EVC_NT_BIG_V2") == nullptr;          // the 224/256-row tiles on two 64-wide stages (A/B switch: the five 32-wide ones)
-  static const bool v3 = getenv("EVC_NT_V2_LOOP") == nullptr;      // 64-wide K stages for the 128-column ring tiles (A/B switch)
-#ifdef EVC_EXPERIMENT_4WAVE
-  if (pick == 12) { launch_gemm<TileCfg3<256, 1, 256, 2, 2, 2>>(p, s, K, 1, st); EVC_LAUNCH_CHECK(); return EVC_OK; }   // 4 waves, 128 x 128 per wave
-#endif
-  if (pick == 5 && v3) launch_gemm<TileCfg3<128, 1, 128, 2, 4, 4>>(p, s, K, 1, st);
-  else if (pick == 5) launch_gemm<CfgTn128>(p, s, K, 1, st);
-  else if (pick == 4 && nt_v3) launch_gemm<TileCfg3<224, 1, 256, 2, 4, 2>>(p, s, K, 1, st);
-  else if (pick == 4) launch_gemm<CfgPlainV2_224>(p, s, K, 1, st);
+  // the ring tiles on 64-wide K stages (the 224 / 256-row ones on two of them, the 128-column ones on four)
+  if (pick == 5) launch_gemm<TileCfg3<128, 1, 128, 2, 4, 4>>(p, s, K, 1, st);
+  else if (pick == 4) launch_gemm<TileCfg3<224, 1, 256, 2, 4, 2>>(p, s, K, 1, st);
   else if (pick == 6) launch_gemm<CfgPlainV2_320>(p, s, K, 1, st);
-  else if (pick == 1 && nt_v3) launch_gemm<TileCfg3<256, 1, 256, 2, 4, 2>>(p, s, K, 1, st);
-  else if (pick == 7 && v3) launch_gemm<TileCfg3<160, 1, 128, 2, 4, 4>>(p, s, K, 1, st);
-  else if (pick == 7) launch_gemm<TileCfg2<160, 1, 128, 2, 4, 5, true>>(p, s, K, 1, st);
-  else if (pick == 1) launch_gemm<CfgPlainV2>(p, s, K, 1, st);
+  else if (pick == 1) launch_gemm<TileCfg3<256, 1, 256, 2, 4, 2>>(p, s, K, 1, st);
+  else if (pick == 7) launch_gemm<TileCfg3<160, 1, 128, 2, 4, 4>>(p, s, K, 1, st);
   else if (pick == 2) launch_gemm<CfgPlainBig>(p, s, K, 1, st);
   else launch_gemm<CfgPlainSmall>(p, s, K, 1, st);
   EVC_LAUNCH_CHECK();

@@ -51,7 +51,7 @@ __global__ __launch_bounds__(Cfg::NT) void gemm_tn_kernel(GemmOperandsT p, Store
     p.nk = min(s.ksteps_per_split, p.nk - k0);
   }
   f32x4 acc[Cfg::MI][1][Cfg::NI];
-  gemm_mainloop_tn<Cfg, true, EVC_TN_LOOP_MODE, SEG>(p, m0, nb, lds_dyn, acc);      // transposed accumulators: lane = one row, 4 consecutive columns
+  gemm_mainloop_tn<Cfg, true, TN_LOOP_MODE, SEG>(p, m0, nb, lds_dyn, acc);      // transposed accumulators: lane = one row, 4 consecutive columns
   // Through the per-wave LDS transpose (store_tile_via_lds): whole sub-tile rows for the plain / slab stores, contiguous
   // row runs for the split-K atomics ("accumulate" is the same join onto what C already holds).
   float* C = s.C + split * s.slab_stride;
@@ -59,9 +59,6 @@ __global__ __launch_bounds__(Cfg::NT) void gemm_tn_kernel(GemmOperandsT p, Store
   const bool plain = s.slab_stride > 0 || (s.splits == 1 && !s.accumulate);
   const bool aligned = (s.ldc % 4) == 0 && ((uintptr_t)C % 16) == 0 && n0 + wc * Cfg::WU + Cfg::WU <= s.N;
   __syncthreads();                                             // every wave has read its last ring slot
-#ifdef EVC_ABLATE_TN_ATOMICS     // debug build: plain stores instead of the split-K atomics (wrong sums, timing only)
-  store_tile_via_lds<Cfg, 4, false>(acc, lds_dyn, C, s.ldc, s.M, s.N, m0, n0, nullptr, s.row_il_H);
-#else
   if (plain && aligned) {
     store_tile_via_lds<Cfg, 4, false>(acc, lds_dyn, C, s.ldc, s.M, s.N, m0, n0, nullptr, s.row_il_H);
   } else if (s.splits == 1 && s.accumulate && aligned) {     // one workgroup per tile: C += tile needs no atomics
@@ -84,7 +81,6 @@ __global__ __launch_bounds__(Cfg::NT) void gemm_tn_kernel(GemmOperandsT p, Store
   } else {
     store_tile_via_lds<Cfg, 4, true>(acc, lds_dyn, C, s.ldc, s.M, s.N, m0, n0, nullptr, s.row_il_H);
   }
-#endif
 }
 
 static int gemm_tn_impl(const evc_bf16* A, int64_t lda, const evc_bf16* B, int64_t ldb, int N1, const evc_bf16* B2, int64_t ldb2,
@@ -287,33 +283,19 @@ struct MoeUpdateParams {
   float l2, clip, lr_t, b1, b2, eps;
 };
 
-#ifndef EVC_ADAM_NT
-#define EVC_ADAM_NT 1       // (round 5: 1 = W, m, v of the fused MoE update - read once, written once, 5.9 GB per step - as non-temporal accesses: same box, alternated three times, 10.00 -> 9.93 ms per step; 0 = plain accesses; 2 = the bf16 shadows too - they are read again soon: 9.82 -> 9.93)
-#endif
+// W, m, v of the fused MoE update - read once, written once, 5.9 GB per step - as non-temporal accesses (round 5: same box, alternated three times,
+// 10.00 -> 9.93 ms per step); the bf16 shadows stay plain - they are read again soon (non-temporal too: 9.82 -> 9.93)
 __device__ __forceinline__ float4 ld_stream_moe(const float* p) {
-#if EVC_ADAM_NT
   const f32x4 v = __builtin_nontemporal_load((const f32x4*)p);
   return make_float4(v[0], v[1], v[2], v[3]);
-#else
-  return *(const float4*)p;
-#endif
 }
 __device__ __forceinline__ void st_stream_moe(float* p, float a, float b, float c, float d) {
-#if EVC_ADAM_NT
   __builtin_nontemporal_store(f32x4{a, b, c, d}, (f32x4*)p);
-#else
-  *(float4*)p = make_float4(a, b, c, d);
-#endif
 }
-#ifndef EVC_MOE_UPD_EARLY_MV
-#define EVC_MOE_UPD_EARLY_MV 0          // (A/B, round 5: 1 = m and v asked for ahead of the factor product like p - 219 VGPRs, still one workgroup per CU;
-                                        //  measured 459-462 / 309-316 us against 442-456 / 302-305: nothing, the pass is not waiting for those loads)
-#endif
-#ifndef EVC_MOE_UPD_WAVES_PER_EU
-#define EVC_MOE_UPD_WAVES_PER_EU 2      // (A/B: 4 = cap the kernel at 128 VGPRs so that two of its 80 KB workgroups share a CU)
-#endif
+// (m and v asked for ahead of the factor product like p - 219 VGPRs, still one workgroup per CU - measured 459-462 / 309-316 us against
+//  442-456 / 302-305: nothing, the pass is not waiting for those loads)
 template <class Cfg, int PASS>
-__global__ __launch_bounds__(Cfg::NT, EVC_MOE_UPD_WAVES_PER_EU) void moe_update_kernel(GemmOperandsT p, MoeUpdateParams u, int tiles_m, int tiles_n) {
+__global__ __launch_bounds__(Cfg::NT, 2) void moe_update_kernel(GemmOperandsT p, MoeUpdateParams u, int tiles_m, int tiles_n) {
   const int nwg = tiles_m * tiles_n;
   const int id = xcd_remap(blockIdx.x, nwg);
   int tm, tn;
@@ -335,21 +317,6 @@ __global__ __launch_bounds__(Cfg::NT, EVC_MOE_UPD_WAVES_PER_EU) void moe_update_
       const int vr = m0 + tc.row0 + mi * 16, k = n0 + tc.unit0 + ni * 16;
       pv[mi][ni] = (vr < u.V && k < K) ? ld_stream_moe(u.p + (long)vr * K + k) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
-#if EVC_MOE_UPD_EARLY_MV
-  // (A/B) m and v asked for up front too: the update pass owns its CU either way (184 -> 219 VGPRs, still one 8-wave workgroup)
-  float4 mv[Cfg::MI][Cfg::NI], vv[Cfg::MI][Cfg::NI];
-  if (PASS == 2) {
-#pragma unroll
-    for (int mi = 0; mi < Cfg::MI; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < Cfg::NI; ++ni) {
-        const int vr = m0 + tc.row0 + mi * 16, k = n0 + tc.unit0 + ni * 16;
-        const bool ok = vr < u.V && k < K;
-        mv[mi][ni] = ok ? *(const float4*)(u.m + (long)vr * K + k) : make_float4(0.f, 0.f, 0.f, 0.f);
-        vv[mi][ni] = ok ? *(const float4*)(u.v + (long)vr * K + k) : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-  }
-#endif
   gemm_mainloop_tn<Cfg, true>(p, m0, n0, lds_dyn, acc);
   if (PASS == 1) {
     float sg = 0.f, sp = 0.f;
@@ -384,7 +351,6 @@ __global__ __launch_bounds__(Cfg::NT, EVC_MOE_UPD_WAVES_PER_EU) void moe_update_
     }
     return;
   }
-#if !EVC_MOE_UPD_EARLY_MV
   float4 mv[Cfg::MI][Cfg::NI], vv[Cfg::MI][Cfg::NI];
 #pragma unroll
   for (int mi = 0; mi < Cfg::MI; ++mi)
@@ -395,7 +361,6 @@ __global__ __launch_bounds__(Cfg::NT, EVC_MOE_UPD_WAVES_PER_EU) void moe_update_
       mv[mi][ni] = ok ? ld_stream_moe(u.m + (long)vr * K + k) : make_float4(0.f, 0.f, 0.f, 0.f);
       vv[mi][ni] = ok ? ld_stream_moe(u.v + (long)vr * K + k) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
-#endif
   float scale = 1.f;
   if (u.clip > 0.f) scale = u.clip / fmaxf(sqrtf(u.sums[0]), u.clip);      // tf.clip_by_norm
   float wsq = 0.f;                                     // sum of the NEW weights squared (the next update's |W|^2: evc_moe_grad_norms)
@@ -430,11 +395,7 @@ __global__ __launch_bounds__(Cfg::NT, EVC_MOE_UPD_WAVES_PER_EU) void moe_update_
         st_stream_moe(u.v + o, vn[0], vn[1], vn[2], vn[3]);
         if (u.p_bf16) {
           const u32x2_t sb = {(uint32_t)pb[0] | ((uint32_t)pb[1] << 16), (uint32_t)pb[2] | ((uint32_t)pb[3] << 16)};
-#if EVC_ADAM_NT >= 2
-          __builtin_nontemporal_store(sb, (u32x2_t*)(u.p_bf16 + o));
-#else
           *(u32x2_t*)(u.p_bf16 + o) = sb;
-#endif
         }
         if (u.p_f16) {                                // f16 + e4m3 images: saves the passes over the f32 weights (evc_cast_f32_to_f16 / _fp8_lo) per update
           const uint32_t h01 = pack_f16x2_hw(pn[0], pn[1]), h23 = pack_f16x2_hw(pn[2], pn[3]);
@@ -475,11 +436,7 @@ __global__ __launch_bounds__(Cfg::NT, EVC_MOE_UPD_WAVES_PER_EU) void moe_update_
     const int k = n0 + kl;
     if (k >= K || v4 >= u.V) continue;                 // V % 4 == 0: a lane's 4 rows are all valid or all not
     const uint2 q = *(const uint2*)(tile + kl * PITCH + (lane % LPR) * 4);
-#if EVC_ADAM_NT >= 2
-    __builtin_nontemporal_store(u32x2_t{q.x, q.y}, (u32x2_t*)(u.pT_bf16 + (long)k * u.ldT + v4));
-#else
     *(uint2*)(u.pT_bf16 + (long)k * u.ldT + v4) = q;
-#endif
   }
   if (u.wsq_partial) {                                 // per-workgroup partial, summed in a fixed order by moe_update_finalize_kernel
     wsq = wave_sum(wsq);

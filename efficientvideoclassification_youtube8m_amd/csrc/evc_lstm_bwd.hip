@@ -135,12 +135,7 @@ __device__ __forceinline__ void lstm_bwd_zero_tile(const LstmBwdParams& e, int m
 // global access of the tail is a contiguous run over the whole wave (gate records 1 KB, dz 1 KB, dc 512 B, cell history
 // 256 B per row), GROUP rows in flight per thread.  Straight from the accumulator layout (lane = 4 units of one row, 16
 // rows per instruction) the same bytes moved in 32-64-byte pieces and the tail took 32 of the step's 70 us.
-#ifndef EVC_BWD_TAPE_NT
-#define EVC_BWD_TAPE_NT 0
-#endif
-#ifndef EVC_BWD_TAIL_PRE
-#define EVC_BWD_TAIL_PRE 8          // row slots (of BM / 8 per thread) whose tape / state loads are issued BEFORE the main loop (round 6); 0 = every load in the tail (rounds 3-5)
-#endif
+constexpr int BWD_TAIL_PRE = 8;     // row slots (of BM / 8 per thread) whose tape / state loads are issued BEFORE the main loop (round 6; rounds 3-5 issued every load in the tail)
 // What a thread loads for N of its rows: the running dc (or the state gradient dS at a row's last step), the gate records, the cell history before and
 // after the step, the gradient arriving from the layer above.  None of it depends on this launch's product.
 template <int N>
@@ -176,17 +171,10 @@ __device__ __forceinline__ void lstm_bwd_tail_load(const LstmBwdParams& e, int m
         r.dcv[i] = *(const unsigned long long*)(last ? e.dS_c + su : e.dc_ws + hu);
       }
       if (last) r.dhs[i] = *(const unsigned long long*)(e.dS_h + su);
-#if EVC_BWD_TAPE_NT      // (A/B: the tape - gate records, cell history, the gradient from the layer above - is read ONCE, milliseconds after it was written: non-temporal loads)
-      if (e.dh_above) r.dha[i] = __builtin_nontemporal_load((const uint32_t*)(e.dh_above + hu));
-      { const u32x4_t gq = __builtin_nontemporal_load((const u32x4_t*)(e.gates + hu)); r.grec[i] = make_uint4(gq[0], gq[1], gq[2], gq[3]); }
-      r.cn[i] = __builtin_nontemporal_load((const uint32_t*)(e.c_new + hu));
-      if (e.c_old) r.co[i] = __builtin_nontemporal_load((const uint32_t*)(e.c_old + hu));
-#else
       if (e.dh_above) r.dha[i] = *(const uint32_t*)(e.dh_above + hu);
       r.grec[i] = *(const uint4*)(e.gates + hu);
       r.cn[i] = *(const uint32_t*)(e.c_new + hu);
       if (e.c_old) r.co[i] = *(const uint32_t*)(e.c_old + hu);
-#endif
     }
   }
 }
@@ -333,27 +321,16 @@ __device__ __forceinline__ void lstm_bwd_step_body(const GemmOperands& p, const 
     return;
   }
   f32x4 acc[Cfg::MI][1][Cfg::NI];
-#if !defined(EVC_ABLATE_BWD_EPI) && !defined(EVC_BWD_TAIL_FRAGMENTS)
   constexpr bool ROWMAJOR = is_v2<Cfg>::value && Cfg::BU == 128 && Cfg::NT == 512 && Cfg::BM % 32 == 0 && BATCH_LOADS;
-#else
-  constexpr bool ROWMAJOR = false;
-#endif
   // the row-major tail's first PRE row slots: loads issued here, consumed after the product (older than every ring load: the ring's counted waits hold)
-  constexpr int PRE = (ROWMAJOR && (Cfg::BM / 8 - EVC_BWD_TAIL_PRE) % 8 == 0 && EVC_BWD_TAIL_PRE <= Cfg::BM / 8) ? EVC_BWD_TAIL_PRE : 0;
+  constexpr int PRE = (ROWMAJOR && (Cfg::BM / 8 - BWD_TAIL_PRE) % 8 == 0 && BWD_TAIL_PRE <= Cfg::BM / 8) ? BWD_TAIL_PRE : 0;
   BwdTailRows<(PRE > 0 ? PRE : 1)> pre;
   if constexpr (PRE > 0) {
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int u = u0 + lane * 2;
     lstm_bwd_tail_load<PRE>(e, m0, u, u < e.H, wave, 0, pre);
   }
-#ifdef EVC_ABLATE_BWD_MAIN     // debug build: epilogue only
-#pragma unroll
-  for (int mi = 0; mi < Cfg::MI; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < Cfg::NI; ++ni) acc[mi][0][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
-#else
-  run_mainloop<Cfg, 1, true, true, EVC_BWD_LOOP_MODE>(p, m0, u0, acc);     // transposed accumulators: lane = one row, 4 consecutive units
-#endif
+  run_mainloop<Cfg, 1, true, true, BWD_LOOP_MODE>(p, m0, u0, acc);     // transposed accumulators: lane = one row, 4 consecutive units
   if constexpr (ROWMAJOR) {
     lstm_bwd_tail_rowmajor<Cfg, PRE>(acc, e, m0, u0, lds_dyn, pre);
     return;
@@ -380,9 +357,6 @@ __device__ __forceinline__ void lstm_bwd_step_body(const GemmOperands& p, const 
     for (int mi = 0; mi < Cfg::MI; ++mi) {
       const int m = m0 + tc.row0 + mi * 16;
       const float dh[4] = {acc[mi][0][ni][0], acc[mi][0][ni][1], acc[mi][0][ni][2], acc[mi][0][ni][3]};
-#ifdef EVC_ABLATE_BWD_EPI     // debug build: main loop only (keep the accumulators alive, store nothing)
-      asm volatile("" :: "v"(dh[0]), "v"(dh[1]), "v"(dh[2]), "v"(dh[3]));
-#else
       float dzv[4][4];
       if constexpr (!BATCH_LOADS) lstm_bwd_load(e, m, u, m < e.M, in[0]);
       lstm_bwd_finish(e, m, u, dh, in[BATCH_LOADS ? mi : 0], dzv);
@@ -390,7 +364,6 @@ __device__ __forceinline__ void lstm_bwd_step_body(const GemmOperands& p, const 
       for (int r = 0; r < 4; ++r)
 #pragma unroll
         for (int g = 0; g < 4; ++g) bs[r][g] += dzv[r][g];
-#endif
     }
     if (e.db) {                                        // bias gradient: the 16 lanes l&15 hold 16 rows of the same 4 units
 #pragma unroll
@@ -428,122 +401,7 @@ __global__ __launch_bounds__(Cfg::NT, 4) void lstm_bwd_pair_kernel(GemmOperands 
 
 // "Skinny" BPTT step for M ~ batch (the L2 stacks: 256 rows, K = 4H = 4096): with a 32x32 tile per
 // workgroup the LDS-staged loops above are latency-bound (64 dependent load->barrier->MFMA rounds, ~30 us
-// for 2 GFLOP).  Here the K range is split over the KW waves of the workgroup and every wave loads its MFMA
-// fragments STRAIGHT from global memory into registers (for v_mfma_f32_16x16x32_bf16 lane l supplies row
-// l&15, k = 8*(l>>4)..+7 = one aligned 16-byte load): no LDS staging, no barrier in the loop, DEPTH K steps
-// of loads in flight per wave.  The KW partial 32x32 tiles meet in LDS once, then 256 threads run the tail.
-template <int KW, int DEPTH>
-__global__ __launch_bounds__(64 * KW) void lstm_bwd_step_skinny_kernel(GemmOperands p, LstmBwdParams e, int tiles_m, int tiles_n) {
-  constexpr int NT = 64 * KW;
-  __shared__ float part[KW][32][36];                 // [wave][row][unit] (+4 pad: conflict-free float4 rows)
-  const int nwg = tiles_m * tiles_n;
-  const int id = xcd_remap(blockIdx.x, nwg);
-  const int tm = id % tiles_m, tn = id / tiles_m;    // consecutive ids (one XCD) share the B panel of a unit tile
-  const int m0 = tm * 32, u0 = tn * 32;
-  if (m0 >= e.m_active) {
-    lstm_bwd_zero_tile<32, 32, NT>(e, m0, u0);
-    return;
-  }
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int fr = lane & 15, fq = lane >> 4;
-  const int nk = p.nk1;                              // 32-wide K steps
-  const int per = (nk + KW - 1) / KW;
-  const int k0 = min(wave * per, max(nk - 1, 0)), k1 = min(nk, wave * per + per);   // k0 clamped: idle waves still load in bounds
-  const bf16_t* ap[2];
-  const bf16_t* bp[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int m = min(m0 + i * 16 + fr, p.M - 1), u = min(u0 + i * 16 + fr, p.Nu - 1);
-    ap[i] = p.A1 + (long)m * p.lda1 + fq * 8 + (long)k0 * 32;
-    bp[i] = p.B + (long)u * p.ldb + fq * 8 + (long)k0 * 32;
-  }
-  f32x4 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  bf16x8 fa[DEPTH][2], fb[DEPTH][2];
-  const int n = k1 - k0;                             // this wave's K steps (wave-uniform, may be <= 0)
-#pragma unroll
-  for (int d = 0; d < DEPTH; ++d) {
-    const int kk = min(d, max(n - 1, 0));            // clamped: surplus loads re-read a valid step
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      fa[d][i] = *(const bf16x8*)(ap[i] + (long)kk * 32);
-      fb[d][i] = *(const bf16x8*)(bp[i] + (long)kk * 32);
-    }
-  }
-  for (int k = 0; k < n; k += DEPTH) {
-#pragma unroll
-    for (int d = 0; d < DEPTH; ++d) {
-      if (k + d < n) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[d][i], fb[d][j], acc[i][j], 0, 0, 0);
-      }
-#ifndef EVC_ABLATE_SKINNY_LOADS
-      const int kn = min(k + d + DEPTH, max(n - 1, 0));
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        fa[d][i] = *(const bf16x8*)(ap[i] + (long)kn * 32);
-        fb[d][i] = *(const bf16x8*)(bp[i] + (long)kn * 32);
-      }
-#endif
-    }
-  }
-  // acc[i][j][r]: row = i*16 + fq*4 + r (A row), unit = j*16 + fr (B row)
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) part[wave][i * 16 + fq * 4 + r][j * 16 + fr] = acc[i][j][r];
-  __syncthreads();
-  const int row = (threadIdx.x >> 3) & 31, ug = (threadIdx.x & 7) * 4;
-  float dzv[4][4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) dzv[r][g] = 0.f;
-  if (threadIdx.x < 256) {
-    float4 s = *(const float4*)&part[0][row][ug];
-#pragma unroll
-    for (int w = 1; w < KW; ++w) {
-      const float4 v = *(const float4*)&part[w][row][ug];
-      s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-    }
-    const int m = m0 + row, u = u0 + ug;
-    if (m < e.M && u < e.H) {
-      const float dh[4] = {s.x, s.y, s.z, s.w};
-      LstmBwdIn in;
-      lstm_bwd_load(e, m, u, true, in);
-      lstm_bwd_finish(e, m, u, dh, in, dzv);
-    }
-  }
-  if (e.db) {            // bias gradient (e.db is a kernel argument: uniform branch): column sums of the tile's 32 rows
-    __syncthreads();     // every partial has been read
-    float* cs = &part[0][0][0];                        // [32 rows][128 = 32 units x 4 gates]
-    if (threadIdx.x < 256) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) cs[row * 128 + (ug + r) * 4 + g] = dzv[r][g];
-    }
-    __syncthreads();
-    if (threadIdx.x < 128) {
-      float v = 0.f;
-#pragma unroll 8
-      for (int r = 0; r < 32; ++r) v += cs[r * 128 + threadIdx.x];
-      const int u = u0 + (threadIdx.x >> 2), g = threadIdx.x & 3;
-      if (u < e.H) atomicAdd(e.db + (long)g * e.H + u, v);
-    }
-  }
-}
-
-// Skinny BPTT step, second form: the same K split over the waves, but every wave stages its K slice through a
+// for 2 GFLOP).  Here the K range is split over the KW waves of the workgroup and every wave stages its K slice through a
 // PRIVATE ring of LDS-DMA stages (64-wide K steps, 128-byte rows: each 1 KiB DMA instruction moves 8 full cache
 // lines, where a direct fragment load touches 16 half-used ones) and waits only on its own vmcnt - no barrier in
 // the loop, 3 stages in flight per wave.  LDS: KW x STAGES x 8 KiB rings + the partial tiles.
@@ -713,12 +571,6 @@ static inline void launch_lstm_bwd(GemmOperands p, const LstmBwdParams& e, int k
 
 typedef TileCfg2<128, 1, 128, 2, 4, 5, true> CfgBwdV2_128;   // BPTT step tiles: BM rows x 128 units, 8 waves (2x4)
 typedef TileCfg3<128, 1, 128, 2, 4, 4> CfgBwdV3_128;         // the same tile on 64-wide K stages (whole cache lines per LDS-DMA piece)
-// shallower rings for the same tile (A/B, EVC_BWD_STAGES=3 | 2): 96 / 66 KB of LDS instead of 128 - room for a 64 KB workgroup of another stream on the CU
-typedef TileCfg3<128, 1, 128, 2, 4, 3> CfgBwdV3_128s3;
-typedef TileCfg3<128, 1, 128, 2, 4, 5> CfgBwdV3_128s5;        // (and a deeper one: the whole 160 KB)
-struct CfgBwdV3_128s2 : TileCfg3<128, 1, 128, 2, 4, 2> { static constexpr int LDS_BYTES = 128 * (128 * 4 + 16); };   // (the row-major tail's dh tile: 66 KB)
-template <> struct is_v2<CfgBwdV3_128s2> { static constexpr bool value = true; };
-template <> struct is_v3<CfgBwdV3_128s2> { static constexpr bool value = true; };
 typedef TileCfg3<64, 1, 64, 2, 4, 4> CfgBwdV3_64;            // ~1000 live rows (the student's L1 levels): 16 x 16 = 256 tiles of 64 x 64, 64 KB of LDS
 typedef TileCfg2<160, 1, 128, 2, 4, 5, true> CfgBwdV2_160;
 typedef TileCfg2<192, 1, 128, 2, 4, 5, true> CfgBwdV2_192;
@@ -764,7 +616,7 @@ extern "C" int evc_lstm_layer_bwd(const evc_bf16* w_il, const int32_t* len, int 
       const double c = tile_cost((long)ceil_div(ma, bm[i]) * ceil_div(H, bn[i]), bm[i], bn[i], 1, cf[i]);
       if (c < bc) { bc = c; pick = i; }
     }
-    if ((long)ceil_div(ma, 32) * ceil_div(H, 32) <= 512) pick = 5;   // M ~ batch: K split over the waves, fragments straight from global
+    if ((long)ceil_div(ma, 32) * ceil_div(H, 32) <= 512) pick = 5;   // M ~ batch: K split over the waves, a private LDS ring per wave
     if (forced_tile()) pick = forced_tile() - 1;          // debug: 1 -> 192, 2 -> 160, 3 -> 128, 4 -> v1 64, 5 -> v1 32, 6 -> skinny, 7 -> ring 64x64
     if (dz_above && pick > 2) pick = 2;                   // the two-matrix K walk (B2) exists in the ring loop only
     GemmOperands p;
@@ -790,41 +642,26 @@ extern "C" int evc_lstm_layer_bwd(const evc_bf16* w_il, const int32_t* len, int 
     e.dc_bf16 = bwd_dc_bf16();
     e.row_map = row_map; e.db = db; e.m_active = Mt;
     e.M = M; e.H = H; e.fused_above = dz_above ? 1 : 0;
-    static const int bwd_stages = getenv("EVC_BWD_STAGES") ? atoi(getenv("EVC_BWD_STAGES")) : 4;     // A/B: ring depth of the 128 x 128 BPTT tile
     switch (pick) {
       case 0: launch_lstm_bwd<CfgBwdV2_192>(p, e, k1, st); break;
       case 1: launch_lstm_bwd<CfgBwdV2_160>(p, e, k1, st); break;
       case 2:
-        if (getenv("EVC_BWD_V2_LOOP") || dz_above) launch_lstm_bwd<CfgBwdV2_128>(p, e, k1, st);   // (two-matrix K walk: nk2 is set in 32-wide steps above)
-        else if (bwd_stages == 3) launch_lstm_bwd<CfgBwdV3_128s3>(p, e, k1, st);
-        else if (bwd_stages == 5) launch_lstm_bwd<CfgBwdV3_128s5>(p, e, k1, st);
-        else if (bwd_stages == 2) launch_lstm_bwd<CfgBwdV3_128s2>(p, e, k1, st);
+        if (dz_above) launch_lstm_bwd<CfgBwdV2_128>(p, e, k1, st);   // (two-matrix K walk: nk2 is set in 32-wide steps above)
         else launch_lstm_bwd<CfgBwdV3_128>(p, e, k1, st);
         break;
       case 4: launch_lstm_bwd<CfgPlainTiny>(p, e, k1, st); break;
       case 6: launch_lstm_bwd<CfgBwdV3_64>(p, e, k1, st); break;
       case 5: {
         const int tm = ceil_div(M, 32), tn = ceil_div(H, 32);
-        if (getenv("EVC_SKINNY_DIRECT")) {               // first form: fragments straight from global memory
-          p.nk1 = k1 / 32;
-          hipLaunchKernelGGL((lstm_bwd_step_skinny_kernel<8, 4>), dim3(tm * tn), dim3(512), 0, st, p, e, tm, tn);
-        } else {
-          // ring depth per wave / waves per workgroup (LDS = waves x depth x 8 KiB; the partial tiles alias the rings).  Two stages = 64 KiB:
-          // ALONE the step is a little slower than with four (one stage in flight per wave instead of three), but in the training step
-          // these launches run next to the other towers' / the optimizer's workgroups, and a 64 KiB workgroup finds room on a CU that a
-          // 146 KiB one has to wait for: 10.37 -> 10.15-10.23 ms per step (same box, alternating runs; three stages: no change)
-          static const int stg = getenv("EVC_SKINNY_STAGES") ? atoi(getenv("EVC_SKINNY_STAGES")) : 2;
-          p.nk1 = k1 / 64;
-#define EVC_SKINNY_LAUNCH(KW_, STG_)                                                                                              \
-  do {                                                                                                                          \
-    allow_big_lds((const void*)lstm_bwd_step_skinny_lds_kernel<KW_, STG_>, KW_ * STG_ * 8192);                                  \
-    hipLaunchKernelGGL((lstm_bwd_step_skinny_lds_kernel<KW_, STG_>), dim3(tm * tn), dim3(64 * KW_), KW_ * STG_ * 8192, st, p, e, tm, tn); \
-  } while (0)
-          if (stg == 3) EVC_SKINNY_LAUNCH(4, 3);           // (four waves: the tail's thread -> (row, unit) map is written for 256 threads)
-          else if (stg == 4) EVC_SKINNY_LAUNCH(4, 4);
-          else EVC_SKINNY_LAUNCH(4, 2);
-#undef EVC_SKINNY_LAUNCH
-        }
+        // ring depth per wave / waves per workgroup (LDS = waves x depth x 8 KiB; the partial tiles alias the rings).  Two stages = 64 KiB:
+        // ALONE the step is a little slower than with four (one stage in flight per wave instead of three), but in the training step
+        // these launches run next to the other towers' / the optimizer's workgroups, and a 64 KiB workgroup finds room on a CU that a
+        // 146 KiB one has to wait for: 10.37 -> 10.15-10.23 ms per step (same box, alternating runs; three stages: no change)
+        // (four waves: the tail's thread -> (row, unit) map is written for 256 threads)
+        constexpr int KW = 4, STG = 2, LDS = KW * STG * 8192;
+        p.nk1 = k1 / 64;
+        allow_big_lds((const void*)lstm_bwd_step_skinny_lds_kernel<KW, STG>, LDS);
+        hipLaunchKernelGGL((lstm_bwd_step_skinny_lds_kernel<KW, STG>), dim3(tm * tn), dim3(64 * KW), LDS, st, p, e, tm, tn);
         break;
       }
       default: launch_lstm_bwd<CfgPlainSmall>(p, e, k1, st); break;

@@ -52,13 +52,6 @@ __device__ __forceinline__ void lstm_fwd_acc_bias(const LstmFwdParams& e, const 
 template <class Cfg, bool SPLIT, bool F16, bool FP8>
 __device__ __forceinline__ void lstm_fwd_epilogue(const GemmOperands& p, const LstmFwdParams& e, const int m0, const int u0,
                                                   f32x4 (&acc)[Cfg::MI][4][Cfg::NI]) {
-#ifdef EVC_ABLATE_EPI    // debug build: main loop only (keep the accumulators alive, store nothing)
-#pragma unroll
-  for (int mi = 0; mi < Cfg::MI; ++mi)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) asm volatile("" :: "v"(acc[mi][g][0]));
-  return;
-#endif
   TileCoordsT<Cfg> tc;
   const int H = e.H;     // H % 4 == 0 (checked on the host): a lane's 4 units never straddle H
   // Every load of the tail is issued before the first store: the stores of one fragment and the loads of the next
@@ -83,9 +76,9 @@ __device__ __forceinline__ void lstm_fwd_epilogue(const GemmOperands& p, const L
       cv[mi] = make_float4(0.f, 0.f, 0.f, 0.f);        // zero initial state (no memset of the state buffers)
       if (e.t > 0 && e.t < ln[mi]) cv[mi] = *(const float4*)(e.c_state + (long)rm[mi] * e.ld_state + u);   // running f32 cell state, in place
     }
-    // stores: uniform base + 32-bit lane byte offset (a time slab is far below 4 GiB: checked by the launchers), policy EVC_FWD_STORE_POLICY
-    constexpr int SP = EVC_FWD_STORE_POLICY;
-    constexpr int TP = EVC_FWD_TAPE_POLICY;           // the write-once tapes of the backward pass (gate records, bf16 cell history) on their own policy
+    // stores: uniform base + 32-bit lane byte offset (a time slab is far below 4 GiB: checked by the launchers), plain cache policy (evc_common.h store16<>) -
+    // also for the write-once tapes of the backward pass (gate records, bf16 cell history)
+    constexpr int SP = 0, TP = 0;
 #pragma unroll
     for (int mi = 0; mi < Cfg::MI; ++mi) {
       const int m = m0 + tc.row0 + mi * 16;
@@ -211,7 +204,7 @@ __device__ __forceinline__ void lstm_fwd_step_body(const GemmOperands& p, const 
   //  itself is the plain one; only the epilogue differs: it writes h_t's wide [lo | hi] image for the next step.)
   // (XINT, round 6: e.bias holds (255/256) colsum(f16(Wx)) here - the accumulators start from the constant term of the dequantised frames - and the
   //  loop rescales them by the frame's factor and adds the true bias behind the x-part: LOOP_ROW_SCALE)
-  run_mainloop<Cfg, 4, true, false, EVC_FWD_LOOP_MODE | (F16 ? LOOP_F16 : 0) | (FP8 ? LOOP_FP8_TAIL : 0) | (XINT ? LOOP_ROW_SCALE : 0)>(p, m0, u0, acc);   // transposed accumulators: lane = one row, 4 consecutive units
+  run_mainloop<Cfg, 4, true, false, FWD_LOOP_MODE | (F16 ? LOOP_F16 : 0) | (FP8 ? LOOP_FP8_TAIL : 0) | (XINT ? LOOP_ROW_SCALE : 0)>(p, m0, u0, acc);   // transposed accumulators: lane = one row, 4 consecutive units
   EVC_STAMP(p.stamp_slot, 2);
   lstm_fwd_epilogue<Cfg, SPLIT, F16, FP8>(p, e, m0, u0, acc);
 }
@@ -228,8 +221,8 @@ __global__ __launch_bounds__(Cfg::NT) void lstm_fwd_walk2_kernel(GemmOperands pa
   static_assert(is_v3<Cfg>::value && Cfg::G == 4, "tile walk: the 64-wide ring tiles");
   static_assert((!FP8 && !FP8B) || F16, "the e4m3 tail rides behind f16 stages");
   static_assert(!XINT || FP8, "the integer-frame form rides on the f16 + e4m3 loop");
-  constexpr int MODE_A = EVC_FWD_LOOP_MODE | (F16 ? LOOP_F16 : 0) | (FP8 ? LOOP_FP8_TAIL : 0) | (XINT ? LOOP_ROW_SCALE : 0);
-  constexpr int MODE_B = EVC_FWD_LOOP_MODE | (F16 ? LOOP_F16 : 0) | (FP8B ? LOOP_FP8_TAIL : 0);
+  constexpr int MODE_A = FWD_LOOP_MODE | (F16 ? LOOP_F16 : 0) | (FP8 ? LOOP_FP8_TAIL : 0) | (XINT ? LOOP_ROW_SCALE : 0);
+  constexpr int MODE_B = FWD_LOOP_MODE | (F16 ? LOOP_F16 : 0) | (FP8B ? LOOP_FP8_TAIL : 0);
   const int tiles_m = tiles_ma > tiles_mb ? tiles_ma : tiles_mb;
   const int id = xcd_remap(blockIdx.x, tiles_m * tiles_n);
   int tm, tn;
@@ -306,8 +299,7 @@ typedef TileCfg2<192, 4, 64, 2, 4, 5, true> CfgLstmV2_192;
 typedef TileCfg2<160, 4, 64, 2, 4, 5, true> CfgLstmV2_160;
 typedef TileCfg2<128, 4, 64, 2, 4, 5, true> CfgLstmV2_128;
 typedef TileCfg2<64, 4, 64, 2, 4, 5, true> CfgLstmV2_64;
-typedef TileCfg2<64, 4, 16, 4, 1, 5, true> CfgLstmV2Small;
-typedef TileCfg3<64, 4, 16, 4, 1, 4> CfgLstmV3Small;         // the same tile on 64-wide K stages (64 KB of LDS: still two workgroups per CU)   // 64 rows x 16 units x 4 gates on the ring loop, 4 waves, 40 KB: M ~ batch steps
+typedef TileCfg3<64, 4, 16, 4, 1, 4> CfgLstmV3Small;         // 64 rows x 16 units x 4 gates on 64-wide K stages, 4 waves (64 KB of LDS: still two workgroups per CU): M ~ batch steps
 
 template <class Cfg, bool SPLIT = false, bool F16 = false, bool FP8 = false, bool XINT = false>
 static inline void launch_lstm_fwd(GemmOperands p, const LstmFwdParams& e, int k1, int k2, hipStream_t st) {
@@ -326,11 +318,9 @@ static inline int pick_fwd_tile(int rows, int H) {
   static const int bn[NC] = {256, 256, 256, 256, 256, 256, 128, 64, 256, 256, 256};
   static const int bu[NC] = {64, 64, 64, 64, 64, 64, 32, 16, 64, 64, 64};
   static const double cf[NC] = {1.0, 1.0, 1.0, 1.02, 1.04, 1.08, 1.3, 2.6, 1.15, 1.5, 1.01};   // smaller tiles: less efficient per flop
-  static const bool no240 = getenv("EVC_FWD_NO_240") != nullptr;      // A/B: the tile set of round 3
   int best = 0;
   double bc = 1e300;
   for (int i = 0; i < NC; ++i) {
-    if (i == 10 && no240) continue;
     const double c = tile_cost((long)ceil_div(rows, bm[i]) * ceil_div(H, bu[i]), bm[i], bn[i], 1, cf[i]);
     if (c < bc) { bc = c; best = i; }
   }
@@ -341,16 +331,14 @@ static inline int pick_fwd_tile(int rows, int H) {
 
 // one bf16 forward step on the tile the cost model picks for Mt rows
 static inline void launch_fwd_step_bf16(const GemmOperands& p, const LstmFwdParams& e, int k1, int k2, int Mt, int H, hipStream_t st) {
-  static const bool uneven224 = getenv("EVC_FWD_EVEN_224") == nullptr;      // the 224-row tile as 6 + 8 row fragments (A/B switch: 7 + 7; 58.3 -> 58.0 us per launch)
-  static const bool fwd_v2 = getenv("EVC_FWD_V2_LOOP") != nullptr;          // A/B: the 32-wide K stages for the 160-256-row tiles
   switch (pick_fwd_tile(Mt, H)) {
     case 0: launch_lstm_fwd<CfgLstmV2a>(p, e, k1, k2, st); break;
     case 1: launch_lstm_fwd<CfgLstmV2_288>(p, e, k1, k2, st); break;
-    case 2: if (fwd_v2) launch_lstm_fwd<CfgLstmV2b>(p, e, k1, k2, st); else launch_lstm_fwd<CfgLstmV3_256>(p, e, k1, k2, st); break;
-    case 3: if (fwd_v2) launch_lstm_fwd<CfgLstmV2_224>(p, e, k1, k2, st); else if (uneven224) launch_lstm_fwd<CfgLstmV3_224u>(p, e, k1, k2, st); else launch_lstm_fwd<CfgLstmV3_224>(p, e, k1, k2, st); break;
+    case 2: launch_lstm_fwd<CfgLstmV3_256>(p, e, k1, k2, st); break;
+    case 3: launch_lstm_fwd<CfgLstmV3_224u>(p, e, k1, k2, st); break;     // 6 + 8 row fragments (7 + 7: 58.3 -> 58.0 us per launch)
     case 10: launch_lstm_fwd<CfgLstmV3_240>(p, e, k1, k2, st); break;
-    case 4: if (fwd_v2) launch_lstm_fwd<CfgLstmV2_192>(p, e, k1, k2, st); else launch_lstm_fwd<CfgLstmV3_192>(p, e, k1, k2, st); break;
-    case 5: if (fwd_v2) launch_lstm_fwd<CfgLstmV2_160>(p, e, k1, k2, st); else launch_lstm_fwd<CfgLstmV3_160>(p, e, k1, k2, st); break;
+    case 4: launch_lstm_fwd<CfgLstmV3_192>(p, e, k1, k2, st); break;
+    case 5: launch_lstm_fwd<CfgLstmV3_160>(p, e, k1, k2, st); break;
     case 6: launch_lstm_fwd<CfgLstmBig>(p, e, k1, k2, st); break;
     case 8: launch_lstm_fwd<CfgLstmV2_128>(p, e, k1, k2, st); break;
     case 9: launch_lstm_fwd<CfgLstmV2_64>(p, e, k1, k2, st); break;
@@ -451,13 +439,12 @@ static int lstm_layer_fwd_impl(const evc_bf16* x, const evc_bf16* wT, const floa
     e.c_hist = c_all ? c_all + (long)(t + 1) * M * H : nullptr;      // slab t+1 = c after step t
     e.row_map = row_map;
     e.M = Mt; e.H = H;
-    static const bool uneven224 = getenv("EVC_FWD_EVEN_224") == nullptr;      // the 224-row tile as 6 + 8 row fragments (A/B switch: 7 + 7; 58.3 -> 58.0 us per launch)
     if (f16) {        // IEEE f16 operands, one MFMA product per depth: the tiles of the bf16 step
       switch (pick_fwd_tile(Mt, H)) {
         case 0: launch_lstm_fwd<CfgLstmV2a, false, true>(p, e, k1, k2, st); break;
         case 1: launch_lstm_fwd<CfgLstmV2_288, false, true>(p, e, k1, k2, st); break;
         case 2: launch_lstm_fwd<CfgLstmV3_256, false, true>(p, e, k1, k2, st); break;
-        case 3: if (uneven224) launch_lstm_fwd<CfgLstmV3_224u, false, true>(p, e, k1, k2, st); else launch_lstm_fwd<CfgLstmV3_224, false, true>(p, e, k1, k2, st); break;
+        case 3: launch_lstm_fwd<CfgLstmV3_224u, false, true>(p, e, k1, k2, st); break;
         case 10: launch_lstm_fwd<CfgLstmV3_240, false, true>(p, e, k1, k2, st); break;
         case 4: launch_lstm_fwd<CfgLstmV3_192, false, true>(p, e, k1, k2, st); break;
         case 5: launch_lstm_fwd<CfgLstmV3_160, false, true>(p, e, k1, k2, st); break;
@@ -519,7 +506,6 @@ extern "C" int evc_lstm_level2_fwd(const evc_bf16* x, const evc_bf16* wT0, const
   hipStream_t st = (hipStream_t)stream;
   EVC_CHECK_HIP(hipMemsetAsync(hbuf0, 0, (size_t)M * H * sizeof(bf16_t), st));       // h_{-1} = 0, both layers
   EVC_CHECK_HIP(hipMemsetAsync(hbuf1, 0, (size_t)M * H * sizeof(bf16_t), st));
-  static const bool uneven224 = getenv("EVC_FWD_EVEN_224") == nullptr;
   auto step_args = [&](int layer, int t, GemmOperands& p, LstmFwdParams& e, int& k1, int& k2) {
     const int kin = layer ? H : Kin;
     const evc_bf16* xin = layer ? hbuf0 + (long)(t + 1) * M * H : x + (long)t * M * Kin;        // layer 1's x_t = layer 0's output slab t+1
@@ -555,11 +541,7 @@ extern "C" int evc_lstm_level2_fwd(const evc_bf16* x, const evc_bf16* wT0, const
       if (!has_b) { pb = pa; eb = ea; }
       if (pick == 2) { launch_lstm_fwd_walk2<CfgLstmV3_256>(pa, ea, k1a, k2a, has_a, pb, eb, k1b, k2b, has_b, st); continue; }
       if (pick == 10) { launch_lstm_fwd_walk2<CfgLstmV3_240>(pa, ea, k1a, k2a, has_a, pb, eb, k1b, k2b, has_b, st); continue; }
-      if (pick == 3) {
-        if (uneven224) launch_lstm_fwd_walk2<CfgLstmV3_224u>(pa, ea, k1a, k2a, has_a, pb, eb, k1b, k2b, has_b, st);
-        else launch_lstm_fwd_walk2<CfgLstmV3_224>(pa, ea, k1a, k2a, has_a, pb, eb, k1b, k2b, has_b, st);
-        continue;
-      }
+      if (pick == 3) { launch_lstm_fwd_walk2<CfgLstmV3_224u>(pa, ea, k1a, k2a, has_a, pb, eb, k1b, k2b, has_b, st); continue; }
     }
     if (has_a) launch_fwd_step_bf16(pa, ea, k1a, k2a, ea.M, H, st);
     if (has_b) launch_fwd_step_bf16(pb, eb, k1b, k2b, eb.M, H, st);
@@ -572,10 +554,9 @@ extern "C" int evc_lstm_level2_fwd(const evc_bf16* x, const evc_bf16* wT0, const
 static inline int pick_fwd_tile_v3(int rows, int H) {
   static const int bm[5] = {256, 224, 192, 160, 240};
   static const double cf[5] = {1.0, 1.02, 1.04, 1.08, 1.01};
-  static const bool no240 = getenv("EVC_FWD_NO_240") != nullptr;
   int best = 0;
   double bc = 1e300;
-  for (int i = 0; i < (no240 ? 4 : 5); ++i) {
+  for (int i = 0; i < 5; ++i) {
     const double c = tile_cost((long)ceil_div(rows, bm[i]) * ceil_div(H, 64), bm[i], 256, 1, cf[i]);
     if (c < bc) { bc = c; best = i; }
   }
@@ -867,7 +848,6 @@ extern "C" int evc_lstm_level2_fwd_high(const evc_f16* x, int64_t ldx, int kx16,
     e.row_map = row_map;
     e.M = p.M; e.H = H;
   };
-  static const bool uneven224 = getenv("EVC_FWD_EVEN_224") == nullptr;
   for (int s = 0; s <= T; ++s) {
     GemmOperands pa, pb;
     LstmFwdParams ea, eb;
@@ -887,8 +867,7 @@ extern "C" int evc_lstm_level2_fwd_high(const evc_f16* x, int64_t ldx, int kx16,
       } while (0)
       if (pick == 0) EVC_WALK2_HIGH(CfgLstmV3_256);
       else if (pick == 4) EVC_WALK2_HIGH(CfgLstmV3_240);
-      else if (uneven224) EVC_WALK2_HIGH(CfgLstmV3_224u);
-      else EVC_WALK2_HIGH(CfgLstmV3_224);
+      else EVC_WALK2_HIGH(CfgLstmV3_224u);
 #undef EVC_WALK2_HIGH
       continue;
     }
@@ -1040,8 +1019,6 @@ extern "C" int evc_lstm_stack2_fwd(const evc_bf16* x, const evc_bf16* wT0, const
     if (has_b) fwd_step_args(L1, len, s - 1, M, H, ld_state, pb, eb, k1b, k2b);
     if (has_a && has_b && (tile == 6 || tile == 7)) {
       if (tile == 6) launch_lstm_fwd_pair<CfgLstmBig>(pa, ea, k1a, k2a, pb, eb, k1b, k2b, st);
-      else if (getenv("EVC_PAIR_V1")) launch_lstm_fwd_pair<CfgLstmSmall>(pa, ea, k1a, k2a, pb, eb, k1b, k2b, st);
-      else if (getenv("EVC_PAIR_V2")) launch_lstm_fwd_pair<CfgLstmV2Small>(pa, ea, k1a, k2a, pb, eb, k1b, k2b, st);
       else launch_lstm_fwd_pair<CfgLstmV3Small>(pa, ea, k1a, k2a, pb, eb, k1b, k2b, st);
       continue;
     }

@@ -21,13 +21,8 @@
 #include "gemm_core_v2.h"
 
 typedef __attribute__((ext_vector_type(4))) short s16x4;
-#ifndef EVC_TN_AUX_A
-#define EVC_TN_AUX_A 0      // cache policy of the LDS-DMA loads (2 = nt).  Measured: nt on A +2.5 % in a replayed
-                            // microbenchmark, -1.2 % in the training step (dz is fresh in the caches there); nt on B -5 %
-#endif
-#ifndef EVC_TN_AUX_B
-#define EVC_TN_AUX_B 0
-#endif
+// (cache policy of the LDS-DMA loads: plain.  Measured: nt on A +2.5 % in a replayed microbenchmark, -1.2 % in the training step -
+//  dz is fresh in the caches there; nt on B -5 %)
 
 struct GemmOperandsT {
   const bf16_t* A; long lda;   // [K][lda], m contiguous
@@ -141,11 +136,11 @@ __device__ __forceinline__ void gemm_mainloop_tn(const GemmOperandsT& p, const i
 #pragma unroll
     for (int i = 0; i < ACH; ++i)
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a_base + (a_vo[i] + a_k)),
-                                       (__attribute__((address_space(3))) void*)(sbase + ((wave % NPW) + i * NPW) * 1024), 16, 0, EVC_TN_AUX_A);
+                                       (__attribute__((address_space(3))) void*)(sbase + ((wave % NPW) + i * NPW) * 1024), 16, 0, 0);
 #pragma unroll
     for (int i = 0; i < BCH; ++i)
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(b_base + (b_vo[i] + b_k)),
-                                       (__attribute__((address_space(3))) void*)(sbase + Cfg::A_BYTES + ((wave % NPW) + i * NPW) * 1024), 16, 0, EVC_TN_AUX_B);
+                                       (__attribute__((address_space(3))) void*)(sbase + Cfg::A_BYTES + ((wave % NPW) + i * NPW) * 1024), 16, 0, 0);
     advance();
     slot_issue = (slot_issue + 1 == Cfg::STAGES) ? 0 : slot_issue + 1;
   };
@@ -172,14 +167,10 @@ __device__ __forceinline__ void gemm_mainloop_tn(const GemmOperandsT& p, const i
   // DMA it had just issued (the whole ring's latency hiding gone; found in the ISA in round 2).  The asm has no memory
   // operand; its result is retired by the explicit lgkmcnt(0) of end_of_step() before the next step's MFMAs read it.
   auto tr = [&](const char* ptr) {
-#ifdef EVC_TN_TR_BUILTIN
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)ptr);
-#else
     const uint32_t a = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) const char*)ptr);
     s16x4 v;
     asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(a));
     return v;
-#endif
   };
   auto read_frags = [&](bf16x8 (&af)[Cfg::MI], bf16x8 (&bfr)[Cfg::NI]) {
     const char* sb = lds + slot_read * Cfg::STAGE_BYTES;
@@ -234,32 +225,21 @@ __device__ __forceinline__ void gemm_mainloop_tn(const GemmOperandsT& p, const i
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     if constexpr ((MODE & LOOP_NO_PRIO) == 0) __builtin_amdgcn_s_setprio(1);
-#ifdef EVC_TN_UNORDERED
-    stage_role();
-    read_frags(afn, bfn);
-    mfma_all(afc, bfc);
-#else
-    // EVC_TN_STAGGER (experiment): the waves that issue no LDS-DMA start their fragment reads SKIP MFMA groups into the step (the producers'
-    // reads come behind their LDS-DMA pieces anyway), so that the SIMD partners' LDS reads do not run in step
-#ifndef EVC_TN_STAGGER
-#define EVC_TN_STAGGER 0
-#endif
     constexpr int NM = Cfg::MI * Cfg::NI, ND = PROD ? PER : 0, NF = Cfg::MI + Cfg::NI, NIT = ND + NF;
-    constexpr int SKIP = (PRODUCERS && !PROD && EVC_TN_STAGGER < NM - NIT) ? EVC_TN_STAGGER : 0;
     char* sbase = lds + slot_issue * Cfg::STAGE_BYTES;
     const char* sb = lds + slot_read * Cfg::STAGE_BYTES;
     slot_read = (slot_read + 1 == Cfg::STAGES) ? 0 : slot_read + 1;
 #pragma unroll
     for (int gi = 0; gi < NM; ++gi) {
 #pragma unroll
-      for (int it = (gi < SKIP ? 0 : (gi - SKIP) * NIT / (NM - SKIP)); it < (gi < SKIP ? 0 : (gi - SKIP + 1) * NIT / (NM - SKIP)); ++it) {   // items of this group: LDS-DMA pieces first, then fragments
+      for (int it = gi * NIT / NM; it < (gi + 1) * NIT / NM; ++it) {   // items of this group: LDS-DMA pieces first, then fragments
         if (it < ND) {
           if (it < ACH)
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a_base + (a_vo[it] + a_k)),
-                                             (__attribute__((address_space(3))) void*)(sbase + ((wave % NPW) + it * NPW) * 1024), 16, 0, EVC_TN_AUX_A);
+                                             (__attribute__((address_space(3))) void*)(sbase + ((wave % NPW) + it * NPW) * 1024), 16, 0, 0);
           else
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(b_base + (b_vo[it - ACH] + b_k)),
-                                             (__attribute__((address_space(3))) void*)(sbase + Cfg::A_BYTES + ((wave % NPW) + (it - ACH) * NPW) * 1024), 16, 0, EVC_TN_AUX_B);
+                                             (__attribute__((address_space(3))) void*)(sbase + Cfg::A_BYTES + ((wave % NPW) + (it - ACH) * NPW) * 1024), 16, 0, 0);
         } else if (it - ND < Cfg::NI) {
           const int f = it - ND;
           const s16x4 lo = tr(sb + b_rd[f][0]), hi = tr(sb + b_rd[f][1]);
@@ -279,7 +259,6 @@ __device__ __forceinline__ void gemm_mainloop_tn(const GemmOperandsT& p, const i
       advance();
       slot_issue = (slot_issue + 1 == Cfg::STAGES) ? 0 : slot_issue + 1;
     }
-#endif
     if constexpr ((MODE & LOOP_NO_PRIO) == 0) __builtin_amdgcn_s_setprio(0);
     end_of_step();
   };

@@ -31,10 +31,6 @@
 //  LOOP_FP8_TAIL  (v3 loop only) the 16-bit stages are followed by stages of 128 e4m3 bytes per row on the MX-scaled MFMA
 //                 (GemmOperands::A3 / A4 / B8); needs nk1 + nk2 >= 1 and nk3 + nk4 >= STAGES
 constexpr int LOOP_PRODUCER = 1, LOOP_DMA_FIRST = 2, LOOP_NO_PRIO = 4, LOOP_F16 = 8, LOOP_FP8_TAIL = 16;
-//  LOOP_PREFETCH  (v3 loop with LOOP_PRODUCER, experiment of round 4) two of the waves that issue no LDS-DMA touch, per trip, one dword of every 128-byte
-//                 line of this workgroup's SHARE of the operand panels of a stage a few trips ahead (a 4-byte LDS-DMA into the sink: no destination
-//                 register), so that the producers' refill of that stage finds its lines in the XCD's L2 instead of waiting for the Infinity Cache / HBM
-constexpr int LOOP_PREFETCH = 32;
 //  LOOP_B_NT      (v3 loop) the B operand's LDS-DMA loads are non-temporal: for products whose B rows are read by ONE workgroup each (the batch-row
 //                 products, M <= 256: one row tile) - the weight matrix streams through the chip once and should not evict what the others re-read
 constexpr int LOOP_B_NT = 64;
@@ -42,9 +38,7 @@ constexpr int LOOP_B_NT = 64;
 // rescaled per ROW and offset per COLUMN - acc = acc * row_scale[row] + col_add[column] (GemmOperands) - the integer-frame form of an L1 layer's
 // step (round 6): the A1 segment contracts exact integers, the row scale is the frame's dequantise / l2-normalise factor.
 constexpr int LOOP_ROW_SCALE = 128;
-#ifndef EVC_LOOP_MODE_DEFAULT
-#define EVC_LOOP_MODE_DEFAULT 0
-#endif
+constexpr int LOOP_MODE_DEFAULT = 0;
 
 template <int BM_, int G_, int BU_, int WR_, int WC_, int STAGES_ = 5, bool PIPE_ = true>
 struct TileCfg2 {
@@ -71,7 +65,7 @@ __device__ __forceinline__ void wait_vmcnt() {     // (the counter has 6 bits: a
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N > 63 ? 63 : N) : "memory");
 }
 
-template <class Cfg, bool SWAP = false, bool INIT = true, int MODE = EVC_LOOP_MODE_DEFAULT>
+template <class Cfg, bool SWAP = false, bool INIT = true, int MODE = LOOP_MODE_DEFAULT>
 __device__ __forceinline__ void gemm_mainloop_v2(const GemmOperands& p, const int m0, const int u0, char* lds,
                                                  f32x4 (&acc)[Cfg::MI][Cfg::G][Cfg::NI]) {
   const int tid = threadIdx.x;
@@ -266,9 +260,7 @@ __device__ __forceinline__ void gemm_mainloop_v2(const GemmOperands& p, const in
       stage_role();                   // refill step kt-1's slot with step kt+STAGES-1
       read_frags(afn, bfn);
       mfma_all(afc, bfc);
-#ifndef EVC_NO_INTERLEAVE
       interleave_pipe();
-#endif
       if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);
       end_of_step();
     };
@@ -314,7 +306,6 @@ __device__ __forceinline__ void gemm_mainloop_v2(const GemmOperands& p, const in
       read_frags(af, bfr);
       stage_role();
       mfma_all(af, bfr);
-#ifndef EVC_NO_INTERLEAVE
       // B fragments + the first A fragment up front, then one MFMA row per further A read, LDS-DMA last
       __builtin_amdgcn_sched_group_barrier(0x100, Cfg::G * Cfg::NI + 1, 0);
 #pragma unroll
@@ -324,7 +315,6 @@ __device__ __forceinline__ void gemm_mainloop_v2(const GemmOperands& p, const in
         if (i < PERX) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
       }
       __builtin_amdgcn_sched_group_barrier(0x008, Cfg::G * Cfg::NI, 0);
-#endif
       if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);
       end_of_step();
     }

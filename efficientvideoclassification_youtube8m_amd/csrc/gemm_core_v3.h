@@ -25,12 +25,6 @@
 #pragma once
 #include "gemm_core_v2.h"
 
-#ifndef EVC_V3_AUX_A
-#define EVC_V3_AUX_A 0      // cache policy of the ring's LDS-DMA loads (2 = nt), A / B operand: measured in round 4 (dropped), default policy kept
-#endif
-#ifndef EVC_V3_AUX_B
-#define EVC_V3_AUX_B 0
-#endif
 #ifdef EVC_STAMPS      // diagnostic build (scripts/fwd_stamps.py): s_memrealtime (100 MHz) marks per workgroup, read back through evc_debug_read_stamps
 static __device__ unsigned long long evc_stamps[8][512][8];       // [GemmOperands::stamp_slot][workgroup][mark]
 #define EVC_STAMP(slot, k) do { if (threadIdx.x == 0 && blockIdx.x < 512) evc_stamps[(slot) & 7][blockIdx.x][k] = __builtin_amdgcn_s_memrealtime(); } while (0)
@@ -57,12 +51,7 @@ struct TileCfg3 {
   static constexpr int A_BYTES = BM * 128, B_BYTES = BN * 128, STAGE_BYTES = A_BYTES + B_BYTES;
   static constexpr bool RAGGED = (BM / 8) % (NT / 64) != 0 || (BN / 8) % (NT / 64) != 0 || (BM / 8) % 4 != 0 || (BN / 8) % 4 != 0;
   static constexpr int DUMMY_OFF = STAGES * STAGE_BYTES;       // 1 KiB sink for the surplus lanes of a ragged last round
-#ifdef EVC_V3_PREFETCH_SINK
-  static constexpr bool SINK = RAGGED || DUMMY_OFF + 1024 <= 160 * 1024;     // (LOOP_PREFETCH builds: the sink also takes the prefetch dwords)
-#else
-  static constexpr bool SINK = RAGGED;
-#endif
-  static constexpr int LDS_BYTES = DUMMY_OFF + (SINK ? 1024 : 0);
+  static constexpr int LDS_BYTES = DUMMY_OFF + (RAGGED ? 1024 : 0);
   static_assert((UNEVEN || BM % (16 * WR) == 0) && WU % 16 == 0 && BM % 8 == 0 && BN % 8 == 0, "wave tile must be a multiple of 16x16");
   static_assert(STAGES >= 2 && STAGES <= 6, "ring depth 2..6");
   static_assert(LDS_BYTES <= 160 * 1024, "exceeds the 160 KiB LDS of a CU");
@@ -73,7 +62,7 @@ struct TileCfg3 {
 // (a barrier), so that the ring fills under the current tile's epilogue; 2 = the loop for a tile whose first stages were issued by a
 // PHASE-1 call (same p, m0, u0): nothing is issued in the prologue and the first wait is vmcnt(0) - the wave's epilogue stores were
 // issued after those stages and a counted wait would count them instead.
-template <class Cfg, bool SWAP = false, bool INIT = true, int MODE = EVC_LOOP_MODE_DEFAULT, int PHASE = 0>
+template <class Cfg, bool SWAP = false, bool INIT = true, int MODE = LOOP_MODE_DEFAULT, int PHASE = 0>
 __device__ __forceinline__ void gemm_mainloop_v3(const GemmOperands& p, const int m0, const int u0, char* lds,
                                                  f32x4 (&acc)[Cfg::MI][Cfg::G][Cfg::NI]) {
   const int tid = threadIdx.x;
@@ -137,7 +126,7 @@ __device__ __forceinline__ void gemm_mainloop_v3(const GemmOperands& p, const in
     uint32_t lda_b = (uint32_t)(s1 ? p.lda1 : p.lda2) * 2u;
     const char* b_base = (const char*)((s1 ? p.B : b2) + (long)ks_issue * 64);
     uint32_t ldb_b = (uint32_t)p.ldb * 2u;
-    uint32_t chunk_b = (uint32_t)(lc8 * 2);
+    const uint32_t chunk_b = (uint32_t)(lc8 * 2);
     if constexpr (FP8) {               // stages behind the 16-bit ones: rows of 128 e4m3 bytes
       const int k8 = ks_issue - nkf;
       const bool f = k8 < 0, s3 = k8 < p.nk3;
@@ -146,39 +135,21 @@ __device__ __forceinline__ void gemm_mainloop_v3(const GemmOperands& p, const in
       lda_b = f ? lda_b : (uint32_t)(s3 ? p.lda3 : p.lda4);
       b_base = f ? b_base : (const char*)p.B8 + (long)k8 * 128 + (s3 ? 0 : p.b8_gap);
       ldb_b = f ? ldb_b : (uint32_t)p.ldb8;
-#ifdef EVC_ABLATE_FP6   // TIMING ablation (wrong results): what an e2m3 tail could cost - the e-stages fetch DENSE stage-major rows of 96 bytes
-      // (lanes 6, 7 of a row repeat chunk 5: 96 of the 128 bytes per row come from memory) and the MFMAs run in the FP6 formats
-      ab = f ? ab : (s3 ? (const char*)p.A3 + (long)k8 * p.M * 96 : (const char*)p.A4 + (long)(k8 - p.nk3) * p.M * 96);
-      lda_b = f ? lda_b : 96u;
-      b_base = f ? b_base : (const char*)p.B8 + (long)k8 * (4 * p.group_stride) * 96;
-      ldb_b = f ? ldb_b : 96u;
-      chunk_b = f ? (uint32_t)(lc8 * 2) : (uint32_t)(min(lc8 / 8, 5) * 16);
-#endif
-#ifdef EVC_ABLATE_E_HOT   // TIMING ablation (wrong results): every row of an e-stage fetches row 0's bytes - L2-hot lines, the same LDS-DMA count
-      lda_b = f ? lda_b : 0u;
-      ldb_b = f ? ldb_b : 0u;
-#endif
     }
-#ifdef EVC_ABLATE_E_NOA   // TIMING ablation (wrong results): the e-stages issue their B pieces only (half the LDS-DMA instructions)
-    const bool skip_a = FP8 && ks_issue >= nkf;
-#else
-    constexpr bool skip_a = false;
-#endif
     char* sbase = lds + slot_issue * Cfg::STAGE_BYTES;
 #pragma unroll
     for (int i = 0; i < ACH; ++i) {
-      if (skip_a) break;
       char* dst = a_dst[i] >= 0 ? sbase + a_dst[i] : lds + Cfg::DUMMY_OFF;
       const uint32_t vo = __umul24((uint32_t)a_row[i], lda_b) + chunk_b;
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(ab + vo),
-                                       (__attribute__((address_space(3))) void*)dst, 16, 0, EVC_V3_AUX_A);
+                                       (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
     }
 #pragma unroll
     for (int i = 0; i < BCH; ++i) {
       char* dst = b_dst[i] >= 0 ? sbase + b_dst[i] : lds + Cfg::DUMMY_OFF;
       const uint32_t vo = FP8 ? __umul24(b_vo[i], ldb_b) + chunk_b : b_vo[i];
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(b_base + vo),
-                                       (__attribute__((address_space(3))) void*)dst, 16, 0, (MODE & LOOP_B_NT) ? 2 : EVC_V3_AUX_B);
+                                       (__attribute__((address_space(3))) void*)dst, 16, 0, (MODE & LOOP_B_NT) ? 2 : 0);
     }
     ++ks_issue;
     slot_issue = (slot_issue + 1 == Cfg::STAGES) ? 0 : slot_issue + 1;
@@ -232,50 +203,6 @@ __device__ __forceinline__ void gemm_mainloop_v3(const GemmOperands& p, const in
     else wait_vmcnt<0>();
   };
 
-  // ---- LOOP_PREFETCH: which lines this wave touches ahead of the ring.  Within an XCD's patch of tiles (tile_of: 8 row tiles x ~4 column
-  // tiles) an A row panel is shared by the column tiles, a B column panel by the row tiles: the workgroup with tn % 4 == q takes quarter q of its A
-  // rows (wave NPW), the one with tm % 8 == q eighth q of its B rows (wave NPW + 1); a share nobody takes just stays a demand miss.
-#ifndef EVC_PREFETCH_DIST
-#define EVC_PREFETCH_DIST 2
-#endif
-  constexpr bool PREFETCH = (MODE & LOOP_PREFETCH) != 0 && PRODUCERS && Cfg::SINK && !FP8;
-  long pf_off1 = -1, pf_off2 = -1;       // byte offset of this lane's row in the A1 / A2 segment (wave NPW) or in B (wave NPW + 1); -1: no duty
-  if constexpr (PREFETCH) {
-    const int tm_ = m0 / Cfg::BM, tn_ = u0 / Cfg::BU;
-    if (wave == NPW) {
-      constexpr int QA = (Cfg::BM / 4 + 7) / 8 * 8;
-      const int r = (tn_ & 3) * QA + lane;
-      if (lane < QA && r < Cfg::BM) {
-        int gr = m0 + r;
-        gr = gr < p.M ? gr : p.M - 1;
-        pf_off1 = (long)gr * p.lda1 * 2;
-        pf_off2 = (long)gr * p.lda2 * 2;
-      }
-    } else if (wave == NPW + 1) {
-      constexpr int QB = Cfg::BN / 8;
-      const int r = (tm_ & 7) * QB + lane;
-      if (lane < QB) {
-        const int g = r / Cfg::BU, u = r % Cfg::BU;
-        int gu = u0 + u;
-        gu = gu < p.Nu ? gu : p.Nu - 1;
-        pf_off1 = pf_off2 = ((long)g * p.group_stride + gu) * p.ldb * 2;
-      }
-    }
-  }
-  auto prefetch = [&](int ks) {          // one dword of every line of stage ks (wave-uniform ks; lanes without a duty are masked)
-    if constexpr (PREFETCH) {
-      if (ks < nkf && wave <= NPW + 1) {
-        const bool s1 = ks < p.nk1;
-        const char* base = wave == NPW ? (const char*)(s1 ? p.A1 + (long)ks * 64 : p.A2 + (long)(ks - p.nk1) * 64)
-                                       : (const char*)((s1 ? p.B : b2) + (long)ks * 64);
-        const long off = s1 ? pf_off1 : pf_off2;
-        if (off >= 0)
-          __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(base + off + (lane & 31) * 4),
-                                           (__attribute__((address_space(3))) void*)(lds + Cfg::DUMMY_OFF), 4, 0, 0);
-      }
-    }
-  };
-
   auto run = [&](auto prod_tag) {     // one copy of the loop per role (LOOP_PRODUCER), each steady-state body branch-free
   constexpr bool PROD = decltype(prod_tag)::value;
   constexpr bool PRIO = (MODE & LOOP_NO_PRIO) == 0;
@@ -287,17 +214,9 @@ __device__ __forceinline__ void gemm_mainloop_v3(const GemmOperands& p, const in
   auto stage_role = [&]() {
     if constexpr (PROD) stage();
   };
-  // EVC_STAGGER_LEAD (experiment, MI355X_MICROARCH.md "Two waves per SIMD" item 9 adapted to a loop whose two halves are alike): the waves
-  // that issue no LDS-DMA (4-7: the SIMD partners of the producers) open the first half-step with LEAD bare MFMAs and read their
-  // fragments behind them, so that the partners' LDS read bursts do not start together at the barrier.
-#ifndef EVC_STAGGER_LEAD
-#define EVC_STAGGER_LEAD 0
-#endif
-  auto interleave = [&](auto ndma_tag, auto lead_tag) {   // MFMAs with one LDS read / LDS-DMA between small groups of them
+  auto interleave = [&](auto ndma_tag) {   // MFMAs with one LDS read / LDS-DMA between small groups of them
     constexpr int ndma = decltype(ndma_tag)::value;
-    constexpr int lead = (decltype(lead_tag)::value < NMFMA - (NREAD + ndma)) ? decltype(lead_tag)::value : 0;
-    if constexpr (lead > 0) __builtin_amdgcn_sched_group_barrier(0x008, lead, 0);
-    constexpr int per = (NMFMA - lead) / (NREAD + ndma) > 0 ? (NMFMA - lead) / (NREAD + ndma) : 1;
+    constexpr int per = NMFMA / (NREAD + ndma) > 0 ? NMFMA / (NREAD + ndma) : 1;
     if constexpr ((MODE & LOOP_DMA_FIRST) != 0) {
 #pragma unroll
       for (int i = 0; i < ndma; ++i) {
@@ -317,7 +236,7 @@ __device__ __forceinline__ void gemm_mainloop_v3(const GemmOperands& p, const in
         __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
       }
     }
-    __builtin_amdgcn_sched_group_barrier(0x008, NMFMA - lead - per * (NREAD + ndma), 0);
+    __builtin_amdgcn_sched_group_barrier(0x008, NMFMA - per * (NREAD + ndma), 0);
   };
 
   // ---- prologue: every slot of the ring in flight ----
@@ -347,9 +266,7 @@ __device__ __forceinline__ void gemm_mainloop_v3(const GemmOperands& p, const in
     if constexpr (PRIO) __builtin_amdgcn_s_setprio(1);
     read_half(MIT{}, 1, afB, bfB);
     mfma_all(MIT{}, afA, bfA);
-#ifndef EVC_NO_INTERLEAVE
-    interleave(std::integral_constant<int, 0>{}, std::integral_constant<int, (PRODUCERS && !PROD) ? EVC_STAGGER_LEAD : 0>{});
-#endif
+    interleave(std::integral_constant<int, 0>{});
     if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);
     end_of_step();
     // second half: the next stage must have landed; after the barrier every wave has read all of this stage -> refill its slot
@@ -358,13 +275,10 @@ __device__ __forceinline__ void gemm_mainloop_v3(const GemmOperands& p, const in
     asm volatile("" ::: "memory");
     if constexpr (PRIO) __builtin_amdgcn_s_setprio(1);
     stage_role();
-    if constexpr (!PROD) prefetch(j + Cfg::STAGES + EVC_PREFETCH_DIST);
     next_slot();
     if constexpr (decltype(prefetch_tag)::value) read_half(MIT{}, 0, afA, bfA);
     mfma_all(MIT{}, afB, bfB);
-#ifndef EVC_NO_INTERLEAVE
-    if constexpr (decltype(prefetch_tag)::value) interleave(std::integral_constant<int, PERX>{}, std::integral_constant<int, 0>{});
-#endif
+    if constexpr (decltype(prefetch_tag)::value) interleave(std::integral_constant<int, PERX>{});
     if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);
     end_of_step();
   };
@@ -439,11 +353,7 @@ __device__ __forceinline__ void gemm_mainloop_v3(const GemmOperands& p, const in
       const v4i_t lo = *(const v4i_t*)(sb + base0 + off), hi = *(const v4i_t*)(sb + base1 + off);
       return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
     };
-#ifdef EVC_ABLATE_FP6
-    constexpr int FMT8 = 2;             // e2m3 (timing ablation)
-#else
     constexpr int FMT8 = 0;             // e4m3
-#endif
     auto mfma8 = [&](const v8i_t& a, const v8i_t& b, f32x4& c) {
       c = SWAP ? __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(b, a, c, FMT8, FMT8, 0, sc_first, 0, sc_second)
                : __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, FMT8, FMT8, 0, sc_first, 0, sc_second);
@@ -493,9 +403,7 @@ __device__ __forceinline__ void gemm_mainloop_v3(const GemmOperands& p, const in
     __builtin_amdgcn_s_waitcnt(0xC07F);
     auto half1 = [&]() {
       lower();
-#ifndef EVC_NO_INTERLEAVE
       pattern(std::integral_constant<int, ML * GN>{}, std::integral_constant<int, 2 * MH>{}, I0{});
-#endif
       // hipcc otherwise SINKS these MFMAs below the barrier (their results are first read a trip later): all 32 of a trip then sit
       // behind the barrier, the reads of both halves stand alone in front of an lgkmcnt(0), and the two waves of a SIMD - in step
       // through the barrier - wait for LDS together
@@ -516,9 +424,7 @@ __device__ __forceinline__ void gemm_mainloop_v3(const GemmOperands& p, const in
       next_slot();
       rd_lower();
       upper(std::true_type{});
-#ifndef EVC_NO_INTERLEAVE
       pattern(std::integral_constant<int, MH * GN>{}, std::integral_constant<int, 2 * (ML + GN)>{}, std::integral_constant<int, PERX>{});
-#endif
       end_of_step();
     }
     for (; j + 1 < nk; ++j) {             // last STAGES stages: no refills

@@ -5,23 +5,11 @@
 #include "gemm_launch.h"
 
 // Loop options per kernel (gemm_core_v2.h; same-box A/B measurements in DESIGN.md 4.2)
-#ifndef EVC_FWD_STORE_POLICY
-#define EVC_FWD_STORE_POLICY 0      // cache policy of the forward step's epilogue stores (evc_common.h store16<>): 0 plain, 1 sc1 (write-through), 2 nt
-#endif
-#ifndef EVC_FWD_TAPE_POLICY
-#define EVC_FWD_TAPE_POLICY 0       // ... of its write-once tape stores alone (gate records + cell history: 36 of the 68 MB a teacher L1 launch writes)
-#endif
-#ifndef EVC_FWD_LOOP_MODE
-#define EVC_FWD_LOOP_MODE (LOOP_PRODUCER | LOOP_DMA_FIRST | LOOP_NO_PRIO)   // forward step: 81.7 -> 77.4 us per step
-#endif
-#ifndef EVC_BWD_LOOP_MODE
-#define EVC_BWD_LOOP_MODE (LOOP_PRODUCER | LOOP_DMA_FIRST | LOOP_NO_PRIO)   // BPTT step: 64.8 -> 62.1 us per step on the 32-wide stages without producers; on the 64-wide ones producers give another 56.0 -> 54.1
-#endif
-#ifndef EVC_TN_LOOP_MODE
-#define EVC_TN_LOOP_MODE LOOP_PRODUCER                                      // weight-gradient products: -2 .. -5 %
-#endif
+constexpr int FWD_LOOP_MODE = LOOP_PRODUCER | LOOP_DMA_FIRST | LOOP_NO_PRIO;   // forward step: 81.7 -> 77.4 us per step
+constexpr int BWD_LOOP_MODE = LOOP_PRODUCER | LOOP_DMA_FIRST | LOOP_NO_PRIO;   // BPTT step: 64.8 -> 62.1 us per step on the 32-wide stages without producers; on the 64-wide ones producers give another 56.0 -> 54.1
+constexpr int TN_LOOP_MODE = LOOP_PRODUCER;                                    // weight-gradient products: -2 .. -5 %
 
-template <class Cfg, int NG, bool SWAP = false, bool INIT = true, int MODE = EVC_LOOP_MODE_DEFAULT>
+template <class Cfg, int NG, bool SWAP = false, bool INIT = true, int MODE = LOOP_MODE_DEFAULT>
 __device__ __forceinline__ void run_mainloop(const GemmOperands& p, int m0, int u0, f32x4 (&acc)[Cfg::MI][NG][Cfg::NI]) {
   if constexpr (is_v2<Cfg>::value) {
     if constexpr (is_v3<Cfg>::value) gemm_mainloop_v3<Cfg, SWAP, INIT, MODE>(p, m0, u0, lds_dyn, acc);
@@ -159,10 +147,8 @@ typedef TileCfg<128, 1, 128, 2, 2> CfgPlainBig;   // 128x128, 4 waves, 4x4 MFMA 
 typedef TileCfg<64, 1, 64, 2, 2> CfgPlainSmall;   // 64x64 for skinny problems
 typedef TileCfg<32, 1, 32, 2, 2> CfgPlainTiny;    // 32x32: M ~ batch recurrent steps (256 workgroups at M=256, H=1024)
 typedef TileCfg2<256, 1, 256, 2, 4, 5, true> CfgPlainV2;   // 256x256, 8 waves (2x4), 128x64 per wave, 5-deep ring (160 KiB)
-typedef TileCfg2<224, 1, 256, 2, 4, 5, true> CfgPlainV2_224;   // same, 224 rows: picked when it cuts M into fewer rounds of 256 workgroups
 typedef TileCfg2<320, 1, 256, 2, 4, 4, false> CfgPlainV2_320;  // 320 rows (4-deep ring, single fragment set): 5120 rows = 16 x 16 tiles, ONE round of 256 workgroups instead of 320 tiles
 typedef TileCfg2<128, 1, 128, 2, 4, 5, true> CfgTn128;     // 128x128 v2 tile (80 KB ring: two workgroups per CU)
-typedef TileCfg2<256, 1, 64, 2, 4, 5, true> CfgTallV2;     // 256x64: M <= 256 (batch-row) products against a long weight matrix
 // (256x128 tiles + split-K 2, to halve the re-reads of the [256][K] row operand: 80 vs 61 us at N = 14148 - not the bound)
 
 __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) { return pack_bf16x2_hw(lo, hi); }

@@ -436,9 +436,7 @@ class DistillGraph:
         self.student_forward_early = False
         # True: the student's forward starts when the teacher's L1 level has been enqueued, next to the teacher's L2 chain /
         # MoE head (latency-bound launches).  Measured 13.01 -> 12.88 ms/step with the teacher's L1 steps unaffected.
-        self.student_forward_after_l1 = os.environ.get("EVC_STUDENT_AFTER_L1", "1") == "1"
-        if os.environ.get("EVC_STUDENT_EARLY") is not None:
-            self.student_forward_early = os.environ["EVC_STUDENT_EARLY"] == "1"
+        self.student_forward_after_l1 = True
         # Cross-step deferral (one process): the MoE-head and L2-level updates of step k are enqueued at the start of step k+1,
         # under its L1 forward, instead of under step k's BPTT chain (HLstmTower.backward(defer=True)).  Whoever reads the
         # weights between two steps calls flush() first (state_dict() / consolidate() / apply_gradients() do).
@@ -460,13 +458,12 @@ class DistillGraph:
                 from .streams import cu_masked_stream
                 f = [int(v) for v in m.split(":")]
                 self._opt_t = cu_masked_stream(self.device, f[0], f[1] if len(f) > 1 else 0)
-                self._opt_s = self._opt_t if os.environ.get("EVC_OPT_CU_MASK_SHARED", "1") == "1" else cu_masked_stream(self.device, f[0], f[1] if len(f) > 1 else 0)
+                self._opt_s = self._opt_t          # (both towers' optimizer launches share the masked stream)
             # Single-tower graphs (cfg 2 teacher only, cfg 5 student only) use two of the four streams: the tower's collectives + optimizer launches
             # take a THIRD one (the other tower's idle aux stream) instead of queueing on the aux stream between the weight-gradient products - under
             # data parallelism that stream is the step's critical path and every byte on the wire was exposed (cfg 5 as rank 0 of 8 with stand-in
-            # collectives at 300 GB/s: 5.67 ms; profiles/r06_dp_sim_world.txt).  EVC_OPT_SPARE_STREAM=0 / 1 forces it off / on (default: under DP).
-            spare = os.environ.get("EVC_OPT_SPARE_STREAM")
-            if (spare == "1" or (spare is None and self.dp)) and os.environ.get("EVC_SINGLE_STREAM") != "1" and not m:
+            # collectives at 300 GB/s: 5.67 ms; profiles/r06_dp_sim_world.txt).  Under data parallelism only.
+            if self.dp and os.environ.get("EVC_SINGLE_STREAM") != "1" and not m:
                 if mode == "student":
                     self._opt_s = self._aux_t
                 elif mode == "teacher":

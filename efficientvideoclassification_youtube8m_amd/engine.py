@@ -119,25 +119,23 @@ class LstmStack:
     # rows below which a stack counts as "M ~ batch": hoisted x-projection + wavefront pair launches.  1025 since round 6 (was 1024): cfg 5's L2 level
     # (M = 1024 videos, K = 4096 + 1024) as ONE 172 GFLOP product + 6 pair launches instead of ten 49 us step launches at 0.25 of peak -
     # 3.85 -> 3.68 ms per step, same box, alternating (profiles/r06_cfg5_hoist_ab.txt)
-    HOIST_BELOW = int(os.environ.get("EVC_HOIST_BELOW", "1025"))
-    wavefront = os.environ.get("EVC_NO_WAVEFRONT") != "1"   # two-layer M ~ batch stacks: see forward()
-    fwd_walk2 = os.environ.get("EVC_FWD_WALK2", "1") != "0"   # two-layer many-row stacks (bf16): two tiles per workgroup, T + 1 launches (A/B: 0)
+    HOIST_BELOW = 1025
+    fwd_walk2 = True   # two-layer many-row stacks (bf16): two tiles per workgroup, T + 1 launches
     # ... and the "high" mode's L1 level (round 6, ops.lstm_level2_fwd_high: bit-identical, NOT faster - alone 2.41 against 2.37 ms per teacher level, the training
-    # step 11.67 against 11.56 ms, profiles/r06_walk2_high_ab.txt: a 96 us tile on 59 ring stages does not notice a 10 us tail; off unless EVC_FWD_WALK2_HIGH=1)
-    fwd_walk2_high = os.environ.get("EVC_FWD_WALK2_HIGH", "0") == "1"
+    # step 11.67 against 11.56 ms, profiles/r06_walk2_high_ab.txt: a 96 us tile on 59 ring stages does not notice a 10 us tail; off, the tests switch it on)
+    fwd_walk2_high = False
     # two-layer stacks with many rows (the L1 levels), the gradient arriving at layer 0 from layer 1:
     #   "off"   (default) one hoisted dX = dz1 . Wx1^T product over all T (bf16 result, re-read by layer 0's steps);
     #   "fused" contracted inside layer 0's BPTT steps (two-matrix K walk, K = 8H, f32 accumulator);
     #   "pair"  fused + wavefront order: layer 0's step t+1 and layer 1's step t in one launch (evc_lstm_stack2_bwd).
     # Measured on the headline step (DESIGN.md "Measured and dropped"): 12.75 / 12.95 / 12.89 ms - the step kernels' main
-    # loops are L2->LDS-bound, so FLOPs moved into them cost more than the 1 PF/s hoisted product saves; kept for A/B runs.
-    bwd_fuse = os.environ.get("EVC_BWD_FUSE", "off")
-    bwd_wavefront = True          # (tests toggle this to compare the fused forms against the hoisted one)
+    # loops are L2->LDS-bound, so FLOPs moved into them cost more than the 1 PF/s hoisted product saves; the tests compare the three forms.
+    bwd_fuse = "off"
     # M ~ batch two-layer stacks: wavefront BPTT on the skinny pair launches.  Built and measured in round 5 (same box, alternating): ALONE the
     # teacher's chain takes 453 instead of 507 us and the student's 119 instead of 144 (scripts/l2_bwd_bench.py), the training step 10.26 instead
     # of 10.07-10.13 ms - a pair launch wants two 64 KB workgroups on every CU at once and waits longer for them beside the other streams' tiles
-    # than two 256-workgroup launches do, and layer 1's weight gradients / update no longer run under layer 0's chain.  Off; EVC_L2_BWD_PAIR=1.
-    small_pair = os.environ.get("EVC_L2_BWD_PAIR", "0") == "1"
+    # than two 256-workgroup launches do, and layer 1's weight gradients / update no longer run under layer 0's chain.  Off; the tests switch it on.
+    small_pair = False
     timing = None      # set to a list to collect (start event, end event, launches, algorithmic flops) per layer forward
     timing_bwd = None  # set to {"bwd_step": [], "dx_nt": [], "wgrad_tn": []} to collect the same per backward launch sequence
 
@@ -335,7 +333,7 @@ class LstmStack:
             return self.S
         self.x_in, self.lens = x, lens
         inp = x
-        if (L == 2 and plan is None and all(self.hoist) and self.wavefront and self.timing is None
+        if (L == 2 and plan is None and all(self.hoist) and self.timing is None
                 and self.Kin % 64 == 0 and H % 64 == 0):
             # M ~ batch: layer 0 step t+1 and layer 1 step t share a launch (T+1 dependent launches instead of 2T)
             (k0, b0), (k1, b1) = self.names(0), self.names(1)
@@ -419,10 +417,6 @@ class LstmStack:
             inp = self._hb[l][1:]
         return res
 
-    # A/B: 0 = the weight-gradient products of a row-planned level contract over every row of the [T][P] images (rounds 1-5) instead of
-    # skipping each time slab's dead rows (ops.gemm_tn(live_rows=...))
-    wgrad_live_rows = os.environ.get("EVC_WGRAD_LIVE_ROWS", "1") != "0"
-
     def _wgrad_tn(self, dz2, layer_in, h_prev, kin, rows, gW, live=None):
         """gW [4H][kin+H] += dz^T . [layer_in | h_prev] (gate rows de-interleaved).  One launch over both column segments when
         the input width allows it (kin == H, a multiple of 256: the upper layers): dz is read once and the launch has twice the
@@ -441,11 +435,9 @@ class LstmStack:
                 ops.gemm_tn_det(dz2, layer_in, 4 * H, kin, rows, gW, row_interleave_H=H, accumulate=True, ldc=kin + H)
                 ops.gemm_tn_det(dz2, h_prev, 4 * H, H, rows, gW[:, kin:], row_interleave_H=H, accumulate=True, ldc=kin + H)
             return
-        if not self.wgrad_live_rows:
-            live = None
-        if kin == H and kin % 256 == 0 and self.fuse_wgrad:
+        if kin == H and kin % 256 == 0:
             ops.gemm_tn2(dz2, layer_in, kin, h_prev, H, 4 * H, rows, gW, row_interleave_H=H, accumulate=True, live_rows=live)
-        elif self.fuse_wgrad and kin - n1 in (64, 128) and n1 >= H and rows >= 16384 and (n1 + H) % 2048 == 0:
+        elif kin - n1 in (64, 128) and n1 >= H and rows >= 16384 and (n1 + H) % 2048 == 0:
             # layer 0 of the L1 stacks (1152 = 1024 + 128 input columns): the first 1024 input columns next to the h-part as one
             # 2048-column launch, the last 128 as a narrow strip of their own (1.0 + 0.13 ms against 0.75 + 0.6 ms)
             ops.gemm_tn2(dz2, layer_in, n1, h_prev, H, 4 * H, rows, gW, row_interleave_H=H, accumulate=True, c_col2=kin, live_rows=live)
@@ -454,8 +446,6 @@ class LstmStack:
         else:
             ops.gemm_tn(dz2, layer_in, 4 * H, kin, rows, gW, row_interleave_H=H, ldc=kin + H, accumulate=True, live_rows=live)
             ops.gemm_tn(dz2, h_prev, 4 * H, H, rows, gW[:, kin:], row_interleave_H=H, ldc=kin + H, accumulate=True, live_rows=live)
-
-    fuse_wgrad = os.environ.get("EVC_NO_FUSED_WGRAD") != "1"
 
     def backward(self, dS, need_dx, aux=None, on_layer_grads=None):
         """backward_layers run to its end; returns dX (or None)."""
@@ -481,10 +471,10 @@ class LstmStack:
         main = torch.cuda.current_stream(tw.device)
         use_tn = (T * M) % 32 == 0 and all(k % 8 == 0 for k in self.kin)
         assert use_tn or not self.use_tn or M == self.M
-        fuse_ok = L == 2 and self.bwd_wavefront and use_tn and not need_dx and M >= 1024 and H % 128 == 0
+        fuse_ok = L == 2 and use_tn and not need_dx and M >= 1024 and H % 128 == 0
         # M ~ batch stacks (the L2 levels; round 5): BPTT in wavefront order on the skinny pair launches - layer 0's step t+1 (the gradient from
         # layer 1 contracted in its own K walk) and layer 1's step t in ONE launch: T + 1 dependent launches instead of 2 T + the hoisted dX
-        # product of layer 1.  Not under EVC_DETERMINISTIC (the pair launches sum their bias gradients with atomics).  EVC_L2_BWD_PAIR=0: A/B.
+        # product of layer 1.  Not under EVC_DETERMINISTIC (the pair launches sum their bias gradients with atomics).
         small_pair = (L == 2 and self.small_pair and use_tn and M <= 512 and H % 128 == 0 and plan is None and not ops.DETERMINISTIC
                       and self.dc_ws2 is not None)
         if small_pair or (fuse_ok and self.bwd_fuse == "pair"):
@@ -699,11 +689,11 @@ class MoeHead:
         return (self.V * (self.Mx + 1)) % 4 == 0 and (self.V * self.Mx) % 4 == 0 and self.K % 8 == 0
 
     dynamic_fp8_range = os.environ.get("EVC_HIGH_DYNAMIC_RANGE", "1") != "0"     # "high" head: e4m3 range of the input state from the batch (A/B: 0 = fixed 2^6)
-    FUSE_MAX_ROWS = int(os.environ.get("EVC_MOE_FUSE_MAX_ROWS", "512"))
+    FUSE_MAX_ROWS = 512
     # one process: the clip norm of the fused update from Gram matrices of the factors instead of a pass over the weights
-    # (csrc/evc_moe_norms.hip; EVC_MOE_GRAM_NORMS=0: the two-pass form)
-    gram_norms = os.environ.get("EVC_MOE_GRAM_NORMS", "1") != "0"
-    gram_force = True if os.environ.get("EVC_MOE_GRAM_NORMS") == "1" else None     # unset: chosen by shape (use_gram_norms)
+    # (csrc/evc_moe_norms.hip; gram_norms = False: the two-pass form)
+    gram_norms = True
+    gram_force = None     # None: chosen by shape (use_gram_norms); True / False forces
     skip_stale_fwd_shadow = os.environ.get("EVC_HIGH_KEEP_BF16_SHADOW", "0") != "1"
 
     @staticmethod
@@ -722,7 +712,7 @@ class MoeHead:
         rank-`rows` gradient tile; the Gram route costs ~3.5 small launches per matrix plus 2 rows^2 (cols + K/2) flops on a
         fragments-from-global kernel - it grows with rows^2, pass 1 with K.  Constants fitted to both measured points
         (profiles/r04_bench_kernel_stats_default.csv: rows 256, K 4096 - Gram 0.16 vs pass 1 0.36 ms per tower;
-        profiles/r04_bench_dbof_kernel_stats.csv: rows 512, K 1024 - Gram 0.16 vs pass 1 0.06 ms).  EVC_MOE_GRAM_NORMS=0 / 1 forces."""
+        profiles/r04_bench_dbof_kernel_stats.csv: rows 512, K 1024 - Gram 0.16 vs pass 1 0.06 ms).  gram_norms / gram_force override."""
         if not self.gram_norms or self.gram_a is None:
             return False
         K = self.K
@@ -1135,7 +1125,7 @@ class TowerBase:
         # (evc_clip_adam_small runs ONE workgroup per tensor in two serial passes: sized for a few thousand elements each - anything above
         #  SMALL_ADAM_MAX elements stays on the two full-grid launches below)
         small = [k for k in rest if k not in self.l2_names and k not in self.shadow_fwd and self.store.p(k).numel() <= self.SMALL_ADAM_MAX]
-        if self.fused_small_adam and len(small) >= 2 and not ops.DETERMINISTIC:
+        if len(small) >= 2 and not ops.DETERMINISTIC:
             st = self.store
             for i in range(0, len(small), 16):
                 grp = small[i:i + 16]
@@ -1168,8 +1158,7 @@ class TowerBase:
                     ops.transpose_to_bf16(p, p.shape[0], p.shape[1], sb, sb.shape[1], interleave_H=il)
 
     SMALL_ADAM_MAX = 1 << 15        # elements per tensor of the one-launch small-tensor update (evc_clip_adam_small's limit)
-    fused_small_adam = os.environ.get("EVC_FUSED_SMALL_ADAM", "1") != "0"   # A/B: 0 = grad_sqnorm + clip_adam launches per small tensor
-    fused_lstm_adam = os.environ.get("EVC_FUSED_LSTM_ADAM", "1") != "0"     # A/B: 0 = grad_sqnorm / clip_adam / transpose / cast launches per tensor
+    fused_lstm_adam = True          # False: grad_sqnorm / clip_adam / transpose / cast launches per tensor (the tests compare the two)
 
     def _adam_images_2d(self, k):
         """The same for a plain 2-D weight (ops.adam2d_fused): {} in bf16; f16 + e4m3 images where this tower keeps them (shadow_w16 / shadow_w8
@@ -1629,9 +1618,6 @@ class HLstmTower(TowerBase):
 
     fused_moe_update = True      # recompute the rank-B MoE gradient inside the Adam step instead of materialising it
     _deferred, _deferred_ev, _deferred_aux = (), None, None    # backward(defer=True): closures / event / stream of the pending updates
-    # experiment: the fused MoE update enqueued behind the L2 level's BPTT chain + weight gradients instead of in front of them
-    # (its 80 / 48 KB workgroups hold the LDS the skinny chain kernels of the critical path are waiting for)
-    moe_update_after_l2 = os.environ.get("EVC_MOE_UPDATE_AFTER_L2") == "1"
 
     def backward(self, *args, **kwargs):
         """backward_phases run to its end."""
@@ -1701,7 +1687,6 @@ class HLstmTower(TowerBase):
         if aux is None or early_apply is None:
             opt = None
         ostream = opt if opt is not None else aux
-        late_moe = None
         if aux is not None and early_apply is not None:
             ev = torch.cuda.Event()
             ev.record(main)
@@ -1717,22 +1702,17 @@ class HLstmTower(TowerBase):
                 else:
                     self._deferred.append(lambda: self.apply_group(g_moe, *early_apply, lr_t=lr_t_now))
             else:
-                def moe_update_now():
-                    with torch.cuda.stream(ostream):                   # 2/3 of the parameters, under the LSTM BPTT
-                        ops.mark(self.scope + ":moe_update_begin")
-                        if fuse:
-                            lr, clip, l2c = early_apply
-                            self.moe.fused_update(lr_t_now, clip, l2c, dp=dp)
-                        elif route_rs:
-                            lr, clip, l2c = early_apply
-                            self.moe.sharded_update(lr_t_now, clip, l2c, dp)
-                        else:
-                            reduce_then_apply(g_moe, seg_moe, f32=True)    # (a bf16 gradient payload is for the LSTM segments only)
-                        ops.mark(self.scope + ":moe_update_done")
-                if self.moe_update_after_l2 and dp is None:
-                    late_moe = moe_update_now                          # (experiment: behind the L2 level's BPTT chain, see below)
-                else:
-                    moe_update_now()
+                with torch.cuda.stream(ostream):                       # 2/3 of the parameters, under the LSTM BPTT
+                    ops.mark(self.scope + ":moe_update_begin")
+                    if fuse:
+                        lr, clip, l2c = early_apply
+                        self.moe.fused_update(lr_t_now, clip, l2c, dp=dp)
+                    elif route_rs:
+                        lr, clip, l2c = early_apply
+                        self.moe.sharded_update(lr_t_now, clip, l2c, dp)
+                    else:
+                        reduce_then_apply(g_moe, seg_moe, f32=True)        # (a bf16 gradient payload is for the LSTM segments only)
+                    ops.mark(self.scope + ":moe_update_done")
         # Per LAYER: as soon as a layer's weight-gradient products are enqueued on the aux stream its kernel + bias gradients are
         # final there - reduce (data parallel) and clip + Adam them right behind, under the BPTT of the layer below.  Only the
         # LOWEST layer of the L1 level is left for the end of the step (round 3; before, a level's four tensors waited for its
@@ -1765,8 +1745,6 @@ class HLstmTower(TowerBase):
         yield "moe"
         dS1 = yield from self.l2.backward_layers(dS2, need_dx=True, aux=aux, on_layer_grads=layer_cb(self.l2, defer))   # [C*B][2LH] = d(L1 final state)
         ops.mark(self.scope + ":l2_bwd_done")
-        if late_moe is not None:
-            late_moe()
         yield from self.l1.backward_layers(dS1, need_dx=False, aux=aux, on_layer_grads=layer_cb(self.l1))
         ops.mark(self.scope + ":l1_bwd_done")
         if aux is not None:

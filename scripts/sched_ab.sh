@@ -22,9 +22,7 @@ except Exception as e:
 PY
 }
 run "baseline" X=1
-run "student_early" EVC_STUDENT_EARLY=1
 run "defer" EVC_DEFER_UPDATES=1
-run "defer+student_early" EVC_DEFER_UPDATES=1 EVC_STUDENT_EARLY=1
 run "opt on 16 CUs" EVC_OPT_CU_MASK=2
 run "opt on 32 CUs" EVC_OPT_CU_MASK=4
 run "opt on 64 CUs" EVC_OPT_CU_MASK=8

@@ -45,9 +45,8 @@ for i in range(K):
         gm, g.debug_marks = g.debug_marks, None
 g.flush()
 torch.cuda.synchronize()
-print("%.3f ms/step (%s; EVC_DEFER_UPDATES=%s EVC_STUDENT_EARLY=%s EVC_OPT_CU_MASK=%s)" % (
-    (time.perf_counter() - t0) / K * 1e3, args.precision, os.environ.get("EVC_DEFER_UPDATES"), os.environ.get("EVC_STUDENT_EARLY"),
-    os.environ.get("EVC_OPT_CU_MASK")))
+print("%.3f ms/step (%s; EVC_DEFER_UPDATES=%s EVC_OPT_CU_MASK=%s)" % (
+    (time.perf_counter() - t0) / K * 1e3, args.precision, os.environ.get("EVC_DEFER_UPDATES"), os.environ.get("EVC_OPT_CU_MASK")))
 base = gm[0][1]
 names = {g._main.cuda_stream: "main", g._side.cuda_stream: "side", g._aux_t.cuda_stream: "aux_t", g._aux_s.cuda_stream: "aux_s"}
 if g._opt_t is not None:
