@@ -124,6 +124,7 @@ SIGNATURES = {
     "evc_gemm_tn_slabs": [vp, i64, vp, i64, vp, i32, i32, i32, i32, vp],
     "evc_dbof_wgrad_finish": [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp],
     "evc_topk_rows": [vp, i32, i32, i32, i32, vp, vp, vp],
+    "evc_eval_select_rows": [vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp],
 }
 EXPORTS = tuple(SIGNATURES) + ("evc_version", "evc_last_error")
 

@@ -14,6 +14,10 @@
 //   4. bitonic sort of the <= 256 survivors in LDS on (key << 32 | ~column), descending;
 //   5. coalesced stores of the values (the input's own bits) and the column indices.
 // No float atomics and no order-dependent placement: every launch gives the same bits.
+//
+// evc_eval_select_rows runs the same steps (shared __device__ helpers) for the evaluation binaries and adds what Hit@1 / PERR /
+// mAP need from the label row - the labels of the selected columns, the row's positive count, the PERR numerator and the
+// per-class positive counts - so that validate.py fetches [rows, k] + a few [rows] vectors instead of two [rows, cols] matrices.
 #include "evc_common.h"
 
 #include <mutex>
@@ -30,6 +34,7 @@ constexpr int TK_OFF_GRP = TK_OFF_HIST + 256 * 4;
 constexpr int TK_OFF_MISC = TK_OFF_GRP + TK_GROUPS * 4;
 constexpr int TK_OFF_ROW = TK_OFF_MISC + 64;
 constexpr int TK_MAX_LDS = TK_OFF_ROW + TK_MAX_COLS * 4;
+constexpr int EV_MAX_LDS = TK_MAX_LDS + TK_GROUPS * 8;              // eval_select_rows_kernel: + one label bit per column behind the row
 
 // Total order of the selection as an unsigned key, larger = ranks first: -0 ties with +0; every NaN maps to the largest
 // key (above +inf, all NaNs tied: numpy's sort order); otherwise the usual sign-flip map of the IEEE bits.
@@ -57,21 +62,12 @@ __device__ __forceinline__ uint32_t block_incl_scan(uint32_t v, uint32_t* ws) {
   return v;
 }
 
-__global__ __launch_bounds__(TK_THREADS) void topk_rows_kernel(const float* __restrict__ x, long ld, int cols, int k, int sort_n,
-                                                               float* __restrict__ out_val, int32_t* __restrict__ out_idx) {
-  extern __shared__ __attribute__((aligned(16))) char tk_lds[];
-  unsigned long long* sv = (unsigned long long*)tk_lds;              // [sort_n] survivors: key << 32 | ~column
-  uint32_t* hist = (uint32_t*)(tk_lds + TK_OFF_HIST);                // [256]
-  uint32_t* grp = (uint32_t*)(tk_lds + TK_OFF_GRP);                  // [cols / 64]: gt | eq << 16, then its exclusive prefix
-  uint32_t* scan_ws = (uint32_t*)(tk_lds + TK_OFF_MISC);             // [4]
-  uint32_t* sel = scan_ws + 4;                                       // prefix, ties to admit, walk done
-  uint32_t* row = (uint32_t*)(tk_lds + TK_OFF_ROW);                  // [cols] raw bits of the row
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const uint32_t* xr = (const uint32_t*)(x + (long)blockIdx.x * ld);
+// ---- the steps of the selection, shared by topk_rows_kernel and eval_select_rows_kernel (whole block calls each) ----
 
-  hist[tid] = 0;
-  __syncthreads();
-  // ---- 1. row -> LDS, digit histogram of pass 0 on the way ----
+// 1. row -> LDS as raw bits, digit histogram of radix pass 0 on the way.  hist is zeroed and synchronised by the caller, which
+// also synchronises afterwards.
+__device__ __forceinline__ void tk_load_row(const uint32_t* __restrict__ xr, int cols, uint32_t* row, uint32_t* hist) {
+  const int tid = threadIdx.x;
   if ((((uintptr_t)xr) & 15) == 0) {
     const int n4 = cols >> 2;
 #pragma unroll 4
@@ -93,14 +89,20 @@ __global__ __launch_bounds__(TK_THREADS) void topk_rows_kernel(const float* __re
       atomicAdd(&hist[topk_key(u) >> 24], 1u);
     }
   }
-  __syncthreads();
+}
 
-  // ---- 2. radix select: the k-th key's prefix and the ties admitted at it ----
-  uint32_t prefix = 0, mask = 0;
-  uint32_t krem = (uint32_t)k;
+// 2. radix select of the k-th key (1 <= k <= cols, block-uniform) of the row in LDS: (key & mask) > prefix are admitted whole
+// (k - krem of them), (key & mask) == prefix are the ties of which krem are admitted.  hist0_ready: hist already holds the digit
+// histogram of pass 0 (tk_load_row).  Leaves hist, scan_ws and sel free again (a barrier ends it).
+__device__ __forceinline__ void tk_radix_select(const uint32_t* row, int cols, uint32_t k, bool hist0_ready, uint32_t* hist,
+                                                uint32_t* scan_ws, uint32_t* sel, uint32_t& prefix, uint32_t& mask, uint32_t& krem) {
+  const int tid = threadIdx.x;
+  prefix = 0;
+  mask = 0;
+  krem = k;
   for (int pass = 0; pass < 4; ++pass) {
     const int shift = 24 - 8 * pass;
-    if (pass > 0) {
+    if (pass > 0 || !hist0_ready) {
       hist[tid] = 0;
       __syncthreads();
       for (int i = tid; i < cols; i += TK_THREADS) {
@@ -125,9 +127,14 @@ __global__ __launch_bounds__(TK_THREADS) void topk_rows_kernel(const float* __re
     __syncthreads();                                                 // sel and scan_ws are rewritten by the next pass
     if (done) break;
   }
-  const uint32_t n_gt = (uint32_t)k - krem;                          // (key & mask) > prefix: all admitted; == prefix: krem of them
+}
 
-  // ---- 3. compaction in column order ----
+// 3a. per 64-column group the counts of (key & mask) > prefix and == prefix from ballots, then their exclusive prefix over the
+// groups in column order: grp[g] = gt | eq << 16 (gt sums < cols <= 32768, eq sums <= 32768: the halves never carry).  The caller
+// synchronises before it reads grp.
+__device__ __forceinline__ void tk_group_prefix(const uint32_t* row, int cols, uint32_t prefix, uint32_t mask, uint32_t* grp,
+                                                uint32_t* scan_ws) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int ngroups = (cols + 63) >> 6;
   for (int c = 0; c * TK_THREADS < cols; ++c) {
     const int i = c * TK_THREADS + tid;
@@ -138,16 +145,18 @@ __global__ __launch_bounds__(TK_THREADS) void topk_rows_kernel(const float* __re
     if (lane == 0 && g < ngroups) grp[g] = (uint32_t)__popcll(bgt) | ((uint32_t)__popcll(beq) << 16);
   }
   __syncthreads();
-  {
-    const int g0 = 2 * tid;
-    const uint32_t a = g0 < ngroups ? grp[g0] : 0u;
-    const uint32_t b = g0 + 1 < ngroups ? grp[g0 + 1] : 0u;
-    const uint32_t incl = block_incl_scan(a + b, scan_ws);           // gt sums < 256, eq sums <= 32768: the halves never carry
-    if (g0 < ngroups) grp[g0] = incl - a - b;
-    if (g0 + 1 < ngroups) grp[g0 + 1] = incl - b;
-  }
-  for (int j = k + tid; j < sort_n; j += TK_THREADS) sv[j] = 0ull;   // padding: below every real entry
-  __syncthreads();
+  const int g0 = 2 * tid;
+  const uint32_t a = g0 < ngroups ? grp[g0] : 0u;
+  const uint32_t b = g0 + 1 < ngroups ? grp[g0 + 1] : 0u;
+  const uint32_t incl = block_incl_scan(a + b, scan_ws);
+  if (g0 < ngroups) grp[g0] = incl - a - b;
+  if (g0 + 1 < ngroups) grp[g0 + 1] = incl - b;
+}
+
+// 3b. compaction in column order into sv[0 .. k): slot = group base + mbcnt; ties are admitted lowest columns first.
+__device__ __forceinline__ void tk_compact(const uint32_t* row, int cols, int k, uint32_t prefix, uint32_t mask, uint32_t n_gt,
+                                           const uint32_t* grp, unsigned long long* sv) {
+  const int tid = threadIdx.x, wave = tid >> 6;
   for (int c = 0; c * TK_THREADS < cols; ++c) {
     const int i = c * TK_THREADS + tid;
     const uint32_t key = i < cols ? topk_key(row[i]) : 0u;
@@ -161,8 +170,11 @@ __global__ __launch_bounds__(TK_THREADS) void topk_rows_kernel(const float* __re
       if (slot < (uint32_t)k) sv[slot] = ((unsigned long long)key << 32) | (uint32_t)~(uint32_t)i;
     }
   }
+}
 
-  // ---- 4. bitonic sort, descending ----
+// 4. bitonic sort of sv[0 .. sort_n), descending; a barrier ends it.
+__device__ __forceinline__ void tk_sort_desc(unsigned long long* sv, int sort_n) {
+  const int tid = threadIdx.x;
   for (int size = 2; size <= sort_n; size <<= 1) {
     for (int stride = size >> 1; stride > 0; stride >>= 1) {
       __syncthreads();
@@ -178,6 +190,37 @@ __global__ __launch_bounds__(TK_THREADS) void topk_rows_kernel(const float* __re
     }
   }
   __syncthreads();
+}
+
+// Steps 2 - 4 for the row in LDS (pass-0 histogram ready): sv[0 .. k) = the k first elements in the total order, sorted.
+__device__ __forceinline__ void tk_select_sorted(const uint32_t* row, int cols, int k, int sort_n, unsigned long long* sv, uint32_t* hist,
+                                                 uint32_t* grp, uint32_t* scan_ws, uint32_t* sel) {
+  uint32_t prefix, mask, krem;
+  tk_radix_select(row, cols, (uint32_t)k, true, hist, scan_ws, sel, prefix, mask, krem);
+  const uint32_t n_gt = (uint32_t)k - krem;                          // (key & mask) > prefix: all admitted; == prefix: krem of them
+  tk_group_prefix(row, cols, prefix, mask, grp, scan_ws);
+  for (int j = k + threadIdx.x; j < sort_n; j += TK_THREADS) sv[j] = 0ull;   // padding: below every real entry
+  __syncthreads();
+  tk_compact(row, cols, k, prefix, mask, n_gt, grp, sv);
+  tk_sort_desc(sv, sort_n);
+}
+
+__global__ __launch_bounds__(TK_THREADS) void topk_rows_kernel(const float* __restrict__ x, long ld, int cols, int k, int sort_n,
+                                                               float* __restrict__ out_val, int32_t* __restrict__ out_idx) {
+  extern __shared__ __attribute__((aligned(16))) char tk_lds[];
+  unsigned long long* sv = (unsigned long long*)tk_lds;              // [sort_n] survivors: key << 32 | ~column
+  uint32_t* hist = (uint32_t*)(tk_lds + TK_OFF_HIST);                // [256]
+  uint32_t* grp = (uint32_t*)(tk_lds + TK_OFF_GRP);                  // [cols / 64]: gt | eq << 16, then its exclusive prefix
+  uint32_t* scan_ws = (uint32_t*)(tk_lds + TK_OFF_MISC);             // [4]
+  uint32_t* sel = scan_ws + 4;                                       // prefix, ties to admit, walk done
+  uint32_t* row = (uint32_t*)(tk_lds + TK_OFF_ROW);                  // [cols] raw bits of the row
+  const int tid = threadIdx.x;
+
+  hist[tid] = 0;
+  __syncthreads();
+  tk_load_row((const uint32_t*)(x + (long)blockIdx.x * ld), cols, row, hist);
+  __syncthreads();
+  tk_select_sorted(row, cols, k, sort_n, sv, hist, grp, scan_ws, sel);
 
   // ---- 5. stores ----
   const long o = (long)blockIdx.x * k;
@@ -185,6 +228,87 @@ __global__ __launch_bounds__(TK_THREADS) void topk_rows_kernel(const float* __re
     const uint32_t col = ~(uint32_t)sv[j];
     out_idx[o + j] = (int32_t)col;
     out_val[o + j] = __uint_as_float(row[col]);
+  }
+}
+
+// evc_eval_select_rows: the selection above plus what Hit@1 / PERR / the per-class positive counts need from the label row.
+// The label row is read once (one byte per thread, coalesced) into a bit per column in LDS behind the row; its population count
+// n_pos is the k' of a second radix select over the same row in LDS, after which the PERR numerator is a ballot count:
+// positives with a value > 0 above the threshold, plus those among the admitted ties (lowest columns first) - no sort.
+__global__ __launch_bounds__(TK_THREADS) void eval_select_rows_kernel(const float* __restrict__ x, long ld, const uint8_t* __restrict__ labels,
+                                                                      long ld_lab, int cols, int k, int sort_n, float* __restrict__ top_val,
+                                                                      int32_t* __restrict__ top_idx, uint8_t* __restrict__ top_lab,
+                                                                      int32_t* __restrict__ n_pos, int32_t* __restrict__ perr_hits,
+                                                                      int32_t* __restrict__ class_pos) {
+  extern __shared__ __attribute__((aligned(16))) char tk_lds[];
+  unsigned long long* sv = (unsigned long long*)tk_lds;
+  uint32_t* hist = (uint32_t*)(tk_lds + TK_OFF_HIST);
+  uint32_t* grp = (uint32_t*)(tk_lds + TK_OFF_GRP);
+  uint32_t* scan_ws = (uint32_t*)(tk_lds + TK_OFF_MISC);
+  uint32_t* sel = scan_ws + 4;
+  uint32_t* wave_pos = scan_ws + 8;                                  // [4] positives seen by each wave
+  uint32_t* wave_hits = scan_ws + 12;                                // [4] PERR hits seen by each wave
+  uint32_t* row = (uint32_t*)(tk_lds + TK_OFF_ROW);
+  uint32_t* lab = row + ((cols + 3) & ~3);                           // [2 * groups] label != 0, one bit per column
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ngroups = (cols + 63) >> 6;
+
+  hist[tid] = 0;
+  __syncthreads();
+  tk_load_row((const uint32_t*)(x + (long)blockIdx.x * ld), cols, row, hist);
+  {
+    const uint8_t* lr = labels + (long)blockIdx.x * ld_lab;
+    uint32_t seen = 0;                                               // wave-uniform
+    for (int c = 0; c * TK_THREADS < cols; ++c) {
+      const int i = c * TK_THREADS + tid;
+      const bool on = i < cols && lr[i] != 0;
+      const unsigned long long b = __ballot(on);
+      seen += (uint32_t)__popcll(b);
+      const int g = 4 * c + wave;
+      if (lane == 0 && g < ngroups) {
+        lab[2 * g] = (uint32_t)b;
+        lab[2 * g + 1] = (uint32_t)(b >> 32);
+      }
+      if (on && class_pos != nullptr) atomicAdd(&class_pos[i], 1);   // integer: the sum does not depend on the order
+    }
+    if (lane == 0) wave_pos[wave] = seen;
+  }
+  __syncthreads();
+  tk_select_sorted(row, cols, k, sort_n, sv, hist, grp, scan_ws, sel);
+
+  const long o = (long)blockIdx.x * k;
+  for (int j = tid; j < k; j += TK_THREADS) {
+    const uint32_t col = ~(uint32_t)sv[j];
+    top_idx[o + j] = (int32_t)col;
+    top_val[o + j] = __uint_as_float(row[col]);
+    top_lab[o + j] = (uint8_t)((lab[col >> 5] >> (col & 31)) & 1u);
+  }
+
+  // ---- PERR numerator: the first n_pos columns of the same total order ----
+  const uint32_t npos = wave_pos[0] + wave_pos[1] + wave_pos[2] + wave_pos[3];   // block-uniform, <= cols
+  uint32_t hits = 0;                                                 // wave-uniform
+  if (npos > 0) {
+    uint32_t prefix, mask, krem;
+    tk_radix_select(row, cols, npos, false, hist, scan_ws, sel, prefix, mask, krem);
+    tk_group_prefix(row, cols, prefix, mask, grp, scan_ws);
+    __syncthreads();
+    for (int c = 0; c * TK_THREADS < cols; ++c) {
+      const int i = c * TK_THREADS + tid;
+      const uint32_t u = i < cols ? row[i] : 0u;
+      const uint32_t mk = topk_key(u) & mask;
+      const bool gt = i < cols && mk > prefix, eq = i < cols && mk == prefix;
+      const unsigned long long beq = __ballot(eq);
+      const bool admitted = gt || (eq && (grp[4 * c + wave] >> 16) + lanes_below(beq) < krem);
+      const uint32_t key = topk_key(u);
+      const bool hit = admitted && ((lab[i >> 5] >> (i & 31)) & 1u) != 0 && key > 0x80000000u && key != 0xffffffffu;   // value > 0, not NaN
+      hits += (uint32_t)__popcll(__ballot(hit));
+    }
+  }
+  if (lane == 0) wave_hits[wave] = hits;
+  __syncthreads();
+  if (tid == 0) {
+    n_pos[blockIdx.x] = (int32_t)npos;
+    perr_hits[blockIdx.x] = (int32_t)(wave_hits[0] + wave_hits[1] + wave_hits[2] + wave_hits[3]);
   }
 }
 
@@ -206,6 +330,31 @@ extern "C" int evc_topk_rows(const float* x, int ld, int rows, int cols, int k, 
   });
   hipLaunchKernelGGL(topk_rows_kernel, dim3(rows), dim3(TK_THREADS), lds, (hipStream_t)stream, x, (long)ld, cols, k, sort_n, out_val,
                      out_idx);
+  EVC_LAUNCH_CHECK();
+  return EVC_OK;
+}
+
+extern "C" int evc_eval_select_rows(const float* pred, int ld, const uint8_t* labels, int ld_lab, int rows, int cols, int k, float* top_val,
+                                    int32_t* top_idx, uint8_t* top_lab, int32_t* n_pos, int32_t* perr_hits, int32_t* class_pos,
+                                    void* stream) {
+  EVC_REQUIRE(cols >= 1 && cols <= TK_MAX_COLS, EVC_ERR_BAD_ARG, "evc_eval_select_rows: cols=%d (1 .. %d)", cols, TK_MAX_COLS);
+  EVC_REQUIRE(k >= 1 && k <= cols && k <= TK_MAX_K, EVC_ERR_BAD_ARG, "evc_eval_select_rows: k=%d (1 .. min(cols=%d, %d))", k, cols, TK_MAX_K);
+  EVC_REQUIRE(ld >= cols, EVC_ERR_BAD_ARG, "evc_eval_select_rows: ld=%d < cols=%d", ld, cols);
+  EVC_REQUIRE(ld_lab >= cols, EVC_ERR_BAD_ARG, "evc_eval_select_rows: ld_lab=%d < cols=%d", ld_lab, cols);
+  EVC_REQUIRE(rows >= 0, EVC_ERR_BAD_ARG, "evc_eval_select_rows: rows=%d", rows);
+  if (rows == 0) return EVC_OK;
+  EVC_REQUIRE(pred != nullptr && labels != nullptr && top_val != nullptr && top_idx != nullptr && top_lab != nullptr && n_pos != nullptr &&
+                  perr_hits != nullptr,
+              EVC_ERR_BAD_ARG, "evc_eval_select_rows: NULL argument");
+  int sort_n = 1;
+  while (sort_n < k) sort_n <<= 1;
+  const size_t lds = (size_t)TK_OFF_ROW + (size_t)((cols + 3) & ~3) * sizeof(uint32_t) + (size_t)((cols + 63) >> 6) * 8;
+  static std::once_flag once;
+  std::call_once(once, [] {
+    (void)hipFuncSetAttribute((const void*)eval_select_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, EV_MAX_LDS);
+  });
+  hipLaunchKernelGGL(eval_select_rows_kernel, dim3(rows), dim3(TK_THREADS), lds, (hipStream_t)stream, pred, (long)ld, labels, (long)ld_lab,
+                     cols, k, sort_n, top_val, top_idx, top_lab, n_pos, perr_hits, class_pos);
   EVC_LAUNCH_CHECK();
   return EVC_OK;
 }

@@ -10,7 +10,9 @@ distinct; when exact ties are present the reference's value depends on its
 heap order and seeded shuffle, so that (rare) case is routed through an exact
 emulation of those two steps.  Accepts numpy arrays or torch tensors (device
 tensors are copied to the host first - the metrics are host arithmetic in
-float64, as in the reference).
+float64, as in the reference).  EvaluationMetrics.accumulate_selected takes
+the per-batch selection of ops.eval_select_rows instead of the full
+predictions and labels (validate.py --metrics_on_device).
 """
 from __future__ import annotations
 
@@ -191,6 +193,38 @@ class EvaluationMetrics(object):
         class_pos = labels.sum(axis=0)
         self._class_pos += class_pos
         self._num_pos += _num_positives(labels)
+        self.num_examples += batch_size
+        self.sum_hit_at_one += mean_hit_at_one * batch_size
+        self.sum_perr += mean_perr * batch_size
+        self.sum_loss += mean_loss * batch_size
+        return {"hit_at_one": mean_hit_at_one, "perr": mean_perr, "loss": mean_loss}
+
+    def accumulate_selected(self, top_val, top_idx, top_lab, n_pos, perr_hits, class_pos, loss):
+        """accumulate() fed by the device's selection (ops.eval_select_rows with k = top_k) instead of the [B, C] matrices:
+        top_val f32 / top_idx / top_lab [B, top_k] (each row's top_k best classes, best first, and their labels), n_pos [B]
+        (positives per row), perr_hits [B] (positives with a score > 0 among the row's n_pos best classes), class_pos [C]
+        (positives per class), loss.  Same state, same returned dict, bit for bit - every sum below is taken in the dtype
+        and the order accumulate() takes it in (which sees float32 labels).  The one accepted difference: where a row has
+        an exact tie across its top_k-th / (top_k+1)-th place (GAP / mAP pool) or a tie at a score > 0 across its n_pos-th
+        / (n_pos+1)-th place (PERR), np.argpartition picks an implementation-defined member of the tie and the device the
+        lowest class - the documented, deterministic rule."""
+        top_val, top_idx, top_lab = _np(top_val), _np(top_idx), _np(top_lab)
+        n_pos, perr_hits, class_pos = _np(n_pos), _np(perr_hits), _np(class_pos)
+        loss = _np(loss)
+        batch_size = top_val.shape[0]
+        mean_hit_at_one = np.average(top_lab[:, 0].astype(np.float32))
+        total = 0.0
+        for hits, k in zip(perr_hits.tolist(), n_pos.tolist()):      # same left-to-right float accumulation as accumulate()
+            total += hits / float(k) if k else 0.0
+        mean_perr = np.float64(total / batch_size)
+        mean_loss = np.mean(loss)
+        fi = top_idx.reshape(-1).astype(np.intp)
+        order = np.argsort(fi, kind="stable")       # class-major; a class occurs once per row, so video order inside a class
+        self._pool_p.append(top_val.reshape(-1)[order])
+        self._pool_l.append(top_lab.reshape(-1).astype(np.float32)[order])
+        self._pool_c.append(fi[order])
+        self._class_pos += class_pos
+        self._num_pos += np.float32(np.sum(n_pos, dtype=np.int64))
         self.num_examples += batch_size
         self.sum_hit_at_one += mean_hit_at_one * batch_size
         self.sum_perr += mean_perr * batch_size

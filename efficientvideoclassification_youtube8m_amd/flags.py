@@ -94,6 +94,10 @@ _define("precision", "bf16", str, "'bf16' (one bf16 MFMA product per forward con
 _define("netvlad_cluster_size", 64, int, "NetVLADModel (extension): number of clusters")
 _define("netvlad_hidden_size", 1024, int, "NetVLADModel (extension): width of the hidden layer after the aggregation")
 _define("log_every", 1, int, "host metrics / logging period in iterations (the reference logs every step)")
+_define("metrics_on_device", False, _bool, "validate / eval_finetune: select what Hit@1 / PERR / GAP / mAP need from each batch on the device "
+        "(ops.eval_select_rows) and fetch [B, top_k] + a few [B] vectors instead of the [B, 4716] predictions and labels; same metrics bit "
+        "for bit except for rows with an exact tie at the top_k-th / label-count-th place, where the device admits the lowest class "
+        "(eval_util.EvaluationMetrics.accumulate_selected); needs 1 <= top_k <= min(256, classes)")
 
 
 class FlagValues(object):

@@ -600,6 +600,32 @@ def topk_rows(x, k):
     return values, indices
 
 
+def eval_select_rows(predictions, labels, k):
+    """What eval_util.EvaluationMetrics.accumulate_selected needs from one batch, selected on the current stream
+    (evc_eval_select_rows): predictions [B, C] f32 and labels [B, C] uint8 (rows contiguous, any row stride) -> dict of device tensors
+    top_val [B, k] f32 / top_idx [B, k] int32 (= topk_rows(predictions, k)), top_lab [B, k] uint8 (the labels of those columns),
+    n_pos [B] int32 (positives per row), perr_hits [B] int32 (positives with a value > 0 among each row's first n_pos columns in the
+    order of topk_rows) and class_pos [C] int32 (positives per class)."""
+    x, y = predictions, labels
+    if x.dtype != F32 or x.dim() != 2 or (x.shape[0] > 0 and x.shape[1] > 1 and x.stride(1) != 1):
+        raise _lib.EvcError("eval_select_rows: needs 2-D float32 predictions with contiguous rows (got %s %s)" % (x.dtype, tuple(x.shape)))
+    if y.dtype != torch.uint8 or y.dim() != 2 or tuple(y.shape) != tuple(x.shape) or (y.shape[0] > 0 and y.shape[1] > 1 and y.stride(1) != 1):
+        raise _lib.EvcError("eval_select_rows: needs uint8 labels of the predictions' shape %s with contiguous rows (got %s %s)"
+                            % (tuple(x.shape), y.dtype, tuple(y.shape)))
+    if y.device != x.device:
+        raise _lib.EvcError("eval_select_rows: predictions on %s, labels on %s" % (x.device, y.device))
+    B, cols = x.shape
+    kk = max(int(k), 0)
+    out = {"top_val": torch.empty((B, kk), dtype=F32, device=x.device), "top_idx": torch.empty((B, kk), dtype=torch.int32, device=x.device),
+           "top_lab": torch.empty((B, kk), dtype=torch.uint8, device=x.device), "n_pos": torch.empty((B,), dtype=torch.int32, device=x.device),
+           "perr_hits": torch.empty((B,), dtype=torch.int32, device=x.device),
+           "class_pos": torch.zeros((cols,), dtype=torch.int32, device=x.device)}
+    _lib.call("evc_eval_select_rows", _p(x), x.stride(0) if B > 1 else cols, _p(y), y.stride(0) if B > 1 else cols, B, cols, int(k),
+              _p(out["top_val"]), _p(out["top_idx"]), _p(out["top_lab"]), _p(out["n_pos"]), _p(out["perr_hits"]), _p(out["class_pos"]),
+              _stream())
+    return out
+
+
 # ---------------------------------------------------------------------------
 def moe_tail_fwd(gate_logits, expert_logits, B, V, M, pred, rowsum):
     _lib.call("evc_moe_tail_fwd", _p(gate_logits), _p(expert_logits), B, V, M, _p(pred), _p(rowsum), _stream())

@@ -14,6 +14,9 @@ EvaluationMetrics accumulation (Hit@1 / PERR / mAP / GAP@top_k, host float64), "
 when the global step has not moved, looping until --run_once.  Replaced: TF session / queue runners
 -> readers.get_input_evaluation_tensors + distill.EvalGraph; events file -> events.jsonl.
 ``--eval_data_pattern synthetic`` evaluates ``--synthetic_videos`` random videos (no data set on the box).
+``--metrics_on_device True`` (off by default) keeps the [B, 4716] predictions and labels on the device: ops.eval_select_rows
+(evc_eval_select_rows) runs behind the MoE head and the fetch carries [B, top_k] values / classes / labels, two [B] vectors and
+the per-class positive counts, which EvaluationMetrics.accumulate_selected turns into the same numbers (ties: see there).
 """
 from __future__ import annotations
 
@@ -64,6 +67,14 @@ def _batches(reader, device):
             yield b
 
 
+def check_flags():
+    """What is refused before a record is read or the device is touched."""
+    if FLAGS.metrics_on_device:
+        top_max = min(ops.TOPK_MAX_K, NUM_CLASSES)
+        if not 1 <= FLAGS.top_k <= top_max:
+            raise ValueError("--top_k %d: must be in [1, %d] with --metrics_on_device" % (FLAGS.top_k, top_max))
+
+
 def evaluation_loop(graph, reader, label_loss_fn, summary_writer, evl_metrics, last_global_step_val, device):
     """Run the evaluation loop once (cs/validate.py:192-303).  Returns (global_step_val, epoch_info_dict or None)."""
     ck = latest_checkpoint(FLAGS.train_dir)
@@ -89,6 +100,7 @@ def evaluation_loop(graph, reader, label_loss_fn, summary_writer, evl_metrics, l
     evl_metrics.clear()
     examples_processed, total_example_per_sec = 0, []
     fused_ce = isinstance(label_loss_fn, losses.CrossEntropyLoss)
+    on_device = FLAGS.metrics_on_device
     fetcher = utils.AsyncFetcher(device)
     last_time = [time.time()]
 
@@ -96,14 +108,22 @@ def evaluation_loop(graph, reader, label_loss_fn, summary_writer, evl_metrics, l
         """The host side of one batch (cs/validate.py:240-282), run while the GPU already works on the next batch."""
         nonlocal examples_processed
         got = fetcher.result(handle)
-        predictions_val, labels_val = got["predictions"], got["labels"].astype(np.float32)
+        if on_device:
+            batch = got["top_val"].shape[0]
+        else:
+            predictions_val, labels_val = got["predictions"], got["labels"].astype(np.float32)
+            batch = labels_val.shape[0]
         loss_val = float(got["loss"].reshape(-1)[0])
         now = time.time()
         seconds_per_batch, last_time[0] = max(now - last_time[0], 1e-9), now
-        example_per_second = labels_val.shape[0] / seconds_per_batch
+        example_per_second = batch / seconds_per_batch
         total_example_per_sec.append(example_per_second)
-        examples_processed += labels_val.shape[0]
-        iteration_info_dict = evl_metrics.accumulate(predictions_val, labels_val, loss_val)
+        examples_processed += batch
+        if on_device:
+            iteration_info_dict = evl_metrics.accumulate_selected(got["top_val"], got["top_idx"], got["top_lab"], got["n_pos"],
+                                                                  got["perr_hits"], got["class_pos"], loss_val)
+        else:
+            iteration_info_dict = evl_metrics.accumulate(predictions_val, labels_val, loss_val)
         iteration_info_dict["examples_per_second"] = example_per_second
         iterinfo_pre = ""
         if "student_state_loss" in got:                                 # cs/validate.py:268-275
@@ -117,7 +137,11 @@ def evaluation_loop(graph, reader, label_loss_fn, summary_writer, evl_metrics, l
     for ids, q, labels, n, n_host in _batches(reader, device):
         out = graph.step(q, labels, n, num_frames_host=n_host)
         loss_t = out["loss"] if fused_ce else label_loss_fn.calculate_loss(out["predictions"], labels)
-        fetch = {"predictions": out["predictions"], "labels": labels, "loss": loss_t.reshape(1)}
+        if on_device:                                                    # same stream, right behind the MoE head
+            fetch = ops.eval_select_rows(out["predictions"], labels, FLAGS.top_k)
+            fetch["loss"] = loss_t.reshape(1)
+        else:
+            fetch = {"predictions": out["predictions"], "labels": labels, "loss": loss_t.reshape(1)}
         if "student_state_loss" in out:
             fetch["student_state_loss"] = out["student_state_loss"].reshape(1)
         handle = fetcher.fetch(fetch)                                    # the fetch: clones + D2H on a copy stream
@@ -146,6 +170,7 @@ def evaluation_loop(graph, reader, label_loss_fn, summary_writer, evl_metrics, l
 def evaluate(student_only=False, max_evals=None):
     """cs/validate.py:306-397.  Returns the last epoch_info_dict (None if nothing was evaluated)."""
     start_time = time.time()
+    check_flags()
     device = "cuda:%d" % FLAGS.gpu
     torch.cuda.set_device(FLAGS.gpu)
     ops.check_device(FLAGS.gpu)

@@ -760,6 +760,19 @@ int evc_adam2d_fused(float* p, const float* g, float* m, float* v, int R, int C,
  * (any ld; rows that are not 16-byte aligned take a narrower load path); rows == 0 launches nothing; anything else is EVC_ERR_BAD_ARG
  * before any launch.  No float atomics: every launch gives the same bits. */
 int evc_topk_rows(const float* x, int ld, int rows, int cols, int k, float* out_val, int32_t* out_idx, void* stream);
+/* Evaluation: everything eval_util.EvaluationMetrics needs from a batch (Hit@1, PERR, the GAP / mAP pool, the per-class positive counts),
+ * selected on the device from pred [rows][ld] f32 and labels [rows][ld_lab] bytes (nonzero = positive), in the total order of evc_topk_rows:
+ *   top_val / top_idx [rows][k]: exactly what evc_topk_rows(pred, ld, rows, cols, k, ...) writes (same bits);
+ *   top_lab [rows][k]: labels[r][top_idx[r][j]] != 0 (top_lab[r][0] is the Hit@1 flag: numpy's argmax picks the first maximum);
+ *   n_pos [rows]: nonzero label bytes of the row;
+ *   perr_hits [rows]: among the first n_pos[r] columns of the row in that order (n_pos is not bounded by 256), those with a nonzero label and
+ *     a value > 0.0f (NaN is not > 0) - the numerator of calculate_precision_at_equal_recall_rate; 0 when n_pos[r] == 0;
+ *   class_pos [cols] (may be NULL): class_pos[c] += rows with a nonzero label in column c (int32 atomics; the caller zeroes it).
+ * Where numpy.argpartition leaves the choice among exact ties at the k-th / n_pos-th place open, this picks the lowest columns.
+ * Limits as evc_topk_rows, and ld_lab >= cols; rows == 0 launches nothing; anything else is EVC_ERR_BAD_ARG before any launch.  Integer
+ * atomics only: every launch gives the same bits. */
+int evc_eval_select_rows(const float* pred, int ld, const uint8_t* labels, int ld_lab, int rows, int cols, int k, float* top_val,
+                         int32_t* top_idx, uint8_t* top_lab, int32_t* n_pos, int32_t* perr_hits, int32_t* class_pos, void* stream);
 
 /* utility: out[i] = value for n floats (avoids torch for tiny fills inside C loops) */
 int evc_fill_f32(float* p, int64_t n, float value, void* stream);
