@@ -125,6 +125,7 @@ SIGNATURES = {
     "evc_dbof_wgrad_finish": [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp],
     "evc_topk_rows": [vp, i32, i32, i32, i32, vp, vp, vp],
     "evc_eval_select_rows": [vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp],
+    "evc_ensemble_topk_rows": [vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i64, vp],
 }
 EXPORTS = tuple(SIGNATURES) + ("evc_version", "evc_last_error")
 

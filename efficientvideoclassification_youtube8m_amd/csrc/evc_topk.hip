@@ -18,6 +18,11 @@
 // evc_eval_select_rows runs the same steps (shared __device__ helpers) for the evaluation binaries and adds what Hit@1 / PERR /
 // mAP need from the label row - the labels of the selected columns, the row's positive count, the PERR numerator and the
 // per-class positive counts - so that validate.py fetches [rows, k] + a few [rows] vectors instead of two [rows, cols] matrices.
+//
+// evc_ensemble_topk_rows puts a combination in front of the same steps: the rows of M member matrices are loaded by the thread that owns the
+// column group, combined in registers (per-class maximum in the total order, or a weighted mean with one rounding per operation) and written
+// to the LDS row once; the sparse lists of P earlier prediction files are then applied to that row, one file after another; the combined row
+// is selected from and / or stored whole.
 #include "evc_common.h"
 
 #include <mutex>
@@ -192,11 +197,12 @@ __device__ __forceinline__ void tk_sort_desc(unsigned long long* sv, int sort_n)
   __syncthreads();
 }
 
-// Steps 2 - 4 for the row in LDS (pass-0 histogram ready): sv[0 .. k) = the k first elements in the total order, sorted.
+// Steps 2 - 4 for the row in LDS (hist0_ready: hist holds the pass-0 histogram): sv[0 .. k) = the k first elements in the total order,
+// sorted.
 __device__ __forceinline__ void tk_select_sorted(const uint32_t* row, int cols, int k, int sort_n, unsigned long long* sv, uint32_t* hist,
-                                                 uint32_t* grp, uint32_t* scan_ws, uint32_t* sel) {
+                                                 uint32_t* grp, uint32_t* scan_ws, uint32_t* sel, bool hist0_ready = true) {
   uint32_t prefix, mask, krem;
-  tk_radix_select(row, cols, (uint32_t)k, true, hist, scan_ws, sel, prefix, mask, krem);
+  tk_radix_select(row, cols, (uint32_t)k, hist0_ready, hist, scan_ws, sel, prefix, mask, krem);
   const uint32_t n_gt = (uint32_t)k - krem;                          // (key & mask) > prefix: all admitted; == prefix: krem of them
   tk_group_prefix(row, cols, prefix, mask, grp, scan_ws);
   for (int j = k + threadIdx.x; j < sort_n; j += TK_THREADS) sv[j] = 0ull;   // padding: below every real entry
@@ -312,6 +318,159 @@ __global__ __launch_bounds__(TK_THREADS) void eval_select_rows_kernel(const floa
   }
 }
 
+// evc_ensemble_topk_rows: the combination of M member prediction matrices (and P sparse prior lists) in front of the selection above.
+// The host arrays of the entry (member pointers, row strides, weights) travel by value in the kernel's argument block.
+constexpr int ENS_MAX_M = 8;
+constexpr int ENS_MAX_P = 8;
+constexpr int ENS_MAX_KP = 256;
+struct EnsArgs {
+  const uint32_t* pred[ENS_MAX_M];
+  long ld[ENS_MAX_M];
+  float w[ENS_MAX_M + ENS_MAX_P];
+};
+
+// acc + w * x with the product and the sum each rounded to f32 (hipcc contracts a * b + c into one FMA by default, and its __fmul_rn /
+// __fadd_rn are plain operators that contract as well: contraction is switched off for these two functions).
+__device__ __forceinline__ float ens_mul(float w, float x) {
+#pragma clang fp contract(off)
+  return w * x;
+}
+__device__ __forceinline__ float ens_mul_add(float acc, float w, float x) {
+#pragma clang fp contract(off)
+  const float p = w * x;
+  return acc + p;
+}
+
+// One element of the combined row from the M member values (static indices after unrolling: x stays in registers).
+// mode 0: the value with the largest topk_key, the lowest member on equal keys; mode 1: w0 x0 + w1 x1 + ... left to right, every
+// product and every sum rounded to f32 on its own (ens_mul / ens_mul_add).
+__device__ __forceinline__ uint32_t ens_combine(const uint32_t (&x)[ENS_MAX_M], const EnsArgs& a, int M, int mode) {
+  if (mode == 0) {
+    uint32_t best = x[0], bk = topk_key(x[0]);
+#pragma unroll
+    for (int m = 1; m < ENS_MAX_M; ++m) {
+      if (m < M) {
+        const uint32_t km = topk_key(x[m]);
+        if (km > bk) {
+          best = x[m];
+          bk = km;
+        }
+      }
+    }
+    return best;
+  }
+  float acc = ens_mul(a.w[0], __uint_as_float(x[0]));
+#pragma unroll
+  for (int m = 1; m < ENS_MAX_M; ++m)
+    if (m < M) acc = ens_mul_add(acc, a.w[m], __uint_as_float(x[m]));
+  return __float_as_uint(acc);
+}
+
+__global__ __launch_bounds__(TK_THREADS) void ensemble_topk_rows_kernel(const EnsArgs a, int M, const int32_t* __restrict__ prior_idx,
+                                                                        const float* __restrict__ prior_val, int P, int kp, int rows, int cols,
+                                                                        int mode, int k, int sort_n, float* __restrict__ out_val,
+                                                                        int32_t* __restrict__ out_idx, float* __restrict__ out_dense,
+                                                                        long ld_dense) {
+  extern __shared__ __attribute__((aligned(16))) char tk_lds[];
+  unsigned long long* sv = (unsigned long long*)tk_lds;
+  uint32_t* hist = (uint32_t*)(tk_lds + TK_OFF_HIST);
+  uint32_t* grp = (uint32_t*)(tk_lds + TK_OFF_GRP);
+  uint32_t* scan_ws = (uint32_t*)(tk_lds + TK_OFF_MISC);
+  uint32_t* sel = scan_ws + 4;
+  uint32_t* row = (uint32_t*)(tk_lds + TK_OFF_ROW);                  // [cols] raw bits of the combined row
+  const int tid = threadIdx.x;
+  const long r = blockIdx.x;
+  const bool hist0 = P == 0 && k > 0;                                // the pass-0 histogram comes from the combined registers
+
+  hist[tid] = 0;
+  __syncthreads();
+
+  // ---- 1. the M member rows -> one combined row in LDS; a thread owns the same columns in every member ----
+  const uint32_t* xr[ENS_MAX_M];
+  bool al[ENS_MAX_M];
+#pragma unroll
+  for (int m = 0; m < ENS_MAX_M; ++m) {
+    xr[m] = m < M ? a.pred[m] + r * a.ld[m] : nullptr;
+    al[m] = (((uintptr_t)xr[m]) & 15) == 0;
+  }
+  const int n4 = cols >> 2;
+  for (int i = tid; i < n4; i += TK_THREADS) {
+    u32x4_t v[ENS_MAX_M];
+#pragma unroll
+    for (int m = 0; m < ENS_MAX_M; ++m) {                            // the M loads of the column group, back to back
+      if (m < M) {
+        if (al[m]) {
+          v[m] = *(const u32x4_t*)(xr[m] + 4 * i);
+        } else {                                                     // this member's rows are not 16-byte aligned
+          const uint32_t* q = xr[m] + 4 * i;
+          v[m] = u32x4_t{q[0], q[1], q[2], q[3]};
+        }
+      }
+    }
+    u32x4_t c;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      uint32_t x[ENS_MAX_M];
+#pragma unroll
+      for (int m = 0; m < ENS_MAX_M; ++m) x[m] = m < M ? v[m][j] : 0u;
+      c[j] = ens_combine(x, a, M, mode);
+    }
+    *(u32x4_t*)(row + 4 * i) = c;
+    if (hist0) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) atomicAdd(&hist[topk_key(c[j]) >> 24], 1u);
+    }
+  }
+  for (int i = 4 * n4 + tid; i < cols; i += TK_THREADS) {
+    uint32_t x[ENS_MAX_M];
+#pragma unroll
+    for (int m = 0; m < ENS_MAX_M; ++m) x[m] = m < M ? xr[m][i] : 0u;
+    const uint32_t c = ens_combine(x, a, M, mode);
+    row[i] = c;
+    if (hist0) atomicAdd(&hist[topk_key(c) >> 24], 1u);
+  }
+  __syncthreads();
+
+  // ---- 1b. the sparse prior lists of this row, one file after another (indices within a list are distinct: no two threads of a
+  // file meet in one column); an index outside [0, cols) is padding ----
+  for (int p = 0; p < P; ++p) {
+    const long o = ((long)p * rows + r) * kp;
+    const float w = mode == 1 ? a.w[M + p] : 0.f;
+    for (int e = tid; e < kp; e += TK_THREADS) {
+      const int32_t c = prior_idx[o + e];
+      if (c >= 0 && c < cols) {
+        const float val = prior_val[o + e];
+        if (mode == 0) {
+          if (topk_key(__float_as_uint(val)) > topk_key(row[c])) row[c] = __float_as_uint(val);
+        } else {
+          row[c] = __float_as_uint(ens_mul_add(__uint_as_float(row[c]), w, val));
+        }
+      }
+    }
+    __syncthreads();
+  }
+
+  // ---- the dense exit: the combined row as it stands in LDS ----
+  if (out_dense != nullptr) {
+    uint32_t* d = (uint32_t*)out_dense + r * ld_dense;
+    if ((((uintptr_t)d) & 15) == 0) {
+      for (int i = tid; i < n4; i += TK_THREADS) *(u32x4_t*)(d + 4 * i) = *(const u32x4_t*)(row + 4 * i);
+      for (int i = 4 * n4 + tid; i < cols; i += TK_THREADS) d[i] = row[i];
+    } else {
+      for (int i = tid; i < cols; i += TK_THREADS) d[i] = row[i];
+    }
+  }
+  if (k == 0) return;                                                // block-uniform
+
+  tk_select_sorted(row, cols, k, sort_n, sv, hist, grp, scan_ws, sel, hist0);
+  const long o = r * k;
+  for (int j = tid; j < k; j += TK_THREADS) {
+    const uint32_t col = ~(uint32_t)sv[j];
+    out_idx[o + j] = (int32_t)col;
+    out_val[o + j] = __uint_as_float(row[col]);
+  }
+}
+
 }  // namespace
 
 extern "C" int evc_topk_rows(const float* x, int ld, int rows, int cols, int k, float* out_val, int32_t* out_idx, void* stream) {
@@ -355,6 +514,51 @@ extern "C" int evc_eval_select_rows(const float* pred, int ld, const uint8_t* la
   });
   hipLaunchKernelGGL(eval_select_rows_kernel, dim3(rows), dim3(TK_THREADS), lds, (hipStream_t)stream, pred, (long)ld, labels, (long)ld_lab,
                      cols, k, sort_n, top_val, top_idx, top_lab, n_pos, perr_hits, class_pos);
+  EVC_LAUNCH_CHECK();
+  return EVC_OK;
+}
+
+extern "C" int evc_ensemble_topk_rows(const float* const* preds, const int64_t* ld, const float* weights, int M, const int32_t* prior_idx,
+                                      const float* prior_val, int P, int kp, int rows, int cols, int mode, int k, float* out_val,
+                                      int32_t* out_idx, float* out_dense, int64_t ld_dense, void* stream) {
+  EVC_REQUIRE(M >= 1 && M <= ENS_MAX_M, EVC_ERR_BAD_ARG, "evc_ensemble_topk_rows: M=%d (1 .. %d)", M, ENS_MAX_M);
+  EVC_REQUIRE(P >= 0 && P <= ENS_MAX_P, EVC_ERR_BAD_ARG, "evc_ensemble_topk_rows: P=%d (0 .. %d)", P, ENS_MAX_P);
+  EVC_REQUIRE(P == 0 || (kp >= 1 && kp <= ENS_MAX_KP), EVC_ERR_BAD_ARG, "evc_ensemble_topk_rows: kp=%d (1 .. %d)", kp, ENS_MAX_KP);
+  EVC_REQUIRE(mode == 0 || mode == 1, EVC_ERR_BAD_ARG, "evc_ensemble_topk_rows: mode=%d (0 = max, 1 = weighted mean)", mode);
+  EVC_REQUIRE(cols >= 1 && cols <= TK_MAX_COLS, EVC_ERR_BAD_ARG, "evc_ensemble_topk_rows: cols=%d (1 .. %d)", cols, TK_MAX_COLS);
+  EVC_REQUIRE(k >= 0 && k <= cols && k <= TK_MAX_K, EVC_ERR_BAD_ARG, "evc_ensemble_topk_rows: k=%d (0 .. min(cols=%d, %d))", k, cols, TK_MAX_K);
+  EVC_REQUIRE(rows >= 0, EVC_ERR_BAD_ARG, "evc_ensemble_topk_rows: rows=%d", rows);
+  EVC_REQUIRE(preds != nullptr && ld != nullptr && (mode == 0 || weights != nullptr), EVC_ERR_BAD_ARG,
+              "evc_ensemble_topk_rows: NULL host array");
+  for (int m = 0; m < M; ++m)
+    EVC_REQUIRE(ld[m] >= cols, EVC_ERR_BAD_ARG, "evc_ensemble_topk_rows: ld[%d]=%lld < cols=%d", m, (long long)ld[m], cols);
+  EVC_REQUIRE(out_dense == nullptr || ld_dense >= cols, EVC_ERR_BAD_ARG, "evc_ensemble_topk_rows: ld_dense=%lld < cols=%d",
+              (long long)ld_dense, cols);
+  if (rows == 0) return EVC_OK;                                      // (an empty tensor's pointer may be NULL: the pointers are looked at below)
+  if (k == 0)
+    EVC_REQUIRE(out_val == nullptr && out_idx == nullptr && out_dense != nullptr, EVC_ERR_BAD_ARG,
+                "evc_ensemble_topk_rows: k=0 takes out_val = out_idx = NULL and a dense output");
+  else
+    EVC_REQUIRE(out_val != nullptr && out_idx != nullptr, EVC_ERR_BAD_ARG, "evc_ensemble_topk_rows: NULL argument");
+  for (int m = 0; m < M; ++m) EVC_REQUIRE(preds[m] != nullptr, EVC_ERR_BAD_ARG, "evc_ensemble_topk_rows: NULL member %d", m);
+  EVC_REQUIRE(P == 0 || (prior_idx != nullptr && prior_val != nullptr), EVC_ERR_BAD_ARG, "evc_ensemble_topk_rows: NULL prior lists");
+  EnsArgs a;
+  memset(&a, 0, sizeof(a));
+  for (int m = 0; m < M; ++m) {
+    a.pred[m] = (const uint32_t*)preds[m];
+    a.ld[m] = (long)ld[m];
+  }
+  if (mode == 1)
+    for (int j = 0; j < M + P; ++j) a.w[j] = weights[j];
+  int sort_n = 1;
+  while (sort_n < k) sort_n <<= 1;
+  const size_t lds = (size_t)TK_OFF_ROW + (size_t)((cols + 3) & ~3) * sizeof(uint32_t);
+  static std::once_flag once;
+  std::call_once(once, [] {
+    (void)hipFuncSetAttribute((const void*)ensemble_topk_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TK_MAX_LDS);
+  });
+  hipLaunchKernelGGL(ensemble_topk_rows_kernel, dim3(rows), dim3(TK_THREADS), lds, (hipStream_t)stream, a, M, prior_idx, prior_val, P, kp,
+                     rows, cols, mode, k, sort_n, out_val, out_idx, out_dense, (long)ld_dense);
   EVC_LAUNCH_CHECK();
   return EVC_OK;
 }

@@ -830,6 +830,34 @@ class EvalGraph:
         return dict(predictions=t_pred, teacher_state=t_state, teacher_predictions=t_pred)
 
 
+class EnsembleGraph:
+    """N forward-only members for one input: each an EvalGraph that is ``teacher_only`` or ``student_only`` at its own every_n, all on
+    one device with one --precision and one set of model sizes (``members``: list of (tower, every_n), tower 'teacher' | 'student';
+    the other arguments are EvalGraph's).  step() runs every member on the same input tensors and returns their prediction tensors,
+    each the buffer of that member's own tower, so all of them are alive together for ops.ensemble_topk_rows."""
+
+    def __init__(self, batch_size, members, **kw):
+        if not members:
+            raise ValueError("EnsembleGraph: no members")
+        self.members = []
+        for tower, every_n in members:
+            if tower not in ("teacher", "student"):
+                raise ValueError("EnsembleGraph: tower %r (teacher | student)" % (tower,))
+            self.members.append(EvalGraph(batch_size, every_n=every_n, student_only=tower == "student", teacher_only=tower == "teacher", **kw))
+
+    def restore(self, state_dicts):
+        """Each member restores its own checkpoint (the 11 variables of its tower by name)."""
+        if len(state_dicts) != len(self.members):
+            raise ValueError("EnsembleGraph.restore: %d state dicts for %d members" % (len(state_dicts), len(self.members)))
+        for g, sd in zip(self.members, state_dicts):
+            g.restore(sd)
+
+    def step(self, x_raw, labels_u8, num_frames, num_frames_host=None):
+        if num_frames_host is None:
+            num_frames_host = num_frames.cpu()
+        return [g.step(x_raw, labels_u8, num_frames, num_frames_host=num_frames_host)["predictions"] for g in self.members]
+
+
 class SingleTowerGraph:
     """Teacher-only training step for dict-returning models (DbofModel,
     FrameLevelLogisticModel).  The reference's train.py cannot run these

@@ -98,6 +98,18 @@ _define("metrics_on_device", False, _bool, "validate / eval_finetune: select wha
         "(ops.eval_select_rows) and fetch [B, top_k] + a few [B] vectors instead of the [B, 4716] predictions and labels; same metrics bit "
         "for bit except for rows with an exact tie at the top_k-th / label-count-th place, where the device admits the lowest class "
         "(eval_util.EvaluationMetrics.accumulate_selected); needs 1 <= top_k <= min(256, classes)")
+# ---- ensembles (inference / validate; cs/inference_ensemble.py:28-61 has preds_pattern, the others are additions) -----------------------
+_define("ensemble_dirs", "", str, "comma separated checkpoint directories of the ensemble's members (1 .. 8); '' = the single model of "
+        "--train_dir, which is not consulted otherwise.  Every member runs its forward on the same batch and ops.ensemble_topk_rows "
+        "combines and selects in one launch")
+_define("ensemble_towers", "", str, "one word per member from auto|teacher|student: auto = the tower the checkpoint's variables name "
+        "(inference.serving_tower), student on a train.py checkpoint = its model_student/*; '' = auto for all")
+_define("ensemble_every_n", "", str, "one every_n per member (ignored for teachers); '' = --every_n for all")
+_define("ensemble_mode", "max", str, "max (per-class maximum, cs/max_ensemble.py) | mean (weighted mean)")
+_define("ensemble_weights", "", str, "comma separated weights, one per member and then one per --preds_pattern file; mean mode only; "
+        "'' = 1 / (members + files) each")
+_define("preds_pattern", "", str, "inference: glob of earlier VideoId,LabelConfidencePairs files, sorted by name, that join the ensemble as "
+        "sparse members (a class a file does not list counts 0; cs/inference_ensemble.py:155-193)")
 
 
 class FlagValues(object):

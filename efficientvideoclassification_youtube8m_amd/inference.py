@@ -14,6 +14,16 @@ train_finetune checkpoint (``model_student/*`` only) serves the student at --eve
 Replaced: TF session / queue runners -> readers.get_input_evaluation_tensors + distill.EvalGraph; argpartition + sort of the
 [B, 4716] predictions on the host -> ops.topk_rows (evc_topk_rows) on the device behind the MoE head: only the [B, top_k]
 values and indices are copied back, and batch k is formatted while the GPU runs batch k+1.
+
+Ensembles (cs/inference_ensemble.py:155-193 --preds_pattern, cs/max_ensemble.py): with ``--ensemble_dirs dirA,dirB,...`` every member
+(``--ensemble_towers`` auto|teacher|student, ``--ensemble_every_n``) runs its forward on the same batch, the lists of the earlier prediction
+files matched by ``--preds_pattern`` join as sparse members, and one launch of ops.ensemble_topk_rows (evc_ensemble_topk_rows) combines them
+(``--ensemble_mode`` max | mean, ``--ensemble_weights``) and selects: the frames are read once and still only [B, top_k] leaves the device.
+
+    python -m efficientvideoclassification_youtube8m_amd.inference \
+        --input_data_pattern "./yt8m/test*.tfrecord" --output_file ./predictions_ensemble.csv --top_k 20 --batch_size 1024 \
+        --ensemble_dirs "./model_train/,./model_train/,./model_every30_finetune/" --ensemble_towers "teacher,student,auto" \
+        --ensemble_every_n "1,10,30" --ensemble_mode max --preds_pattern "./earlier_predictions/*.csv"  (+ the model / input flags above)
 """
 from __future__ import annotations
 
@@ -26,7 +36,7 @@ import numpy as np
 import torch
 
 from . import frame_level_models, ops, readers, utils, video_level_models
-from .distill import EvalGraph
+from .distill import EnsembleGraph, EvalGraph
 from .flags import FLAGS
 from .train import NUM_CLASSES, find_class_by_name, get_reader, latest_checkpoint
 
@@ -44,8 +54,111 @@ def format_lines(video_ids, values, indices):
         yield vid + "," + " ".join("%i %f" % pair for pair in zip(i, v)) + "\n"
 
 
+def _words(text):
+    return [w.strip() for w in text.split(",")] if text.strip() else []
+
+
+def ensemble_spec(allow_preds_files=True):
+    """The ensemble the flags describe, checked: None without --ensemble_dirs, else dict(dirs, towers, every_n [M]; mode; weights
+    float32 [M + P] or None; files [P], sorted by name as cs/inference_ensemble.py:169-170).  Raises ValueError for everything that can be
+    refused before the device is touched."""
+    dirs = _words(FLAGS.ensemble_dirs)
+    towers, every_n, weights = _words(FLAGS.ensemble_towers), _words(FLAGS.ensemble_every_n), _words(FLAGS.ensemble_weights)
+    if FLAGS.preds_pattern != "" and not allow_preds_files:
+        raise ValueError("--preds_pattern: earlier prediction files join an ensemble in inference only")
+    if not dirs:
+        if FLAGS.preds_pattern != "":
+            raise ValueError("--preds_pattern without --ensemble_dirs: no model is served that the files could join")
+        for name, given in (("towers", towers), ("every_n", every_n), ("weights", weights)):
+            if given:
+                raise ValueError("--ensemble_%s: %d entries for 0 --ensemble_dirs" % (name, len(given)))
+        return None
+    M = len(dirs)
+    if M > ops.ENSEMBLE_MAX_MEMBERS or "" in dirs:
+        raise ValueError("--ensemble_dirs: %d members (1 .. %d, none empty)" % (M, ops.ENSEMBLE_MAX_MEMBERS))
+    towers = towers or ["auto"] * M
+    every_n = every_n or [str(FLAGS.every_n)] * M
+    for name, given in (("towers", towers), ("every_n", every_n)):
+        if len(given) != M:
+            raise ValueError("--ensemble_%s: %d entries for %d --ensemble_dirs" % (name, len(given), M))
+    for t in towers:
+        if t not in ("auto", "teacher", "student"):
+            raise ValueError("--ensemble_towers: %r (auto | teacher | student)" % t)
+    every_n = [int(e) for e in every_n]
+    if FLAGS.ensemble_mode not in ops.ENSEMBLE_MODES:
+        raise ValueError("--ensemble_mode %r (max | mean)" % FLAGS.ensemble_mode)
+    files = []
+    if FLAGS.preds_pattern != "":
+        files = sorted(glob.glob(FLAGS.preds_pattern))
+        if not files:
+            raise ValueError("--preds_pattern '%s' matches no file" % FLAGS.preds_pattern)
+        if len(files) > ops.ENSEMBLE_MAX_PRIORS:
+            raise ValueError("--preds_pattern: %d files (at most %d)" % (len(files), ops.ENSEMBLE_MAX_PRIORS))
+    w = None
+    if weights:
+        if FLAGS.ensemble_mode != "mean":
+            raise ValueError("--ensemble_weights needs --ensemble_mode mean (max has no weights)")
+        if len(weights) != M + len(files):
+            raise ValueError("--ensemble_weights: %d entries for %d members + %d prediction files" % (len(weights), M, len(files)))
+        w = np.asarray([float(x) for x in weights], np.float32)
+    return dict(dirs=dirs, towers=towers, every_n=every_n, mode=FLAGS.ensemble_mode, weights=w, files=files)
+
+
+def read_prediction_file(path, num_classes=NUM_CLASSES):
+    """A ``VideoId,LabelConfidencePairs`` file (format_lines; read_pred_file of cs/inference_ensemble.py:155-167) as
+    {video id: (classes int32 [n], confidences float32 [n])}, pairs in the order of the line.  ValueError for a missing header, a
+    malformed line, a class repeated within a line or outside [0, num_classes), or more than 256 pairs (evc_ensemble_topk_rows' kp)."""
+    table = {}
+    with open(path) as f:
+        if f.readline() != HEADER:
+            raise ValueError("%s: the first line is not %r" % (path, HEADER.strip()))
+        for lineno, line in enumerate(f, 2):
+            line = line.rstrip("\n")
+            if line == "":
+                continue
+            vid, sep, pairs = line.partition(",")
+            toks = pairs.split()
+            if sep == "" or len(toks) % 2:
+                raise ValueError("%s:%d: not 'id,class conf class conf ...'" % (path, lineno))
+            if len(toks) // 2 > ops.ENSEMBLE_MAX_KP:
+                raise ValueError("%s:%d: %d pairs (at most %d)" % (path, lineno, len(toks) // 2, ops.ENSEMBLE_MAX_KP))
+            cls = np.asarray([int(t) for t in toks[0::2]], np.int64)
+            conf = np.asarray([float(t) for t in toks[1::2]], np.float32)
+            if cls.size and (cls.min() < 0 or cls.max() >= num_classes):
+                raise ValueError("%s:%d: class outside [0, %d)" % (path, lineno, num_classes))
+            if np.unique(cls).size != cls.size:
+                raise ValueError("%s:%d: a class is listed twice" % (path, lineno))
+            table[vid] = (cls.astype(np.int32), conf)
+    return table
+
+
+def prior_list_length(tables):
+    """kp of a set of parsed prediction files: their longest list (at least 1)."""
+    return max([1] + [c.size for t in tables for c, _ in t.values()])
+
+
+def gather_priors(tables, files, video_ids, kp, out=None):
+    """The lists of one batch as the arrays evc_ensemble_topk_rows reads: (idx int32, val float32) [P, B, kp] in the order of tables
+    and of video_ids, shorter lists padded with idx = -1 (val 0).  out: arrays to fill (the loop passes pinned ones).  A video id that
+    a file does not hold is a KeyError naming both (the reference fails there too, cs/inference_ensemble.py:190)."""
+    P, B = len(tables), len(video_ids)
+    idx, val = out if out is not None else (np.empty((P, B, kp), np.int32), np.empty((P, B, kp), np.float32))
+    idx[...] = -1
+    val[...] = 0
+    for p, (table, path) in enumerate(zip(tables, files)):
+        for b, vid in enumerate(video_ids):
+            if isinstance(vid, bytes):
+                vid = vid.decode("utf-8")
+            if vid not in table:
+                raise KeyError("video id %r is not in the prediction file %s" % (vid, path))
+            cls, conf = table[vid]
+            idx[p, b, :cls.size] = cls
+            val[p, b, :cls.size] = conf
+    return idx, val
+
+
 def check_flags():
-    """Everything that is refused before a record is read or the device is touched."""
+    """Everything that is refused before a record is read or the device is touched.  Returns ensemble_spec()."""
     if FLAGS.output_file == "":
         raise ValueError("'output_file' was not specified. Unable to continue with inference.")
     if FLAGS.input_data_pattern == "":
@@ -59,6 +172,7 @@ def check_flags():
     top_max = min(ops.TOPK_MAX_K, NUM_CLASSES)
     if not 1 <= FLAGS.top_k <= top_max:
         raise ValueError("--top_k %d: must be in [1, %d]" % (FLAGS.top_k, top_max))
+    return ensemble_spec()
 
 
 def serving_tower(state_dict):
@@ -72,6 +186,43 @@ def serving_tower(state_dict):
     raise ValueError("the checkpoint holds neither model/* nor model_student/* variables")
 
 
+def member_tower(state_dict, word, where=""):
+    """The tower a member serves: 'auto' = serving_tower(); 'teacher' / 'student' = that tower, which the checkpoint must hold
+    ('student' on a train.py checkpoint serves the student trained next to the teacher)."""
+    if word == "auto":
+        return serving_tower(state_dict)
+    scope = "model/" if word == "teacher" else "model_student/"
+    if not any(k.startswith(scope) and torch.is_tensor(v) for k, v in state_dict.items()):
+        raise ValueError("the checkpoint %sholds no %s* variables: it cannot serve the %s" % (where + " " if where else "", scope, word))
+    return word
+
+
+def load_members(spec):
+    """Checkpoints and towers of an ensemble_spec(): ([state dict per member], [(dir, tower, every_n)], [checkpoint path]).  A
+    directory listed twice is read once."""
+    loaded, sds, members, cks = {}, [], [], []
+    for d, word, every_n in zip(spec["dirs"], spec["towers"], spec["every_n"]):
+        if d not in loaded:
+            ck = latest_checkpoint(d)
+            if ck is None:
+                raise IOError("unable to find a checkpoint at location: %s" % d)
+            logging.info("restoring variables from " + ck)
+            loaded[d] = (ck, torch.load(ck, map_location="cpu"))
+        ck, sd = loaded[d]
+        sds.append(sd)
+        cks.append(ck)
+        members.append((d, member_tower(sd, word, ck), every_n))
+    return sds, members, cks
+
+
+def build_ensemble_graph(reader, members, batch_size, device):
+    """Forward-only graphs of an ensemble's members (members: (dir, tower, every_n)); sizes and --precision shared."""
+    return EnsembleGraph(batch_size, [(tower, every_n) for _, tower, every_n in members], feature_size=sum(reader.feature_sizes),
+                         vocab_size=reader.num_classes, max_frames=FLAGS.max_num_frames, num_inputs_to_lstm=FLAGS.num_inputs_to_lstm,
+                         lstm_cells=FLAGS.lstm_cells, lstm_layers=FLAGS.lstm_layers, num_mixtures=FLAGS.moe_num_mixtures, device=device,
+                         precision=FLAGS.precision)
+
+
 def build_graph(reader, tower, batch_size, device):
     """Forward-only graph of the one tower served (EvalGraph: the validate / eval_finetune forward, row plans and --precision)."""
     return EvalGraph(batch_size, every_n=FLAGS.every_n, student_only=tower == "student", teacher_only=tower == "teacher",
@@ -80,20 +231,19 @@ def build_graph(reader, tower, batch_size, device):
                      num_mixtures=FLAGS.moe_num_mixtures, device=device, precision=FLAGS.precision)
 
 
-def inference(reader, train_dir, data_pattern, out_file_location, batch_size, top_k):
-    """cs/inference_ensemble.py:113-210 without the ensembling inputs.  Returns the counts and the host-side time split:
-    reader_wait_s (blocked on the reader threads / staging), fetch_wait_s (blocked on a batch's values + indices),
-    format_s (text formatting and writing)."""
-    files = sorted(glob.glob(data_pattern))
-    if not files:
-        raise IOError("Unable to find input files. data_pattern='" + data_pattern + "'")
-    logging.info("number of input files: " + str(len(files)))
+def _open_device():
+    torch.cuda.set_device(FLAGS.gpu)
+    ops.check_device(FLAGS.gpu)
+    return "cuda:%d" % FLAGS.gpu
+
+
+def _single_selector(reader, train_dir, batch_size, top_k, stats):
+    """The one tower of --train_dir: (select, device) with select(ids, q, labels, n, n_host) -> (values, indices) on the device.  A
+    missing checkpoint is reported before the device is touched."""
     ck = latest_checkpoint(train_dir)
     if ck is None:
         raise IOError("unable to find a checkpoint at location: %s" % train_dir)
-    device = "cuda:%d" % FLAGS.gpu
-    torch.cuda.set_device(FLAGS.gpu)
-    ops.check_device(FLAGS.gpu)
+    device = _open_device()
     logging.info("restoring variables from " + ck)
     sd = torch.load(ck, map_location="cpu")
     tower = serving_tower(sd)
@@ -101,10 +251,59 @@ def inference(reader, train_dir, data_pattern, out_file_location, batch_size, to
     graph.restore(sd)
     logging.info("serving the %s tower (%s/*)%s", tower, "model" if tower == "teacher" else "model_student",
                  " at every_n = %d" % FLAGS.every_n if tower == "student" else "")
+    stats.update(tower=tower, checkpoint=ck, members=[(train_dir, tower, FLAGS.every_n)])
+
+    def select(ids, q, labels, n, n_host):
+        predictions = graph.step(q, labels, n, num_frames_host=n_host)["predictions"]
+        return ops.topk_rows(predictions, top_k)                           # same stream, right behind the MoE head
+    return select, device
+
+
+def _ensemble_selector(reader, spec, batch_size, top_k, stats):
+    """The members of --ensemble_dirs and the files of --preds_pattern: (select, device), select(...) -> (values, indices) of their
+    combination.  Unreadable prediction files and missing checkpoints are reported before the device is touched."""
+    tables = []
+    for path in spec["files"]:
+        logging.info("reading: " + path)
+        tables.append(read_prediction_file(path, reader.num_classes))
+    kp = prior_list_length(tables)
+    sds, members, cks = load_members(spec)
+    device = _open_device()
+    graph = build_ensemble_graph(reader, members, batch_size, device)
+    graph.restore(sds)
+    for d, tower, every_n in members:
+        logging.info("ensemble member: the %s tower of %s%s", tower, d, " at every_n = %d" % every_n if tower == "student" else "")
+    logging.info("ensemble: %d members + %d prediction files, mode %s", len(members), len(tables), spec["mode"])
+    stats.update(tower="ensemble", checkpoint=cks, members=members)
+
+    def select(ids, q, labels, n, n_host):
+        priors = None
+        if tables:                                                         # this batch's lists: pinned arrays, copied on the stream
+            shape = (len(tables), len(ids), kp)
+            idx_h, val_h = torch.empty(shape, dtype=torch.int32, pin_memory=True), torch.empty(shape, dtype=torch.float32, pin_memory=True)
+            gather_priors(tables, spec["files"], ids, kp, out=(idx_h.numpy(), val_h.numpy()))
+            priors = (idx_h.to(device, non_blocking=True), val_h.to(device, non_blocking=True))
+        preds = graph.step(q, labels, n, num_frames_host=n_host)
+        return ops.ensemble_topk_rows(preds, top_k, mode=spec["mode"], weights=spec["weights"], priors=priors)
+    return select, device
+
+
+def inference(reader, train_dir, data_pattern, out_file_location, batch_size, top_k, ensemble=None):
+    """cs/inference_ensemble.py:113-210.  ensemble: None = the one tower of train_dir, else an ensemble_spec() (train_dir is then not
+    consulted).  Returns the counts, the members served as (dir, tower, every_n) and the host-side time split: reader_wait_s (blocked
+    on the reader threads / staging), fetch_wait_s (blocked on a batch's values + indices), format_s (text formatting and writing)."""
+    files = sorted(glob.glob(data_pattern))
+    if not files:
+        raise IOError("Unable to find input files. data_pattern='" + data_pattern + "'")
+    logging.info("number of input files: " + str(len(files)))
+    stats = dict(tower=None, checkpoint=None, members=None, videos=0, batches=0, reader_wait_s=0.0, fetch_wait_s=0.0, format_s=0.0)
+    if ensemble is None:
+        select, device = _single_selector(reader, train_dir, batch_size, top_k, stats)
+    else:
+        select, device = _ensemble_selector(reader, ensemble, batch_size, top_k, stats)
     pipe = readers.get_input_evaluation_tensors(reader, files, batch_size=batch_size, num_readers=FLAGS.num_readers, device=device,
                                                 with_host_counts=True)
     fetcher = utils.AsyncFetcher(device)
-    stats = dict(tower=tower, checkpoint=ck, videos=0, batches=0, reader_wait_s=0.0, fetch_wait_s=0.0, format_s=0.0)
     start = time.time()
     with open(out_file_location, "w") as out_file:
         out_file.write(HEADER)
@@ -130,8 +329,7 @@ def inference(reader, train_dir, data_pattern, out_file_location, batch_size, to
             except StopIteration:
                 break
             stats["reader_wait_s"] += time.perf_counter() - t0
-            predictions = graph.step(q, labels, n, num_frames_host=n_host)["predictions"]
-            values, indices = ops.topk_rows(predictions, top_k)            # same stream, right behind the MoE head
+            values, indices = select(ids, q, labels, n, n_host)
             handle = fetcher.fetch({"values": values, "indices": indices})
             stats["batches"] += 1
             if pending is not None:
@@ -149,9 +347,9 @@ def inference(reader, train_dir, data_pattern, out_file_location, batch_size, to
 def main(argv=None):
     FLAGS.parse(sys.argv[1:] if argv is None else argv)
     logging.basicConfig(level=logging.INFO, format="INFO:evc:%(message)s")
-    check_flags()
+    ensemble = check_flags()
     reader = get_reader()
-    return inference(reader, FLAGS.train_dir, FLAGS.input_data_pattern, FLAGS.output_file, FLAGS.batch_size, FLAGS.top_k)
+    return inference(reader, FLAGS.train_dir, FLAGS.input_data_pattern, FLAGS.output_file, FLAGS.batch_size, FLAGS.top_k, ensemble)
 
 
 if __name__ == "__main__":

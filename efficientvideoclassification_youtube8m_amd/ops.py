@@ -626,6 +626,70 @@ def eval_select_rows(predictions, labels, k):
     return out
 
 
+ENSEMBLE_MAX_MEMBERS = 8   # evc_ensemble_topk_rows: 1 <= M <= 8 dense members, 0 <= P <= 8 sparse prior lists of 1 <= kp <= 256 entries
+ENSEMBLE_MAX_PRIORS = 8
+ENSEMBLE_MAX_KP = 256
+ENSEMBLE_MODES = {"max": 0, "mean": 1}
+
+
+def ensemble_topk_rows(preds, k, mode="max", weights=None, priors=None, dense=False):
+    """The members' predictions combined and selected in one launch on the current stream (evc_ensemble_topk_rows).  preds: list of M
+    2-D f32 device tensors of one shape (rows contiguous, any row stride); priors: None or (idx [P, B, kp] int32, val [P, B, kp] f32)
+    on the device - the sparse (class, confidence) lists of P earlier prediction files for these rows, padded with idx = -1, classes
+    distinct within a list.  mode "max": per class the largest value in the order of topk_rows, the lowest member on ties, then the
+    prior files in order; "mean": w[0] x_0 + w[1] x_1 + ... + w[M + p] val_p left to right, one f32 rounding per operation, weights
+    [M + P] (default np.float32(1) / np.float32(M + P) each).  Returns (values [B, k] f32, indices [B, k] int32) of the combined row in
+    the order of topk_rows, and with dense=True also the combined [B, C] tensor; k = 0 needs dense=True and selects nothing."""
+    import numpy as np
+    preds = list(preds)
+    M = len(preds)
+    if not 1 <= M <= ENSEMBLE_MAX_MEMBERS:
+        raise _lib.EvcError("ensemble_topk_rows: %d members (1 .. %d)" % (M, ENSEMBLE_MAX_MEMBERS))
+    if mode not in ENSEMBLE_MODES:
+        raise _lib.EvcError("ensemble_topk_rows: mode %r (max | mean)" % (mode,))
+    x0 = preds[0]
+    for x in preds:
+        if not torch.is_tensor(x) or not x.is_cuda:
+            raise _lib.EvcError("ensemble_topk_rows: evc ops need device tensors (got a CPU tensor); there is no CPU path")
+        if x.dtype != F32 or x.dim() != 2 or (x.shape[0] > 0 and x.shape[1] > 1 and x.stride(1) != 1):
+            raise _lib.EvcError("ensemble_topk_rows: needs 2-D float32 tensors with contiguous rows (got %s %s)" % (x.dtype, tuple(x.shape)))
+        if tuple(x.shape) != tuple(x0.shape) or x.device != x0.device:
+            raise _lib.EvcError("ensemble_topk_rows: members differ: %s on %s, %s on %s" % (tuple(x0.shape), x0.device, tuple(x.shape), x.device))
+    B, cols = x0.shape
+    P, kp, pidx, pval = 0, 0, None, None
+    if priors is not None:
+        pidx, pval = priors
+        if (not pidx.is_cuda or not pval.is_cuda or pidx.device != x0.device or pval.device != x0.device or pidx.dtype != torch.int32
+                or pval.dtype != F32 or pidx.dim() != 3 or tuple(pidx.shape) != tuple(pval.shape) or pidx.shape[1] != B
+                or not pidx.is_contiguous() or not pval.is_contiguous()):
+            raise _lib.EvcError("ensemble_topk_rows: priors are a contiguous (idx [P, %d, kp] int32, val [P, %d, kp] float32) pair on %s" % (B, B, x0.device))
+        P, kp = int(pidx.shape[0]), int(pidx.shape[2])
+        if P == 0:
+            pidx = pval = None
+        elif P > ENSEMBLE_MAX_PRIORS or not 1 <= kp <= ENSEMBLE_MAX_KP:
+            raise _lib.EvcError("ensemble_topk_rows: %d prior lists of %d entries (at most %d of 1 .. %d)" % (P, kp, ENSEMBLE_MAX_PRIORS, ENSEMBLE_MAX_KP))
+    if weights is None:
+        w = np.full(M + P, np.float32(1) / np.float32(M + P), np.float32)
+    else:
+        if mode != "mean":
+            raise _lib.EvcError("ensemble_topk_rows: weights are read in mode 'mean' only")
+        w = np.ascontiguousarray(np.asarray(weights, np.float32).reshape(-1))
+        if w.size != M + P:
+            raise _lib.EvcError("ensemble_topk_rows: %d weights for %d members + %d prior lists" % (w.size, M, P))
+    kk = int(k)
+    if kk == 0 and not dense:
+        raise _lib.EvcError("ensemble_topk_rows: k = 0 without dense=True asks for nothing")
+    values = torch.empty((B, max(kk, 0)), dtype=F32, device=x0.device)
+    indices = torch.empty((B, max(kk, 0)), dtype=torch.int32, device=x0.device)
+    out = torch.empty((B, cols), dtype=F32, device=x0.device) if dense else None
+    ptrs = (C.c_void_p * M)(*[x.data_ptr() for x in preds])
+    lds = (C.c_int64 * M)(*[x.stride(0) if B > 1 else cols for x in preds])
+    ws = (C.c_float * (M + P))(*w.tolist())
+    _lib.call("evc_ensemble_topk_rows", ptrs, lds, ws, M, _p(pidx), _p(pval), P, kp, B, cols, ENSEMBLE_MODES[mode], kk,
+              _p(values) if kk != 0 else None, _p(indices) if kk != 0 else None, _p(out), cols, _stream())
+    return (values, indices, out) if dense else (values, indices)
+
+
 # ---------------------------------------------------------------------------
 def moe_tail_fwd(gate_logits, expert_logits, B, V, M, pred, rowsum):
     _lib.call("evc_moe_tail_fwd", _p(gate_logits), _p(expert_logits), B, V, M, _p(pred), _p(rowsum), _stream())

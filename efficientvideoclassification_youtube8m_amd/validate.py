@@ -17,6 +17,10 @@ when the global step has not moved, looping until --run_once.  Replaced: TF sess
 ``--metrics_on_device True`` (off by default) keeps the [B, 4716] predictions and labels on the device: ops.eval_select_rows
 (evc_eval_select_rows) runs behind the MoE head and the fetch carries [B, top_k] values / classes / labels, two [B] vectors and
 the per-class positive counts, which EvaluationMetrics.accumulate_selected turns into the same numbers (ties: see there).
+``--ensemble_dirs`` (+ --ensemble_towers / --ensemble_every_n / --ensemble_mode / --ensemble_weights, see inference.py; needs
+``--run_once True``) evaluates the combination of several checkpoints: every member runs on the batch, ops.ensemble_topk_rows writes the
+combined [B, 4716] predictions, and the loss (ops.ce_loss) and the metrics - host or --metrics_on_device - are those of the combination;
+no student_state_loss is reported and --train_dir only receives events.jsonl.
 """
 from __future__ import annotations
 
@@ -58,6 +62,19 @@ def build_graph(reader, model, batch_size, device, student_only=False):
                      precision=FLAGS.precision)
 
 
+def build_ensemble(reader, model, spec, batch_size, device):
+    """The members of an inference.ensemble_spec(), restored, behind one step() that returns their combination."""
+    from . import inference
+    if not isinstance(model, frame_level_models.HierarchicalLstmModel):
+        raise NotImplementedError("an ensemble serves H-LSTM teacher / student towers; model %s has no path here" % type(model).__name__)
+    sds, members, _ = inference.load_members(spec)
+    graph = inference.build_ensemble_graph(reader, members, batch_size, device)
+    graph.restore(sds)
+    for d, tower, every_n in members:
+        logging.info("ensemble member: the %s tower of %s%s", tower, d, " at every_n = %d" % every_n if tower == "student" else "")
+    return _CombinedMembers(graph, spec, max(int(sd.get("global_step", 0)) for sd in sds))
+
+
 def _batches(reader, device):
     if FLAGS.eval_data_pattern == "synthetic":
         for i, (q, y, n, nh) in enumerate(synthetic_batches(FLAGS.batch_size, sum(reader.feature_sizes), device, FLAGS.synthetic_videos, 1, 4321)):
@@ -68,15 +85,41 @@ def _batches(reader, device):
 
 
 def check_flags():
-    """What is refused before a record is read or the device is touched."""
+    """What is refused before a record is read or the device is touched.  Returns the ensemble to evaluate (inference.ensemble_spec) or None."""
     if FLAGS.metrics_on_device:
         top_max = min(ops.TOPK_MAX_K, NUM_CLASSES)
         if not 1 <= FLAGS.top_k <= top_max:
             raise ValueError("--top_k %d: must be in [1, %d] with --metrics_on_device" % (FLAGS.top_k, top_max))
+    from .inference import ensemble_spec
+    spec = ensemble_spec(allow_preds_files=False)
+    if spec is not None and not FLAGS.run_once:
+        raise ValueError("--ensemble_dirs needs --run_once True: there is no one directory to poll for the checkpoints of several members")
+    return spec
+
+
+class _CombinedMembers:
+    """An ensemble behind the step() of an EvalGraph: the members' predictions combined by ops.ensemble_topk_rows (its dense output)
+    as "predictions", and the cross-entropy of the combination (ops.ce_loss) as "loss"."""
+
+    def __init__(self, graph, spec, global_step):
+        self.graph, self.spec, self.global_step = graph, spec, global_step
+        self.teacher = self.student = None
+        self._loss = None
+
+    def step(self, x_raw, labels_u8, num_frames, num_frames_host=None):
+        preds = self.graph.step(x_raw, labels_u8, num_frames, num_frames_host=num_frames_host)
+        _, _, combined = ops.ensemble_topk_rows(preds, 0, mode=self.spec["mode"], weights=self.spec["weights"], dense=True)
+        if self._loss is None:
+            self._loss = torch.zeros(1, dtype=torch.float32, device=combined.device)
+        self._loss.zero_()
+        ops.ce_loss(combined, labels_u8, self._loss[0:1])
+        return {"predictions": combined, "loss": self._loss[0]}
 
 
 def evaluation_loop(graph, reader, label_loss_fn, summary_writer, evl_metrics, last_global_step_val, device):
     """Run the evaluation loop once (cs/validate.py:192-303).  Returns (global_step_val, epoch_info_dict or None)."""
+    if isinstance(graph, _CombinedMembers):                              # restored in evaluate(); --run_once: nothing to poll
+        return _evaluate_restored(graph, reader, label_loss_fn, summary_writer, evl_metrics, graph.global_step, device)
     ck = latest_checkpoint(FLAGS.train_dir)
     if not ck:
         logging.info("No checkpoint file found.")
@@ -96,6 +139,11 @@ def evaluation_loop(graph, reader, label_loss_fn, summary_writer, evl_metrics, l
     if global_step_val == last_global_step_val:
         logging.info("skip this checkpoint global_step_val=%s (same as the previous one).", global_step_val)
         return global_step_val, None
+    return _evaluate_restored(graph, reader, label_loss_fn, summary_writer, evl_metrics, global_step_val, device)
+
+
+def _evaluate_restored(graph, reader, label_loss_fn, summary_writer, evl_metrics, global_step_val, device):
+    """One pass over the evaluation set with the restored graph (cs/validate.py:225-303)."""
     logging.info("enter eval_once loop global_step_val = %s. ", global_step_val)
     evl_metrics.clear()
     examples_processed, total_example_per_sec = 0, []
@@ -170,7 +218,9 @@ def evaluation_loop(graph, reader, label_loss_fn, summary_writer, evl_metrics, l
 def evaluate(student_only=False, max_evals=None):
     """cs/validate.py:306-397.  Returns the last epoch_info_dict (None if nothing was evaluated)."""
     start_time = time.time()
-    check_flags()
+    spec = check_flags()
+    if spec is not None and student_only:
+        raise ValueError("--ensemble_dirs: evaluate an ensemble with validate.py (each member names its own tower)")
     device = "cuda:%d" % FLAGS.gpu
     torch.cuda.set_device(FLAGS.gpu)
     ops.check_device(FLAGS.gpu)
@@ -179,7 +229,10 @@ def evaluate(student_only=False, max_evals=None):
     label_loss_fn = find_class_by_name(FLAGS.label_loss, [losses])()
     if FLAGS.eval_data_pattern == "":
         raise IOError("'eval_data_pattern' was not specified. Nothing to evaluate.")
-    graph = build_graph(reader, model, FLAGS.batch_size, device, student_only)
+    if spec is None:
+        graph = build_graph(reader, model, FLAGS.batch_size, device, student_only)
+    else:
+        graph = build_ensemble(reader, model, spec, FLAGS.batch_size, device)
     logging.info("built evaluation graph")
     for tw in (graph.teacher, graph.student):
         if tw is not None:

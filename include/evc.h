@@ -36,7 +36,7 @@ extern "C" {
 #define EVC_ERR_HIP (-4)
 #define EVC_ERR_BAD_ARG (-5)
 
-#define EVC_VERSION 107   /* 107 (round 6, late): evc_lstm_level2_fwd_high (the two-layer L1 level of the "high" mode in T + 1 two-tile launches); evc_topk_rows (per-row top-k of the inference binary's prediction file; an addition, no existing entry changed); 106 (round 6): evc_gemm_nt_sqnorm, evc_l2norm_chunk_int + the x_row_scale / x_col_const / b8_gap arguments of evc_lstm_layer_fwd_f16_fp8lo (integer-frame layer 0: the uint8 input exact), evc_lstm_layer_fwd_f16_fp8lo / evc_lstm_stack2_fwd_f16_fp8lo gained h_lo (low-order half of h corrected: 4H-byte h rows), evc_cast_f32_to_fp8_lohi, evc_lstm_adam_fused gained fp8_hi_tail; evc_absmax_partials, evc_cast_f32_to_f16_fp8x_dyn, evc_gemm_nt_f16_fp8_dyn (dynamic e4m3 range of the MoE head's input state); evc_l2norm_chunk_fwd accepts out1 == NULL (student-only graphs read the sub-sampled frames only), evc_clip_adam_small limited to 2^15 elements per tensor; 105 (round 5, second session): evc_cast_f32_to_f16_dither, evc_lstm_layer_fwd_f16_dith (time-dithered f16 weight images: an L1 layer of the "high" mode without stages for its weights' low-order halves), evc_gemm_tn2_rows (weight-gradient products that skip the dead rows of a row-planned level's time slabs); 104 (round 5): evc_lstm_level2_fwd, evc_ce_loss_ordered, evc_rep_loss_ordered, evc_gemm_tn2_slabs, evc_sum_slabs, evc_clip_adam_small; evc_moe_grad_update* accept p_bf16 == NULL (forward shadow not written), evc_lstm_stack2_bwd runs M <= 512 stacks on the skinny pair launches, evc_dbof_cluster_pool_fwd walks tiles (EVC_DBOF_WALK), EVC_DETERMINISTIC parsed as "set, not empty, not 0"; 103 (round 4): evc_sqnorm2_partials, evc_lstm_adam_fused, evc_gram_slabs, evc_moe_grad_norms, evc_moe_grad_update_apply, evc_adam2d_fused, evc_colsum_bf16_det, evc_sample_sequence_gather, evc_relu6_fwd/bwd, evc_framepool_mean_fwd/bwd, evc_stream_create_cu_mask / evc_stream_destroy; EVC_DETERMINISTIC=1 read by the library; 102: evc_lstm_layer_fwd_f16_fp8lo, evc_lstm_stack2_fwd_f16_fp8lo, evc_gemm_nt_f16_fp8, evc_cast_f32_to_fp8_lo, evc_cast_f32_to_f16_fp8x, aux_mode 5, evc_moe_grad_update_wide; 101 (round 3): evc_l2norm_chunk_fwd gained aux_mode; evc_lstm_layer_fwd_hp takes wide split operands; f16 / wide-split entries added */
+#define EVC_VERSION 107   /* 107 (round 6, late): evc_lstm_level2_fwd_high (the two-layer L1 level of the "high" mode in T + 1 two-tile launches); evc_topk_rows (per-row top-k of the inference binary's prediction file; an addition, no existing entry changed), later evc_eval_select_rows and evc_ensemble_topk_rows (the combination of several members' predictions in front of that selection) the same way; 106 (round 6): evc_gemm_nt_sqnorm, evc_l2norm_chunk_int + the x_row_scale / x_col_const / b8_gap arguments of evc_lstm_layer_fwd_f16_fp8lo (integer-frame layer 0: the uint8 input exact), evc_lstm_layer_fwd_f16_fp8lo / evc_lstm_stack2_fwd_f16_fp8lo gained h_lo (low-order half of h corrected: 4H-byte h rows), evc_cast_f32_to_fp8_lohi, evc_lstm_adam_fused gained fp8_hi_tail; evc_absmax_partials, evc_cast_f32_to_f16_fp8x_dyn, evc_gemm_nt_f16_fp8_dyn (dynamic e4m3 range of the MoE head's input state); evc_l2norm_chunk_fwd accepts out1 == NULL (student-only graphs read the sub-sampled frames only), evc_clip_adam_small limited to 2^15 elements per tensor; 105 (round 5, second session): evc_cast_f32_to_f16_dither, evc_lstm_layer_fwd_f16_dith (time-dithered f16 weight images: an L1 layer of the "high" mode without stages for its weights' low-order halves), evc_gemm_tn2_rows (weight-gradient products that skip the dead rows of a row-planned level's time slabs); 104 (round 5): evc_lstm_level2_fwd, evc_ce_loss_ordered, evc_rep_loss_ordered, evc_gemm_tn2_slabs, evc_sum_slabs, evc_clip_adam_small; evc_moe_grad_update* accept p_bf16 == NULL (forward shadow not written), evc_lstm_stack2_bwd runs M <= 512 stacks on the skinny pair launches, evc_dbof_cluster_pool_fwd walks tiles (EVC_DBOF_WALK), EVC_DETERMINISTIC parsed as "set, not empty, not 0"; 103 (round 4): evc_sqnorm2_partials, evc_lstm_adam_fused, evc_gram_slabs, evc_moe_grad_norms, evc_moe_grad_update_apply, evc_adam2d_fused, evc_colsum_bf16_det, evc_sample_sequence_gather, evc_relu6_fwd/bwd, evc_framepool_mean_fwd/bwd, evc_stream_create_cu_mask / evc_stream_destroy; EVC_DETERMINISTIC=1 read by the library; 102: evc_lstm_layer_fwd_f16_fp8lo, evc_lstm_stack2_fwd_f16_fp8lo, evc_gemm_nt_f16_fp8, evc_cast_f32_to_fp8_lo, evc_cast_f32_to_f16_fp8x, aux_mode 5, evc_moe_grad_update_wide; 101 (round 3): evc_l2norm_chunk_fwd gained aux_mode; evc_lstm_layer_fwd_hp takes wide split operands; f16 / wide-split entries added */
 
 typedef uint16_t evc_bf16;
 typedef uint16_t evc_f16;   /* raw IEEE binary16 bits (the "high" precision forward operands of the L1 levels) */
@@ -773,6 +773,28 @@ int evc_topk_rows(const float* x, int ld, int rows, int cols, int k, float* out_
  * atomics only: every launch gives the same bits. */
 int evc_eval_select_rows(const float* pred, int ld, const uint8_t* labels, int ld_lab, int rows, int cols, int k, float* top_val,
                          int32_t* top_idx, uint8_t* top_lab, int32_t* n_pos, int32_t* perr_hits, int32_t* class_pos, void* stream);
+/* Ensembles: the combination of M member prediction matrices, and of the sparse lists of P earlier prediction files, in front of the selection
+ * of evc_topk_rows - cs/max_ensemble.py:21-36 (per-class maximum over prediction files, then the top 20) and cs/inference_ensemble.py:155-193
+ * (earlier files joined through --preds_pattern, an absent class counting 0), on the device, one launch, one workgroup per row.
+ *   preds [M] HOST array of device pointers, member m = [rows][ld[m]] f32; ld [M] and weights [M + P] HOST arrays too (weights is read in mode 1
+ *     only, and may be NULL in mode 0); all three are read before the call returns and travel by value in the kernel's argument block - like
+ *     rows_per_step an exception to "device pointers only".  1 <= M <= 8.
+ *   prior_idx / prior_val [P][rows][kp] DEVICE arrays: the (class, confidence) lists of P earlier files for exactly these rows; an entry with an
+ *     index outside [0, cols) (the host pads with -1) is skipped; the indices of one list are distinct (the caller guarantees it).  0 <= P <= 8,
+ *     1 <= kp <= 256 when P > 0.
+ *   mode 0 (max): the combined element is the member value with the largest key in the total order of evc_topk_rows (NaN above +inf, -0 ties
+ *     +0); on equal keys the lowest member supplies the bits.  The prior files follow in order: row[c] = val if key(val) > key(row[c]).
+ *   mode 1 (weighted mean): acc = w[0] x_0; acc = acc + w[m] x_m for m ascending; then acc = acc + w[M + p] val for p ascending, where file p lists
+ *     the class (an absent class adds nothing: the 0 of cs/inference_ensemble.py:187-191).  Every product and every sum is rounded to f32 on its own
+ *     (no fused multiply-add), so a numpy float32 restatement gives the same bits.
+ *   k >= 1: out_val / out_idx [rows][k] = the top-k of the combined row, order and tie rule of evc_topk_rows, the values being the combined row's
+ *     bits.  out_dense != NULL: also the combined row itself, [rows][ld_dense] (the evaluation binaries need it for the loss and for
+ *     evc_eval_select_rows).  k == 0 with out_val == out_idx == NULL and out_dense != NULL is the dense exit alone.
+ * Limits as evc_topk_rows (cols <= 32768, k <= min(cols, 256)), ld[m] >= cols, ld_dense >= cols; rows == 0 launches nothing; anything else is
+ * EVC_ERR_BAD_ARG before any launch.  No float atomics: every launch gives the same bits. */
+int evc_ensemble_topk_rows(const float* const* preds, const int64_t* ld, const float* weights, int M, const int32_t* prior_idx,
+                           const float* prior_val, int P, int kp, int rows, int cols, int mode, int k, float* out_val, int32_t* out_idx,
+                           float* out_dense, int64_t ld_dense, void* stream);
 
 /* utility: out[i] = value for n floats (avoids torch for tiny fills inside C loops) */
 int evc_fill_f32(float* p, int64_t n, float value, void* stream);
