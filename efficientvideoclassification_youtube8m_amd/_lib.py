@@ -126,6 +126,9 @@ SIGNATURES = {
     "evc_topk_rows": [vp, i32, i32, i32, i32, vp, vp, vp],
     "evc_eval_select_rows": [vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp],
     "evc_ensemble_topk_rows": [vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i64, vp],
+    "evc_student_frame_select": [vp, i32, i32, i32, i32, C.c_uint32, C.c_uint32, i32, vp, vp],
+    "evc_l2norm_chunk_sel_fwd": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, i32, vp, i32, vp],
+    "evc_l2norm_chunk_sel_int": [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp],
 }
 EXPORTS = tuple(SIGNATURES) + ("evc_version", "evc_last_error")
 

@@ -342,9 +342,28 @@ def input_views(g, x_raw, num_frames, tp, sp, need_student):
     take the INTEGER-frame images (ops.l2norm_chunk_int, HLstmTower.x_int: the input exact, round 6)."""
     towers = [t for t in (g.teacher, g.student if need_student else None) if t is not None]
     p1, p2 = (tp[2] if tp else None), (sp[3] if sp else None)
-    if x_raw.dtype == torch.uint8 and towers and all(t.precision == "high" and t.x_int() for t in towers):
+    as_int = x_raw.dtype == torch.uint8 and towers and all(t.precision == "high" and t.x_int() for t in towers)
+    nf = num_frames if x_raw.dtype == torch.uint8 else None
+    if need_student and getattr(g, "student_sampling", "uniform") != "uniform":
+        # A student on other frames than the grid s * every_n (--student_sampling): the teacher view as ever, without a student view, then the
+        # student view from the table of its source frames + the gathering pass, on the same stream.  The image forms are the ones the shared
+        # call would have produced (decided over both towers), the frame counts and row plans do not depend on which frames are taken.
+        img = input_image_args(g.teacher, g.student)
+        xt = None
+        if g.teacher is not None:
+            if as_int:
+                xt = ops.l2norm_chunk_int(x_raw, num_frames, g.C1, None, g.C2, plan1=p1)[0]
+            else:
+                xt = ops.l2norm_chunk(x_raw, g.C1, None, g.C2, num_frames=nf, split=towers[0].input_split(), plan1=p1, **img)[0]
+        src = ops.student_frame_select(num_frames, g.max_frames, g.every_n, g.student_sampling, seed=g.sampling_seed,
+                                       draw=getattr(g, "sampling_draw", 0), row0=getattr(g, "sampling_row0", 0))
+        g.last_frame_table = src          # (the table of the last batch, for whoever wants to look: tests, diagnostics)
+        if as_int:
+            return xt, ops.l2norm_chunk_int_sel(x_raw, num_frames, src, g.every_n, g.C2, plan2=p2)
+        return xt, ops.l2norm_chunk_sel(x_raw, src, g.every_n, g.C2, num_frames=nf, split=towers[0].input_split(), plan2=p2, **img)
+    if as_int:
         return ops.l2norm_chunk_int(x_raw, num_frames, g.C1, g.every_n if need_student else None, g.C2, plan1=p1, plan2=p2, teacher_view=g.teacher is not None)
-    return ops.l2norm_chunk(x_raw, g.C1, g.every_n if need_student else None, g.C2, num_frames=num_frames if x_raw.dtype == torch.uint8 else None,
+    return ops.l2norm_chunk(x_raw, g.C1, g.every_n if need_student else None, g.C2, num_frames=nf,
                             split=towers[0].input_split(), plan1=p1, plan2=p2, teacher_view=g.teacher is not None,
                             **input_image_args(g.teacher, g.student if need_student else None))
 
@@ -385,9 +404,11 @@ class DistillGraph:
                  num_mixtures=2, base_learning_rate=0.001, learning_rate_decay=1.0,
                  learning_rate_decay_examples=4000000, regularization_penalty=2.0, clip_gradient_norm=1.0,
                  count_rep_twice=True, device="cuda:0", seed=7, process_group=None, overlap_towers=True,
-                 precision="bf16"):
+                 precision="bf16", student_sampling="uniform", sampling_seed=0):
         assert mode in ("teacher_student", "teacher", "student")
         self.mode, self.B, self.every_n = mode, batch_size, every_n
+        # which frames the student sees (ops.STUDENT_SAMPLING; input_views): "uniform" is the grid s * every_n of the reference
+        self.student_sampling, self.sampling_seed = ops.check_student_sampling(student_sampling), int(sampling_seed)
         self.max_frames, self.C1, self.C2 = max_frames, num_inputs_to_lstm, num_inputs_l1_student
         self.lr0, self.lr_decay, self.lr_decay_examples = base_learning_rate, learning_rate_decay, learning_rate_decay_examples
         self.reg_pen, self.clip = regularization_penalty, clip_gradient_norm
@@ -532,6 +553,10 @@ class DistillGraph:
         need_student = self.student is not None
         main = torch.cuda.current_stream(dev)
         tp, sp = frame_counts_and_plans(self, num_frames, nh, self.teacher is not None, need_student)
+        # "random" student frames: a new draw per training iteration (global_step counts one per train op, cs/train.py:332,416), other videos
+        # on every rank - stateless, so a run is reproducible from its seed and a restored global_step
+        self.sampling_draw = self.global_step // ((self.teacher is not None) + (self.student is not None))
+        self.sampling_row0 = self.reducer.rank * B
         xt, xs = input_views(self, x_raw, num_frames, tp, sp, need_student)     # (student only: the sub-sampled frames alone are read)
         for tw in (self.teacher, self.student):     # step k-1's deferred MoE / L2-level updates: now, under this step's L1 forward
             if tw is not None:
@@ -739,9 +764,11 @@ class EvalGraph:
 
     def __init__(self, batch_size, every_n=10, student_only=False, feature_size=1152, vocab_size=4716, max_frames=300,
                  num_inputs_to_lstm=20, num_inputs_l1_student=5, lstm_cells=1024, lstm_layers=2, num_mixtures=2,
-                 device="cuda:0", precision="bf16", teacher_only=False):
+                 device="cuda:0", precision="bf16", teacher_only=False, student_sampling="uniform", sampling_seed=0):
         if student_only and teacher_only:
             raise ValueError("EvalGraph: student_only and teacher_only exclude each other")
+        # the student's frames (ops.STUDENT_SAMPLING); evaluation draws "random" frames with draw 0: the same frames for the same batching
+        self.student_sampling, self.sampling_seed = ops.check_student_sampling(student_sampling), int(sampling_seed)
         if not teacher_only:
             validate_every_n(every_n, num_inputs_l1_student, max_frames)
         self.every_n, self.max_frames, self.C1, self.C2 = every_n, max_frames, num_inputs_to_lstm, num_inputs_l1_student
@@ -832,18 +859,22 @@ class EvalGraph:
 
 class EnsembleGraph:
     """N forward-only members for one input: each an EvalGraph that is ``teacher_only`` or ``student_only`` at its own every_n, all on
-    one device with one --precision and one set of model sizes (``members``: list of (tower, every_n), tower 'teacher' | 'student';
-    the other arguments are EvalGraph's).  step() runs every member on the same input tensors and returns their prediction tensors,
+    one device with one --precision and one set of model sizes (``members``: list of (tower, every_n[, student_sampling]), tower
+    'teacher' | 'student'; the other arguments are EvalGraph's, student_sampling / sampling_seed among them).  step() runs every member on the same input tensors and returns their prediction tensors,
     each the buffer of that member's own tower, so all of them are alive together for ops.ensemble_topk_rows."""
 
     def __init__(self, batch_size, members, **kw):
         if not members:
             raise ValueError("EnsembleGraph: no members")
         self.members = []
-        for tower, every_n in members:
+        for member in members:
+            tower, every_n = member[0], member[1]
             if tower not in ("teacher", "student"):
                 raise ValueError("EnsembleGraph: tower %r (teacher | student)" % (tower,))
-            self.members.append(EvalGraph(batch_size, every_n=every_n, student_only=tower == "student", teacher_only=tower == "teacher", **kw))
+            mkw = dict(kw)
+            if len(member) > 2:               # (tower, every_n, student_sampling): this member's own frame selection
+                mkw["student_sampling"] = member[2]
+            self.members.append(EvalGraph(batch_size, every_n=every_n, student_only=tower == "student", teacher_only=tower == "teacher", **mkw))
 
     def restore(self, state_dicts):
         """Each member restores its own checkpoint (the 11 variables of its tower by name)."""

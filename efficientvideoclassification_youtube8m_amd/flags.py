@@ -16,6 +16,12 @@ def _define(name, default, typ, help_=""):
     _DEFS[name] = (default, typ, help_)
 
 
+def _sampling(v):
+    """A --student_sampling word, checked while the flags are parsed: an unknown one is a ValueError before anything touches the device."""
+    from .ops import check_student_sampling
+    return check_student_sampling(str(v).strip(), "--student_sampling")
+
+
 def _bool(v):
     if isinstance(v, bool):
         return v
@@ -98,6 +104,16 @@ _define("metrics_on_device", False, _bool, "validate / eval_finetune: select wha
         "(ops.eval_select_rows) and fetch [B, top_k] + a few [B] vectors instead of the [B, 4716] predictions and labels; same metrics bit "
         "for bit except for rows with an exact tie at the top_k-th / label-count-th place, where the device admits the lowest class "
         "(eval_util.EvaluationMetrics.accumulate_selected); needs 1 <= top_k <= min(256, classes)")
+# ---- which frames the student sees (train, train_finetune, train_convert_model, validate, eval_finetune, inference) ----------------------
+_define("student_sampling", "uniform", _sampling, "uniform|first|middle|last|first_middle_last|random: the student's int(n/300*S) frames are the "
+        "grid s * every_n of the padded tensor (uniform: the reference), the first, the middle or the last ones of the video's n frames, three "
+        "runs at its start, middle and end, or drawn at random without replacement (kept in time order).  The table is built on the device "
+        "(ops.student_frame_select) and the input pass gathers the frames.  random: training draws anew at every iteration (hash of seed, "
+        "iteration, position in the global batch, frame); evaluation and inference always use draw 0, so they are deterministic for a given "
+        "batching (batch size and order of the records) - another batch size gives a video another position and other frames.  Checkpoints "
+        "record the word; validate / inference warn when the flag disagrees with it, and the flag wins")
+_define("student_sampling_seed", 0, int, "seed of --student_sampling random")
+_define("ensemble_sampling", "", str, "one --student_sampling word per member (ignored for teachers); '' = --student_sampling for all")
 # ---- ensembles (inference / validate; cs/inference_ensemble.py:28-61 has preds_pattern, the others are additions) -----------------------
 _define("ensemble_dirs", "", str, "comma separated checkpoint directories of the ensemble's members (1 .. 8); '' = the single model of "
         "--train_dir, which is not consulted otherwise.  Every member runs its forward on the same batch and ops.ensemble_topk_rows "

@@ -59,17 +59,18 @@ def _words(text):
 
 
 def ensemble_spec(allow_preds_files=True):
-    """The ensemble the flags describe, checked: None without --ensemble_dirs, else dict(dirs, towers, every_n [M]; mode; weights
+    """The ensemble the flags describe, checked: None without --ensemble_dirs, else dict(dirs, towers, every_n, sampling [M]; mode; weights
     float32 [M + P] or None; files [P], sorted by name as cs/inference_ensemble.py:169-170).  Raises ValueError for everything that can be
     refused before the device is touched."""
     dirs = _words(FLAGS.ensemble_dirs)
     towers, every_n, weights = _words(FLAGS.ensemble_towers), _words(FLAGS.ensemble_every_n), _words(FLAGS.ensemble_weights)
+    sampling = _words(FLAGS.ensemble_sampling)
     if FLAGS.preds_pattern != "" and not allow_preds_files:
         raise ValueError("--preds_pattern: earlier prediction files join an ensemble in inference only")
     if not dirs:
         if FLAGS.preds_pattern != "":
             raise ValueError("--preds_pattern without --ensemble_dirs: no model is served that the files could join")
-        for name, given in (("towers", towers), ("every_n", every_n), ("weights", weights)):
+        for name, given in (("towers", towers), ("every_n", every_n), ("weights", weights), ("sampling", sampling)):
             if given:
                 raise ValueError("--ensemble_%s: %d entries for 0 --ensemble_dirs" % (name, len(given)))
         return None
@@ -78,13 +79,16 @@ def ensemble_spec(allow_preds_files=True):
         raise ValueError("--ensemble_dirs: %d members (1 .. %d, none empty)" % (M, ops.ENSEMBLE_MAX_MEMBERS))
     towers = towers or ["auto"] * M
     every_n = every_n or [str(FLAGS.every_n)] * M
-    for name, given in (("towers", towers), ("every_n", every_n)):
+    sampling = sampling or [FLAGS.student_sampling] * M
+    for name, given in (("towers", towers), ("every_n", every_n), ("sampling", sampling)):
         if len(given) != M:
             raise ValueError("--ensemble_%s: %d entries for %d --ensemble_dirs" % (name, len(given), M))
     for t in towers:
         if t not in ("auto", "teacher", "student"):
             raise ValueError("--ensemble_towers: %r (auto | teacher | student)" % t)
     every_n = [int(e) for e in every_n]
+    for s in sampling:
+        ops.check_student_sampling(s, "--ensemble_sampling")
     if FLAGS.ensemble_mode not in ops.ENSEMBLE_MODES:
         raise ValueError("--ensemble_mode %r (max | mean)" % FLAGS.ensemble_mode)
     files = []
@@ -101,7 +105,7 @@ def ensemble_spec(allow_preds_files=True):
         if len(weights) != M + len(files):
             raise ValueError("--ensemble_weights: %d entries for %d members + %d prediction files" % (len(weights), M, len(files)))
         w = np.asarray([float(x) for x in weights], np.float32)
-    return dict(dirs=dirs, towers=towers, every_n=every_n, mode=FLAGS.ensemble_mode, weights=w, files=files)
+    return dict(dirs=dirs, towers=towers, every_n=every_n, sampling=sampling, mode=FLAGS.ensemble_mode, weights=w, files=files)
 
 
 def read_prediction_file(path, num_classes=NUM_CLASSES):
@@ -197,6 +201,13 @@ def member_tower(state_dict, word, where=""):
     return word
 
 
+def warn_sampling(state_dict, word, where):
+    """A student evaluated on other frames than it was trained on is a legitimate experiment, so the flag wins - but say so."""
+    trained = state_dict.get("student_sampling")
+    if trained is not None and trained != word:
+        logging.warning("--student_sampling %s, but the student of %s was trained with %s (the flag is used)", word, where, trained)
+
+
 def load_members(spec):
     """Checkpoints and towers of an ensemble_spec(): ([state dict per member], [(dir, tower, every_n)], [checkpoint path]).  A
     directory listed twice is read once."""
@@ -212,15 +223,20 @@ def load_members(spec):
         sds.append(sd)
         cks.append(ck)
         members.append((d, member_tower(sd, word, ck), every_n))
+        if members[-1][1] == "student":
+            warn_sampling(sd, spec.get("sampling", [FLAGS.student_sampling] * len(spec["dirs"]))[len(members) - 1], ck)
     return sds, members, cks
 
 
-def build_ensemble_graph(reader, members, batch_size, device):
-    """Forward-only graphs of an ensemble's members (members: (dir, tower, every_n)); sizes and --precision shared."""
-    return EnsembleGraph(batch_size, [(tower, every_n) for _, tower, every_n in members], feature_size=sum(reader.feature_sizes),
+def build_ensemble_graph(reader, members, batch_size, device, sampling=None):
+    """Forward-only graphs of an ensemble's members (members: (dir, tower, every_n); sampling: the members' --ensemble_sampling words, None =
+    --student_sampling for all); sizes, --precision and --student_sampling_seed shared."""
+    sampling = sampling or [FLAGS.student_sampling] * len(members)
+    return EnsembleGraph(batch_size, [(tower, every_n, s) for (_, tower, every_n), s in zip(members, sampling)],
+                         feature_size=sum(reader.feature_sizes),
                          vocab_size=reader.num_classes, max_frames=FLAGS.max_num_frames, num_inputs_to_lstm=FLAGS.num_inputs_to_lstm,
                          lstm_cells=FLAGS.lstm_cells, lstm_layers=FLAGS.lstm_layers, num_mixtures=FLAGS.moe_num_mixtures, device=device,
-                         precision=FLAGS.precision)
+                         precision=FLAGS.precision, sampling_seed=FLAGS.student_sampling_seed)
 
 
 def build_graph(reader, tower, batch_size, device):
@@ -228,7 +244,8 @@ def build_graph(reader, tower, batch_size, device):
     return EvalGraph(batch_size, every_n=FLAGS.every_n, student_only=tower == "student", teacher_only=tower == "teacher",
                      feature_size=sum(reader.feature_sizes), vocab_size=reader.num_classes, max_frames=FLAGS.max_num_frames,
                      num_inputs_to_lstm=FLAGS.num_inputs_to_lstm, lstm_cells=FLAGS.lstm_cells, lstm_layers=FLAGS.lstm_layers,
-                     num_mixtures=FLAGS.moe_num_mixtures, device=device, precision=FLAGS.precision)
+                     num_mixtures=FLAGS.moe_num_mixtures, device=device, precision=FLAGS.precision,
+                     student_sampling=FLAGS.student_sampling, sampling_seed=FLAGS.student_sampling_seed)
 
 
 def _open_device():
@@ -249,6 +266,8 @@ def _single_selector(reader, train_dir, batch_size, top_k, stats):
     tower = serving_tower(sd)
     graph = build_graph(reader, tower, batch_size, device)
     graph.restore(sd)
+    if tower == "student":
+        warn_sampling(sd, FLAGS.student_sampling, ck)
     logging.info("serving the %s tower (%s/*)%s", tower, "model" if tower == "teacher" else "model_student",
                  " at every_n = %d" % FLAGS.every_n if tower == "student" else "")
     stats.update(tower=tower, checkpoint=ck, members=[(train_dir, tower, FLAGS.every_n)])
@@ -269,10 +288,10 @@ def _ensemble_selector(reader, spec, batch_size, top_k, stats):
     kp = prior_list_length(tables)
     sds, members, cks = load_members(spec)
     device = _open_device()
-    graph = build_ensemble_graph(reader, members, batch_size, device)
+    graph = build_ensemble_graph(reader, members, batch_size, device, spec["sampling"])
     graph.restore(sds)
-    for d, tower, every_n in members:
-        logging.info("ensemble member: the %s tower of %s%s", tower, d, " at every_n = %d" % every_n if tower == "student" else "")
+    for (d, tower, every_n), s in zip(members, spec["sampling"]):
+        logging.info("ensemble member: the %s tower of %s%s", tower, d, " at every_n = %d, %s frames" % (every_n, s) if tower == "student" else "")
     logging.info("ensemble: %d members + %d prediction files, mode %s", len(members), len(tables), spec["mode"])
     stats.update(tower="ensemble", checkpoint=cks, members=members)
 

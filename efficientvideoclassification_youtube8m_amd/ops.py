@@ -404,6 +404,72 @@ def frame_counts(num_frames, every_n, num_chunks, chunk_len, max_frames=300, sub
     return n_out, l1, l2
 
 
+# Which frames the student sees (--student_sampling); the position in the tuple is the EVC_SELECT_* code of evc_student_frame_select.
+STUDENT_SAMPLING = ("uniform", "first", "middle", "last", "first_middle_last", "random")
+
+
+def check_student_sampling(word, flag="student_sampling"):
+    """The word itself, or a ValueError that names the choices (raised before anything touches the device)."""
+    if word not in STUDENT_SAMPLING:
+        raise ValueError("%s: %r (%s)" % (flag, word, " | ".join(STUDENT_SAMPLING)))
+    return word
+
+
+def student_frame_select(num_frames, T, every_n, strategy, seed=0, draw=0, row0=0):
+    """The student's source-frame table (evc_student_frame_select): src [B, T // every_n] int32 on the device, -1 = no frame.  num_frames [B]
+    int32 (device); strategy a word of STUDENT_SAMPLING; seed / draw / row0 only matter under "random" (draw: the training iteration,
+    row0: index of this batch's first video in the global batch)."""
+    code = STUDENT_SAMPLING.index(check_student_sampling(strategy, "student_frame_select"))
+    assert num_frames.dtype == torch.int32 and num_frames.dim() == 1 and num_frames.is_contiguous()
+    B = num_frames.shape[0]
+    src = torch.empty((B, T // max(1, every_n)), dtype=torch.int32, device=num_frames.device)
+    _lib.call("evc_student_frame_select", _p(num_frames), B, T, every_n, code, int(seed) & 0xFFFFFFFF, int(draw) & 0xFFFFFFFF, int(row0), _p(src), _stream())
+    return src
+
+
+def l2norm_chunk_sel(x_raw, src, every_n, num_chunks_student, num_frames=None, normalize=True, split=False, plan2=None, f16_segments=1,
+                     fp8_tail=False):
+    """The student view of l2norm_chunk(..., teacher_view=False) from the frames a table names (evc_l2norm_chunk_sel_fwd): slot j of video b
+    holds frame src[b, j] of x_raw (student_frame_select; -1: a zero row).  Same arguments and the same return form as that view: the bf16
+    image, or with split the pair (bf16 image, second image)."""
+    B, T, F = x_raw.shape
+    dev = x_raw.device
+    S = T // every_n
+    assert src.dtype == torch.int32 and tuple(src.shape) == (B, S) and src.is_contiguous() and x_raw.is_contiguous()
+    rows2 = plan2.P if plan2 is not None else num_chunks_student * B
+    out2 = torch.empty((S // num_chunks_student, rows2, F), dtype=BF16, device=dev)
+    is_u8 = x_raw.dtype == torch.uint8
+    aux_dt = F16 if split == "f16" else BF16
+    nseg = f16_segments if split == "f16" else (2 if split == "wide" else 1)
+    aux_mode = nseg if split == "f16" else (4 if split == "wide" else 0)
+    wrow = nseg * F
+    if fp8_tail:
+        assert split == "f16" and f16_segments == 1 and F % 32 == 0, "fp8_tail: the f16 image + two e4m3 images, F % 32 == 0"
+        aux_mode, wrow = 5, 2 * F
+    lo2 = torch.empty(out2.shape[:2] + (wrow,), dtype=aux_dt, device=dev) if split else None
+    _lib.call("evc_l2norm_chunk_sel_fwd", None if is_u8 else _p(x_raw), _p(x_raw) if is_u8 else None, _p(num_frames), _p(src), B, T, F, every_n,
+              num_chunks_student, _p(out2), 1 if normalize else 0, _p(lo2), aux_mode, _p(plan2.pos) if plan2 is not None else None, rows2, _stream())
+    return (out2, lo2) if split else out2
+
+
+def l2norm_chunk_int_sel(x_u8, num_frames, src, every_n, num_chunks_student, plan2=None):
+    """The student view of l2norm_chunk_int(..., teacher_view=False) from the frames a table names (evc_l2norm_chunk_sel_int):
+    (bf16 image, integer image, row scales)."""
+    B, T, F = x_u8.shape
+    S = T // every_n
+    assert x_u8.dtype == torch.uint8 and F % 32 == 0 and x_u8.is_contiguous()
+    assert src.dtype == torch.int32 and tuple(src.shape) == (B, S) and src.is_contiguous()
+    dev = x_u8.device
+    rows2 = plan2.P if plan2 is not None else num_chunks_student * B
+    L2 = S // num_chunks_student
+    out2 = torch.empty((L2, rows2, F), dtype=BF16, device=dev)
+    int2 = torch.empty((L2, rows2, 3 * F // 2), dtype=F16, device=dev)
+    rs2 = torch.zeros((L2, rows2), dtype=F32, device=dev)
+    _lib.call("evc_l2norm_chunk_sel_int", _p(x_u8), _p(num_frames), _p(src), B, T, F, every_n, num_chunks_student, _p(out2), _p(int2), _p(rs2),
+              _p(plan2.pos) if plan2 is not None else None, rows2, _stream())
+    return out2, int2, rs2
+
+
 # ---------------------------------------------------------------------------
 def _plan_args(plan):
     return (_p(plan.inv), plan.rows_c) if plan is not None else (None, None)

@@ -69,7 +69,8 @@ def build_graph(model, label_loss_fn, feature_size, batch_size, every_n, device,
         return DistillGraph(batch_size, every_n=every_n, mode=mode, feature_size=feature_size, vocab_size=NUM_CLASSES,
                             max_frames=FLAGS.max_num_frames, num_inputs_to_lstm=FLAGS.num_inputs_to_lstm,
                             lstm_cells=FLAGS.lstm_cells, lstm_layers=FLAGS.lstm_layers,
-                            num_mixtures=FLAGS.moe_num_mixtures, device=device, precision=FLAGS.precision, **common)
+                            num_mixtures=FLAGS.moe_num_mixtures, device=device, precision=FLAGS.precision,
+                            student_sampling=FLAGS.student_sampling, sampling_seed=FLAGS.student_sampling_seed, **common)
     if isinstance(model, frame_level_models.DbofModel):
         tw = DbofTower(batch_size, FLAGS.max_num_frames, feature_size, NUM_CLASSES, FLAGS.iterations,
                        FLAGS.dbof_cluster_size, FLAGS.dbof_hidden_size, FLAGS.moe_num_mixtures, device=device,
@@ -160,6 +161,8 @@ def save_checkpoint(graph, train_dir, rank):
         return
     os.makedirs(train_dir, exist_ok=True)
     sd = {"global_step": graph.global_step}
+    if getattr(graph, "student", None) is not None:
+        sd["student_sampling"] = graph.student_sampling          # metadata: the frames this student was trained on (--student_sampling)
     for tw in (getattr(graph, "teacher", None), getattr(graph, "student", None), getattr(graph, "tower", None)):
         if tw is not None:
             sd.update({k: v.cpu() for k, v in tw.state_dict().items()})

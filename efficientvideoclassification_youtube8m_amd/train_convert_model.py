@@ -33,6 +33,8 @@ def extract_student(state_dict):
     if not out:
         raise ValueError("checkpoint holds no '%s*' variables - was it written by teacher+student training?" % STUDENT_SCOPE)
     out["global_step"] = 0
+    if "student_sampling" in state_dict:                           # metadata: the frames the student was trained on (--student_sampling)
+        out["student_sampling"] = state_dict["student_sampling"]
     return out
 
 
@@ -41,6 +43,9 @@ def convert(train_dir, out_dir=None):
     if ck is None:
         raise IOError("No checkpoint file found in " + train_dir)
     sd = extract_student(torch.load(ck, map_location="cpu"))
+    if sd.get("student_sampling", FLAGS.student_sampling) != FLAGS.student_sampling:      # (a checkpoint without the word: nothing to carry)
+        logging.warning("--student_sampling %s, but %s was trained with %s: the converted checkpoint keeps what it was trained with",
+                        FLAGS.student_sampling, ck, sd["student_sampling"])
     logging.info("saver_student loaded successfully !")
     logging.info([k for k in sd if k != "global_step"])
     out_dir = out_dir or finetune_dir(train_dir)

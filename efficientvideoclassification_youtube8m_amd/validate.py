@@ -59,7 +59,7 @@ def build_graph(reader, model, batch_size, device, student_only=False):
     return EvalGraph(batch_size, every_n=FLAGS.every_n, student_only=student_only, feature_size=sum(reader.feature_sizes),
                      vocab_size=reader.num_classes, max_frames=FLAGS.max_num_frames, num_inputs_to_lstm=FLAGS.num_inputs_to_lstm,
                      lstm_cells=FLAGS.lstm_cells, lstm_layers=FLAGS.lstm_layers, num_mixtures=FLAGS.moe_num_mixtures, device=device,
-                     precision=FLAGS.precision)
+                     precision=FLAGS.precision, student_sampling=FLAGS.student_sampling, sampling_seed=FLAGS.student_sampling_seed)
 
 
 def build_ensemble(reader, model, spec, batch_size, device):
@@ -68,7 +68,7 @@ def build_ensemble(reader, model, spec, batch_size, device):
     if not isinstance(model, frame_level_models.HierarchicalLstmModel):
         raise NotImplementedError("an ensemble serves H-LSTM teacher / student towers; model %s has no path here" % type(model).__name__)
     sds, members, _ = inference.load_members(spec)
-    graph = inference.build_ensemble_graph(reader, members, batch_size, device)
+    graph = inference.build_ensemble_graph(reader, members, batch_size, device, spec["sampling"])
     graph.restore(sds)
     for d, tower, every_n in members:
         logging.info("ensemble member: the %s tower of %s%s", tower, d, " at every_n = %d" % every_n if tower == "student" else "")
@@ -135,6 +135,9 @@ def evaluation_loop(graph, reader, label_loss_fn, summary_writer, evl_metrics, l
         logging.info("checkpoint %s disappeared before it could be loaded (%s); will look again.", ck, e)
         return last_global_step_val, None
     graph.restore(sd)
+    if graph.student is not None:
+        from .inference import warn_sampling
+        warn_sampling(sd, FLAGS.student_sampling, ck)
     global_step_val = int(sd.get("global_step", 0))
     if global_step_val == last_global_step_val:
         logging.info("skip this checkpoint global_step_val=%s (same as the previous one).", global_step_val)

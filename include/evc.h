@@ -36,7 +36,7 @@ extern "C" {
 #define EVC_ERR_HIP (-4)
 #define EVC_ERR_BAD_ARG (-5)
 
-#define EVC_VERSION 107   /* 107 (round 6, late): evc_lstm_level2_fwd_high (the two-layer L1 level of the "high" mode in T + 1 two-tile launches); evc_topk_rows (per-row top-k of the inference binary's prediction file; an addition, no existing entry changed), later evc_eval_select_rows and evc_ensemble_topk_rows (the combination of several members' predictions in front of that selection) the same way; 106 (round 6): evc_gemm_nt_sqnorm, evc_l2norm_chunk_int + the x_row_scale / x_col_const / b8_gap arguments of evc_lstm_layer_fwd_f16_fp8lo (integer-frame layer 0: the uint8 input exact), evc_lstm_layer_fwd_f16_fp8lo / evc_lstm_stack2_fwd_f16_fp8lo gained h_lo (low-order half of h corrected: 4H-byte h rows), evc_cast_f32_to_fp8_lohi, evc_lstm_adam_fused gained fp8_hi_tail; evc_absmax_partials, evc_cast_f32_to_f16_fp8x_dyn, evc_gemm_nt_f16_fp8_dyn (dynamic e4m3 range of the MoE head's input state); evc_l2norm_chunk_fwd accepts out1 == NULL (student-only graphs read the sub-sampled frames only), evc_clip_adam_small limited to 2^15 elements per tensor; 105 (round 5, second session): evc_cast_f32_to_f16_dither, evc_lstm_layer_fwd_f16_dith (time-dithered f16 weight images: an L1 layer of the "high" mode without stages for its weights' low-order halves), evc_gemm_tn2_rows (weight-gradient products that skip the dead rows of a row-planned level's time slabs); 104 (round 5): evc_lstm_level2_fwd, evc_ce_loss_ordered, evc_rep_loss_ordered, evc_gemm_tn2_slabs, evc_sum_slabs, evc_clip_adam_small; evc_moe_grad_update* accept p_bf16 == NULL (forward shadow not written), evc_lstm_stack2_bwd runs M <= 512 stacks on the skinny pair launches, evc_dbof_cluster_pool_fwd walks tiles (EVC_DBOF_WALK), EVC_DETERMINISTIC parsed as "set, not empty, not 0"; 103 (round 4): evc_sqnorm2_partials, evc_lstm_adam_fused, evc_gram_slabs, evc_moe_grad_norms, evc_moe_grad_update_apply, evc_adam2d_fused, evc_colsum_bf16_det, evc_sample_sequence_gather, evc_relu6_fwd/bwd, evc_framepool_mean_fwd/bwd, evc_stream_create_cu_mask / evc_stream_destroy; EVC_DETERMINISTIC=1 read by the library; 102: evc_lstm_layer_fwd_f16_fp8lo, evc_lstm_stack2_fwd_f16_fp8lo, evc_gemm_nt_f16_fp8, evc_cast_f32_to_fp8_lo, evc_cast_f32_to_f16_fp8x, aux_mode 5, evc_moe_grad_update_wide; 101 (round 3): evc_l2norm_chunk_fwd gained aux_mode; evc_lstm_layer_fwd_hp takes wide split operands; f16 / wide-split entries added */
+#define EVC_VERSION 107   /* 107 (round 6, late): evc_lstm_level2_fwd_high (the two-layer L1 level of the "high" mode in T + 1 two-tile launches); evc_topk_rows (per-row top-k of the inference binary's prediction file; an addition, no existing entry changed), later evc_eval_select_rows and evc_ensemble_topk_rows (the combination of several members' predictions in front of that selection) and evc_student_frame_select / evc_l2norm_chunk_sel_fwd / evc_l2norm_chunk_sel_int (student frame selection) the same way; 106 (round 6): evc_gemm_nt_sqnorm, evc_l2norm_chunk_int + the x_row_scale / x_col_const / b8_gap arguments of evc_lstm_layer_fwd_f16_fp8lo (integer-frame layer 0: the uint8 input exact), evc_lstm_layer_fwd_f16_fp8lo / evc_lstm_stack2_fwd_f16_fp8lo gained h_lo (low-order half of h corrected: 4H-byte h rows), evc_cast_f32_to_fp8_lohi, evc_lstm_adam_fused gained fp8_hi_tail; evc_absmax_partials, evc_cast_f32_to_f16_fp8x_dyn, evc_gemm_nt_f16_fp8_dyn (dynamic e4m3 range of the MoE head's input state); evc_l2norm_chunk_fwd accepts out1 == NULL (student-only graphs read the sub-sampled frames only), evc_clip_adam_small limited to 2^15 elements per tensor; 105 (round 5, second session): evc_cast_f32_to_f16_dither, evc_lstm_layer_fwd_f16_dith (time-dithered f16 weight images: an L1 layer of the "high" mode without stages for its weights' low-order halves), evc_gemm_tn2_rows (weight-gradient products that skip the dead rows of a row-planned level's time slabs); 104 (round 5): evc_lstm_level2_fwd, evc_ce_loss_ordered, evc_rep_loss_ordered, evc_gemm_tn2_slabs, evc_sum_slabs, evc_clip_adam_small; evc_moe_grad_update* accept p_bf16 == NULL (forward shadow not written), evc_lstm_stack2_bwd runs M <= 512 stacks on the skinny pair launches, evc_dbof_cluster_pool_fwd walks tiles (EVC_DBOF_WALK), EVC_DETERMINISTIC parsed as "set, not empty, not 0"; 103 (round 4): evc_sqnorm2_partials, evc_lstm_adam_fused, evc_gram_slabs, evc_moe_grad_norms, evc_moe_grad_update_apply, evc_adam2d_fused, evc_colsum_bf16_det, evc_sample_sequence_gather, evc_relu6_fwd/bwd, evc_framepool_mean_fwd/bwd, evc_stream_create_cu_mask / evc_stream_destroy; EVC_DETERMINISTIC=1 read by the library; 102: evc_lstm_layer_fwd_f16_fp8lo, evc_lstm_stack2_fwd_f16_fp8lo, evc_gemm_nt_f16_fp8, evc_cast_f32_to_fp8_lo, evc_cast_f32_to_f16_fp8x, aux_mode 5, evc_moe_grad_update_wide; 101 (round 3): evc_l2norm_chunk_fwd gained aux_mode; evc_lstm_layer_fwd_hp takes wide split operands; f16 / wide-split entries added */
 
 typedef uint16_t evc_bf16;
 typedef uint16_t evc_f16;   /* raw IEEE binary16 bits (the "high" precision forward operands of the L1 levels) */
@@ -795,6 +795,41 @@ int evc_eval_select_rows(const float* pred, int ld, const uint8_t* labels, int l
 int evc_ensemble_topk_rows(const float* const* preds, const int64_t* ld, const float* weights, int M, const int32_t* prior_idx,
                            const float* prior_val, int P, int kp, int rows, int cols, int mode, int k, float* out_val, int32_t* out_idx,
                            float* out_dense, int64_t ld_dense, void* stream);
+
+/* ---- student frame selection (an addition; the reference directory keeps the uniform student only) --------------------------------
+ * Which frames the student sees: src [B][S] int32, S = T / every_n (T <= 1024), src[b][j] = source frame of student slot j of video b
+ * or -1 for "no frame: a zero row".  With n = min(max(num_frames[b], 0), T) and k = int64(float64(n) / T * S) - the arithmetic of
+ * evc_frame_counts with subsampled != 0, its float64 quirk at every_n = 1 included - the entries j < k are
+ *   EVC_SELECT_UNIFORM            j * every_n, for EVERY j < S (the rule of evc_l2norm_chunk_fwd's student view, bit for bit)
+ *   EVC_SELECT_FIRST              j
+ *   EVC_SELECT_MIDDLE             (n - k) / 2 + j
+ *   EVC_SELECT_LAST               n - k + j
+ *   EVC_SELECT_FIRST_MIDDLE_LAST  three runs of kf = (k + 2) / 3, km = (k + 1) / 3, kl = k / 3 frames starting at 0, at
+ *                                 min(max((n - km) / 2, kf), n - kl - km) and at n - kl (disjoint and increasing for every k <= n)
+ *   EVC_SELECT_RANDOM             the k frames t of [0, n) with the smallest (key(t), t), in ascending t
+ * (integer divisions) and -1 for j >= k except under UNIFORM: strictly increasing, distinct frames of [0, n).
+ * key(t), all in uint32 arithmetic (wrapping products and sums), row = row0 + b:
+ *   fmix(h): h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16
+ *   h = fmix(seed * 0x9E3779B1 + draw); h = fmix(h ^ (row * 0x85EBCA77)); key = fmix(h ^ (t * 0xC2B2AE3D))
+ * stateless: a training run passes draw = its iteration and row0 = rank * B, evaluation draw = 0.
+ * One workgroup per video, ranks counted in LDS, compaction by ballots; no atomics, no scratch. */
+#define EVC_SELECT_UNIFORM 0
+#define EVC_SELECT_FIRST 1
+#define EVC_SELECT_MIDDLE 2
+#define EVC_SELECT_LAST 3
+#define EVC_SELECT_FIRST_MIDDLE_LAST 4
+#define EVC_SELECT_RANDOM 5
+int evc_student_frame_select(const int32_t* num_frames, int B, int T, int every_n, int strategy, uint32_t seed, uint32_t draw, int row0,
+                             int32_t* src, void* stream);
+/* The student-only forms (out1 == NULL) of evc_l2norm_chunk_fwd / evc_l2norm_chunk_int with the table src [B][T / every_n] in place of
+ * the rule s2 * every_n: slot j of video b reads frame src[b][j] of x and writes what that entry writes for its slot (out2, out2_lo by
+ * aux_mode, the integer image + row scales; row_pos2 / rows2).  The pad rule follows the SOURCE frame (uint8 frames at or beyond
+ * num_frames[b] are zero); an entry < 0 (or >= T) reads nothing and writes a zero row.  Only the selected frames of x are read. */
+int evc_l2norm_chunk_sel_fwd(const float* x_raw, const uint8_t* x_u8, const int32_t* num_frames, const int32_t* src, int B, int T, int F,
+                             int every_n, int C2, evc_bf16* out2, int normalize, evc_bf16* out2_lo, int aux_mode,
+                             const int32_t* row_pos2, int rows2, void* stream);
+int evc_l2norm_chunk_sel_int(const uint8_t* x_u8, const int32_t* num_frames, const int32_t* src, int B, int T, int F, int every_n, int C2,
+                             evc_bf16* out2, evc_f16* out2_int, float* rs2, const int32_t* row_pos2, int rows2, void* stream);
 
 /* utility: out[i] = value for n floats (avoids torch for tiny fills inside C loops) */
 int evc_fill_f32(float* p, int64_t n, float value, void* stream);
