@@ -1182,6 +1182,149 @@ extern "C" int evc_rep_loss_ordered(const float* state_t, const float* state_s, 
   return rep_loss_impl(state_t, state_s, B, D, grad_scale, loss, dstate_s, accumulate_grad, partials, stream);
 }
 
+// The loss section of the SERIAL distillation step (frozen teacher, DistillGraph(mode="serial")) as one launch: the teacher's CE (value
+// only), L_REP, L_PRED and the student's CE with dpred_s = g_ce dCE_s + g_kl dKL written ONCE and dstate_s = g_rep dREP.  Workgroups
+// [0, B): one prediction row each (pred_t, pred_s and the labels are read once); workgroups [B, B + NS): the [B, D] state part, grid-stride.
+// The per-element arithmetic is that of ce_loss_kernel / kl_loss_kernel / rep_loss_kernel above (same eps, same degenerate-row rules).
+// Every workgroup leaves its partial sums in the workspace - ws[0..B) teacher CE, [B..2B) L_PRED, [2B..3B) student CE, [3B..3B+NS) L_REP -
+// and distill_losses_finish_kernel adds each list in block order: the same bits on every call, in every mode.  A scale of 0 switches its
+// term off exactly (0, not 0 * inf).
+struct DistillElem { float ce_t, kl, ce_s, g; };
+__device__ __forceinline__ DistillElem distill_elem(float pt, float ps, bool pos, float it, float is, bool t_ok, float g_ce, float g_kl) {
+  const float eps = 10e-6f;   // cs/losses.py:92
+  const float FMIN = 1.17549435e-38f;
+  DistillElem r;
+  const float at = pt + eps, bt = 1.f - pt + eps;
+  r.ce_t = -(pos ? __logf(at) : __logf(bt));
+  const float a = ps + eps, bq = 1.f - ps + eps;
+  r.ce_s = -(pos ? __logf(a) : __logf(bq));
+  const float P = pt * it, q = fmaxf(ps, FMIN);
+  r.kl = (P >= FMIN) ? P * (__logf(P) - __logf(fmaxf(q * is, FMIN))) : 0.f;
+  const float gce = (g_ce != 0.f) ? (pos ? -1.f / a : 1.f / bq) * g_ce : 0.f;
+  const float gkl = (t_ok && g_kl != 0.f) ? (-P / q + is) * g_kl : 0.f;
+  r.g = gce + gkl;
+  return r;
+}
+
+__global__ __launch_bounds__(256) void distill_losses_kernel(const float* __restrict__ pt, const float* __restrict__ st,
+                                                             const float* __restrict__ ps, const float* __restrict__ ss,
+                                                             const uint8_t* __restrict__ y, const float* __restrict__ a,
+                                                             const float* __restrict__ b, int B, int V, long nd, int NS, float inv_b,
+                                                             float g_ce, float g_kl, float g_rep, float* __restrict__ dps,
+                                                             float* __restrict__ db, float* __restrict__ ws) {
+  __shared__ float sh[4];
+  if ((int)blockIdx.x < B) {
+    const int row = blockIdx.x;
+    const float FMIN = 1.17549435e-38f;
+    const bool t_ok = st[row] >= FMIN;
+    const float it = t_ok ? 1.f / st[row] : 0.f, is = 1.f / fmaxf(ss[row], FMIN);
+    const long base = (long)row * V;
+    float s_ct = 0.f, s_kl = 0.f, s_cs = 0.f;
+    const bool v4 = (V & 3) == 0 && ((uintptr_t)pt & 15) == 0 && ((uintptr_t)ps & 15) == 0 && ((uintptr_t)y & 3) == 0 &&
+                    (!dps || ((uintptr_t)dps & 15) == 0);
+    if (v4) {
+      const float4* pt4 = (const float4*)(pt + base);
+      const float4* ps4 = (const float4*)(ps + base);
+      const uchar4* y4 = (const uchar4*)(y + base);
+      for (int c4 = threadIdx.x; c4 < (V >> 2); c4 += 256) {
+        const float4 tq = pt4[c4], sq = ps4[c4];
+        const uchar4 yq = y4[c4];
+        const float tv[4] = {tq.x, tq.y, tq.z, tq.w}, sv[4] = {sq.x, sq.y, sq.z, sq.w};
+        const bool pos[4] = {yq.x != 0, yq.y != 0, yq.z != 0, yq.w != 0};
+        float g[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const DistillElem e = distill_elem(tv[r], sv[r], pos[r], it, is, t_ok, g_ce, g_kl);
+          s_ct += e.ce_t; s_kl += e.kl; s_cs += e.ce_s; g[r] = e.g;
+        }
+        if (dps) ((float4*)(dps + base))[c4] = make_float4(g[0], g[1], g[2], g[3]);
+      }
+    } else {
+      for (int c = threadIdx.x; c < V; c += 256) {
+        const DistillElem e = distill_elem(pt[base + c], ps[base + c], y[base + c] != 0, it, is, t_ok, g_ce, g_kl);
+        s_ct += e.ce_t; s_kl += e.kl; s_cs += e.ce_s;
+        if (dps) dps[base + c] = e.g;
+      }
+    }
+    s_ct = block_sum(s_ct, sh);
+    s_kl = block_sum(s_kl, sh);
+    s_cs = block_sum(s_cs, sh);
+    if (threadIdx.x == 0) {
+      ws[row] = s_ct * inv_b;
+      ws[B + row] = s_kl;
+      ws[2 * B + row] = s_cs * inv_b;
+    }
+    return;
+  }
+  const int blk = (int)blockIdx.x - B;
+  float s = 0.f;
+  const bool v4 = (nd & 3) == 0 && ((uintptr_t)a & 15) == 0 && ((uintptr_t)b & 15) == 0 && (!db || ((uintptr_t)db & 15) == 0);
+  if (v4) {
+    for (long i4 = (long)blk * 256 + threadIdx.x; i4 < (nd >> 2); i4 += (long)NS * 256) {
+      const float4 aq = ((const float4*)a)[i4], bq = ((const float4*)b)[i4];
+      const float d[4] = {aq.x - bq.x, aq.y - bq.y, aq.z - bq.z, aq.w - bq.w};
+      float g[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        s += d[r] * d[r];
+        g[r] = (g_rep != 0.f) ? -2.f * d[r] * inv_b * g_rep : 0.f;
+      }
+      if (db) ((float4*)db)[i4] = make_float4(g[0], g[1], g[2], g[3]);
+    }
+  } else {
+    for (long i = (long)blk * 256 + threadIdx.x; i < nd; i += (long)NS * 256) {
+      const float d = a[i] - b[i];
+      s += d * d;
+      if (db) db[i] = (g_rep != 0.f) ? -2.f * d * inv_b * g_rep : 0.f;
+    }
+  }
+  s = block_sum(s, sh);
+  if (threadIdx.x == 0) ws[3 * (long)B + blk] = s * inv_b;
+}
+
+// One workgroup, four waves: wave w owns loss slot w.  The partials pass through LDS in pieces of 1024 (loaded by all 256 threads), lane 0
+// of each wave adds its piece in block order - the order loss_partials_finish_kernel adds in, without a chain of dependent global loads.
+__global__ __launch_bounds__(256) void distill_losses_finish_kernel(const float* __restrict__ ws, int B, int NS, float* __restrict__ losses) {
+  __shared__ float sh[4][1024];
+  // loss slot (DistillGraph.LOSS_SLOTS) -> its list of partials: teacher CE, L_REP, L_PRED, student CE
+  const long off[4] = {0, 3 * (long)B, (long)B, 2 * (long)B};
+  const int cnt[4] = {B, NS, B, B};
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int nmax = B > NS ? B : NS;
+  float s = 0.f;
+  for (int base = 0; base < nmax; base += 1024) {
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      for (int i = threadIdx.x; i < 1024; i += 256)
+        if (base + i < cnt[k]) sh[k][i] = ws[off[k] + base + i];
+    __syncthreads();
+    if (lane == 0) {
+      const int n = cnt[w] - base < 1024 ? cnt[w] - base : 1024;
+      for (int i = 0; i < n; ++i) s += sh[w][i];
+    }
+  }
+  if (lane == 0) losses[w] += s;
+}
+
+extern "C" int evc_distill_losses(const float* pred_t, const float* rowsum_t, const float* pred_s, const float* rowsum_s,
+                                  const uint8_t* labels, const float* state_t, const float* state_s, int B, int V, int D,
+                                  float g_ce, float g_kl, float g_rep, float* losses, float* dpred_s, float* dstate_s,
+                                  float* workspace, void* stream) {
+  EVC_REQUIRE(B > 0 && V > 0 && D > 0, EVC_ERR_BAD_SHAPE, "evc_distill_losses: bad shape");
+  EVC_REQUIRE(pred_t && rowsum_t && pred_s && rowsum_s && labels && state_t && state_s && losses, EVC_ERR_BAD_ARG,
+              "evc_distill_losses: a required pointer is NULL");
+  EVC_REQUIRE(workspace, EVC_ERR_BAD_ARG, "evc_distill_losses: workspace (3 * B + 256 floats of scratch) is required");
+  const long nd = (long)B * D;
+  const long want = (nd + 1023) / 1024;                 // 4 elements per thread and trip
+  const int NS = (int)(want < 1 ? 1 : (want < 256 ? want : 256));
+  hipLaunchKernelGGL(distill_losses_kernel, dim3(B + NS), dim3(256), 0, (hipStream_t)stream, pred_t, rowsum_t, pred_s, rowsum_s, labels,
+                     state_t, state_s, B, V, nd, NS, 1.0f / B, g_ce, g_kl, g_rep, dpred_s, dstate_s, workspace);
+  hipLaunchKernelGGL(distill_losses_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, B, NS, losses);
+  EVC_LAUNCH_CHECK();
+  return EVC_OK;
+}
+
 // ---------------------------------------------------------------------------
 // a8 + a9: regulariser, per-tensor clip, TF-Adam
 // ---------------------------------------------------------------------------

@@ -9,6 +9,9 @@ iteration (one increment per train op, :332,:416), per-tensor gradient
 clipping, teacher tensors constant in the student loss, both updates computed
 from the pre-update weights of the same step.
 
+Serial distillation (new; the paper's Serial training, which the reference's train.py does not ship): mode "serial" trains
+the student against a frozen, forward-only teacher - one train op, the loss section as one launch (ops.distill_losses).
+
 Data parallel (new; the reference is single-device): one process per GPU,
 replicated parameters, per-rank batch, gradients summed with RCCL all-reduce
 (``torch.distributed`` backend "nccl") on the flat gradient buffer - the MoE
@@ -295,6 +298,19 @@ class GradReducer:
         self._pending = []
 
 
+def check_distill_losses(words):
+    """--distill_losses / DistillGraph(distill_losses=...): a non-empty subset of ("rep", "pred", "ce"), as a comma list or a
+    sequence; returned as a tuple in that canonical order.  Unknown, empty and repeated words are refused."""
+    if isinstance(words, str):
+        words = [w.strip() for w in words.split(",")]
+    words = list(words)
+    known = ("rep", "pred", "ce")
+    bad = [w for w in words if w not in known]
+    if bad or not words or len(set(words)) != len(words):
+        raise ValueError("distill_losses %r: a comma list of distinct words out of rep, pred, ce (at least one)" % (",".join(map(str, words)),))
+    return tuple(w for w in known if w in words)
+
+
 def serial_comm():
     """EVC_DP_SERIAL_COMM=1: one communicator, one collective at a time (see GradReducer)."""
     return os.environ.get("EVC_DP_SERIAL_COMM") == "1"
@@ -392,20 +408,26 @@ def frame_counts_and_plans(g, num_frames, nh, need_teacher, need_student):
 
 class DistillGraph:
     """mode: 'teacher_student' (train.py), 'teacher' (teacher only, BASELINE cfg 2),
-    'student' (train_finetune.py)."""
+    'student' (train_finetune.py), 'serial' (the paper's Serial training: the student against a FROZEN teacher -
+    forward-only 'model' tower, no tape / gradient / Adam state, never written; one train op)."""
 
     LOSS_SLOTS = ("label_loss", "student_loss_state", "pred_loss", "student_label_loss")
     # host issue orders of the two towers' backward phases (HLstmTower.backward_phases: MoE head, L2 layer 1, L2 layer 0, L1 layer 1,
     # L1 layer 0 each): letters name the tower whose next phase is issued; whatever is left afterwards is drained student first
     ISSUE_ORDERS = {"sequential": "sssss", "interleaved": "tsstsstst"}
+    MODES = ("teacher_student", "teacher", "student", "serial")
+    DISTILL_LOSSES = ("rep", "pred", "ce")      # the student's loss terms in mode "serial" (the paper's ablation); all three = cs/train.py:406
 
     def __init__(self, batch_size, every_n=10, mode="teacher_student", feature_size=1152, vocab_size=4716,
                  max_frames=300, num_inputs_to_lstm=20, num_inputs_l1_student=5, lstm_cells=1024, lstm_layers=2,
                  num_mixtures=2, base_learning_rate=0.001, learning_rate_decay=1.0,
                  learning_rate_decay_examples=4000000, regularization_penalty=2.0, clip_gradient_norm=1.0,
                  count_rep_twice=True, device="cuda:0", seed=7, process_group=None, overlap_towers=True,
-                 precision="bf16", student_sampling="uniform", sampling_seed=0):
-        assert mode in ("teacher_student", "teacher", "student")
+                 precision="bf16", student_sampling="uniform", sampling_seed=0, distill_losses=DISTILL_LOSSES):
+        assert mode in self.MODES
+        self.distill_losses = check_distill_losses(distill_losses)
+        if self.distill_losses != self.DISTILL_LOSSES and mode != "serial":
+            raise ValueError("distill_losses selects the student's loss terms of mode 'serial' only (mode %r trains on all of its losses)" % mode)
         self.mode, self.B, self.every_n = mode, batch_size, every_n
         # which frames the student sees (ops.STUDENT_SAMPLING; input_views): "uniform" is the grid s * every_n of the reference
         self.student_sampling, self.sampling_seed = ops.check_student_sampling(student_sampling), int(sampling_seed)
@@ -417,6 +439,9 @@ class DistillGraph:
         self.pg = process_group
         self.reducer = GradReducer(process_group)
         self.world, self.dp = self.reducer.world, self.reducer.active
+        if mode == "serial" and (self.world > 1 or self.dp):
+            raise ValueError("DistillGraph(mode='serial') is not data parallel yet (process group of %d ranks): train the student "
+                             "against the frozen teacher on one device" % self.world)
         # The student's collectives get a communicator of their own: one process group executes its collectives in
         # issue order, so on a shared group the teacher's early factor all-gather (host-issued after the student's
         # backward) would queue behind the student's last gradient all-reduce and hold the teacher's whole update
@@ -427,9 +452,12 @@ class DistillGraph:
             self.reducer_s = GradReducer(torch.distributed.new_group(ranks) if ranks is not None else process_group)
         self.global_step = 0
         self.teacher = self.student = None
+        self.train_teacher = mode in ("teacher_student", "teacher")       # "serial": the teacher is a constant of the step
         if mode != "student":
             self.teacher = HLstmTower(batch_size, max_frames, num_inputs_to_lstm, feature_size, vocab_size, lstm_cells,
-                                      lstm_layers, num_mixtures, device, True, "model", seed)
+                                      lstm_layers, num_mixtures, device, self.train_teacher, "model", seed)
+            if not self.train_teacher:
+                self.teacher.store.drop_training_state()
         if mode != "teacher":
             validate_every_n(every_n, num_inputs_l1_student, max_frames)
             self.S = max_frames // every_n
@@ -539,6 +567,8 @@ class DistillGraph:
         teacher's forward is done (teacher tensors are constants in the student loss), so the
         student runs on a second HIP stream: its many small launches (M = batch L2 steps, 30-frame
         L1) fill the CUs that the teacher's under-filled launches leave idle."""
+        if self.mode == "serial":
+            return self._step_serial(x_raw, labels_u8, num_frames, apply, nh)
         B = x_raw.shape[0]
         V = labels_u8.shape[1]
         dev = self.device
@@ -697,6 +727,78 @@ class DistillGraph:
         out["global_step"] = self.global_step
         return out
 
+    def _step_serial(self, x_raw, labels_u8, num_frames, apply=True, nh=None):
+        """mode "serial": one iteration of the student against the frozen teacher.  Same inputs and `out` keys as _step.
+
+        Schedule: the teacher's forward (tape-free, the step's longest chain) on `main`, the student's forward next to it on `side`
+        - neither reads the other -; the loss section (ops.distill_losses: one launch + its finish, dpred_s written once) on `side`
+        once both are done; then the student's backward and update exactly as in mode "student".  The teacher's backward, weight
+        gradients, update and tape of the parallel step do not exist here."""
+        B, V = x_raw.shape[0], labels_u8.shape[1]
+        dev = self.device
+        if self._dp_s is None or self._dp_s.shape[0] != B:
+            self._dp_s = torch.empty((B, V), dtype=F32, device=dev)
+        main = torch.cuda.current_stream(dev)
+        tp, sp = frame_counts_and_plans(self, num_frames, nh, True, True)
+        self.sampling_draw = self.global_step          # one train op per iteration: a new "random" draw per step
+        self.sampling_row0 = 0
+        xt, xs = input_views(self, x_raw, num_frames, tp, sp, True)
+        self.student.run_deferred()
+        self.losses.zero_()
+        mark = self._mark
+        mark("start", main)
+        lr = exponential_decay(self.lr0, self.global_step, B, self.lr_decay_examples, self.lr_decay)
+        l2c = self.reg_pen * 1e-8
+        self._teacher_applied = self._student_applied = False
+        two_streams = self.overlap_towers
+        side = self._side if two_streams else main
+        n_s, l1s, l2s, plan_s = sp
+        l1, l2, plan_t = tp
+        if two_streams:
+            self._ev_in.record(main)
+            side.wait_event(self._ev_in)
+        t_state, t_pred = self.teacher.forward(xt, l1, l2, plan_t)
+        mark("teacher_fwd_done", main)
+        if two_streams:
+            self._ev_fwd.record(main)
+        with torch.cuda.stream(side):
+            mark("student_start", side)
+            s_state, s_pred = self.student.forward(xs, l1s, l2s, plan_s)
+            mark("student_fwd_done", side)
+            if two_streams:
+                side.wait_event(self._ev_fwd)
+            if self._ds_s is None or self._ds_s.shape != s_state.shape:
+                self._ds_s = torch.empty_like(s_state)
+            on = self.distill_losses
+            ops.distill_losses(t_pred, self.teacher.rowsum, s_pred, self.student.rowsum, labels_u8, t_state, s_state, self.losses,
+                               self._dp_s, self._ds_s, g_ce=(1.0 / B) if "ce" in on else 0.0, g_kl=1.0 if "pred" in on else 0.0,
+                               g_rep=self.rep_w if "rep" in on else 0.0)
+            mark("losses_done", side)
+            early_s = (lr, self.clip, l2c) if (apply and self.overlap_towers and self._aux_s is not None) else None
+            gen_s = self.student.backward_phases(self._ds_s, self._dp_s, aux=self._aux_s if self.overlap_towers else None,
+                                                 early_apply=early_s, defer=self.defer_updates, opt=self._opt_s)
+            while next(gen_s, self) is not self:       # every phase to its end (2 * lstm_layers + 2 resumptions, as in _step)
+                pass
+            self._student_applied = early_s is not None
+            mark("student_done", side)
+            if two_streams:
+                self._ev_student.record(side)
+                used = (xs if isinstance(xs, tuple) else (xs,)) + (n_s, l1s, l2s)
+                if plan_s is not None:
+                    used += (plan_s.pos, plan_s.inv, plan_s.lens)
+                for t in used:                                          # allocated on `main`, consumed on `side`
+                    if t is not None:
+                        t.record_stream(side)
+        if two_streams:
+            main.wait_event(self._ev_student)
+        out = dict(student_predictions=s_pred, student_state=s_state, num_frames_student=n_s, student_loss_state=self.losses[1],
+                   pred_loss=self.losses[2], student_label_loss=self.losses[3], predictions=t_pred, teacher_state=t_state,
+                   loss=self.losses[0])
+        if apply:
+            self._apply_gradients(B, lr)
+        out["global_step"] = self.global_step
+        return out
+
     def flush(self):
         """Enqueue and join the deferred updates of the last step (defer_updates): afterwards every weight, moment and operand
         shadow of both towers is current in the order of the caller's stream.  Cheap no-op when nothing is pending."""
@@ -717,7 +819,7 @@ class DistillGraph:
         l2c = self.reg_pen * 1e-8
         if lr is None:
             lr = exponential_decay(self.lr0, self.global_step, batch_size * self.world, self.lr_decay_examples, self.lr_decay)
-        if self.teacher is not None:
+        if self.teacher is not None and self.train_teacher:
             if not getattr(self, "_teacher_applied", False):
                 self.teacher.apply_gradients(lr, self.clip, l2c)
             self.global_step += 1

@@ -65,6 +65,10 @@ class ParamStore:
         self.m = torch.zeros(off, dtype=F32, device=device)
         self.v = torch.zeros(off, dtype=F32, device=device)
 
+    def drop_training_state(self):
+        """A frozen tower (DistillGraph(mode="serial")'s teacher): no gradient buffer, no Adam moments - the masters alone."""
+        self.grad = self.m = self.v = None
+
     def view(self, buf, k):
         shp = self.shapes[k]
         n = int(math.prod(shp))

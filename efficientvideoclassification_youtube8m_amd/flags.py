@@ -22,6 +22,12 @@ def _sampling(v):
     return check_student_sampling(str(v).strip(), "--student_sampling")
 
 
+def _distill_losses(v):
+    """A --distill_losses list, checked while the flags are parsed (distill.check_distill_losses); kept as the canonical comma list."""
+    from .distill import check_distill_losses
+    return ",".join(check_distill_losses(str(v)))
+
+
 def _bool(v):
     if isinstance(v, bool):
         return v
@@ -114,6 +120,14 @@ _define("student_sampling", "uniform", _sampling, "uniform|first|middle|last|fir
         "record the word; validate / inference warn when the flag disagrees with it, and the flag wins")
 _define("student_sampling_seed", 0, int, "seed of --student_sampling random")
 _define("ensemble_sampling", "", str, "one --student_sampling word per member (ignored for teachers); '' = --student_sampling for all")
+# ---- serial distillation (train): the student against a finished, frozen teacher -----------------------------------------------------------
+_define("teacher_dir", "", str, "HierarchicalLstmModel: directory of a finished teacher (train --teacher_only True, or any checkpoint with "
+        "model/* variables).  Set: the student is trained against that FROZEN teacher (the paper's Serial training; DistillGraph mode "
+        "'serial'): the teacher runs forward only and is never written, one train op per iteration (global_step += 1); the checkpoint keeps "
+        "model/* bit-identical to the source next to model_student/*.  On resume both towers come from --train_dir.  Not with "
+        "--teacher_only, train_finetune or several ranks")
+_define("distill_losses", "rep,pred,ce", _distill_losses, "with --teacher_dir: which of L_REP, L_PRED, L_CE the student is trained on (comma "
+        "list out of rep, pred, ce; the default is the reference's total, L_REP counted twice).  A loss left out is still computed and logged")
 # ---- ensembles (inference / validate; cs/inference_ensemble.py:28-61 has preds_pattern, the others are additions) -----------------------
 _define("ensemble_dirs", "", str, "comma separated checkpoint directories of the ensemble's members (1 .. 8); '' = the single model of "
         "--train_dir, which is not consulted otherwise.  Every member runs its forward on the same batch and ops.ensemble_topk_rows "

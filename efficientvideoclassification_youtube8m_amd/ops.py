@@ -833,6 +833,26 @@ def rep_loss(state_t, state_s, loss, dstate_s=None, grad_scale=1.0, accumulate_g
     _lib.call("evc_rep_loss", _p(state_t), _p(state_s), B, D, grad_scale, _p(loss), _p(dstate_s), 1 if accumulate_grad else 0, _stream())
 
 
+def distill_losses(pred_t, rowsum_t, pred_s, rowsum_s, labels_u8, state_t, state_s, losses, dpred_s=None, dstate_s=None,
+                   g_ce=1.0, g_kl=1.0, g_rep=1.0):
+    """The four losses of the serial distillation step in one launch + its finish (evc_distill_losses): losses[0:4] += (teacher CE,
+    L_REP, L_PRED, student CE) - DistillGraph.LOSS_SLOTS -, dpred_s = g_ce dCE_s + g_kl dL_PRED (written once), dstate_s = g_rep dL_REP.
+    The scales are the grad_scale arguments of ce_loss / kl_pred_loss / rep_loss; a scale of 0 leaves its term out of the gradient (its
+    value is still reported).  Fixed summation order in every mode; scratch from the stream-aware caching allocator."""
+    B, V = pred_t.shape
+    D = state_t.shape[1]
+    assert pred_s.shape == (B, V) and labels_u8.shape == (B, V) and state_s.shape == (B, D) and state_t.shape[0] == B
+    assert rowsum_t.numel() >= B and rowsum_s.numel() >= B and losses.numel() >= 4
+    assert pred_t.dtype == F32 and pred_s.dtype == F32 and state_t.dtype == F32 and state_s.dtype == F32 and labels_u8.dtype == torch.uint8
+    for t in (pred_t, pred_s, labels_u8, state_t, state_s, losses):
+        assert t.is_contiguous()
+    for t, shp in ((dpred_s, (B, V)), (dstate_s, (B, D))):
+        assert t is None or (t.dtype == F32 and t.shape == shp and t.is_contiguous())
+    ws = torch.empty(3 * B + 256, dtype=F32, device=pred_t.device)
+    _lib.call("evc_distill_losses", _p(pred_t), _p(rowsum_t), _p(pred_s), _p(rowsum_s), _p(labels_u8), _p(state_t), _p(state_s), B, V, D,
+              float(g_ce), float(g_kl), float(g_rep), _p(losses), _p(dpred_s), _p(dstate_s), _p(ws), _stream())
+
+
 def clip_adam_small(ps, gs, ms, vs, sums, clip_norm, lr_t, beta1=0.9, beta2=0.999, eps=1e-8):
     """Per-tensor clip + TF-Adam of up to 16 small tensors (no l2 term) in one launch (evc_clip_adam_small): sums[i] receives {|g_i|^2, 0}."""
     import ctypes as C

@@ -15,6 +15,8 @@ What is replaced: TF Supervisor/queue runners -> a plain loop; TF checkpoints ->
 ``torch.save`` of a TF-named state dict (model.ckpt-<step>.pt, max_to_keep=1);
 TFRecord input -> readers.py (native parser, uint8 feed, pinned staging); the pattern
 "synthetic" generates random uint8 videos on the device instead.
+Serial distillation (not a reference mode; the paper's second way to train a student): ``--teacher_dir DIR`` trains the
+student against the frozen teacher of DIR's latest checkpoint (distill.DistillGraph mode "serial").
 Multi-GPU: launch with ``python -m torch.distributed.run --nproc-per-node N``;
 ``--gpu`` is then ignored in favour of LOCAL_RANK.
 """
@@ -52,6 +54,41 @@ def _apply_precision(tw):
         tw.set_precision(FLAGS.precision)
 
 
+DEFAULT_DISTILL_LOSSES = "rep,pred,ce"
+
+
+def check_serial_flags(finetune=False, world=1):
+    """--teacher_dir / --distill_losses against the flags and the launch they exclude (all ValueError, before anything touches the device).
+    Returns True when the flags ask for serial distillation."""
+    serial = bool(FLAGS.teacher_dir)
+    if not serial:
+        if FLAGS.distill_losses != DEFAULT_DISTILL_LOSSES:
+            raise ValueError("--distill_losses %s needs --teacher_dir: it selects the student's losses of serial distillation "
+                             "(the teacher+student graph trains on all of them)" % FLAGS.distill_losses)
+        return False
+    if getattr(FLAGS, "teacher_only", False):
+        raise ValueError("--teacher_dir %s with --teacher_only: a frozen teacher cannot be the tower that is trained" % FLAGS.teacher_dir)
+    if finetune:
+        raise ValueError("--teacher_dir %s with --finetune: train_finetune trains the student on L_CE alone, without a teacher "
+                         "(serial distillation is train --teacher_dir)" % FLAGS.teacher_dir)
+    if world > 1:
+        raise ValueError("--teacher_dir %s on %d ranks: serial distillation is not data parallel yet, run it on one device" %
+                         (FLAGS.teacher_dir, world))
+    return True
+
+
+def load_frozen_teacher(graph, teacher_dir):
+    """The model/* variables of latest_checkpoint(teacher_dir) into the serial graph's frozen teacher.  Returns the checkpoint's path."""
+    ck = latest_checkpoint(teacher_dir)
+    if ck is None:
+        raise ValueError("--teacher_dir %s: no model.ckpt-*.pt checkpoint there" % teacher_dir)
+    sd = torch.load(ck, map_location="cpu")
+    if not any(k.startswith("model/") and torch.is_tensor(v) for k, v in sd.items()):
+        raise ValueError("--teacher_dir %s: %s holds no model/* variables (not a teacher checkpoint)" % (teacher_dir, os.path.basename(ck)))
+    graph.teacher.load_state_dict(sd)
+    return ck
+
+
 def build_graph(model, label_loss_fn, feature_size, batch_size, every_n, device, finetune=False, process_group=None):
     """Equivalent of cs/train.py:185-427 (and cs/train_finetune.py:185-331 when
     finetune): returns the graph object whose ``step`` runs one iteration."""
@@ -66,11 +103,17 @@ def build_graph(model, label_loss_fn, feature_size, batch_size, every_n, device,
         # frames in 5 chunks of 60 (cs/train.py:262-272,349-356): global_step += 2 and the checkpoint holds both scopes.
         # Teacher-only training (BASELINE cfg 2) is not a reference mode: it is asked for with --teacher_only.
         mode = "student" if finetune else ("teacher" if getattr(FLAGS, "teacher_only", False) else "teacher_student")
+        if FLAGS.teacher_dir and check_serial_flags(finetune):
+            # Serial distillation (--teacher_dir): the student against a frozen teacher - not a reference mode either
+            mode = "serial"
+            common["distill_losses"] = FLAGS.distill_losses
         return DistillGraph(batch_size, every_n=every_n, mode=mode, feature_size=feature_size, vocab_size=NUM_CLASSES,
                             max_frames=FLAGS.max_num_frames, num_inputs_to_lstm=FLAGS.num_inputs_to_lstm,
                             lstm_cells=FLAGS.lstm_cells, lstm_layers=FLAGS.lstm_layers,
                             num_mixtures=FLAGS.moe_num_mixtures, device=device, precision=FLAGS.precision,
                             student_sampling=FLAGS.student_sampling, sampling_seed=FLAGS.student_sampling_seed, **common)
+    if FLAGS.teacher_dir:
+        raise ValueError("--teacher_dir %s: serial distillation is built for HierarchicalLstmModel, not %s" % (FLAGS.teacher_dir, type(model).__name__))
     if isinstance(model, frame_level_models.DbofModel):
         tw = DbofTower(batch_size, FLAGS.max_num_frames, feature_size, NUM_CLASSES, FLAGS.iterations,
                        FLAGS.dbof_cluster_size, FLAGS.dbof_hidden_size, FLAGS.moe_num_mixtures, device=device,
@@ -163,10 +206,13 @@ def save_checkpoint(graph, train_dir, rank):
     sd = {"global_step": graph.global_step}
     if getattr(graph, "student", None) is not None:
         sd["student_sampling"] = graph.student_sampling          # metadata: the frames this student was trained on (--student_sampling)
+    if getattr(graph, "mode", None) == "serial":                 # metadata: trained against the frozen teacher in model/*, on these losses
+        sd["distill_mode"], sd["distill_losses"] = "serial", ",".join(graph.distill_losses)
     for tw in (getattr(graph, "teacher", None), getattr(graph, "student", None), getattr(graph, "tower", None)):
         if tw is not None:
             sd.update({k: v.cpu() for k, v in tw.state_dict().items()})
-            sd["%s/adam" % tw.scope] = {"t": tw.adam_t, "m": tw.store.m.cpu(), "v": tw.store.v.cpu()}
+            if tw.store.m is not None:                           # (a frozen tower has no optimizer state: serial distillation's teacher)
+                sd["%s/adam" % tw.scope] = {"t": tw.adam_t, "m": tw.store.m.cpu(), "v": tw.store.v.cpu()}
             sd["%s/precision_layout" % tw.scope] = tw.precision_layout()      # metadata: the forward-operand layout these weights were trained under
     path = os.path.join(train_dir, "model.ckpt-%d.pt" % graph.global_step)
     # like tf.train.Saver: write to a temporary name, flush to disk, rename (a validate.py polling the directory never
@@ -193,7 +239,7 @@ def restore_checkpoint(graph, path):
         if tw is not None and any(k.startswith(tw.scope + "/") for k in sd):
             tw.load_state_dict(sd)
             ad = sd.get("%s/adam" % tw.scope)
-            if ad:
+            if ad and tw.store.m is not None:                    # (a frozen tower keeps no moments, whatever the checkpoint holds)
                 tw.adam_t = ad["t"]
                 tw.store.m.copy_(ad["m"])
                 tw.store.v.copy_(ad["v"])
@@ -224,6 +270,7 @@ def main(argv=None):
     logging.basicConfig(level=logging.INFO, format="INFO:evc:%(message)s")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
+    serial = check_serial_flags(finetune, world)
     local = int(os.environ.get("LOCAL_RANK", str(FLAGS.gpu)))
     # test hook (tests/test_gpu_dp.py): several ranks on ONE GPU over gloo, to run this file's multi-rank path on a
     # single-GPU box (RCCL refuses two ranks per device).  Never set in a real run.
@@ -257,6 +304,11 @@ def main(argv=None):
     else:
         logging.info("%s: Restoring from %s", task, ck)
         restore_checkpoint(graph, ck)
+        if serial:
+            logging.info("%s: --teacher_dir %s only selects serial distillation on resume: the frozen teacher and the student both "
+                         "come from %s", task, FLAGS.teacher_dir, ck)
+    if serial and ck is None and getattr(graph, "mode", None) == "serial":
+        logging.info("%s: Frozen teacher from %s", task, load_frozen_teacher(graph, FLAGS.teacher_dir))
     data, num_batches = get_input_data(FLAGS.train_data_pattern, FLAGS.batch_size, feature_size, device, FLAGS.num_epochs,
                                        1234 + rank, rank, world)
     step_limit = agree_step_limit(FLAGS.max_steps, num_batches, world, device)
@@ -266,7 +318,7 @@ def main(argv=None):
     logging.info("%s: Entering training loop.", task)
     start, last_save, it = time.time(), time.time(), 0
     is_distill = isinstance(graph, DistillGraph)
-    steps_per_it = 2 if is_distill and graph.teacher and graph.student else 1
+    steps_per_it = 2 if is_distill and graph.mode == "teacher_student" else 1
     copy_stream = torch.cuda.Stream(device=device)
     host_bufs = {}                       # pinned staging, two alternating sets (one may still be read while the next fills)
 

@@ -36,7 +36,7 @@ extern "C" {
 #define EVC_ERR_HIP (-4)
 #define EVC_ERR_BAD_ARG (-5)
 
-#define EVC_VERSION 107   /* 107 (round 6, late): evc_lstm_level2_fwd_high (the two-layer L1 level of the "high" mode in T + 1 two-tile launches); evc_topk_rows (per-row top-k of the inference binary's prediction file; an addition, no existing entry changed), later evc_eval_select_rows and evc_ensemble_topk_rows (the combination of several members' predictions in front of that selection) and evc_student_frame_select / evc_l2norm_chunk_sel_fwd / evc_l2norm_chunk_sel_int (student frame selection) the same way; 106 (round 6): evc_gemm_nt_sqnorm, evc_l2norm_chunk_int + the x_row_scale / x_col_const / b8_gap arguments of evc_lstm_layer_fwd_f16_fp8lo (integer-frame layer 0: the uint8 input exact), evc_lstm_layer_fwd_f16_fp8lo / evc_lstm_stack2_fwd_f16_fp8lo gained h_lo (low-order half of h corrected: 4H-byte h rows), evc_cast_f32_to_fp8_lohi, evc_lstm_adam_fused gained fp8_hi_tail; evc_absmax_partials, evc_cast_f32_to_f16_fp8x_dyn, evc_gemm_nt_f16_fp8_dyn (dynamic e4m3 range of the MoE head's input state); evc_l2norm_chunk_fwd accepts out1 == NULL (student-only graphs read the sub-sampled frames only), evc_clip_adam_small limited to 2^15 elements per tensor; 105 (round 5, second session): evc_cast_f32_to_f16_dither, evc_lstm_layer_fwd_f16_dith (time-dithered f16 weight images: an L1 layer of the "high" mode without stages for its weights' low-order halves), evc_gemm_tn2_rows (weight-gradient products that skip the dead rows of a row-planned level's time slabs); 104 (round 5): evc_lstm_level2_fwd, evc_ce_loss_ordered, evc_rep_loss_ordered, evc_gemm_tn2_slabs, evc_sum_slabs, evc_clip_adam_small; evc_moe_grad_update* accept p_bf16 == NULL (forward shadow not written), evc_lstm_stack2_bwd runs M <= 512 stacks on the skinny pair launches, evc_dbof_cluster_pool_fwd walks tiles (EVC_DBOF_WALK), EVC_DETERMINISTIC parsed as "set, not empty, not 0"; 103 (round 4): evc_sqnorm2_partials, evc_lstm_adam_fused, evc_gram_slabs, evc_moe_grad_norms, evc_moe_grad_update_apply, evc_adam2d_fused, evc_colsum_bf16_det, evc_sample_sequence_gather, evc_relu6_fwd/bwd, evc_framepool_mean_fwd/bwd, evc_stream_create_cu_mask / evc_stream_destroy; EVC_DETERMINISTIC=1 read by the library; 102: evc_lstm_layer_fwd_f16_fp8lo, evc_lstm_stack2_fwd_f16_fp8lo, evc_gemm_nt_f16_fp8, evc_cast_f32_to_fp8_lo, evc_cast_f32_to_f16_fp8x, aux_mode 5, evc_moe_grad_update_wide; 101 (round 3): evc_l2norm_chunk_fwd gained aux_mode; evc_lstm_layer_fwd_hp takes wide split operands; f16 / wide-split entries added */
+#define EVC_VERSION 107   /* 107 (round 6, late): evc_lstm_level2_fwd_high (the two-layer L1 level of the "high" mode in T + 1 two-tile launches); evc_topk_rows (per-row top-k of the inference binary's prediction file; an addition, no existing entry changed), later evc_eval_select_rows and evc_ensemble_topk_rows (the combination of several members' predictions in front of that selection) and evc_student_frame_select / evc_l2norm_chunk_sel_fwd / evc_l2norm_chunk_sel_int (student frame selection) and evc_distill_losses (the loss section of the serial distillation step) the same way; 106 (round 6): evc_gemm_nt_sqnorm, evc_l2norm_chunk_int + the x_row_scale / x_col_const / b8_gap arguments of evc_lstm_layer_fwd_f16_fp8lo (integer-frame layer 0: the uint8 input exact), evc_lstm_layer_fwd_f16_fp8lo / evc_lstm_stack2_fwd_f16_fp8lo gained h_lo (low-order half of h corrected: 4H-byte h rows), evc_cast_f32_to_fp8_lohi, evc_lstm_adam_fused gained fp8_hi_tail; evc_absmax_partials, evc_cast_f32_to_f16_fp8x_dyn, evc_gemm_nt_f16_fp8_dyn (dynamic e4m3 range of the MoE head's input state); evc_l2norm_chunk_fwd accepts out1 == NULL (student-only graphs read the sub-sampled frames only), evc_clip_adam_small limited to 2^15 elements per tensor; 105 (round 5, second session): evc_cast_f32_to_f16_dither, evc_lstm_layer_fwd_f16_dith (time-dithered f16 weight images: an L1 layer of the "high" mode without stages for its weights' low-order halves), evc_gemm_tn2_rows (weight-gradient products that skip the dead rows of a row-planned level's time slabs); 104 (round 5): evc_lstm_level2_fwd, evc_ce_loss_ordered, evc_rep_loss_ordered, evc_gemm_tn2_slabs, evc_sum_slabs, evc_clip_adam_small; evc_moe_grad_update* accept p_bf16 == NULL (forward shadow not written), evc_lstm_stack2_bwd runs M <= 512 stacks on the skinny pair launches, evc_dbof_cluster_pool_fwd walks tiles (EVC_DBOF_WALK), EVC_DETERMINISTIC parsed as "set, not empty, not 0"; 103 (round 4): evc_sqnorm2_partials, evc_lstm_adam_fused, evc_gram_slabs, evc_moe_grad_norms, evc_moe_grad_update_apply, evc_adam2d_fused, evc_colsum_bf16_det, evc_sample_sequence_gather, evc_relu6_fwd/bwd, evc_framepool_mean_fwd/bwd, evc_stream_create_cu_mask / evc_stream_destroy; EVC_DETERMINISTIC=1 read by the library; 102: evc_lstm_layer_fwd_f16_fp8lo, evc_lstm_stack2_fwd_f16_fp8lo, evc_gemm_nt_f16_fp8, evc_cast_f32_to_fp8_lo, evc_cast_f32_to_f16_fp8x, aux_mode 5, evc_moe_grad_update_wide; 101 (round 3): evc_l2norm_chunk_fwd gained aux_mode; evc_lstm_layer_fwd_hp takes wide split operands; f16 / wide-split entries added */
 
 typedef uint16_t evc_bf16;
 typedef uint16_t evc_f16;   /* raw IEEE binary16 bits (the "high" precision forward operands of the L1 levels) */
@@ -492,6 +492,23 @@ int evc_rep_loss(const float* state_t, const float* state_s, int B, int D, float
 int evc_rep_loss_ordered(const float* state_t, const float* state_s, int B, int D, float grad_scale,
                          float* loss, float* dstate_s, int accumulate_grad, float* partials /* 256 floats of scratch: fixed-order sum, as evc_ce_loss_ordered */,
                          void* stream);
+/* The loss section of the SERIAL distillation step (a student trained against a frozen teacher) in one launch + a one-workgroup finish:
+ *   losses[0] += CE(pred_t, labels)   (value only: the teacher is a constant)      losses[1] += L_REP(state_t, state_s)
+ *   losses[2] += L_PRED(pred_t || pred_s)                                          losses[3] += CE(pred_s, labels)
+ * with the definitions of evc_ce_loss / evc_rep_loss / evc_kl_pred_loss (eps = 10e-6; a teacher row sum below FLT_MIN contributes loss 0 and
+ * KL gradient 0, student values are clamped at FLT_MIN); the values do not depend on the scales.
+ *   dpred_s  [B][V] (may be NULL) = g_ce * d(sum_b CE_s)/dpred_s + g_kl * dL_PRED/dpred_s   - written once, never accumulated
+ *   dstate_s [B][D] (may be NULL) = g_rep * dL_REP/dstate_s
+ * g_ce / g_kl / g_rep are the grad_scale arguments of evc_ce_loss / evc_kl_pred_loss / evc_rep_loss with their meaning there: g_ce carries
+ * the caller's 1/B of the batch mean (as evc_ce_loss's does), L_REP's 1/B is applied here (as in evc_rep_loss); loss weights and data-parallel
+ * factors ride on all three.  A scale of 0 gives exactly 0 for its term, on degenerate rows too.
+ * pred_* / labels rows and the states are read once, 16 bytes per lane where V % 4 == 0 / (B * D) % 4 == 0 and the pointers are 16-byte
+ * aligned (labels: 4-byte).  workspace: 3 * B + 256 floats of scratch - every workgroup leaves its partial sums there and the finish
+ * launch adds them in workgroup order: two calls on the same inputs give the same bits, with or without EVC_DETERMINISTIC. */
+int evc_distill_losses(const float* pred_t, const float* rowsum_t, const float* pred_s, const float* rowsum_s,
+                       const uint8_t* labels, const float* state_t, const float* state_s, int B, int V, int D,
+                       float g_ce, float g_kl, float g_rep, float* losses /* [4] */, float* dpred_s, float* dstate_s,
+                       float* workspace, void* stream);
 
 /* ---- a8 + a9: regulariser, per-tensor clip, TF-Adam ---------------------------
  * slim.l2_regularizer (cs/video_level_models.py:428,434) folded into the
