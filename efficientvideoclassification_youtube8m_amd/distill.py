@@ -855,6 +855,249 @@ class DistillGraph:
         return rep
 
 
+class _TowerSlot:
+    """What frame_counts_and_plans / input_views read of a graph, for ONE tower of SerialStudentsGraph: the frozen teacher
+    (student None) or one student (teacher None) with its own every_n and frame selection."""
+
+    def __init__(self, graph, teacher=None, student=None, every_n=1, student_sampling="uniform"):
+        self.teacher, self.student, self.every_n, self.student_sampling = teacher, student, every_n, student_sampling
+        self.max_frames, self.C1, self.C2, self.row_plans = graph.max_frames, graph.C1, graph.C2, graph.row_plans
+        self.S = graph.max_frames // every_n
+        self.sampling_seed, self.sampling_draw, self.sampling_row0 = graph.sampling_seed, 0, 0
+        self.last_frame_table = None
+
+
+class SerialStudentView:
+    """Student k of a SerialStudentsGraph as train.save_checkpoint / restore_checkpoint see a DistillGraph(mode="serial"): the
+    shared frozen teacher, this student, its losses and frames, the common global_step."""
+
+    mode = "serial"
+
+    def __init__(self, graph, k, with_teacher=True):
+        self._graph, self.k = graph, k
+        self.teacher, self.student = graph.teacher if with_teacher else None, graph.students[k]
+        self.distill_losses, self.student_sampling, self.every_n = graph.distill_losses[k], graph.student_sampling[k], graph.every_n[k]
+
+    @property
+    def global_step(self):
+        return self._graph.global_step
+
+    @global_step.setter
+    def global_step(self, v):
+        self._graph.global_step = int(v)
+
+    def consolidate(self):
+        self._graph.consolidate()
+
+
+class SerialStudentsGraph:
+    """Serial distillation of K students (1 <= K <= 8) against ONE forward of a frozen teacher per iteration: what K
+    DistillGraph(mode="serial") runs on the same batches compute, with the teacher's forward, the batch's input pass for the teacher
+    and the teacher's share of the loss section done once.  Each student has its own every_n, frame selection and loss subset; all
+    share the batch, the seed of their initial weights (seed + 1: student k starts where the student of a serial DistillGraph with
+    the same seed starts), the hyper-parameters and global_step (+= 1 per iteration: every student sees the learning-rate schedule
+    of a run of its own).  One device, precision "bf16"."""
+
+    LOSS_SLOTS = DistillGraph.LOSS_SLOTS
+    MAX_STUDENTS = ops.DISTILL_MAX_STUDENTS
+
+    def __init__(self, batch_size, every_n=(10,), student_sampling=None, distill_losses=None, feature_size=1152, vocab_size=4716,
+                 max_frames=300, num_inputs_to_lstm=20, num_inputs_l1_student=5, lstm_cells=1024, lstm_layers=2, num_mixtures=2,
+                 base_learning_rate=0.001, learning_rate_decay=1.0, learning_rate_decay_examples=4000000,
+                 regularization_penalty=2.0, clip_gradient_norm=1.0, count_rep_twice=True, device="cuda:0", seed=7,
+                 process_group=None, overlap_towers=True, precision="bf16", sampling_seed=0):
+        every_n = [int(e) for e in every_n]
+        K = len(every_n)
+        if not 1 <= K <= self.MAX_STUDENTS:
+            raise ValueError("SerialStudentsGraph: %d students (1 .. %d)" % (K, self.MAX_STUDENTS))
+        student_sampling = ["uniform"] * K if student_sampling is None else list(student_sampling)
+        distill_losses = [DistillGraph.DISTILL_LOSSES] * K if distill_losses is None else list(distill_losses)
+        if len(student_sampling) != K or len(distill_losses) != K:
+            raise ValueError("SerialStudentsGraph: %d every_n values, %d student_sampling words, %d distill_losses subsets: one of each "
+                             "per student" % (K, len(student_sampling), len(distill_losses)))
+        world = 1
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            world = torch.distributed.get_world_size(process_group)
+        if world > 1:
+            raise ValueError("SerialStudentsGraph is not data parallel (process group of %d ranks): train the students against the "
+                             "frozen teacher on one device" % world)
+        if precision != "bf16":
+            raise ValueError("SerialStudentsGraph: precision %r (bf16 only: the input image of the other layouts is decided over the towers "
+                             "that share it)" % (precision,))
+        for e in every_n:
+            validate_every_n(e, num_inputs_l1_student, max_frames)
+        self.every_n = tuple(every_n)
+        self.student_sampling = tuple(ops.check_student_sampling(w) for w in student_sampling)
+        self.distill_losses = tuple(check_distill_losses(w) for w in distill_losses)
+        self.K, self.B, self.sampling_seed = K, batch_size, int(sampling_seed)
+        self.max_frames, self.C1, self.C2 = max_frames, num_inputs_to_lstm, num_inputs_l1_student
+        self.lr0, self.lr_decay, self.lr_decay_examples = base_learning_rate, learning_rate_decay, learning_rate_decay_examples
+        self.reg_pen, self.clip = regularization_penalty, clip_gradient_norm
+        self.rep_w = 2.0 if count_rep_twice else 1.0
+        self.device = torch.device(device)
+        self.precision, self.row_plans = precision, True
+        self.world, self.dp = 1, False
+        self.global_step = 0
+        self.teacher = HLstmTower(batch_size, max_frames, num_inputs_to_lstm, feature_size, vocab_size, lstm_cells, lstm_layers,
+                                  num_mixtures, device, False, "model", seed)
+        self.teacher.store.drop_training_state()
+        self.students = [HLstmTower(batch_size, max_frames // e, num_inputs_l1_student, feature_size, vocab_size, lstm_cells,
+                                    lstm_layers, num_mixtures, device, True, "model_student", seed + 1) for e in self.every_n]
+        self._t_slot = _TowerSlot(self, teacher=self.teacher)
+        self._s_slots = [_TowerSlot(self, student=s, every_n=e, student_sampling=w)
+                         for s, e, w in zip(self.students, self.every_n, self.student_sampling)]
+        self.losses = torch.zeros((K, 4), dtype=F32, device=self.device)
+        self._dp_s = self._ds_s = None
+        self._applied = [False] * K
+        self.overlap_towers = overlap_towers
+        self.defer_updates = os.environ.get("EVC_DEFER_UPDATES", "0") == "1"
+        self._opt_s = None
+        if self.device.type == "cuda":
+            self._main, self._side, _, self._aux_s = concurrent_streams(self.device, 4)
+            if os.environ.get("EVC_SINGLE_STREAM") == "1":
+                self._side = self._aux_s = self._main
+            m = os.environ.get("EVC_OPT_CU_MASK")        # the optimizer launches on a CU-masked stream of their own, as in DistillGraph
+            if m:
+                from .streams import cu_masked_stream
+                f = [int(v) for v in m.split(":")]
+                self._opt_s = cu_masked_stream(self.device, f[0], f[1] if len(f) > 1 else 0)
+            self._ev_fwd, self._ev_student, self._ev_in = torch.cuda.Event(), torch.cuda.Event(), torch.cuda.Event()
+
+    def student_view(self, k, with_teacher=True):
+        """with_teacher=False: the student alone (restoring student k > 0 must not load the shared teacher again)."""
+        return SerialStudentView(self, k, with_teacher)
+
+    @property
+    def last_frame_tables(self):
+        """Per student: the source-frame table of the last batch (None for a `uniform` student, which needs none)."""
+        return [s.last_frame_table for s in self._s_slots]
+
+    def step(self, x_raw, labels_u8, num_frames, apply=True, num_frames_host=None):
+        """One iteration of every student on this batch (DistillGraph.step's stream semantics and arguments)."""
+        if num_frames_host is None:
+            num_frames_host = num_frames.cpu()
+        nh = np.asarray(num_frames_host, dtype=np.int64).reshape(-1)
+        caller = torch.cuda.current_stream(self.device)
+        if caller == self._main:
+            return self._step(x_raw, labels_u8, num_frames, apply, nh)
+        self._main.wait_stream(caller)
+        with torch.cuda.stream(self._main):
+            out = self._step(x_raw, labels_u8, num_frames, apply, nh)
+        for t in (x_raw, labels_u8, num_frames):
+            t.record_stream(self._main)
+        caller.wait_stream(self._main)
+        return out
+
+    def _step(self, x_raw, labels_u8, num_frames, apply, nh):
+        """Schedule: the teacher's forward ONCE on `main`; the K students' forwards next to it on `side`, from the start of the step;
+        one ops.distill_losses_multi on `side` once all forwards are done; then each student's backward and update exactly as
+        DistillGraph._step_serial issues its one (aux stream, early apply, defer_updates); `main` joins at the end."""
+        B, V, K = x_raw.shape[0], labels_u8.shape[1], self.K
+        dev = self.device
+        if self._dp_s is None or self._dp_s[0].shape[0] != B:
+            self._dp_s = [torch.empty((B, V), dtype=F32, device=dev) for _ in range(K)]
+        main = torch.cuda.current_stream(dev)
+        tp, _ = frame_counts_and_plans(self._t_slot, num_frames, nh, True, False)
+        xt, _ = input_views(self._t_slot, x_raw, num_frames, tp, None, False)
+        sps, xss = [], []
+        for slot in self._s_slots:
+            slot.sampling_draw, slot.sampling_row0 = self.global_step, 0      # one train op per iteration: a new "random" draw per step
+            _, sp = frame_counts_and_plans(slot, num_frames, nh, False, True)
+            sps.append(sp)
+            xss.append(input_views(slot, x_raw, num_frames, None, sp, True)[1])
+        for s in self.students:
+            s.run_deferred()
+        self.losses.zero_()
+        lr = exponential_decay(self.lr0, self.global_step, B, self.lr_decay_examples, self.lr_decay)
+        l2c = self.reg_pen * 1e-8
+        self._applied = [False] * K
+        two_streams = self.overlap_towers
+        side = self._side if two_streams else main
+        l1, l2, plan_t = tp
+        if two_streams:
+            self._ev_in.record(main)
+            side.wait_event(self._ev_in)
+        t_state, t_pred = self.teacher.forward(xt, l1, l2, plan_t)
+        if two_streams:
+            self._ev_fwd.record(main)
+        outs = []
+        with torch.cuda.stream(side):
+            fwd = []
+            for s, xs, (n_s, l1s, l2s, plan_s) in zip(self.students, xss, sps):
+                fwd.append(s.forward(xs, l1s, l2s, plan_s))
+            if two_streams:
+                side.wait_event(self._ev_fwd)
+            if self._ds_s is None or self._ds_s[0].shape != fwd[0][0].shape:
+                self._ds_s = [torch.empty_like(f[0]) for f in fwd]
+            on = self.distill_losses
+            ops.distill_losses_multi(t_pred, self.teacher.rowsum, labels_u8, t_state, [f[1] for f in fwd],
+                                     [s.rowsum for s in self.students], [f[0] for f in fwd], self.losses, self._dp_s, self._ds_s,
+                                     g_ce=[(1.0 / B) if "ce" in o else 0.0 for o in on], g_kl=[1.0 if "pred" in o else 0.0 for o in on],
+                                     g_rep=[self.rep_w if "rep" in o else 0.0 for o in on])
+            early_s = (lr, self.clip, l2c) if (apply and self.overlap_towers and self._aux_s is not None) else None
+            for k, s in enumerate(self.students):
+                gen = s.backward_phases(self._ds_s[k], self._dp_s[k], aux=self._aux_s if self.overlap_towers else None,
+                                        early_apply=early_s, defer=self.defer_updates, opt=self._opt_s)
+                while next(gen, self) is not self:       # every phase to its end, as in DistillGraph._step_serial
+                    pass
+                self._applied[k] = early_s is not None
+            if two_streams:
+                self._ev_student.record(side)
+                for xs, (n_s, l1s, l2s, plan_s) in zip(xss, sps):
+                    used = (xs if isinstance(xs, tuple) else (xs,)) + (n_s, l1s, l2s)
+                    if plan_s is not None:
+                        used += (plan_s.pos, plan_s.inv, plan_s.lens)
+                    for t in used:                                          # allocated on `main`, consumed on `side`
+                        if t is not None:
+                            t.record_stream(side)
+        if two_streams:
+            main.wait_event(self._ev_student)
+        for k in range(K):
+            outs.append(dict(student_predictions=fwd[k][1], student_state=fwd[k][0], num_frames_student=sps[k][0],
+                             student_loss_state=self.losses[k, 1], pred_loss=self.losses[k, 2], student_label_loss=self.losses[k, 3]))
+        out = dict(predictions=t_pred, teacher_state=t_state, loss=self.losses[0, 0], students=outs)
+        if apply:
+            self._apply_gradients(B, lr)
+        out["global_step"] = self.global_step
+        return out
+
+    def flush(self):
+        """Enqueue and join the students' deferred updates of the last step (defer_updates); a cheap no-op when nothing is pending."""
+        if self.device.type != "cuda":
+            return
+        cur = torch.cuda.current_stream(self.device)
+        for s in self.students:
+            s.wait_deferred(cur)
+
+    def apply_gradients(self, batch_size, lr=None):
+        """Runs every student's train op that has not been applied inside step(); global_step += 1 for the iteration."""
+        self.flush()
+        self._apply_gradients(batch_size, lr)
+
+    def _apply_gradients(self, batch_size, lr=None):
+        l2c = self.reg_pen * 1e-8
+        if lr is None:
+            lr = exponential_decay(self.lr0, self.global_step, batch_size, self.lr_decay_examples, self.lr_decay)
+        for k, s in enumerate(self.students):
+            if not self._applied[k]:
+                s.apply_gradients(lr, self.clip, l2c)
+        self.global_step += 1
+        self._applied = [False] * self.K
+
+    def consolidate(self):
+        """One rank: nothing is sharded; the deferred updates are joined (as DistillGraph.consolidate does first)."""
+        self.flush()
+
+    @property
+    def losses_for_report(self):
+        return self.losses
+
+    def loss_report(self, losses=None):
+        """A list of K dicts keyed by LOSS_SLOTS (host floats).  losses: a copy of losses_for_report taken after an earlier step."""
+        v = (self.losses if losses is None else losses).reshape(self.K, 4).tolist()
+        return [{name: v[k][i] for i, name in enumerate(self.LOSS_SLOTS)} for k in range(self.K)]
+
+
 class EvalGraph:
     """Forward-only graph of cs/validate.py:109-189 (teacher built too, so that the
     student_state_loss ||teacher_state - student_state||^2 can be logged) and of

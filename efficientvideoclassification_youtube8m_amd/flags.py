@@ -28,6 +28,34 @@ def _distill_losses(v):
     return ",".join(check_distill_losses(str(v)))
 
 
+def _serial_sampling(v):
+    """A --serial_sampling list: one --student_sampling word per student, each checked while the flags are parsed; '' stays ''."""
+    v = str(v).strip()
+    return ",".join(_sampling(w) for w in v.split(",")) if v else ""
+
+
+def _serial_losses(v):
+    """A --serial_losses list: one '+'-joined --distill_losses subset per student, each canonicalised (distill.check_distill_losses)
+    while the flags are parsed; '' stays ''."""
+    from .distill import check_distill_losses
+    v = str(v).strip()
+    return ",".join("+".join(check_distill_losses([w.strip() for w in e.split("+")])) for e in v.split(",")) if v else ""
+
+
+def _serial_every_n(v):
+    """A --serial_every_n list: one positive integer per student; '' stays ''."""
+    v = str(v).strip()
+    if not v:
+        return ""
+    try:
+        vals = [int(e) for e in v.split(",")]
+    except ValueError:
+        vals = [0]
+    if min(vals) <= 0:
+        raise ValueError("--serial_every_n %r: a comma list of positive integers, one per student" % v)
+    return ",".join(str(e) for e in vals)
+
+
 def _bool(v):
     if isinstance(v, bool):
         return v
@@ -128,6 +156,17 @@ _define("teacher_dir", "", str, "HierarchicalLstmModel: directory of a finished 
         "--teacher_only, train_finetune or several ranks")
 _define("distill_losses", "rep,pred,ce", _distill_losses, "with --teacher_dir: which of L_REP, L_PRED, L_CE the student is trained on (comma "
         "list out of rep, pred, ce; the default is the reference's total, L_REP counted twice).  A loss left out is still computed and logged")
+# ---- serial distillation of several students against ONE forward of the frozen teacher per batch (train) ---------------------------------
+_define("serial_student_dirs", "", str, "with --teacher_dir: comma separated train directories, one per student (1 .. 8).  Set: all of them are "
+        "trained in one run against one forward of the frozen teacher per batch (distill.SerialStudentsGraph); every batch is read once and "
+        "each directory receives the checkpoints a --teacher_dir run of its own would write.  --train_dir is then not consulted.  On resume "
+        "every directory must hold a checkpoint of the same global_step (or none of them any).  HierarchicalLstmModel, --precision bf16, one "
+        "rank; not with --teacher_only or train_finetune")
+_define("serial_every_n", "", _serial_every_n, "one every_n per --serial_student_dirs entry; '' = --every_n for all")
+_define("serial_sampling", "", _serial_sampling, "one --student_sampling word per --serial_student_dirs entry; '' = --student_sampling for all "
+        "(--student_sampling_seed is shared)")
+_define("serial_losses", "", _serial_losses, "one --distill_losses subset per --serial_student_dirs entry, its words joined with '+' "
+        "(rep+pred+ce,rep,rep+pred); '' = --distill_losses for all")
 # ---- ensembles (inference / validate; cs/inference_ensemble.py:28-61 has preds_pattern, the others are additions) -----------------------
 _define("ensemble_dirs", "", str, "comma separated checkpoint directories of the ensemble's members (1 .. 8); '' = the single model of "
         "--train_dir, which is not consulted otherwise.  Every member runs its forward on the same batch and ops.ensemble_topk_rows "

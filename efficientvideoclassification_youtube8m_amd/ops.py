@@ -853,6 +853,45 @@ def distill_losses(pred_t, rowsum_t, pred_s, rowsum_s, labels_u8, state_t, state
               float(g_ce), float(g_kl), float(g_rep), _p(losses), _p(dpred_s), _p(dstate_s), _p(ws), _stream())
 
 
+DISTILL_MAX_STUDENTS = 8   # evc_distill_losses_multi: 1 <= K <= 8 students against one teacher
+
+
+def distill_losses_multi(pred_t, rowsum_t, labels_u8, state_t, preds_s, rowsums_s, states_s, losses, dpreds_s=None, dstates_s=None,
+                         g_ce=1.0, g_kl=1.0, g_rep=1.0):
+    """distill_losses for K students against one teacher in one launch + its finish (evc_distill_losses_multi): the teacher's
+    share of every element is computed once for all K (the prediction rows are read twice: double row sums first).  preds_s / rowsums_s / states_s: lists of K tensors; dpreds_s / dstates_s: None or lists
+    of K tensors-or-None; g_ce / g_kl / g_rep: one number for all students or a sequence of K; losses [K, 4] += each student's four values
+    (row k, DistillGraph.LOSS_SLOTS order; slot 0, the teacher's CE, is the same in every row).  Student k's outputs are the bits a
+    K = 1 call on it alone gives, wherever it stands in the lists."""
+    import ctypes as C
+    K = len(preds_s)
+    if not 1 <= K <= DISTILL_MAX_STUDENTS:
+        raise ValueError("distill_losses_multi: %d students (1 .. %d)" % (K, DISTILL_MAX_STUDENTS))
+    B, V = pred_t.shape
+    D = state_t.shape[1]
+    dpreds_s = [None] * K if dpreds_s is None else list(dpreds_s)
+    dstates_s = [None] * K if dstates_s is None else list(dstates_s)
+    assert len(rowsums_s) == len(states_s) == len(dpreds_s) == len(dstates_s) == K
+    assert labels_u8.shape == (B, V) and state_t.shape[0] == B and rowsum_t.numel() >= B and tuple(losses.shape) == (K, 4)
+    assert pred_t.dtype == F32 and state_t.dtype == F32 and labels_u8.dtype == torch.uint8 and losses.dtype == F32
+    for t in (pred_t, labels_u8, state_t, losses):
+        assert t.is_contiguous()
+    for k in range(K):
+        assert preds_s[k].shape == (B, V) and states_s[k].shape == (B, D) and rowsums_s[k].numel() >= B
+        assert preds_s[k].dtype == F32 and states_s[k].dtype == F32 and preds_s[k].is_contiguous() and states_s[k].is_contiguous()
+        for t, shp in ((dpreds_s[k], (B, V)), (dstates_s[k], (B, D))):
+            assert t is None or (t.dtype == F32 and t.shape == shp and t.is_contiguous())
+    scales = []
+    for g in (g_ce, g_kl, g_rep):
+        g = [float(g)] * K if isinstance(g, (int, float)) else [float(x) for x in g]
+        assert len(g) == K
+        scales.append((C.c_float * K)(*g))
+    arr = lambda ts: (C.c_void_p * K)(*[_p(t) for t in ts])
+    ws = torch.empty((1 + 2 * K) * B + 256 * K, dtype=F32, device=pred_t.device)
+    _lib.call("evc_distill_losses_multi", _p(pred_t), _p(rowsum_t), _p(labels_u8), _p(state_t), K, arr(preds_s), arr(rowsums_s),
+              arr(states_s), scales[0], scales[1], scales[2], arr(dpreds_s), arr(dstates_s), B, V, D, _p(losses), _p(ws), _stream())
+
+
 def clip_adam_small(ps, gs, ms, vs, sums, clip_norm, lr_t, beta1=0.9, beta2=0.999, eps=1e-8):
     """Per-tensor clip + TF-Adam of up to 16 small tensors (no l2 term) in one launch (evc_clip_adam_small): sums[i] receives {|g_i|^2, 0}."""
     import ctypes as C

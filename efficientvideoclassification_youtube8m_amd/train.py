@@ -17,6 +17,8 @@ TFRecord input -> readers.py (native parser, uint8 feed, pinned staging); the pa
 "synthetic" generates random uint8 videos on the device instead.
 Serial distillation (not a reference mode; the paper's second way to train a student): ``--teacher_dir DIR`` trains the
 student against the frozen teacher of DIR's latest checkpoint (distill.DistillGraph mode "serial").
+``--serial_student_dirs A/,B/,...`` next to it trains up to 8 students in ONE run against one forward of that teacher per batch
+(distill.SerialStudentsGraph): one checkpoint directory per student, each what a run of its own would have written.
 Multi-GPU: launch with ``python -m torch.distributed.run --nproc-per-node N``;
 ``--gpu`` is then ignored in favour of LOCAL_RANK.
 """
@@ -32,7 +34,7 @@ import numpy as np
 import torch
 
 from . import eval_util, frame_level_models, losses, ops, readers, video_level_models
-from .distill import DistillGraph, SingleTowerGraph
+from .distill import DistillGraph, SerialStudentsGraph, SingleTowerGraph
 from .flags import FLAGS, GetListOfFeatureNamesAndSizes
 from .towers import DbofTower, LogisticTower, NetVladTower
 
@@ -57,10 +59,15 @@ def _apply_precision(tw):
 DEFAULT_DISTILL_LOSSES = "rep,pred,ce"
 
 
-def check_serial_flags(finetune=False, world=1):
+_UNSET = object()
+
+
+def check_serial_flags(finetune=False, world=1, students=_UNSET):
     """--teacher_dir / --distill_losses against the flags and the launch they exclude (all ValueError, before anything touches the device).
     Returns True when the flags ask for serial distillation."""
     serial = bool(FLAGS.teacher_dir)
+    if students is _UNSET:
+        serial_students(finetune, world)    # --serial_student_dirs and its lists: every refusal of theirs, before the rest
     if not serial:
         if FLAGS.distill_losses != DEFAULT_DISTILL_LOSSES:
             raise ValueError("--distill_losses %s needs --teacher_dir: it selects the student's losses of serial distillation "
@@ -77,6 +84,83 @@ def check_serial_flags(finetune=False, world=1):
     return True
 
 
+def serial_students(finetune=False, world=1):
+    """--serial_student_dirs / --serial_every_n / --serial_sampling / --serial_losses: None when no directories are given, else
+    {"dirs", "every_n", "sampling", "losses"} with one entry per student ('' lists filled from --every_n / --student_sampling /
+    --distill_losses).  Every refused combination is a ValueError here, before anything touches the device."""
+    from .distill import check_distill_losses, validate_every_n
+    dirs = [d.strip() for d in FLAGS.serial_student_dirs.split(",") if d.strip()]
+    lists = {"serial_every_n": FLAGS.serial_every_n, "serial_sampling": FLAGS.serial_sampling, "serial_losses": FLAGS.serial_losses}
+    if not dirs:
+        stray = [k for k, v in lists.items() if v]
+        if stray or FLAGS.serial_student_dirs.strip():
+            raise ValueError("--%s needs --serial_student_dirs (one train directory per student)" % (stray[0] if stray else "serial_student_dirs"))
+        return None
+    K = len(dirs)
+    what = "--serial_student_dirs %s" % FLAGS.serial_student_dirs
+    if K > SerialStudentsGraph.MAX_STUDENTS:
+        raise ValueError("%s: %d directories, at most %d students share a teacher's forward" % (what, K, SerialStudentsGraph.MAX_STUDENTS))
+    norm = [os.path.normpath(os.path.abspath(d)) for d in dirs]
+    twice = sorted({d for d, n in zip(dirs, norm) if norm.count(n) > 1})
+    if twice:
+        raise ValueError("%s: a directory is named more than once (%s): every student writes its own" % (what, ", ".join(twice)))
+    if not FLAGS.teacher_dir:
+        raise ValueError("%s needs --teacher_dir: the students are trained against its frozen teacher" % what)
+    if getattr(FLAGS, "teacher_only", False):
+        raise ValueError("%s with --teacher_only: a frozen teacher cannot be the tower that is trained" % what)
+    if finetune:
+        raise ValueError("%s with --finetune: train_finetune trains one student on L_CE alone, without a teacher" % what)
+    if world > 1:
+        raise ValueError("%s on %d ranks: serial distillation is not data parallel yet, run it on one device" % (what, world))
+    if FLAGS.model != "HierarchicalLstmModel":
+        raise ValueError("%s: serial distillation is built for HierarchicalLstmModel, not %s" % (what, FLAGS.model))
+    if FLAGS.precision != "bf16":
+        raise ValueError("%s with --precision %s: several students share a teacher's forward in bf16 only" % (what, FLAGS.precision))
+    out = {"dirs": dirs}
+    for key, flag, default in (("every_n", "serial_every_n", str(FLAGS.every_n)), ("sampling", "serial_sampling", FLAGS.student_sampling),
+                               ("losses", "serial_losses", FLAGS.distill_losses.replace(",", "+"))):
+        vals = [v.strip() for v in lists[flag].split(",")] if lists[flag] else [default] * K
+        if len(vals) != K:
+            raise ValueError("--%s %s: %d entries for the %d directories of %s" % (flag, lists[flag], len(vals), K, what))
+        out[key] = vals
+    out["every_n"] = [int(e) for e in out["every_n"]]
+    for e in out["every_n"]:
+        validate_every_n(e, 5, FLAGS.max_num_frames)
+    out["losses"] = [check_distill_losses(e.split("+")) for e in out["losses"]]
+    return out
+
+
+def serial_students_checkpoints(dirs, start_new_model=False):
+    """The checkpoints a --serial_student_dirs run resumes from: one path per directory when every directory holds one and all are
+    at the same global_step, None for a fresh start (--start_new_model, or no directory holds one).  Anything else is a ValueError
+    that names the directories and their steps.  Reads file names only."""
+    if start_new_model:
+        return None
+    cks = [latest_checkpoint(d) for d in dirs]
+    if all(c is None for c in cks):
+        return None
+    steps = [None if c is None else _ckpt_step(c) for c in cks]
+    if any(c is None for c in cks) or len(set(steps)) != 1:
+        raise ValueError("--serial_student_dirs: the students resume together or not at all, but the directories stand at %s (every "
+                         "directory needs a checkpoint of the same global_step, or none of them any)" %
+                         ", ".join("%s: %s" % (d, "no checkpoint" if st is None else "step %d" % st) for d, st in zip(dirs, steps)))
+    return cks
+
+
+def restore_serial_students(graph, cks):
+    """Resume of a --serial_student_dirs run: student k from cks[k], the frozen teacher from cks[0].  The other checkpoints must carry
+    the same model/* tensors - they were written next to each other by one run - or the directories do not belong together."""
+    restore_checkpoint(graph.student_view(0), cks[0])
+    teacher = {k: v.cpu() for k, v in graph.teacher.state_dict().items()}
+    for k in range(1, len(cks)):
+        sd = torch.load(cks[k], map_location="cpu")
+        other = [n for n, v in teacher.items() if n not in sd or not torch.equal(sd[n], v)]
+        if other:
+            raise ValueError("--serial_student_dirs: %s holds another teacher than %s (%s differs): the students of one run share "
+                             "their frozen teacher" % (cks[k], cks[0], other[0]))
+        restore_checkpoint(graph.student_view(k, with_teacher=False), cks[k])
+
+
 def load_frozen_teacher(graph, teacher_dir):
     """The model/* variables of latest_checkpoint(teacher_dir) into the serial graph's frozen teacher.  Returns the checkpoint's path."""
     ck = latest_checkpoint(teacher_dir)
@@ -89,7 +173,7 @@ def load_frozen_teacher(graph, teacher_dir):
     return ck
 
 
-def build_graph(model, label_loss_fn, feature_size, batch_size, every_n, device, finetune=False, process_group=None):
+def build_graph(model, label_loss_fn, feature_size, batch_size, every_n, device, finetune=False, process_group=None, students=_UNSET):
     """Equivalent of cs/train.py:185-427 (and cs/train_finetune.py:185-331 when
     finetune): returns the graph object whose ``step`` runs one iteration."""
     if not isinstance(label_loss_fn, losses.CrossEntropyLoss):
@@ -102,6 +186,14 @@ def build_graph(model, label_loss_fn, feature_size, batch_size, every_n, device,
         # every_n == 1 (the reference's default, cs/train.py:100-101) still builds and trains model_student, on all 300
         # frames in 5 chunks of 60 (cs/train.py:262-272,349-356): global_step += 2 and the checkpoint holds both scopes.
         # Teacher-only training (BASELINE cfg 2) is not a reference mode: it is asked for with --teacher_only.
+        spec = serial_students(finetune) if students is _UNSET else students
+        if spec is not None:
+            # K students against one forward of the frozen teacher (--serial_student_dirs): hyper-parameters as below, one of each list per student
+            return SerialStudentsGraph(batch_size, every_n=spec["every_n"], student_sampling=spec["sampling"], distill_losses=spec["losses"],
+                                       feature_size=feature_size, vocab_size=NUM_CLASSES, max_frames=FLAGS.max_num_frames,
+                                       num_inputs_to_lstm=FLAGS.num_inputs_to_lstm, lstm_cells=FLAGS.lstm_cells, lstm_layers=FLAGS.lstm_layers,
+                                       num_mixtures=FLAGS.moe_num_mixtures, device=device, precision=FLAGS.precision,
+                                       sampling_seed=FLAGS.student_sampling_seed, **common)
         mode = "student" if finetune else ("teacher" if getattr(FLAGS, "teacher_only", False) else "teacher_student")
         if FLAGS.teacher_dir and check_serial_flags(finetune):
             # Serial distillation (--teacher_dir): the student against a frozen teacher - not a reference mode either
@@ -270,7 +362,9 @@ def main(argv=None):
     logging.basicConfig(level=logging.INFO, format="INFO:evc:%(message)s")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
-    serial = check_serial_flags(finetune, world)
+    multi = serial_students(finetune, world)
+    serial = check_serial_flags(finetune, world, students=multi)
+    multi_cks = serial_students_checkpoints(multi["dirs"], FLAGS.start_new_model) if multi else None
     local = int(os.environ.get("LOCAL_RANK", str(FLAGS.gpu)))
     # test hook (tests/test_gpu_dp.py): several ranks on ONE GPU over gloo, to run this file's multi-rank path on a
     # single-GPU box (RCCL refuses two ranks per device).  Never set in a real run.
@@ -294,10 +388,18 @@ def main(argv=None):
     label_loss_fn = find_class_by_name(FLAGS.label_loss, [losses])()
     if FLAGS.optimizer != "AdamOptimizer":
         raise NotImplementedError("only AdamOptimizer (the reference default, cs/train.py:91) is built")
-    graph = build_graph(model, label_loss_fn, feature_size, FLAGS.batch_size, FLAGS.every_n, device, finetune)
+    graph = build_graph(model, label_loss_fn, feature_size, FLAGS.batch_size, FLAGS.every_n, device, finetune, students=multi)
     logging.info("%s: Built graph.", task)
-    ck = None if FLAGS.start_new_model else latest_checkpoint(FLAGS.train_dir)
-    if FLAGS.start_new_model:
+    ck = None if (FLAGS.start_new_model or multi) else latest_checkpoint(FLAGS.train_dir)
+    if multi and multi_cks:
+        for k, c in enumerate(multi_cks):
+            logging.info("%s: Restoring student %d from %s", task, k, c)
+        restore_serial_students(graph, multi_cks)
+        logging.info("%s: --teacher_dir %s only selects serial distillation on resume: the frozen teacher comes from %s", task,
+                     FLAGS.teacher_dir, multi_cks[0])
+    elif multi:
+        logging.info("%s: Building %d new students. Frozen teacher from %s", task, len(multi["dirs"]), load_frozen_teacher(graph, FLAGS.teacher_dir))
+    elif FLAGS.start_new_model:
         logging.info("%s: Flag 'start_new_model' is set. Building a new model.", task)
     elif ck is None:
         logging.info("%s: No checkpoint file found. Building a new model.", task)
@@ -317,8 +419,9 @@ def main(argv=None):
                         "(give every rank at least batch_size records)", task, FLAGS.batch_size)
     logging.info("%s: Entering training loop.", task)
     start, last_save, it = time.time(), time.time(), 0
-    is_distill = isinstance(graph, DistillGraph)
-    steps_per_it = 2 if is_distill and graph.mode == "teacher_student" else 1
+    is_multi = isinstance(graph, SerialStudentsGraph)
+    is_distill = isinstance(graph, DistillGraph) or is_multi
+    steps_per_it = 2 if is_distill and not is_multi and graph.mode == "teacher_student" else 1
     copy_stream = torch.cuda.Stream(device=device)
     host_bufs = {}                       # pinned staging, two alternating sets (one may still be read while the next fills)
 
@@ -353,26 +456,41 @@ def main(argv=None):
             return
         snap["event"].synchronize()              # nothing here touches a stream that step it_now+1 has been queued on
         r = graph.loss_report(losses=snap["slot"]["loss"]) if is_distill else None
-        if is_distill and not all(np.isfinite(v) for v in r.values()):          # slim.learning.create_train_op's check_numerics;
+        if is_distill and not all(np.isfinite(v) for rk in (r if is_multi else [r]) for v in rk.values()):   # slim.learning.create_train_op's check_numerics;
             raise FloatingPointError("LossTensor is inf or nan : %s" % r)      # same (reduced) values on every rank: all stop
         if rank != 0:
             return
         p, y = snap["slot"]["pred"].numpy(), snap["slot"]["lab"].numpy().astype(np.float32)
         hit, perr, gap = (eval_util.calculate_hit_at_one(p, y), eval_util.calculate_precision_at_equal_recall_rate(p, y),
                           eval_util.calculate_gap(p, y))
-        history.append((snap["global_step"], dict(r) if is_distill else {"loss": float(snap["slot"]["loss"][0])},
-                        {"hit_at_one": float(hit), "perr": float(perr), "gap": float(gap)}))
-        if is_distill:
+        if is_multi:
+            # one line per student in the reference's format, prefixed with its directory (Hit@1 / PERR / GAP: the shared teacher's predictions)
+            history.append((snap["global_step"], [dict(rk) for rk in r]))
+            for d, rk in zip(multi["dirs"], r):
+                logging.info("%s %s: training step %d| Hit@1: %.2f| PERR: %.2f| GAP: %.2f| Teacher_Loss: %s| L_REP: %s| L_PRED: %s"
+                             "| L_CE: %s", d, task, snap["global_step"], hit, perr, gap, round(rk["label_loss"], 2),
+                             round(rk["student_loss_state"], 2), round(rk["pred_loss"], 2), round(rk["student_label_loss"], 2))
+        elif is_distill:
+            history.append((snap["global_step"], dict(r), {"hit_at_one": float(hit), "perr": float(perr), "gap": float(gap)}))
             logging.info("%s: training step %d| Hit@1: %.2f| PERR: %.2f| GAP: %.2f| Teacher_Loss: %s| L_REP: %s| L_PRED: %s"
                          "| L_CE: %s", task, snap["global_step"], hit, perr, gap, round(r["label_loss"], 2),
                          round(r["student_loss_state"], 2), round(r["pred_loss"], 2), round(r["student_label_loss"], 2))
         else:
+            history.append((snap["global_step"], {"loss": float(snap["slot"]["loss"][0])},
+                            {"hit_at_one": float(hit), "perr": float(perr), "gap": float(gap)}))
             logging.info("%s: training step %d| Hit@1: %.2f| PERR: %.2f| GAP: %.2f| Loss: %s", task, snap["global_step"],
                          hit, perr, gap, round(float(snap["slot"]["loss"][0]), 2))
         now = time.time()
         dt = max(now - last_log_time[0], 1e-9) / max(1, it_now - last_log_time[1])
         last_log_time[0], last_log_time[1] = now, it_now
         logging.info("global_step/sec: %g  Examples/Second: %g", steps_per_it / dt, snap["batch"] * world / dt)
+
+    def save_checkpoints():
+        """Wherever a single run saves: --train_dir, or one checkpoint per student into its own directory (--serial_student_dirs)."""
+        if not is_multi:
+            return save_checkpoint(graph, FLAGS.train_dir, rank)
+        for k, d in enumerate(multi["dirs"]):
+            save_checkpoint(graph.student_view(k), d, rank)
 
     history = []                         # (global_step, loss dict) of every logged step, returned to the caller
     pending = None
@@ -394,14 +512,14 @@ def main(argv=None):
                 torch.distributed.broadcast(flag, src=0)
                 save_due = bool(flag.item())
         if save_due:
-            save_checkpoint(graph, FLAGS.train_dir, rank)
+            save_checkpoints()
             last_save = time.time()
         if step_limit is not None and it >= step_limit:
             break
     if pending is not None:
         finish_log(pending, it)
     logging.info("%s: Done training -- epoch limit reached.", task)
-    save_checkpoint(graph, FLAGS.train_dir, rank)
+    save_checkpoints()
     logging.info("%s: Exited training loop.", task)
     print("Total time taken is " + str(time.time() - start))
     if world > 1:

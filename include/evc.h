@@ -36,7 +36,7 @@ extern "C" {
 #define EVC_ERR_HIP (-4)
 #define EVC_ERR_BAD_ARG (-5)
 
-#define EVC_VERSION 107   /* 107 (round 6, late): evc_lstm_level2_fwd_high (the two-layer L1 level of the "high" mode in T + 1 two-tile launches); evc_topk_rows (per-row top-k of the inference binary's prediction file; an addition, no existing entry changed), later evc_eval_select_rows and evc_ensemble_topk_rows (the combination of several members' predictions in front of that selection) and evc_student_frame_select / evc_l2norm_chunk_sel_fwd / evc_l2norm_chunk_sel_int (student frame selection) and evc_distill_losses (the loss section of the serial distillation step) the same way; 106 (round 6): evc_gemm_nt_sqnorm, evc_l2norm_chunk_int + the x_row_scale / x_col_const / b8_gap arguments of evc_lstm_layer_fwd_f16_fp8lo (integer-frame layer 0: the uint8 input exact), evc_lstm_layer_fwd_f16_fp8lo / evc_lstm_stack2_fwd_f16_fp8lo gained h_lo (low-order half of h corrected: 4H-byte h rows), evc_cast_f32_to_fp8_lohi, evc_lstm_adam_fused gained fp8_hi_tail; evc_absmax_partials, evc_cast_f32_to_f16_fp8x_dyn, evc_gemm_nt_f16_fp8_dyn (dynamic e4m3 range of the MoE head's input state); evc_l2norm_chunk_fwd accepts out1 == NULL (student-only graphs read the sub-sampled frames only), evc_clip_adam_small limited to 2^15 elements per tensor; 105 (round 5, second session): evc_cast_f32_to_f16_dither, evc_lstm_layer_fwd_f16_dith (time-dithered f16 weight images: an L1 layer of the "high" mode without stages for its weights' low-order halves), evc_gemm_tn2_rows (weight-gradient products that skip the dead rows of a row-planned level's time slabs); 104 (round 5): evc_lstm_level2_fwd, evc_ce_loss_ordered, evc_rep_loss_ordered, evc_gemm_tn2_slabs, evc_sum_slabs, evc_clip_adam_small; evc_moe_grad_update* accept p_bf16 == NULL (forward shadow not written), evc_lstm_stack2_bwd runs M <= 512 stacks on the skinny pair launches, evc_dbof_cluster_pool_fwd walks tiles (EVC_DBOF_WALK), EVC_DETERMINISTIC parsed as "set, not empty, not 0"; 103 (round 4): evc_sqnorm2_partials, evc_lstm_adam_fused, evc_gram_slabs, evc_moe_grad_norms, evc_moe_grad_update_apply, evc_adam2d_fused, evc_colsum_bf16_det, evc_sample_sequence_gather, evc_relu6_fwd/bwd, evc_framepool_mean_fwd/bwd, evc_stream_create_cu_mask / evc_stream_destroy; EVC_DETERMINISTIC=1 read by the library; 102: evc_lstm_layer_fwd_f16_fp8lo, evc_lstm_stack2_fwd_f16_fp8lo, evc_gemm_nt_f16_fp8, evc_cast_f32_to_fp8_lo, evc_cast_f32_to_f16_fp8x, aux_mode 5, evc_moe_grad_update_wide; 101 (round 3): evc_l2norm_chunk_fwd gained aux_mode; evc_lstm_layer_fwd_hp takes wide split operands; f16 / wide-split entries added */
+#define EVC_VERSION 107   /* 107 (round 6, late): evc_lstm_level2_fwd_high (the two-layer L1 level of the "high" mode in T + 1 two-tile launches); evc_topk_rows (per-row top-k of the inference binary's prediction file; an addition, no existing entry changed), later evc_eval_select_rows and evc_ensemble_topk_rows (the combination of several members' predictions in front of that selection) and evc_student_frame_select / evc_l2norm_chunk_sel_fwd / evc_l2norm_chunk_sel_int (student frame selection) and evc_distill_losses (the loss section of the serial distillation step) and evc_distill_losses_multi (that section for K students against one teacher) the same way; 106 (round 6): evc_gemm_nt_sqnorm, evc_l2norm_chunk_int + the x_row_scale / x_col_const / b8_gap arguments of evc_lstm_layer_fwd_f16_fp8lo (integer-frame layer 0: the uint8 input exact), evc_lstm_layer_fwd_f16_fp8lo / evc_lstm_stack2_fwd_f16_fp8lo gained h_lo (low-order half of h corrected: 4H-byte h rows), evc_cast_f32_to_fp8_lohi, evc_lstm_adam_fused gained fp8_hi_tail; evc_absmax_partials, evc_cast_f32_to_f16_fp8x_dyn, evc_gemm_nt_f16_fp8_dyn (dynamic e4m3 range of the MoE head's input state); evc_l2norm_chunk_fwd accepts out1 == NULL (student-only graphs read the sub-sampled frames only), evc_clip_adam_small limited to 2^15 elements per tensor; 105 (round 5, second session): evc_cast_f32_to_f16_dither, evc_lstm_layer_fwd_f16_dith (time-dithered f16 weight images: an L1 layer of the "high" mode without stages for its weights' low-order halves), evc_gemm_tn2_rows (weight-gradient products that skip the dead rows of a row-planned level's time slabs); 104 (round 5): evc_lstm_level2_fwd, evc_ce_loss_ordered, evc_rep_loss_ordered, evc_gemm_tn2_slabs, evc_sum_slabs, evc_clip_adam_small; evc_moe_grad_update* accept p_bf16 == NULL (forward shadow not written), evc_lstm_stack2_bwd runs M <= 512 stacks on the skinny pair launches, evc_dbof_cluster_pool_fwd walks tiles (EVC_DBOF_WALK), EVC_DETERMINISTIC parsed as "set, not empty, not 0"; 103 (round 4): evc_sqnorm2_partials, evc_lstm_adam_fused, evc_gram_slabs, evc_moe_grad_norms, evc_moe_grad_update_apply, evc_adam2d_fused, evc_colsum_bf16_det, evc_sample_sequence_gather, evc_relu6_fwd/bwd, evc_framepool_mean_fwd/bwd, evc_stream_create_cu_mask / evc_stream_destroy; EVC_DETERMINISTIC=1 read by the library; 102: evc_lstm_layer_fwd_f16_fp8lo, evc_lstm_stack2_fwd_f16_fp8lo, evc_gemm_nt_f16_fp8, evc_cast_f32_to_fp8_lo, evc_cast_f32_to_f16_fp8x, aux_mode 5, evc_moe_grad_update_wide; 101 (round 3): evc_l2norm_chunk_fwd gained aux_mode; evc_lstm_layer_fwd_hp takes wide split operands; f16 / wide-split entries added */
 
 typedef uint16_t evc_bf16;
 typedef uint16_t evc_f16;   /* raw IEEE binary16 bits (the "high" precision forward operands of the L1 levels) */
@@ -509,6 +509,23 @@ int evc_distill_losses(const float* pred_t, const float* rowsum_t, const float* 
                        const uint8_t* labels, const float* state_t, const float* state_s, int B, int V, int D,
                        float g_ce, float g_kl, float g_rep, float* losses /* [4] */, float* dpred_s, float* dstate_s,
                        float* workspace, void* stream);
+/* The same loss section for K students (1 <= K <= 8) against ONE teacher, in one launch + one finish launch (SerialStudentsGraph):
+ * labels, state_t and every student's state_s are read once; pred_t and every pred_s row are read twice by the workgroup that owns the row (a
+ * first pass for the row sums in double, the second from cache), the teacher's share of every element is computed once for all K.  pred_s, rowsum_s, state_s, dpred_s, dstate_s:
+ * HOST arrays of K device pointers, g_ce, g_kl, g_rep: HOST arrays of K scales (all copied into the launch's arguments); dpred_s / dstate_s
+ * may be NULL as a whole or per student.  losses [K][4] += student k's four values in evc_distill_losses' order; slot 0 (the teacher's CE)
+ * receives the same bits in every row.  Definitions, scales and degenerate-row rules are evc_distill_losses', per student.
+ * 16-byte accesses where V % 4 == 0 / (B * D) % 4 == 0 and the teacher's pointers are 16-byte aligned (labels: 4-byte), for every student
+ * whose own pointers are; a student whose pointers are not takes 4-byte accesses alone.
+ * The two row sums of the KL gradient -P / p_s + 1 / sum(p_s) are taken in double inside the kernel (a first pass over the row) and that
+ * difference is evaluated in double, so that dpred_s holds 1e-5 (|ce term| + |kl term|) at few classes under a large batch as well; rowsum_t /
+ * rowsum_s decide the degenerate-row rules only (rowsum_t below FLT_MIN: loss 0, KL gradient 0; rowsum_s below FLT_MIN: clamped to FLT_MIN).
+ * workspace: (1 + 2 K) * B + 256 * K floats of scratch; the finish launch adds every list of partials in workgroup order (no atomics).
+ * A student's outputs do not depend on K, on its position in the lists or on the other students: the same bits as a K = 1 call. */
+int evc_distill_losses_multi(const float* pred_t, const float* rowsum_t, const uint8_t* labels, const float* state_t, int K,
+                             const float* const* pred_s, const float* const* rowsum_s, const float* const* state_s,
+                             const float* g_ce, const float* g_kl, const float* g_rep, float* const* dpred_s, float* const* dstate_s,
+                             int B, int V, int D, float* losses /* [K][4] */, float* workspace, void* stream);
 
 /* ---- a8 + a9: regulariser, per-tensor clip, TF-Adam ---------------------------
  * slim.l2_regularizer (cs/video_level_models.py:428,434) folded into the
