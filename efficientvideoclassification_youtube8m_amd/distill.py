@@ -29,6 +29,7 @@ import os
 import numpy as np
 import torch
 
+from . import losses as losses_mod
 from . import ops
 from .streams import concurrent_streams
 from .engine import HLstmTower
@@ -298,6 +299,14 @@ class GradReducer:
         self._pending = []
 
 
+def _resolve_label_loss(label_loss, vocab_size):
+    """label_loss of a graph (None | class name | losses.BaseLoss) -> the instance, after its host-side refusals for vocab_size classes."""
+    fn = losses_mod.resolve(label_loss)
+    if vocab_size is not None:
+        fn.check(vocab_size)
+    return fn
+
+
 def check_distill_losses(words):
     """--distill_losses / DistillGraph(distill_losses=...): a non-empty subset of ("rep", "pred", "ce"), as a comma list or a
     sequence; returned as a tuple in that canonical order.  Unknown, empty and repeated words are refused."""
@@ -423,8 +432,13 @@ class DistillGraph:
                  num_mixtures=2, base_learning_rate=0.001, learning_rate_decay=1.0,
                  learning_rate_decay_examples=4000000, regularization_penalty=2.0, clip_gradient_norm=1.0,
                  count_rep_twice=True, device="cuda:0", seed=7, process_group=None, overlap_towers=True,
-                 precision="bf16", student_sampling="uniform", sampling_seed=0, distill_losses=DISTILL_LOSSES):
+                 precision="bf16", student_sampling="uniform", sampling_seed=0, distill_losses=DISTILL_LOSSES, label_loss=None):
         assert mode in self.MODES
+        # the label loss L_CE of both towers (losses.BaseLoss instance, class name, None = CrossEntropyLoss: --label_loss)
+        self.label_loss = _resolve_label_loss(label_loss, vocab_size)
+        if mode == "serial" and not losses_mod.is_default(self.label_loss):
+            raise ValueError("DistillGraph(mode='serial') has CrossEntropyLoss built into its loss section (evc_distill_losses), not %s"
+                             % type(self.label_loss).__name__)
         self.distill_losses = check_distill_losses(distill_losses)
         if self.distill_losses != self.DISTILL_LOSSES and mode != "serial":
             raise ValueError("distill_losses selects the student's loss terms of mode 'serial' only (mode %r trains on all of its losses)" % mode)
@@ -528,6 +542,20 @@ class DistillGraph:
         else:
             self.reducer.reduce(st.grad, 0, moe_lo, f32=False)
 
+    def _label_loss(self, pred, labels_u8, loss, dpred=None, grad_scale=1.0):
+        """The label loss of one tower: CrossEntropyLoss issues ops.ce_loss, any other loss ops.label_loss with the same arguments."""
+        self.label_loss.fused(pred, labels_u8, loss, dpred, grad_scale=grad_scale)
+
+    def label_grads(self):
+        """The dL/dpred buffers the last step filled ({"teacher": ..., "student": ...}, whichever exist; the student's holds its label
+        loss's and L_PRED's gradient).  For tests and debugging."""
+        out = {}
+        if self.teacher is not None and self.train_teacher and self._dp_t is not None:
+            out["teacher"] = self._dp_t
+        if self.student is not None and self._dp_s is not None:
+            out["student"] = self._dp_s
+        return out
+
     # ---- one training iteration -----------------------------------------------
     def step(self, x_raw, labels_u8, num_frames, apply=True, num_frames_host=None):
         """Runs ``_step`` on the graph's own main stream, ordered after the caller's current stream on entry
@@ -617,7 +645,7 @@ class DistillGraph:
                 mark("student_start", side)
                 n_s, l1s, l2s, plan_s = sp
                 s_state, s_pred = self.student.forward(xs, l1s, l2s, plan_s)
-                ops.ce_loss(s_pred, labels_u8, self.losses[3:4], self._dp_s, grad_scale=sc["ce"] / B)
+                self._label_loss(s_pred, labels_u8, self.losses[3:4], self._dp_s, grad_scale=sc["ce"] / B)
                 mark("student_fwd_done", side)
         def student_forward_mid():
             nonlocal s_state, s_pred, n_s, l1s, l2s, plan_s
@@ -627,13 +655,13 @@ class DistillGraph:
                 mark("student_start", side)
                 n_s, l1s, l2s, plan_s = sp
                 s_state, s_pred = self.student.forward(xs, l1s, l2s, plan_s)
-                ops.ce_loss(s_pred, labels_u8, self.losses[3:4], self._dp_s, grad_scale=sc["ce"] / B)
+                self._label_loss(s_pred, labels_u8, self.losses[3:4], self._dp_s, grad_scale=sc["ce"] / B)
                 mark("student_fwd_done", side)
 
         if self.teacher is not None:
             l1, l2, plan_t = tp
             t_state, t_pred = self.teacher.forward(xt, l1, l2, plan_t, after_l1=student_forward_mid if mid_student else None)
-            ops.ce_loss(t_pred, labels_u8, self.losses[0:1], self._dp_t, grad_scale=sc["ce"] / B)
+            self._label_loss(t_pred, labels_u8, self.losses[0:1], self._dp_t, grad_scale=sc["ce"] / B)
             if two_streams:
                 self._ev_fwd.record(main)
             mark("teacher_fwd_done", main)
@@ -645,7 +673,7 @@ class DistillGraph:
                     mark("student_start", side)
                     n_s, l1s, l2s, plan_s = sp
                     s_state, s_pred = self.student.forward(xs, l1s, l2s, plan_s)
-                    ops.ce_loss(s_pred, labels_u8, self.losses[3:4], self._dp_s, grad_scale=sc["ce"] / B)
+                    self._label_loss(s_pred, labels_u8, self.losses[3:4], self._dp_s, grad_scale=sc["ce"] / B)
                     mark("student_fwd_done", side)
                 ds = None
                 if self.teacher is not None:
@@ -1109,7 +1137,8 @@ class EvalGraph:
 
     def __init__(self, batch_size, every_n=10, student_only=False, feature_size=1152, vocab_size=4716, max_frames=300,
                  num_inputs_to_lstm=20, num_inputs_l1_student=5, lstm_cells=1024, lstm_layers=2, num_mixtures=2,
-                 device="cuda:0", precision="bf16", teacher_only=False, student_sampling="uniform", sampling_seed=0):
+                 device="cuda:0", precision="bf16", teacher_only=False, student_sampling="uniform", sampling_seed=0, label_loss=None):
+        self.label_loss = _resolve_label_loss(label_loss, vocab_size)       # the loss reported as out["loss"] (--label_loss)
         if student_only and teacher_only:
             raise ValueError("EvalGraph: student_only and teacher_only exclude each other")
         # the student's frames (ops.STUDENT_SAMPLING); evaluation draws "random" frames with draw 0: the same frames for the same batching
@@ -1174,7 +1203,7 @@ class EvalGraph:
         n_s, l1s, l2s, plan_s = sp
         with torch.cuda.stream(self._side):
             s_state, s_pred = self.student.forward(xs, l1s, l2s, plan_s)
-            ops.ce_loss(s_pred, labels_u8, self.losses[0:1])
+            self._label_loss(s_pred, labels_u8, self.losses[0:1])
             self._ev_out.record(self._side)
             used = (xs if isinstance(xs, tuple) else (xs,)) + (n_s, l1s, l2s)
             if plan_s is not None:
@@ -1192,6 +1221,9 @@ class EvalGraph:
         out.update(predictions=s_pred, student_state=s_state, num_frames=n_s, student_label_loss=self.losses[0],
                    loss=self.losses[0])
         return out
+
+    def _label_loss(self, pred, labels_u8, loss, dpred=None, grad_scale=1.0):
+        self.label_loss.fused(pred, labels_u8, loss, dpred, grad_scale=grad_scale)
 
     def _step_teacher(self, x_raw, num_frames, nh):
         """teacher_only: the teacher's forward alone (same input views, row plans and precision handling as _step)."""
@@ -1250,8 +1282,9 @@ class SingleTowerGraph:
     batch-norm scale/offset gradients of cluster_bn / hidden1_bn are global through the all-reduced f64 sums."""
 
     def __init__(self, tower, base_learning_rate=0.001, learning_rate_decay=1.0, learning_rate_decay_examples=4000000,
-                 regularization_penalty=2.0, clip_gradient_norm=1.0, process_group=None):
+                 regularization_penalty=2.0, clip_gradient_norm=1.0, process_group=None, label_loss=None):
         self.tower, self.device = tower, tower.device
+        self.label_loss = _resolve_label_loss(label_loss, getattr(tower, "V", None))      # --label_loss (None = CrossEntropyLoss)
         self.lr0, self.lr_decay, self.lr_decay_examples = base_learning_rate, learning_rate_decay, learning_rate_decay_examples
         self.reg_pen, self.clip, self.pg = regularization_penalty, clip_gradient_norm, process_group
         self.reducer = GradReducer(process_group)
@@ -1269,6 +1302,13 @@ class SingleTowerGraph:
         """Collective (no-op on one rank): complete f32 MoE weights / moments on every rank (before a checkpoint)."""
         if self.moe is not None:
             self.moe.consolidate(self.reducer)
+
+    def _label_loss(self, pred, labels_u8, loss, dpred=None, grad_scale=1.0):
+        self.label_loss.fused(pred, labels_u8, loss, dpred, grad_scale=grad_scale)
+
+    def label_grads(self):
+        """The dL/dpred buffer the last step filled, as {"teacher": ...} (the one tower).  For tests and debugging."""
+        return {} if self._dp is None else {"teacher": self._dp}
 
     def step(self, x_raw, labels_u8, num_frames, uniform=None, apply=True):
         """x_raw [B,T,F] float32 or uint8 (as the reader delivers it: Dequantize is fused into the input kernels)."""
@@ -1288,7 +1328,7 @@ class SingleTowerGraph:
         else:
             pred = tw.forward(x_raw, num_frames)
         self.losses.zero_()
-        ops.ce_loss(pred, labels_u8, self.losses[0:1], self._dp, grad_scale=1.0 / (B * self.world))
+        self._label_loss(pred, labels_u8, self.losses[0:1], self._dp, grad_scale=1.0 / (B * self.world))
         fuse = (apply and self.fused_moe_update and self.moe is not None and self.moe.can_fuse_update()
                 and self.moe.prefer_fused_update(self.dp)
                 and tw.precision == "bf16")

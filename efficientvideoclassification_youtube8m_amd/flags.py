@@ -79,6 +79,8 @@ _define("start_new_model", False, _bool)
 _define("batch_size", 1024, int)
 _define("every_n", 1, int)
 _define("label_loss", "CrossEntropyLoss", str)
+_define("label_loss_counts_file", "counts_tv", str, "CrossEntropyLossClassImbalance: the file of class counts, one integer per line, one line per "
+        "class (the reference opens 'counts_tv' in the working directory, cs/losses.py:107)")
 _define("dropout", 0.5, float)
 _define("regularization_penalty", 2.0, float)
 _define("base_learning_rate", 0.001, float)

@@ -818,6 +818,25 @@ def ce_loss(pred, labels_u8, loss, dpred=None, grad_scale=1.0, accumulate_grad=F
     _lib.call("evc_ce_loss", _p(pred), _p(labels_u8), B, V, grad_scale, _p(loss), _p(dpred), 1 if accumulate_grad else 0, _stream())
 
 
+# evc_label_loss kinds (include/evc.h EVC_LOSS_*): the label losses of cs/losses.py besides CrossEntropyLoss
+LOSS_WITH_SPARSITY, LOSS_TOP50, LOSS_CLASS_IMBALANCE, LOSS_POSITIVES, LOSS_NEW, LOSS_HINGE, LOSS_SOFTMAX = 1, 2, 3, 4, 5, 6, 7
+LABEL_LOSS_MAX_V = 32768
+
+
+def label_loss(kind, pred, labels_u8, loss, dpred=None, grad_scale=1.0, accumulate_grad=False, class_weights=None):
+    """loss[0] += mean_b row_loss_b of label loss ``kind`` (LOSS_*), dpred (= | +=) grad_scale * d(sum_b row_loss_b)/dpred
+    (evc_label_loss: the contract of ce_loss; class_weights [V] f32 with LOSS_CLASS_IMBALANCE only).  Fixed summation order in every
+    mode; scratch from the stream-aware caching allocator.  What the library refuses raises _lib.EvcError before any launch."""
+    B, V = pred.shape
+    assert pred.dtype == F32 and labels_u8.dtype == torch.uint8 and loss.dtype == F32 and labels_u8.shape == (B, V)
+    assert pred.is_contiguous() and labels_u8.is_contiguous()
+    assert dpred is None or (dpred.dtype == F32 and dpred.shape == (B, V) and dpred.is_contiguous())
+    assert class_weights is None or (class_weights.dtype == F32 and class_weights.numel() == V and class_weights.is_contiguous())
+    ws = torch.empty(max(B, 0) + 320, dtype=F32, device=pred.device)
+    _lib.call("evc_label_loss", int(kind), _p(pred), _p(labels_u8), B, V, float(grad_scale), _p(class_weights), _p(loss), _p(dpred),
+              1 if accumulate_grad else 0, _p(ws), _stream())
+
+
 def kl_pred_loss(pred_t, rowsum_t, pred_s, rowsum_s, loss, dpred_s=None, grad_scale=1.0, accumulate_grad=False):
     B, V = pred_t.shape
     _lib.call("evc_kl_pred_loss", _p(pred_t), _p(rowsum_t), _p(pred_s), _p(rowsum_s), B, V, grad_scale, _p(loss), _p(dpred_s),

@@ -173,15 +173,29 @@ def load_frozen_teacher(graph, teacher_dir):
     return ck
 
 
+def check_label_loss(label_loss_fn, finetune=False):
+    """--label_loss against the number of classes and the flags it excludes (ValueError / NotImplementedError, before anything touches the
+    device): PWELoss refuses itself, CrossEntropyLossTop50 needs 50 classes, CrossEntropyLossClassImbalance its counts file, and the
+    serial modes have CrossEntropyLoss built into their loss kernels."""
+    if not isinstance(label_loss_fn, losses.BaseLoss):
+        raise ValueError("--label_loss: %r is not a losses.BaseLoss" % (label_loss_fn,))
+    label_loss_fn.check(NUM_CLASSES)
+    if not losses.is_default(label_loss_fn) and (FLAGS.teacher_dir or FLAGS.serial_student_dirs.strip()):
+        raise ValueError("--label_loss %s with --teacher_dir / --serial_student_dirs: serial distillation has CrossEntropyLoss built into "
+                         "its loss kernels (evc_distill_losses, evc_distill_losses_multi); train it with --label_loss CrossEntropyLoss"
+                         % type(label_loss_fn).__name__)
+
+
 def build_graph(model, label_loss_fn, feature_size, batch_size, every_n, device, finetune=False, process_group=None, students=_UNSET):
     """Equivalent of cs/train.py:185-427 (and cs/train_finetune.py:185-331 when
     finetune): returns the graph object whose ``step`` runs one iteration."""
-    if not isinstance(label_loss_fn, losses.CrossEntropyLoss):
-        raise NotImplementedError("only CrossEntropyLoss is fused into the training graph (SURVEY.md 8a row a6)")
+    check_label_loss(label_loss_fn, finetune)
     common = dict(base_learning_rate=FLAGS.base_learning_rate, learning_rate_decay=FLAGS.learning_rate_decay,
                   learning_rate_decay_examples=FLAGS.learning_rate_decay_examples,
                   regularization_penalty=FLAGS.regularization_penalty, clip_gradient_norm=FLAGS.clip_gradient_norm,
                   process_group=process_group)
+    if not losses.is_default(label_loss_fn):           # (the default keeps the graphs' own default: the same constructor calls as ever)
+        common["label_loss"] = label_loss_fn
     if isinstance(model, frame_level_models.HierarchicalLstmModel):
         # every_n == 1 (the reference's default, cs/train.py:100-101) still builds and trains model_student, on all 300
         # frames in 5 chunks of 60 (cs/train.py:262-272,349-356): global_step += 2 and the checkpoint holds both scopes.
@@ -189,6 +203,7 @@ def build_graph(model, label_loss_fn, feature_size, batch_size, every_n, device,
         spec = serial_students(finetune) if students is _UNSET else students
         if spec is not None:
             # K students against one forward of the frozen teacher (--serial_student_dirs): hyper-parameters as below, one of each list per student
+            common.pop("label_loss", None)        # (refused above for anything but CrossEntropyLoss, which SerialStudentsGraph has built in)
             return SerialStudentsGraph(batch_size, every_n=spec["every_n"], student_sampling=spec["sampling"], distill_losses=spec["losses"],
                                        feature_size=feature_size, vocab_size=NUM_CLASSES, max_frames=FLAGS.max_num_frames,
                                        num_inputs_to_lstm=FLAGS.num_inputs_to_lstm, lstm_cells=FLAGS.lstm_cells, lstm_layers=FLAGS.lstm_layers,
@@ -300,6 +315,9 @@ def save_checkpoint(graph, train_dir, rank):
         sd["student_sampling"] = graph.student_sampling          # metadata: the frames this student was trained on (--student_sampling)
     if getattr(graph, "mode", None) == "serial":                 # metadata: trained against the frozen teacher in model/*, on these losses
         sd["distill_mode"], sd["distill_losses"] = "serial", ",".join(graph.distill_losses)
+    fn = getattr(graph, "label_loss", None)
+    if fn is not None and not losses.is_default(fn):             # metadata: the --label_loss these weights were trained on (the default: no key)
+        sd["label_loss"] = type(fn).__name__
     for tw in (getattr(graph, "teacher", None), getattr(graph, "student", None), getattr(graph, "tower", None)):
         if tw is not None:
             sd.update({k: v.cpu() for k, v in tw.state_dict().items()})
@@ -364,6 +382,7 @@ def main(argv=None):
     rank = int(os.environ.get("RANK", "0"))
     multi = serial_students(finetune, world)
     serial = check_serial_flags(finetune, world, students=multi)
+    check_label_loss(find_class_by_name(FLAGS.label_loss, [losses])(), finetune)
     multi_cks = serial_students_checkpoints(multi["dirs"], FLAGS.start_new_model) if multi else None
     local = int(os.environ.get("LOCAL_RANK", str(FLAGS.gpu)))
     # test hook (tests/test_gpu_dp.py): several ranks on ONE GPU over gloo, to run this file's multi-rank path on a

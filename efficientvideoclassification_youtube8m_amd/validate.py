@@ -19,7 +19,7 @@ when the global step has not moved, looping until --run_once.  Replaced: TF sess
 the per-class positive counts, which EvaluationMetrics.accumulate_selected turns into the same numbers (ties: see there).
 ``--ensemble_dirs`` (+ --ensemble_towers / --ensemble_every_n / --ensemble_mode / --ensemble_weights, see inference.py; needs
 ``--run_once True``) evaluates the combination of several checkpoints: every member runs on the batch, ops.ensemble_topk_rows writes the
-combined [B, 4716] predictions, and the loss (ops.ce_loss) and the metrics - host or --metrics_on_device - are those of the combination;
+combined [B, 4716] predictions, and the loss (--label_loss; by default ops.ce_loss) and the metrics - host or --metrics_on_device - are those of the combination;
 no student_state_loss is reported and --train_dir only receives events.jsonl.
 """
 from __future__ import annotations
@@ -51,7 +51,7 @@ def get_input_evaluation_tensors(reader, data_pattern, batch_size=1024, num_read
     return pipe
 
 
-def build_graph(reader, model, batch_size, device, student_only=False):
+def build_graph(reader, model, batch_size, device, student_only=False, label_loss=None):
     """cs/validate.py:107-189 / cs/eval_finetune.py:108-175."""
     if not isinstance(model, frame_level_models.HierarchicalLstmModel):
         raise NotImplementedError("validate.py unpacks the H-LSTM (state, result) pair (cs/validate.py:150,157); "
@@ -59,10 +59,11 @@ def build_graph(reader, model, batch_size, device, student_only=False):
     return EvalGraph(batch_size, every_n=FLAGS.every_n, student_only=student_only, feature_size=sum(reader.feature_sizes),
                      vocab_size=reader.num_classes, max_frames=FLAGS.max_num_frames, num_inputs_to_lstm=FLAGS.num_inputs_to_lstm,
                      lstm_cells=FLAGS.lstm_cells, lstm_layers=FLAGS.lstm_layers, num_mixtures=FLAGS.moe_num_mixtures, device=device,
-                     precision=FLAGS.precision, student_sampling=FLAGS.student_sampling, sampling_seed=FLAGS.student_sampling_seed)
+                     precision=FLAGS.precision, student_sampling=FLAGS.student_sampling, sampling_seed=FLAGS.student_sampling_seed,
+                     label_loss=label_loss)
 
 
-def build_ensemble(reader, model, spec, batch_size, device):
+def build_ensemble(reader, model, spec, batch_size, device, label_loss=None):
     """The members of an inference.ensemble_spec(), restored, behind one step() that returns their combination."""
     from . import inference
     if not isinstance(model, frame_level_models.HierarchicalLstmModel):
@@ -72,7 +73,7 @@ def build_ensemble(reader, model, spec, batch_size, device):
     graph.restore(sds)
     for d, tower, every_n in members:
         logging.info("ensemble member: the %s tower of %s%s", tower, d, " at every_n = %d" % every_n if tower == "student" else "")
-    return _CombinedMembers(graph, spec, max(int(sd.get("global_step", 0)) for sd in sds))
+    return _CombinedMembers(graph, spec, max(int(sd.get("global_step", 0)) for sd in sds), label_loss)
 
 
 def _batches(reader, device):
@@ -99,10 +100,11 @@ def check_flags():
 
 class _CombinedMembers:
     """An ensemble behind the step() of an EvalGraph: the members' predictions combined by ops.ensemble_topk_rows (its dense output)
-    as "predictions", and the cross-entropy of the combination (ops.ce_loss) as "loss"."""
+    as "predictions", and the label loss of the combination (--label_loss; CrossEntropyLoss: ops.ce_loss) as "loss"."""
 
-    def __init__(self, graph, spec, global_step):
+    def __init__(self, graph, spec, global_step, label_loss=None):
         self.graph, self.spec, self.global_step = graph, spec, global_step
+        self.label_loss = losses.resolve(label_loss)
         self.teacher = self.student = None
         self._loss = None
 
@@ -112,7 +114,7 @@ class _CombinedMembers:
         if self._loss is None:
             self._loss = torch.zeros(1, dtype=torch.float32, device=combined.device)
         self._loss.zero_()
-        ops.ce_loss(combined, labels_u8, self._loss[0:1])
+        self.label_loss.fused(combined, labels_u8, self._loss[0:1])
         return {"predictions": combined, "loss": self._loss[0]}
 
 
@@ -150,7 +152,6 @@ def _evaluate_restored(graph, reader, label_loss_fn, summary_writer, evl_metrics
     logging.info("enter eval_once loop global_step_val = %s. ", global_step_val)
     evl_metrics.clear()
     examples_processed, total_example_per_sec = 0, []
-    fused_ce = isinstance(label_loss_fn, losses.CrossEntropyLoss)
     on_device = FLAGS.metrics_on_device
     fetcher = utils.AsyncFetcher(device)
     last_time = [time.time()]
@@ -187,7 +188,7 @@ def _evaluate_restored(graph, reader, label_loss_fn, summary_writer, evl_metrics
     pending = None
     for ids, q, labels, n, n_host in _batches(reader, device):
         out = graph.step(q, labels, n, num_frames_host=n_host)
-        loss_t = out["loss"] if fused_ce else label_loss_fn.calculate_loss(out["predictions"], labels)
+        loss_t = out["loss"]                                             # --label_loss, computed by the graph behind the MoE head
         if on_device:                                                    # same stream, right behind the MoE head
             fetch = ops.eval_select_rows(out["predictions"], labels, FLAGS.top_k)
             fetch["loss"] = loss_t.reshape(1)
@@ -230,12 +231,13 @@ def evaluate(student_only=False, max_evals=None):
     reader = get_reader()
     model = find_class_by_name(FLAGS.model, [frame_level_models, video_level_models])()
     label_loss_fn = find_class_by_name(FLAGS.label_loss, [losses])()
+    label_loss_fn.check(reader.num_classes)
     if FLAGS.eval_data_pattern == "":
         raise IOError("'eval_data_pattern' was not specified. Nothing to evaluate.")
     if spec is None:
-        graph = build_graph(reader, model, FLAGS.batch_size, device, student_only)
+        graph = build_graph(reader, model, FLAGS.batch_size, device, student_only, label_loss=label_loss_fn)
     else:
-        graph = build_ensemble(reader, model, spec, FLAGS.batch_size, device)
+        graph = build_ensemble(reader, model, spec, FLAGS.batch_size, device, label_loss=label_loss_fn)
     logging.info("built evaluation graph")
     for tw in (graph.teacher, graph.student):
         if tw is not None:

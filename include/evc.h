@@ -36,7 +36,7 @@ extern "C" {
 #define EVC_ERR_HIP (-4)
 #define EVC_ERR_BAD_ARG (-5)
 
-#define EVC_VERSION 107   /* 107 (round 6, late): evc_lstm_level2_fwd_high (the two-layer L1 level of the "high" mode in T + 1 two-tile launches); evc_topk_rows (per-row top-k of the inference binary's prediction file; an addition, no existing entry changed), later evc_eval_select_rows and evc_ensemble_topk_rows (the combination of several members' predictions in front of that selection) and evc_student_frame_select / evc_l2norm_chunk_sel_fwd / evc_l2norm_chunk_sel_int (student frame selection) and evc_distill_losses (the loss section of the serial distillation step) and evc_distill_losses_multi (that section for K students against one teacher) the same way; 106 (round 6): evc_gemm_nt_sqnorm, evc_l2norm_chunk_int + the x_row_scale / x_col_const / b8_gap arguments of evc_lstm_layer_fwd_f16_fp8lo (integer-frame layer 0: the uint8 input exact), evc_lstm_layer_fwd_f16_fp8lo / evc_lstm_stack2_fwd_f16_fp8lo gained h_lo (low-order half of h corrected: 4H-byte h rows), evc_cast_f32_to_fp8_lohi, evc_lstm_adam_fused gained fp8_hi_tail; evc_absmax_partials, evc_cast_f32_to_f16_fp8x_dyn, evc_gemm_nt_f16_fp8_dyn (dynamic e4m3 range of the MoE head's input state); evc_l2norm_chunk_fwd accepts out1 == NULL (student-only graphs read the sub-sampled frames only), evc_clip_adam_small limited to 2^15 elements per tensor; 105 (round 5, second session): evc_cast_f32_to_f16_dither, evc_lstm_layer_fwd_f16_dith (time-dithered f16 weight images: an L1 layer of the "high" mode without stages for its weights' low-order halves), evc_gemm_tn2_rows (weight-gradient products that skip the dead rows of a row-planned level's time slabs); 104 (round 5): evc_lstm_level2_fwd, evc_ce_loss_ordered, evc_rep_loss_ordered, evc_gemm_tn2_slabs, evc_sum_slabs, evc_clip_adam_small; evc_moe_grad_update* accept p_bf16 == NULL (forward shadow not written), evc_lstm_stack2_bwd runs M <= 512 stacks on the skinny pair launches, evc_dbof_cluster_pool_fwd walks tiles (EVC_DBOF_WALK), EVC_DETERMINISTIC parsed as "set, not empty, not 0"; 103 (round 4): evc_sqnorm2_partials, evc_lstm_adam_fused, evc_gram_slabs, evc_moe_grad_norms, evc_moe_grad_update_apply, evc_adam2d_fused, evc_colsum_bf16_det, evc_sample_sequence_gather, evc_relu6_fwd/bwd, evc_framepool_mean_fwd/bwd, evc_stream_create_cu_mask / evc_stream_destroy; EVC_DETERMINISTIC=1 read by the library; 102: evc_lstm_layer_fwd_f16_fp8lo, evc_lstm_stack2_fwd_f16_fp8lo, evc_gemm_nt_f16_fp8, evc_cast_f32_to_fp8_lo, evc_cast_f32_to_f16_fp8x, aux_mode 5, evc_moe_grad_update_wide; 101 (round 3): evc_l2norm_chunk_fwd gained aux_mode; evc_lstm_layer_fwd_hp takes wide split operands; f16 / wide-split entries added */
+#define EVC_VERSION 107   /* 107 (round 6, late): evc_lstm_level2_fwd_high (the two-layer L1 level of the "high" mode in T + 1 two-tile launches); evc_topk_rows (per-row top-k of the inference binary's prediction file; an addition, no existing entry changed), later evc_eval_select_rows and evc_ensemble_topk_rows (the combination of several members' predictions in front of that selection) and evc_student_frame_select / evc_l2norm_chunk_sel_fwd / evc_l2norm_chunk_sel_int (student frame selection) and evc_distill_losses (the loss section of the serial distillation step) and evc_distill_losses_multi (that section for K students against one teacher) and evc_label_loss (the label losses of --label_loss besides CrossEntropyLoss) the same way; 106 (round 6): evc_gemm_nt_sqnorm, evc_l2norm_chunk_int + the x_row_scale / x_col_const / b8_gap arguments of evc_lstm_layer_fwd_f16_fp8lo (integer-frame layer 0: the uint8 input exact), evc_lstm_layer_fwd_f16_fp8lo / evc_lstm_stack2_fwd_f16_fp8lo gained h_lo (low-order half of h corrected: 4H-byte h rows), evc_cast_f32_to_fp8_lohi, evc_lstm_adam_fused gained fp8_hi_tail; evc_absmax_partials, evc_cast_f32_to_f16_fp8x_dyn, evc_gemm_nt_f16_fp8_dyn (dynamic e4m3 range of the MoE head's input state); evc_l2norm_chunk_fwd accepts out1 == NULL (student-only graphs read the sub-sampled frames only), evc_clip_adam_small limited to 2^15 elements per tensor; 105 (round 5, second session): evc_cast_f32_to_f16_dither, evc_lstm_layer_fwd_f16_dith (time-dithered f16 weight images: an L1 layer of the "high" mode without stages for its weights' low-order halves), evc_gemm_tn2_rows (weight-gradient products that skip the dead rows of a row-planned level's time slabs); 104 (round 5): evc_lstm_level2_fwd, evc_ce_loss_ordered, evc_rep_loss_ordered, evc_gemm_tn2_slabs, evc_sum_slabs, evc_clip_adam_small; evc_moe_grad_update* accept p_bf16 == NULL (forward shadow not written), evc_lstm_stack2_bwd runs M <= 512 stacks on the skinny pair launches, evc_dbof_cluster_pool_fwd walks tiles (EVC_DBOF_WALK), EVC_DETERMINISTIC parsed as "set, not empty, not 0"; 103 (round 4): evc_sqnorm2_partials, evc_lstm_adam_fused, evc_gram_slabs, evc_moe_grad_norms, evc_moe_grad_update_apply, evc_adam2d_fused, evc_colsum_bf16_det, evc_sample_sequence_gather, evc_relu6_fwd/bwd, evc_framepool_mean_fwd/bwd, evc_stream_create_cu_mask / evc_stream_destroy; EVC_DETERMINISTIC=1 read by the library; 102: evc_lstm_layer_fwd_f16_fp8lo, evc_lstm_stack2_fwd_f16_fp8lo, evc_gemm_nt_f16_fp8, evc_cast_f32_to_fp8_lo, evc_cast_f32_to_f16_fp8x, aux_mode 5, evc_moe_grad_update_wide; 101 (round 3): evc_l2norm_chunk_fwd gained aux_mode; evc_lstm_layer_fwd_hp takes wide split operands; f16 / wide-split entries added */
 
 typedef uint16_t evc_bf16;
 typedef uint16_t evc_f16;   /* raw IEEE binary16 bits (the "high" precision forward operands of the L1 levels) */
@@ -526,6 +526,42 @@ int evc_distill_losses_multi(const float* pred_t, const float* rowsum_t, const u
                              const float* const* pred_s, const float* const* rowsum_s, const float* const* state_s,
                              const float* g_ce, const float* g_kl, const float* g_rep, float* const* dpred_s, float* const* dstate_s,
                              int B, int V, int D, float* losses /* [K][4] */, float* workspace, void* stream);
+
+/* The label losses of cs/losses.py besides CrossEntropyLoss (--label_loss), value and gradient in one pass, with evc_ce_loss's semantics:
+ *   *loss += (1/B) sum_b row_loss_b ;  dpred (= | +=) grad_scale * d(sum_b row_loss_b)/dpred  (the caller passes grad_scale = w / B).
+ * labels are bytes, nonzero = positive (y = 1).  All in f32; eps = 10e-6, a = p + eps, b = 1 - p + eps, CE = -(y log a + (1-y) log b),
+ * dCE = -y/a + (1-y)/b.  Row loss = sum over the classes c of:
+ *   EVC_LOSS_WITH_SPARSITY    CE + 0.1 p                                          d/dp: dCE + 0.1                     (cs/losses.py:28-41)
+ *   EVC_LOSS_TOP50            m_c (4716/50) CE, m_c = [p_c >= t], t = the 50th largest value of the row counting duplicates (ties at t
+ *                             are all kept); the factor is the literal 4716/50 whatever V is           d/dp: m_c 94.32 dCE  (:43-60)
+ *   EVC_LOSS_CLASS_IMBALANCE  -(w_c y log a + (1-y) log b), w = class_weights [V]  d/dp: -w_c y/a + (1-y)/b            (:99-119)
+ *   EVC_LOSS_POSITIVES        -y log a                                            d/dp: -y/a                          (:121-131)
+ *   EVC_LOSS_NEW              -(bp y log a + bn (1-y) log b), bp = [p < 0.9f], bn = [p (1-y) > mpp],
+ *                             mpp = max(min_{b,c}(y ? p : 1) - 0.1f, 0.1f): a minimum over the WHOLE [B][V] batch of this call
+ *                                                                                 d/dp: -bp y/a + bn (1-y)/b          (:133-151)
+ *   EVC_LOSS_HINGE            max(0, 1 - s p), s = 2y - 1                         d/dp: -s where 1 - s p > 0, else exactly 0 (:153-169, b = 1)
+ *   EVC_LOSS_SOFTMAX          -sum_c yhat_c log softmax(p)_c, yhat = y / max(sum y, 10e-8); a row without positives: loss 0, gradient 0
+ *                                                                                 d/dp: softmax_c sum(yhat) - yhat_c  (:172-196)
+ * No mask (m, bp, bn, the hinge's side) carries a gradient; a masked element's gradient is exactly 0, and grad_scale = 0 gives exact zeros.
+ * One 256-thread workgroup per row (the grid strides over the rows).  The elementwise kinds read pred / labels once and write dpred once,
+ * 16 bytes per lane where the row's pointers are 16-byte aligned (labels: 4-byte), 4 bytes otherwise - decided per row; TOP50 and SOFTMAX
+ * stage the row in LDS (V <= 32768): TOP50 selects the exact 50th key by a 4-pass radix select, SOFTMAX takes max and sum exp from LDS;
+ * NEW runs a launch in front that leaves per-workgroup minima in the workspace, reduced by every workgroup of the main launch.
+ * workspace: B + 320 floats of scratch.  Every workgroup leaves its row's loss in workspace[row] and a one-workgroup finish launch adds
+ * them in a fixed order: no float atomics, two calls on the same inputs give the same bits, with or without EVC_DETERMINISTIC.
+ * Refused before any launch: B <= 0, V <= 0 or V > 32768 (EVC_ERR_BAD_SHAPE); an unknown kind, TOP50 with V < 50, CLASS_IMBALANCE
+ * without class_weights or class_weights with any other kind, a NULL workspace / pred / labels / loss (EVC_ERR_BAD_ARG). */
+#define EVC_LOSS_WITH_SPARSITY 1
+#define EVC_LOSS_TOP50 2
+#define EVC_LOSS_CLASS_IMBALANCE 3
+#define EVC_LOSS_POSITIVES 4
+#define EVC_LOSS_NEW 5
+#define EVC_LOSS_HINGE 6
+#define EVC_LOSS_SOFTMAX 7
+int evc_label_loss(int kind, const float* pred, const uint8_t* labels, int B, int V, float grad_scale,
+                   const float* class_weights /* [V], kind CLASS_IMBALANCE only, else NULL */,
+                   float* loss, float* dpred /* may be NULL */, int accumulate_grad,
+                   float* workspace /* B + 320 floats */, void* stream);
 
 /* ---- a8 + a9: regulariser, per-tensor clip, TF-Adam ---------------------------
  * slim.l2_regularizer (cs/video_level_models.py:428,434) folded into the
