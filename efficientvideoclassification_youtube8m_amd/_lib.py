@@ -132,6 +132,8 @@ SIGNATURES = {
     "evc_student_frame_select": [vp, i32, i32, i32, i32, C.c_uint32, C.c_uint32, i32, vp, vp],
     "evc_l2norm_chunk_sel_fwd": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, i32, vp, i32, vp],
     "evc_l2norm_chunk_sel_int": [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp],
+    "evc_frame_change_keys": [vp, vp, vp, i32, i32, i32, vp, vp],
+    "evc_student_frame_select_scored": [vp, vp, i32, i32, i32, i32, vp, vp],
 }
 EXPORTS = tuple(SIGNATURES) + ("evc_version", "evc_last_error")
 

@@ -361,10 +361,16 @@ def input_image_args(*towers):
     return dict(f16_segments=max(t.f16_x_segments for t in tw))
 
 
-def input_views(g, x_raw, num_frames, tp, sp, need_student):
+def scored_sampling(g):
+    """Whether graph ``g``'s student takes its frames by their content (ops.STUDENT_SAMPLING_SCORED): its table needs ops.frame_change_keys."""
+    return getattr(g, "student", None) is not None and getattr(g, "student_sampling", "uniform") in ops.STUDENT_SAMPLING_SCORED
+
+
+def input_views(g, x_raw, num_frames, tp, sp, need_student, keys=None):
     """The L1 input images of graph ``g``'s towers for one batch (ops.l2norm_chunk): (teacher view, student view), each the plain bf16 image or - in
     the non-bf16 modes - a tuple (bf16 image, second image[, row scales]).  uint8 frames into "high" towers whose layer 0 is on the f16 + e4m3 form
-    take the INTEGER-frame images (ops.l2norm_chunk_int, HLstmTower.x_int: the input exact, round 6)."""
+    take the INTEGER-frame images (ops.l2norm_chunk_int, HLstmTower.x_int: the input exact, round 6).  ``keys``: the batch's
+    ops.frame_change_keys where the owner of several graphs on one batch has computed them already (only read under a scored word)."""
     towers = [t for t in (g.teacher, g.student if need_student else None) if t is not None]
     p1, p2 = (tp[2] if tp else None), (sp[3] if sp else None)
     as_int = x_raw.dtype == torch.uint8 and towers and all(t.precision == "high" and t.x_int() for t in towers)
@@ -380,8 +386,13 @@ def input_views(g, x_raw, num_frames, tp, sp, need_student):
                 xt = ops.l2norm_chunk_int(x_raw, num_frames, g.C1, None, g.C2, plan1=p1)[0]
             else:
                 xt = ops.l2norm_chunk(x_raw, g.C1, None, g.C2, num_frames=nf, split=towers[0].input_split(), plan1=p1, **img)[0]
-        src = ops.student_frame_select(num_frames, g.max_frames, g.every_n, g.student_sampling, seed=g.sampling_seed,
-                                       draw=getattr(g, "sampling_draw", 0), row0=getattr(g, "sampling_row0", 0))
+        if g.student_sampling in ops.STUDENT_SAMPLING_SCORED:      # by content: one key per raw frame on this stream, then the ranking table
+            if keys is None:
+                keys = ops.frame_change_keys(x_raw, num_frames)
+            src = ops.student_frame_select_scored(num_frames, keys, g.max_frames, g.every_n, g.student_sampling)
+        else:
+            src = ops.student_frame_select(num_frames, g.max_frames, g.every_n, g.student_sampling, seed=g.sampling_seed,
+                                           draw=getattr(g, "sampling_draw", 0), row0=getattr(g, "sampling_row0", 0))
         g.last_frame_table = src          # (the table of the last batch, for whoever wants to look: tests, diagnostics)
         if as_int:
             return xt, ops.l2norm_chunk_int_sel(x_raw, num_frames, src, g.every_n, g.C2, plan2=p2)
@@ -1028,11 +1039,13 @@ class SerialStudentsGraph:
         tp, _ = frame_counts_and_plans(self._t_slot, num_frames, nh, True, False)
         xt, _ = input_views(self._t_slot, x_raw, num_frames, tp, None, False)
         sps, xss = [], []
+        # the keys of the content-aware strategies depend on the batch alone: once, for every student that ranks by them
+        keys = ops.frame_change_keys(x_raw, num_frames) if any(scored_sampling(slot) for slot in self._s_slots) else None
         for slot in self._s_slots:
             slot.sampling_draw, slot.sampling_row0 = self.global_step, 0      # one train op per iteration: a new "random" draw per step
             _, sp = frame_counts_and_plans(slot, num_frames, nh, False, True)
             sps.append(sp)
-            xss.append(input_views(slot, x_raw, num_frames, None, sp, True)[1])
+            xss.append(input_views(slot, x_raw, num_frames, None, sp, True, keys=keys)[1])
         for s in self.students:
             s.run_deferred()
         self.losses.zero_()
@@ -1173,20 +1186,21 @@ class EvalGraph:
             if tw is not None:
                 tw.load_state_dict(state_dict)
 
-    def step(self, x_raw, labels_u8, num_frames, num_frames_host=None):
+    def step(self, x_raw, labels_u8, num_frames, num_frames_host=None, keys=None):
+        """``keys``: the batch's ops.frame_change_keys, computed on the caller's stream by an owner of several graphs (EnsembleGraph)."""
         if num_frames_host is None:
             num_frames_host = num_frames.cpu()
         nh = np.asarray(num_frames_host, dtype=np.int64).reshape(-1)
         caller = torch.cuda.current_stream(self.device)
         self._main.wait_stream(caller)
         with torch.cuda.stream(self._main):
-            out = self._step(x_raw, labels_u8, num_frames, nh)
-        for t in (x_raw, labels_u8, num_frames):
+            out = self._step(x_raw, labels_u8, num_frames, nh, keys)
+        for t in (x_raw, labels_u8, num_frames) + (() if keys is None else (keys,)):
             t.record_stream(self._main)
         caller.wait_stream(self._main)
         return out
 
-    def _step(self, x_raw, labels_u8, num_frames, nh):
+    def _step(self, x_raw, labels_u8, num_frames, nh, keys=None):
         """Returns predictions (student), student_label_loss, student_state_loss (teacher_student only) - the
         tensors cs/validate.py:240 fetches.  The two towers are independent: they run on two streams."""
         if self.student is None:
@@ -1195,7 +1209,7 @@ class EvalGraph:
         split = self.student.input_split()
         u8 = x_raw.dtype == torch.uint8
         tp, sp = frame_counts_and_plans(self, num_frames, nh, self.teacher is not None, True)
-        xt, xs = input_views(self, x_raw, num_frames, tp, sp, True)
+        xt, xs = input_views(self, x_raw, num_frames, tp, sp, True, keys=keys)
         self.losses.zero_()
         out = {}
         self._ev_in.record(main)
@@ -1263,7 +1277,10 @@ class EnsembleGraph:
     def step(self, x_raw, labels_u8, num_frames, num_frames_host=None):
         if num_frames_host is None:
             num_frames_host = num_frames.cpu()
-        return [g.step(x_raw, labels_u8, num_frames, num_frames_host=num_frames_host)["predictions"] for g in self.members]
+        # the keys of the content-aware strategies depend on the batch alone: once, for every member that ranks by them
+        keys = ops.frame_change_keys(x_raw, num_frames) if any(scored_sampling(g) for g in self.members) else None
+        return [g.step(x_raw, labels_u8, num_frames, num_frames_host=num_frames_host, keys=keys if scored_sampling(g) else None)["predictions"]
+                for g in self.members]
 
 
 class SingleTowerGraph:

@@ -141,12 +141,15 @@ _define("metrics_on_device", False, _bool, "validate / eval_finetune: select wha
         "for bit except for rows with an exact tie at the top_k-th / label-count-th place, where the device admits the lowest class "
         "(eval_util.EvaluationMetrics.accumulate_selected); needs 1 <= top_k <= min(256, classes)")
 # ---- which frames the student sees (train, train_finetune, train_convert_model, validate, eval_finetune, inference) ----------------------
-_define("student_sampling", "uniform", _sampling, "uniform|first|middle|last|first_middle_last|random: the student's int(n/300*S) frames are the "
+_define("student_sampling", "uniform", _sampling, "uniform|first|middle|last|first_middle_last|random|change|segment_change: the student's int(n/300*S) frames are the "
         "grid s * every_n of the padded tensor (uniform: the reference), the first, the middle or the last ones of the video's n frames, three "
         "runs at its start, middle and end, or drawn at random without replacement (kept in time order).  The table is built on the device "
         "(ops.student_frame_select) and the input pass gathers the frames.  random: training draws anew at every iteration (hash of seed, "
         "iteration, position in the global batch, frame); evaluation and inference always use draw 0, so they are deterministic for a given "
-        "batching (batch size and order of the records) - another batch size gives a video another position and other frames.  Checkpoints "
+        "batching (batch size and order of the records) - another batch size gives a video another position and other frames.  change / "
+        "segment_change choose by content: every raw frame is scored on the device by its squared change from the frame before it "
+        "(ops.frame_change_keys; the first frame counts as the largest change), and the student sees the k frames of largest change, or of "
+        "each of k equal segments of the video the one of largest change; both read every live frame of the batch once more.  Checkpoints "
         "record the word; validate / inference warn when the flag disagrees with it, and the flag wins")
 _define("student_sampling_seed", 0, int, "seed of --student_sampling random")
 _define("ensemble_sampling", "", str, "one --student_sampling word per member (ignored for teachers); '' = --student_sampling for all")

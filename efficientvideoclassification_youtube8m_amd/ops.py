@@ -408,10 +408,15 @@ def frame_counts(num_frames, every_n, num_chunks, chunk_len, max_frames=300, sub
 STUDENT_SAMPLING = ("uniform", "first", "middle", "last", "first_middle_last", "random")
 
 
+# The strategies that read the video: the table is ranked by one key per frame (frame_change_keys); the EVC_SELECT_* codes go on from
+# STUDENT_SAMPLING's, for evc_student_frame_select_scored.
+STUDENT_SAMPLING_SCORED = ("change", "segment_change")
+
+
 def check_student_sampling(word, flag="student_sampling"):
     """The word itself, or a ValueError that names the choices (raised before anything touches the device)."""
-    if word not in STUDENT_SAMPLING:
-        raise ValueError("%s: %r (%s)" % (flag, word, " | ".join(STUDENT_SAMPLING)))
+    if word not in STUDENT_SAMPLING and word not in STUDENT_SAMPLING_SCORED:
+        raise ValueError("%s: %r (%s)" % (flag, word, " | ".join(STUDENT_SAMPLING + STUDENT_SAMPLING_SCORED)))
     return word
 
 
@@ -419,11 +424,41 @@ def student_frame_select(num_frames, T, every_n, strategy, seed=0, draw=0, row0=
     """The student's source-frame table (evc_student_frame_select): src [B, T // every_n] int32 on the device, -1 = no frame.  num_frames [B]
     int32 (device); strategy a word of STUDENT_SAMPLING; seed / draw / row0 only matter under "random" (draw: the training iteration,
     row0: index of this batch's first video in the global batch)."""
-    code = STUDENT_SAMPLING.index(check_student_sampling(strategy, "student_frame_select"))
+    if check_student_sampling(strategy, "student_frame_select") in STUDENT_SAMPLING_SCORED:
+        raise ValueError("student_frame_select: %r ranks the frames by their content, so the frames are needed: frame_change_keys, then "
+                         "student_frame_select_scored" % (strategy,))
+    code = STUDENT_SAMPLING.index(strategy)
     assert num_frames.dtype == torch.int32 and num_frames.dim() == 1 and num_frames.is_contiguous()
     B = num_frames.shape[0]
     src = torch.empty((B, T // max(1, every_n)), dtype=torch.int32, device=num_frames.device)
     _lib.call("evc_student_frame_select", _p(num_frames), B, T, every_n, code, int(seed) & 0xFFFFFFFF, int(draw) & 0xFFFFFFFF, int(row0), _p(src), _stream())
+    return src
+
+
+def frame_change_keys(x_raw, num_frames):
+    """One key per frame, its squared change from the frame before (evc_frame_change_keys): x_raw [B, T, F] float32 or uint8 RAW frames
+    (contiguous, device), num_frames [B] int32 -> keys [B, T], the uint32 keys as the bit patterns of an int32 tensor (what
+    student_frame_select_scored takes; .cpu().numpy().view(numpy.uint32) to look at them).  Depends on the data only."""
+    assert x_raw.dim() == 3 and x_raw.is_contiguous() and x_raw.dtype in (torch.float32, torch.uint8)
+    assert num_frames.dtype == torch.int32 and num_frames.dim() == 1 and num_frames.is_contiguous() and num_frames.shape[0] == x_raw.shape[0]
+    B, T, F = x_raw.shape
+    keys = torch.empty((B, T), dtype=torch.int32, device=x_raw.device)
+    is_u8 = x_raw.dtype == torch.uint8
+    _lib.call("evc_frame_change_keys", None if is_u8 else _p(x_raw), _p(x_raw) if is_u8 else None, _p(num_frames), B, T, F, _p(keys), _stream())
+    return keys
+
+
+def student_frame_select_scored(num_frames, keys, T, every_n, strategy):
+    """The student's source-frame table under a word of STUDENT_SAMPLING_SCORED (evc_student_frame_select_scored): src [B, T // every_n]
+    int32 on the device, -1 = no frame, from keys [B, T] (frame_change_keys)."""
+    if strategy not in STUDENT_SAMPLING_SCORED:
+        raise ValueError("student_frame_select_scored: %r (%s)" % (strategy, " | ".join(STUDENT_SAMPLING_SCORED)))
+    code = len(STUDENT_SAMPLING) + STUDENT_SAMPLING_SCORED.index(strategy)
+    assert num_frames.dtype == torch.int32 and num_frames.dim() == 1 and num_frames.is_contiguous()
+    B = num_frames.shape[0]
+    assert keys.dtype == torch.int32 and tuple(keys.shape) == (B, T) and keys.is_contiguous()
+    src = torch.empty((B, T // max(1, every_n)), dtype=torch.int32, device=num_frames.device)
+    _lib.call("evc_student_frame_select_scored", _p(num_frames), _p(keys), B, T, every_n, code, _p(src), _stream())
     return src
 
 

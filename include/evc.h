@@ -901,6 +901,35 @@ int evc_l2norm_chunk_sel_fwd(const float* x_raw, const uint8_t* x_u8, const int3
 int evc_l2norm_chunk_sel_int(const uint8_t* x_u8, const int32_t* num_frames, const int32_t* src, int B, int T, int F, int every_n, int C2,
                              evc_bf16* out2, evc_f16* out2_int, float* rs2, const int32_t* row_pos2, int rows2, void* stream);
 
+/* ---- content-aware student frames: largest-change selection (an addition, as the section above) ------------------------------------
+ * evc_frame_change_keys scores every frame of x [B][T][F] by its change from the frame before it, keys [B][T] uint32, larger = more change.
+ * Exactly one of x_f32 / x_u8 is non-NULL.  With n = min(max(num_frames[b], 0), T):
+ *   keys[b][0] = 0xFFFFFFFF when n >= 1 (the first frame opens the first shot); keys[b][t] = 0 for t >= n; frames at or beyond n are never read;
+ *   uint8 frames, 0 < t < n: keys[b][t] = sum_f (q_t[f] - q_{t-1}[f])^2 as an exact integer.  Dequantisation is affine, so this orders the
+ *     frames exactly as the dequantised differences would.  The sum has to fit 32 bits: F <= 66051, a larger F is EVC_ERR_BAD_SHAPE;
+ *   f32 frames, 0 < t < n: s = sum_f (x_t[f] - x_{t-1}[f])^2 in f32, in a fixed order (two calls on the same inputs give the same bits; the
+ *     order depends on F and on the alignment of x only).  s >= 0, so the key is the bit pattern of s; a NaN sum gives 0xFFFFFFFF (a NaN frame
+ *     is "a change", and it always sorts the same way).
+ * The scores are taken on the RAW frames, not on the l2-normalised ones the towers read: that is what makes the uint8 form exact.  The same
+ * video given as bytes and as dequantised floats may order near-ties differently (the f32 sum rounds, the integer sum does not).
+ * Limits as evc_student_frame_select: T <= 1024, B > 0, F > 0; anything else is EVC_ERR_BAD_SHAPE / EVC_ERR_BAD_ARG before any launch.
+ * One wave per run of 8 consecutive frames of a video, the previous row kept in registers (rows of at most 5120 bytes that start on a
+ * 16-byte boundary; other rows by 16-, 4- or 1-byte accesses, decided per row), wave reductions, one store per frame; no atomics, no
+ * scratch, no LDS.
+ *
+ * evc_student_frame_select_scored: the sibling of evc_student_frame_select for the strategies that rank by such keys.  n, k, S and the
+ * entries j >= k (-1) exactly as there; the entries j < k are
+ *   EVC_SELECT_CHANGE          the k frames t of [0, n) with the largest (key[b][t], then smaller t), in ascending t
+ *   EVC_SELECT_SEGMENT_CHANGE  of segment j = [j n / k, (j + 1) n / k) (integer divisions; non-empty because k <= n) the frame with the
+ *                              largest key, the smallest t on ties: strictly increasing by construction
+ * Any other strategy code is EVC_ERR_BAD_ARG.  One 256-thread workgroup per video, the keys staged in LDS. */
+#define EVC_SELECT_CHANGE 6
+#define EVC_SELECT_SEGMENT_CHANGE 7
+int evc_frame_change_keys(const float* x_f32, const uint8_t* x_u8, const int32_t* num_frames, int B, int T, int F, uint32_t* keys /* [B][T] */,
+                          void* stream);
+int evc_student_frame_select_scored(const int32_t* num_frames, const uint32_t* keys, int B, int T, int every_n, int strategy,
+                                    int32_t* src /* [B][T / every_n] */, void* stream);
+
 /* utility: out[i] = value for n floats (avoids torch for tiny fills inside C loops) */
 int evc_fill_f32(float* p, int64_t n, float value, void* stream);
 /* Measurement aid, not part of the path: `blocks` workgroups of `threads` threads with `lds_bytes` of LDS each stay resident for
