@@ -266,6 +266,10 @@ extern "C" int evc_sum_slabs(const float* slabs, int64_t slab_stride, int nslab,
 //   pass 1: sum (g + l2 p)^2 and sum p^2 per workgroup -> partials (summed in a fixed order afterwards)
 //   pass 2: per-tensor clip + TF-Adam in the epilogue: reads p, m, v, writes p, m, v, the bf16 forward
 //           shadow and - through an LDS transpose - the bf16 transposed shadow: 30 bytes per parameter.
+//           The epilogue runs ROW-MAJOR over the tile (the gradient tile changes layout through the idle ring): every global
+//           access of a wave covers whole rows of the tile.  From the transposed accumulator layout one instruction touched 16
+//           rows with 64 bytes each (half a 128-byte line): 368 -> 273 us on the gates matrix, 257 -> 188 us on the experts
+//           matrix, same bits (profiles/moe_update_lines_ab.txt).
 // Under data parallelism the factors of all ranks are all-gathered (14 MB per rank) instead of all-reducing
 // the 386 MB gradient; the contraction then simply runs over world x batch rows.
 // ===========================================================================
@@ -309,13 +313,20 @@ __global__ __launch_bounds__(Cfg::NT, 2) void moe_update_kernel(GemmOperandsT p,
   // 8 x (load latency + store acknowledge) per workgroup; issued up front they overlap - 3.4 -> see DESIGN.md).
   // The weights themselves are asked for BEFORE the factor product: they do not depend on it, and their HBM
   // latency then runs under the 8-step loop instead of after it.
-  float4 pv[Cfg::MI][Cfg::NI];
+  // PASS 1 reads them in the accumulator layout (its sums run in that order); PASS 2 reads, computes and writes ROW-MAJOR: thread t
+  // owns, in round i, the 4 consecutive k at (row i * RROWS + t / LPR, column (t % LPR) * 4) of the tile, so a wave-instruction covers
+  // whole rows of the tile - 512 contiguous bytes of p, m, v, 256 of a bf16 image - instead of 16 rows x 64 bytes.
+  constexpr int LPR = Cfg::BU / 4, RROWS = Cfg::NT / LPR, ROUNDS = Cfg::BM / RROWS;   // 32 lanes per row, 16 rows per round, 8 rounds
+  static_assert(Cfg::MI * Cfg::NI == ROUNDS && Cfg::NT % LPR == 0 && Cfg::BM % RROWS == 0, "row-major rounds must cover the tile");
+  const int rrow = threadIdx.x / LPR, rcol = (threadIdx.x % LPR) * 4;
+  float4 pv[Cfg::MI * Cfg::NI];
 #pragma unroll
   for (int mi = 0; mi < Cfg::MI; ++mi)
 #pragma unroll
     for (int ni = 0; ni < Cfg::NI; ++ni) {
-      const int vr = m0 + tc.row0 + mi * 16, k = n0 + tc.unit0 + ni * 16;
-      pv[mi][ni] = (vr < u.V && k < K) ? ld_stream_moe(u.p + (long)vr * K + k) : make_float4(0.f, 0.f, 0.f, 0.f);
+      const int i = mi * Cfg::NI + ni;
+      const int vr = PASS == 1 ? m0 + tc.row0 + mi * 16 : m0 + i * RROWS + rrow, k = PASS == 1 ? n0 + tc.unit0 + ni * 16 : n0 + rcol;
+      pv[i] = (vr < u.V && k < K) ? ld_stream_moe(u.p + (long)vr * K + k) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
   gemm_mainloop_tn<Cfg, true>(p, m0, n0, lds_dyn, acc);
   if (PASS == 1) {
@@ -327,7 +338,8 @@ __global__ __launch_bounds__(Cfg::NT, 2) void moe_update_kernel(GemmOperandsT p,
       for (int ni = 0; ni < Cfg::NI; ++ni) {
         const int k = n0 + tc.unit0 + ni * 16;
         if (vr >= u.V || k >= K) continue;
-        const float pa[4] = {pv[mi][ni].x, pv[mi][ni].y, pv[mi][ni].z, pv[mi][ni].w};
+        const float4 pq = pv[mi * Cfg::NI + ni];
+        const float pa[4] = {pq.x, pq.y, pq.z, pq.w};
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const float w = acc[mi][0][ni][r] + u.l2 * pa[r];
@@ -351,48 +363,72 @@ __global__ __launch_bounds__(Cfg::NT, 2) void moe_update_kernel(GemmOperandsT p,
     }
     return;
   }
-  float4 mv[Cfg::MI][Cfg::NI], vv[Cfg::MI][Cfg::NI];
+  float4 mv[ROUNDS], vv[ROUNDS];
 #pragma unroll
-  for (int mi = 0; mi < Cfg::MI; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < Cfg::NI; ++ni) {
-      const int vr = m0 + tc.row0 + mi * 16, k = n0 + tc.unit0 + ni * 16;
-      const bool ok = vr < u.V && k < K;
-      mv[mi][ni] = ok ? ld_stream_moe(u.m + (long)vr * K + k) : make_float4(0.f, 0.f, 0.f, 0.f);
-      vv[mi][ni] = ok ? ld_stream_moe(u.v + (long)vr * K + k) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+  for (int i = 0; i < ROUNDS; ++i) {
+    const int vr = m0 + i * RROWS + rrow, k = n0 + rcol;
+    const bool ok = vr < u.V && k < K;
+    mv[i] = ok ? ld_stream_moe(u.m + (long)vr * K + k) : make_float4(0.f, 0.f, 0.f, 0.f);
+    vv[i] = ok ? ld_stream_moe(u.v + (long)vr * K + k) : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
   float scale = 1.f;
   if (u.clip > 0.f) scale = u.clip / fmaxf(sqrtf(u.sums[0]), u.clip);      // tf.clip_by_norm
   float wsq = 0.f;                                     // sum of the NEW weights squared (the next update's |W|^2: evc_moe_grad_norms)
-  __syncthreads();                                     // every wave is done with the ring: reuse it for the transpose
-  constexpr int PITCH = Cfg::BM + 8;                   // bf16 elements per k row of the [BU k][BM v] image (+16 B: bank spread)
-  bf16_t* tile = (bf16_t*)lds_dyn;
-  static_assert((long)Cfg::BU * PITCH * 2 <= Cfg::LDS_BYTES, "transpose image must fit the ring");
+  // The gradient tile changes layout through the (idle) ring, one wave row (WM tile rows) at a time: its waves lay their accumulators
+  // down as an f32 image gbuf [WM][GP], all waves pick them up row-major, and - for wsq, whose sum keeps its accumulator-layout order -
+  // put the new weights back in the same places for the owners to read.  The bf16 transpose image [BU k][BM v] sits behind gbuf.
+  constexpr int GP = Cfg::BU + 4;                      // floats per gbuf row (+16 B: bank spread, as in store_tile_via_lds)
+  constexpr int TP = Cfg::BM + 2;                      // bf16 per k row of the transpose image: 65 dwords, so the 4 k of a lane and the 32
+                                                       // lanes of a row spread over the banks (a multiple of 4 dwords puts them on two)
+  constexpr int G_BYTES = Cfg::WM * GP * 4, T_BYTES = Cfg::BU * TP * 2;
+  static_assert(G_BYTES % 16 == 0 && T_BYTES % 4 == 0 && G_BYTES + T_BYTES + (Cfg::NT / 64) * 4 <= Cfg::LDS_BYTES, "staging must fit the ring");
+  static_assert(Cfg::WM % RROWS == 0 && Cfg::WR * Cfg::WM == Cfg::BM, "a wave row is a whole number of row-major rounds");
+  constexpr int RPH = Cfg::WM / RROWS;                 // rounds per wave row
+  float* gbuf = (float*)lds_dyn;
+  bf16_t* tile = (bf16_t*)(lds_dyn + G_BYTES);
+  float* red = (float*)(lds_dyn + G_BYTES + T_BYTES);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int wr = wave / Cfg::WC;
+  const int arow = lane & 15;                          // accumulator layout inside gbuf: row mi * 16 + arow, columns tc.unit0 + ni * 16 ..
 #pragma unroll
-  for (int mi = 0; mi < Cfg::MI; ++mi) {
-    const int vl = tc.row0 + mi * 16, vr = m0 + vl;
+  for (int h = 0; h < Cfg::WR; ++h) {
+    __syncthreads();                                   // h == 0: every wave is done with the ring; later: gbuf has been read
+    if (wr == h) {
 #pragma unroll
-    for (int ni = 0; ni < Cfg::NI; ++ni) {
-      const int kl = tc.unit0 + ni * 16, k = n0 + kl;
+      for (int mi = 0; mi < Cfg::MI; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < Cfg::NI; ++ni) {
+          const f32x4 a = acc[mi][0][ni];
+          *(float4*)(gbuf + (mi * 16 + arow) * GP + tc.unit0 + ni * 16) = make_float4(a[0], a[1], a[2], a[3]);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < RPH; ++j) {
+      const int i = h * RPH + j;
+      const int vl = i * RROWS + rrow, vr = m0 + vl, k = n0 + rcol;
+      float* gp = gbuf + (j * RROWS + rrow) * GP + rcol;
       bf16_t pb[4] = {0, 0, 0, 0};
       if (vr < u.V && k < K) {
         const long o = (long)vr * K + k;
-        const float pa[4] = {pv[mi][ni].x, pv[mi][ni].y, pv[mi][ni].z, pv[mi][ni].w};
-        const float ma[4] = {mv[mi][ni].x, mv[mi][ni].y, mv[mi][ni].z, mv[mi][ni].w};
-        const float va[4] = {vv[mi][ni].x, vv[mi][ni].y, vv[mi][ni].z, vv[mi][ni].w};
+        const float4 gq = *(const float4*)gp;
+        const float ga[4] = {gq.x, gq.y, gq.z, gq.w};
+        const float pa[4] = {pv[i].x, pv[i].y, pv[i].z, pv[i].w};
+        const float ma[4] = {mv[i].x, mv[i].y, mv[i].z, mv[i].w};
+        const float va[4] = {vv[i].x, vv[i].y, vv[i].z, vv[i].w};
         float pn[4], mn[4], vn[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {                 // same operation order as clip_adam_kernel
-          const float gc = (acc[mi][0][ni][r] + u.l2 * pa[r]) * scale;
+          const float gc = (ga[r] + u.l2 * pa[r]) * scale;
           mn[r] = u.b1 * ma[r] + (1.f - u.b1) * gc;
           vn[r] = u.b2 * va[r] + (1.f - u.b2) * gc * gc;
           pn[r] = adam_step_(pa[r], mn[r], vn[r], u.lr_t, u.eps);
           pb[r] = f32_to_bf16(pn[r]);
-          wsq += pn[r] * pn[r];
         }
         st_stream_moe(u.p + o, pn[0], pn[1], pn[2], pn[3]);
         st_stream_moe(u.m + o, mn[0], mn[1], mn[2], mn[3]);
         st_stream_moe(u.v + o, vn[0], vn[1], vn[2], vn[3]);
+        if (u.wsq_partial) *(float4*)gp = make_float4(pn[0], pn[1], pn[2], pn[3]);
         if (u.p_bf16) {
           const u32x2_t sb = {(uint32_t)pb[0] | ((uint32_t)pb[1] << 16), (uint32_t)pb[2] | ((uint32_t)pb[3] << 16)};
           *(u32x2_t*)(u.p_bf16 + o) = sb;
@@ -423,26 +459,38 @@ __global__ __launch_bounds__(Cfg::NT, 2) void moe_update_kernel(GemmOperandsT p,
         }
       }
 #pragma unroll
-      for (int r = 0; r < 4; ++r) tile[(kl + r) * PITCH + vl] = pb[r];
+      for (int r = 0; r < 4; ++r) tile[(rcol + r) * TP + vl] = pb[r];
+    }
+    __syncthreads();                                   // gbuf holds the new weights of this wave row, the transpose image its columns
+    if (u.wsq_partial && wr == h) {                    // (kernel-uniform / wave-uniform)
+#pragma unroll
+      for (int mi = 0; mi < Cfg::MI; ++mi) {
+        const int vr = m0 + tc.row0 + mi * 16;
+#pragma unroll
+        for (int ni = 0; ni < Cfg::NI; ++ni) {
+          const int k = n0 + tc.unit0 + ni * 16;
+          if (vr >= u.V || k >= K) continue;
+          const float4 q = *(const float4*)(gbuf + (mi * 16 + arow) * GP + tc.unit0 + ni * 16);
+          const float pn[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+          for (int r = 0; r < 4; ++r) wsq += pn[r] * pn[r];
+        }
+      }
     }
   }
-  __syncthreads();
-  // rows k of the transposed shadow: 4 bf16 per lane, BM/4 lanes per row, 64/(BM/4) rows per wave-instruction
-  constexpr int LPR = Cfg::BM / 4, RPW = 64 / LPR;
-  static_assert(LPR <= 64 && 64 % LPR == 0, "row of the transposed image must fit a wave");
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int v4 = m0 + (lane % LPR) * 4;
-  for (int kl = wave * RPW + lane / LPR; kl < Cfg::BU; kl += (Cfg::NT / 64) * RPW) {
+  // rows k of the transposed shadow: 4 bf16 per lane, BM/4 lanes per row (256 contiguous bytes), 64/(BM/4) rows per wave-instruction
+  constexpr int TLPR = Cfg::BM / 4, RPW = 64 / TLPR;
+  static_assert(TLPR <= 64 && 64 % TLPR == 0, "row of the transposed image must fit a wave");
+  const int v4 = m0 + (lane % TLPR) * 4;
+  for (int kl = wave * RPW + lane / TLPR; kl < Cfg::BU; kl += (Cfg::NT / 64) * RPW) {
     const int k = n0 + kl;
     if (k >= K || v4 >= u.V) continue;                 // V % 4 == 0: a lane's 4 rows are all valid or all not
-    const uint2 q = *(const uint2*)(tile + kl * PITCH + (lane % LPR) * 4);
-    *(uint2*)(u.pT_bf16 + (long)k * u.ldT + v4) = q;
+    const uint32_t* src = (const uint32_t*)(tile + kl * TP + (lane % TLPR) * 4);     // (4-byte aligned: TP is not a multiple of 4)
+    *(uint2*)(u.pT_bf16 + (long)k * u.ldT + v4) = make_uint2(src[0], src[1]);
   }
   if (u.wsq_partial) {                                 // per-workgroup partial, summed in a fixed order by moe_update_finalize_kernel
     wsq = wave_sum(wsq);
-    __syncthreads();                                   // the transpose image has been read
-    float* red = (float*)lds_dyn;
-    if ((threadIdx.x & 63) == 0) red[wave] = wsq;
+    if (lane == 0) red[wave] = wsq;                    // (its own corner of the ring: nothing to wait for)
     __syncthreads();
     if (threadIdx.x == 0) {
       float a = 0.f;
