@@ -23,6 +23,7 @@ single-device gradient at the global batch; L_PRED is a batch *sum*
 """
 from __future__ import annotations
 
+import dataclasses
 import math
 import os
 
@@ -32,7 +33,7 @@ import torch
 from . import losses as losses_mod
 from . import ops
 from .streams import concurrent_streams
-from .engine import HLstmTower
+from .engine import HLstmTower, drain
 
 F32 = torch.float32
 
@@ -361,72 +362,239 @@ def input_image_args(*towers):
     return dict(f16_segments=max(t.f16_x_segments for t in tw))
 
 
-def scored_sampling(g):
-    """Whether graph ``g``'s student takes its frames by their content (ops.STUDENT_SAMPLING_SCORED): its table needs ops.frame_change_keys."""
-    return getattr(g, "student", None) is not None and getattr(g, "student_sampling", "uniform") in ops.STUDENT_SAMPLING_SCORED
+@dataclasses.dataclass(slots=True)
+class FramePlan:
+    """What frame_counts_and_plans / input_views / scored_sampling read, for the tower or towers that take their input in one pass: every field
+    is declared here with its default, and a misspelt one raises (slots).  `sampling_draw` / `sampling_row0` are set per step by the owner."""
+    teacher: object = None
+    student: object = None
+    every_n: int = 1
+    C1: int = 20
+    C2: int = 5
+    max_frames: int = 300
+    row_plans: bool = True
+    student_sampling: str = "uniform"          # ops.STUDENT_SAMPLING
+    sampling_seed: int = 0
+    sampling_draw: int = 0
+    sampling_row0: int = 0
+    last_frame_table: object = None            # the source-frame table of the last batch (a student off the uniform grid), for tests and diagnostics
+
+    @property
+    def S(self):
+        return self.max_frames // self.every_n
 
 
-def input_views(g, x_raw, num_frames, tp, sp, need_student, keys=None):
-    """The L1 input images of graph ``g``'s towers for one batch (ops.l2norm_chunk): (teacher view, student view), each the plain bf16 image or - in
+def scored_sampling(p):
+    """Whether the student of FramePlan ``p`` takes its frames by their content (ops.STUDENT_SAMPLING_SCORED): its table needs ops.frame_change_keys."""
+    return p.student is not None and p.student_sampling in ops.STUDENT_SAMPLING_SCORED
+
+
+def input_views(p, x_raw, num_frames, tp, sp, need_student, keys=None):
+    """The L1 input images of FramePlan ``p``'s towers for one batch (ops.l2norm_chunk): (teacher view, student view), each the plain bf16 image or - in
     the non-bf16 modes - a tuple (bf16 image, second image[, row scales]).  uint8 frames into "high" towers whose layer 0 is on the f16 + e4m3 form
     take the INTEGER-frame images (ops.l2norm_chunk_int, HLstmTower.x_int: the input exact, round 6).  ``keys``: the batch's
     ops.frame_change_keys where the owner of several graphs on one batch has computed them already (only read under a scored word)."""
-    towers = [t for t in (g.teacher, g.student if need_student else None) if t is not None]
+    towers = [t for t in (p.teacher, p.student if need_student else None) if t is not None]
     p1, p2 = (tp[2] if tp else None), (sp[3] if sp else None)
     as_int = x_raw.dtype == torch.uint8 and towers and all(t.precision == "high" and t.x_int() for t in towers)
     nf = num_frames if x_raw.dtype == torch.uint8 else None
-    if need_student and getattr(g, "student_sampling", "uniform") != "uniform":
+    if need_student and p.student_sampling != "uniform":
         # A student on other frames than the grid s * every_n (--student_sampling): the teacher view as ever, without a student view, then the
         # student view from the table of its source frames + the gathering pass, on the same stream.  The image forms are the ones the shared
         # call would have produced (decided over both towers), the frame counts and row plans do not depend on which frames are taken.
-        img = input_image_args(g.teacher, g.student)
+        img = input_image_args(p.teacher, p.student)
         xt = None
-        if g.teacher is not None:
+        if p.teacher is not None:
             if as_int:
-                xt = ops.l2norm_chunk_int(x_raw, num_frames, g.C1, None, g.C2, plan1=p1)[0]
+                xt = ops.l2norm_chunk_int(x_raw, num_frames, p.C1, None, p.C2, plan1=p1)[0]
             else:
-                xt = ops.l2norm_chunk(x_raw, g.C1, None, g.C2, num_frames=nf, split=towers[0].input_split(), plan1=p1, **img)[0]
-        if g.student_sampling in ops.STUDENT_SAMPLING_SCORED:      # by content: one key per raw frame on this stream, then the ranking table
+                xt = ops.l2norm_chunk(x_raw, p.C1, None, p.C2, num_frames=nf, split=towers[0].input_split(), plan1=p1, **img)[0]
+        if p.student_sampling in ops.STUDENT_SAMPLING_SCORED:      # by content: one key per raw frame on this stream, then the ranking table
             if keys is None:
                 keys = ops.frame_change_keys(x_raw, num_frames)
-            src = ops.student_frame_select_scored(num_frames, keys, g.max_frames, g.every_n, g.student_sampling)
+            src = ops.student_frame_select_scored(num_frames, keys, p.max_frames, p.every_n, p.student_sampling)
         else:
-            src = ops.student_frame_select(num_frames, g.max_frames, g.every_n, g.student_sampling, seed=g.sampling_seed,
-                                           draw=getattr(g, "sampling_draw", 0), row0=getattr(g, "sampling_row0", 0))
-        g.last_frame_table = src          # (the table of the last batch, for whoever wants to look: tests, diagnostics)
+            src = ops.student_frame_select(num_frames, p.max_frames, p.every_n, p.student_sampling, seed=p.sampling_seed,
+                                           draw=p.sampling_draw, row0=p.sampling_row0)
+        p.last_frame_table = src
         if as_int:
-            return xt, ops.l2norm_chunk_int_sel(x_raw, num_frames, src, g.every_n, g.C2, plan2=p2)
-        return xt, ops.l2norm_chunk_sel(x_raw, src, g.every_n, g.C2, num_frames=nf, split=towers[0].input_split(), plan2=p2, **img)
+            return xt, ops.l2norm_chunk_int_sel(x_raw, num_frames, src, p.every_n, p.C2, plan2=p2)
+        return xt, ops.l2norm_chunk_sel(x_raw, src, p.every_n, p.C2, num_frames=nf, split=towers[0].input_split(), plan2=p2, **img)
     if as_int:
-        return ops.l2norm_chunk_int(x_raw, num_frames, g.C1, g.every_n if need_student else None, g.C2, plan1=p1, plan2=p2, teacher_view=g.teacher is not None)
-    return ops.l2norm_chunk(x_raw, g.C1, g.every_n if need_student else None, g.C2, num_frames=nf,
-                            split=towers[0].input_split(), plan1=p1, plan2=p2, teacher_view=g.teacher is not None,
-                            **input_image_args(g.teacher, g.student if need_student else None))
+        return ops.l2norm_chunk_int(x_raw, num_frames, p.C1, p.every_n if need_student else None, p.C2, plan1=p1, plan2=p2, teacher_view=p.teacher is not None)
+    return ops.l2norm_chunk(x_raw, p.C1, p.every_n if need_student else None, p.C2, num_frames=nf,
+                            split=towers[0].input_split(), plan1=p1, plan2=p2, teacher_view=p.teacher is not None,
+                            **input_image_args(p.teacher, p.student if need_student else None))
 
 
-def frame_counts_and_plans(g, num_frames, nh, need_teacher, need_student):
-    """Frame counts (device) and the L1 row plans of both towers of graph ``g`` (DistillGraph / EvalGraph): rows
+def frame_counts_and_plans(p, num_frames, nh, need_teacher, need_student):
+    """Frame counts (device) and the L1 row plans of FramePlan ``p``'s towers: rows
     sorted by length so the padding rows drop out of every L1 kernel (ops.RowPlan).  Host twins of the counts
     give the launch geometry.  Returns ((len_l1, len_l2, plan) | None, (n_student, len_l1, len_l2, plan) | None)."""
     t = s = None
     if need_teacher:
-        _, l1, l2 = ops.frame_counts(num_frames, 1, g.C1, g.max_frames // g.C1, g.max_frames)
+        _, l1, l2 = ops.frame_counts(num_frames, 1, p.C1, p.max_frames // p.C1, p.max_frames)
         plan = None
-        if g.row_plans:
-            _, l1h, _ = ops.host_frame_counts(nh, 1, g.C1, g.max_frames // g.C1, g.max_frames)
-            plan = ops.RowPlan(l1, l1h, g.max_frames // g.C1)
+        if p.row_plans:
+            _, l1h, _ = ops.host_frame_counts(nh, 1, p.C1, p.max_frames // p.C1, p.max_frames)
+            plan = ops.RowPlan(l1, l1h, p.max_frames // p.C1)
         t = (l1, l2, plan)
     if need_student:
-        n_s, l1s, l2s = ops.frame_counts(num_frames, g.every_n, g.C2, g.S // g.C2, g.max_frames, subsampled=True)
+        n_s, l1s, l2s = ops.frame_counts(num_frames, p.every_n, p.C2, p.S // p.C2, p.max_frames, subsampled=True)
         plan = None
-        if g.row_plans:
-            _, l1h, _ = ops.host_frame_counts(nh, g.every_n, g.C2, g.S // g.C2, g.max_frames, subsampled=True)
-            plan = ops.RowPlan(l1s, l1h, g.S // g.C2)
+        if p.row_plans:
+            _, l1h, _ = ops.host_frame_counts(nh, p.every_n, p.C2, p.S // p.C2, p.max_frames, subsampled=True)
+            plan = ops.RowPlan(l1s, l1h, p.S // p.C2)
         s = (n_s, l1s, l2s, plan)
     return t, s
 
 
-class DistillGraph:
+class _StepGraph:
+    """What every graph's step is built from: the learning rate, the entry onto the graph's own main stream, the keep-alive of tensors
+    that cross streams (SingleTowerGraph takes the learning rate alone)."""
+
+    world = 1
+    debug_marks = None      # set to a list to collect (name, timing event) pairs of one step (scripts/step_marks.py)
+
+    def _mark(self, name, stream):
+        if self.debug_marks is not None:
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record(stream)
+            self.debug_marks.append((name, ev))
+
+    def _lr_l2c(self, batch_size):
+        """(learning rate of this iteration - every train op of it reads the same global_step, cs/train.py:223-236 -, weight of the l2 term)."""
+        return (exponential_decay(self.lr0, self.global_step, batch_size * self.world, self.lr_decay_examples, self.lr_decay),
+                self.reg_pen * 1e-8)
+
+    def _on_main(self, inputs, num_frames_host, body):
+        """Runs ``body(host frame counts)`` on the graph's own main stream, ordered after the caller's current stream on entry
+        and before it on exit (so callers see ordinary single-stream semantics).  ``inputs``: the caller's tensors the step reads
+        (the first three are x_raw, labels_u8, num_frames; None entries are skipped).
+
+        num_frames_host: the same frame counts on the host (numpy / CPU tensor / list), as the input pipeline
+        has them before the H2D copy.  The launch geometry of the row-planned L1 stacks depends on them; without
+        it they are read back from the device, which stalls the host on everything queued before."""
+        if num_frames_host is None:
+            num_frames_host = inputs[2].cpu()
+        nh = np.asarray(num_frames_host, dtype=np.int64).reshape(-1)
+        caller = torch.cuda.current_stream(self.device)
+        if caller == self._main:
+            return body(nh)
+        self._main.wait_stream(caller)
+        with torch.cuda.stream(self._main):
+            out = body(nh)
+        for t in inputs:
+            if t is not None:
+                t.record_stream(self._main)
+        caller.wait_stream(self._main)
+        return out
+
+    @staticmethod
+    def _keep_alive(stream, views, plans):
+        """The students' input views and plan tuples (n, len_l1, len_l2, row plan): allocated on `main`, consumed on ``stream``."""
+        for xs, sp in zip(views, plans):
+            used = (xs if isinstance(xs, tuple) else (xs,)) + sp[:3]
+            if sp[3] is not None:
+                used += (sp[3].pos, sp[3].inv, sp[3].lens)
+            for t in used:
+                if t is not None:
+                    t.record_stream(stream)
+
+
+class _TrainGraph(_StepGraph):
+    """The training graphs over H-LSTM towers (DistillGraph, SerialStudentsGraph): their streams, the deferred updates, and the step
+    against a frozen teacher.  A subclass names its towers (_towers) and counts its train ops (_apply_gradients)."""
+
+    def _make_streams(self):
+        """Four streams that measurably overlap (streams.py) - the step never runs on the default stream - and the step's events."""
+        self._opt_t = self._opt_s = None
+        if self.device.type != "cuda":
+            return
+        self._main, self._side, self._aux_t, self._aux_s = concurrent_streams(self.device, 4)
+        if os.environ.get("EVC_SINGLE_STREAM") == "1":     # profiling aid: the same launches, all on ONE stream (solo kernel times)
+            self._side = self._aux_t = self._aux_s = self._main
+        # experiment (DESIGN.md 5): the optimizer launches on a CU-masked stream of their own - EVC_OPT_CU_MASK=<CUs per XCD>[:<first>]
+        m = os.environ.get("EVC_OPT_CU_MASK")
+        if m:
+            from .streams import cu_masked_stream
+            f = [int(v) for v in m.split(":")]
+            self._opt_t = self._opt_s = cu_masked_stream(self.device, f[0], f[1] if len(f) > 1 else 0)      # (shared by both towers)
+        self._ev_fwd, self._ev_student, self._ev_in = torch.cuda.Event(), torch.cuda.Event(), torch.cuda.Event()
+
+    def flush(self):
+        """Enqueue and join the deferred updates of the last step (defer_updates): afterwards every weight, moment and operand
+        shadow of every tower is current in the order of the caller's stream.  Cheap no-op when nothing is pending."""
+        if self.device.type != "cuda":
+            return
+        cur = torch.cuda.current_stream(self.device)
+        for tw in self._towers():
+            tw.wait_deferred(cur)
+
+    def apply_gradients(self, batch_size, lr=None):
+        """Runs whichever train op has not been applied inside step() and counts global_step on (_apply_gradients)."""
+        self.flush()
+        self._apply_gradients(batch_size, lr)
+
+    def _serial_step(self, students, xt, tp, xss, sps, labels_u8, dps, apply, loss_section):
+        """One iteration of ``students`` against the frozen teacher, after the input stage (teacher view ``xt`` and plan ``tp``, per
+        student a view, a plan tuple and a dL/dpred buffer).  Returns `out`, the students' dicts as the list out["students"].
+
+        Schedule: the teacher's forward (tape-free, the step's longest chain) ONCE on `main`, the students' forwards next to it on
+        `side` from the start of the step, one after the other - neither reads the other -; ``loss_section(t_state, t_pred, fwd, ds)``
+        on `side` once all forwards are done (one launch + its finish, every dpred / dstate written once); then each student's backward
+        and update exactly as in mode "student" (aux stream, early apply, defer_updates), student after student; `main` joins at the
+        end.  The teacher's backward, weight gradients, update and tape of the parallel step do not exist here."""
+        B = labels_u8.shape[0]
+        main = torch.cuda.current_stream(self.device)
+        for s in students:
+            s.run_deferred()
+        self.losses.zero_()
+        mark = self._mark
+        mark("start", main)
+        lr, l2c = self._lr_l2c(B)
+        two_streams = self.overlap_towers
+        side = self._side if two_streams else main
+        l1, l2, plan_t = tp
+        if two_streams:
+            self._ev_in.record(main)
+            side.wait_event(self._ev_in)
+        t_state, t_pred = self.teacher.forward(xt, l1, l2, plan_t)
+        mark("teacher_fwd_done", main)
+        if two_streams:
+            self._ev_fwd.record(main)
+        with torch.cuda.stream(side):
+            mark("student_start", side)
+            fwd = [s.forward(xs, l1s, l2s, plan_s) for s, xs, (_, l1s, l2s, plan_s) in zip(students, xss, sps)]
+            mark("student_fwd_done", side)
+            if two_streams:
+                side.wait_event(self._ev_fwd)
+            if self._ds_serial is None or self._ds_serial[0].shape != fwd[0][0].shape:
+                self._ds_serial = [torch.empty_like(f[0]) for f in fwd]
+            loss_section(t_state, t_pred, fwd, self._ds_serial)
+            mark("losses_done", side)
+            early_s = (lr, self.clip, l2c) if (apply and self.overlap_towers and self._aux_s is not None) else None
+            for s, ds, dp in zip(students, self._ds_serial, dps):
+                drain(s.backward_phases(ds, dp, aux=self._aux_s if self.overlap_towers else None, early_apply=early_s,
+                                        defer=self.defer_updates, opt=self._opt_s))      # every phase to its end
+            mark("student_done", side)
+            if two_streams:
+                self._ev_student.record(side)
+                self._keep_alive(side, xss, sps)
+        if two_streams:
+            main.wait_event(self._ev_student)
+        rows = self.losses.view(-1, 4)
+        outs = [dict(student_predictions=f[1], student_state=f[0], num_frames_student=sp[0], student_loss_state=rows[k, 1],
+                     pred_loss=rows[k, 2], student_label_loss=rows[k, 3]) for k, (f, sp) in enumerate(zip(fwd, sps))]
+        out = dict(predictions=t_pred, teacher_state=t_state, loss=rows[0, 0], students=outs)
+        self._student_applied = early_s is not None
+        if apply:
+            self._apply_gradients(B, lr)
+        out["global_step"] = self.global_step
+        return out
+
+
+class DistillGraph(_TrainGraph):
     """mode: 'teacher_student' (train.py), 'teacher' (teacher only, BASELINE cfg 2),
     'student' (train_finetune.py), 'serial' (the paper's Serial training: the student against a FROZEN teacher -
     forward-only 'model' tower, no tape / gradient / Adam state, never written; one train op)."""
@@ -485,8 +653,7 @@ class DistillGraph:
                 self.teacher.store.drop_training_state()
         if mode != "teacher":
             validate_every_n(every_n, num_inputs_l1_student, max_frames)
-            self.S = max_frames // every_n
-            self.student = HLstmTower(batch_size, self.S, num_inputs_l1_student, feature_size, vocab_size, lstm_cells,
+            self.student = HLstmTower(batch_size, max_frames // every_n, num_inputs_l1_student, feature_size, vocab_size, lstm_cells,
                                       lstm_layers, num_mixtures, device, True, "model_student", seed + 1)
         if self.dp:                      # row-shard the MoE optimizer state now, while nothing is in flight on any stream
             for tw, red in ((self.teacher, self.reducer), (self.student, self.reducer_s)):
@@ -495,15 +662,17 @@ class DistillGraph:
         self.precision = precision       # engine.TowerBase.precision: "bf16" | "high" (1e-3 at trained magnitudes) | "split" (uniform)
         student_light(self.student, precision)
         if precision != "bf16":
-            for tw in (self.teacher, self.student):
-                if tw is not None:
-                    tw.set_precision(precision)
+            for tw in self._towers():
+                tw.set_precision(precision)
+        # both towers take their input in one pass; row_plans: sort the L1 chunk rows by length and skip the padding rows (ops.RowPlan)
+        # (the uniform split-bf16 layers run on every row)
+        self.frames = FramePlan(self.teacher, self.student, every_n, self.C1, self.C2, max_frames, precision != "split",
+                                self.student_sampling, self.sampling_seed)
         self.losses = torch.zeros(8, dtype=F32, device=self.device)
         self._losses_reduced = torch.zeros(8, dtype=F32, device=self.device)   # data parallel: SUM over the ranks, per step
-        self._dp_t = self._dp_s = self._ds_s = None
+        self._dp_t = self._dp_s = self._ds_s = self._ds_serial = None
+        self._teacher_applied = self._student_applied = False
         self.overlap_towers = overlap_towers
-        self.row_plans = precision != "split"   # sort the L1 chunk rows by length and skip the padding rows (ops.RowPlan);
-        # (the uniform split-bf16 layers run on every row)
         # True: the student's forward starts next to the teacher's forward instead of after it.  Measured 0.1 ms/step
         # faster, but the teacher's fused forward steps then share the chip (67 -> 84 us per launch): off by default so
         # that the step's dominant kernel runs - and is measured - alone.
@@ -520,29 +689,23 @@ class DistillGraph:
         self.issue_order = os.environ.get("EVC_ISSUE_ORDER", "interleaved" if (self.dp and serial_comm()) else "sequential")
         if self.issue_order not in self.ISSUE_ORDERS:
             raise ValueError("EVC_ISSUE_ORDER must be one of %s" % sorted(self.ISSUE_ORDERS))
-        self._opt_t = self._opt_s = None
-        if self.device.type == "cuda":
-            # four streams that measurably overlap (streams.py); the step never runs on the default stream
-            self._main, self._side, self._aux_t, self._aux_s = concurrent_streams(self.device, 4)
-            if os.environ.get("EVC_SINGLE_STREAM") == "1":     # profiling aid: the same launches, all on ONE stream (solo kernel times)
-                self._side = self._aux_t = self._aux_s = self._main
-            # experiment: the optimizer launches on a CU-masked stream of their own - EVC_OPT_CU_MASK=<CUs per XCD>[:<first>]
-            m = os.environ.get("EVC_OPT_CU_MASK")
-            if m:
-                from .streams import cu_masked_stream
-                f = [int(v) for v in m.split(":")]
-                self._opt_t = cu_masked_stream(self.device, f[0], f[1] if len(f) > 1 else 0)
-                self._opt_s = self._opt_t          # (both towers' optimizer launches share the masked stream)
-            # Single-tower graphs (cfg 2 teacher only, cfg 5 student only) use two of the four streams: the tower's collectives + optimizer launches
-            # take a THIRD one (the other tower's idle aux stream) instead of queueing on the aux stream between the weight-gradient products - under
-            # data parallelism that stream is the step's critical path and every byte on the wire was exposed (cfg 5 as rank 0 of 8 with stand-in
-            # collectives at 300 GB/s: 5.67 ms; profiles/r06_dp_sim_world.txt).  Under data parallelism only.
-            if self.dp and os.environ.get("EVC_SINGLE_STREAM") != "1" and not m:
-                if mode == "student":
-                    self._opt_s = self._aux_t
-                elif mode == "teacher":
-                    self._opt_t = self._aux_s
-            self._ev_fwd, self._ev_student, self._ev_in = torch.cuda.Event(), torch.cuda.Event(), torch.cuda.Event()
+        self._make_streams()
+        # Single-tower graphs (cfg 2 teacher only, cfg 5 student only) use two of the four streams: the tower's collectives + optimizer launches
+        # take a THIRD one (the other tower's idle aux stream) instead of queueing on the aux stream between the weight-gradient products - under
+        # data parallelism that stream is the step's critical path and every byte on the wire was exposed (cfg 5 as rank 0 of 8 with stand-in
+        # collectives at 300 GB/s: 5.67 ms; profiles/r06_dp_sim_world.txt).  Under data parallelism only.
+        if self.device.type == "cuda" and self.dp and os.environ.get("EVC_SINGLE_STREAM") != "1" and self._opt_t is None:
+            if mode == "student":
+                self._opt_s = self._aux_t
+            elif mode == "teacher":
+                self._opt_t = self._aux_s
+
+    S = property(lambda self: self.frames.S)
+    last_frame_table = property(lambda self: self.frames.last_frame_table)
+    row_plans = property(lambda self: self.frames.row_plans, lambda self, on: setattr(self.frames, "row_plans", on))
+
+    def _towers(self):
+        return [tw for tw in (self.teacher, self.student) if tw is not None]
 
     # ---- data-parallel gradient reduction -------------------------------------
     def _reduce_tower(self, tower, moe_first):
@@ -552,10 +715,6 @@ class DistillGraph:
             self.reducer.reduce(st.grad, moe_lo, st.total, f32=True)
         else:
             self.reducer.reduce(st.grad, 0, moe_lo, f32=False)
-
-    def _label_loss(self, pred, labels_u8, loss, dpred=None, grad_scale=1.0):
-        """The label loss of one tower: CrossEntropyLoss issues ops.ce_loss, any other loss ops.label_loss with the same arguments."""
-        self.label_loss.fused(pred, labels_u8, loss, dpred, grad_scale=grad_scale)
 
     def label_grads(self):
         """The dL/dpred buffers the last step filled ({"teacher": ..., "student": ...}, whichever exist; the student's holds its label
@@ -569,33 +728,9 @@ class DistillGraph:
 
     # ---- one training iteration -----------------------------------------------
     def step(self, x_raw, labels_u8, num_frames, apply=True, num_frames_host=None):
-        """Runs ``_step`` on the graph's own main stream, ordered after the caller's current stream on entry
-        and before it on exit (so callers see ordinary single-stream semantics).
-
-        num_frames_host: the same frame counts on the host (numpy / CPU tensor / list), as the input pipeline
-        has them before the H2D copy.  The launch geometry of the row-planned L1 stacks depends on them; without
-        it they are read back from the device, which stalls the host on everything queued before."""
-        if num_frames_host is None:
-            num_frames_host = num_frames.cpu()
-        nh = np.asarray(num_frames_host, dtype=np.int64).reshape(-1)
-        caller = torch.cuda.current_stream(self.device)
-        if caller == self._main:
-            return self._step(x_raw, labels_u8, num_frames, apply, nh)
-        self._main.wait_stream(caller)
-        with torch.cuda.stream(self._main):
-            out = self._step(x_raw, labels_u8, num_frames, apply, nh)
-        for t in (x_raw, labels_u8, num_frames):
-            t.record_stream(self._main)
-        caller.wait_stream(self._main)
-        return out
-
-    debug_marks = None      # set to a list to collect (name, timing event) pairs of one step (scripts/step_marks.py)
-
-    def _mark(self, name, stream):
-        if self.debug_marks is not None:
-            ev = torch.cuda.Event(enable_timing=True)
-            ev.record(stream)
-            self.debug_marks.append((name, ev))
+        """One iteration on the graph's own main stream (_on_main: stream semantics, num_frames_host)."""
+        body = self._step_frozen_teacher if self.mode == "serial" else self._step
+        return self._on_main((x_raw, labels_u8, num_frames), num_frames_host, lambda nh: body(x_raw, labels_u8, num_frames, apply, nh))
 
     def _step(self, x_raw, labels_u8, num_frames, apply=True, nh=None):
         """x_raw [B,300,F] f32 (or uint8), labels_u8 [B,V] uint8, num_frames [B] int32.
@@ -606,8 +741,6 @@ class DistillGraph:
         teacher's forward is done (teacher tensors are constants in the student loss), so the
         student runs on a second HIP stream: its many small launches (M = batch L2 steps, 30-frame
         L1) fill the CUs that the teacher's under-filled launches leave idle."""
-        if self.mode == "serial":
-            return self._step_serial(x_raw, labels_u8, num_frames, apply, nh)
         B = x_raw.shape[0]
         V = labels_u8.shape[1]
         dev = self.device
@@ -621,58 +754,53 @@ class DistillGraph:
             self._dp_s = torch.empty((B, V), dtype=F32, device=dev)
         need_student = self.student is not None
         main = torch.cuda.current_stream(dev)
-        tp, sp = frame_counts_and_plans(self, num_frames, nh, self.teacher is not None, need_student)
+        fp = self.frames
+        tp, sp = frame_counts_and_plans(fp, num_frames, nh, self.teacher is not None, need_student)
         # "random" student frames: a new draw per training iteration (global_step counts one per train op, cs/train.py:332,416), other videos
         # on every rank - stateless, so a run is reproducible from its seed and a restored global_step
-        self.sampling_draw = self.global_step // ((self.teacher is not None) + (self.student is not None))
-        self.sampling_row0 = self.reducer.rank * B
-        xt, xs = input_views(self, x_raw, num_frames, tp, sp, need_student)     # (student only: the sub-sampled frames alone are read)
-        for tw in (self.teacher, self.student):     # step k-1's deferred MoE / L2-level updates: now, under this step's L1 forward
-            if tw is not None:
-                tw.run_deferred()
+        fp.sampling_draw = self.global_step // ((self.teacher is not None) + (self.student is not None))
+        fp.sampling_row0 = self.reducer.rank * B
+        xt, xs = input_views(fp, x_raw, num_frames, tp, sp, need_student)     # (student only: the sub-sampled frames alone are read)
+        for tw in self._towers():     # step k-1's deferred MoE / L2-level updates: now, under this step's L1 forward
+            tw.run_deferred()
         self.losses.zero_()
         out = {}
         mark = self._mark
         mark("start", main)
         sc = dp_loss_scales(self.world)
-        # both train ops read the same global_step / learning rate within one iteration (cs/train.py:223-236)
-        lr = exponential_decay(self.lr0, self.global_step, B * self.world, self.lr_decay_examples, self.lr_decay)
-        l2c = self.reg_pen * 1e-8
+        lr, l2c = self._lr_l2c(B)
         self._teacher_applied = self._student_applied = False
         two_streams = self.teacher is not None and need_student and self.overlap_towers
         side = self._side if two_streams else main
         early_student = two_streams and self.student_forward_early
         # "after_l1": the student's forward starts when the teacher's L1 level is done - next to the teacher's L2 chain
         # and MoE head (small launches), not next to its L1 steps (the roofline kernel keeps the chip to itself)
-        mid_student = two_streams and not early_student and self.student_forward_after_l1 and self.teacher is not None and need_student
-        s_state = s_pred = n_s = l1s = l2s = plan_s = gen_s = early_s = None
-        if need_student and early_student:
-            # The student's forward needs only its own inputs and weights: it starts right away, next to the
-            # teacher's forward (whose L2 / MoE tail is a chain of small launches that leaves most CUs idle);
+        mid_student = two_streams and not early_student and self.student_forward_after_l1
+        s_state = s_pred = gen_s = early_s = None
+        n_s, l1s, l2s, plan_s = sp if need_student else (None,) * 4
+
+        def student_forward():                  # (on `side`)
+            nonlocal s_state, s_pred
+            mark("student_start", side)
+            s_state, s_pred = self.student.forward(xs, l1s, l2s, plan_s)
+            self.label_loss.fused(s_pred, labels_u8, self.losses[3:4], self._dp_s, grad_scale=sc["ce"] / B)
+            mark("student_fwd_done", side)
+
+        def student_forward_from_inputs():
+            # The student's forward needs only its own inputs and weights: it can start next to the teacher's forward
+            # (whose L2 / MoE tail is a chain of small launches that leaves most CUs idle);
             # only its distillation losses wait for the teacher's outputs.
             self._ev_in.record(main)
             side.wait_event(self._ev_in)
             with torch.cuda.stream(side):
-                mark("student_start", side)
-                n_s, l1s, l2s, plan_s = sp
-                s_state, s_pred = self.student.forward(xs, l1s, l2s, plan_s)
-                self._label_loss(s_pred, labels_u8, self.losses[3:4], self._dp_s, grad_scale=sc["ce"] / B)
-                mark("student_fwd_done", side)
-        def student_forward_mid():
-            nonlocal s_state, s_pred, n_s, l1s, l2s, plan_s
-            self._ev_in.record(main)
-            side.wait_event(self._ev_in)
-            with torch.cuda.stream(side):
-                mark("student_start", side)
-                n_s, l1s, l2s, plan_s = sp
-                s_state, s_pred = self.student.forward(xs, l1s, l2s, plan_s)
-                self._label_loss(s_pred, labels_u8, self.losses[3:4], self._dp_s, grad_scale=sc["ce"] / B)
-                mark("student_fwd_done", side)
+                student_forward()
 
+        if early_student:
+            student_forward_from_inputs()
         if self.teacher is not None:
             l1, l2, plan_t = tp
-            t_state, t_pred = self.teacher.forward(xt, l1, l2, plan_t, after_l1=student_forward_mid if mid_student else None)
-            self._label_loss(t_pred, labels_u8, self.losses[0:1], self._dp_t, grad_scale=sc["ce"] / B)
+            t_state, t_pred = self.teacher.forward(xt, l1, l2, plan_t, after_l1=student_forward_from_inputs if mid_student else None)
+            self.label_loss.fused(t_pred, labels_u8, self.losses[0:1], self._dp_t, grad_scale=sc["ce"] / B)
             if two_streams:
                 self._ev_fwd.record(main)
             mark("teacher_fwd_done", main)
@@ -681,11 +809,7 @@ class DistillGraph:
                 side.wait_event(self._ev_fwd)
             with torch.cuda.stream(side):
                 if not early_student and not mid_student:
-                    mark("student_start", side)
-                    n_s, l1s, l2s, plan_s = sp
-                    s_state, s_pred = self.student.forward(xs, l1s, l2s, plan_s)
-                    self._label_loss(s_pred, labels_u8, self.losses[3:4], self._dp_s, grad_scale=sc["ce"] / B)
-                    mark("student_fwd_done", side)
+                    student_forward()
                 ds = None
                 if self.teacher is not None:
                     if self._ds_s is None or self._ds_s.shape != s_state.shape:
@@ -739,12 +863,7 @@ class DistillGraph:
                 mark("student_done", side)
                 if two_streams:
                     self._ev_student.record(side)
-                    used = (xs if isinstance(xs, tuple) else (xs,)) + (n_s, l1s, l2s)
-                    if plan_s is not None:
-                        used += (plan_s.pos, plan_s.inv, plan_s.lens)
-                    for t in used:                                          # allocated on `main`, consumed on `side`
-                        if t is not None:
-                            t.record_stream(side)
+                    self._keep_alive(side, [xs], [sp])
             out.update(student_predictions=s_pred, student_state=s_state, num_frames_student=n_s,
                        student_loss_state=self.losses[1], pred_loss=self.losses[2], student_label_loss=self.losses[3])
         if self.teacher is not None:
@@ -766,104 +885,39 @@ class DistillGraph:
         out["global_step"] = self.global_step
         return out
 
-    def _step_serial(self, x_raw, labels_u8, num_frames, apply=True, nh=None):
-        """mode "serial": one iteration of the student against the frozen teacher.  Same inputs and `out` keys as _step.
-
-        Schedule: the teacher's forward (tape-free, the step's longest chain) on `main`, the student's forward next to it on `side`
-        - neither reads the other -; the loss section (ops.distill_losses: one launch + its finish, dpred_s written once) on `side`
-        once both are done; then the student's backward and update exactly as in mode "student".  The teacher's backward, weight
-        gradients, update and tape of the parallel step do not exist here."""
+    def _step_frozen_teacher(self, x_raw, labels_u8, num_frames, apply=True, nh=None):
+        """mode "serial": the input stage of _step (one pass for both towers), then _serial_step for the one student with the loss
+        section ops.distill_losses.  Same inputs and `out` keys as _step."""
         B, V = x_raw.shape[0], labels_u8.shape[1]
-        dev = self.device
         if self._dp_s is None or self._dp_s.shape[0] != B:
-            self._dp_s = torch.empty((B, V), dtype=F32, device=dev)
-        main = torch.cuda.current_stream(dev)
-        tp, sp = frame_counts_and_plans(self, num_frames, nh, True, True)
-        self.sampling_draw = self.global_step          # one train op per iteration: a new "random" draw per step
-        self.sampling_row0 = 0
-        xt, xs = input_views(self, x_raw, num_frames, tp, sp, True)
-        self.student.run_deferred()
-        self.losses.zero_()
-        mark = self._mark
-        mark("start", main)
-        lr = exponential_decay(self.lr0, self.global_step, B, self.lr_decay_examples, self.lr_decay)
-        l2c = self.reg_pen * 1e-8
-        self._teacher_applied = self._student_applied = False
-        two_streams = self.overlap_towers
-        side = self._side if two_streams else main
-        n_s, l1s, l2s, plan_s = sp
-        l1, l2, plan_t = tp
-        if two_streams:
-            self._ev_in.record(main)
-            side.wait_event(self._ev_in)
-        t_state, t_pred = self.teacher.forward(xt, l1, l2, plan_t)
-        mark("teacher_fwd_done", main)
-        if two_streams:
-            self._ev_fwd.record(main)
-        with torch.cuda.stream(side):
-            mark("student_start", side)
-            s_state, s_pred = self.student.forward(xs, l1s, l2s, plan_s)
-            mark("student_fwd_done", side)
-            if two_streams:
-                side.wait_event(self._ev_fwd)
-            if self._ds_s is None or self._ds_s.shape != s_state.shape:
-                self._ds_s = torch.empty_like(s_state)
-            on = self.distill_losses
+            self._dp_s = torch.empty((B, V), dtype=F32, device=self.device)
+        fp = self.frames
+        tp, sp = frame_counts_and_plans(fp, num_frames, nh, True, True)
+        fp.sampling_draw, fp.sampling_row0 = self.global_step, 0          # one train op per iteration: a new "random" draw per step
+        xt, xs = input_views(fp, x_raw, num_frames, tp, sp, True)
+        on = self.distill_losses
+
+        def loss_section(t_state, t_pred, fwd, ds):
+            (s_state, s_pred), = fwd
             ops.distill_losses(t_pred, self.teacher.rowsum, s_pred, self.student.rowsum, labels_u8, t_state, s_state, self.losses,
-                               self._dp_s, self._ds_s, g_ce=(1.0 / B) if "ce" in on else 0.0, g_kl=1.0 if "pred" in on else 0.0,
+                               self._dp_s, ds[0], g_ce=(1.0 / B) if "ce" in on else 0.0, g_kl=1.0 if "pred" in on else 0.0,
                                g_rep=self.rep_w if "rep" in on else 0.0)
-            mark("losses_done", side)
-            early_s = (lr, self.clip, l2c) if (apply and self.overlap_towers and self._aux_s is not None) else None
-            gen_s = self.student.backward_phases(self._ds_s, self._dp_s, aux=self._aux_s if self.overlap_towers else None,
-                                                 early_apply=early_s, defer=self.defer_updates, opt=self._opt_s)
-            while next(gen_s, self) is not self:       # every phase to its end (2 * lstm_layers + 2 resumptions, as in _step)
-                pass
-            self._student_applied = early_s is not None
-            mark("student_done", side)
-            if two_streams:
-                self._ev_student.record(side)
-                used = (xs if isinstance(xs, tuple) else (xs,)) + (n_s, l1s, l2s)
-                if plan_s is not None:
-                    used += (plan_s.pos, plan_s.inv, plan_s.lens)
-                for t in used:                                          # allocated on `main`, consumed on `side`
-                    if t is not None:
-                        t.record_stream(side)
-        if two_streams:
-            main.wait_event(self._ev_student)
-        out = dict(student_predictions=s_pred, student_state=s_state, num_frames_student=n_s, student_loss_state=self.losses[1],
-                   pred_loss=self.losses[2], student_label_loss=self.losses[3], predictions=t_pred, teacher_state=t_state,
-                   loss=self.losses[0])
-        if apply:
-            self._apply_gradients(B, lr)
-        out["global_step"] = self.global_step
+
+        out = self._serial_step([self.student], xt, tp, [xs], [sp], labels_u8, [self._dp_s], apply, loss_section)
+        out.update(out.pop("students")[0])
         return out
 
-    def flush(self):
-        """Enqueue and join the deferred updates of the last step (defer_updates): afterwards every weight, moment and operand
-        shadow of both towers is current in the order of the caller's stream.  Cheap no-op when nothing is pending."""
-        if self.device.type != "cuda":
-            return
-        cur = torch.cuda.current_stream(self.device)
-        for tw in (self.teacher, self.student):
-            if tw is not None:
-                tw.wait_deferred(cur)
-
-    def apply_gradients(self, batch_size, lr=None):
-        """Runs whichever train op has not been applied inside step(); each one increments
-        global_step (cs/train.py:332,416 -> += 2 per iteration, README.md:116,121)."""
-        self.flush()
-        self._apply_gradients(batch_size, lr)
-
     def _apply_gradients(self, batch_size, lr=None):
+        """Each train op increments global_step (cs/train.py:332,416 -> += 2 per iteration, README.md:116,121)."""
         l2c = self.reg_pen * 1e-8
         if lr is None:
-            lr = exponential_decay(self.lr0, self.global_step, batch_size * self.world, self.lr_decay_examples, self.lr_decay)
+            lr = self._lr_l2c(batch_size)[0]
         if self.teacher is not None and self.train_teacher:
-            if not getattr(self, "_teacher_applied", False):
+            if not self._teacher_applied:
                 self.teacher.apply_gradients(lr, self.clip, l2c)
             self.global_step += 1
         if self.student is not None:
-            if not getattr(self, "_student_applied", False):
+            if not self._student_applied:
                 self.student.apply_gradients(lr, self.clip, l2c)
             self.global_step += 1
         self._teacher_applied = self._student_applied = False
@@ -894,18 +948,6 @@ class DistillGraph:
         return rep
 
 
-class _TowerSlot:
-    """What frame_counts_and_plans / input_views read of a graph, for ONE tower of SerialStudentsGraph: the frozen teacher
-    (student None) or one student (teacher None) with its own every_n and frame selection."""
-
-    def __init__(self, graph, teacher=None, student=None, every_n=1, student_sampling="uniform"):
-        self.teacher, self.student, self.every_n, self.student_sampling = teacher, student, every_n, student_sampling
-        self.max_frames, self.C1, self.C2, self.row_plans = graph.max_frames, graph.C1, graph.C2, graph.row_plans
-        self.S = graph.max_frames // every_n
-        self.sampling_seed, self.sampling_draw, self.sampling_row0 = graph.sampling_seed, 0, 0
-        self.last_frame_table = None
-
-
 class SerialStudentView:
     """Student k of a SerialStudentsGraph as train.save_checkpoint / restore_checkpoint see a DistillGraph(mode="serial"): the
     shared frozen teacher, this student, its losses and frames, the common global_step."""
@@ -929,7 +971,7 @@ class SerialStudentView:
         self._graph.consolidate()
 
 
-class SerialStudentsGraph:
+class SerialStudentsGraph(_TrainGraph):
     """Serial distillation of K students (1 <= K <= 8) against ONE forward of a frozen teacher per iteration: what K
     DistillGraph(mode="serial") runs on the same batches compute, with the teacher's forward, the batch's input pass for the teacher
     and the teacher's share of the loss section done once.  Each student has its own every_n, frame selection and loss subset; all
@@ -982,25 +1024,19 @@ class SerialStudentsGraph:
         self.teacher.store.drop_training_state()
         self.students = [HLstmTower(batch_size, max_frames // e, num_inputs_l1_student, feature_size, vocab_size, lstm_cells,
                                     lstm_layers, num_mixtures, device, True, "model_student", seed + 1) for e in self.every_n]
-        self._t_slot = _TowerSlot(self, teacher=self.teacher)
-        self._s_slots = [_TowerSlot(self, student=s, every_n=e, student_sampling=w)
-                         for s, e, w in zip(self.students, self.every_n, self.student_sampling)]
+        # one input pass per tower: the frozen teacher, and each student with its own every_n and frame selection
+        self._t_frames = FramePlan(teacher=self.teacher, C1=self.C1, C2=self.C2, max_frames=max_frames)
+        self._s_frames = [FramePlan(None, s, e, self.C1, self.C2, max_frames, True, w, self.sampling_seed)
+                          for s, e, w in zip(self.students, self.every_n, self.student_sampling)]
         self.losses = torch.zeros((K, 4), dtype=F32, device=self.device)
-        self._dp_s = self._ds_s = None
-        self._applied = [False] * K
+        self._dp_s = self._ds_serial = None
+        self._student_applied = False       # (all K students: their updates run inside the step together or not at all)
         self.overlap_towers = overlap_towers
         self.defer_updates = os.environ.get("EVC_DEFER_UPDATES", "0") == "1"
-        self._opt_s = None
-        if self.device.type == "cuda":
-            self._main, self._side, _, self._aux_s = concurrent_streams(self.device, 4)
-            if os.environ.get("EVC_SINGLE_STREAM") == "1":
-                self._side = self._aux_s = self._main
-            m = os.environ.get("EVC_OPT_CU_MASK")        # the optimizer launches on a CU-masked stream of their own, as in DistillGraph
-            if m:
-                from .streams import cu_masked_stream
-                f = [int(v) for v in m.split(":")]
-                self._opt_s = cu_masked_stream(self.device, f[0], f[1] if len(f) > 1 else 0)
-            self._ev_fwd, self._ev_student, self._ev_in = torch.cuda.Event(), torch.cuda.Event(), torch.cuda.Event()
+        self._make_streams()
+
+    def _towers(self):
+        return self.students
 
     def student_view(self, k, with_teacher=True):
         """with_teacher=False: the student alone (restoring student k > 0 must not load the shared teacher again)."""
@@ -1009,121 +1045,47 @@ class SerialStudentsGraph:
     @property
     def last_frame_tables(self):
         """Per student: the source-frame table of the last batch (None for a `uniform` student, which needs none)."""
-        return [s.last_frame_table for s in self._s_slots]
+        return [p.last_frame_table for p in self._s_frames]
 
     def step(self, x_raw, labels_u8, num_frames, apply=True, num_frames_host=None):
         """One iteration of every student on this batch (DistillGraph.step's stream semantics and arguments)."""
-        if num_frames_host is None:
-            num_frames_host = num_frames.cpu()
-        nh = np.asarray(num_frames_host, dtype=np.int64).reshape(-1)
-        caller = torch.cuda.current_stream(self.device)
-        if caller == self._main:
-            return self._step(x_raw, labels_u8, num_frames, apply, nh)
-        self._main.wait_stream(caller)
-        with torch.cuda.stream(self._main):
-            out = self._step(x_raw, labels_u8, num_frames, apply, nh)
-        for t in (x_raw, labels_u8, num_frames):
-            t.record_stream(self._main)
-        caller.wait_stream(self._main)
-        return out
+        return self._on_main((x_raw, labels_u8, num_frames), num_frames_host, lambda nh: self._step(x_raw, labels_u8, num_frames, apply, nh))
 
     def _step(self, x_raw, labels_u8, num_frames, apply, nh):
-        """Schedule: the teacher's forward ONCE on `main`; the K students' forwards next to it on `side`, from the start of the step;
-        one ops.distill_losses_multi on `side` once all forwards are done; then each student's backward and update exactly as
-        DistillGraph._step_serial issues its one (aux stream, early apply, defer_updates); `main` joins at the end."""
-        B, V, K = x_raw.shape[0], labels_u8.shape[1], self.K
-        dev = self.device
+        """The input stage - one pass per tower -, then _serial_step for the K students with the loss section ops.distill_losses_multi."""
+        B, V = x_raw.shape[0], labels_u8.shape[1]
         if self._dp_s is None or self._dp_s[0].shape[0] != B:
-            self._dp_s = [torch.empty((B, V), dtype=F32, device=dev) for _ in range(K)]
-        main = torch.cuda.current_stream(dev)
-        tp, _ = frame_counts_and_plans(self._t_slot, num_frames, nh, True, False)
-        xt, _ = input_views(self._t_slot, x_raw, num_frames, tp, None, False)
+            self._dp_s = [torch.empty((B, V), dtype=F32, device=self.device) for _ in range(self.K)]
+        tp, _ = frame_counts_and_plans(self._t_frames, num_frames, nh, True, False)
+        xt, _ = input_views(self._t_frames, x_raw, num_frames, tp, None, False)
         sps, xss = [], []
         # the keys of the content-aware strategies depend on the batch alone: once, for every student that ranks by them
-        keys = ops.frame_change_keys(x_raw, num_frames) if any(scored_sampling(slot) for slot in self._s_slots) else None
-        for slot in self._s_slots:
-            slot.sampling_draw, slot.sampling_row0 = self.global_step, 0      # one train op per iteration: a new "random" draw per step
-            _, sp = frame_counts_and_plans(slot, num_frames, nh, False, True)
+        keys = ops.frame_change_keys(x_raw, num_frames) if any(scored_sampling(p) for p in self._s_frames) else None
+        for p in self._s_frames:
+            p.sampling_draw, p.sampling_row0 = self.global_step, 0      # one train op per iteration: a new "random" draw per step
+            _, sp = frame_counts_and_plans(p, num_frames, nh, False, True)
             sps.append(sp)
-            xss.append(input_views(slot, x_raw, num_frames, None, sp, True, keys=keys)[1])
-        for s in self.students:
-            s.run_deferred()
-        self.losses.zero_()
-        lr = exponential_decay(self.lr0, self.global_step, B, self.lr_decay_examples, self.lr_decay)
-        l2c = self.reg_pen * 1e-8
-        self._applied = [False] * K
-        two_streams = self.overlap_towers
-        side = self._side if two_streams else main
-        l1, l2, plan_t = tp
-        if two_streams:
-            self._ev_in.record(main)
-            side.wait_event(self._ev_in)
-        t_state, t_pred = self.teacher.forward(xt, l1, l2, plan_t)
-        if two_streams:
-            self._ev_fwd.record(main)
-        outs = []
-        with torch.cuda.stream(side):
-            fwd = []
-            for s, xs, (n_s, l1s, l2s, plan_s) in zip(self.students, xss, sps):
-                fwd.append(s.forward(xs, l1s, l2s, plan_s))
-            if two_streams:
-                side.wait_event(self._ev_fwd)
-            if self._ds_s is None or self._ds_s[0].shape != fwd[0][0].shape:
-                self._ds_s = [torch.empty_like(f[0]) for f in fwd]
-            on = self.distill_losses
+            xss.append(input_views(p, x_raw, num_frames, None, sp, True, keys=keys)[1])
+        on = self.distill_losses
+
+        def loss_section(t_state, t_pred, fwd, ds):
             ops.distill_losses_multi(t_pred, self.teacher.rowsum, labels_u8, t_state, [f[1] for f in fwd],
-                                     [s.rowsum for s in self.students], [f[0] for f in fwd], self.losses, self._dp_s, self._ds_s,
+                                     [s.rowsum for s in self.students], [f[0] for f in fwd], self.losses, self._dp_s, ds,
                                      g_ce=[(1.0 / B) if "ce" in o else 0.0 for o in on], g_kl=[1.0 if "pred" in o else 0.0 for o in on],
                                      g_rep=[self.rep_w if "rep" in o else 0.0 for o in on])
-            early_s = (lr, self.clip, l2c) if (apply and self.overlap_towers and self._aux_s is not None) else None
-            for k, s in enumerate(self.students):
-                gen = s.backward_phases(self._ds_s[k], self._dp_s[k], aux=self._aux_s if self.overlap_towers else None,
-                                        early_apply=early_s, defer=self.defer_updates, opt=self._opt_s)
-                while next(gen, self) is not self:       # every phase to its end, as in DistillGraph._step_serial
-                    pass
-                self._applied[k] = early_s is not None
-            if two_streams:
-                self._ev_student.record(side)
-                for xs, (n_s, l1s, l2s, plan_s) in zip(xss, sps):
-                    used = (xs if isinstance(xs, tuple) else (xs,)) + (n_s, l1s, l2s)
-                    if plan_s is not None:
-                        used += (plan_s.pos, plan_s.inv, plan_s.lens)
-                    for t in used:                                          # allocated on `main`, consumed on `side`
-                        if t is not None:
-                            t.record_stream(side)
-        if two_streams:
-            main.wait_event(self._ev_student)
-        for k in range(K):
-            outs.append(dict(student_predictions=fwd[k][1], student_state=fwd[k][0], num_frames_student=sps[k][0],
-                             student_loss_state=self.losses[k, 1], pred_loss=self.losses[k, 2], student_label_loss=self.losses[k, 3]))
-        out = dict(predictions=t_pred, teacher_state=t_state, loss=self.losses[0, 0], students=outs)
-        if apply:
-            self._apply_gradients(B, lr)
-        out["global_step"] = self.global_step
-        return out
 
-    def flush(self):
-        """Enqueue and join the students' deferred updates of the last step (defer_updates); a cheap no-op when nothing is pending."""
-        if self.device.type != "cuda":
-            return
-        cur = torch.cuda.current_stream(self.device)
-        for s in self.students:
-            s.wait_deferred(cur)
-
-    def apply_gradients(self, batch_size, lr=None):
-        """Runs every student's train op that has not been applied inside step(); global_step += 1 for the iteration."""
-        self.flush()
-        self._apply_gradients(batch_size, lr)
+        return self._serial_step(self.students, xt, tp, xss, sps, labels_u8, self._dp_s, apply, loss_section)
 
     def _apply_gradients(self, batch_size, lr=None):
+        """Every student's train op; global_step += 1 for the iteration."""
         l2c = self.reg_pen * 1e-8
         if lr is None:
-            lr = exponential_decay(self.lr0, self.global_step, batch_size, self.lr_decay_examples, self.lr_decay)
-        for k, s in enumerate(self.students):
-            if not self._applied[k]:
+            lr = self._lr_l2c(batch_size)[0]
+        if not self._student_applied:
+            for s in self.students:
                 s.apply_gradients(lr, self.clip, l2c)
         self.global_step += 1
-        self._applied = [False] * self.K
+        self._student_applied = False
 
     def consolidate(self):
         """One rank: nothing is sharded; the deferred updates are joined (as DistillGraph.consolidate does first)."""
@@ -1139,7 +1101,7 @@ class SerialStudentsGraph:
         return [{name: v[k][i] for i, name in enumerate(self.LOSS_SLOTS)} for k in range(self.K)]
 
 
-class EvalGraph:
+class EvalGraph(_StepGraph):
     """Forward-only graph of cs/validate.py:109-189 (teacher built too, so that the
     student_state_loss ||teacher_state - student_state||^2 can be logged) and of
     cs/eval_finetune.py:108-175 (``student_only``).  Towers are built with
@@ -1179,6 +1141,10 @@ class EvalGraph:
         self._main, self._side = concurrent_streams(self.device, 4)[:2]
         self._ev_in, self._ev_out = torch.cuda.Event(), torch.cuda.Event()
         self.row_plans = precision != "split"
+        self.frames = FramePlan(self.teacher, self.student, every_n, self.C1, self.C2, max_frames, self.row_plans,
+                                self.student_sampling, self.sampling_seed)
+
+    last_frame_table = property(lambda self: self.frames.last_frame_table)
 
     def restore(self, state_dict):
         """saver_teacher / saver_student .restore (cs/validate.py:350-384): the 11 variables of each tower by name."""
@@ -1188,17 +1154,7 @@ class EvalGraph:
 
     def step(self, x_raw, labels_u8, num_frames, num_frames_host=None, keys=None):
         """``keys``: the batch's ops.frame_change_keys, computed on the caller's stream by an owner of several graphs (EnsembleGraph)."""
-        if num_frames_host is None:
-            num_frames_host = num_frames.cpu()
-        nh = np.asarray(num_frames_host, dtype=np.int64).reshape(-1)
-        caller = torch.cuda.current_stream(self.device)
-        self._main.wait_stream(caller)
-        with torch.cuda.stream(self._main):
-            out = self._step(x_raw, labels_u8, num_frames, nh, keys)
-        for t in (x_raw, labels_u8, num_frames) + (() if keys is None else (keys,)):
-            t.record_stream(self._main)
-        caller.wait_stream(self._main)
-        return out
+        return self._on_main((x_raw, labels_u8, num_frames, keys), num_frames_host, lambda nh: self._step(x_raw, labels_u8, num_frames, nh, keys))
 
     def _step(self, x_raw, labels_u8, num_frames, nh, keys=None):
         """Returns predictions (student), student_label_loss, student_state_loss (teacher_student only) - the
@@ -1206,10 +1162,8 @@ class EvalGraph:
         if self.student is None:
             return self._step_teacher(x_raw, num_frames, nh)
         main = torch.cuda.current_stream(self.device)
-        split = self.student.input_split()
-        u8 = x_raw.dtype == torch.uint8
-        tp, sp = frame_counts_and_plans(self, num_frames, nh, self.teacher is not None, True)
-        xt, xs = input_views(self, x_raw, num_frames, tp, sp, True, keys=keys)
+        tp, sp = frame_counts_and_plans(self.frames, num_frames, nh, self.teacher is not None, True)
+        xt, xs = input_views(self.frames, x_raw, num_frames, tp, sp, True, keys=keys)
         self.losses.zero_()
         out = {}
         self._ev_in.record(main)
@@ -1217,13 +1171,9 @@ class EvalGraph:
         n_s, l1s, l2s, plan_s = sp
         with torch.cuda.stream(self._side):
             s_state, s_pred = self.student.forward(xs, l1s, l2s, plan_s)
-            self._label_loss(s_pred, labels_u8, self.losses[0:1])
+            self.label_loss.fused(s_pred, labels_u8, self.losses[0:1])
             self._ev_out.record(self._side)
-            used = (xs if isinstance(xs, tuple) else (xs,)) + (n_s, l1s, l2s)
-            if plan_s is not None:
-                used += (plan_s.pos, plan_s.inv, plan_s.lens)
-            for t in used:
-                t.record_stream(self._side)
+            self._keep_alive(self._side, [xs], [sp])
         if self.teacher is not None:
             l1, l2, plan_t = tp
             t_state, t_pred = self.teacher.forward(xt, l1, l2, plan_t)
@@ -1236,13 +1186,10 @@ class EvalGraph:
                    loss=self.losses[0])
         return out
 
-    def _label_loss(self, pred, labels_u8, loss, dpred=None, grad_scale=1.0):
-        self.label_loss.fused(pred, labels_u8, loss, dpred, grad_scale=grad_scale)
-
     def _step_teacher(self, x_raw, num_frames, nh):
         """teacher_only: the teacher's forward alone (same input views, row plans and precision handling as _step)."""
-        tp, _ = frame_counts_and_plans(self, num_frames, nh, True, False)
-        xt, _ = input_views(self, x_raw, num_frames, tp, None, False)
+        tp, _ = frame_counts_and_plans(self.frames, num_frames, nh, True, False)
+        xt, _ = input_views(self.frames, x_raw, num_frames, tp, None, False)
         l1, l2, plan_t = tp
         t_state, t_pred = self.teacher.forward(xt, l1, l2, plan_t)
         return dict(predictions=t_pred, teacher_state=t_state, teacher_predictions=t_pred)
@@ -1278,12 +1225,12 @@ class EnsembleGraph:
         if num_frames_host is None:
             num_frames_host = num_frames.cpu()
         # the keys of the content-aware strategies depend on the batch alone: once, for every member that ranks by them
-        keys = ops.frame_change_keys(x_raw, num_frames) if any(scored_sampling(g) for g in self.members) else None
-        return [g.step(x_raw, labels_u8, num_frames, num_frames_host=num_frames_host, keys=keys if scored_sampling(g) else None)["predictions"]
+        keys = ops.frame_change_keys(x_raw, num_frames) if any(scored_sampling(g.frames) for g in self.members) else None
+        return [g.step(x_raw, labels_u8, num_frames, num_frames_host=num_frames_host, keys=keys if scored_sampling(g.frames) else None)["predictions"]
                 for g in self.members]
 
 
-class SingleTowerGraph:
+class SingleTowerGraph(_StepGraph):
     """Teacher-only training step for dict-returning models (DbofModel,
     FrameLevelLogisticModel).  The reference's train.py cannot run these
     (it unpacks the H-LSTM tuple, cs/train.py:282 - SURVEY.md Appendix D-8);
@@ -1320,9 +1267,6 @@ class SingleTowerGraph:
         if self.moe is not None:
             self.moe.consolidate(self.reducer)
 
-    def _label_loss(self, pred, labels_u8, loss, dpred=None, grad_scale=1.0):
-        self.label_loss.fused(pred, labels_u8, loss, dpred, grad_scale=grad_scale)
-
     def label_grads(self):
         """The dL/dpred buffer the last step filled, as {"teacher": ...} (the one tower).  For tests and debugging."""
         return {} if self._dp is None else {"teacher": self._dp}
@@ -1345,7 +1289,7 @@ class SingleTowerGraph:
         else:
             pred = tw.forward(x_raw, num_frames)
         self.losses.zero_()
-        self._label_loss(pred, labels_u8, self.losses[0:1], self._dp, grad_scale=1.0 / (B * self.world))
+        self.label_loss.fused(pred, labels_u8, self.losses[0:1], self._dp, grad_scale=1.0 / (B * self.world))
         fuse = (apply and self.fused_moe_update and self.moe is not None and self.moe.can_fuse_update()
                 and self.moe.prefer_fused_update(self.dp)
                 and tw.precision == "bf16")
@@ -1374,8 +1318,7 @@ class SingleTowerGraph:
         if self.dp:
             main.wait_stream(self._aux)
         if apply:
-            lr = exponential_decay(self.lr0, self.global_step, B * self.world, self.lr_decay_examples, self.lr_decay)
-            l2c = self.reg_pen * 1e-8
+            lr, l2c = self._lr_l2c(B)
             if fuse:
                 tw.begin_update()
                 if route_rs:

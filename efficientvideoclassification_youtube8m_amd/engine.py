@@ -40,7 +40,7 @@ def _align(n, a=16):
     return (n + a - 1) // a * a
 
 
-def _drain(gen):
+def drain(gen):
     """Run a generator to its end and return its return value."""
     try:
         while True:
@@ -453,7 +453,7 @@ class LstmStack:
 
     def backward(self, dS, need_dx, aux=None, on_layer_grads=None):
         """backward_layers run to its end; returns dX (or None)."""
-        return _drain(self.backward_layers(dS, need_dx, aux, on_layer_grads))
+        return drain(self.backward_layers(dS, need_dx, aux, on_layer_grads))
 
     def backward_layers(self, dS, need_dx, aux=None, on_layer_grads=None):
         """GENERATOR form of backward(): yields the layer index after each layer's launches have been enqueued (upper layer first)
@@ -1625,7 +1625,7 @@ class HLstmTower(TowerBase):
 
     def backward(self, *args, **kwargs):
         """backward_phases run to its end."""
-        _drain(self.backward_phases(*args, **kwargs))
+        drain(self.backward_phases(*args, **kwargs))
 
     def backward_phases(self, dstate, dpred, on_moe_grads_ready=None, aux=None, early_apply=None, reduce_fn=None, dp=None, defer=False, opt=None):
         """GENERATOR: yields after the MoE head's backward (+ its update / collectives) and after every LSTM layer of the L2 and L1
