@@ -71,6 +71,7 @@ SIGNATURES = {
     "evc_ce_loss_ordered": [vp, vp, i32, i32, f32, vp, vp, i32, vp, vp],
     "evc_rep_loss_ordered": [vp, vp, i32, i32, f32, vp, vp, i32, vp, vp],
     "evc_kl_pred_loss": [vp, vp, vp, vp, i32, i32, f32, vp, vp, i32, vp],
+    "evc_kl_pred_loss_ordered": [vp, vp, vp, vp, i32, i32, f32, vp, vp, i32, vp, vp],
     "evc_rep_loss": [vp, vp, i32, i32, f32, vp, vp, i32, vp],
     "evc_distill_losses": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, vp, vp, vp, vp, vp],
     "evc_distill_losses_multi": [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp],

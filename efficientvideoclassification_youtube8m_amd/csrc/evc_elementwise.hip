@@ -1104,7 +1104,8 @@ extern "C" int evc_ce_loss_ordered(const float* pred, const uint8_t* labels, int
 
 __global__ __launch_bounds__(256) void kl_loss_kernel(const float* __restrict__ pt, const float* __restrict__ st,
                                                       const float* __restrict__ ps, const float* __restrict__ ss, int V,
-                                                      float gs, float* __restrict__ loss, float* __restrict__ dps, int acc) {
+                                                      float gs, float* __restrict__ loss, float* __restrict__ dps, int acc,
+                                                      float* __restrict__ part = nullptr) {
   __shared__ float sh[4];
   const int b = blockIdx.x;
   // Degenerate rows (only reached once a tower has collapsed, e.g. on random labels after a few Adam steps, where
@@ -1129,16 +1130,31 @@ __global__ __launch_bounds__(256) void kl_loss_kernel(const float* __restrict__ 
     }
   }
   s = block_sum(s, sh);
-  if (threadIdx.x == 0) atomicAdd(loss, s);
+  if (threadIdx.x == 0) {
+    if (part) part[b] = s;
+    else atomicAdd(loss, s);
+  }
+}
+static int kl_pred_loss_impl(const float* pred_t, const float* rowsum_t, const float* pred_s, const float* rowsum_s, int B, int V, float grad_scale,
+                             float* loss, float* dpred_s, int accumulate_grad, float* partials, void* stream) {
+  EVC_REQUIRE(B > 0 && V > 0, EVC_ERR_BAD_SHAPE, "evc_kl_pred_loss: bad shape");
+  hipLaunchKernelGGL(kl_loss_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, pred_t, rowsum_t, pred_s, rowsum_s, V,
+                     grad_scale, loss, dpred_s, accumulate_grad, partials);
+  if (partials) hipLaunchKernelGGL(loss_partials_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const float*)partials, B, loss);
+  EVC_LAUNCH_CHECK();
+  return EVC_OK;
 }
 extern "C" int evc_kl_pred_loss(const float* pred_t, const float* rowsum_t, const float* pred_s, const float* rowsum_s,
                                 int B, int V, float grad_scale, float* loss, float* dpred_s, int accumulate_grad,
                                 void* stream) {
-  EVC_REQUIRE(B > 0 && V > 0, EVC_ERR_BAD_SHAPE, "evc_kl_pred_loss: bad shape");
-  hipLaunchKernelGGL(kl_loss_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, pred_t, rowsum_t, pred_s, rowsum_s, V,
-                     grad_scale, loss, dpred_s, accumulate_grad);
-  EVC_LAUNCH_CHECK();
-  return EVC_OK;
+  return kl_pred_loss_impl(pred_t, rowsum_t, pred_s, rowsum_s, B, V, grad_scale, loss, dpred_s, accumulate_grad, nullptr, stream);
+}
+// the row sums joined in row order instead of by float atomics (EVC_DETERMINISTIC=1 callers): partials = B floats of scratch
+extern "C" int evc_kl_pred_loss_ordered(const float* pred_t, const float* rowsum_t, const float* pred_s, const float* rowsum_s,
+                                        int B, int V, float grad_scale, float* loss, float* dpred_s, int accumulate_grad,
+                                        float* partials, void* stream) {
+  EVC_REQUIRE(partials, EVC_ERR_BAD_ARG, "evc_kl_pred_loss_ordered: partials (B floats of scratch) is required");
+  return kl_pred_loss_impl(pred_t, rowsum_t, pred_s, rowsum_s, B, V, grad_scale, loss, dpred_s, accumulate_grad, partials, stream);
 }
 
 __global__ __launch_bounds__(256) void rep_loss_kernel(const float* __restrict__ a, const float* __restrict__ b, long n,

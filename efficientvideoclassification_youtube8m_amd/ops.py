@@ -874,6 +874,11 @@ def label_loss(kind, pred, labels_u8, loss, dpred=None, grad_scale=1.0, accumula
 
 def kl_pred_loss(pred_t, rowsum_t, pred_s, rowsum_s, loss, dpred_s=None, grad_scale=1.0, accumulate_grad=False):
     B, V = pred_t.shape
+    if DETERMINISTIC:      # the row sums joined in row order (scratch from the stream-aware caching allocator)
+        ws = torch.empty(B, dtype=F32, device=pred_t.device)
+        _lib.call("evc_kl_pred_loss_ordered", _p(pred_t), _p(rowsum_t), _p(pred_s), _p(rowsum_s), B, V, grad_scale, _p(loss), _p(dpred_s),
+                  1 if accumulate_grad else 0, _p(ws), _stream())
+        return
     _lib.call("evc_kl_pred_loss", _p(pred_t), _p(rowsum_t), _p(pred_s), _p(rowsum_s), B, V, grad_scale, _p(loss), _p(dpred_s),
               1 if accumulate_grad else 0, _stream())
 

@@ -486,6 +486,10 @@ int evc_ce_loss_ordered(const float* pred, const uint8_t* labels, int B, int V, 
 int evc_kl_pred_loss(const float* pred_t, const float* rowsum_t, const float* pred_s, const float* rowsum_s,
                      int B, int V, float grad_scale, float* loss, float* dpred_s, int accumulate_grad,
                      void* stream);
+/* The same with the B row sums joined in row order instead of by float atomics (EVC_DETERMINISTIC=1 callers): partials = B floats of scratch. */
+int evc_kl_pred_loss_ordered(const float* pred_t, const float* rowsum_t, const float* pred_s, const float* rowsum_s,
+                             int B, int V, float grad_scale, float* loss, float* dpred_s, int accumulate_grad,
+                             float* partials, void* stream);
 /* loss += mean_b sum_d (sT-sS)^2 ; dstate_s (=|+=) grad_scale * d/dsS. */
 int evc_rep_loss(const float* state_t, const float* state_s, int B, int D, float grad_scale,
                  float* loss, float* dstate_s, int accumulate_grad, void* stream);

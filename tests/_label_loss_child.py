@@ -4,6 +4,8 @@ per process).
     python tests/_label_loss_child.py digest    two digests over the loss and dpred bits of every evc_label_loss kind (two runs), then ok
     python tests/_label_loss_child.py graph     DistillGraph(label_loss=None) and (label_loss="CrossEntropyLoss") from the same seed run the
                                                 same step: outputs, loss values, dL/dpred and every weight gradient must be torch.equal
+    python tests/_label_loss_child.py kl        ops.kl_pred_loss (evc_kl_pred_loss_ordered in this mode): 20 calls give the same bits, the value
+                                                and the gradient are float64's (tests/_distill_losses_ref.py)
 """
 import os
 import sys
@@ -30,6 +32,28 @@ elif mode == "graph":
         if not torch.equal(u, v):
             sys.exit("%s differs between label_loss=None and label_loss='CrossEntropyLoss'" % name)
     print("%d tensors bit-identical" % len(a))
+elif mode == "kl":
+    import _distill_losses_ref as dref
+    B, V, D = 64, 257, 4                       # 64 row sums: 64 float atomics in arrival order would not repeat
+    inp = dref.make_inputs(B, V, D)
+    want = dref.reference(inp, g_ce=1.0 / B, g_kl=1.0, g_rep=2.0)
+    dv = {k: torch.from_numpy(v).to("cuda:0") for k, v in inp.items()}
+    first = None
+    for _ in range(20):
+        loss = torch.zeros(1, dtype=torch.float32, device="cuda:0")
+        dp = torch.zeros_like(dv["pred_s"])
+        ops.kl_pred_loss(dv["pred_t"], dv["rowsum_t"], dv["pred_s"], dv["rowsum_s"], loss, dp, grad_scale=1.0)
+        torch.cuda.synchronize()
+        first = (loss, dp) if first is None else first
+        if not (torch.equal(loss, first[0]) and torch.equal(dp, first[1])):
+            sys.exit("evc_kl_pred_loss_ordered: two calls differ (%r, %r)" % (float(loss), float(first[0])))
+    ref_l = float(want["losses"][2])
+    if not abs(float(first[0]) - ref_l) <= 1e-4 * abs(ref_l):
+        sys.exit("L_PRED %r, float64 %r" % (float(first[0]), ref_l))
+    err = np.abs(first[1].double().cpu().numpy() - want["kl"])
+    if not np.all(err <= 1e-5 * want["kl_parts"]):
+        sys.exit("dL_PRED/dpred_s outside 1e-5 of its two addends")
+    print("L_PRED %.9g (float64 %.9g), 20 calls bit-identical" % (float(first[0]), ref_l))
 else:
-    sys.exit("usage: _label_loss_child.py digest | graph")
+    sys.exit("usage: _label_loss_child.py digest | graph | kl")
 print("ok")

@@ -6,6 +6,10 @@ Bounds.  Gradients, elementwise, no element exempt: |got - ref| <= 1e-5 (|ce ter
 contraction).  Where a scale is 0 the remaining term stands alone; the KL gradient is a DIFFERENCE, -P/p_s + 1/sum(p_s), that cancels
 where teacher and student agree, so alone it is held to 1e-5 of the magnitudes of its two addends (f32 rounds each addend to 6e-8 of
 itself: nothing can be asked relative to a difference that may be 0).  Loss values: 1e-4 relative."""
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 import torch
@@ -128,3 +132,15 @@ def test_losses_accumulate_into_the_four_slots():
         ops.distill_losses(dv["pred_t"], dv["rowsum_t"], dv["pred_s"], dv["rowsum_s"], dv["labels"], dv["state_t"], dv["state_s"], losses)
     got = losses.double().cpu().numpy()
     assert np.all(np.abs(got[:4] - 2 * want["losses"]) <= RTOL_LOSS * 2 * np.abs(want["losses"])) and not got[4:].any()
+
+
+def test_kl_pred_loss_repeats_bit_for_bit_under_evc_deterministic():
+    """EVC_DETERMINISTIC=1 (read once per process: a child): ops.kl_pred_loss joins its row sums in row order (evc_kl_pred_loss_ordered),
+    not by float atomics - 20 calls on 64 rows give the same bits, and value and gradient are float64's within the bounds above."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run(["timeout", "-k", "10", "120", sys.executable, os.path.join(root, "tests", "_label_loss_child.py"), "kl"],
+                       env=dict(os.environ, EVC_DETERMINISTIC="1"), capture_output=True, text=True)
+    print(r.stdout[-2000:])
+    if r.returncode in (-6, -11, -9, 134, 139, 137, 124):
+        pytest.exit("the kl child died with %d, stopping:\n%s" % (r.returncode, r.stdout[-2000:] + r.stderr[-3000:]), returncode=3)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout[-2000:] + r.stderr[-4000:]
