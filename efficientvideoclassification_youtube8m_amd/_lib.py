@@ -135,6 +135,8 @@ SIGNATURES = {
     "evc_l2norm_chunk_sel_int": [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp],
     "evc_frame_change_keys": [vp, vp, vp, i32, i32, i32, vp, vp],
     "evc_student_frame_select_scored": [vp, vp, i32, i32, i32, i32, vp, vp],
+    "evc_cascade_confidence_rows": [vp, i64, vp, i32, i32, i32, i32, vp, vp, i64, vp, vp],
+    "evc_cascade_pick_rows": [vp, vp, vp, i32, f32, i32, vp, vp, vp, vp],
 }
 EXPORTS = tuple(SIGNATURES) + ("evc_version", "evc_last_error")
 

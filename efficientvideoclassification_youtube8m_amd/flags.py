@@ -184,6 +184,23 @@ _define("ensemble_weights", "", str, "comma separated weights, one per member an
         "'' = 1 / (members + files) each")
 _define("preds_pattern", "", str, "inference: glob of earlier VideoId,LabelConfidencePairs files, sorted by name, that join the ensemble as "
         "sparse members (a class a file does not list counts 0; cs/inference_ensemble.py:155-193)")
+# ---- confidence cascades (inference / validate; an addition): escalate only the videos the cheaper tower is unsure of -------------------
+_define("cascade_dirs", "", str, "comma separated checkpoint directories of the cascade's stages, cheapest first (2 .. 8; a directory listed "
+        "twice is read once); '' = no cascade.  Stage 0 runs on the whole batch, a gate on the device (ops.cascade_confidence_rows + "
+        "ops.cascade_pick_rows) measures how sure each video's prediction is, and only the unsure videos run the next stage: their "
+        "settled neighbours get num_frames = 0 and drop out of the row plans.  Under --precision split the row plans are off: the cascade "
+        "is correct there but saves nothing.  Not with --ensemble_dirs or --preds_pattern; validate needs --run_once True")
+_define("cascade_towers", "", str, "one word per stage from auto|teacher|student, as --ensemble_towers; '' = auto for all")
+_define("cascade_every_n", "", str, "one every_n per stage (ignored for teachers); '' = --every_n for all")
+_define("cascade_sampling", "", str, "one --student_sampling word per stage (ignored for teachers); '' = --student_sampling for all")
+_define("cascade_confidence", "", str, "top1 (the video's largest prediction) | margin (largest - second largest); '' = top1")
+_define("cascade_thresholds", "", str, "one value per gate (stages - 1): a video whose confidence is >= t_k is settled at stage k "
+        "(-inf: every video settles, inf: every video goes on).  At least one of --cascade_thresholds / --cascade_fractions is needed; "
+        "with both the threshold names the candidates and the fraction caps them")
+_define("cascade_fractions", "", str, "one value in [0, 1] per gate: at most ceil(f_k * batch rows) videos leave stage k, the least "
+        "confident first")
+_define("cascade_stage_file", "", str, "inference: also write VideoId,Stage,Confidence per video to this file (the stage that decided "
+        "the video and its confidence there, '%f')")
 
 
 class FlagValues(object):

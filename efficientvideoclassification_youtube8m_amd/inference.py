@@ -24,6 +24,16 @@ files matched by ``--preds_pattern`` join as sparse members, and one launch of o
         --input_data_pattern "./yt8m/test*.tfrecord" --output_file ./predictions_ensemble.csv --top_k 20 --batch_size 1024 \
         --ensemble_dirs "./model_train/,./model_train/,./model_every30_finetune/" --ensemble_towers "teacher,student,auto" \
         --ensemble_every_n "1,10,30" --ensemble_mode max --preds_pattern "./earlier_predictions/*.csv"  (+ the model / input flags above)
+
+Cascades (an addition): with ``--cascade_dirs dirA,dirB[,...]`` (cheapest first; ``--cascade_towers`` / ``--cascade_every_n`` /
+``--cascade_sampling`` per stage) stage 0 runs on the whole batch, a gate on the device measures each video's confidence
+(``--cascade_confidence`` top1 | margin) and only the videos below ``--cascade_thresholds`` - at most ``--cascade_fractions`` of the batch,
+the least confident first - run the next stage (cascade.CascadeGraph); ops.topk_rows then selects from the merged predictions, each video's
+row being that of the last stage that ran it.  ``--cascade_stage_file`` records which stage decided each video.
+
+    python -m efficientvideoclassification_youtube8m_amd.inference \
+        --input_data_pattern "./yt8m/test*.tfrecord" --output_file ./predictions_cascade.csv --top_k 20 --batch_size 1024 \
+        --cascade_dirs "./model_every30_finetune/,./model_train/" --cascade_every_n "30,1" --cascade_thresholds 0.9 --cascade_fractions 0.3
 """
 from __future__ import annotations
 
@@ -108,6 +118,60 @@ def ensemble_spec(allow_preds_files=True):
     return dict(dirs=dirs, towers=towers, every_n=every_n, sampling=sampling, mode=FLAGS.ensemble_mode, weights=w, files=files)
 
 
+def cascade_spec():
+    """The cascade the flags describe, checked: None without --cascade_dirs, else dict(dirs, towers, every_n, sampling [K]; confidence;
+    thresholds / fractions: [K - 1] floats or None; stage_file).  Raises ValueError for everything that can be refused before the device is
+    touched."""
+    dirs = _words(FLAGS.cascade_dirs)
+    lists = {name: _words(getattr(FLAGS, "cascade_" + name)) for name in ("towers", "every_n", "sampling", "thresholds", "fractions")}
+    if not dirs:
+        for name, given in lists.items():
+            if given:
+                raise ValueError("--cascade_%s: %d entries for 0 --cascade_dirs" % (name, len(given)))
+        for name in ("confidence", "stage_file"):
+            if getattr(FLAGS, "cascade_" + name) != "":
+                raise ValueError("--cascade_%s without --cascade_dirs: there is no cascade it could apply to" % name)
+        return None
+    if FLAGS.ensemble_dirs != "" or FLAGS.preds_pattern != "":
+        raise ValueError("--cascade_dirs together with --ensemble_dirs / --preds_pattern: a cascade serves each video from ONE of its stages, "
+                         "an ensemble combines all members; choose one")
+    K = len(dirs)
+    if not 2 <= K <= ops.CASCADE_MAX_STAGES or "" in dirs:
+        raise ValueError("--cascade_dirs: %d stages (2 .. %d, none empty)" % (K, ops.CASCADE_MAX_STAGES))
+    towers = lists["towers"] or ["auto"] * K
+    every_n = lists["every_n"] or [str(FLAGS.every_n)] * K
+    sampling = lists["sampling"] or [FLAGS.student_sampling] * K
+    for name, given in (("towers", towers), ("every_n", every_n), ("sampling", sampling)):
+        if len(given) != K:
+            raise ValueError("--cascade_%s: %d entries for %d --cascade_dirs" % (name, len(given), K))
+    for t in towers:
+        if t not in ("auto", "teacher", "student"):
+            raise ValueError("--cascade_towers: %r (auto | teacher | student)" % t)
+    every_n = [int(e) for e in every_n]
+    for s in sampling:
+        ops.check_student_sampling(s, "--cascade_sampling")
+    confidence = FLAGS.cascade_confidence or "top1"
+    if confidence not in ops.CASCADE_CONFIDENCE:
+        raise ValueError("--cascade_confidence %r (%s)" % (confidence, " | ".join(ops.CASCADE_CONFIDENCE)))
+    gates = {}
+    for name in ("thresholds", "fractions"):
+        given = lists[name]
+        if given and len(given) != K - 1:
+            raise ValueError("--cascade_%s: %d entries for the %d gates of %d --cascade_dirs" % (name, len(given), K - 1, K))
+        try:
+            gates[name] = [float(x) for x in given] if given else None
+        except ValueError:
+            raise ValueError("--cascade_%s: %r is not a list of numbers" % (name, getattr(FLAGS, "cascade_" + name)))
+    if gates["thresholds"] is None and gates["fractions"] is None:
+        raise ValueError("--cascade_dirs needs --cascade_thresholds or --cascade_fractions (or both): without a gate no video would "
+                         "leave the first stage")
+    for f in gates["fractions"] or []:
+        if not 0.0 <= f <= 1.0:
+            raise ValueError("--cascade_fractions: %r is outside [0, 1]" % f)
+    return dict(dirs=dirs, towers=towers, every_n=every_n, sampling=sampling, confidence=confidence, thresholds=gates["thresholds"],
+                fractions=gates["fractions"], stage_file=FLAGS.cascade_stage_file)
+
+
 def read_prediction_file(path, num_classes=NUM_CLASSES):
     """A ``VideoId,LabelConfidencePairs`` file (format_lines; read_pred_file of cs/inference_ensemble.py:155-167) as
     {video id: (classes int32 [n], confidences float32 [n])}, pairs in the order of the line.  ValueError for a missing header, a
@@ -162,7 +226,9 @@ def gather_priors(tables, files, video_ids, kp, out=None):
 
 
 def check_flags():
-    """Everything that is refused before a record is read or the device is touched.  Returns ensemble_spec()."""
+    """Everything that is refused before a record is read or the device is touched.  Returns ensemble_spec() (cascade_spec() is checked
+    here too; main() asks for it again)."""
+    cascade_spec()
     if FLAGS.output_file == "":
         raise ValueError("'output_file' was not specified. Unable to continue with inference.")
     if FLAGS.input_data_pattern == "":
@@ -239,6 +305,18 @@ def build_ensemble_graph(reader, members, batch_size, device, sampling=None):
                          precision=FLAGS.precision, sampling_seed=FLAGS.student_sampling_seed)
 
 
+def build_cascade_graph(reader, members, batch_size, device, spec):
+    """Forward-only graphs of a cascade's stages (members: (dir, tower, every_n), cheapest first; spec: cascade_spec()); sizes, --precision
+    and --student_sampling_seed shared."""
+    from .cascade import CascadeGraph
+    return CascadeGraph(batch_size, [(tower, every_n, s) for (_, tower, every_n), s in zip(members, spec["sampling"])],
+                        confidence=spec["confidence"], thresholds=spec["thresholds"], fractions=spec["fractions"],
+                        feature_size=sum(reader.feature_sizes), vocab_size=reader.num_classes, max_frames=FLAGS.max_num_frames,
+                        num_inputs_to_lstm=FLAGS.num_inputs_to_lstm, lstm_cells=FLAGS.lstm_cells, lstm_layers=FLAGS.lstm_layers,
+                        num_mixtures=FLAGS.moe_num_mixtures, device=device, precision=FLAGS.precision,
+                        sampling_seed=FLAGS.student_sampling_seed)
+
+
 def build_graph(reader, tower, batch_size, device):
     """Forward-only graph of the one tower served (EvalGraph: the validate / eval_finetune forward, row plans and --precision)."""
     return EvalGraph(batch_size, every_n=FLAGS.every_n, student_only=tower == "student", teacher_only=tower == "teacher",
@@ -307,16 +385,60 @@ def _ensemble_selector(reader, spec, batch_size, top_k, stats):
     return select, device
 
 
-def inference(reader, train_dir, data_pattern, out_file_location, batch_size, top_k, ensemble=None):
+def log_cascade_stages(spec, members):
+    for k, ((d, tower, every_n), s) in enumerate(zip(members, spec["sampling"])):
+        logging.info("cascade stage %d: the %s tower of %s%s", k, tower, d, " at every_n = %d, %s frames" % (every_n, s) if tower == "student" else "")
+    logging.info("cascade: %d stages, confidence %s, thresholds %s, fractions %s", len(members), spec["confidence"], spec["thresholds"],
+                 spec["fractions"])
+
+
+def cascade_shares(stage_videos, stage_frames):
+    """The closing line of a cascade run: the share of the videos each stage ran, and the mean frames read per video over all stages."""
+    total = max(int(stage_videos[0]), 1) if stage_videos else 1
+    return "stage videos %s (%s), stage frames %s, mean frames read per video %.1f" % (
+        list(stage_videos), " ".join("%.1f%%" % (100.0 * v / total) for v in stage_videos), list(stage_frames), sum(stage_frames) / total)
+
+
+def _cascade_selector(reader, spec, batch_size, top_k, stats):
+    """The stages of --cascade_dirs: (select, device), select(...) -> (values, indices, {stage_of, confidence}) of the merged predictions.
+    Missing checkpoints are reported before the device is touched."""
+    sds, members, cks = load_members(spec)
+    device = _open_device()
+    graph = build_cascade_graph(reader, members, batch_size, device, spec)
+    graph.restore(sds)
+    log_cascade_stages(spec, members)
+    K = len(members)
+    stats.update(tower="cascade", checkpoint=cks, members=members, stage_videos=[0] * K, stage_frames=[0] * K, gate_wait_s=0.0,
+                 stage_steps=graph.stage_steps)
+
+    def select(ids, q, labels, n, n_host):
+        out = graph.step(q, labels, n, num_frames_host=n_host)
+        for k in range(K):
+            stats["stage_videos"][k] += out["stage_rows"][k]
+            stats["stage_frames"][k] += out["stage_frames"][k]
+        stats["gate_wait_s"] += out["gate_wait_s"]
+        values, indices = ops.topk_rows(out["predictions"], top_k)         # same stream, right behind the last gate
+        return values, indices, {"stage_of": out["stage_of"], "confidence": out["confidence"]}
+    return select, device
+
+
+def inference(reader, train_dir, data_pattern, out_file_location, batch_size, top_k, ensemble=None, cascade=None):
     """cs/inference_ensemble.py:113-210.  ensemble: None = the one tower of train_dir, else an ensemble_spec() (train_dir is then not
-    consulted).  Returns the counts, the members served as (dir, tower, every_n) and the host-side time split: reader_wait_s (blocked
+    consulted); cascade: a cascade_spec() instead (stats then carry stage_videos / stage_frames [K] and gate_wait_s).  Returns the counts, the members served as (dir, tower, every_n) and the host-side time split: reader_wait_s (blocked
     on the reader threads / staging), fetch_wait_s (blocked on a batch's values + indices), format_s (text formatting and writing)."""
     files = sorted(glob.glob(data_pattern))
     if not files:
         raise IOError("Unable to find input files. data_pattern='" + data_pattern + "'")
     logging.info("number of input files: " + str(len(files)))
     stats = dict(tower=None, checkpoint=None, members=None, videos=0, batches=0, reader_wait_s=0.0, fetch_wait_s=0.0, format_s=0.0)
-    if ensemble is None:
+    stage_file = None
+    if cascade is not None:
+        select, device = _cascade_selector(reader, cascade, batch_size, top_k, stats)
+        if cascade["stage_file"]:
+            from .cascade import STAGE_FILE_HEADER, format_stage_lines
+            stage_file = open(cascade["stage_file"], "w")
+            stage_file.write(STAGE_FILE_HEADER)
+    elif ensemble is None:
         select, device = _single_selector(reader, train_dir, batch_size, top_k, stats)
     else:
         select, device = _ensemble_selector(reader, ensemble, batch_size, top_k, stats)
@@ -334,6 +456,8 @@ def inference(reader, train_dir, data_pattern, out_file_location, batch_size, to
             got = fetcher.result(handle)
             t1 = time.perf_counter()
             out_file.writelines(format_lines(ids, got["values"], got["indices"]))
+            if stage_file is not None:
+                stage_file.writelines(format_stage_lines(ids, got["stage_of"], got["confidence"]))
             stats["fetch_wait_s"] += t1 - t0
             stats["format_s"] += time.perf_counter() - t1
             stats["videos"] += len(ids)
@@ -348,18 +472,22 @@ def inference(reader, train_dir, data_pattern, out_file_location, batch_size, to
             except StopIteration:
                 break
             stats["reader_wait_s"] += time.perf_counter() - t0
-            values, indices = select(ids, q, labels, n, n_host)
-            handle = fetcher.fetch({"values": values, "indices": indices})
+            selected = select(ids, q, labels, n, n_host)
+            handle = fetcher.fetch(dict({"values": selected[0], "indices": selected[1]}, **(selected[2] if len(selected) > 2 else {})))
             stats["batches"] += 1
             if pending is not None:
                 write(pending)
             pending = (ids, handle)
         if pending is not None:
             write(pending)
+    if stage_file is not None:
+        stage_file.close()
     stats["seconds"] = time.time() - start
     logging.info("Done with inference. The output file was written to " + out_file_location)
     logging.info("%d videos in %.2f s: reader wait %.2f s, fetch wait %.2f s, formatting %.2f s", stats["videos"], stats["seconds"],
                  stats["reader_wait_s"], stats["fetch_wait_s"], stats["format_s"])
+    if cascade is not None:
+        logging.info("cascade: %s, gate wait %.2f s", cascade_shares(stats["stage_videos"], stats["stage_frames"]), stats["gate_wait_s"])
     return stats
 
 
@@ -367,8 +495,9 @@ def main(argv=None):
     FLAGS.parse(sys.argv[1:] if argv is None else argv)
     logging.basicConfig(level=logging.INFO, format="INFO:evc:%(message)s")
     ensemble = check_flags()
+    cascade = cascade_spec()
     reader = get_reader()
-    return inference(reader, FLAGS.train_dir, FLAGS.input_data_pattern, FLAGS.output_file, FLAGS.batch_size, FLAGS.top_k, ensemble)
+    return inference(reader, FLAGS.train_dir, FLAGS.input_data_pattern, FLAGS.output_file, FLAGS.batch_size, FLAGS.top_k, ensemble, cascade)
 
 
 if __name__ == "__main__":

@@ -791,6 +791,69 @@ def ensemble_topk_rows(preds, k, mode="max", weights=None, priors=None, dense=Fa
     return (values, indices, out) if dense else (values, indices)
 
 
+CASCADE_CONFIDENCE = {"top1": 0, "margin": 1}   # the EVC_CONF_* codes of evc_cascade_confidence_rows
+CASCADE_MAX_STAGES = 8
+CASCADE_MAX_ROWS = 16384   # evc_cascade_pick_rows: the keys of one batch in LDS
+
+
+def _cascade_vector(name, what, t, rows, dtype, device):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise _lib.EvcError("%s: evc ops need device tensors (got a CPU tensor for %s); there is no CPU path" % (name, what))
+    if t.dtype != dtype or t.dim() != 1 or t.shape[0] != rows or not t.is_contiguous() or t.device != device:
+        raise _lib.EvcError("%s: %s must be a contiguous %s [%d] on %s (got %s %s on %s)" % (name, what, dtype, rows, device, t.dtype, tuple(t.shape), t.device))
+
+
+def cascade_confidence_rows(pred, kind, stage, conf, merged, stage_of, active=None):
+    """The gate's first half on the current stream (evc_cascade_confidence_rows).  pred [B, C] f32 (rows contiguous, any row stride): the
+    predictions of stage `stage`; active: None (every row) or uint8 [B], the rows that stage ran.  For those rows, in place: conf [B] f32 = the
+    confidence (kind "top1": the row's largest value; "margin": largest - second largest, duplicates counted, one f32 subtraction; NaN for
+    a row that holds one), merged [B, C] f32 = the row's bits, stage_of [B] uint8 = stage.  Every other row of the three is left untouched.
+    Returns conf."""
+    name = "cascade_confidence_rows"
+    if kind not in CASCADE_CONFIDENCE:
+        raise ValueError("%s: kind %r (%s)" % (name, kind, " | ".join(CASCADE_CONFIDENCE)))
+    for what, x in (("pred", pred), ("merged", merged)):
+        if not torch.is_tensor(x) or not x.is_cuda:
+            raise _lib.EvcError("%s: evc ops need device tensors (got a CPU tensor for %s); there is no CPU path" % (name, what))
+        if x.dtype != F32 or x.dim() != 2 or (x.shape[0] > 0 and x.shape[1] > 1 and x.stride(1) != 1):
+            raise _lib.EvcError("%s: %s must be a 2-D float32 tensor with contiguous rows (got %s %s)" % (name, what, x.dtype, tuple(x.shape)))
+    if tuple(merged.shape) != tuple(pred.shape) or merged.device != pred.device:
+        raise _lib.EvcError("%s: pred %s on %s, merged %s on %s" % (name, tuple(pred.shape), pred.device, tuple(merged.shape), merged.device))
+    B, cols = pred.shape
+    _cascade_vector(name, "conf", conf, B, F32, pred.device)
+    _cascade_vector(name, "stage_of", stage_of, B, torch.uint8, pred.device)
+    if active is not None:
+        _cascade_vector(name, "active", active, B, torch.uint8, pred.device)
+    if not 0 <= int(stage) <= 255:
+        raise ValueError("%s: stage %r (0 .. 255)" % (name, stage))
+    _lib.call("evc_cascade_confidence_rows", _p(pred), pred.stride(0) if B > 1 else cols, _p(active), B, cols, CASCADE_CONFIDENCE[kind],
+              int(stage), _p(conf), _p(merged), merged.stride(0) if B > 1 else cols, _p(stage_of), _stream())
+    return conf
+
+
+def cascade_pick_rows(conf, num_frames, threshold, max_rows=-1, active=None):
+    """The gate's second half on the current stream (evc_cascade_pick_rows): which rows go on to the next stage.  conf [B] f32, num_frames [B]
+    int32 (the batch's original counts), active None or uint8 [B].  Candidates: active rows for which conf >= threshold is false (NaN
+    always); with max_rows >= 0 at most that many are kept, the least confident first (NaN, then conf ascending with -0 = +0, then the
+    lower row).  Returns (active_next uint8 [B], num_frames_next int32 [B] = the counts of the kept rows and 0 elsewhere, count int32 [1])."""
+    name = "cascade_pick_rows"
+    if not torch.is_tensor(conf) or not conf.is_cuda:
+        raise _lib.EvcError("%s: evc ops need device tensors (got a CPU tensor for conf); there is no CPU path" % name)
+    if conf.dim() != 1:
+        raise _lib.EvcError("%s: conf must be a float32 vector (got %s %s)" % (name, conf.dtype, tuple(conf.shape)))
+    B = int(conf.shape[0])
+    _cascade_vector(name, "conf", conf, B, F32, conf.device)
+    _cascade_vector(name, "num_frames", num_frames, B, torch.int32, conf.device)
+    if active is not None:
+        _cascade_vector(name, "active", active, B, torch.uint8, conf.device)
+    active_next = torch.empty(B, dtype=torch.uint8, device=conf.device)
+    num_frames_next = torch.empty(B, dtype=torch.int32, device=conf.device)
+    count = torch.zeros(1, dtype=torch.int32, device=conf.device) if B == 0 else torch.empty(1, dtype=torch.int32, device=conf.device)
+    _lib.call("evc_cascade_pick_rows", _p(conf), _p(active), _p(num_frames), B, float(threshold), int(max_rows), _p(active_next),
+              _p(num_frames_next), _p(count), _stream())
+    return active_next, num_frames_next, count
+
+
 # ---------------------------------------------------------------------------
 def moe_tail_fwd(gate_logits, expert_logits, B, V, M, pred, rowsum):
     _lib.call("evc_moe_tail_fwd", _p(gate_logits), _p(expert_logits), B, V, M, _p(pred), _p(rowsum), _stream())

@@ -21,6 +21,10 @@ the per-class positive counts, which EvaluationMetrics.accumulate_selected turns
 ``--run_once True``) evaluates the combination of several checkpoints: every member runs on the batch, ops.ensemble_topk_rows writes the
 combined [B, 4716] predictions, and the loss (--label_loss; by default ops.ce_loss) and the metrics - host or --metrics_on_device - are those of the combination;
 no student_state_loss is reported and --train_dir only receives events.jsonl.
+``--cascade_dirs`` (+ --cascade_towers / --cascade_every_n / --cascade_sampling / --cascade_confidence / --cascade_thresholds /
+--cascade_fractions, see inference.py; needs ``--run_once True``) evaluates a confidence cascade the same way: cascade.CascadeGraph merges
+each video's predictions from the last stage that ran it, loss and metrics are those of the merged predictions, and the share of the
+videos and the frames each stage read are logged and returned as ``cascade_stage_videos`` / ``cascade_stage_frames``.
 """
 from __future__ import annotations
 
@@ -76,6 +80,18 @@ def build_ensemble(reader, model, spec, batch_size, device, label_loss=None):
     return _CombinedMembers(graph, spec, max(int(sd.get("global_step", 0)) for sd in sds), label_loss)
 
 
+def build_cascade(reader, model, spec, batch_size, device, label_loss=None):
+    """The stages of an inference.cascade_spec(), restored, behind one step() that returns the merged predictions."""
+    from . import inference
+    if not isinstance(model, frame_level_models.HierarchicalLstmModel):
+        raise NotImplementedError("a cascade serves H-LSTM teacher / student towers; model %s has no path here" % type(model).__name__)
+    sds, members, _ = inference.load_members(spec)
+    graph = inference.build_cascade_graph(reader, members, batch_size, device, spec)
+    graph.restore(sds)
+    inference.log_cascade_stages(spec, members)
+    return _CascadeStages(graph, spec, max(int(sd.get("global_step", 0)) for sd in sds), label_loss)
+
+
 def _batches(reader, device):
     if FLAGS.eval_data_pattern == "synthetic":
         for i, (q, y, n, nh) in enumerate(synthetic_batches(FLAGS.batch_size, sum(reader.feature_sizes), device, FLAGS.synthetic_videos, 1, 4321)):
@@ -91,7 +107,9 @@ def check_flags():
         top_max = min(ops.TOPK_MAX_K, NUM_CLASSES)
         if not 1 <= FLAGS.top_k <= top_max:
             raise ValueError("--top_k %d: must be in [1, %d] with --metrics_on_device" % (FLAGS.top_k, top_max))
-    from .inference import ensemble_spec
+    from .inference import cascade_spec, ensemble_spec
+    if cascade_spec() is not None and not FLAGS.run_once:
+        raise ValueError("--cascade_dirs needs --run_once True: there is no one directory to poll for the checkpoints of several stages")
     spec = ensemble_spec(allow_preds_files=False)
     if spec is not None and not FLAGS.run_once:
         raise ValueError("--ensemble_dirs needs --run_once True: there is no one directory to poll for the checkpoints of several members")
@@ -118,8 +136,42 @@ class _CombinedMembers:
         return {"predictions": combined, "loss": self._loss[0]}
 
 
+class _CascadeStages(_CombinedMembers):
+    """A cascade behind the step() of an EvalGraph: cascade.CascadeGraph's merged matrix as "predictions", its label loss (--label_loss) as
+    "loss"; the rows and frames of every stage are summed over the batches (``stage_videos`` / ``stage_frames`` / ``gate_wait_s``)."""
+
+    def __init__(self, graph, spec, global_step, label_loss=None):
+        super().__init__(graph, spec, global_step, label_loss)
+        self.reset()
+
+    def reset(self):
+        K = len(self.graph.graphs)
+        self.stage_videos, self.stage_frames, self.gate_wait_s = [0] * K, [0] * K, 0.0
+
+    def step(self, x_raw, labels_u8, num_frames, num_frames_host=None):
+        out = self.graph.step(x_raw, labels_u8, num_frames, num_frames_host=num_frames_host)
+        for k, (r, f) in enumerate(zip(out["stage_rows"], out["stage_frames"])):
+            self.stage_videos[k] += r
+            self.stage_frames[k] += f
+        self.gate_wait_s += out["gate_wait_s"]
+        merged = out["predictions"]
+        if self._loss is None:
+            self._loss = torch.zeros(1, dtype=torch.float32, device=merged.device)
+        self._loss.zero_()
+        self.label_loss.fused(merged, labels_u8, self._loss[0:1])
+        return {"predictions": merged, "loss": self._loss[0]}
+
+
 def evaluation_loop(graph, reader, label_loss_fn, summary_writer, evl_metrics, last_global_step_val, device):
     """Run the evaluation loop once (cs/validate.py:192-303).  Returns (global_step_val, epoch_info_dict or None)."""
+    if isinstance(graph, _CascadeStages):
+        graph.reset()
+        step, info = _evaluate_restored(graph, reader, label_loss_fn, summary_writer, evl_metrics, graph.global_step, device)
+        if info is not None:
+            from .inference import cascade_shares
+            info["cascade_stage_videos"], info["cascade_stage_frames"] = list(graph.stage_videos), list(graph.stage_frames)
+            logging.info("cascade: %s, gate wait %.2f s", cascade_shares(graph.stage_videos, graph.stage_frames), graph.gate_wait_s)
+        return step, info
     if isinstance(graph, _CombinedMembers):                              # restored in evaluate(); --run_once: nothing to poll
         return _evaluate_restored(graph, reader, label_loss_fn, summary_writer, evl_metrics, graph.global_step, device)
     ck = latest_checkpoint(FLAGS.train_dir)
@@ -225,6 +277,12 @@ def evaluate(student_only=False, max_evals=None):
     spec = check_flags()
     if spec is not None and student_only:
         raise ValueError("--ensemble_dirs: evaluate an ensemble with validate.py (each member names its own tower)")
+    from .inference import cascade_spec
+    cascade = cascade_spec()
+    if cascade is not None and student_only:
+        raise ValueError("--cascade_dirs: evaluate a cascade with validate.py (each stage names its own tower)")
+    if cascade is not None and cascade["stage_file"]:
+        raise ValueError("--cascade_stage_file is written by inference.py only")
     device = "cuda:%d" % FLAGS.gpu
     torch.cuda.set_device(FLAGS.gpu)
     ops.check_device(FLAGS.gpu)
@@ -234,7 +292,9 @@ def evaluate(student_only=False, max_evals=None):
     label_loss_fn.check(reader.num_classes)
     if FLAGS.eval_data_pattern == "":
         raise IOError("'eval_data_pattern' was not specified. Nothing to evaluate.")
-    if spec is None:
+    if cascade is not None:
+        graph = build_cascade(reader, model, cascade, FLAGS.batch_size, device, label_loss=label_loss_fn)
+    elif spec is None:
         graph = build_graph(reader, model, FLAGS.batch_size, device, student_only, label_loss=label_loss_fn)
     else:
         graph = build_ensemble(reader, model, spec, FLAGS.batch_size, device, label_loss=label_loss_fn)

@@ -934,6 +934,38 @@ int evc_frame_change_keys(const float* x_f32, const uint8_t* x_u8, const int32_t
 int evc_student_frame_select_scored(const int32_t* num_frames, const uint32_t* keys, int B, int T, int every_n, int strategy,
                                     int32_t* src /* [B][T / every_n] */, void* stream);
 
+/* ---- confidence cascade: the gate between two towers (csrc/evc_cascade.hip; an addition) ---------------------------------------------
+ * A cascade runs its cheapest tower on the whole batch and hands only the rows that tower is unsure of to the next one.  The next stage
+ * is the same forward with num_frames = 0 for the settled rows (they drop out of evc_sort_rows_by_len's plan), so the gate is two small
+ * kernels: the confidence of every live row, and the pick of the rows that go on.
+ *
+ * evc_cascade_confidence_rows: pred [rows][ld] f32 are the predictions of stage `stage` (0 .. 255); active [rows] bytes (NULL = every row)
+ * names the rows this stage ran.  For every active row r:
+ *   conf[r]      EVC_CONF_TOP1: the largest value of the row (+0 ranks above -0); EVC_CONF_MARGIN: largest - second largest, duplicates
+ *                counted (two equal maxima give exactly +0), one f32 subtraction, with cols == 1 the second largest is 0.0f.  A row that
+ *                holds a NaN, or whose subtraction is inf - inf, gets the quiet NaN 0x7fc00000;
+ *   merged[r]    [rows][ld_merged]: the row's cols values, exact bits (the row is read from memory once for both);
+ *   stage_of[r]  = stage.
+ * A row with active[r] == 0 is not read and nothing of it is written.  One 256-thread workgroup per row, the grid strides over the rows;
+ * 16 bytes per lane where pred's row and merged's row both start on a 16-byte boundary, 4 bytes otherwise, decided per row; wave64
+ * reductions; no atomics, no scratch.  cols <= 32768, ld >= cols, ld_merged >= cols; rows == 0 launches nothing; anything else is
+ * EVC_ERR_BAD_ARG before any launch.
+ *
+ * evc_cascade_pick_rows: conf / active as above, num_frames [rows] the batch's ORIGINAL frame counts.  The candidates are the active rows
+ * for which conf[r] >= threshold is false (NaN always; threshold +inf: every active row; -inf: no row without a NaN).  With max_rows >= 0
+ * and more candidates than that, the max_rows least confident are kept: NaN first, then conf ascending with -0 = +0, then the lower row;
+ * max_rows == -1 keeps every candidate.  active_next[r] = 1 for a kept candidate and 0 for every other row (inactive ones included),
+ * num_frames_next[r] = active_next[r] ? num_frames[r] : 0, count[0] = the number kept.  One workgroup, keys in LDS, an exact radix select
+ * on the ordered 32-bit key with the row as tie-break; integer LDS atomics only: two calls give the same bits.  rows <= 16384 (more is
+ * EVC_ERR_BAD_SHAPE); rows == 0 launches nothing (count is not written); rows < 0, max_rows < -1 or a NULL conf / num_frames / output is
+ * EVC_ERR_BAD_ARG before any launch. */
+#define EVC_CONF_TOP1 0
+#define EVC_CONF_MARGIN 1
+int evc_cascade_confidence_rows(const float* pred, int64_t ld, const uint8_t* active, int rows, int cols, int kind, int stage, float* conf,
+                                float* merged, int64_t ld_merged, uint8_t* stage_of, void* stream);
+int evc_cascade_pick_rows(const float* conf, const uint8_t* active, const int32_t* num_frames, int rows, float threshold, int max_rows,
+                          uint8_t* active_next, int32_t* num_frames_next, int32_t* count, void* stream);
+
 /* utility: out[i] = value for n floats (avoids torch for tiny fills inside C loops) */
 int evc_fill_f32(float* p, int64_t n, float value, void* stream);
 /* Measurement aid, not part of the path: `blocks` workgroups of `threads` threads with `lds_bytes` of LDS each stay resident for
