@@ -536,9 +536,12 @@ class _TrainGraph(_StepGraph):
         self.flush()
         self._apply_gradients(batch_size, lr)
 
-    def _serial_step(self, students, xt, tp, xss, sps, labels_u8, dps, apply, loss_section):
+    def _serial_step(self, students, xt, tp, xss, sps, labels_u8, dps, apply, loss_section, teacher_forwards=None):
         """One iteration of ``students`` against the frozen teacher, after the input stage (teacher view ``xt`` and plan ``tp``, per
         student a view, a plan tuple and a dL/dpred buffer).  Returns `out`, the students' dicts as the list out["students"].
+        ``teacher_forwards`` (EnsembleDistillGraph): a callable that runs the forwards of SEVERAL frozen teachers one after another on
+        `main` in place of the one teacher's, and returns (list of states, list of predictions), which ``loss_section`` and `out` then
+        receive as they are; None: the launches of the one-teacher step, unchanged.
 
         Schedule: the teacher's forward (tape-free, the step's longest chain) ONCE on `main`, the students' forwards next to it on
         `side` from the start of the step, one after the other - neither reads the other -; ``loss_section(t_state, t_pred, fwd, ds)``
@@ -559,7 +562,7 @@ class _TrainGraph(_StepGraph):
         if two_streams:
             self._ev_in.record(main)
             side.wait_event(self._ev_in)
-        t_state, t_pred = self.teacher.forward(xt, l1, l2, plan_t)
+        t_state, t_pred = self.teacher.forward(xt, l1, l2, plan_t) if teacher_forwards is None else teacher_forwards()
         mark("teacher_fwd_done", main)
         if two_streams:
             self._ev_fwd.record(main)
@@ -1099,6 +1102,200 @@ class SerialStudentsGraph(_TrainGraph):
         """A list of K dicts keyed by LOSS_SLOTS (host floats).  losses: a copy of losses_for_report taken after an earlier step."""
         v = (self.losses if losses is None else losses).reshape(self.K, 4).tolist()
         return [{name: v[k][i] for i, name in enumerate(self.LOSS_SLOTS)} for k in range(self.K)]
+
+
+class EnsembleDistillGraph(_TrainGraph):
+    """Serial distillation of ONE student against J frozen teachers (1 <= J <= 8) per iteration: the teachers' predictions are combined
+    as an ensemble combines them (``teacher_mode`` "max" | "mean" with ``teacher_weights``), their states by ``rep_weights``, and the
+    student is trained against the combination (ops.distill_losses_ensemble).  ``teachers``: a list of (tower, every_n, student_sampling)
+    as EnsembleGraph's members - 'teacher' = an all-frames tower (scope `model`; every_n and the word are ignored), 'student' = a
+    few-frame tower (scope `model_student`) at its own every_n and frame selection: teacher-assistant distillation.  Entry 0 is a
+    'teacher' tower: it is `self.teacher`, the model/* of the checkpoint.  The student is built as DistillGraph(mode="serial") builds
+    its own (seed + 1, its own FramePlan); with one teacher and weight 1 the step computes what that graph computes.  global_step += 1
+    per iteration.  One device, precision "bf16"."""
+
+    LOSS_SLOTS = DistillGraph.LOSS_SLOTS
+    MAX_TEACHERS = ops.DISTILL_MAX_TEACHERS
+    mode = "ensemble"
+
+    def __init__(self, batch_size, teachers=(("teacher", 1, "uniform"),), every_n=10, teacher_mode="mean", teacher_weights=None,
+                 rep_weights=None, student_sampling="uniform", distill_losses=DistillGraph.DISTILL_LOSSES, feature_size=1152,
+                 vocab_size=4716, max_frames=300, num_inputs_to_lstm=20, num_inputs_l1_student=5, lstm_cells=1024, lstm_layers=2,
+                 num_mixtures=2, base_learning_rate=0.001, learning_rate_decay=1.0, learning_rate_decay_examples=4000000,
+                 regularization_penalty=2.0, clip_gradient_norm=1.0, count_rep_twice=True, device="cuda:0", seed=7, process_group=None,
+                 overlap_towers=True, precision="bf16", sampling_seed=0):
+        teachers = [tuple(t) + (1, "uniform")[len(t) - 1:] for t in teachers]
+        J = len(teachers)
+        if not 1 <= J <= self.MAX_TEACHERS:
+            raise ValueError("EnsembleDistillGraph: %d teachers (1 .. %d)" % (J, self.MAX_TEACHERS))
+        for tower, _, _ in teachers:
+            if tower not in ("teacher", "student"):
+                raise ValueError("EnsembleDistillGraph: tower %r (teacher | student)" % (tower,))
+        if teachers[0][0] != "teacher":
+            raise ValueError("EnsembleDistillGraph: entry 0 is a %r tower: the checkpoint's model/* is entry 0, a 'teacher' tower" % (teachers[0][0],))
+        if teacher_mode not in ops.ENSEMBLE_MODES:
+            raise ValueError("EnsembleDistillGraph: teacher_mode %r (max | mean)" % (teacher_mode,))
+        if teacher_weights is not None and teacher_mode != "mean":
+            raise ValueError("EnsembleDistillGraph: teacher_weights are read in teacher_mode 'mean' only")
+        w = np.full(J, np.float32(1) / np.float32(J), np.float32) if teacher_weights is None else np.asarray(teacher_weights, np.float32).reshape(-1)
+        r = np.asarray([1.0] + [0.0] * (J - 1) if rep_weights is None else rep_weights, np.float32).reshape(-1)
+        if w.size != J or r.size != J:
+            raise ValueError("EnsembleDistillGraph: %d teacher_weights and %d rep_weights for %d teachers" % (w.size, r.size, J))
+        world = 1
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            world = torch.distributed.get_world_size(process_group)
+        if world > 1:
+            raise ValueError("EnsembleDistillGraph is not data parallel (process group of %d ranks): train the student against the "
+                             "frozen teachers on one device" % world)
+        if precision != "bf16":
+            raise ValueError("EnsembleDistillGraph: precision %r (bf16 only: the input image of the other layouts is decided over the towers "
+                             "that share it)" % (precision,))
+        self.distill_losses = check_distill_losses(distill_losses)
+        if not r.any():
+            raise ValueError("EnsembleDistillGraph: every rep_weight is 0: L_REP and its gradient need a combined state (leave the term out "
+                             "of the training with distill_losses instead)")
+        validate_every_n(every_n, num_inputs_l1_student, max_frames)
+        for tower, e, _ in teachers:
+            if tower == "student":
+                validate_every_n(int(e), num_inputs_l1_student, max_frames)
+        self.teacher_towers = tuple(t[0] for t in teachers)
+        self.teacher_every_n = tuple(1 if t[0] == "teacher" else int(t[1]) for t in teachers)
+        self.teacher_sampling = tuple("uniform" if t[0] == "teacher" else ops.check_student_sampling(t[2]) for t in teachers)
+        self.teacher_mode = teacher_mode
+        self.teacher_weights = None if teacher_mode == "max" else w
+        self.rep_weights = r
+        self.J, self.B, self.every_n = J, batch_size, every_n
+        self.student_sampling, self.sampling_seed = ops.check_student_sampling(student_sampling), int(sampling_seed)
+        self.max_frames, self.C1, self.C2 = max_frames, num_inputs_to_lstm, num_inputs_l1_student
+        self.lr0, self.lr_decay, self.lr_decay_examples = base_learning_rate, learning_rate_decay, learning_rate_decay_examples
+        self.reg_pen, self.clip = regularization_penalty, clip_gradient_norm
+        self.rep_w = 2.0 if count_rep_twice else 1.0
+        self.device = torch.device(device)
+        self.precision, self.row_plans = precision, True
+        self.world, self.dp = 1, False
+        self.global_step = 0
+        self.teachers = []
+        for tower, e in zip(self.teacher_towers, self.teacher_every_n):
+            if tower == "teacher":
+                tw = HLstmTower(batch_size, max_frames, num_inputs_to_lstm, feature_size, vocab_size, lstm_cells, lstm_layers, num_mixtures,
+                                device, False, "model", seed)
+            else:
+                tw = HLstmTower(batch_size, max_frames // e, num_inputs_l1_student, feature_size, vocab_size, lstm_cells, lstm_layers,
+                                num_mixtures, device, False, "model_student", seed + 1)
+            tw.store.drop_training_state()
+            self.teachers.append(tw)
+        self.teacher = self.teachers[0]
+        self.student = HLstmTower(batch_size, max_frames // every_n, num_inputs_l1_student, feature_size, vocab_size, lstm_cells, lstm_layers,
+                                  num_mixtures, device, True, "model_student", seed + 1)
+        # one all-frames input pass for every 'teacher' tower; one pass each for the 'student'-tower teachers and the trained student
+        self._t_frames = FramePlan(teacher=self.teacher, C1=self.C1, C2=self.C2, max_frames=max_frames)
+        self._a_frames = [None if tower == "teacher" else FramePlan(None, tw, e, self.C1, self.C2, max_frames, True, word, self.sampling_seed)
+                          for tower, tw, e, word in zip(self.teacher_towers, self.teachers, self.teacher_every_n, self.teacher_sampling)]
+        self.frames = FramePlan(None, self.student, every_n, self.C1, self.C2, max_frames, True, self.student_sampling, self.sampling_seed)
+        # [0:4] the LOSS_SLOTS, [4:4 + J] every teacher's own CE (evc_distill_losses_ensemble's teacher_ce); 12 floats = three rows of four
+        self.losses = torch.zeros(4 + self.MAX_TEACHERS, dtype=F32, device=self.device)
+        self._dp_s = self._ds_serial = self._pred_comb = None
+        self._student_applied = False
+        self.overlap_towers = overlap_towers
+        self.defer_updates = os.environ.get("EVC_DEFER_UPDATES", "0") == "1"
+        self._make_streams()
+
+    S = property(lambda self: self.frames.S)
+    last_frame_table = property(lambda self: self.frames.last_frame_table)
+
+    def _towers(self):
+        return [self.student]
+
+    def teacher_meta(self):
+        """What a checkpoint records of the teachers besides their sources: towers, every_n, sampling, mode, weights, rep weights."""
+        return dict(towers=list(self.teacher_towers), every_n=list(self.teacher_every_n), sampling=list(self.teacher_sampling),
+                    mode=self.teacher_mode, weights=None if self.teacher_weights is None else [float(x) for x in self.teacher_weights],
+                    rep_weights=[float(x) for x in self.rep_weights])
+
+    def step(self, x_raw, labels_u8, num_frames, apply=True, num_frames_host=None):
+        """One iteration (DistillGraph.step's stream semantics and arguments)."""
+        return self._on_main((x_raw, labels_u8, num_frames), num_frames_host, lambda nh: self._step(x_raw, labels_u8, num_frames, apply, nh))
+
+    def _step(self, x_raw, labels_u8, num_frames, apply, nh):
+        """The input stage - one all-frames pass shared by the 'teacher' towers, one pass per 'student'-tower teacher and one for the
+        trained student -, then _serial_step: the J teacher forwards one after another on `main`, the student's forward on `side` from the
+        start, the loss section ops.distill_losses_ensemble on `side` once all are done, the student's backward and update as ever.
+        `out`: DistillGraph's keys, "predictions" being the combined row the student is trained against; "teacher_predictions" /
+        "teacher_states": the J teachers' own, "teacher_label_losses": their CE."""
+        B, V = x_raw.shape[0], labels_u8.shape[1]
+        if self._dp_s is None or self._dp_s.shape[0] != B:
+            self._dp_s = torch.empty((B, V), dtype=F32, device=self.device)
+            self._pred_comb = torch.empty((B, V), dtype=F32, device=self.device)
+        tp, _ = frame_counts_and_plans(self._t_frames, num_frames, nh, True, False)
+        xt, _ = input_views(self._t_frames, x_raw, num_frames, tp, None, False)
+        # the keys of the content-aware strategies depend on the batch alone: once, for every tower that ranks by them
+        plans = [p for p in self._a_frames if p is not None] + [self.frames]
+        keys = ops.frame_change_keys(x_raw, num_frames) if any(scored_sampling(p) for p in plans) else None
+        a_in = []
+        for p in self._a_frames:
+            if p is None:
+                a_in.append(None)
+                continue
+            p.sampling_draw, p.sampling_row0 = 0, 0                       # a frozen tower sees the frames it is served with: draw 0, as EvalGraph
+            _, sp_a = frame_counts_and_plans(p, num_frames, nh, False, True)
+            a_in.append((input_views(p, x_raw, num_frames, None, sp_a, True, keys=keys)[1], sp_a))
+        fp = self.frames
+        fp.sampling_draw, fp.sampling_row0 = self.global_step, 0          # one train op per iteration: a new "random" draw per step
+        _, sp = frame_counts_and_plans(fp, num_frames, nh, False, True)
+        xs = input_views(fp, x_raw, num_frames, None, sp, True, keys=keys)[1]
+        on = self.distill_losses
+
+        def teacher_forwards():
+            states, preds = [], []
+            for tw, a in zip(self.teachers, a_in):
+                if a is None:
+                    st, pr = tw.forward(xt, tp[0], tp[1], tp[2])
+                else:
+                    st, pr = tw.forward(a[0], a[1][1], a[1][2], a[1][3])
+                states.append(st)
+                preds.append(pr)
+            return states, preds
+
+        def loss_section(t_states, t_preds, fwd, ds):
+            (s_state, s_pred), = fwd
+            ops.distill_losses_ensemble(t_preds, [st if rw != 0 else None for st, rw in zip(t_states, self.rep_weights)], labels_u8, s_pred,
+                                        s_state, self.losses[0:4], self._dp_s, ds[0], mode=self.teacher_mode, weights=self.teacher_weights,
+                                        rep_weights=self.rep_weights, g_ce=(1.0 / B) if "ce" in on else 0.0,
+                                        g_kl=1.0 if "pred" in on else 0.0, g_rep=self.rep_w if "rep" in on else 0.0,
+                                        teacher_ce=self.losses[4:4 + self.J], pred_comb=self._pred_comb)
+
+        out = self._serial_step([self.student], xt, tp, [xs], [sp], labels_u8, [self._dp_s], apply, loss_section, teacher_forwards)
+        out.update(out.pop("students")[0])
+        out.update(teacher_predictions=out["predictions"], teacher_states=out.pop("teacher_state"), predictions=self._pred_comb,
+                   teacher_label_losses=self.losses[4:4 + self.J])
+        out["teacher_state"] = out["teacher_states"][0]
+        return out
+
+    def _apply_gradients(self, batch_size, lr=None):
+        """The student's train op; global_step += 1 for the iteration."""
+        l2c = self.reg_pen * 1e-8
+        if lr is None:
+            lr = self._lr_l2c(batch_size)[0]
+        if not self._student_applied:
+            self.student.apply_gradients(lr, self.clip, l2c)
+        self.global_step += 1
+        self._student_applied = False
+
+    def consolidate(self):
+        """One rank: nothing is sharded; the deferred updates are joined (as DistillGraph.consolidate does first)."""
+        self.flush()
+
+    @property
+    def losses_for_report(self):
+        return self.losses
+
+    def loss_report(self, losses=None):
+        """Host floats keyed by LOSS_SLOTS ("label_loss": the CE of the combined prediction), plus "teacher_<j>_label_loss" for each of
+        the J teachers.  losses: a copy of losses_for_report taken after an earlier step."""
+        v = (self.losses if losses is None else losses).reshape(-1).tolist()
+        rep = {k: v[i] for i, k in enumerate(self.LOSS_SLOTS)}
+        rep.update({"teacher_%d_label_loss" % j: v[4 + j] for j in range(self.J)})
+        return rep
 
 
 class EvalGraph(_StepGraph):

@@ -172,6 +172,24 @@ _define("serial_sampling", "", _serial_sampling, "one --student_sampling word pe
         "(--student_sampling_seed is shared)")
 _define("serial_losses", "", _serial_losses, "one --distill_losses subset per --serial_student_dirs entry, its words joined with '+' "
         "(rep+pred+ce,rep,rep+pred); '' = --distill_losses for all")
+# ---- ensemble distillation (train): one student against SEVERAL frozen teachers, combined as an ensemble combines them -----------------
+_define("teacher_dirs", "", str, "comma separated checkpoint directories of 1 .. 8 frozen teachers (a directory may repeat with another "
+        "tower).  Set: the student is trained against their combination (distill.EnsembleDistillGraph): every teacher runs forward only, "
+        "the predictions are combined as --teacher_mode says, the states by --teacher_rep_weights, one train op per iteration "
+        "(global_step += 1).  Entry 0 is a teacher tower; the checkpoint keeps its model/* bit-identical next to model_student/*.  On resume "
+        "the student and entry 0 come from --train_dir, the other teachers from --teacher_dirs again (the list must be the recorded one).  "
+        "HierarchicalLstmModel, --precision bf16, --label_loss CrossEntropyLoss, one rank; not with --teacher_dir, --serial_student_dirs, "
+        "--teacher_only or train_finetune")
+_define("teacher_towers", "", str, "one word per --teacher_dirs entry from auto|teacher|student, as --ensemble_towers (student = the "
+        "checkpoint's model_student/*, a teaching assistant); '' = auto for all")
+_define("teacher_every_n", "", str, "one every_n per --teacher_dirs entry (ignored for teacher towers); '' = --every_n for all")
+_define("teacher_sampling", "", str, "one --student_sampling word per --teacher_dirs entry (ignored for teacher towers); '' = "
+        "--student_sampling for all")
+_define("teacher_mode", "mean", str, "max (per-class maximum) | mean (weighted mean): how the teachers' predictions are combined")
+_define("teacher_weights", "", str, "comma separated prediction weights, one per --teacher_dirs entry; --teacher_mode mean only; '' = 1 / J each")
+_define("teacher_rep_weights", "", str, "comma separated weights of the teachers' states in L_REP's target; '' = 1,0,...,0: the state of "
+        "entry 0 alone (a mean over independently trained teachers has no common basis; over a teacher and the students distilled from it, "
+        "it has)")
 # ---- ensembles (inference / validate; cs/inference_ensemble.py:28-61 has preds_pattern, the others are additions) -----------------------
 _define("ensemble_dirs", "", str, "comma separated checkpoint directories of the ensemble's members (1 .. 8); '' = the single model of "
         "--train_dir, which is not consulted otherwise.  Every member runs its forward on the same batch and ops.ensemble_topk_rows "

@@ -1014,6 +1014,60 @@ def distill_losses_multi(pred_t, rowsum_t, labels_u8, state_t, preds_s, rowsums_
               arr(states_s), scales[0], scales[1], scales[2], arr(dpreds_s), arr(dstates_s), B, V, D, _p(losses), _p(ws), _stream())
 
 
+DISTILL_MAX_TEACHERS = 8   # evc_distill_losses_ensemble: one student against 1 <= J <= 8 teachers
+
+
+def distill_losses_ensemble(preds_t, states_t, labels_u8, pred_s, state_s, losses, dpred_s=None, dstate_s=None, mode="mean", weights=None,
+                            rep_weights=None, g_ce=1.0, g_kl=1.0, g_rep=1.0, teacher_ce=None, pred_comb=None):
+    """distill_losses for one student against J teachers in one launch + its finish (evc_distill_losses_ensemble).  preds_t: list of J
+    [B, V] f32 tensors, combined as ensemble_topk_rows(dense=True) combines them (mode "max" | "mean"; weights [J], mean only, default
+    np.float32(1) / np.float32(J) each); states_t: list of J [B, D] tensors, or None where rep_weights[j] == 0 (rep_weights default
+    1, 0, ..., 0: the state of entry 0); the combined state is rep_weights[j] * states_t[j] summed left to right in f32.  losses[0:4] +=
+    (CE of the combined row, L_REP, L_PRED, student CE); teacher_ce [J] (optional) += each teacher's own CE; pred_comb [B, V] (optional)
+    receives the combined row.  For a given combined row and state the outputs do not depend on J."""
+    import ctypes as C
+    import numpy as np
+    preds_t = list(preds_t)
+    J = len(preds_t)
+    if not 1 <= J <= DISTILL_MAX_TEACHERS:
+        raise ValueError("distill_losses_ensemble: %d teachers (1 .. %d)" % (J, DISTILL_MAX_TEACHERS))
+    if mode not in ENSEMBLE_MODES:
+        raise ValueError("distill_losses_ensemble: mode %r (max | mean)" % (mode,))
+    if weights is None:
+        w = np.full(J, np.float32(1) / np.float32(J), np.float32)
+    else:
+        if mode != "mean":
+            raise ValueError("distill_losses_ensemble: weights are read in mode 'mean' only")
+        w = np.asarray(weights, np.float32).reshape(-1)
+    r = np.asarray([1.0] + [0.0] * (J - 1) if rep_weights is None else rep_weights, np.float32).reshape(-1)
+    states_t = [None] * J if states_t is None else list(states_t)
+    if w.size != J or r.size != J or len(states_t) != J:
+        raise ValueError("distill_losses_ensemble: %d weights, %d rep_weights, %d states for %d teachers" % (w.size, r.size, len(states_t), J))
+    B, V = pred_s.shape
+    D = state_s.shape[1]
+    if not r.any() and (g_rep != 0.0 or dstate_s is not None):
+        raise ValueError("distill_losses_ensemble: every rep_weight is 0: no combined state for L_REP's gradient (g_rep = 0 and no dstate_s only)")
+    assert labels_u8.shape == (B, V) and state_s.shape[0] == B and losses.numel() >= 4
+    assert pred_s.dtype == F32 and state_s.dtype == F32 and labels_u8.dtype == torch.uint8 and losses.dtype == F32
+    for t in (pred_s, labels_u8, state_s, losses):
+        assert t.is_cuda and t.is_contiguous()
+    for j in range(J):
+        assert preds_t[j].shape == (B, V) and preds_t[j].dtype == F32 and preds_t[j].is_contiguous() and preds_t[j].is_cuda
+        if r[j] != 0:
+            if states_t[j] is None:
+                raise ValueError("distill_losses_ensemble: teacher %d has rep_weight %g and no state" % (j, r[j]))
+            assert states_t[j].shape == (B, D) and states_t[j].dtype == F32 and states_t[j].is_contiguous()
+    for t, shp in ((dpred_s, (B, V)), (dstate_s, (B, D)), (pred_comb, (B, V))):
+        assert t is None or (t.dtype == F32 and t.shape == shp and t.is_contiguous())
+    assert teacher_ce is None or (teacher_ce.dtype == F32 and teacher_ce.numel() >= J and teacher_ce.is_contiguous())
+    arr = lambda ts: (C.c_void_p * J)(*[_p(t) for t in ts])
+    ws = torch.empty((3 + J) * B + 256, dtype=F32, device=pred_s.device)
+    _lib.call("evc_distill_losses_ensemble", J, arr(preds_t), arr([s if r[j] != 0 else None for j, s in enumerate(states_t)]),
+              (C.c_float * J)(*w.tolist()), (C.c_float * J)(*r.tolist()), ENSEMBLE_MODES[mode], _p(labels_u8), _p(pred_s), _p(state_s),
+              B, V, D, float(g_ce), float(g_kl), float(g_rep), _p(losses), _p(teacher_ce), _p(pred_comb), _p(dpred_s), _p(dstate_s), _p(ws),
+              _stream())
+
+
 def clip_adam_small(ps, gs, ms, vs, sums, clip_norm, lr_t, beta1=0.9, beta2=0.999, eps=1e-8):
     """Per-tensor clip + TF-Adam of up to 16 small tensors (no l2 term) in one launch (evc_clip_adam_small): sums[i] receives {|g_i|^2, 0}."""
     import ctypes as C

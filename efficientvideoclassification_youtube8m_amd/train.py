@@ -19,6 +19,8 @@ Serial distillation (not a reference mode; the paper's second way to train a stu
 student against the frozen teacher of DIR's latest checkpoint (distill.DistillGraph mode "serial").
 ``--serial_student_dirs A/,B/,...`` next to it trains up to 8 students in ONE run against one forward of that teacher per batch
 (distill.SerialStudentsGraph): one checkpoint directory per student, each what a run of its own would have written.
+``--teacher_dirs A/,B/,...`` trains ONE student against the combination of up to 8 frozen teachers - an ensemble folded back into one
+small model, or a teacher next to the teaching assistants distilled from it (distill.EnsembleDistillGraph).
 Multi-GPU: launch with ``python -m torch.distributed.run --nproc-per-node N``;
 ``--gpu`` is then ignored in favour of LOCAL_RANK.
 """
@@ -34,7 +36,7 @@ import numpy as np
 import torch
 
 from . import eval_util, frame_level_models, losses, ops, readers, video_level_models
-from .distill import DistillGraph, SerialStudentsGraph, SingleTowerGraph
+from .distill import DistillGraph, EnsembleDistillGraph, SerialStudentsGraph, SingleTowerGraph
 from .flags import FLAGS, GetListOfFeatureNamesAndSizes
 from .towers import DbofTower, LogisticTower, NetVladTower
 
@@ -69,7 +71,7 @@ def check_serial_flags(finetune=False, world=1, students=_UNSET):
     if students is _UNSET:
         serial_students(finetune, world)    # --serial_student_dirs and its lists: every refusal of theirs, before the rest
     if not serial:
-        if FLAGS.distill_losses != DEFAULT_DISTILL_LOSSES:
+        if FLAGS.distill_losses != DEFAULT_DISTILL_LOSSES and not FLAGS.teacher_dirs.strip():
             raise ValueError("--distill_losses %s needs --teacher_dir: it selects the student's losses of serial distillation "
                              "(the teacher+student graph trains on all of them)" % FLAGS.distill_losses)
         return False
@@ -130,6 +132,121 @@ def serial_students(finetune=False, world=1):
     return out
 
 
+TEACHER_LIST_FLAGS = ("teacher_towers", "teacher_every_n", "teacher_sampling", "teacher_weights", "teacher_rep_weights")
+
+
+def ensemble_teachers(finetune=False, world=1):
+    """--teacher_dirs and its lists: None when no directories are given, else {"dirs", "towers" (auto | teacher | student words),
+    "every_n", "sampling", "mode", "weights" (float32 [J], None in mode max), "rep_weights" (float32 [J])}, one entry per teacher ('' lists
+    filled from --every_n / --student_sampling, the weights with float32(1) / float32(J), the rep weights with 1, 0, ..., 0).  Every
+    refused combination is a ValueError here, before anything touches the device."""
+    from .distill import validate_every_n
+    words = lambda text: [w.strip() for w in text.split(",")] if text.strip() else []
+    dirs = words(FLAGS.teacher_dirs)
+    lists = {k: words(getattr(FLAGS, k)) for k in TEACHER_LIST_FLAGS}
+    if not dirs:
+        stray = [k for k, v in lists.items() if v]
+        if stray:
+            raise ValueError("--%s needs --teacher_dirs (the frozen teachers the student is trained against)" % stray[0])
+        return None
+    J = len(dirs)
+    what = "--teacher_dirs %s" % FLAGS.teacher_dirs
+    if J > EnsembleDistillGraph.MAX_TEACHERS or "" in dirs:
+        raise ValueError("%s: %d entries (1 .. %d, none empty)" % (what, J, EnsembleDistillGraph.MAX_TEACHERS))
+    if FLAGS.teacher_dir:
+        raise ValueError("%s with --teacher_dir %s: one frozen teacher (--teacher_dir) or several (--teacher_dirs), not both" % (what, FLAGS.teacher_dir))
+    if FLAGS.serial_student_dirs.strip():
+        raise ValueError("%s with --serial_student_dirs: several students against several teachers in one run is not built" % what)
+    if getattr(FLAGS, "teacher_only", False):
+        raise ValueError("%s with --teacher_only: frozen teachers cannot be the tower that is trained" % what)
+    if finetune:
+        raise ValueError("%s with --finetune: train_finetune trains the student on L_CE alone, without a teacher" % what)
+    if world > 1:
+        raise ValueError("%s on %d ranks: ensemble distillation is not data parallel yet, run it on one device" % (what, world))
+    if FLAGS.model != "HierarchicalLstmModel":
+        raise ValueError("%s: ensemble distillation is built for HierarchicalLstmModel, not --model %s" % (what, FLAGS.model))
+    if FLAGS.label_loss != "CrossEntropyLoss":
+        raise ValueError("%s with --label_loss %s: ensemble distillation has CrossEntropyLoss built into its loss kernel "
+                         "(evc_distill_losses_ensemble)" % (what, FLAGS.label_loss))
+    if FLAGS.precision != "bf16":
+        raise ValueError("%s with --precision %s: the teachers share their input image in bf16 only" % (what, FLAGS.precision))
+    if FLAGS.teacher_mode not in ops.ENSEMBLE_MODES:
+        raise ValueError("--teacher_mode %r (max | mean)" % FLAGS.teacher_mode)
+    for key in TEACHER_LIST_FLAGS:
+        if lists[key] and len(lists[key]) != J:
+            raise ValueError("--%s %s: %d entries for the %d directories of %s" % (key, getattr(FLAGS, key), len(lists[key]), J, what))
+    towers = lists["teacher_towers"] or ["auto"] * J
+    for t in towers:
+        if t not in ("auto", "teacher", "student"):
+            raise ValueError("--teacher_towers: %r (auto | teacher | student)" % t)
+    if towers[0] == "student":
+        raise ValueError("--teacher_towers %s: entry 0 of --teacher_dirs is the model/* of the checkpoint, a teacher tower" % FLAGS.teacher_towers)
+    try:
+        every_n = [int(e) for e in lists["teacher_every_n"]] if lists["teacher_every_n"] else [FLAGS.every_n] * J
+    except ValueError:
+        raise ValueError("--teacher_every_n %r: a comma list of integers, one per --teacher_dirs entry" % FLAGS.teacher_every_n)
+    sampling = [ops.check_student_sampling(w, "--teacher_sampling") for w in lists["teacher_sampling"]] or [FLAGS.student_sampling] * J
+    for t, e in zip(towers, every_n):
+        if t == "student":
+            validate_every_n(e, 5, FLAGS.max_num_frames)
+    validate_every_n(FLAGS.every_n, 5, FLAGS.max_num_frames)
+    weights = None
+    if lists["teacher_weights"] and FLAGS.teacher_mode != "mean":
+        raise ValueError("--teacher_weights needs --teacher_mode mean (max has no weights)")
+    try:
+        if FLAGS.teacher_mode == "mean":
+            weights = (np.asarray([float(x) for x in lists["teacher_weights"]], np.float32) if lists["teacher_weights"]
+                       else np.full(J, np.float32(1) / np.float32(J), np.float32))
+        rep = np.asarray([float(x) for x in lists["teacher_rep_weights"]] if lists["teacher_rep_weights"] else [1.0] + [0.0] * (J - 1), np.float32)
+    except ValueError:
+        raise ValueError("--teacher_weights %r / --teacher_rep_weights %r: comma lists of numbers" % (FLAGS.teacher_weights, FLAGS.teacher_rep_weights))
+    if not rep.any():
+        raise ValueError("--teacher_rep_weights %s: every weight is 0 (leave L_REP out with --distill_losses instead)" % FLAGS.teacher_rep_weights)
+    return dict(dirs=dirs, towers=towers, every_n=every_n, sampling=sampling, mode=FLAGS.teacher_mode, weights=weights, rep_weights=rep)
+
+
+def load_teachers(spec):
+    """The checkpoints of an ensemble_teachers() spec, read on the host: ([state dict per teacher], [tower per teacher], [checkpoint
+    path]).  'auto' resolves as for an ensemble member (inference.member_tower); a directory listed twice is read once.  ValueError
+    when a directory holds no checkpoint, not the tower asked for, or entry 0 does not resolve to a teacher tower."""
+    from .inference import member_tower
+    loaded, sds, towers, cks = {}, [], [], []
+    for d, word in zip(spec["dirs"], spec["towers"]):
+        if d not in loaded:
+            ck = latest_checkpoint(d)
+            if ck is None:
+                raise ValueError("--teacher_dirs: no model.ckpt-*.pt checkpoint in %s" % d)
+            loaded[d] = (ck, torch.load(ck, map_location="cpu"))
+        ck, sd = loaded[d]
+        sds.append(sd)
+        cks.append(ck)
+        towers.append(member_tower(sd, word, ck))
+    if towers[0] != "teacher":
+        raise ValueError("--teacher_dirs / --teacher_towers: entry 0 (%s) resolves to a %s tower; entry 0 is the model/* of the checkpoint, a "
+                         "teacher tower" % (cks[0], towers[0]))
+    return sds, towers, cks
+
+
+def teacher_record(spec, towers, cks):
+    """What a --teacher_dirs checkpoint records of its teachers (metadata key "distill_teachers"): plain lists, strings and floats."""
+    return {"dirs": list(spec["dirs"]), "checkpoints": [os.path.basename(c) for c in cks], "towers": list(towers),
+            "every_n": [1 if t == "teacher" else int(e) for t, e in zip(towers, spec["every_n"])],
+            "sampling": ["uniform" if t == "teacher" else w for t, w in zip(towers, spec["sampling"])], "mode": spec["mode"],
+            "weights": None if spec["weights"] is None else [float(x) for x in spec["weights"]],
+            "rep_weights": [float(x) for x in spec["rep_weights"]]}
+
+
+def check_recorded_teachers(recorded, current, ck=""):
+    """Resume of a --teacher_dirs run: the teachers the flags name must be the ones the checkpoint ``ck`` records (teacher_record of
+    both); anything else is a ValueError that shows both."""
+    if recorded is None:
+        raise ValueError("--teacher_dirs: the checkpoint %s to resume from records no teacher list (it was not written by a --teacher_dirs "
+                         "run); the flags name %s" % (ck, current))
+    if recorded != current:
+        raise ValueError("--teacher_dirs: the checkpoint %s was trained against other teachers than the flags name.\n  recorded: %s\n  "
+                         "flags:    %s\n(resume with the recorded list, or start a new model)" % (ck, recorded, current))
+
+
 def serial_students_checkpoints(dirs, start_new_model=False):
     """The checkpoints a --serial_student_dirs run resumes from: one path per directory when every directory holds one and all are
     at the same global_step, None for a fresh start (--start_new_model, or no directory holds one).  Anything else is a ValueError
@@ -186,7 +303,8 @@ def check_label_loss(label_loss_fn, finetune=False):
                          % type(label_loss_fn).__name__)
 
 
-def build_graph(model, label_loss_fn, feature_size, batch_size, every_n, device, finetune=False, process_group=None, students=_UNSET):
+def build_graph(model, label_loss_fn, feature_size, batch_size, every_n, device, finetune=False, process_group=None, students=_UNSET,
+                teachers=None):
     """Equivalent of cs/train.py:185-427 (and cs/train_finetune.py:185-331 when
     finetune): returns the graph object whose ``step`` runs one iteration."""
     check_label_loss(label_loss_fn, finetune)
@@ -200,6 +318,16 @@ def build_graph(model, label_loss_fn, feature_size, batch_size, every_n, device,
         # every_n == 1 (the reference's default, cs/train.py:100-101) still builds and trains model_student, on all 300
         # frames in 5 chunks of 60 (cs/train.py:262-272,349-356): global_step += 2 and the checkpoint holds both scopes.
         # Teacher-only training (BASELINE cfg 2) is not a reference mode: it is asked for with --teacher_only.
+        if teachers is not None:
+            # one student against several frozen teachers (--teacher_dirs): teachers = an ensemble_teachers() spec with resolved "towers"
+            common.pop("label_loss", None)        # (refused for anything but CrossEntropyLoss, which EnsembleDistillGraph has built in)
+            return EnsembleDistillGraph(batch_size, teachers=list(zip(teachers["towers"], teachers["every_n"], teachers["sampling"])),
+                                        every_n=every_n, teacher_mode=teachers["mode"], teacher_weights=teachers["weights"],
+                                        rep_weights=teachers["rep_weights"], student_sampling=FLAGS.student_sampling,
+                                        distill_losses=FLAGS.distill_losses, feature_size=feature_size, vocab_size=NUM_CLASSES,
+                                        max_frames=FLAGS.max_num_frames, num_inputs_to_lstm=FLAGS.num_inputs_to_lstm,
+                                        lstm_cells=FLAGS.lstm_cells, lstm_layers=FLAGS.lstm_layers, num_mixtures=FLAGS.moe_num_mixtures,
+                                        device=device, precision=FLAGS.precision, sampling_seed=FLAGS.student_sampling_seed, **common)
         spec = serial_students(finetune) if students is _UNSET else students
         if spec is not None:
             # K students against one forward of the frozen teacher (--serial_student_dirs): hyper-parameters as below, one of each list per student
@@ -315,6 +443,9 @@ def save_checkpoint(graph, train_dir, rank):
         sd["student_sampling"] = graph.student_sampling          # metadata: the frames this student was trained on (--student_sampling)
     if getattr(graph, "mode", None) == "serial":                 # metadata: trained against the frozen teacher in model/*, on these losses
         sd["distill_mode"], sd["distill_losses"] = "serial", ",".join(graph.distill_losses)
+    if getattr(graph, "mode", None) == "ensemble":               # metadata: trained against several frozen teachers, model/* being entry 0
+        sd["distill_mode"], sd["distill_losses"] = "ensemble", ",".join(graph.distill_losses)
+        sd["distill_teachers"] = getattr(graph, "teacher_record", None) or graph.teacher_meta()
     fn = getattr(graph, "label_loss", None)
     if fn is not None and not losses.is_default(fn):             # metadata: the --label_loss these weights were trained on (the default: no key)
         sd["label_loss"] = type(fn).__name__
@@ -380,9 +511,19 @@ def main(argv=None):
     logging.basicConfig(level=logging.INFO, format="INFO:evc:%(message)s")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
+    ens = ensemble_teachers(finetune, world)
     multi = serial_students(finetune, world)
     serial = check_serial_flags(finetune, world, students=multi)
     check_label_loss(find_class_by_name(FLAGS.label_loss, [losses])(), finetune)
+    ens_sds = None
+    if ens:
+        # the teachers' checkpoints on the host, and - on resume - the recorded list against the flags: all before the device is touched
+        ens_sds, ens_towers, ens_cks = load_teachers(ens)
+        ens = dict(ens, towers=ens_towers)
+        ens_record = teacher_record(ens, ens_towers, ens_cks)
+        ens_resume = None if FLAGS.start_new_model else latest_checkpoint(FLAGS.train_dir)
+        if ens_resume is not None:
+            check_recorded_teachers(torch.load(ens_resume, map_location="cpu").get("distill_teachers"), ens_record, ens_resume)
     multi_cks = serial_students_checkpoints(multi["dirs"], FLAGS.start_new_model) if multi else None
     local = int(os.environ.get("LOCAL_RANK", str(FLAGS.gpu)))
     # test hook (tests/test_gpu_dp.py): several ranks on ONE GPU over gloo, to run this file's multi-rank path on a
@@ -407,7 +548,7 @@ def main(argv=None):
     label_loss_fn = find_class_by_name(FLAGS.label_loss, [losses])()
     if FLAGS.optimizer != "AdamOptimizer":
         raise NotImplementedError("only AdamOptimizer (the reference default, cs/train.py:91) is built")
-    graph = build_graph(model, label_loss_fn, feature_size, FLAGS.batch_size, FLAGS.every_n, device, finetune, students=multi)
+    graph = build_graph(model, label_loss_fn, feature_size, FLAGS.batch_size, FLAGS.every_n, device, finetune, students=multi, teachers=ens)
     logging.info("%s: Built graph.", task)
     ck = None if (FLAGS.start_new_model or multi) else latest_checkpoint(FLAGS.train_dir)
     if multi and multi_cks:
@@ -430,6 +571,14 @@ def main(argv=None):
                          "come from %s", task, FLAGS.teacher_dir, ck)
     if serial and ck is None and getattr(graph, "mode", None) == "serial":
         logging.info("%s: Frozen teacher from %s", task, load_frozen_teacher(graph, FLAGS.teacher_dir))
+    if ens:
+        # entry 0 came with the student from --train_dir on resume (restore_checkpoint above); every other teacher from its directory
+        graph.teacher_record = ens_record
+        for j, (tw, sd_j, ck_j) in enumerate(zip(graph.teachers, ens_sds, ens_cks)):
+            if j > 0 or ck is None:
+                tw.load_state_dict(sd_j)
+                logging.info("%s: Frozen teacher %d (%s tower) from %s", task, j, ens["towers"][j], ck_j)
+        ens_sds = None
     data, num_batches = get_input_data(FLAGS.train_data_pattern, FLAGS.batch_size, feature_size, device, FLAGS.num_epochs,
                                        1234 + rank, rank, world)
     step_limit = agree_step_limit(FLAGS.max_steps, num_batches, world, device)
@@ -439,7 +588,8 @@ def main(argv=None):
     logging.info("%s: Entering training loop.", task)
     start, last_save, it = time.time(), time.time(), 0
     is_multi = isinstance(graph, SerialStudentsGraph)
-    is_distill = isinstance(graph, DistillGraph) or is_multi
+    is_ens = isinstance(graph, EnsembleDistillGraph)
+    is_distill = isinstance(graph, DistillGraph) or is_multi or is_ens
     steps_per_it = 2 if is_distill and not is_multi and graph.mode == "teacher_student" else 1
     copy_stream = torch.cuda.Stream(device=device)
     host_bufs = {}                       # pinned staging, two alternating sets (one may still be read while the next fills)
@@ -494,6 +644,9 @@ def main(argv=None):
             logging.info("%s: training step %d| Hit@1: %.2f| PERR: %.2f| GAP: %.2f| Teacher_Loss: %s| L_REP: %s| L_PRED: %s"
                          "| L_CE: %s", task, snap["global_step"], hit, perr, gap, round(r["label_loss"], 2),
                          round(r["student_loss_state"], 2), round(r["pred_loss"], 2), round(r["student_label_loss"], 2))
+            if is_ens:                   # Teacher_Loss above is the combined prediction's; each teacher's own next to it
+                logging.info("%s: training step %d| Teacher_Losses: %s", task, snap["global_step"],
+                             " ".join("%s" % round(r["teacher_%d_label_loss" % j], 2) for j in range(graph.J)))
         else:
             history.append((snap["global_step"], {"loss": float(snap["slot"]["loss"][0])},
                             {"hit_at_one": float(hit), "perr": float(perr), "gap": float(gap)}))

@@ -530,6 +530,38 @@ int evc_distill_losses_multi(const float* pred_t, const float* rowsum_t, const u
                              const float* const* pred_s, const float* const* rowsum_s, const float* const* state_s,
                              const float* g_ce, const float* g_kl, const float* g_rep, float* const* dpred_s, float* const* dstate_s,
                              int B, int V, int D, float* losses /* [K][4] */, float* workspace, void* stream);
+/* The loss section for ONE student against J frozen teachers (1 <= J <= 8), in one launch + one finish launch (EnsembleDistillGraph): the
+ * teachers are combined into one prediction row P and one state s per video, and the student is trained against those two as
+ * evc_distill_losses_multi trains a student against pred_t := P, state_t := s.
+ *   pred_t / state_t [J] HOST arrays of device pointers ([B][V] / [B][D] f32), w / r [J] HOST arrays (prediction weights, read in mode 1 only
+ *   and then required; representation weights): all read before the call returns, they travel by value in the launch's arguments.
+ *   P, mode 1 (weighted mean): acc = w[0] x_0; acc = acc + w[j] x_j for j ascending, every product and every sum rounded to f32 on its own.
+ *   P, mode 0 (max): the member value with the largest key in the total order of evc_topk_rows (NaN above +inf, -0 ties +0); on equal keys
+ *     the lowest member supplies the bits.  Either way P holds exactly the bits evc_ensemble_topk_rows' dense exit writes for the same
+ *     members, mode and weights with P = 0 prior files; pred_comb [B][V] (may be NULL) receives it.
+ *   s: r[j] state_t[j] summed left to right in f32 (product and sum each rounded on its own) over the entries with r[j] != 0.  An entry with
+ *     r[j] == 0 is not read and its pointer may be NULL; a single entry with r[j] == 1 yields that teacher's bits; no entry at all is s = 0,
+ *     allowed only with g_rep == 0 and dstate_s == NULL.
+ *   losses[4] += CE(P, labels), L_REP(s, state_s), L_PRED(P || pred_s), CE(pred_s, labels); teacher_ce [J] (may be NULL) += CE(pred_t[j], labels),
+ *   value only.  dpred_s / dstate_s (may be NULL) are written once; g_ce / g_kl / g_rep as in evc_distill_losses, a scale of 0 gives exact 0.
+ * The row sums of P and of pred_s are taken in double inside the kernel and the difference -P / p_s + 1 / sum(p_s) is evaluated in double, as
+ * in evc_distill_losses_multi; there are no row-sum inputs, the FLT_MIN rules apply to those sums (sum(P) below FLT_MIN, or NaN: L_PRED 0 and KL
+ * gradient exactly 0 on that row; sum(p_s) below FLT_MIN: clamped to it).  L_PRED's value is the same sum_c P log(P / Q), but its terms cancel
+ * down to the second order where the student is close to P: the ratio P / Q is formed in double, its logarithm is log1pf(ratio - 1) for a ratio in
+ * (0.5, 2), and a row's terms are added in double (rows are joined in f32), which holds 1e-4 relative on that value for such a student too.
+ * For a given P and s the outputs do not depend on J or on how they came about: J = 2 on [p, p] with w = [.5, .5], or mode 0 over copies of p,
+ * gives the bits of J = 1 on [p] with w = [1].  Bit identity with evc_distill_losses(_multi) is not promised (separately compiled).
+ * 16-byte accesses where V % 4 == 0 / (B * D) % 4 == 0, for every array whose own pointer is 16-byte aligned (labels: 4-byte); an array whose
+ * pointer is not takes 4-byte accesses to the same elements in the same order.  Every member row is read twice by the workgroup that owns the
+ * row (the combination is recomputed from cache in the second pass: the same bits, no limit on V).
+ * workspace: (3 + J) * B + 256 floats of scratch; the finish launch adds every list of partials in workgroup order - no float atomics, no
+ * last-block counters: two calls on the same inputs give the same bits, with or without EVC_DETERMINISTIC.
+ * Refused before any launch (EVC_ERR_BAD_ARG / EVC_ERR_BAD_SHAPE): J outside 1..8, a mode other than 0 / 1, a required pointer NULL, every
+ * r[j] == 0 while g_rep != 0 or dstate_s != NULL. */
+int evc_distill_losses_ensemble(int J, const float* const* pred_t, const float* const* state_t, const float* w, const float* r, int mode,
+                                const uint8_t* labels, const float* pred_s, const float* state_s, int B, int V, int D, float g_ce, float g_kl,
+                                float g_rep, float* losses /* [4] */, float* teacher_ce /* [J] */, float* pred_comb, float* dpred_s,
+                                float* dstate_s, float* workspace, void* stream);
 
 /* The label losses of cs/losses.py besides CrossEntropyLoss (--label_loss), value and gradient in one pass, with evc_ce_loss's semantics:
  *   *loss += (1/B) sum_b row_loss_b ;  dpred (= | +=) grad_scale * d(sum_b row_loss_b)/dpred  (the caller passes grad_scale = w / B).
