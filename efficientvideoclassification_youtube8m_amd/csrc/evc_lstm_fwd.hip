@@ -276,6 +276,11 @@ __global__ __launch_bounds__(Cfg::NT) void lstm_fwd_pair_kernel(GemmOperands pa,
   lstm_fwd_step_body<Cfg, false, F16, FP8>(p, e, tiles_m, tiles_n, first ? blockIdx.x : blockIdx.x - n);
 }
 
+
+// ===========================================================================
+// Host side: every entry point describes its layers as FwdLayer records, fwd_step() turns (call, layer, t) into the
+// arguments of one launch, fwd_layer_loop / fwd_wavefront walk the steps, and the entry's launcher picks the kernel for the tile
+// ===========================================================================
 typedef TileCfg<128, 4, 32, 2, 2> CfgLstmBig;    // 128 rows x 32 units x 4 gates
 typedef TileCfg<64, 4, 16, 4, 1> CfgLstmSmall;   // 64 rows x 16 units x 4 gates (M ~ 256 steps)
 // v2 tiles: BM rows x 64 units x 4 gates (256 accumulator columns).  The row count of a step varies with the
@@ -292,7 +297,7 @@ typedef TileCfg3<224, 4, 64, 2, 4, 2> CfgLstmV3_224;
 // 240 rows = 7 row fragments on the producer waves + 8 on their SIMD partners (gemm_core_v3.h, uneven split): 3 585-3 840 live rows are 16 row tiles
 // = 256 workgroups of 240 rows instead of 15 x 16 = 240 workgroups of 256 rows (round 4)
 typedef TileCfg3<240, 4, 64, 2, 4, 2, 7> CfgLstmV3_240;
-typedef TileCfg3<224, 4, 64, 2, 4, 2, 6> CfgLstmV3_224u;      // 6 + 8 instead of 7 + 7: the producer waves issue the LDS-DMA, their partners take the extra row fragment
+typedef TileCfg3<224, 4, 64, 2, 4, 2, 6> CfgLstmV3_224u;      // 6 + 8 instead of 7 + 7: the producer waves issue the LDS-DMA, their partners take the extra row fragment (58.3 -> 58.0 us per launch)
 typedef TileCfg3<192, 4, 64, 2, 4, 2> CfgLstmV3_192;
 typedef TileCfg3<160, 4, 64, 2, 4, 3> CfgLstmV3_160;
 typedef TileCfg2<192, 4, 64, 2, 4, 5, true> CfgLstmV2_192;
@@ -301,17 +306,198 @@ typedef TileCfg2<128, 4, 64, 2, 4, 5, true> CfgLstmV2_128;
 typedef TileCfg2<64, 4, 64, 2, 4, 5, true> CfgLstmV2_64;
 typedef TileCfg3<64, 4, 16, 4, 1, 4> CfgLstmV3Small;         // 64 rows x 16 units x 4 gates on 64-wide K stages, 4 waves (64 KB of LDS: still two workgroups per CU): M ~ batch steps
 
-template <class Cfg, bool SPLIT = false, bool F16 = false, bool FP8 = false, bool XINT = false>
-static inline void launch_lstm_fwd(GemmOperands p, const LstmFwdParams& e, int k1, int k2, hipStream_t st) {
-  p.nk1 = k1 / kdiv<Cfg>(); p.nk2 = k2 / kdiv<Cfg>();
-#ifdef EVC_STAMPS
-  p.stamp_slot = e.t & 7;
-#endif
-  const int tm = ceil_div(e.M, Cfg::BM), tn = ceil_div(e.H, Cfg::BU);
-  launch_cfg<Cfg>(lstm_fwd_step_kernel<Cfg, SPLIT, F16, FP8, XINT>, tm * tn, st, p, e, tm, tn);
+// ---- the call and its layers ------------------------------------------------------------------------------------------------------------
+// What the layers of one call share
+struct FwdShared {
+  const int32_t* len; int T, M, H; long ld_state;
+  const int32_t* row_map; const int32_t* rows_per_step;      // row plan (evc_sort_rows_by_len) or NULL
+  int rows(int t) const { return rows_per_step ? rows_per_step[t] : M; }      // active rows of step t: the prefix [0, rows)
+};
+
+// One layer of a call, in the units the kernels take (16-bit operands in halfwords - bf16_t stands for f16 containers too - e4m3 ones in bytes).
+// Step t contracts [x_t | h_{t-1}] against the rows of B, then - e4m3 forms - the e4m3 parts of the same rows against the rows of B8, and writes
+// slab t + 1 of the h ring; at t = 0 the h segments are absent (h_{-1} = 0).
+struct FwdLayer {
+  // x rows of step t at x + t * M * ldx, kx halfwords contracted.  zx != NULL: that product was hoisted out of the steps ([T][M][4H] f32, added
+  // in the gate tail); the step's only 16-bit segment is then the h ring itself
+  const bf16_t* x = nullptr; long ldx = 0; int kx = 0;
+  const float* zx = nullptr;
+  bf16_t* h = nullptr; long ldh = 0; int kh = 0;          // h ring [T+1][M][ldh], kh halfwords of a row contracted
+  int h_wide = 0;                                        // layout of its rows (LstmFwdParams::h_wide)
+  bf16_t* h_copy = nullptr; long ld_copy = 0;            // second ring the tail writes (LstmFwdParams::hout_lo) or NULL
+  const bf16_t* B = nullptr; long ldb = 0;               // weight image [4H][ldb]; step t reads the image at B + t * w_step_stride (time-dithered images)
+  long w_step_stride = 0;
+  // e4m3 segments (B8 != NULL): kx8 bytes at byte x8_off of the x rows, then kh8 bytes behind the H halfwords of the h rows, against B8's rows
+  // (b8_gap bytes skipped between the two); kx8 = 0: the h rows' bytes alone
+  const uint8_t* B8 = nullptr; long ldb8 = 0, b8_gap = 0; int scale8_exp = 0;
+  long x8_off = 0; int kx8 = 0, kh8 = 0;
+  // integer frames (row_scale != NULL): behind the x-part acc = acc * row_scale[t][row] + col_add (+ 1 on the forget gate); the accumulators
+  // then start from `bias` = the constant term of the dequantised frames and col_add is the true bias
+  const float* row_scale = nullptr; const float* col_add = nullptr;
+  const float* bias = nullptr; float* c_state = nullptr; float* h_state = nullptr;
+  void* gates = nullptr; bf16_t* c_all = nullptr;        // the backward pass's tapes, both or neither
+};
+
+// ---- refusals: each returns the error code, the message names the entry -------------------------------------------------------------------
+static inline bool aligned_to(const void* p, int a) { return ((uintptr_t)p % a) == 0; }
+
+static inline int fwd_shape_ok(const char* entry, int T, int M, int K, int H, int h_mult = 64, int h_min = 64) {
+  EVC_REQUIRE(T > 0 && M > 0 && K > 0 && H >= h_min && K % 64 == 0 && H % h_mult == 0, EVC_ERR_BAD_SHAPE,
+              "%s: bad shape T=%d M=%d K=%d (%%64) H=%d (%%%d, >= %d)", entry, T, M, K, H, h_mult, h_min);
+  return EVC_OK;
 }
 
-// forward tile for a step over `rows` rows: index into {320, 288, 256, 224, 192, 160 (v2), 128 (v1), 64 (v1), 128 (v2), 64 (v2)}
+// x rows that carry an e4m3 part: kx16 halfwords at the row start, kx8 bytes at byte x8_off, row stride ldx halfwords
+static inline int fwd_x8_ok(const char* entry, const void* x, long ldx, int kx16, long x8_off, int kx8) {
+  EVC_REQUIRE(kx8 > 0 && kx8 % 128 == 0 && kx8 >= 384, EVC_ERR_BAD_SHAPE,
+              "%s: kx8=%d (%%128, >= 384: the ring must be full of e4m3 stages at t = 0)", entry, kx8);
+  EVC_REQUIRE(ldx % 8 == 0 && x8_off % 16 == 0 && ldx >= kx16 && ldx * 2 >= x8_off + kx8 && aligned_to(x, 16), EVC_ERR_BAD_ALIGN,
+              "%s: ldx=%ld (%%8, >= kx16=%d), x8_off=%ld (%%16), x 16-byte aligned", entry, ldx, kx16, x8_off);
+  return EVC_OK;
+}
+
+static inline int fwd_xint_ok(const char* entry, const float* x_row_scale, const float* x_col_const, int b8_gap) {
+  EVC_REQUIRE((x_row_scale == nullptr) == (x_col_const == nullptr) && b8_gap >= 0 && b8_gap % 128 == 0 && (x_row_scale || b8_gap == 0) &&
+              aligned_to(x_col_const, 16), EVC_ERR_BAD_ARG,
+              "%s: x_row_scale and x_col_const go together (16-byte aligned), b8_gap=%d (%%128) only with them", entry, b8_gap);
+  return EVC_OK;
+}
+
+static inline int fwd_shared_ok(const char* entry, const FwdShared& S) {
+  EVC_REQUIRE(fwd_tail_ok(S.M, S.H, S.ld_state), EVC_ERR_BAD_SHAPE, "%s: a gate-record / state slab spans 4 GiB or more (M=%d H=%d ld_state=%ld)",
+              entry, S.M, S.H, S.ld_state);
+  EVC_REQUIRE(S.ld_state % 4 == 0, EVC_ERR_BAD_ALIGN, "%s: ld_state=%ld must be a multiple of 4 (16-byte state rows)", entry, S.ld_state);
+  return rows_per_step_ok(entry, S.rows_per_step, S.T, S.M);
+}
+
+// h_align: 8 bytes for rings of plain 16-bit rows, 16 for the rows that carry e4m3 parts or a second image
+static inline int fwd_layer_ok(const char* entry, const FwdLayer& L, int h_align, int copy_align = 8) {
+  EVC_REQUIRE(aligned_to(L.c_state, 16) && aligned_to(L.h_state, 16) && aligned_to(L.bias, 16) && aligned_to(L.col_add, 16) &&
+              aligned_to(L.h, h_align) && aligned_to(L.h_copy, copy_align), EVC_ERR_BAD_ALIGN,
+              "%s: state / bias must be 16-byte aligned, the h buffers %d- / %d-byte", entry, h_align, copy_align);
+  EVC_REQUIRE((L.gates == nullptr) == (L.c_all == nullptr), EVC_ERR_BAD_ARG, "%s: gates and c_all go together", entry);
+  EVC_REQUIRE(aligned_to(L.gates, 16) && aligned_to(L.c_all, 8), EVC_ERR_BAD_ALIGN, "%s: gates must be 16-byte, c_all 8-byte aligned", entry);
+  return EVC_OK;
+}
+
+static inline int fwd_layers2_ok(const char* entry, const FwdLayer& L0, const FwdLayer& L1, int h_align) {
+  EVC_TRY(fwd_layer_ok(entry, L0, h_align));
+  EVC_TRY(fwd_layer_ok(entry, L1, h_align));
+  EVC_REQUIRE((L0.gates == nullptr) == (L1.gates == nullptr), EVC_ERR_BAD_ARG, "%s: gates and c_all go together, for both layers", entry);
+  return EVC_OK;
+}
+
+// h_{-1} = 0: slab 0 of a layer's rings (the state buffers need no clearing: step 0 treats c_old as 0 and writes the zero state of the
+// zero-length rows it covers itself; rows beyond rows_per_step[0] are the caller's)
+static inline int fwd_clear_h(const FwdShared& S, const FwdLayer& L, hipStream_t st) {
+  EVC_CHECK_HIP(hipMemsetAsync(L.h, 0, (size_t)S.M * L.ldh * sizeof(bf16_t), st));
+  return EVC_OK;
+}
+static inline int fwd_clear_copy(const FwdShared& S, const FwdLayer& L, hipStream_t st) {
+  EVC_CHECK_HIP(hipMemsetAsync(L.h_copy, 0, (size_t)S.M * L.ld_copy * sizeof(bf16_t), st));
+  return EVC_OK;
+}
+
+// ---- one step ---------------------------------------------------------------------------------------------------------------------------
+struct FwdStep { GemmOperands p; LstmFwdParams e; int k1, k2; };      // k1, k2: halfwords of the two 16-bit segments (the launchers divide by the tile's K step)
+
+static inline FwdStep fwd_step(const FwdShared& S, const FwdLayer& L, int t) {
+  FwdStep s{};
+  const int M = S.M, H = S.H;
+  const long slab = (long)M * H;
+  const bf16_t* hprev = L.h + (long)t * M * L.ldh;
+  const bf16_t* xt = L.x ? L.x + (long)t * M * L.ldx : nullptr;
+  const int kh = t == 0 ? 0 : L.kh;
+  GemmOperands& p = s.p;
+  p.M = S.rows(t); p.Nu = H; p.group_stride = H;
+  p.B = L.B + (long)t * L.w_step_stride; p.ldb = L.ldb;
+  p.A2 = hprev; p.lda2 = L.ldh;
+  if (L.zx) { p.A1 = hprev; p.lda1 = L.ldh; s.k1 = kh; s.k2 = 0; }
+  else { p.A1 = xt; p.lda1 = L.ldx; s.k1 = L.kx; s.k2 = kh; }
+  if (L.B8) {
+    const uint8_t* h8 = (const uint8_t*)(hprev + H);
+    const int nh8 = (t == 0 ? 0 : L.kh8) / 128;
+    if (L.kx8) { p.A3 = (const uint8_t*)xt + L.x8_off; p.lda3 = L.ldx * 2; p.nk3 = L.kx8 / 128; }
+    else { p.A3 = h8; p.lda3 = L.ldh * 2; p.nk3 = nh8; }
+    if (L.kx8 && L.kh8) { p.A4 = h8; p.lda4 = L.ldh * 2; p.nk4 = nh8; }
+    else { p.A4 = p.A3; p.lda4 = p.lda3; p.nk4 = 0; }                  // one e4m3 segment only
+    p.B8 = L.B8; p.ldb8 = L.ldb8; p.b8_gap = L.b8_gap; p.scale8_exp = L.scale8_exp;
+  }
+  if (L.row_scale) { p.row_scale = L.row_scale + (long)t * M; p.col_add = L.col_add; p.g2_add = 1.0f; }
+  LstmFwdParams& e = s.e;
+  e.zx = L.zx ? L.zx + (long)t * M * 4 * H : nullptr; e.ldzx = 4L * H;
+  e.bias = L.bias; e.len = S.len; e.t = t;
+  e.c_state = L.c_state; e.h_state = L.h_state; e.ld_state = S.ld_state;
+  e.hout = L.h + (long)(t + 1) * M * L.ldh; e.h_wide = L.h_wide;
+  e.hout_lo = L.h_copy ? L.h_copy + (long)(t + 1) * M * L.ld_copy : nullptr;
+  e.gates = L.gates ? (uint2*)L.gates + t * slab : nullptr;
+  e.c_hist = L.c_all ? L.c_all + (t + 1) * slab : nullptr;             // slab t+1 = c after step t
+  e.row_map = S.row_map;
+  e.M = p.M; e.H = H;
+  return s;
+}
+
+// A layer alone: one launch per step, until the row plan runs out of rows
+template <class Launch>
+static inline void fwd_layer_loop(const FwdShared& S, const FwdLayer& L, Launch&& launch) {
+  for (int t = 0; t < S.T && S.rows(t) > 0; ++t) launch(fwd_step(S, L, t));
+}
+
+// Two layers as a wavefront: launch s = layer 0's step s (a) next to layer 1's step s - 1 (b), T + 1 launches.  A level's first launch has only
+// role a, its last only role b, and a row plan may leave a role without rows (layer 1 runs the earlier step: at least as many rows as layer 0);
+// the absent role gets a copy of the present one's arguments (never read).  launch(a, has_a, b, has_b) decides one launch or two.
+template <class Launch>
+static inline void fwd_wavefront(const FwdShared& S, const FwdLayer& L0, const FwdLayer& L1, Launch&& launch) {
+  for (int s = 0; s <= S.T; ++s) {
+    const bool has_a = s < S.T && S.rows(s) > 0, has_b = s >= 1 && S.rows(s - 1) > 0;
+    if (!has_a && !has_b) continue;
+    const FwdStep one = has_a ? fwd_step(S, L0, s) : fwd_step(S, L1, s - 1);
+    if (has_a && has_b) launch(one, true, fwd_step(S, L1, s - 1), true);
+    else launch(one, has_a, one, has_b);
+  }
+}
+
+// ---- launches -----------------------------------------------------------------------------------------------------------------------------
+template <class Cfg, bool SPLIT = false, bool F16 = false, bool FP8 = false, bool XINT = false>
+static inline void launch_lstm_fwd(const FwdStep& s, hipStream_t st) {
+  GemmOperands p = s.p;
+  p.nk1 = s.k1 / kdiv<Cfg>(); p.nk2 = s.k2 / kdiv<Cfg>();
+#ifdef EVC_STAMPS
+  p.stamp_slot = s.e.t & 7;
+#endif
+  const int tm = ceil_div(s.e.M, Cfg::BM), tn = ceil_div(s.e.H, Cfg::BU);
+  launch_cfg<Cfg>(lstm_fwd_step_kernel<Cfg, SPLIT, F16, FP8, XINT>, tm * tn, st, p, s.e, tm, tn);
+}
+
+// both roles in one launch whose workgroups walk both tiles (lstm_fwd_walk2_kernel); with one role, the same kernel: every launch of a level
+// carries one kernel name - the per-kernel averages of a profile then cover exactly the launches bench.py times
+template <class Cfg, bool F16 = false, bool FP8 = false, bool XINT = false, bool FP8B = FP8>
+static inline void launch_lstm_fwd_walk2(const FwdStep& a, bool has_a, const FwdStep& b, bool has_b, hipStream_t st) {
+  GemmOperands pa = a.p, pb = b.p;
+  pa.nk1 = a.k1 / 64; pa.nk2 = a.k2 / 64;
+  pb.nk1 = b.k1 / 64; pb.nk2 = b.k2 / 64;
+  const int tma = has_a ? ceil_div(a.e.M, Cfg::BM) : 0, tmb = has_b ? ceil_div(b.e.M, Cfg::BM) : 0, tn = ceil_div(a.e.H, Cfg::BU);
+  launch_cfg<Cfg>(lstm_fwd_walk2_kernel<Cfg, F16, FP8, XINT, FP8B>, (tma > tmb ? tma : tmb) * tn, st, pa, a.e, tma, pb, b.e, tmb, tn);
+}
+
+// both roles (same geometry) as the two halves of one grid (lstm_fwd_pair_kernel)
+template <class Cfg, bool F16 = false, bool FP8 = false>
+static inline void launch_lstm_fwd_pair(const FwdStep& a, const FwdStep& b, hipStream_t st) {
+  GemmOperands pa = a.p, pb = b.p;
+  pa.nk1 = a.k1 / kdiv<Cfg>(); pa.nk2 = a.k2 / kdiv<Cfg>();
+  pb.nk1 = b.k1 / kdiv<Cfg>(); pb.nk2 = b.k2 / kdiv<Cfg>();
+  const int tm = ceil_div(a.e.M, Cfg::BM), tn = ceil_div(a.e.H, Cfg::BU);
+  launch_cfg<Cfg>(lstm_fwd_pair_kernel<Cfg, F16, FP8>, 2 * tm * tn, st, pa, a.e, pb, b.e, tm, tn);
+}
+
+// ---- tile choice: two cost-model tables, one dispatcher each -----------------------------------------------------------------------------------
+template <class Cfg> struct TileTag { typedef Cfg type; };
+// the tiles lstm_fwd_walk2_kernel is built for
+template <class Cfg> struct is_walk2_tile {
+  static constexpr bool value = std::is_same<Cfg, CfgLstmV3_256>::value || std::is_same<Cfg, CfgLstmV3_240>::value || std::is_same<Cfg, CfgLstmV3_224u>::value;
+};
+
+// forward tile for a step over `rows` rows: index into {320, 288, 256, 224, 192, 160 (v2), 128 (v1), 64 (v1), 128 (v2), 64 (v2), 240}
 static inline int pick_fwd_tile(int rows, int H) {
   constexpr int NC = 11;
   static const int bm[NC] = {320, 288, 256, 224, 192, 160, 128, 64, 128, 64, 240};
@@ -329,228 +515,26 @@ static inline int pick_fwd_tile(int rows, int H) {
   return best;
 }
 
-// one bf16 forward step on the tile the cost model picks for Mt rows
-static inline void launch_fwd_step_bf16(const GemmOperands& p, const LstmFwdParams& e, int k1, int k2, int Mt, int H, hipStream_t st) {
-  switch (pick_fwd_tile(Mt, H)) {
-    case 0: launch_lstm_fwd<CfgLstmV2a>(p, e, k1, k2, st); break;
-    case 1: launch_lstm_fwd<CfgLstmV2_288>(p, e, k1, k2, st); break;
-    case 2: launch_lstm_fwd<CfgLstmV3_256>(p, e, k1, k2, st); break;
-    case 3: launch_lstm_fwd<CfgLstmV3_224u>(p, e, k1, k2, st); break;     // 6 + 8 row fragments (7 + 7: 58.3 -> 58.0 us per launch)
-    case 10: launch_lstm_fwd<CfgLstmV3_240>(p, e, k1, k2, st); break;
-    case 4: launch_lstm_fwd<CfgLstmV3_192>(p, e, k1, k2, st); break;
-    case 5: launch_lstm_fwd<CfgLstmV3_160>(p, e, k1, k2, st); break;
-    case 6: launch_lstm_fwd<CfgLstmBig>(p, e, k1, k2, st); break;
-    case 8: launch_lstm_fwd<CfgLstmV2_128>(p, e, k1, k2, st); break;
-    case 9: launch_lstm_fwd<CfgLstmV2_64>(p, e, k1, k2, st); break;
-    default: launch_lstm_fwd<CfgLstmSmall>(p, e, k1, k2, st); break;
+// f(TileTag<Cfg>()) for the tile of a pick_fwd_tile() index.  RING32 (evc_lstm_stack2_fwd alone): picks 2-5 on the 32-wide ring tiles instead of
+// the 64-wide ones, and no 240-row tile - that pick lands on the 64 x 16 default (open observation)
+template <bool RING32 = false, class F>
+static inline auto with_fwd_tile(int pick, F&& f) {
+  switch (pick) {
+    case 0: return f(TileTag<CfgLstmV2a>());
+    case 1: return f(TileTag<CfgLstmV2_288>());
+    case 2: return f(TileTag<std::conditional_t<RING32, CfgLstmV2b, CfgLstmV3_256>>());
+    case 3: return f(TileTag<std::conditional_t<RING32, CfgLstmV2_224, CfgLstmV3_224u>>());
+    case 4: return f(TileTag<std::conditional_t<RING32, CfgLstmV2_192, CfgLstmV3_192>>());
+    case 5: return f(TileTag<std::conditional_t<RING32, CfgLstmV2_160, CfgLstmV3_160>>());
+    case 6: return f(TileTag<CfgLstmBig>());
+    case 8: return f(TileTag<CfgLstmV2_128>());
+    case 9: return f(TileTag<CfgLstmV2_64>());
+    case 10: return f(TileTag<std::conditional_t<RING32, CfgLstmSmall, CfgLstmV3_240>>());
+    default: return f(TileTag<CfgLstmSmall>());
   }
 }
 
-static int lstm_layer_fwd_impl(const evc_bf16* x, const evc_bf16* wT, const float* bias, const int32_t* len,
-                               int T, int M, int Kin, int H, int hoist, float* zx_ws,
-                               evc_bf16* hbuf, float* c_state, float* h_state, int64_t ld_state,
-                               void* gates, evc_bf16* c_all, evc_bf16* hbuf_bf16,
-                               const int32_t* row_map, const int32_t* rows_per_step, void* stream, int f16 = 0, int64_t ldx = 0, int h_wide = 0,
-                               int64_t w_step_stride = 0);
-
-extern "C" int evc_lstm_layer_fwd(const evc_bf16* x, const evc_bf16* wT, const float* bias, const int32_t* len,
-                                  int T, int M, int Kin, int H, int hoist, float* zx_ws,
-                                  evc_bf16* hbuf, float* c_state, float* h_state, int64_t ld_state,
-                                  void* gates, evc_bf16* c_all, const int32_t* row_map, const int32_t* rows_per_step,
-                                  void* stream) {
-  return lstm_layer_fwd_impl(x, wT, bias, len, T, M, Kin, H, hoist, zx_ws, hbuf, c_state, h_state, ld_state, gates, c_all,
-                             nullptr, row_map, rows_per_step, stream);
-}
-
-extern "C" int evc_lstm_layer_fwd_f16(const evc_f16* x, int64_t ldx, const evc_f16* wT, const float* bias, const int32_t* len,
-                                      int T, int M, int Kin, int H, evc_f16* hbuf, int h_wide, evc_bf16* hbuf_bf16,
-                                      float* c_state, float* h_state, int64_t ld_state, void* gates, evc_bf16* c_all,
-                                      const int32_t* row_map, const int32_t* rows_per_step, void* stream) {
-  EVC_REQUIRE(hbuf_bf16, EVC_ERR_BAD_ARG, "evc_lstm_layer_fwd_f16: hbuf_bf16 (the bf16 copy of h for the backward pass) is required");
-  EVC_REQUIRE(((uintptr_t)hbuf_bf16 % 8) == 0, EVC_ERR_BAD_ALIGN, "evc_lstm_layer_fwd_f16: hbuf_bf16 must be 8-byte aligned");
-  EVC_REQUIRE(ldx >= Kin && ldx % 8 == 0 && (h_wide == 0 || h_wide == 1), EVC_ERR_BAD_ARG, "evc_lstm_layer_fwd_f16: ldx=%ld (>= Kin=%d, %%8), h_wide=%d",
-              (long)ldx, Kin, h_wide);
-  return lstm_layer_fwd_impl((const evc_bf16*)x, (const evc_bf16*)wT, bias, len, T, M, Kin, H, 0, nullptr, (evc_bf16*)hbuf, c_state, h_state,
-                             ld_state, gates, c_all, hbuf_bf16, row_map, rows_per_step, stream, 1, ldx, h_wide);
-}
-
-static int lstm_layer_fwd_impl(const evc_bf16* x, const evc_bf16* wT, const float* bias, const int32_t* len,
-                               int T, int M, int Kin, int H, int hoist, float* zx_ws,
-                               evc_bf16* hbuf, float* c_state, float* h_state, int64_t ld_state,
-                               void* gates, evc_bf16* c_all, evc_bf16* hbuf_bf16,
-                               const int32_t* row_map, const int32_t* rows_per_step, void* stream, int f16, int64_t ldx, int h_wide,
-                               int64_t w_step_stride) {
-  // w_step_stride (elements; 0 = one image): step t contracts the weight image at wT + t * w_step_stride (time-dithered f16 images,
-  // evc_lstm_layer_fwd_f16_dith)
-  // f16: x, wT, hbuf hold IEEE f16 (16-bit containers), hbuf_bf16 receives the bf16 copy of every h_t; ldx = row stride of x
-  // (0: Kin); h_wide: hbuf rows are [h | h/64] (2H) and the kernel's h-part is [Wh | Wh_lo*64] (2H): the recurrent weights
-  // K-extended by their low-order halves.  (The split-bf16 form of a layer is evc_lstm_layer_fwd_hp below.)
-  if (ldx == 0) ldx = Kin;
-  const long ldh = h_wide ? 2L * H : H;            // row stride of hbuf = K of the recurrent part
-  EVC_REQUIRE(T > 0 && M > 0 && H > 0 && Kin > 0, EVC_ERR_BAD_SHAPE, "evc_lstm_layer_fwd: bad shape");
-  EVC_REQUIRE(Kin % 64 == 0 && H % 64 == 0, EVC_ERR_BAD_SHAPE,
-              "evc_lstm_layer_fwd: Kin=%d and H=%d must be multiples of 64", Kin, H);
-  EVC_REQUIRE(ring_operand_ok(M, ldx > ldh ? ldx : ldh) && ring_operand_ok(4L * H, (long)Kin + ldh), EVC_ERR_BAD_SHAPE,
-              "evc_lstm_layer_fwd: a time slab or the kernel spans 4 GiB or more (M=%d Kin=%d H=%d)", M, Kin, H);
-  EVC_REQUIRE(fwd_tail_ok(M, H, ld_state), EVC_ERR_BAD_SHAPE, "LSTM forward: a gate-record / state slab spans 4 GiB or more (M=%d H=%d ld_state=%ld)", M, H, (long)ld_state);
-  EVC_REQUIRE(!hoist || (zx_ws && !h_wide && ldx == Kin), EVC_ERR_BAD_ARG, "evc_lstm_layer_fwd: hoist needs zx_ws (and plain operands)");
-  EVC_REQUIRE(ld_state % 4 == 0 && ((uintptr_t)c_state % 16) == 0 && ((uintptr_t)h_state % 16) == 0 && ((uintptr_t)bias % 16) == 0 &&
-              ((uintptr_t)hbuf % 8) == 0, EVC_ERR_BAD_ALIGN, "evc_lstm_layer_fwd: state/bias/hbuf must allow 16-byte vector access");
-  EVC_REQUIRE((gates == nullptr) == (c_all == nullptr), EVC_ERR_BAD_ARG, "evc_lstm_layer_fwd: gates and c_all go together");
-  EVC_REQUIRE(!gates || (((uintptr_t)gates % 16) == 0 && ((uintptr_t)c_all % 8) == 0), EVC_ERR_BAD_ALIGN,
-              "evc_lstm_layer_fwd: gates must be 16-byte, c_all 8-byte aligned");
-  if (rows_per_step)
-    for (int t = 0; t < T; ++t)
-      EVC_REQUIRE(rows_per_step[t] >= 0 && rows_per_step[t] <= M && (t == 0 || rows_per_step[t] <= rows_per_step[t - 1]), EVC_ERR_BAD_ARG,
-                  "evc_lstm_layer_fwd: rows_per_step[%d]=%d must be non-increasing and within [0, M=%d]", t, rows_per_step[t], M);
-  hipStream_t st = (hipStream_t)stream;
-  const long ldw = Kin + ldh;
-  // h_{-1} = 0 (the state buffers need no clearing: step 0 treats c_old as 0 and writes the zero
-  // state of the zero-length rows it covers itself; rows beyond rows_per_step[0] are the caller's)
-  EVC_CHECK_HIP(hipMemsetAsync(hbuf, 0, (size_t)M * ldh * sizeof(bf16_t), st));
-  if (f16) EVC_CHECK_HIP(hipMemsetAsync(hbuf_bf16, 0, (size_t)M * H * sizeof(bf16_t), st));
-  if (hoist) {
-    int rc = evc_gemm_nt(x, Kin, wT, ldw, zx_ws, 4L * H, T * M, 4 * H, Kin, nullptr, 0, 0, stream);
-    if (rc) return rc;
-  }
-  for (int t = 0; t < T; ++t) {
-    const int Mt = rows_per_step ? rows_per_step[t] : M;     // active rows are the prefix [0, Mt) (row plan)
-    if (Mt == 0) break;
-    GemmOperands p;
-    p.M = Mt; p.Nu = H; p.group_stride = H; p.ldb = ldw; p.nk1 = p.nk2 = 0;
-    p.A1lo = p.A2lo = p.Blo = nullptr;
-    const bf16_t* hprev = hbuf + (long)t * M * ldh;
-    int k1, k2;
-    if (hoist) {
-      p.A1 = hprev; p.lda1 = H; k1 = (t == 0) ? 0 : H; p.A2 = hprev; p.lda2 = H; k2 = 0;
-      p.B = wT + Kin;
-    } else {
-      p.A1 = x + (long)t * M * ldx; p.lda1 = ldx; k1 = Kin;
-      p.A2 = hprev; p.lda2 = ldh; k2 = (t == 0) ? 0 : (int)ldh;
-      p.B = wT + (long)t * w_step_stride;
-    }
-    LstmFwdParams e;
-    e.zx = hoist ? zx_ws + (long)t * M * 4 * H : nullptr; e.ldzx = 4L * H;
-    e.bias = bias; e.len = len; e.t = t;
-    e.c_state = c_state; e.h_state = h_state; e.ld_state = ld_state;
-    e.hout = hbuf + (long)(t + 1) * M * ldh; e.h_wide = h_wide;
-    e.hout_lo = f16 ? hbuf_bf16 + (long)(t + 1) * M * H : nullptr;
-    e.gates = gates ? (uint2*)gates + (long)t * M * H : nullptr;
-    e.c_hist = c_all ? c_all + (long)(t + 1) * M * H : nullptr;      // slab t+1 = c after step t
-    e.row_map = row_map;
-    e.M = Mt; e.H = H;
-    if (f16) {        // IEEE f16 operands, one MFMA product per depth: the tiles of the bf16 step
-      switch (pick_fwd_tile(Mt, H)) {
-        case 0: launch_lstm_fwd<CfgLstmV2a, false, true>(p, e, k1, k2, st); break;
-        case 1: launch_lstm_fwd<CfgLstmV2_288, false, true>(p, e, k1, k2, st); break;
-        case 2: launch_lstm_fwd<CfgLstmV3_256, false, true>(p, e, k1, k2, st); break;
-        case 3: launch_lstm_fwd<CfgLstmV3_224u, false, true>(p, e, k1, k2, st); break;
-        case 10: launch_lstm_fwd<CfgLstmV3_240, false, true>(p, e, k1, k2, st); break;
-        case 4: launch_lstm_fwd<CfgLstmV3_192, false, true>(p, e, k1, k2, st); break;
-        case 5: launch_lstm_fwd<CfgLstmV3_160, false, true>(p, e, k1, k2, st); break;
-        case 6: launch_lstm_fwd<CfgLstmBig, false, true>(p, e, k1, k2, st); break;
-        case 8: launch_lstm_fwd<CfgLstmV2_128, false, true>(p, e, k1, k2, st); break;
-        case 9: launch_lstm_fwd<CfgLstmV2_64, false, true>(p, e, k1, k2, st); break;
-        default: launch_lstm_fwd<CfgLstmSmall, false, true>(p, e, k1, k2, st); break;
-      }
-      continue;
-    }
-    launch_fwd_step_bf16(p, e, k1, k2, Mt, H, st);
-  }
-  EVC_LAUNCH_CHECK();
-  return EVC_OK;
-}
-
-// ===========================================================================
-// Two-layer L1 level (many rows, row plans), bf16: layer 0's step s and layer 1's step s-1 in ONE launch whose workgroups walk both tiles
-// (lstm_fwd_walk2_kernel) - T + 1 launches instead of 2 T, one ring fill and one kernel boundary less per pair of steps; both layers contract
-// [x_t | h_{t-1}] . W^T in one K walk (layer 1's x_t is layer 0's output slab).  Same arithmetic as two evc_lstm_layer_fwd calls: bit-identical
-// results.  Launches whose tile is not one of the 64-wide ring tiles (224 / 240 / 256 rows) run as two separate launches.
-// ===========================================================================
-// has_a / has_b: which of the two tiles exist (a level's first launch has only layer 0's step, its last only layer 1's: the same kernel with one role,
-// so that every launch of the level carries one kernel name - the per-kernel averages of a profile then cover exactly the launches bench.py times)
-template <class Cfg, bool F16 = false, bool FP8 = false, bool XINT = false, bool FP8B = FP8>
-static inline void launch_lstm_fwd_walk2(GemmOperands pa, const LstmFwdParams& ea, int k1a, int k2a, bool has_a, GemmOperands pb, const LstmFwdParams& eb,
-                                         int k1b, int k2b, bool has_b, hipStream_t st) {
-  pa.nk1 = k1a / 64; pa.nk2 = k2a / 64;
-  pb.nk1 = k1b / 64; pb.nk2 = k2b / 64;
-  const int H = has_a ? ea.H : eb.H;
-  const int tma = has_a ? ceil_div(ea.M, Cfg::BM) : 0, tmb = has_b ? ceil_div(eb.M, Cfg::BM) : 0, tn = ceil_div(H, Cfg::BU);
-  launch_cfg<Cfg>(lstm_fwd_walk2_kernel<Cfg, F16, FP8, XINT, FP8B>, (tma > tmb ? tma : tmb) * tn, st, pa, ea, tma, pb, eb, tmb, tn);
-}
-
-extern "C" int evc_lstm_level2_fwd(const evc_bf16* x, const evc_bf16* wT0, const float* bias0, const evc_bf16* wT1, const float* bias1,
-                                   const int32_t* len, int T, int M, int Kin, int H, evc_bf16* hbuf0, evc_bf16* hbuf1,
-                                   float* c_state0, float* h_state0, float* c_state1, float* h_state1, int64_t ld_state,
-                                   void* gates0, evc_bf16* c_all0, void* gates1, evc_bf16* c_all1,
-                                   const int32_t* row_map, const int32_t* rows_per_step, void* stream) {
-  EVC_REQUIRE(T > 0 && M > 0 && H > 0 && Kin > 0 && Kin % 64 == 0 && H % 64 == 0, EVC_ERR_BAD_SHAPE,
-              "evc_lstm_level2_fwd: bad shape T=%d M=%d Kin=%d H=%d (Kin, H multiples of 64)", T, M, Kin, H);
-  EVC_REQUIRE(ring_operand_ok(M, Kin > H ? Kin : H) && ring_operand_ok(4L * H, (long)Kin + H) && ring_operand_ok(4L * H, 2L * H), EVC_ERR_BAD_SHAPE,
-              "evc_lstm_level2_fwd: a time slab or a kernel spans 4 GiB or more (M=%d Kin=%d H=%d)", M, Kin, H);
-  EVC_REQUIRE(fwd_tail_ok(M, H, ld_state), EVC_ERR_BAD_SHAPE, "LSTM forward: a gate-record / state slab spans 4 GiB or more (M=%d H=%d ld_state=%ld)", M, H, (long)ld_state);
-  EVC_REQUIRE(x && wT0 && wT1 && bias0 && bias1 && len && hbuf0 && hbuf1 && c_state0 && h_state0 && c_state1 && h_state1, EVC_ERR_BAD_ARG,
-              "evc_lstm_level2_fwd: NULL operand");
-  EVC_REQUIRE(ld_state % 4 == 0 && ((uintptr_t)c_state0 % 16) == 0 && ((uintptr_t)h_state0 % 16) == 0 && ((uintptr_t)c_state1 % 16) == 0 &&
-              ((uintptr_t)h_state1 % 16) == 0 && ((uintptr_t)bias0 % 16) == 0 && ((uintptr_t)bias1 % 16) == 0 &&
-              ((uintptr_t)hbuf0 % 8) == 0 && ((uintptr_t)hbuf1 % 8) == 0, EVC_ERR_BAD_ALIGN,
-              "evc_lstm_level2_fwd: state/bias/hbuf must allow 16-byte vector access");
-  EVC_REQUIRE((gates0 == nullptr) == (c_all0 == nullptr) && (gates1 == nullptr) == (c_all1 == nullptr) && (gates0 == nullptr) == (gates1 == nullptr),
-              EVC_ERR_BAD_ARG, "evc_lstm_level2_fwd: gates and c_all go together, for both layers");
-  EVC_REQUIRE(!gates0 || (((uintptr_t)gates0 % 16) == 0 && ((uintptr_t)gates1 % 16) == 0 && ((uintptr_t)c_all0 % 8) == 0 && ((uintptr_t)c_all1 % 8) == 0),
-              EVC_ERR_BAD_ALIGN, "evc_lstm_level2_fwd: gates must be 16-byte, c_all 8-byte aligned");
-  if (rows_per_step)
-    for (int t = 0; t < T; ++t)
-      EVC_REQUIRE(rows_per_step[t] >= 0 && rows_per_step[t] <= M && (t == 0 || rows_per_step[t] <= rows_per_step[t - 1]), EVC_ERR_BAD_ARG,
-                  "evc_lstm_level2_fwd: rows_per_step[%d]=%d must be non-increasing and within [0, M=%d]", t, rows_per_step[t], M);
-  hipStream_t st = (hipStream_t)stream;
-  EVC_CHECK_HIP(hipMemsetAsync(hbuf0, 0, (size_t)M * H * sizeof(bf16_t), st));       // h_{-1} = 0, both layers
-  EVC_CHECK_HIP(hipMemsetAsync(hbuf1, 0, (size_t)M * H * sizeof(bf16_t), st));
-  auto step_args = [&](int layer, int t, GemmOperands& p, LstmFwdParams& e, int& k1, int& k2) {
-    const int kin = layer ? H : Kin;
-    const evc_bf16* xin = layer ? hbuf0 + (long)(t + 1) * M * H : x + (long)t * M * Kin;        // layer 1's x_t = layer 0's output slab t+1
-    evc_bf16* hb = layer ? hbuf1 : hbuf0;
-    p = GemmOperands();
-    p.M = rows_per_step ? rows_per_step[t] : M; p.Nu = H; p.group_stride = H; p.ldb = (long)kin + H; p.nk1 = p.nk2 = 0;
-    p.A1lo = p.A2lo = p.Blo = nullptr;
-    p.A1 = xin; p.lda1 = kin; k1 = kin;
-    p.A2 = hb + (long)t * M * H; p.lda2 = H; k2 = (t == 0) ? 0 : H;
-    p.B = layer ? wT1 : wT0;
-    e = LstmFwdParams();
-    e.zx = nullptr; e.ldzx = 4L * H;
-    e.bias = layer ? bias1 : bias0; e.len = len; e.t = t;
-    e.c_state = layer ? c_state1 : c_state0; e.h_state = layer ? h_state1 : h_state0; e.ld_state = ld_state;
-    e.hout = hb + (long)(t + 1) * M * H; e.h_wide = 0; e.hout_lo = nullptr;
-    void* gt = layer ? gates1 : gates0;
-    evc_bf16* ca = layer ? c_all1 : c_all0;
-    e.gates = gt ? (uint2*)gt + (long)t * M * H : nullptr;
-    e.c_hist = ca ? ca + (long)(t + 1) * M * H : nullptr;
-    e.row_map = row_map;
-    e.M = p.M; e.H = H;
-  };
-  for (int s = 0; s <= T; ++s) {
-    GemmOperands pa, pb;
-    LstmFwdParams ea, eb;
-    int k1a = 0, k2a = 0, k1b = 0, k2b = 0;
-    bool has_a = s < T, has_b = s >= 1;
-    if (has_a) { step_args(0, s, pa, ea, k1a, k2a); has_a = ea.M > 0; }
-    if (has_b) { step_args(1, s - 1, pb, eb, k1b, k2b); has_b = eb.M > 0; }
-    if (has_a || has_b) {
-      const int pick = pick_fwd_tile(has_b ? eb.M : ea.M, H);        // layer 1 runs the earlier step: at least as many rows as layer 0
-      if (!has_a) { pa = pb; ea = eb; }                              // (the absent role's arguments are never read: tiles_m = 0)
-      if (!has_b) { pb = pa; eb = ea; }
-      if (pick == 2) { launch_lstm_fwd_walk2<CfgLstmV3_256>(pa, ea, k1a, k2a, has_a, pb, eb, k1b, k2b, has_b, st); continue; }
-      if (pick == 10) { launch_lstm_fwd_walk2<CfgLstmV3_240>(pa, ea, k1a, k2a, has_a, pb, eb, k1b, k2b, has_b, st); continue; }
-      if (pick == 3) { launch_lstm_fwd_walk2<CfgLstmV3_224u>(pa, ea, k1a, k2a, has_a, pb, eb, k1b, k2b, has_b, st); continue; }
-    }
-    if (has_a) launch_fwd_step_bf16(pa, ea, k1a, k2a, ea.M, H, st);
-    if (has_b) launch_fwd_step_bf16(pb, eb, k1b, k2b, eb.M, H, st);
-  }
-  EVC_LAUNCH_CHECK();
-  return EVC_OK;
-}
-
-// forward tile among the 64-wide ring tiles only (the e4m3 tail lives in gemm_core_v3.h): 0..3 = 256 / 224 / 192 / 160 rows
+// forward tile among the 64-wide ring tiles only (the e4m3 tail lives in gemm_core_v3.h): index into {256, 224, 192, 160, 240}
 static inline int pick_fwd_tile_v3(int rows, int H) {
   static const int bm[5] = {256, 224, 192, 160, 240};
   static const double cf[5] = {1.0, 1.02, 1.04, 1.08, 1.01};
@@ -565,6 +549,168 @@ static inline int pick_fwd_tile_v3(int rows, int H) {
   return best;
 }
 
+// f(TileTag<Cfg>()) for the tile of a pick_fwd_tile_v3() index.  C224: the 224-row tile's row split - 6 + 8 (CfgLstmV3_224u) for the f16 and
+// two-tile forms, 7 + 7 (CfgLstmV3_224) for the steps with an e4m3 tail
+template <class C224, class F>
+static inline auto with_fwd_tile_v3(int pick, F&& f) {
+  switch (pick) {
+    case 0: return f(TileTag<CfgLstmV3_256>());
+    case 1: return f(TileTag<C224>());
+    case 2: return f(TileTag<CfgLstmV3_192>());
+    case 4: return f(TileTag<CfgLstmV3_240>());
+    default: return f(TileTag<CfgLstmV3_160>());
+  }
+}
+
+// one bf16 / f16 step on the tile of `pick` (pick_fwd_tile)
+template <bool F16>
+static inline void launch_fwd_step(const FwdStep& s, int pick, hipStream_t st) {
+  with_fwd_tile(pick, [&](auto tile) { launch_lstm_fwd<typename decltype(tile)::type, false, F16>(s, st); });
+}
+
+// one f16 + e4m3 step on the tile of `pick` (pick_fwd_tile_v3); xint: the integer-frame form
+static inline void launch_fwd_step_e4m3(const FwdStep& s, int pick, bool xint, hipStream_t st) {
+  with_fwd_tile_v3<CfgLstmV3_224>(pick, [&](auto tile) {
+    typedef typename decltype(tile)::type Cfg;
+    if (xint) launch_lstm_fwd<Cfg, false, true, true, true>(s, st);
+    else launch_lstm_fwd<Cfg, false, true, true>(s, st);
+  });
+}
+
+// ===========================================================================
+// One layer, bf16 or IEEE f16
+// ===========================================================================
+// f16: x, wT, hbuf hold IEEE f16 (16-bit containers) and one v_mfma_f32_16x16x32_f16 product is issued per depth - the cost of the bf16 step
+// with 8x smaller operand rounding; hbuf_bf16 receives the bf16 copy of every h_t (what the BPTT products contract over); ldx = row stride of x
+// (0: Kin); h_wide: hbuf rows are [h | h/64] (2H) and the kernel's h-part is [Wh | Wh_lo*64] (2H): the recurrent weights K-extended by their
+// low-order halves.  w_step_stride (elements; 0 = one image): step t contracts the weight image at wT + t * w_step_stride (time-dithered f16
+// images, evc_lstm_layer_fwd_f16_dith).  (The split-bf16 form of a layer is evc_lstm_layer_fwd_hp below.)
+static int lstm_layer_fwd_impl(const char* entry, const evc_bf16* x, const evc_bf16* wT, const float* bias, const int32_t* len,
+                               int T, int M, int Kin, int H, int hoist, float* zx_ws,
+                               evc_bf16* hbuf, float* c_state, float* h_state, int64_t ld_state,
+                               void* gates, evc_bf16* c_all, evc_bf16* hbuf_bf16,
+                               const int32_t* row_map, const int32_t* rows_per_step, void* stream, int f16 = 0, int64_t ldx = 0, int h_wide = 0,
+                               int64_t w_step_stride = 0) {
+  if (ldx == 0) ldx = Kin;
+  const long ldh = h_wide ? 2L * H : H;            // row stride of hbuf = K of the recurrent part
+  const long ldw = Kin + ldh;
+  EVC_TRY(fwd_shape_ok(entry, T, M, Kin, H));
+  EVC_REQUIRE(ring_operand_ok(M, ldx > ldh ? ldx : ldh) && ring_operand_ok(4L * H, (long)Kin + ldh), EVC_ERR_BAD_SHAPE,
+              "%s: a time slab or the kernel spans 4 GiB or more (M=%d Kin=%d H=%d)", entry, M, Kin, H);
+  EVC_REQUIRE(!hoist || (zx_ws && !h_wide && ldx == Kin), EVC_ERR_BAD_ARG, "%s: hoist needs zx_ws (and plain operands)", entry);
+  const FwdShared S{len, T, M, H, ld_state, row_map, rows_per_step};
+  FwdLayer L;
+  L.x = x; L.ldx = ldx; L.kx = Kin;
+  L.h = hbuf; L.ldh = ldh; L.kh = (int)ldh;
+  L.B = hoist ? wT + Kin : wT; L.ldb = ldw;
+  L.bias = bias; L.c_state = c_state; L.h_state = h_state; L.gates = gates; L.c_all = c_all;
+  L.zx = hoist ? zx_ws : nullptr; L.h_wide = h_wide; L.w_step_stride = w_step_stride;
+  if (f16) { L.h_copy = hbuf_bf16; L.ld_copy = H; }
+  EVC_TRY(fwd_shared_ok(entry, S));
+  EVC_TRY(fwd_layer_ok(entry, L, 8));
+  hipStream_t st = (hipStream_t)stream;
+  EVC_TRY(fwd_clear_h(S, L, st));
+  if (f16) EVC_TRY(fwd_clear_copy(S, L, st));
+  if (hoist) EVC_TRY(evc_gemm_nt(x, Kin, wT, ldw, zx_ws, 4L * H, T * M, 4 * H, Kin, nullptr, 0, 0, stream));
+  fwd_layer_loop(S, L, [&](const FwdStep& s) {
+    const int pick = pick_fwd_tile(s.e.M, H);
+    if (f16) launch_fwd_step<true>(s, pick, st);
+    else launch_fwd_step<false>(s, pick, st);
+  });
+  EVC_LAUNCH_CHECK();
+  return EVC_OK;
+}
+
+extern "C" int evc_lstm_layer_fwd(const evc_bf16* x, const evc_bf16* wT, const float* bias, const int32_t* len,
+                                  int T, int M, int Kin, int H, int hoist, float* zx_ws,
+                                  evc_bf16* hbuf, float* c_state, float* h_state, int64_t ld_state,
+                                  void* gates, evc_bf16* c_all, const int32_t* row_map, const int32_t* rows_per_step,
+                                  void* stream) {
+  return lstm_layer_fwd_impl("evc_lstm_layer_fwd", x, wT, bias, len, T, M, Kin, H, hoist, zx_ws, hbuf, c_state, h_state, ld_state, gates, c_all,
+                             nullptr, row_map, rows_per_step, stream);
+}
+
+extern "C" int evc_lstm_layer_fwd_f16(const evc_f16* x, int64_t ldx, const evc_f16* wT, const float* bias, const int32_t* len,
+                                      int T, int M, int Kin, int H, evc_f16* hbuf, int h_wide, evc_bf16* hbuf_bf16,
+                                      float* c_state, float* h_state, int64_t ld_state, void* gates, evc_bf16* c_all,
+                                      const int32_t* row_map, const int32_t* rows_per_step, void* stream) {
+  EVC_REQUIRE(hbuf_bf16, EVC_ERR_BAD_ARG, "evc_lstm_layer_fwd_f16: hbuf_bf16 (the bf16 copy of h for the backward pass) is required");
+  EVC_REQUIRE(ldx >= Kin && ldx % 8 == 0 && (h_wide == 0 || h_wide == 1), EVC_ERR_BAD_ARG, "evc_lstm_layer_fwd_f16: ldx=%ld (>= Kin=%d, %%8), h_wide=%d",
+              (long)ldx, Kin, h_wide);
+  return lstm_layer_fwd_impl("evc_lstm_layer_fwd_f16", (const evc_bf16*)x, (const evc_bf16*)wT, bias, len, T, M, Kin, H, 0, nullptr, (evc_bf16*)hbuf,
+                             c_state, h_state, ld_state, gates, c_all, hbuf_bf16, row_map, rows_per_step, stream, 1, ldx, h_wide);
+}
+
+// ===========================================================================
+// Two-layer L1 level (many rows, row plans), bf16: layer 0's step s and layer 1's step s-1 in ONE launch whose workgroups walk both tiles
+// (lstm_fwd_walk2_kernel) - T + 1 launches instead of 2 T, one ring fill and one kernel boundary less per pair of steps; both layers contract
+// [x_t | h_{t-1}] . W^T in one K walk (layer 1's x_t is layer 0's output slab).  Same arithmetic as two evc_lstm_layer_fwd calls: bit-identical
+// results.  Launches whose tile is not one of the 64-wide ring tiles (224 / 240 / 256 rows) run as two separate launches.
+// ===========================================================================
+extern "C" int evc_lstm_level2_fwd(const evc_bf16* x, const evc_bf16* wT0, const float* bias0, const evc_bf16* wT1, const float* bias1,
+                                   const int32_t* len, int T, int M, int Kin, int H, evc_bf16* hbuf0, evc_bf16* hbuf1,
+                                   float* c_state0, float* h_state0, float* c_state1, float* h_state1, int64_t ld_state,
+                                   void* gates0, evc_bf16* c_all0, void* gates1, evc_bf16* c_all1,
+                                   const int32_t* row_map, const int32_t* rows_per_step, void* stream) {
+  const char* entry = "evc_lstm_level2_fwd";
+  EVC_TRY(fwd_shape_ok(entry, T, M, Kin, H));
+  EVC_REQUIRE(ring_operand_ok(M, Kin > H ? Kin : H) && ring_operand_ok(4L * H, (long)Kin + H) && ring_operand_ok(4L * H, 2L * H), EVC_ERR_BAD_SHAPE,
+              "evc_lstm_level2_fwd: a time slab or a kernel spans 4 GiB or more (M=%d Kin=%d H=%d)", M, Kin, H);
+  EVC_REQUIRE(x && wT0 && wT1 && bias0 && bias1 && len && hbuf0 && hbuf1 && c_state0 && h_state0 && c_state1 && h_state1, EVC_ERR_BAD_ARG,
+              "evc_lstm_level2_fwd: NULL operand");
+  const FwdShared S{len, T, M, H, ld_state, row_map, rows_per_step};
+  FwdLayer L0;
+  L0.x = x; L0.ldx = Kin; L0.kx = Kin;
+  L0.h = hbuf0; L0.ldh = H; L0.kh = H;
+  L0.B = wT0; L0.ldb = (long)Kin + H;
+  L0.bias = bias0; L0.c_state = c_state0; L0.h_state = h_state0; L0.gates = gates0; L0.c_all = c_all0;
+  FwdLayer L1;
+  L1.x = hbuf0 + (long)M * H; L1.ldx = H; L1.kx = H;      // x_t = layer 0's output slab t+1
+  L1.h = hbuf1; L1.ldh = H; L1.kh = H;
+  L1.B = wT1; L1.ldb = 2L * H;
+  L1.bias = bias1; L1.c_state = c_state1; L1.h_state = h_state1; L1.gates = gates1; L1.c_all = c_all1;
+  EVC_TRY(fwd_shared_ok(entry, S));
+  EVC_TRY(fwd_layers2_ok(entry, L0, L1, 8));
+  hipStream_t st = (hipStream_t)stream;
+  EVC_TRY(fwd_clear_h(S, L0, st));
+  EVC_TRY(fwd_clear_h(S, L1, st));
+  fwd_wavefront(S, L0, L1, [&](const FwdStep& a, bool has_a, const FwdStep& b, bool has_b) {
+    const bool walked = with_fwd_tile(pick_fwd_tile(has_b ? b.e.M : a.e.M, H), [&](auto tile) {
+      typedef typename decltype(tile)::type Cfg;
+      if constexpr (is_walk2_tile<Cfg>::value) { launch_lstm_fwd_walk2<Cfg>(a, has_a, b, has_b, st); return true; }
+      else return false;
+    });
+    if (walked) return;
+    if (has_a) launch_fwd_step<false>(a, pick_fwd_tile(a.e.M, H), st);
+    if (has_b) launch_fwd_step<false>(b, pick_fwd_tile(b.e.M, H), st);
+  });
+  EVC_LAUNCH_CHECK();
+  return EVC_OK;
+}
+
+// ===========================================================================
+// "High" precision L1 layers: f16 stages + e4m3 stages
+// ===========================================================================
+// Layer 0 of the two "high" L1 entries (evc_lstm_layer_fwd_f16_fp8lo, evc_lstm_level2_fwd_high): x rows [kx16 f16 | kx8 e4m3 at byte x8_off],
+// h rows [f16(h) | e4m3(h 2^7) (| e4m3((h - f16(h)) 2^18) with h_lo)], wT8 rows [kx8 | b8_gap | kh8]
+static inline FwdLayer fwd_layer_fp8lo(const evc_f16* x, int64_t ldx, int kx16, int64_t x8_off, int kx8, const evc_f16* wT16, const uint8_t* wT8,
+                                       int w8_scale_exp, int h_lo, const float* bias, const float* x_row_scale, const float* x_col_const,
+                                       int b8_gap, int H, evc_f16* hbuf, evc_bf16* hbuf_bf16, float* c_state, float* h_state, void* gates,
+                                       evc_bf16* c_all) {
+  const long ldh = h_lo ? 2L * H : 3L * H / 2;      // halfwords per hbuf row
+  // integer frames: the accumulators start from x_col_const, the true bias is added behind the x-part
+  FwdLayer L;
+  L.x = x; L.ldx = ldx; L.kx = kx16;
+  L.h = hbuf; L.ldh = ldh; L.kh = H;
+  L.B = wT16; L.ldb = (long)kx16 + H;
+  L.bias = x_col_const ? x_col_const : bias; L.c_state = c_state; L.h_state = h_state; L.gates = gates; L.c_all = c_all;
+  L.h_wide = h_lo ? 3 : 2; L.h_copy = hbuf_bf16; L.ld_copy = H;
+  L.x8_off = x8_off; L.kx8 = kx8; L.kh8 = h_lo ? 2 * H : H;
+  L.B8 = wT8; L.ldb8 = (long)kx8 + b8_gap + L.kh8; L.b8_gap = b8_gap; L.scale8_exp = -(7 + w8_scale_exp);
+  if (x_row_scale) { L.row_scale = x_row_scale; L.col_add = bias; }
+  return L;
+}
+
 // "High" precision L1 layer with the weights' low-order halves contracted in fp8: per step
 //   z = [x16 | h16] . [W16x | W16h]^T  (IEEE f16, v_mfma_f32_16x16x32_f16)  +  2^-(7 + w8_scale_exp) [x8 | h8] . [W8x | W8h]^T  (OCP e4m3,
 //   v_mfma_scale_f32_16x16x128_f8f6f4: per K element twice the MFMA rate)
@@ -576,89 +722,31 @@ static inline int pick_fwd_tile_v3(int rows, int H) {
 // h_lo = 1 (round 6): the low-order half of h is corrected too - hbuf rows are 4H bytes [f16(h) | e4m3(h 2^7) | e4m3((h - f16(h)) 2^18)] and the
 // h-part of wT8's rows is [lo(Wh) | hi(Wh)] (evc_cast_f32_to_fp8_lo with hi_tail): wT8 [4H][kx8 + 2H]; a layer above reads those rows with
 // x8_off = 2H, kx8 = 2H against [lo(Wx) | hi(Wx)].
+// x_row_scale (integer frames): acc = acc * rs[row] + bias behind the x-part of the f16 stages; the accumulators start from x_col_const.
 extern "C" int evc_lstm_layer_fwd_f16_fp8lo(const evc_f16* x, int64_t ldx, int kx16, int64_t x8_off, int kx8, const evc_f16* wT16,
                                             const uint8_t* wT8, int w8_scale_exp, int h_lo, const float* bias, const int32_t* len,
                                             int T, int M, int H, evc_f16* hbuf, evc_bf16* hbuf_bf16, float* c_state, float* h_state,
                                             int64_t ld_state, void* gates, evc_bf16* c_all, const int32_t* row_map,
                                             const int32_t* rows_per_step, const float* x_row_scale, const float* x_col_const, int b8_gap, void* stream) {
-  EVC_REQUIRE(T > 0 && M > 0 && H > 0 && kx16 > 0 && kx8 > 0, EVC_ERR_BAD_SHAPE, "evc_lstm_layer_fwd_f16_fp8lo: bad shape");
-  EVC_REQUIRE((x_row_scale == nullptr) == (x_col_const == nullptr) && b8_gap >= 0 && b8_gap % 128 == 0 && (x_row_scale || b8_gap == 0) &&
-              (!x_col_const || ((uintptr_t)x_col_const % 16) == 0), EVC_ERR_BAD_ARG,
-              "evc_lstm_layer_fwd_f16_fp8lo: x_row_scale and x_col_const go together (16-byte aligned), b8_gap=%d (%%128) only with them", b8_gap);
-  EVC_REQUIRE(kx16 % 64 == 0 && H % 128 == 0 && kx8 % 128 == 0 && kx8 >= 384, EVC_ERR_BAD_SHAPE,
-              "evc_lstm_layer_fwd_f16_fp8lo: kx16=%d (%%64), H=%d (%%128), kx8=%d (%%128, >= 384: the ring must be full of e4m3 stages at t = 0)", kx16, H, kx8);
+  const char* entry = "evc_lstm_layer_fwd_f16_fp8lo";
+  EVC_TRY(fwd_shape_ok(entry, T, M, kx16, H, 128));
+  EVC_TRY(fwd_xint_ok(entry, x_row_scale, x_col_const, b8_gap));
   EVC_REQUIRE(x && wT16 && wT8 && hbuf && hbuf_bf16 && bias && len, EVC_ERR_BAD_ARG, "evc_lstm_layer_fwd_f16_fp8lo: NULL operand");
-  EVC_REQUIRE(ldx % 8 == 0 && x8_off % 16 == 0 && ldx >= kx16 && ldx * 2 >= x8_off + kx8 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)wT16 % 16) == 0 &&
-              ((uintptr_t)wT8 % 16) == 0 && ((uintptr_t)hbuf % 16) == 0 && ((uintptr_t)hbuf_bf16 % 8) == 0, EVC_ERR_BAD_ALIGN,
-              "evc_lstm_layer_fwd_f16_fp8lo: ldx=%ld (%%8), x8_off=%ld (%%16), 16-byte aligned operands", (long)ldx, (long)x8_off);
+  EVC_TRY(fwd_x8_ok(entry, x, ldx, kx16, x8_off, kx8));
+  EVC_REQUIRE(aligned_to(wT16, 16) && aligned_to(wT8, 16), EVC_ERR_BAD_ALIGN, "evc_lstm_layer_fwd_f16_fp8lo: 16-byte aligned weight images");
   EVC_REQUIRE(w8_scale_exp >= 0 && w8_scale_exp <= 60, EVC_ERR_BAD_ARG, "evc_lstm_layer_fwd_f16_fp8lo: w8_scale_exp=%d", w8_scale_exp);
   EVC_REQUIRE(h_lo == 0 || h_lo == 1, EVC_ERR_BAD_ARG, "evc_lstm_layer_fwd_f16_fp8lo: h_lo=%d", h_lo);
-  const long ldh = h_lo ? 2L * H : 3L * H / 2;      // halfwords per hbuf row
-  const int kh8 = h_lo ? 2 * H : H;                 // e4m3 bytes of the h-part per row
-  EVC_REQUIRE(ring_operand_ok(M, ldx > ldh ? ldx : ldh) && ring_operand_ok(4L * H, (long)kx16 + H), EVC_ERR_BAD_SHAPE,
+  const FwdShared S{len, T, M, H, ld_state, row_map, rows_per_step};
+  const FwdLayer L = fwd_layer_fp8lo(x, ldx, kx16, x8_off, kx8, wT16, wT8, w8_scale_exp, h_lo, bias, x_row_scale, x_col_const, b8_gap, H, hbuf,
+                                     hbuf_bf16, c_state, h_state, gates, c_all);
+  EVC_REQUIRE(ring_operand_ok(M, ldx > L.ldh ? ldx : L.ldh) && ring_operand_ok(4L * H, (long)kx16 + H), EVC_ERR_BAD_SHAPE,
               "evc_lstm_layer_fwd_f16_fp8lo: a time slab or the kernel spans 4 GiB or more");
-  EVC_REQUIRE(fwd_tail_ok(M, H, ld_state), EVC_ERR_BAD_SHAPE, "LSTM forward: a gate-record / state slab spans 4 GiB or more (M=%d H=%d ld_state=%ld)", M, H, (long)ld_state);
-  EVC_REQUIRE(ld_state % 4 == 0 && ((uintptr_t)c_state % 16) == 0 && ((uintptr_t)h_state % 16) == 0 && ((uintptr_t)bias % 16) == 0, EVC_ERR_BAD_ALIGN,
-              "evc_lstm_layer_fwd_f16_fp8lo: state/bias must allow 16-byte vector access");
-  EVC_REQUIRE((gates == nullptr) == (c_all == nullptr), EVC_ERR_BAD_ARG, "evc_lstm_layer_fwd_f16_fp8lo: gates and c_all go together");
-  EVC_REQUIRE(!gates || (((uintptr_t)gates % 16) == 0 && ((uintptr_t)c_all % 8) == 0), EVC_ERR_BAD_ALIGN,
-              "evc_lstm_layer_fwd_f16_fp8lo: gates must be 16-byte, c_all 8-byte aligned");
-  if (rows_per_step)
-    for (int t = 0; t < T; ++t)
-      EVC_REQUIRE(rows_per_step[t] >= 0 && rows_per_step[t] <= M && (t == 0 || rows_per_step[t] <= rows_per_step[t - 1]), EVC_ERR_BAD_ARG,
-                  "evc_lstm_layer_fwd_f16_fp8lo: rows_per_step[%d]=%d must be non-increasing and within [0, M=%d]", t, rows_per_step[t], M);
+  EVC_TRY(fwd_shared_ok(entry, S));
+  EVC_TRY(fwd_layer_ok(entry, L, 16));
   hipStream_t st = (hipStream_t)stream;
-  const bf16_t* xb = (const bf16_t*)x;
-  bf16_t* hb = (bf16_t*)hbuf;
-  EVC_CHECK_HIP(hipMemsetAsync(hb, 0, (size_t)M * ldh * sizeof(bf16_t), st));            // h_{-1} = 0 (both parts of the rows)
-  EVC_CHECK_HIP(hipMemsetAsync(hbuf_bf16, 0, (size_t)M * H * sizeof(bf16_t), st));
-  for (int t = 0; t < T; ++t) {
-    const int Mt = rows_per_step ? rows_per_step[t] : M;
-    if (Mt == 0) break;
-    GemmOperands p;
-    p.M = Mt; p.Nu = H; p.group_stride = H; p.nk1 = p.nk2 = 0;
-    p.A1lo = p.A2lo = p.Blo = nullptr;
-    const bf16_t* xt = xb + (long)t * M * ldx;
-    const bf16_t* hprev = hb + (long)t * M * ldh;
-    p.A1 = xt; p.lda1 = ldx;
-    p.A2 = hprev; p.lda2 = ldh;
-    p.B = (const bf16_t*)wT16; p.ldb = (long)kx16 + H;
-    p.A3 = (const uint8_t*)xt + x8_off; p.lda3 = ldx * 2; p.nk3 = kx8 / 128;
-    p.A4 = (const uint8_t*)(hprev + H); p.lda4 = ldh * 2; p.nk4 = t == 0 ? 0 : kh8 / 128;
-    p.B8 = wT8; p.ldb8 = (long)kx8 + b8_gap + kh8; p.b8_gap = b8_gap;
-    p.scale8_exp = -(7 + w8_scale_exp);
-    if (x_row_scale) {          // integer frames: acc = acc * rs[row] + bias behind the x-part of the f16 stages; the accumulators start from x_col_const
-      p.row_scale = x_row_scale + (long)t * M; p.col_add = bias; p.g2_add = 1.0f;
-    }
-    const int k1 = kx16, k2 = t == 0 ? 0 : H;
-    LstmFwdParams e;
-    e.zx = nullptr; e.ldzx = 0;
-    e.bias = x_col_const ? x_col_const : bias; e.len = len; e.t = t;
-    e.c_state = c_state; e.h_state = h_state; e.ld_state = ld_state;
-    e.hout = hb + (long)(t + 1) * M * ldh; e.h_wide = h_lo ? 3 : 2;
-    e.hout_lo = hbuf_bf16 + (long)(t + 1) * M * H;
-    e.gates = gates ? (uint2*)gates + (long)t * M * H : nullptr;
-    e.c_hist = c_all ? c_all + (long)(t + 1) * M * H : nullptr;
-    e.row_map = row_map;
-    e.M = Mt; e.H = H;
-    if (x_row_scale) {
-      switch (pick_fwd_tile_v3(Mt, H)) {
-        case 0: launch_lstm_fwd<CfgLstmV3_256, false, true, true, true>(p, e, k1, k2, st); break;
-        case 1: launch_lstm_fwd<CfgLstmV3_224, false, true, true, true>(p, e, k1, k2, st); break;
-        case 2: launch_lstm_fwd<CfgLstmV3_192, false, true, true, true>(p, e, k1, k2, st); break;
-        case 4: launch_lstm_fwd<CfgLstmV3_240, false, true, true, true>(p, e, k1, k2, st); break;
-        default: launch_lstm_fwd<CfgLstmV3_160, false, true, true, true>(p, e, k1, k2, st); break;
-      }
-      continue;
-    }
-    switch (pick_fwd_tile_v3(Mt, H)) {
-      case 0: launch_lstm_fwd<CfgLstmV3_256, false, true, true>(p, e, k1, k2, st); break;
-      case 1: launch_lstm_fwd<CfgLstmV3_224, false, true, true>(p, e, k1, k2, st); break;
-      case 2: launch_lstm_fwd<CfgLstmV3_192, false, true, true>(p, e, k1, k2, st); break;
-      case 4: launch_lstm_fwd<CfgLstmV3_240, false, true, true>(p, e, k1, k2, st); break;
-      default: launch_lstm_fwd<CfgLstmV3_160, false, true, true>(p, e, k1, k2, st); break;
-    }
-  }
+  EVC_TRY(fwd_clear_h(S, L, st));                    // (every part of the rows)
+  EVC_TRY(fwd_clear_copy(S, L, st));
+  fwd_layer_loop(S, L, [&](const FwdStep& s) { launch_fwd_step_e4m3(s, pick_fwd_tile_v3(s.e.M, H), x_row_scale != nullptr, st); });
   EVC_LAUNCH_CHECK();
   return EVC_OK;
 }
@@ -679,76 +767,38 @@ extern "C" int evc_lstm_layer_fwd_f16_dith(const evc_f16* x, int64_t ldx, int kx
                                            const int32_t* len, int T, int M, int H, evc_f16* hbuf, evc_bf16* hbuf_bf16, float* c_state,
                                            float* h_state, int64_t ld_state, void* gates, evc_bf16* c_all, const int32_t* row_map,
                                            const int32_t* rows_per_step, void* stream) {
+  const char* entry = "evc_lstm_layer_fwd_f16_dith";
   EVC_REQUIRE(T > 0 && M > 0 && H > 0 && kx16 > 0 && kx8 >= 0, EVC_ERR_BAD_SHAPE, "evc_lstm_layer_fwd_f16_dith: bad shape");
   EVC_REQUIRE(x && wT16 && hbuf && hbuf_bf16 && bias && len, EVC_ERR_BAD_ARG, "evc_lstm_layer_fwd_f16_dith: NULL operand");
-  EVC_REQUIRE(w16_step_stride >= 0 && w16_step_stride % 8 == 0 && ((uintptr_t)wT16 % 16) == 0, EVC_ERR_BAD_ALIGN,
+  EVC_REQUIRE(w16_step_stride >= 0 && w16_step_stride % 8 == 0 && aligned_to(wT16, 16), EVC_ERR_BAD_ALIGN,
               "evc_lstm_layer_fwd_f16_dith: w16_step_stride=%ld (>= 0, %%8: every image 16-byte aligned)", (long)w16_step_stride);
   EVC_REQUIRE(w16_step_stride == 0 || w16_step_stride >= 4L * H * ((long)kx16 + H), EVC_ERR_BAD_ARG,
               "evc_lstm_layer_fwd_f16_dith: w16_step_stride=%ld is smaller than one [4H][kx16 + H] image", (long)w16_step_stride);
   if (kx8 == 0) {                // no e4m3 stages: the plain f16 layer on per-step images
-    EVC_REQUIRE(ldx >= kx16 && ldx % 8 == 0 && ((uintptr_t)hbuf_bf16 % 8) == 0, EVC_ERR_BAD_ALIGN, "evc_lstm_layer_fwd_f16_dith: ldx=%ld (>= kx16=%d, %%8)", (long)ldx, kx16);
-    return lstm_layer_fwd_impl((const evc_bf16*)x, (const evc_bf16*)wT16, bias, len, T, M, kx16, H, 0, nullptr, (evc_bf16*)hbuf, c_state, h_state,
+    EVC_REQUIRE(ldx >= kx16 && ldx % 8 == 0, EVC_ERR_BAD_ALIGN, "evc_lstm_layer_fwd_f16_dith: ldx=%ld (>= kx16=%d, %%8)", (long)ldx, kx16);
+    return lstm_layer_fwd_impl(entry, (const evc_bf16*)x, (const evc_bf16*)wT16, bias, len, T, M, kx16, H, 0, nullptr, (evc_bf16*)hbuf, c_state, h_state,
                                ld_state, gates, c_all, hbuf_bf16, row_map, rows_per_step, stream, 1, ldx, 0, w16_step_stride);
   }
-  EVC_REQUIRE(kx16 % 64 == 0 && H % 128 == 0 && kx8 % 128 == 0 && kx8 >= 384, EVC_ERR_BAD_SHAPE,
-              "evc_lstm_layer_fwd_f16_dith: kx16=%d (%%64), H=%d (%%128), kx8=%d (%%128, >= 384: the ring must be full of e4m3 stages at t = 0)", kx16, H, kx8);
-  EVC_REQUIRE(wT8 && ldb8 >= kx8 && ldb8 % 16 == 0 && ((uintptr_t)wT8 % 16) == 0, EVC_ERR_BAD_ARG, "evc_lstm_layer_fwd_f16_dith: wT8 rows of ldb8=%ld bytes (>= kx8, %%16)", (long)ldb8);
-  EVC_REQUIRE(ldx % 8 == 0 && x8_off % 16 == 0 && ldx >= kx16 && ldx * 2 >= x8_off + kx8 && ((uintptr_t)x % 16) == 0 &&
-              ((uintptr_t)hbuf % 16) == 0 && ((uintptr_t)hbuf_bf16 % 8) == 0, EVC_ERR_BAD_ALIGN,
-              "evc_lstm_layer_fwd_f16_dith: ldx=%ld (%%8), x8_off=%ld (%%16), 16-byte aligned operands", (long)ldx, (long)x8_off);
+  EVC_TRY(fwd_shape_ok(entry, T, M, kx16, H, 128));
+  EVC_TRY(fwd_x8_ok(entry, x, ldx, kx16, x8_off, kx8));
+  EVC_REQUIRE(wT8 && ldb8 >= kx8 && ldb8 % 16 == 0 && aligned_to(wT8, 16), EVC_ERR_BAD_ARG, "evc_lstm_layer_fwd_f16_dith: wT8 rows of ldb8=%ld bytes (>= kx8, %%16)", (long)ldb8);
   EVC_REQUIRE(scale8_exp >= 0 && scale8_exp <= 80, EVC_ERR_BAD_ARG, "evc_lstm_layer_fwd_f16_dith: scale8_exp=%d", scale8_exp);
-  const long ldh = H;                                // halfwords per hbuf row (plain)
-  EVC_REQUIRE(ring_operand_ok(M, ldx > ldh ? ldx : ldh) && ring_operand_ok(4L * H, (long)kx16 + H) && ring_operand_ok(4L * H, (ldb8 + 1) / 2), EVC_ERR_BAD_SHAPE,
+  const FwdShared S{len, T, M, H, ld_state, row_map, rows_per_step};
+  FwdLayer L;
+  L.x = x; L.ldx = ldx; L.kx = kx16;
+  L.h = hbuf; L.ldh = H; L.kh = H;      // plain f16 h rows: no e4m3 stages of h
+  L.B = wT16; L.ldb = (long)kx16 + H;
+  L.bias = bias; L.c_state = c_state; L.h_state = h_state; L.gates = gates; L.c_all = c_all;
+  L.w_step_stride = w16_step_stride; L.h_copy = hbuf_bf16; L.ld_copy = H;
+  L.x8_off = x8_off; L.kx8 = kx8; L.B8 = wT8; L.ldb8 = ldb8; L.scale8_exp = -scale8_exp;
+  EVC_REQUIRE(ring_operand_ok(M, ldx > L.ldh ? ldx : L.ldh) && ring_operand_ok(4L * H, (long)kx16 + H) && ring_operand_ok(4L * H, (ldb8 + 1) / 2), EVC_ERR_BAD_SHAPE,
               "evc_lstm_layer_fwd_f16_dith: a time slab or a weight image spans 4 GiB or more");
-  EVC_REQUIRE(fwd_tail_ok(M, H, ld_state), EVC_ERR_BAD_SHAPE, "LSTM forward: a gate-record / state slab spans 4 GiB or more (M=%d H=%d ld_state=%ld)", M, H, (long)ld_state);
-  EVC_REQUIRE(ld_state % 4 == 0 && ((uintptr_t)c_state % 16) == 0 && ((uintptr_t)h_state % 16) == 0 && ((uintptr_t)bias % 16) == 0, EVC_ERR_BAD_ALIGN,
-              "evc_lstm_layer_fwd_f16_dith: state/bias must allow 16-byte vector access");
-  EVC_REQUIRE((gates == nullptr) == (c_all == nullptr), EVC_ERR_BAD_ARG, "evc_lstm_layer_fwd_f16_dith: gates and c_all go together");
-  EVC_REQUIRE(!gates || (((uintptr_t)gates % 16) == 0 && ((uintptr_t)c_all % 8) == 0), EVC_ERR_BAD_ALIGN,
-              "evc_lstm_layer_fwd_f16_dith: gates must be 16-byte, c_all 8-byte aligned");
-  if (rows_per_step)
-    for (int t = 0; t < T; ++t)
-      EVC_REQUIRE(rows_per_step[t] >= 0 && rows_per_step[t] <= M && (t == 0 || rows_per_step[t] <= rows_per_step[t - 1]), EVC_ERR_BAD_ARG,
-                  "evc_lstm_layer_fwd_f16_dith: rows_per_step[%d]=%d must be non-increasing and within [0, M=%d]", t, rows_per_step[t], M);
+  EVC_TRY(fwd_shared_ok(entry, S));
+  EVC_TRY(fwd_layer_ok(entry, L, 16));
   hipStream_t st = (hipStream_t)stream;
-  const bf16_t* xb = (const bf16_t*)x;
-  bf16_t* hb = (bf16_t*)hbuf;
-  EVC_CHECK_HIP(hipMemsetAsync(hb, 0, (size_t)M * ldh * sizeof(bf16_t), st));            // h_{-1} = 0
-  EVC_CHECK_HIP(hipMemsetAsync(hbuf_bf16, 0, (size_t)M * H * sizeof(bf16_t), st));
-  for (int t = 0; t < T; ++t) {
-    const int Mt = rows_per_step ? rows_per_step[t] : M;
-    if (Mt == 0) break;
-    GemmOperands p;
-    p.M = Mt; p.Nu = H; p.group_stride = H; p.nk1 = p.nk2 = 0;
-    p.A1lo = p.A2lo = p.Blo = nullptr;
-    const bf16_t* xt = xb + (long)t * M * ldx;
-    const bf16_t* hprev = hb + (long)t * M * ldh;
-    p.A1 = xt; p.lda1 = ldx;
-    p.A2 = hprev; p.lda2 = ldh;
-    p.B = (const bf16_t*)wT16 + (long)t * w16_step_stride; p.ldb = (long)kx16 + H;
-    p.A3 = (const uint8_t*)xt + x8_off; p.lda3 = ldx * 2; p.nk3 = kx8 / 128;
-    p.A4 = p.A3; p.lda4 = p.lda3; p.nk4 = 0;                                            // no e4m3 stages of h
-    p.B8 = wT8; p.ldb8 = ldb8;
-    p.scale8_exp = -scale8_exp;
-    const int k1 = kx16, k2 = t == 0 ? 0 : H;
-    LstmFwdParams e;
-    e.zx = nullptr; e.ldzx = 0;
-    e.bias = bias; e.len = len; e.t = t;
-    e.c_state = c_state; e.h_state = h_state; e.ld_state = ld_state;
-    e.hout = hb + (long)(t + 1) * M * ldh; e.h_wide = 0;
-    e.hout_lo = hbuf_bf16 + (long)(t + 1) * M * H;
-    e.gates = gates ? (uint2*)gates + (long)t * M * H : nullptr;
-    e.c_hist = c_all ? c_all + (long)(t + 1) * M * H : nullptr;
-    e.row_map = row_map;
-    e.M = Mt; e.H = H;
-    switch (pick_fwd_tile_v3(Mt, H)) {
-      case 0: launch_lstm_fwd<CfgLstmV3_256, false, true, true>(p, e, k1, k2, st); break;
-      case 1: launch_lstm_fwd<CfgLstmV3_224, false, true, true>(p, e, k1, k2, st); break;
-      case 2: launch_lstm_fwd<CfgLstmV3_192, false, true, true>(p, e, k1, k2, st); break;
-      case 4: launch_lstm_fwd<CfgLstmV3_240, false, true, true>(p, e, k1, k2, st); break;
-      default: launch_lstm_fwd<CfgLstmV3_160, false, true, true>(p, e, k1, k2, st); break;
-    }
-  }
+  EVC_TRY(fwd_clear_h(S, L, st));
+  EVC_TRY(fwd_clear_copy(S, L, st));
+  fwd_layer_loop(S, L, [&](const FwdStep& s) { launch_fwd_step_e4m3(s, pick_fwd_tile_v3(s.e.M, H), false, st); });
   EVC_LAUNCH_CHECK();
   return EVC_OK;
 }
@@ -756,135 +806,60 @@ extern "C" int evc_lstm_layer_fwd_f16_dith(const evc_f16* x, int64_t ldx, int kx
 // The two-layer L1 level of the "high" mode in T + 1 launches (round 6): layer 0 as evc_lstm_layer_fwd_f16_fp8lo (f16 stages + the e4m3 stages of its
 // weights' / activations' low-order halves; integer frames with x_row_scale), layer 1 as evc_lstm_layer_fwd_f16_dith with kx8 = 0 (plain f16 stages on the
 // time-dithered image of its step), layer 0's step s and layer 1's step s-1 per launch, every workgroup walking both tiles (lstm_fwd_walk2_kernel: the second
-// tile's ring fill under the first tile's gate tail).  Same arithmetic as the two layer calls: bit-identical results.  Argument meaning as in those two
-// entries; hbuf0 rows are layer 1's x rows (row stride 2H halfwords with h_lo, else 3H/2).  Launches whose tile is not 224 / 240 / 256 rows run separately.
+// tile's ring fill under the first tile's gate tail, each tile's loop and gate tail in its own mode).  Same arithmetic as the two layer calls: bit-identical
+// results.  Argument meaning as in those two entries; hbuf0 rows are layer 1's x rows (row stride 2H halfwords with h_lo, else 3H/2).  Launches whose tile is
+// not 224 / 240 / 256 rows run separately, both on the tile picked for the launch.
 extern "C" int evc_lstm_level2_fwd_high(const evc_f16* x, int64_t ldx, int kx16, int64_t x8_off, int kx8, const evc_f16* wT16_0, const uint8_t* wT8_0,
                                         int w8_scale_exp, int h_lo, const float* bias0, const float* x_row_scale, const float* x_col_const, int b8_gap,
                                         const evc_f16* wT16_1, int64_t w16_step_stride, const float* bias1, const int32_t* len, int T, int M, int H,
                                         evc_f16* hbuf0, evc_bf16* hbuf0_bf16, evc_f16* hbuf1, evc_bf16* hbuf1_bf16, float* c_state0, float* h_state0,
                                         float* c_state1, float* h_state1, int64_t ld_state, void* gates0, evc_bf16* c_all0, void* gates1, evc_bf16* c_all1,
                                         const int32_t* row_map, const int32_t* rows_per_step, void* stream) {
-  EVC_REQUIRE(T > 0 && M > 0 && H > 0 && kx16 > 0 && kx8 > 0, EVC_ERR_BAD_SHAPE, "evc_lstm_level2_fwd_high: bad shape");
-  EVC_REQUIRE((x_row_scale == nullptr) == (x_col_const == nullptr) && b8_gap >= 0 && b8_gap % 128 == 0 && (x_row_scale || b8_gap == 0) &&
-              (!x_col_const || ((uintptr_t)x_col_const % 16) == 0), EVC_ERR_BAD_ARG,
-              "evc_lstm_level2_fwd_high: x_row_scale and x_col_const go together (16-byte aligned), b8_gap=%d (%%128) only with them", b8_gap);
-  EVC_REQUIRE(kx16 % 64 == 0 && H % 128 == 0 && kx8 % 128 == 0 && kx8 >= 384, EVC_ERR_BAD_SHAPE,
-              "evc_lstm_level2_fwd_high: kx16=%d (%%64), H=%d (%%128), kx8=%d (%%128, >= 384)", kx16, H, kx8);
+  const char* entry = "evc_lstm_level2_fwd_high";
+  EVC_TRY(fwd_shape_ok(entry, T, M, kx16, H, 128));
+  EVC_TRY(fwd_xint_ok(entry, x_row_scale, x_col_const, b8_gap));
   EVC_REQUIRE(x && wT16_0 && wT8_0 && wT16_1 && hbuf0 && hbuf0_bf16 && hbuf1 && hbuf1_bf16 && bias0 && bias1 && len && c_state0 && h_state0 && c_state1 &&
               h_state1, EVC_ERR_BAD_ARG, "evc_lstm_level2_fwd_high: NULL operand");
-  EVC_REQUIRE(ldx % 8 == 0 && x8_off % 16 == 0 && ldx >= kx16 && ldx * 2 >= x8_off + kx8 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)wT16_0 % 16) == 0 &&
-              ((uintptr_t)wT8_0 % 16) == 0 && ((uintptr_t)wT16_1 % 16) == 0 && ((uintptr_t)hbuf0 % 16) == 0 && ((uintptr_t)hbuf1 % 16) == 0 &&
-              ((uintptr_t)hbuf0_bf16 % 8) == 0 && ((uintptr_t)hbuf1_bf16 % 8) == 0, EVC_ERR_BAD_ALIGN,
-              "evc_lstm_level2_fwd_high: ldx=%ld (%%8), x8_off=%ld (%%16), 16-byte aligned operands", (long)ldx, (long)x8_off);
+  EVC_TRY(fwd_x8_ok(entry, x, ldx, kx16, x8_off, kx8));
+  EVC_REQUIRE(aligned_to(wT16_0, 16) && aligned_to(wT8_0, 16) && aligned_to(wT16_1, 16), EVC_ERR_BAD_ALIGN, "evc_lstm_level2_fwd_high: 16-byte aligned weight images");
   EVC_REQUIRE(w8_scale_exp >= 0 && w8_scale_exp <= 60 && (h_lo == 0 || h_lo == 1), EVC_ERR_BAD_ARG, "evc_lstm_level2_fwd_high: w8_scale_exp=%d h_lo=%d",
               w8_scale_exp, h_lo);
   EVC_REQUIRE(w16_step_stride >= 0 && w16_step_stride % 8 == 0 && (w16_step_stride == 0 || w16_step_stride >= 4L * H * 2 * H), EVC_ERR_BAD_ARG,
               "evc_lstm_level2_fwd_high: w16_step_stride=%ld (0 or at least one [4H][2H] image, %%8)", (long)w16_step_stride);
-  const long ldh0 = h_lo ? 2L * H : 3L * H / 2;     // halfwords per hbuf0 row
-  const int kh8 = h_lo ? 2 * H : H;                 // e4m3 bytes of layer 0's h-part per row
-  EVC_REQUIRE(ring_operand_ok(M, ldx > ldh0 ? ldx : ldh0) && ring_operand_ok(4L * H, (long)kx16 + H) && ring_operand_ok(4L * H, 2L * H), EVC_ERR_BAD_SHAPE,
+  const FwdShared S{len, T, M, H, ld_state, row_map, rows_per_step};
+  const FwdLayer L0 = fwd_layer_fp8lo(x, ldx, kx16, x8_off, kx8, wT16_0, wT8_0, w8_scale_exp, h_lo, bias0, x_row_scale, x_col_const, b8_gap, H, hbuf0,
+                                      hbuf0_bf16, c_state0, h_state0, gates0, c_all0);
+  // layer 1: the plain f16 step on image t; x_t = the f16 part of layer 0's row slab t + 1
+  FwdLayer L1;
+  L1.x = hbuf0 + (long)M * L0.ldh; L1.ldx = L0.ldh; L1.kx = H;
+  L1.h = hbuf1; L1.ldh = H; L1.kh = H;
+  L1.B = wT16_1; L1.ldb = 2L * H;
+  L1.bias = bias1; L1.c_state = c_state1; L1.h_state = h_state1; L1.gates = gates1; L1.c_all = c_all1;
+  L1.w_step_stride = w16_step_stride; L1.h_copy = hbuf1_bf16; L1.ld_copy = H;
+  EVC_REQUIRE(ring_operand_ok(M, ldx > L0.ldh ? ldx : L0.ldh) && ring_operand_ok(4L * H, (long)kx16 + H) && ring_operand_ok(4L * H, 2L * H), EVC_ERR_BAD_SHAPE,
               "evc_lstm_level2_fwd_high: a time slab or a kernel spans 4 GiB or more");
-  EVC_REQUIRE(fwd_tail_ok(M, H, ld_state), EVC_ERR_BAD_SHAPE, "LSTM forward: a gate-record / state slab spans 4 GiB or more (M=%d H=%d ld_state=%ld)", M, H, (long)ld_state);
-  EVC_REQUIRE(ld_state % 4 == 0 && ((uintptr_t)c_state0 % 16) == 0 && ((uintptr_t)h_state0 % 16) == 0 && ((uintptr_t)c_state1 % 16) == 0 &&
-              ((uintptr_t)h_state1 % 16) == 0 && ((uintptr_t)bias0 % 16) == 0 && ((uintptr_t)bias1 % 16) == 0, EVC_ERR_BAD_ALIGN,
-              "evc_lstm_level2_fwd_high: state/bias must allow 16-byte vector access");
-  EVC_REQUIRE((gates0 == nullptr) == (c_all0 == nullptr) && (gates1 == nullptr) == (c_all1 == nullptr) && (gates0 == nullptr) == (gates1 == nullptr),
-              EVC_ERR_BAD_ARG, "evc_lstm_level2_fwd_high: gates and c_all go together, for both layers");
-  EVC_REQUIRE(!gates0 || (((uintptr_t)gates0 % 16) == 0 && ((uintptr_t)gates1 % 16) == 0 && ((uintptr_t)c_all0 % 8) == 0 && ((uintptr_t)c_all1 % 8) == 0),
-              EVC_ERR_BAD_ALIGN, "evc_lstm_level2_fwd_high: gates must be 16-byte, c_all 8-byte aligned");
-  if (rows_per_step)
-    for (int t = 0; t < T; ++t)
-      EVC_REQUIRE(rows_per_step[t] >= 0 && rows_per_step[t] <= M && (t == 0 || rows_per_step[t] <= rows_per_step[t - 1]), EVC_ERR_BAD_ARG,
-                  "evc_lstm_level2_fwd_high: rows_per_step[%d]=%d must be non-increasing and within [0, M=%d]", t, rows_per_step[t], M);
+  EVC_TRY(fwd_shared_ok(entry, S));
+  EVC_TRY(fwd_layers2_ok(entry, L0, L1, 16));
   hipStream_t st = (hipStream_t)stream;
-  const bf16_t* xb = (const bf16_t*)x;
-  bf16_t* hb0 = (bf16_t*)hbuf0;
-  bf16_t* hb1 = (bf16_t*)hbuf1;
-  EVC_CHECK_HIP(hipMemsetAsync(hb0, 0, (size_t)M * ldh0 * sizeof(bf16_t), st));          // h_{-1} = 0: every image of both layers' rows
-  EVC_CHECK_HIP(hipMemsetAsync(hbuf0_bf16, 0, (size_t)M * H * sizeof(bf16_t), st));
-  EVC_CHECK_HIP(hipMemsetAsync(hb1, 0, (size_t)M * H * sizeof(bf16_t), st));
-  EVC_CHECK_HIP(hipMemsetAsync(hbuf1_bf16, 0, (size_t)M * H * sizeof(bf16_t), st));
-  auto step0 = [&](int t, GemmOperands& p, LstmFwdParams& e, int& k1, int& k2) {          // layer 0: evc_lstm_layer_fwd_f16_fp8lo's step t
-    p = GemmOperands();
-    p.M = rows_per_step ? rows_per_step[t] : M; p.Nu = H; p.group_stride = H; p.nk1 = p.nk2 = 0;
-    p.A1lo = p.A2lo = p.Blo = nullptr;
-    const bf16_t* xt = xb + (long)t * M * ldx;
-    const bf16_t* hprev = hb0 + (long)t * M * ldh0;
-    p.A1 = xt; p.lda1 = ldx;
-    p.A2 = hprev; p.lda2 = ldh0;
-    p.B = (const bf16_t*)wT16_0; p.ldb = (long)kx16 + H;
-    p.A3 = (const uint8_t*)xt + x8_off; p.lda3 = ldx * 2; p.nk3 = kx8 / 128;
-    p.A4 = (const uint8_t*)(hprev + H); p.lda4 = ldh0 * 2; p.nk4 = t == 0 ? 0 : kh8 / 128;
-    p.B8 = wT8_0; p.ldb8 = (long)kx8 + b8_gap + kh8; p.b8_gap = b8_gap;
-    p.scale8_exp = -(7 + w8_scale_exp);
-    if (x_row_scale) { p.row_scale = x_row_scale + (long)t * M; p.col_add = bias0; p.g2_add = 1.0f; }
-    k1 = kx16; k2 = t == 0 ? 0 : H;
-    e = LstmFwdParams();
-    e.zx = nullptr; e.ldzx = 0;
-    e.bias = x_col_const ? x_col_const : bias0; e.len = len; e.t = t;
-    e.c_state = c_state0; e.h_state = h_state0; e.ld_state = ld_state;
-    e.hout = hb0 + (long)(t + 1) * M * ldh0; e.h_wide = h_lo ? 3 : 2;
-    e.hout_lo = hbuf0_bf16 + (long)(t + 1) * M * H;
-    e.gates = gates0 ? (uint2*)gates0 + (long)t * M * H : nullptr;
-    e.c_hist = c_all0 ? c_all0 + (long)(t + 1) * M * H : nullptr;
-    e.row_map = row_map;
-    e.M = p.M; e.H = H;
-  };
-  auto step1 = [&](int t, GemmOperands& p, LstmFwdParams& e, int& k1, int& k2) {          // layer 1: the plain f16 step on image t; x_t = layer 0's row slab t + 1
-    p = GemmOperands();
-    p.M = rows_per_step ? rows_per_step[t] : M; p.Nu = H; p.group_stride = H; p.ldb = 2L * H; p.nk1 = p.nk2 = 0;
-    p.A1lo = p.A2lo = p.Blo = nullptr;
-    p.A1 = hb0 + (long)(t + 1) * M * ldh0; p.lda1 = ldh0; k1 = H;
-    p.A2 = hb1 + (long)t * M * H; p.lda2 = H; k2 = t == 0 ? 0 : H;
-    p.B = (const bf16_t*)wT16_1 + (long)t * w16_step_stride;
-    e = LstmFwdParams();
-    e.zx = nullptr; e.ldzx = 4L * H;
-    e.bias = bias1; e.len = len; e.t = t;
-    e.c_state = c_state1; e.h_state = h_state1; e.ld_state = ld_state;
-    e.hout = hb1 + (long)(t + 1) * M * H; e.h_wide = 0;
-    e.hout_lo = hbuf1_bf16 + (long)(t + 1) * M * H;
-    e.gates = gates1 ? (uint2*)gates1 + (long)t * M * H : nullptr;
-    e.c_hist = c_all1 ? c_all1 + (long)(t + 1) * M * H : nullptr;
-    e.row_map = row_map;
-    e.M = p.M; e.H = H;
-  };
-  for (int s = 0; s <= T; ++s) {
-    GemmOperands pa, pb;
-    LstmFwdParams ea, eb;
-    int k1a = 0, k2a = 0, k1b = 0, k2b = 0;
-    bool has_a = s < T, has_b = s >= 1;
-    if (has_a) { step0(s, pa, ea, k1a, k2a); has_a = ea.M > 0; }
-    if (has_b) { step1(s - 1, pb, eb, k1b, k2b); has_b = eb.M > 0; }
-    if (!has_a && !has_b) continue;
-    const int pick = pick_fwd_tile_v3(has_b ? eb.M : ea.M, H);       // layer 1 runs the earlier step: at least as many rows as layer 0
-    if (pick == 0 || pick == 1 || pick == 4) {
-      if (!has_a) { pa = pb; ea = eb; }                              // (the absent role's arguments are never read: tiles_m = 0)
-      if (!has_b) { pb = pa; eb = ea; }
-#define EVC_WALK2_HIGH(CFG)                                                                                                   \
-      do {                                                                                                                    \
-        if (x_row_scale) launch_lstm_fwd_walk2<CFG, true, true, true, false>(pa, ea, k1a, k2a, has_a, pb, eb, k1b, k2b, has_b, st);   \
-        else launch_lstm_fwd_walk2<CFG, true, true, false, false>(pa, ea, k1a, k2a, has_a, pb, eb, k1b, k2b, has_b, st);              \
-      } while (0)
-      if (pick == 0) EVC_WALK2_HIGH(CfgLstmV3_256);
-      else if (pick == 4) EVC_WALK2_HIGH(CfgLstmV3_240);
-      else EVC_WALK2_HIGH(CfgLstmV3_224u);
-#undef EVC_WALK2_HIGH
-      continue;
-    }
-    if (has_a) {
-      if (x_row_scale) {
-        if (pick == 2) launch_lstm_fwd<CfgLstmV3_192, false, true, true, true>(pa, ea, k1a, k2a, st);
-        else launch_lstm_fwd<CfgLstmV3_160, false, true, true, true>(pa, ea, k1a, k2a, st);
-      } else {
-        if (pick == 2) launch_lstm_fwd<CfgLstmV3_192, false, true, true>(pa, ea, k1a, k2a, st);
-        else launch_lstm_fwd<CfgLstmV3_160, false, true, true>(pa, ea, k1a, k2a, st);
-      }
-    }
-    if (has_b) {
-      if (pick == 2) launch_lstm_fwd<CfgLstmV3_192, false, true>(pb, eb, k1b, k2b, st);
-      else launch_lstm_fwd<CfgLstmV3_160, false, true>(pb, eb, k1b, k2b, st);
-    }
-  }
+  EVC_TRY(fwd_clear_h(S, L0, st));                   // every image of both layers' rows
+  EVC_TRY(fwd_clear_copy(S, L0, st));
+  EVC_TRY(fwd_clear_h(S, L1, st));
+  EVC_TRY(fwd_clear_copy(S, L1, st));
+  const bool xint = x_row_scale != nullptr;
+  fwd_wavefront(S, L0, L1, [&](const FwdStep& a, bool has_a, const FwdStep& b, bool has_b) {
+    const int pick = pick_fwd_tile_v3(has_b ? b.e.M : a.e.M, H);
+    const bool walked = with_fwd_tile_v3<CfgLstmV3_224u>(pick, [&](auto tile) {
+      typedef typename decltype(tile)::type Cfg;
+      if constexpr (is_walk2_tile<Cfg>::value) {     // tile a: f16 + e4m3 stages, tile b: plain f16 stages
+        if (xint) launch_lstm_fwd_walk2<Cfg, true, true, true, false>(a, has_a, b, has_b, st);
+        else launch_lstm_fwd_walk2<Cfg, true, true, false, false>(a, has_a, b, has_b, st);
+        return true;
+      } else return false;
+    });
+    if (walked) return;
+    if (has_a) launch_fwd_step_e4m3(a, pick, xint, st);
+    if (has_b) with_fwd_tile_v3<CfgLstmV3_224u>(pick, [&](auto tile) { launch_lstm_fwd<typename decltype(tile)::type, false, true>(b, st); });
+  });
   EVC_LAUNCH_CHECK();
   return EVC_OK;
 }
@@ -897,152 +872,91 @@ extern "C" int evc_lstm_layer_fwd_hp(const evc_bf16* x_lohi, const evc_bf16* wx_
                                      const float* bias, const int32_t* len, int T, int M, int Kin, int H, float* zx_ws,
                                      evc_bf16* hbuf, evc_bf16* hbuf_lohi, float* c_state, float* h_state, int64_t ld_state,
                                      void* gates, evc_bf16* c_all, void* stream) {
-  EVC_REQUIRE(T > 0 && M > 0 && H > 0 && Kin > 0 && Kin % 64 == 0 && H % 64 == 0, EVC_ERR_BAD_SHAPE,
-              "evc_lstm_layer_fwd_hp: bad shape T=%d M=%d Kin=%d H=%d (Kin, H multiples of 64)", T, M, Kin, H);
+  const char* entry = "evc_lstm_layer_fwd_hp";
+  EVC_TRY(fwd_shape_ok(entry, T, M, Kin, H));
   EVC_REQUIRE(x_lohi && wx_hilo && wh_hilo && zx_ws && hbuf && hbuf_lohi, EVC_ERR_BAD_ARG, "evc_lstm_layer_fwd_hp: NULL operand");
-  EVC_REQUIRE(ldwx >= 2L * Kin && ldwh >= 2L * H && ldwx % 8 == 0 && ldwh % 8 == 0 && ((uintptr_t)wh_hilo % 16) == 0, EVC_ERR_BAD_ALIGN,
+  const FwdShared S{len, T, M, H, ld_state, nullptr, nullptr};
+  // the tail writes hbuf (plain) and hbuf_lohi (wide); no x rows (hoisted), and the h operands are patched in below
+  FwdLayer L;
+  L.zx = zx_ws;
+  L.h = hbuf; L.ldh = H; L.kh = H; L.h_copy = hbuf_lohi; L.ld_copy = 2L * H;
+  L.B = wh_hilo; L.ldb = ldwh;
+  L.bias = bias; L.c_state = c_state; L.h_state = h_state; L.gates = gates; L.c_all = c_all;
+  EVC_REQUIRE(ldwx >= 2L * Kin && ldwh >= 2L * H && ldwx % 8 == 0 && ldwh % 8 == 0 && aligned_to(wh_hilo, 16), EVC_ERR_BAD_ALIGN,
               "evc_lstm_layer_fwd_hp: weight images are [4H][2Kin] / [4H][2H] (ldwx=%ld ldwh=%ld)", (long)ldwx, (long)ldwh);
   EVC_REQUIRE(ring_operand_ok(M, 2L * H) && ring_operand_ok(4L * H, ldwh), EVC_ERR_BAD_SHAPE, "evc_lstm_layer_fwd_hp: operand spans 4 GiB or more");
-  EVC_REQUIRE(fwd_tail_ok(M, H, ld_state), EVC_ERR_BAD_SHAPE, "LSTM forward: a gate-record / state slab spans 4 GiB or more (M=%d H=%d ld_state=%ld)", M, H, (long)ld_state);
-  EVC_REQUIRE(ld_state % 4 == 0 && ((uintptr_t)c_state % 16) == 0 && ((uintptr_t)h_state % 16) == 0 && ((uintptr_t)bias % 16) == 0 &&
-              ((uintptr_t)hbuf % 8) == 0 && ((uintptr_t)hbuf_lohi % 16) == 0, EVC_ERR_BAD_ALIGN,
-              "evc_lstm_layer_fwd_hp: state/bias/hbuf must allow 16-byte vector access");
-  EVC_REQUIRE((gates == nullptr) == (c_all == nullptr), EVC_ERR_BAD_ARG, "evc_lstm_layer_fwd_hp: gates and c_all go together");
+  EVC_TRY(fwd_shared_ok(entry, S));
+  EVC_TRY(fwd_layer_ok(entry, L, 8, 16));
   hipStream_t st = (hipStream_t)stream;
-  EVC_CHECK_HIP(hipMemsetAsync(hbuf, 0, (size_t)M * H * sizeof(bf16_t), st));               // h_{-1} = 0
-  EVC_CHECK_HIP(hipMemsetAsync(hbuf_lohi, 0, (size_t)M * 2 * H * sizeof(bf16_t), st));
-  int rc = evc_gemm_nt_split(x_lohi, 2L * Kin, wx_hilo, ldwx, zx_ws, 4L * H, T * M, 4 * H, Kin, nullptr, stream);
-  if (rc) return rc;
-  for (int t = 0; t < T; ++t) {
-    GemmOperands p;
-    p.M = M; p.Nu = H; p.group_stride = H; p.ldb = ldwh; p.nk1 = p.nk2 = 0;
-    p.A1lo = p.A2lo = p.Blo = nullptr;
-    const bf16_t* hw = hbuf_lohi + (long)t * M * 2 * H;
-    p.A1 = hw; p.lda1 = 2L * H; p.A2 = hw + H; p.lda2 = 2L * H;
-    p.B = wh_hilo; p.B2 = wh_hilo;
-    const int k1 = (t == 0) ? 0 : 2 * H, k2 = (t == 0) ? 0 : H;
-    LstmFwdParams e;
-    e.zx = zx_ws + (long)t * M * 4 * H; e.ldzx = 4L * H;
-    e.bias = bias; e.len = len; e.t = t;
-    e.c_state = c_state; e.h_state = h_state; e.ld_state = ld_state;
-    e.hout = hbuf + (long)(t + 1) * M * H;
-    e.hout_lo = hbuf_lohi + (long)(t + 1) * M * 2 * H;
-    e.gates = gates ? (uint2*)gates + (long)t * M * H : nullptr;
-    e.c_hist = c_all ? c_all + (long)(t + 1) * M * H : nullptr;
-    e.row_map = nullptr;
-    e.M = M; e.H = H;
-    if (M >= 1024) launch_lstm_fwd<CfgLstmV3_256, true>(p, e, k1, k2, st);
-    else launch_lstm_fwd<CfgLstmV3Small, true>(p, e, k1, k2, st);
-  }
+  EVC_TRY(fwd_clear_h(S, L, st));
+  EVC_TRY(fwd_clear_copy(S, L, st));
+  EVC_TRY(evc_gemm_nt_split(x_lohi, 2L * Kin, wx_hilo, ldwx, zx_ws, 4L * H, T * M, 4 * H, Kin, nullptr, stream));
+  // The one entry whose operands fwd_step() does not build: the step's 16-bit segments both come from the SECOND ring - segment 1 = the wide
+  // rows [lo | hi] against [Wh_hi | Wh_lo], segment 2 = their hi halves against Wh_hi again (B2 = B) - while the h ring proper (hbuf) is only
+  // written.  The common part and the gate tail's arguments are fwd_step()'s.
+  fwd_layer_loop(S, L, [&](FwdStep s) {
+    const bf16_t* hw = hbuf_lohi + (long)s.e.t * M * 2 * H;
+    s.p.A1 = hw; s.p.lda1 = 2L * H; s.p.A2 = hw + H; s.p.lda2 = 2L * H;
+    s.p.B2 = wh_hilo;
+    s.k1 = s.e.t == 0 ? 0 : 2 * H; s.k2 = s.e.t == 0 ? 0 : H;
+    if (M >= 1024) launch_lstm_fwd<CfgLstmV3_256, true>(s, st);
+    else launch_lstm_fwd<CfgLstmV3Small, true>(s, st);
+  });
   EVC_LAUNCH_CHECK();
   return EVC_OK;
 }
 
-// One layer's view of a stack for evc_lstm_stack2_fwd
-struct FwdLayer {
-  const bf16_t* x; int Kin;            // [T][M][Kin] input (unused when the x-projection is hoisted)
-  const bf16_t* wT; const float* bias;
-  const float* zx;                     // hoisted x-projection [T][M][4H] or NULL
-  bf16_t* hbuf; float* c_state; float* h_state;
-  void* gates; bf16_t* c_all;
-};
-
-static inline void fwd_step_args(const FwdLayer& L, const int32_t* len, int t, int M, int H, int64_t ld_state,
-                                 GemmOperands& p, LstmFwdParams& e, int& k1, int& k2) {
-  p.M = M; p.Nu = H; p.group_stride = H; p.ldb = L.Kin + H; p.nk1 = p.nk2 = 0;
-  p.A1lo = p.A2lo = p.Blo = nullptr;
-  const bf16_t* hprev = L.hbuf + (long)t * M * H;
-  if (L.zx) {
-    p.A1 = hprev; p.lda1 = H; k1 = (t == 0) ? 0 : H; p.A2 = hprev; p.lda2 = H; k2 = 0;
-    p.B = L.wT + L.Kin;
-  } else {
-    p.A1 = L.x + (long)t * M * L.Kin; p.lda1 = L.Kin; k1 = L.Kin;
-    p.A2 = hprev; p.lda2 = H; k2 = (t == 0) ? 0 : H;
-    p.B = L.wT;
-  }
-  e.zx = L.zx ? L.zx + (long)t * M * 4 * H : nullptr; e.ldzx = 4L * H;
-  e.bias = L.bias; e.len = len; e.t = t;
-  e.c_state = L.c_state; e.h_state = L.h_state; e.ld_state = ld_state;
-  e.hout = L.hbuf + (long)(t + 1) * M * H;
-  e.hout_lo = nullptr;
-  e.gates = L.gates ? (uint2*)L.gates + (long)t * M * H : nullptr;
-  e.c_hist = L.c_all ? L.c_all + (long)(t + 1) * M * H : nullptr;
-  e.row_map = nullptr;
-  e.M = M; e.H = H;
-}
-
-template <class Cfg, bool F16 = false, bool FP8 = false>
-static inline void launch_lstm_fwd_pair(GemmOperands pa, const LstmFwdParams& ea, int k1a, int k2a,
-                                        GemmOperands pb, const LstmFwdParams& eb, int k1b, int k2b, hipStream_t st) {
-  pa.nk1 = k1a / kdiv<Cfg>(); pa.nk2 = k2a / kdiv<Cfg>();
-  pb.nk1 = k1b / kdiv<Cfg>(); pb.nk2 = k2b / kdiv<Cfg>();
-  const int tm = ceil_div(ea.M, Cfg::BM), tn = ceil_div(ea.H, Cfg::BU);
-  launch_cfg<Cfg>(lstm_fwd_pair_kernel<Cfg, F16, FP8>, 2 * tm * tn, st, pa, ea, pb, eb, tm, tn);
-}
-
+// ===========================================================================
+// Two-layer stacks with M ~ batch rows (the L2 level): wavefront pair launches
+// ===========================================================================
+// Layer 0's x-projection of all T steps is hoisted into one GEMM (M ~ batch: a per-step product would be a sliver); layer 1 reads layer 0's
+// output slab t+1 as its x_t in a fused [x_t | h_{t-1}] contraction (nothing to hoist: x_t exists only one launch earlier).  The steps are
+// latency-bound, so layer 0's step s and layer 1's step s-1 share a launch where the tile has a pair kernel (lstm_fwd_pair_kernel).
 extern "C" int evc_lstm_stack2_fwd(const evc_bf16* x, const evc_bf16* wT0, const float* bias0, const evc_bf16* wT1, const float* bias1,
                                    const int32_t* len, int T, int M, int Kin, int H, float* zx_ws,
                                    evc_bf16* hbuf0, evc_bf16* hbuf1, float* c_state0, float* h_state0, float* c_state1,
                                    float* h_state1, int64_t ld_state, void* gates0, evc_bf16* c_all0, void* gates1,
                                    evc_bf16* c_all1, void* stream) {
-  EVC_REQUIRE(T > 0 && M > 0 && H > 0 && Kin > 0 && H % 64 == 0 && Kin % 64 == 0, EVC_ERR_BAD_SHAPE,
-              "evc_lstm_stack2_fwd: bad shape T=%d M=%d Kin=%d H=%d (Kin, H multiples of 64)", T, M, Kin, H);
+  const char* entry = "evc_lstm_stack2_fwd";
+  EVC_TRY(fwd_shape_ok(entry, T, M, Kin, H));
   EVC_REQUIRE(ring_operand_ok(M, Kin > H ? Kin : H) && ring_operand_ok(4L * H, (long)Kin + H) && ring_operand_ok(4L * H, 2L * H), EVC_ERR_BAD_SHAPE,
               "evc_lstm_stack2_fwd: a time slab or a kernel spans 4 GiB or more (M=%d Kin=%d H=%d)", M, Kin, H);
-  EVC_REQUIRE(fwd_tail_ok(M, H, ld_state), EVC_ERR_BAD_SHAPE, "LSTM forward: a gate-record / state slab spans 4 GiB or more (M=%d H=%d ld_state=%ld)", M, H, (long)ld_state);
   EVC_REQUIRE(zx_ws && hbuf0 && hbuf1, EVC_ERR_BAD_ARG, "evc_lstm_stack2_fwd: zx_ws / hbuf0 / hbuf1 must not be NULL");
-  EVC_REQUIRE(ld_state % 4 == 0 && ((uintptr_t)c_state0 % 16) == 0 && ((uintptr_t)h_state0 % 16) == 0 && ((uintptr_t)c_state1 % 16) == 0 &&
-              ((uintptr_t)h_state1 % 16) == 0 && ((uintptr_t)bias0 % 16) == 0 && ((uintptr_t)bias1 % 16) == 0 &&
-              ((uintptr_t)hbuf0 % 8) == 0 && ((uintptr_t)hbuf1 % 8) == 0, EVC_ERR_BAD_ALIGN,
-              "evc_lstm_stack2_fwd: state/bias/hbuf must allow 16-byte vector access");
-  EVC_REQUIRE((gates0 == nullptr) == (c_all0 == nullptr) && (gates1 == nullptr) == (c_all1 == nullptr) &&
-              (gates0 == nullptr) == (gates1 == nullptr), EVC_ERR_BAD_ARG, "evc_lstm_stack2_fwd: gates and c_all go together, for both layers");
-  EVC_REQUIRE(!gates0 || (((uintptr_t)gates0 % 16) == 0 && ((uintptr_t)gates1 % 16) == 0 && ((uintptr_t)c_all0 % 8) == 0 &&
-                          ((uintptr_t)c_all1 % 8) == 0), EVC_ERR_BAD_ALIGN, "evc_lstm_stack2_fwd: gates must be 16-byte, c_all 8-byte aligned");
+  const FwdShared S{len, T, M, H, ld_state, nullptr, nullptr};
+  FwdLayer L0;
+  L0.x = x; L0.ldx = Kin; L0.kx = Kin;
+  L0.h = hbuf0; L0.ldh = H; L0.kh = H;
+  L0.B = wT0 + Kin; L0.ldb = (long)Kin + H;
+  L0.bias = bias0; L0.c_state = c_state0; L0.h_state = h_state0; L0.gates = gates0; L0.c_all = c_all0;
+  L0.zx = zx_ws;
+  FwdLayer L1;
+  L1.x = hbuf0 + (long)M * H; L1.ldx = H; L1.kx = H;
+  L1.h = hbuf1; L1.ldh = H; L1.kh = H;
+  L1.B = wT1; L1.ldb = 2L * H;
+  L1.bias = bias1; L1.c_state = c_state1; L1.h_state = h_state1; L1.gates = gates1; L1.c_all = c_all1;
+  EVC_TRY(fwd_shared_ok(entry, S));
+  EVC_TRY(fwd_layers2_ok(entry, L0, L1, 8));
   hipStream_t st = (hipStream_t)stream;
-  EVC_CHECK_HIP(hipMemsetAsync(hbuf0, 0, (size_t)M * H * sizeof(bf16_t), st));       // h_{-1} = 0, both layers
-  EVC_CHECK_HIP(hipMemsetAsync(hbuf1, 0, (size_t)M * H * sizeof(bf16_t), st));
-  // layer 0: x-projection of all T steps as one GEMM (M ~ batch: a per-step product would be a sliver)
-  int rc = evc_gemm_nt(x, Kin, wT0, (int64_t)Kin + H, zx_ws, 4L * H, T * M, 4 * H, Kin, nullptr, 0, 0, stream);
-  if (rc) return rc;
-  const FwdLayer L0{x, Kin, wT0, bias0, zx_ws, hbuf0, c_state0, h_state0, gates0, c_all0};
-  // layer 1 reads layer 0's output slab t+1 as its x_t; fused [x_t | h_{t-1}] contraction (nothing to hoist: x_t
-  // exists only one launch earlier)
-  const FwdLayer L1{hbuf0 + (long)M * H, H, wT1, bias1, nullptr, hbuf1, c_state1, h_state1, gates1, c_all1};
-  const int tile = pick_fwd_tile(M, H);     // 6: v1 128 rows x 32 units, 7 (M ~ 256): v1 64 x 16; others: one step per launch
-  for (int s = 0; s <= T; ++s) {            // launch s: layer 0 step s next to layer 1 step s-1
-    GemmOperands pa, pb;
-    LstmFwdParams ea, eb;
-    int k1a = 0, k2a = 0, k1b = 0, k2b = 0;
-    const bool has_a = s < T, has_b = s >= 1;
-    if (has_a) fwd_step_args(L0, len, s, M, H, ld_state, pa, ea, k1a, k2a);
-    if (has_b) fwd_step_args(L1, len, s - 1, M, H, ld_state, pb, eb, k1b, k2b);
-    if (has_a && has_b && (tile == 6 || tile == 7)) {
-      if (tile == 6) launch_lstm_fwd_pair<CfgLstmBig>(pa, ea, k1a, k2a, pb, eb, k1b, k2b, st);
-      else launch_lstm_fwd_pair<CfgLstmV3Small>(pa, ea, k1a, k2a, pb, eb, k1b, k2b, st);
-      continue;
-    }
-    for (int r = 0; r < 2; ++r) {
-      if (!(r == 0 ? has_a : has_b)) continue;
-      const GemmOperands& p = r == 0 ? pa : pb;
-      const LstmFwdParams& e = r == 0 ? ea : eb;
-      const int k1 = r == 0 ? k1a : k1b, k2 = r == 0 ? k2a : k2b;
-      switch (tile) {
-        case 0: launch_lstm_fwd<CfgLstmV2a>(p, e, k1, k2, st); break;
-        case 1: launch_lstm_fwd<CfgLstmV2_288>(p, e, k1, k2, st); break;
-        case 2: launch_lstm_fwd<CfgLstmV2b>(p, e, k1, k2, st); break;
-        case 3: launch_lstm_fwd<CfgLstmV2_224>(p, e, k1, k2, st); break;
-        case 4: launch_lstm_fwd<CfgLstmV2_192>(p, e, k1, k2, st); break;
-        case 5: launch_lstm_fwd<CfgLstmV2_160>(p, e, k1, k2, st); break;
-        case 6: launch_lstm_fwd<CfgLstmBig>(p, e, k1, k2, st); break;
-        case 8: launch_lstm_fwd<CfgLstmV2_128>(p, e, k1, k2, st); break;
-        case 9: launch_lstm_fwd<CfgLstmV2_64>(p, e, k1, k2, st); break;
-        default: launch_lstm_fwd<CfgLstmSmall>(p, e, k1, k2, st); break;
-      }
-    }
-  }
+  EVC_TRY(fwd_clear_h(S, L0, st));
+  EVC_TRY(fwd_clear_h(S, L1, st));
+  EVC_TRY(evc_gemm_nt(x, Kin, wT0, (int64_t)Kin + H, zx_ws, 4L * H, T * M, 4 * H, Kin, nullptr, 0, 0, stream));
+  const int tile = pick_fwd_tile(M, H);     // 6: v1 128 rows x 32 units, 7 (M ~ 256): 64 x 16 - the tiles with a pair kernel; others: one step per launch
+  fwd_wavefront(S, L0, L1, [&](const FwdStep& a, bool has_a, const FwdStep& b, bool has_b) {
+    if (has_a && has_b && tile == 6) return launch_lstm_fwd_pair<CfgLstmBig>(a, b, st);
+    if (has_a && has_b && tile == 7) return launch_lstm_fwd_pair<CfgLstmV3Small>(a, b, st);
+    const auto one = [&](const FwdStep& s) { with_fwd_tile<true>(tile, [&](auto t) { launch_lstm_fwd<typename decltype(t)::type>(s, st); }); };
+    if (has_a) one(a);
+    if (has_b) one(b);
+  });
   EVC_LAUNCH_CHECK();
   return EVC_OK;
+}
+
+// the launcher of the two f16 stacks: one 64 x 16 tile for every launch
+template <bool FP8>
+static inline void launch_stack2_f16(const FwdStep& a, bool has_a, const FwdStep& b, bool has_b, hipStream_t st) {
+  if (has_a && has_b) launch_lstm_fwd_pair<CfgLstmV3Small, true, FP8>(a, b, st);
+  else launch_lstm_fwd<CfgLstmV3Small, false, true, FP8>(has_a ? a : b, st);
 }
 
 // evc_lstm_stack2_fwd on IEEE f16 operands, with the UPPER layer's weights K-extended by their low-order halves - the "high"
@@ -1050,7 +964,8 @@ extern "C" int evc_lstm_stack2_fwd(const evc_bf16* x, const evc_bf16* wT0, const
 // (2^-12) is enough for every activation and for layer 0's weights; the one term it does not cover is the ROUNDING OF THE UPPER
 // LAYER'S WEIGHTS, the same error at every one of the 20 steps into a cell state that integrates it (6e-4 on the states).  So
 // layer 1 contracts [h0_t | h0_t/64 | h1_{t-1} | h1_{t-1}/64] . [Wx | (Wx - f16(Wx))*64 | Wh | (Wh - f16(Wh))*64]^T (K = 4H instead
-// of 2H; split-bf16 would be 6H in three passes), layer 0 runs plain f16 with its x-projection hoisted into one f16 product.
+// of 2H; split-bf16 would be 6H in three passes), layer 0 runs plain f16 with its x-projection hoisted into one f16 product (its step:
+// zx + h0_{s-1} . Wh0^T over K = H of the wide rows; h0_ext: all 2H against [Wh | Wh_lo*64]).
 // h rows are WIDE, [f16(h) | f16(h)/64] (2H), written by the step epilogue together with the bf16 copy the backward pass reads.
 // Same wavefront as evc_lstm_stack2_fwd: launch s = layer 0 step s next to layer 1 step s-1.
 extern "C" int evc_lstm_stack2_fwd_f16(const evc_f16* x, int x_segments, const evc_f16* wT0, int h0_ext, const float* bias0,
@@ -1059,70 +974,37 @@ extern "C" int evc_lstm_stack2_fwd_f16(const evc_f16* x, int x_segments, const e
                                        evc_f16* h0_wide, evc_f16* h1_wide, evc_bf16* hbuf0, evc_bf16* hbuf1,
                                        float* c_state0, float* h_state0, float* c_state1, float* h_state1, int64_t ld_state,
                                        void* gates0, evc_bf16* c_all0, void* gates1, evc_bf16* c_all1, void* stream) {
-  EVC_REQUIRE(T > 0 && M > 0 && H > 0 && Kin > 0 && H % 64 == 0 && Kin % 64 == 0, EVC_ERR_BAD_SHAPE,
-              "evc_lstm_stack2_fwd_f16: bad shape T=%d M=%d Kin=%d H=%d (Kin, H multiples of 64)", T, M, Kin, H);
+  const char* entry = "evc_lstm_stack2_fwd_f16";
+  EVC_TRY(fwd_shape_ok(entry, T, M, Kin, H));
   EVC_REQUIRE(x && wT0 && wT1_wlo && zx_ws && h0_wide && h1_wide && hbuf0 && hbuf1, EVC_ERR_BAD_ARG, "evc_lstm_stack2_fwd_f16: NULL operand");
   EVC_REQUIRE(x_segments >= 1 && x_segments <= 3 && (h0_ext == 0 || h0_ext == 1), EVC_ERR_BAD_ARG, "evc_lstm_stack2_fwd_f16: x_segments=%d h0_ext=%d",
               x_segments, h0_ext);
   const long Kx = (long)x_segments * Kin;              // K of the hoisted x-projection (K-extended input: evc_cast_f32_to_f16_segs)
   const long ldw0 = Kx + (h0_ext ? 2L : 1L) * H;       // row of layer 0's kernel image (evc_cast_f32_to_f16_wide)
+  const FwdShared S{len, T, M, H, ld_state, nullptr, nullptr};
+  FwdLayer L0;
+  L0.x = x; L0.ldx = Kx; L0.kx = (int)Kx;
+  L0.h = h0_wide; L0.ldh = 2L * H; L0.kh = h0_ext ? 2 * H : H;
+  L0.B = wT0 + Kx; L0.ldb = ldw0;
+  L0.bias = bias0; L0.c_state = c_state0; L0.h_state = h_state0; L0.gates = gates0; L0.c_all = c_all0;
+  L0.zx = zx_ws; L0.h_wide = 1; L0.h_copy = hbuf0; L0.ld_copy = H;
+  FwdLayer L1;
+  L1.x = h0_wide + (long)M * 2 * H; L1.ldx = 2L * H; L1.kx = 2 * H;
+  L1.h = h1_wide; L1.ldh = 2L * H; L1.kh = 2 * H;
+  L1.B = wT1_wlo; L1.ldb = 4L * H;
+  L1.bias = bias1; L1.c_state = c_state1; L1.h_state = h_state1; L1.gates = gates1; L1.c_all = c_all1;
+  L1.h_wide = 1; L1.h_copy = hbuf1; L1.ld_copy = H;
   EVC_REQUIRE(ring_operand_ok(M, 2L * H) && ring_operand_ok(4L * H, 4L * H) && ring_operand_ok(4L * H, 3L * Kin + 2L * H), EVC_ERR_BAD_SHAPE,
               "evc_lstm_stack2_fwd_f16: an operand spans 4 GiB or more");
-  EVC_REQUIRE(fwd_tail_ok(M, H, ld_state), EVC_ERR_BAD_SHAPE, "LSTM forward: a gate-record / state slab spans 4 GiB or more (M=%d H=%d ld_state=%ld)", M, H, (long)ld_state);
-  EVC_REQUIRE(ld_state % 4 == 0 && ((uintptr_t)c_state0 % 16) == 0 && ((uintptr_t)h_state0 % 16) == 0 && ((uintptr_t)c_state1 % 16) == 0 &&
-              ((uintptr_t)h_state1 % 16) == 0 && ((uintptr_t)bias0 % 16) == 0 && ((uintptr_t)bias1 % 16) == 0 && ((uintptr_t)h0_wide % 16) == 0 &&
-              ((uintptr_t)h1_wide % 16) == 0 && ((uintptr_t)hbuf0 % 8) == 0 && ((uintptr_t)hbuf1 % 8) == 0, EVC_ERR_BAD_ALIGN,
-              "evc_lstm_stack2_fwd_f16: state/bias/h buffers must allow 16-byte vector access");
-  EVC_REQUIRE((gates0 == nullptr) == (c_all0 == nullptr) && (gates1 == nullptr) == (c_all1 == nullptr) && (gates0 == nullptr) == (gates1 == nullptr),
-              EVC_ERR_BAD_ARG, "evc_lstm_stack2_fwd_f16: gates and c_all go together, for both layers");
+  EVC_TRY(fwd_shared_ok(entry, S));
+  EVC_TRY(fwd_layers2_ok(entry, L0, L1, 16));
   hipStream_t st = (hipStream_t)stream;
-  EVC_CHECK_HIP(hipMemsetAsync(h0_wide, 0, (size_t)M * 2 * H * sizeof(f16_t), st));        // h_{-1} = 0, both layers, both images
-  EVC_CHECK_HIP(hipMemsetAsync(h1_wide, 0, (size_t)M * 2 * H * sizeof(f16_t), st));
-  EVC_CHECK_HIP(hipMemsetAsync(hbuf0, 0, (size_t)M * H * sizeof(bf16_t), st));
-  EVC_CHECK_HIP(hipMemsetAsync(hbuf1, 0, (size_t)M * H * sizeof(bf16_t), st));
-  int rc = gemm_nt_f16(x, Kx, wT0, ldw0, zx_ws, 4L * H, T * M, 4 * H, (int)Kx, stream);
-  if (rc) return rc;
-  for (int s = 0; s <= T; ++s) {            // launch s: layer 0 step s next to layer 1 step s-1
-    GemmOperands pa, pb;
-    LstmFwdParams ea, eb;
-    int k1a = 0, k2a = 0, k1b = 0, k2b = 0;
-    const bool has_a = s < T, has_b = s >= 1;
-    if (has_a) {                             // layer 0, step s: zx + h0_{s-1} . Wh0^T (K = H of the wide rows; h0_ext: all 2H against [Wh | Wh_lo*64])
-      const int t = s;
-      pa.M = M; pa.Nu = H; pa.group_stride = H; pa.ldb = ldw0; pa.nk1 = pa.nk2 = 0;
-      pa.A1lo = pa.A2lo = pa.Blo = nullptr;
-      const bf16_t* hprev = (const bf16_t*)h0_wide + (long)t * M * 2 * H;
-      pa.A1 = hprev; pa.lda1 = 2L * H; k1a = (t == 0) ? 0 : (h0_ext ? 2 * H : H); pa.A2 = hprev; pa.lda2 = 2L * H; k2a = 0;
-      pa.B = (const bf16_t*)wT0 + Kx;
-      ea.zx = zx_ws + (long)t * M * 4 * H; ea.ldzx = 4L * H;
-      ea.bias = bias0; ea.len = len; ea.t = t;
-      ea.c_state = c_state0; ea.h_state = h_state0; ea.ld_state = ld_state;
-      ea.hout = (bf16_t*)h0_wide + (long)(t + 1) * M * 2 * H; ea.h_wide = 1;
-      ea.hout_lo = hbuf0 + (long)(t + 1) * M * H;
-      ea.gates = gates0 ? (uint2*)gates0 + (long)t * M * H : nullptr;
-      ea.c_hist = c_all0 ? c_all0 + (long)(t + 1) * M * H : nullptr;
-      ea.row_map = nullptr; ea.M = M; ea.H = H;
-    }
-    if (has_b) {                             // layer 1, step s-1: [h0_t | h0_t/64 | h1_{t-1} | h1_{t-1}/64] . [Wx | Wx_lo*64 | Wh | Wh_lo*64]^T
-      const int t = s - 1;
-      pb.M = M; pb.Nu = H; pb.group_stride = H; pb.ldb = 4L * H; pb.nk1 = pb.nk2 = 0;
-      pb.A1lo = pb.A2lo = pb.Blo = nullptr;
-      pb.A1 = (const bf16_t*)h0_wide + (long)(t + 1) * M * 2 * H; pb.lda1 = 2L * H; k1b = 2 * H;
-      pb.A2 = (const bf16_t*)h1_wide + (long)t * M * 2 * H; pb.lda2 = 2L * H; k2b = (t == 0) ? 0 : 2 * H;
-      pb.B = (const bf16_t*)wT1_wlo;
-      eb.zx = nullptr; eb.ldzx = 0;
-      eb.bias = bias1; eb.len = len; eb.t = t;
-      eb.c_state = c_state1; eb.h_state = h_state1; eb.ld_state = ld_state;
-      eb.hout = (bf16_t*)h1_wide + (long)(t + 1) * M * 2 * H; eb.h_wide = 1;
-      eb.hout_lo = hbuf1 + (long)(t + 1) * M * H;
-      eb.gates = gates1 ? (uint2*)gates1 + (long)t * M * H : nullptr;
-      eb.c_hist = c_all1 ? c_all1 + (long)(t + 1) * M * H : nullptr;
-      eb.row_map = nullptr; eb.M = M; eb.H = H;
-    }
-    if (has_a && has_b) launch_lstm_fwd_pair<CfgLstmV3Small, true>(pa, ea, k1a, k2a, pb, eb, k1b, k2b, st);
-    else if (has_a) launch_lstm_fwd<CfgLstmV3Small, false, true>(pa, ea, k1a, k2a, st);
-    else launch_lstm_fwd<CfgLstmV3Small, false, true>(pb, eb, k1b, k2b, st);
-  }
+  EVC_TRY(fwd_clear_h(S, L0, st));                     // both layers, both images
+  EVC_TRY(fwd_clear_h(S, L1, st));
+  EVC_TRY(fwd_clear_copy(S, L0, st));
+  EVC_TRY(fwd_clear_copy(S, L1, st));
+  EVC_TRY(gemm_nt_f16(x, Kx, wT0, ldw0, zx_ws, 4L * H, T * M, 4 * H, (int)Kx, stream));
+  fwd_wavefront(S, L0, L1, [&](const FwdStep& a, bool has_a, const FwdStep& b, bool has_b) { launch_stack2_f16<false>(a, has_a, b, has_b, st); });
   EVC_LAUNCH_CHECK();
   return EVC_OK;
 }
@@ -1132,7 +1014,8 @@ extern "C" int evc_lstm_stack2_fwd_f16(const evc_f16* x, int x_segments, const e
 // stages instead of 64 f16 ones (H = 1024) - these steps are bound by their chain of dependent stages.  x [T][M][x_segments Kin] f16
 // (K-extended input of the hoisted product, as before); wT0 [4H][x_segments Kin + H] f16 = [Wx segments | f16(Wh)], wT0_8 [4H][H] bytes =
 // e4m3((Wh - f16(Wh)) 2^w8_scale_exp); wT1 [4H][2H] f16, wT1_8 [4H][2H] bytes; h0_rows / h1_rows [(T+1)][M] rows of 3H bytes = [f16(h) |
-// e4m3(h 2^7)].  H % 128 == 0, H >= 512.
+// e4m3(h 2^7)].  H % 128 == 0, H >= 512.  Layer 0's step: zx + h0_{s-1} . Wh0^T (f16) + 2^-(7+e) e4m3(h0_{s-1}) . e4m3(lo(Wh0))^T; layer 1's:
+// [h0_t | h1_{t-1}] . [Wx | Wh]^T (f16) + the same rows' e4m3 parts against e4m3(lo([Wx | Wh])).
 // h_lo = 1 (round 6): the activations' low-order halves are corrected as well - h rows of 4H bytes [f16(h) | e4m3(h 2^7) | e4m3((h - f16(h)) 2^18)],
 // wT0_8 [4H][2H] = [lo(Wh0) | hi(Wh0)], wT1_8 [4H][4H] = [lo(Wx1) | hi(Wx1) | lo(Wh1) | hi(Wh1)] (evc_cast_f32_to_fp8_lo with hi_tail): layer 1
 // walks 32 f16 + 32 e4m3 stages.
@@ -1142,8 +1025,8 @@ extern "C" int evc_lstm_stack2_fwd_f16_fp8lo(const evc_f16* x, int x_segments, c
                                              evc_f16* h0_rows, evc_f16* h1_rows, evc_bf16* hbuf0, evc_bf16* hbuf1,
                                              float* c_state0, float* h_state0, float* c_state1, float* h_state1, int64_t ld_state,
                                              void* gates0, evc_bf16* c_all0, void* gates1, evc_bf16* c_all1, void* stream) {
-  EVC_REQUIRE(T > 0 && M > 0 && H >= 512 && Kin > 0 && H % 128 == 0 && Kin % 64 == 0, EVC_ERR_BAD_SHAPE,
-              "evc_lstm_stack2_fwd_f16_fp8lo: bad shape T=%d M=%d Kin=%d (%%64) H=%d (%%128, >= 512)", T, M, Kin, H);
+  const char* entry = "evc_lstm_stack2_fwd_f16_fp8lo";
+  EVC_TRY(fwd_shape_ok(entry, T, M, Kin, H, 128, 512));
   EVC_REQUIRE(x && wT0 && wT0_8 && wT1 && wT1_8 && zx_ws && h0_rows && h1_rows && hbuf0 && hbuf1, EVC_ERR_BAD_ARG, "evc_lstm_stack2_fwd_f16_fp8lo: NULL operand");
   EVC_REQUIRE(x_segments >= 1 && x_segments <= 3 && w8_scale_exp >= 0 && w8_scale_exp <= 60, EVC_ERR_BAD_ARG,
               "evc_lstm_stack2_fwd_f16_fp8lo: x_segments=%d w8_scale_exp=%d", x_segments, w8_scale_exp);
@@ -1151,75 +1034,35 @@ extern "C" int evc_lstm_stack2_fwd_f16_fp8lo(const evc_f16* x, int x_segments, c
   const long Kx = (long)x_segments * Kin;
   const long ldw0 = Kx + H, ldh = h_lo ? 2L * H : 3L * H / 2;
   const int kh8 = h_lo ? 2 * H : H;                 // e4m3 bytes per h row: [h8] or [h8 | h_lo8]
+  const FwdShared S{len, T, M, H, ld_state, nullptr, nullptr};
+  FwdLayer L0;
+  L0.x = x; L0.ldx = Kx; L0.kx = (int)Kx;
+  L0.h = h0_rows; L0.ldh = ldh; L0.kh = H;
+  L0.B = wT0 + Kx; L0.ldb = ldw0;
+  L0.bias = bias0; L0.c_state = c_state0; L0.h_state = h_state0; L0.gates = gates0; L0.c_all = c_all0;
+  L0.zx = zx_ws; L0.h_copy = hbuf0;
+  L0.kh8 = kh8; L0.B8 = wT0_8; L0.ldb8 = kh8;
+  FwdLayer L1;
+  L1.x = h0_rows + (long)M * ldh; L1.ldx = ldh; L1.kx = H;
+  L1.h = h1_rows; L1.ldh = ldh; L1.kh = H;
+  L1.B = wT1; L1.ldb = 2L * H;
+  L1.bias = bias1; L1.c_state = c_state1; L1.h_state = h_state1; L1.gates = gates1; L1.c_all = c_all1;
+  L1.h_copy = hbuf1;
+  L1.x8_off = 2L * H; L1.kx8 = kh8; L1.kh8 = kh8; L1.B8 = wT1_8; L1.ldb8 = 2L * kh8;
+  L0.h_wide = L1.h_wide = h_lo ? 3 : 2; L0.ld_copy = L1.ld_copy = H; L0.scale8_exp = L1.scale8_exp = -(7 + w8_scale_exp);
   EVC_REQUIRE(ring_operand_ok(M, ldh) && ring_operand_ok(4L * H, ldw0) && ring_operand_ok(4L * H, 2L * H), EVC_ERR_BAD_SHAPE,
               "evc_lstm_stack2_fwd_f16_fp8lo: an operand spans 4 GiB or more");
-  EVC_REQUIRE(fwd_tail_ok(M, H, ld_state), EVC_ERR_BAD_SHAPE, "LSTM forward: a gate-record / state slab spans 4 GiB or more (M=%d H=%d ld_state=%ld)", M, H, (long)ld_state);
-  EVC_REQUIRE(ld_state % 4 == 0 && ((uintptr_t)c_state0 % 16) == 0 && ((uintptr_t)h_state0 % 16) == 0 && ((uintptr_t)c_state1 % 16) == 0 &&
-              ((uintptr_t)h_state1 % 16) == 0 && ((uintptr_t)bias0 % 16) == 0 && ((uintptr_t)bias1 % 16) == 0 && ((uintptr_t)h0_rows % 16) == 0 &&
-              ((uintptr_t)h1_rows % 16) == 0 && ((uintptr_t)hbuf0 % 8) == 0 && ((uintptr_t)hbuf1 % 8) == 0 && ((uintptr_t)wT0_8 % 16) == 0 &&
-              ((uintptr_t)wT1_8 % 16) == 0 && ((uintptr_t)wT0 % 16) == 0 && ((uintptr_t)wT1 % 16) == 0, EVC_ERR_BAD_ALIGN,
-              "evc_lstm_stack2_fwd_f16_fp8lo: state/bias/h buffers and weight images must allow 16-byte vector access");
-  EVC_REQUIRE((gates0 == nullptr) == (c_all0 == nullptr) && (gates1 == nullptr) == (c_all1 == nullptr) && (gates0 == nullptr) == (gates1 == nullptr),
-              EVC_ERR_BAD_ARG, "evc_lstm_stack2_fwd_f16_fp8lo: gates and c_all go together, for both layers");
+  EVC_REQUIRE(aligned_to(wT0_8, 16) && aligned_to(wT1_8, 16) && aligned_to(wT0, 16) && aligned_to(wT1, 16), EVC_ERR_BAD_ALIGN,
+              "evc_lstm_stack2_fwd_f16_fp8lo: 16-byte aligned weight images");
+  EVC_TRY(fwd_shared_ok(entry, S));
+  EVC_TRY(fwd_layers2_ok(entry, L0, L1, 16));
   hipStream_t st = (hipStream_t)stream;
-  bf16_t* h0r = (bf16_t*)h0_rows;
-  bf16_t* h1r = (bf16_t*)h1_rows;
-  EVC_CHECK_HIP(hipMemsetAsync(h0r, 0, (size_t)M * ldh * sizeof(bf16_t), st));        // h_{-1} = 0, both layers, every image
-  EVC_CHECK_HIP(hipMemsetAsync(h1r, 0, (size_t)M * ldh * sizeof(bf16_t), st));
-  EVC_CHECK_HIP(hipMemsetAsync(hbuf0, 0, (size_t)M * H * sizeof(bf16_t), st));
-  EVC_CHECK_HIP(hipMemsetAsync(hbuf1, 0, (size_t)M * H * sizeof(bf16_t), st));
-  int rc = gemm_nt_f16(x, Kx, wT0, ldw0, zx_ws, 4L * H, T * M, 4 * H, (int)Kx, stream);
-  if (rc) return rc;
-  for (int s = 0; s <= T; ++s) {            // launch s: layer 0 step s next to layer 1 step s-1
-    GemmOperands pa, pb;
-    LstmFwdParams ea, eb;
-    int k1a = 0, k1b = 0, k2b = 0;
-    const bool has_a = s < T, has_b = s >= 1;
-    if (has_a) {                             // layer 0, step s: zx + h0_{s-1} . Wh0^T (f16) + 2^-(7+e) e4m3(h0_{s-1}) . e4m3(lo(Wh0))^T
-      const int t = s;
-      pa.M = M; pa.Nu = H; pa.group_stride = H; pa.ldb = ldw0; pa.nk1 = pa.nk2 = 0;
-      pa.A1lo = pa.A2lo = pa.Blo = nullptr;
-      const bf16_t* hprev = h0r + (long)t * M * ldh;
-      pa.A1 = hprev; pa.lda1 = ldh; k1a = (t == 0) ? 0 : H; pa.A2 = hprev; pa.lda2 = ldh;
-      pa.B = (const bf16_t*)wT0 + Kx;
-      pa.A3 = (const uint8_t*)(hprev + H); pa.lda3 = ldh * 2; pa.nk3 = (t == 0) ? 0 : kh8 / 128;
-      pa.A4 = pa.A3; pa.lda4 = pa.lda3; pa.nk4 = 0;
-      pa.B8 = wT0_8; pa.ldb8 = kh8; pa.scale8_exp = -(7 + w8_scale_exp);
-      ea.zx = zx_ws + (long)t * M * 4 * H; ea.ldzx = 4L * H;
-      ea.bias = bias0; ea.len = len; ea.t = t;
-      ea.c_state = c_state0; ea.h_state = h_state0; ea.ld_state = ld_state;
-      ea.hout = h0r + (long)(t + 1) * M * ldh; ea.h_wide = h_lo ? 3 : 2;
-      ea.hout_lo = hbuf0 + (long)(t + 1) * M * H;
-      ea.gates = gates0 ? (uint2*)gates0 + (long)t * M * H : nullptr;
-      ea.c_hist = c_all0 ? c_all0 + (long)(t + 1) * M * H : nullptr;
-      ea.row_map = nullptr; ea.M = M; ea.H = H;
-    }
-    if (has_b) {                             // layer 1, step s-1: [h0_t | h1_{t-1}] . [Wx | Wh]^T (f16) + the same rows' e4m3 parts against e4m3(lo([Wx | Wh]))
-      const int t = s - 1;
-      pb.M = M; pb.Nu = H; pb.group_stride = H; pb.ldb = 2L * H; pb.nk1 = pb.nk2 = 0;
-      pb.A1lo = pb.A2lo = pb.Blo = nullptr;
-      const bf16_t* xin = h0r + (long)(t + 1) * M * ldh;
-      const bf16_t* hprev = h1r + (long)t * M * ldh;
-      pb.A1 = xin; pb.lda1 = ldh; k1b = H;
-      pb.A2 = hprev; pb.lda2 = ldh; k2b = (t == 0) ? 0 : H;
-      pb.B = (const bf16_t*)wT1;
-      pb.A3 = (const uint8_t*)(xin + H); pb.lda3 = ldh * 2; pb.nk3 = kh8 / 128;
-      pb.A4 = (const uint8_t*)(hprev + H); pb.lda4 = ldh * 2; pb.nk4 = (t == 0) ? 0 : kh8 / 128;
-      pb.B8 = wT1_8; pb.ldb8 = 2L * kh8; pb.scale8_exp = -(7 + w8_scale_exp);
-      eb.zx = nullptr; eb.ldzx = 0;
-      eb.bias = bias1; eb.len = len; eb.t = t;
-      eb.c_state = c_state1; eb.h_state = h_state1; eb.ld_state = ld_state;
-      eb.hout = h1r + (long)(t + 1) * M * ldh; eb.h_wide = h_lo ? 3 : 2;
-      eb.hout_lo = hbuf1 + (long)(t + 1) * M * H;
-      eb.gates = gates1 ? (uint2*)gates1 + (long)t * M * H : nullptr;
-      eb.c_hist = c_all1 ? c_all1 + (long)(t + 1) * M * H : nullptr;
-      eb.row_map = nullptr; eb.M = M; eb.H = H;
-    }
-    if (has_a && has_b) launch_lstm_fwd_pair<CfgLstmV3Small, true, true>(pa, ea, k1a, 0, pb, eb, k1b, k2b, st);
-    else if (has_a) launch_lstm_fwd<CfgLstmV3Small, false, true, true>(pa, ea, k1a, 0, st);
-    else launch_lstm_fwd<CfgLstmV3Small, false, true, true>(pb, eb, k1b, k2b, st);
-  }
+  EVC_TRY(fwd_clear_h(S, L0, st));                     // both layers, every image
+  EVC_TRY(fwd_clear_h(S, L1, st));
+  EVC_TRY(fwd_clear_copy(S, L0, st));
+  EVC_TRY(fwd_clear_copy(S, L1, st));
+  EVC_TRY(gemm_nt_f16(x, Kx, wT0, ldw0, zx_ws, 4L * H, T * M, 4 * H, (int)Kx, stream));
+  fwd_wavefront(S, L0, L1, [&](const FwdStep& a, bool has_a, const FwdStep& b, bool has_b) { launch_stack2_f16<true>(a, has_a, b, has_b, st); });
   EVC_LAUNCH_CHECK();
   return EVC_OK;
 }
-

@@ -1,10 +1,11 @@
-// Launch helpers shared by the GEMM-shaped translation units (evc_gemm.hip, evc_dbof.hip).
+// Launch helpers shared by the GEMM-shaped translation units (evc_gemm.hip, evc_dbof.hip, evc_lstm_fwd.hip, evc_lstm_bwd.hip).
 #pragma once
 #include "gemm_core_tn.h"
 #include "gemm_core_v3.h"
 #include <mutex>
 #include <vector>
 #include <stdlib.h>
+#include <type_traits>
 
 // A kernel is instantiated either on a v1 tile (TileCfg: static 2-stage LDS, K steps of 64)
 // or a v2 tile (TileCfg2: dynamic 4-stage LDS ring, K steps of 32).
@@ -26,6 +27,22 @@ static inline bool fwd_tail_ok(long rows, long H, long ld_state) {
 }
 static inline bool ring_operand_ok(long rows, long ld) {
   return rows < (1L << 24) && ld * 2 < (1L << 24) && rows * ld * 2 < (1L << 32);
+}
+
+// a refusal helper's error code, passed on
+#define EVC_TRY(expr)             \
+  do {                            \
+    const int _rc = (expr);       \
+    if (_rc) return _rc;          \
+  } while (0)
+
+// row plans (evc_sort_rows_by_len): the active rows of step t are the prefix [0, rows_per_step[t]) of M slots sorted by length
+static inline int rows_per_step_ok(const char* entry, const int32_t* rows_per_step, int T, int M) {
+  if (rows_per_step)
+    for (int t = 0; t < T; ++t)
+      EVC_REQUIRE(rows_per_step[t] >= 0 && rows_per_step[t] <= M && (t == 0 || rows_per_step[t] <= rows_per_step[t - 1]), EVC_ERR_BAD_ARG,
+                  "%s: rows_per_step[%d]=%d must be non-increasing and within [0, M=%d]", entry, t, rows_per_step[t], M);
+  return EVC_OK;
 }
 
 // v2 tiles use more dynamic LDS than the 64 KiB default: raise the limit once per kernel (keyed by the
