@@ -76,6 +76,7 @@ SIGNATURES = {
     "evc_distill_losses": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, vp, vp, vp, vp, vp],
     "evc_distill_losses_multi": [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp],
     "evc_distill_losses_ensemble": [i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp],
+    "evc_distill_losses_sparse": [i32, vp, vp, i32, vp, i32, vp, vp, i32, i32, f32, f32, vp, vp, vp, vp, vp],
     "evc_label_loss": [i32, vp, vp, i32, i32, f32, vp, vp, vp, i32, vp, vp],
     "evc_grad_sqnorm": [vp, vp, f32, i64, vp, vp],
     "evc_clip_adam_step": [vp, vp, vp, vp, i64, f32, vp, f32, f32, f32, f32, f32, vp, vp],

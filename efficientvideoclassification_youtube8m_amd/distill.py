@@ -735,6 +735,11 @@ class DistillGraph(_TrainGraph):
         body = self._step_frozen_teacher if self.mode == "serial" else self._step
         return self._on_main((x_raw, labels_u8, num_frames), num_frames_host, lambda nh: body(x_raw, labels_u8, num_frames, apply, nh))
 
+    def _student_label_loss(self, s_pred, labels_u8, B, sc):
+        """The student's loss section where no teacher tower has a say in dL/dpred yet: L_CE and its gradient (OfflineDistillGraph puts
+        ops.distill_losses_sparse here when the step was handed the batch's teacher lists)."""
+        self.label_loss.fused(s_pred, labels_u8, self.losses[3:4], self._dp_s, grad_scale=sc["ce"] / B)
+
     def _step(self, x_raw, labels_u8, num_frames, apply=True, nh=None):
         """x_raw [B,300,F] f32 (or uint8), labels_u8 [B,V] uint8, num_frames [B] int32.
         Returns a dict mirroring the graph collections the reference's loop
@@ -786,7 +791,7 @@ class DistillGraph(_TrainGraph):
             nonlocal s_state, s_pred
             mark("student_start", side)
             s_state, s_pred = self.student.forward(xs, l1s, l2s, plan_s)
-            self.label_loss.fused(s_pred, labels_u8, self.losses[3:4], self._dp_s, grad_scale=sc["ce"] / B)
+            self._student_label_loss(s_pred, labels_u8, B, sc)
             mark("student_fwd_done", side)
 
         def student_forward_from_inputs():
@@ -949,6 +954,70 @@ class DistillGraph(_TrainGraph):
             rep = {"label_loss": v[0] / self.world, "student_loss_state": v[1] / self.world, "pred_loss": v[2],
                    "student_label_loss": v[3] / self.world}
         return rep
+
+
+class OfflineDistillGraph(DistillGraph):
+    """Offline distillation: the student alone against the sparse lists of 1 .. 8 teacher prediction files (train
+    --teacher_preds_pattern).  It IS DistillGraph(mode="student") - the finetune step: the same input pass, row plans, backward, update
+    and streams, no teacher tower in memory - whose L_CE launch gives way to ops.distill_losses_sparse when step() is handed the
+    batch's lists (teacher_lists = (idx [F, B, kp] int32, val [F, B, kp] f32) device tensors, inference.PriorTables.gather_device);
+    without lists the step takes exactly the launches of mode "student".  teacher_mode "max" | "mean" and teacher_weights [F] (mean only)
+    combine the files as ensemble_topk_rows combines prior files; distill_losses: a subset of ("pred", "ce") - a prediction file holds no
+    state, so there is no L_REP.  global_step += 1 per iteration; "random" student frames are drawn anew per step."""
+
+    OFFLINE_LOSSES = ("pred", "ce")
+    MAX_FILES = ops.DISTILL_MAX_FILES
+
+    def __init__(self, batch_size, every_n=10, teacher_mode="mean", teacher_weights=None, distill_losses=OFFLINE_LOSSES, **kw):
+        if kw.pop("mode", "student") != "student":
+            raise ValueError("OfflineDistillGraph is the mode 'student' graph: it has no teacher tower")
+        on = check_distill_losses(distill_losses)
+        if "rep" in on:
+            raise ValueError("distill_losses %s: a prediction file carries no state, so offline distillation has no L_REP (pred, ce)"
+                             % ",".join(on))
+        if teacher_mode not in ops.ENSEMBLE_MODES:
+            raise ValueError("teacher_mode %r (max | mean)" % (teacher_mode,))
+        if teacher_weights is not None and teacher_mode != "mean":
+            raise ValueError("teacher_weights are read in teacher_mode 'mean' only")
+        super().__init__(batch_size, every_n=every_n, mode="student", **kw)
+        if not losses_mod.is_default(self.label_loss):
+            raise ValueError("OfflineDistillGraph has CrossEntropyLoss built into its loss section (evc_distill_losses_sparse), not %s"
+                             % type(self.label_loss).__name__)
+        if self.world > 1 or self.dp:
+            raise ValueError("OfflineDistillGraph is not data parallel yet (process group of %d ranks): train the student on one device"
+                             % self.world)
+        self.offline_losses = on
+        self.teacher_mode = teacher_mode
+        self.teacher_weights = None if teacher_weights is None else np.asarray(teacher_weights, np.float32).reshape(-1)
+        self._teacher_lists = None
+
+    def step(self, x_raw, labels_u8, num_frames, apply=True, num_frames_host=None, teacher_lists=None):
+        """DistillGraph.step; teacher_lists: None (the student-only step), or the (idx, val) lists of exactly these videos."""
+        if teacher_lists is None:
+            return super().step(x_raw, labels_u8, num_frames, apply, num_frames_host)
+        idx, val = teacher_lists
+        if self.teacher_weights is not None and self.teacher_weights.size != idx.shape[0]:
+            raise ValueError("%d teacher_weights for the lists of %d files" % (self.teacher_weights.size, idx.shape[0]))
+        self._teacher_lists = (idx, val)
+        try:
+            return self._on_main((x_raw, labels_u8, num_frames, idx, val), num_frames_host,
+                                 lambda nh: self._step(x_raw, labels_u8, num_frames, apply, nh))
+        finally:
+            self._teacher_lists = None
+
+    def _student_label_loss(self, s_pred, labels_u8, B, sc):
+        if self._teacher_lists is None:
+            return super()._student_label_loss(s_pred, labels_u8, B, sc)
+        idx, val = self._teacher_lists
+        on = self.offline_losses
+        # losses[0] = CE of the combined teacher row, [2] = L_PRED, [3] = the student's L_CE; the scales of the serial step
+        ops.distill_losses_sparse(idx, val, labels_u8, s_pred, self.losses, self._dp_s, mode=self.teacher_mode, weights=self.teacher_weights,
+                                  g_ce=(sc["ce"] / B) if "ce" in on else 0.0, g_kl=sc["kl"] if "pred" in on else 0.0)
+
+    def state_dict(self):
+        """The variables a checkpoint of this graph holds: the student tower alone."""
+        self.flush()
+        return self.student.state_dict()
 
 
 class SerialStudentView:

@@ -190,6 +190,15 @@ _define("teacher_weights", "", str, "comma separated prediction weights, one per
 _define("teacher_rep_weights", "", str, "comma separated weights of the teachers' states in L_REP's target; '' = 1,0,...,0: the state of "
         "entry 0 alone (a mean over independently trained teachers has no common basis; over a teacher and the students distilled from it, "
         "it has)")
+# ---- offline distillation (train): the student against teacher PREDICTION FILES, no teacher tower in memory ----------------------------
+_define("teacher_preds_pattern", "", str, "glob of 1 .. 8 VideoId,LabelConfidencePairs files (what inference --output_file writes for one "
+        "tower or a whole ensemble, or any program writing that format), sorted by name.  Set: the student alone is trained against the "
+        "lists of every batch's videos (distill.OfflineDistillGraph: the train_finetune step with the loss section "
+        "evc_distill_losses_sparse), no teacher runs and none is loaded; the files are combined as --teacher_mode / --teacher_weights say "
+        "(one weight per file), --distill_losses defaults to pred,ce and refuses rep (a prediction file carries no state); the checkpoint "
+        "is train_finetune's, the student tower alone.  Every training video must be in every file.  HierarchicalLstmModel, --label_loss "
+        "CrossEntropyLoss, one rank, real records (synthetic data has no video ids); not with --teacher_dir, --teacher_dirs, "
+        "--serial_student_dirs, --teacher_only or train_finetune")
 # ---- ensembles (inference / validate; cs/inference_ensemble.py:28-61 has preds_pattern, the others are additions) -----------------------
 _define("ensemble_dirs", "", str, "comma separated checkpoint directories of the ensemble's members (1 .. 8); '' = the single model of "
         "--train_dir, which is not consulted otherwise.  Every member runs its forward on the same batch and ops.ensemble_topk_rows "

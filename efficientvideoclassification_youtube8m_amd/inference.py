@@ -225,6 +225,68 @@ def gather_priors(tables, files, video_ids, kp, out=None):
     return idx, val
 
 
+class PriorTables:
+    """Prediction files as arrays, for a loop that gathers the lists of every training batch (train --teacher_preds_pattern): each file is
+    parsed once by read_prediction_file (same format, same errors) and kept as contiguous idx int32 [N, kp] / val float32 [N, kp] (shorter
+    lists padded with idx = -1, val 0: the padding of gather_priors) plus a {video id: row} dictionary; kp is the longest list of all the
+    files (prior_list_length).  gather() then costs one dictionary lookup per id and one np.take per file."""
+
+    def __init__(self, files, num_classes=NUM_CLASSES, tables=None):
+        self.files = list(files)
+        tables = [read_prediction_file(path, num_classes) for path in self.files] if tables is None else list(tables)
+        self.kp = prior_list_length(tables)
+        self.rows, self.idx, self.val = [], [], []
+        for table in tables:
+            n = len(table)
+            idx, val = np.full((n, self.kp), -1, np.int32), np.zeros((n, self.kp), np.float32)
+            rows = {}
+            for r, (vid, (cls, conf)) in enumerate(table.items()):
+                rows[vid] = r
+                idx[r, :cls.size] = cls
+                val[r, :cls.size] = conf
+            self.rows.append(rows)
+            self.idx.append(idx)
+            self.val.append(val)
+        self._pinned, self._turn = {}, 0
+
+    def __len__(self):
+        return len(self.files)
+
+    def gather(self, video_ids, out=None):
+        """gather_priors(tables, files, video_ids, kp, out): exactly its arrays (idx int32, val float32) [P, B, kp], and its KeyError naming
+        the id and the file for an id a file does not hold."""
+        P, B = len(self.files), len(video_ids)
+        idx, val = out if out is not None else (np.empty((P, B, self.kp), np.int32), np.empty((P, B, self.kp), np.float32))
+        ids = [v.decode("utf-8") if isinstance(v, bytes) else v for v in video_ids]
+        for p, (rows, path) in enumerate(zip(self.rows, self.files)):
+            try:
+                sel = np.fromiter((rows[v] for v in ids), np.intp, B)
+            except KeyError:
+                vid = next(v for v in ids if v not in rows)
+                raise KeyError("video id %r is not in the prediction file %s" % (vid, path)) from None
+            np.take(self.idx[p], sel, axis=0, out=idx[p])
+            np.take(self.val[p], sel, axis=0, out=val[p])
+        return idx, val
+
+    def gather_device(self, video_ids, device):
+        """gather() into pinned buffers - two sets used alternately, so that the set of the step in flight is not overwritten - and their
+        non_blocking copies to `device` on the current stream.  Returns (idx [P, B, kp] int32, val [P, B, kp] f32) device tensors."""
+        P, B = len(self.files), len(video_ids)
+        key = (self._turn, B)
+        self._turn ^= 1
+        if key not in self._pinned:          # (a smaller final batch gets sets of its own)
+            self._pinned[key] = (torch.empty((P, B, self.kp), dtype=torch.int32, pin_memory=True),
+                                 torch.empty((P, B, self.kp), dtype=torch.float32, pin_memory=True), [None])
+        idx_h, val_h, ev = self._pinned[key]
+        if ev[0] is not None:
+            ev[0].synchronize()              # the copies of two steps ago have left these buffers
+        self.gather(video_ids, out=(idx_h.numpy(), val_h.numpy()))
+        idx_d, val_d = idx_h.to(device, non_blocking=True), val_h.to(device, non_blocking=True)
+        ev[0] = torch.cuda.Event()
+        ev[0].record(torch.cuda.current_stream(device))
+        return idx_d, val_d
+
+
 def check_flags():
     """Everything that is refused before a record is read or the device is touched.  Returns ensemble_spec() (cascade_spec() is checked
     here too; main() asks for it again)."""

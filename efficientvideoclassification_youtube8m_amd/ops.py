@@ -1068,6 +1068,56 @@ def distill_losses_ensemble(preds_t, states_t, labels_u8, pred_s, state_s, losse
               _stream())
 
 
+DISTILL_MAX_FILES = 8      # evc_distill_losses_sparse: one student against 1 <= F <= 8 sparse lists of 1 <= kp <= 256 entries, V <= 32768
+DISTILL_SPARSE_MAX_V = 32768
+
+
+def distill_losses_sparse(prior_idx, prior_val, labels_u8, pred_s, losses, dpred_s=None, mode="mean", weights=None, g_ce=1.0, g_kl=1.0,
+                          pred_comb=None):
+    """The loss section of the offline distillation step in one launch + its finish (evc_distill_losses_sparse): one student against
+    the sparse (class, confidence) lists of F prediction files.  prior_idx [F, B, kp] int32 / prior_val [F, B, kp] f32 on the device, as
+    ensemble_topk_rows takes its priors (idx = -1 pads, classes distinct within a list); they are scattered into one combined row per
+    video exactly as ensemble_topk_rows(dense=True) scatters them over one all-zero member (mode "max" | "mean"; weights [F], mean only,
+    default np.float32(1) / np.float32(F) each).  losses[0] += CE of the combined row, losses[2] += L_PRED, losses[3] += student CE
+    (DistillGraph.LOSS_SLOTS; slot 1, L_REP, is left alone: a prediction file holds no state); dpred_s [B, V] (optional) = g_ce dCE_s +
+    g_kl dL_PRED, written once; pred_comb [B, V] (optional) receives the combined row."""
+    import ctypes as C
+    import numpy as np
+    if mode not in ENSEMBLE_MODES:
+        raise ValueError("distill_losses_sparse: mode %r (max | mean)" % (mode,))
+    for t in (prior_idx, prior_val, labels_u8, pred_s, losses):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise _lib.EvcError("distill_losses_sparse: evc ops need device tensors (got a CPU tensor); there is no CPU path")
+    if (prior_idx.dtype != torch.int32 or prior_val.dtype != F32 or prior_idx.dim() != 3 or tuple(prior_idx.shape) != tuple(prior_val.shape)
+            or not prior_idx.is_contiguous() or not prior_val.is_contiguous()):
+        raise ValueError("distill_losses_sparse: the lists are a contiguous (idx [F, B, kp] int32, val [F, B, kp] float32) pair")
+    F, B, kp = (int(x) for x in prior_idx.shape)
+    if not 1 <= F <= DISTILL_MAX_FILES or not 1 <= kp <= ENSEMBLE_MAX_KP:
+        raise ValueError("distill_losses_sparse: %d lists of %d entries (1 .. %d of 1 .. %d)" % (F, kp, DISTILL_MAX_FILES, ENSEMBLE_MAX_KP))
+    if pred_s.dim() != 2 or pred_s.shape[0] != B:
+        raise ValueError("distill_losses_sparse: pred_s %s for lists of %d rows" % (tuple(pred_s.shape), B))
+    V = int(pred_s.shape[1])
+    if not 1 <= V <= DISTILL_SPARSE_MAX_V:
+        raise ValueError("distill_losses_sparse: %d classes (1 .. %d: the combined row is built in LDS)" % (V, DISTILL_SPARSE_MAX_V))
+    if weights is None:
+        w = np.full(F, np.float32(1) / np.float32(F), np.float32)
+    else:
+        if mode != "mean":
+            raise ValueError("distill_losses_sparse: weights are read in mode 'mean' only")
+        w = np.asarray(weights, np.float32).reshape(-1)
+        if w.size != F:
+            raise ValueError("distill_losses_sparse: %d weights for %d lists" % (w.size, F))
+    assert labels_u8.shape == (B, V) and losses.numel() >= 4
+    assert pred_s.dtype == F32 and labels_u8.dtype == torch.uint8 and losses.dtype == F32
+    for t in (pred_s, labels_u8, losses):
+        assert t.is_contiguous()
+    for t in (dpred_s, pred_comb):
+        assert t is None or (t.is_cuda and t.dtype == F32 and t.shape == (B, V) and t.is_contiguous())
+    ws = torch.empty(3 * max(B, 1), dtype=F32, device=pred_s.device)
+    _lib.call("evc_distill_losses_sparse", F, _p(prior_idx), _p(prior_val), kp, (C.c_float * F)(*w.tolist()), ENSEMBLE_MODES[mode],
+              _p(labels_u8), _p(pred_s), B, V, float(g_ce), float(g_kl), _p(losses), _p(pred_comb), _p(dpred_s), _p(ws), _stream())
+
+
 def clip_adam_small(ps, gs, ms, vs, sums, clip_norm, lr_t, beta1=0.9, beta2=0.999, eps=1e-8):
     """Per-tensor clip + TF-Adam of up to 16 small tensors (no l2 term) in one launch (evc_clip_adam_small): sums[i] receives {|g_i|^2, 0}."""
     import ctypes as C

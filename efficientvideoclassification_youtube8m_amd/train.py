@@ -21,6 +21,9 @@ student against the frozen teacher of DIR's latest checkpoint (distill.DistillGr
 (distill.SerialStudentsGraph): one checkpoint directory per student, each what a run of its own would have written.
 ``--teacher_dirs A/,B/,...`` trains ONE student against the combination of up to 8 frozen teachers - an ensemble folded back into one
 small model, or a teacher next to the teaching assistants distilled from it (distill.EnsembleDistillGraph).
+``--teacher_preds_pattern GLOB`` trains the student ALONE against 1 .. 8 teacher prediction files (what inference --output_file writes):
+the train_finetune step with the loss section evc_distill_losses_sparse, no teacher tower in memory (distill.OfflineDistillGraph,
+DESIGN.md 7.11).
 Multi-GPU: launch with ``python -m torch.distributed.run --nproc-per-node N``;
 ``--gpu`` is then ignored in favour of LOCAL_RANK.
 """
@@ -36,7 +39,7 @@ import numpy as np
 import torch
 
 from . import eval_util, frame_level_models, losses, ops, readers, video_level_models
-from .distill import DistillGraph, EnsembleDistillGraph, SerialStudentsGraph, SingleTowerGraph
+from .distill import DistillGraph, EnsembleDistillGraph, OfflineDistillGraph, SerialStudentsGraph, SingleTowerGraph
 from .flags import FLAGS, GetListOfFeatureNamesAndSizes
 from .towers import DbofTower, LogisticTower, NetVladTower
 
@@ -71,7 +74,7 @@ def check_serial_flags(finetune=False, world=1, students=_UNSET):
     if students is _UNSET:
         serial_students(finetune, world)    # --serial_student_dirs and its lists: every refusal of theirs, before the rest
     if not serial:
-        if FLAGS.distill_losses != DEFAULT_DISTILL_LOSSES and not FLAGS.teacher_dirs.strip():
+        if FLAGS.distill_losses != DEFAULT_DISTILL_LOSSES and not FLAGS.teacher_dirs.strip() and not FLAGS.teacher_preds_pattern:
             raise ValueError("--distill_losses %s needs --teacher_dir: it selects the student's losses of serial distillation "
                              "(the teacher+student graph trains on all of them)" % FLAGS.distill_losses)
         return False
@@ -145,7 +148,8 @@ def ensemble_teachers(finetune=False, world=1):
     dirs = words(FLAGS.teacher_dirs)
     lists = {k: words(getattr(FLAGS, k)) for k in TEACHER_LIST_FLAGS}
     if not dirs:
-        stray = [k for k, v in lists.items() if v]
+        # (--teacher_weights - like --teacher_mode - also combines the files of --teacher_preds_pattern: offline_teachers)
+        stray = [k for k, v in lists.items() if v and not (k == "teacher_weights" and FLAGS.teacher_preds_pattern)]
         if stray:
             raise ValueError("--%s needs --teacher_dirs (the frozen teachers the student is trained against)" % stray[0])
         return None
@@ -203,6 +207,95 @@ def ensemble_teachers(finetune=False, world=1):
     if not rep.any():
         raise ValueError("--teacher_rep_weights %s: every weight is 0 (leave L_REP out with --distill_losses instead)" % FLAGS.teacher_rep_weights)
     return dict(dirs=dirs, towers=towers, every_n=every_n, sampling=sampling, mode=FLAGS.teacher_mode, weights=weights, rep_weights=rep)
+
+
+OFFLINE_DISTILL_LOSSES = "pred,ce"
+
+
+def offline_teachers(finetune=False, world=1, argv=None):
+    """--teacher_preds_pattern: None when it is not set, else {"files" (sorted paths), "names" (their base names), "mode", "weights"
+    (float32 [F], None in mode max), "losses" (the --distill_losses tuple; its default under this flag is pred,ce)}.  argv: the command
+    line, to tell a --distill_losses that was given from the flag's default.  Every refused combination is a ValueError that names both
+    flags, here, before a file is parsed or the device is touched."""
+    from .distill import check_distill_losses, validate_every_n
+    pattern = FLAGS.teacher_preds_pattern
+    if not pattern:
+        return None
+    what = "--teacher_preds_pattern %s" % pattern
+    if FLAGS.teacher_dir:
+        raise ValueError("%s with --teacher_dir %s: the teacher is a set of prediction files or a frozen tower, not both (mixing them in "
+                         "one step is not built)" % (what, FLAGS.teacher_dir))
+    if FLAGS.teacher_dirs.strip():
+        raise ValueError("%s with --teacher_dirs %s: the teachers are prediction files or frozen towers, not both (mixing them in one "
+                         "step is not built)" % (what, FLAGS.teacher_dirs))
+    if FLAGS.serial_student_dirs.strip():
+        raise ValueError("%s with --serial_student_dirs: several students against prediction files in one run is not built" % what)
+    if getattr(FLAGS, "teacher_only", False):
+        raise ValueError("%s with --teacher_only: offline distillation trains the student alone, there is no teacher tower" % what)
+    if FLAGS.label_loss != "CrossEntropyLoss":
+        raise ValueError("%s with --label_loss %s: offline distillation has CrossEntropyLoss built into its loss kernel "
+                         "(evc_distill_losses_sparse)" % (what, FLAGS.label_loss))
+    if finetune:
+        raise ValueError("%s with train_finetune (--finetune): train_finetune trains the student on L_CE alone, without a teacher "
+                         "(offline distillation is train --teacher_preds_pattern)" % what)
+    if FLAGS.train_data_pattern in ("", "synthetic"):
+        raise ValueError("%s with --train_data_pattern %r: synthetic training data has no video ids to look up in the files" %
+                         (what, FLAGS.train_data_pattern))
+    if world > 1:
+        raise ValueError("%s on %d ranks: offline distillation is not data parallel yet, run it on one device" % (what, world))
+    if FLAGS.model != "HierarchicalLstmModel":
+        raise ValueError("%s: offline distillation is built for HierarchicalLstmModel, not --model %s" % (what, FLAGS.model))
+    if FLAGS.teacher_mode not in ops.ENSEMBLE_MODES:
+        raise ValueError("--teacher_mode %r (max | mean)" % FLAGS.teacher_mode)
+    given = argv is not None and any(a == "--distill_losses" or a.startswith("--distill_losses=") for a in argv)
+    words = FLAGS.distill_losses if (given or FLAGS.distill_losses != DEFAULT_DISTILL_LOSSES) else OFFLINE_DISTILL_LOSSES
+    on = check_distill_losses(words)
+    if "rep" in on:
+        raise ValueError("%s with --distill_losses %s: a prediction file carries no state, so there is no L_REP to train on (pred, ce)"
+                         % (what, ",".join(on)))
+    validate_every_n(FLAGS.every_n, 5, FLAGS.max_num_frames)
+    files = sorted(glob.glob(pattern))
+    if not files:
+        raise ValueError("%s matches no file" % what)
+    if len(files) > OfflineDistillGraph.MAX_FILES:
+        raise ValueError("%s: %d files (1 .. %d)" % (what, len(files), OfflineDistillGraph.MAX_FILES))
+    given_w = [w.strip() for w in FLAGS.teacher_weights.split(",")] if FLAGS.teacher_weights.strip() else []
+    if given_w and FLAGS.teacher_mode != "mean":
+        raise ValueError("--teacher_weights needs --teacher_mode mean (max has no weights)")
+    if given_w and len(given_w) != len(files):
+        raise ValueError("--teacher_weights %s: %d entries for the %d files of %s" % (FLAGS.teacher_weights, len(given_w), len(files), what))
+    weights = None
+    if FLAGS.teacher_mode == "mean":
+        try:
+            weights = (np.asarray([float(x) for x in given_w], np.float32) if given_w
+                       else np.full(len(files), np.float32(1) / np.float32(len(files)), np.float32))
+        except ValueError:
+            raise ValueError("--teacher_weights %r: a comma list of numbers" % FLAGS.teacher_weights)
+    return dict(files=files, names=[os.path.basename(f) for f in files], mode=FLAGS.teacher_mode, weights=weights, losses=on)
+
+
+def offline_record(spec):
+    """What a --teacher_preds_pattern checkpoint records of its teachers (metadata key "distill_teacher_files"): plain lists, strings and
+    floats.  The loss list is recorded next to it, under "distill_losses"."""
+    return {"files": list(spec["names"]), "mode": spec["mode"], "weights": None if spec["weights"] is None else [float(x) for x in spec["weights"]]}
+
+
+def check_recorded_files(sd, spec, ck=""):
+    """Resume of a --teacher_preds_pattern run from the checkpoint dict ``sd``: the number of files, the mode, the weights and the loss
+    list must be the recorded ones (ValueError showing both); other file names are only logged.  A checkpoint that records no files
+    (train_convert_model's, train_finetune's, a plain student) is a start from its weights."""
+    recorded = sd.get("distill_teacher_files")
+    if recorded is None:
+        return
+    current = offline_record(spec)
+    was = (len(recorded["files"]), recorded["mode"], recorded["weights"], sd.get("distill_losses"))
+    now = (len(current["files"]), current["mode"], current["weights"], ",".join(spec["losses"]))
+    if was != now:
+        raise ValueError("--teacher_preds_pattern: the checkpoint %s was trained against other teacher files than the flags name.\n"
+                         "  recorded (files, --teacher_mode, --teacher_weights, --distill_losses): %s\n  flags: %s\n"
+                         "(resume with the recorded settings, or start a new model)" % (ck, was, now))
+    if recorded["files"] != current["files"]:
+        logging.info("--teacher_preds_pattern: the checkpoint %s records the files %s, the flags name %s", ck, recorded["files"], current["files"])
 
 
 def load_teachers(spec):
@@ -304,7 +397,7 @@ def check_label_loss(label_loss_fn, finetune=False):
 
 
 def build_graph(model, label_loss_fn, feature_size, batch_size, every_n, device, finetune=False, process_group=None, students=_UNSET,
-                teachers=None):
+                teachers=None, offline=None):
     """Equivalent of cs/train.py:185-427 (and cs/train_finetune.py:185-331 when
     finetune): returns the graph object whose ``step`` runs one iteration."""
     check_label_loss(label_loss_fn, finetune)
@@ -328,6 +421,15 @@ def build_graph(model, label_loss_fn, feature_size, batch_size, every_n, device,
                                         max_frames=FLAGS.max_num_frames, num_inputs_to_lstm=FLAGS.num_inputs_to_lstm,
                                         lstm_cells=FLAGS.lstm_cells, lstm_layers=FLAGS.lstm_layers, num_mixtures=FLAGS.moe_num_mixtures,
                                         device=device, precision=FLAGS.precision, sampling_seed=FLAGS.student_sampling_seed, **common)
+        if offline is not None:
+            # the student alone against prediction files (--teacher_preds_pattern): offline = an offline_teachers() spec
+            common.pop("label_loss", None)        # (refused for anything but CrossEntropyLoss, which the loss kernel has built in)
+            return OfflineDistillGraph(batch_size, every_n=every_n, teacher_mode=offline["mode"], teacher_weights=offline["weights"],
+                                       distill_losses=offline["losses"], feature_size=feature_size, vocab_size=NUM_CLASSES,
+                                       max_frames=FLAGS.max_num_frames, num_inputs_to_lstm=FLAGS.num_inputs_to_lstm,
+                                       lstm_cells=FLAGS.lstm_cells, lstm_layers=FLAGS.lstm_layers, num_mixtures=FLAGS.moe_num_mixtures,
+                                       device=device, precision=FLAGS.precision, student_sampling=FLAGS.student_sampling,
+                                       sampling_seed=FLAGS.student_sampling_seed, **common)
         spec = serial_students(finetune) if students is _UNSET else students
         if spec is not None:
             # K students against one forward of the frozen teacher (--serial_student_dirs): hyper-parameters as below, one of each list per student
@@ -446,6 +548,9 @@ def save_checkpoint(graph, train_dir, rank):
     if getattr(graph, "mode", None) == "ensemble":               # metadata: trained against several frozen teachers, model/* being entry 0
         sd["distill_mode"], sd["distill_losses"] = "ensemble", ",".join(graph.distill_losses)
         sd["distill_teachers"] = getattr(graph, "teacher_record", None) or graph.teacher_meta()
+    if isinstance(graph, OfflineDistillGraph) and getattr(graph, "teacher_record", None):    # metadata: trained against these prediction files
+        sd["distill_mode"], sd["distill_losses"] = "offline", ",".join(graph.offline_losses)
+        sd["distill_teacher_files"] = graph.teacher_record
     fn = getattr(graph, "label_loss", None)
     if fn is not None and not losses.is_default(fn):             # metadata: the --label_loss these weights were trained on (the default: no key)
         sd["label_loss"] = type(fn).__name__
@@ -511,6 +616,7 @@ def main(argv=None):
     logging.basicConfig(level=logging.INFO, format="INFO:evc:%(message)s")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
+    offline = offline_teachers(finetune, world, argv)
     ens = ensemble_teachers(finetune, world)
     multi = serial_students(finetune, world)
     serial = check_serial_flags(finetune, world, students=multi)
@@ -525,6 +631,16 @@ def main(argv=None):
         if ens_resume is not None:
             check_recorded_teachers(torch.load(ens_resume, map_location="cpu").get("distill_teachers"), ens_record, ens_resume)
     multi_cks = serial_students_checkpoints(multi["dirs"], FLAGS.start_new_model) if multi else None
+    tables = None
+    if offline:
+        # the files parsed on the host, and - on resume - the recorded settings against the flags: all before the device is touched
+        from .inference import PriorTables
+        off_resume = None if FLAGS.start_new_model else latest_checkpoint(FLAGS.train_dir)
+        if off_resume is not None:
+            check_recorded_files(torch.load(off_resume, map_location="cpu"), offline, off_resume)
+        tables = PriorTables(offline["files"], NUM_CLASSES)
+        logging.info("offline distillation against %d prediction files (%s), lists of up to %d classes, --teacher_mode %s, losses %s",
+                     len(tables), ", ".join(offline["names"]), tables.kp, offline["mode"], ",".join(offline["losses"]))
     local = int(os.environ.get("LOCAL_RANK", str(FLAGS.gpu)))
     # test hook (tests/test_gpu_dp.py): several ranks on ONE GPU over gloo, to run this file's multi-rank path on a
     # single-GPU box (RCCL refuses two ranks per device).  Never set in a real run.
@@ -548,7 +664,10 @@ def main(argv=None):
     label_loss_fn = find_class_by_name(FLAGS.label_loss, [losses])()
     if FLAGS.optimizer != "AdamOptimizer":
         raise NotImplementedError("only AdamOptimizer (the reference default, cs/train.py:91) is built")
-    graph = build_graph(model, label_loss_fn, feature_size, FLAGS.batch_size, FLAGS.every_n, device, finetune, students=multi, teachers=ens)
+    graph = build_graph(model, label_loss_fn, feature_size, FLAGS.batch_size, FLAGS.every_n, device, finetune, students=multi, teachers=ens,
+                        offline=offline)
+    if offline:
+        graph.teacher_record = offline_record(offline)
     logging.info("%s: Built graph.", task)
     ck = None if (FLAGS.start_new_model or multi) else latest_checkpoint(FLAGS.train_dir)
     if multi and multi_cks:
@@ -667,7 +786,10 @@ def main(argv=None):
     history = []                         # (global_step, loss dict) of every logged step, returned to the caller
     pending = None
     for q, labels, n, n_host in (data if step_limit != 0 else ()):
-        out = graph.step(q, labels, n, num_frames_host=n_host) if is_distill else graph.step(q, labels, n)    # uint8 features: Dequantize is fused into every input kernel
+        if tables is not None:      # the teacher files' lists of exactly these videos: pinned staging, non_blocking copies on this stream
+            out = graph.step(q, labels, n, num_frames_host=n_host, teacher_lists=tables.gather_device(LAST_BATCH["ids"], device))
+        else:
+            out = graph.step(q, labels, n, num_frames_host=n_host) if is_distill else graph.step(q, labels, n)    # uint8 features: Dequantize is fused into every input kernel
         it += 1
         graph.last_batch_ids = LAST_BATCH["ids"]
         logging_step = it % max(1, FLAGS.log_every) == 0

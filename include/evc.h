@@ -562,6 +562,32 @@ int evc_distill_losses_ensemble(int J, const float* const* pred_t, const float* 
                                 const uint8_t* labels, const float* pred_s, const float* state_s, int B, int V, int D, float g_ce, float g_kl,
                                 float g_rep, float* losses /* [4] */, float* teacher_ce /* [J] */, float* pred_comb, float* dpred_s,
                                 float* dstate_s, float* workspace, void* stream);
+/* The loss section for ONE student against F sparse teacher lists (1 <= F <= 8), in one launch + one finish launch (offline distillation:
+ * the teachers are the (class, confidence) lists of F earlier prediction files, no teacher tower runs and there is no state, so no L_REP).
+ *   prior_idx / prior_val [F][B][kp] DEVICE arrays, exactly as evc_ensemble_topk_rows takes them: an entry with an index outside [0, V) (the
+ *     host pads with -1) is skipped; the indices of one list are distinct (the caller guarantees it); 1 <= kp <= 256.
+ *   w [F] HOST array, read in mode 1 only and then required (read before the call returns; it travels by value in the launch's arguments).
+ *   The combined row P starts at +0.0 for every class.  mode 1 (weighted mean): P[c] = P[c] + w[f] val for f ascending over the files that
+ *     list c, product and sum each rounded to f32 on its own (no fused multiply-add); mode 0 (max): P[c] = val if key(val) > key(P[c]) in the
+ *     total order of evc_topk_rows (NaN above +inf, -0 ties +0), the files in order.  P holds exactly the bits evc_ensemble_topk_rows' dense
+ *     exit writes for ONE all-zero member plus these F files with the same mode and, in mode 1, the weights {0, w[0], ..., w[F - 1]};
+ *     pred_comb [B][V] (may be NULL) receives it.
+ *   losses[0] += CE(P, labels) (value only), losses[1] is left alone, losses[2] += L_PRED(P || pred_s), losses[3] += CE(pred_s, labels);
+ *   dpred_s [B][V] (may be NULL) = g_ce dCE_s + g_kl dL_PRED / dpred_s, written once, every element of it (a class no file lists still has
+ *   the + 1 / sum(p_s) term).  A scale of 0 gives exact 0 for its term.
+ * Definitions, eps, the row sums in double, the log1p path of L_PRED's value and the degenerate-row rules are evc_distill_losses_ensemble's: a
+ * row whose lists are empty or all padding has sum(P) below FLT_MIN, so its L_PRED is 0 and its KL gradient exactly 0.
+ * One 256-thread workgroup per row at a time (at most 2048 workgroups stride over the rows); P is built in LDS (zeroed, then one file after
+ * the other with a barrier between them: a fixed order), so V <= 32768 (128 KiB: one workgroup per CU at that size).  pred_s, labels, dpred_s
+ * and pred_comb take 16-byte accesses where V % 4 == 0 and the array's own pointer is 16-byte aligned (labels: 4-byte), 4-byte accesses to the
+ * same elements in the same order otherwise.
+ * workspace: 3 * B floats of scratch; every row's partials are left there and the finish launch adds them in row order - no float atomics, no
+ * last-block counters: two calls on the same inputs give the same bits.  B == 0 launches nothing.
+ * Refused before any launch (EVC_ERR_BAD_ARG / EVC_ERR_BAD_SHAPE): F outside 1..8, kp outside 1..256, V outside 1..32768, a mode other than
+ * 0 / 1, mode 1 without w, a required pointer (the lists, labels, pred_s, losses, workspace) NULL. */
+int evc_distill_losses_sparse(int F, const int32_t* prior_idx, const float* prior_val, int kp, const float* w, int mode,
+                              const uint8_t* labels, const float* pred_s, int B, int V, float g_ce, float g_kl, float* losses /* [4] */,
+                              float* pred_comb, float* dpred_s, float* workspace, void* stream);
 
 /* The label losses of cs/losses.py besides CrossEntropyLoss (--label_loss), value and gradient in one pass, with evc_ce_loss's semantics:
  *   *loss += (1/B) sum_b row_loss_b ;  dpred (= | +=) grad_scale * d(sum_b row_loss_b)/dpred  (the caller passes grad_scale = w / B).
