@@ -117,6 +117,18 @@ SIGNATURES = {
     "evc_netvlad_dcenters": [vp, vp, i32, i32, i32, vp, vp],
     "evc_netvlad_normalize_fwd": [vp, i32, i32, i32, vp, vp, vp, vp, vp],
     "evc_netvlad_normalize_bwd": [vp, vp, vp, vp, i32, i32, i32, vp, vp],
+    "evc_nextvlad_assign_fwd": [vp, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp],
+    "evc_nextvlad_assign_bwd": [vp, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp],
+    "evc_nextvlad_aggregate_fwd": [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp],
+    "evc_nextvlad_aggregate_bwd": [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp],
+    "evc_nextvlad_normalize_fwd": [vp, i32, i32, i32, vp, vp, vp],
+    "evc_nextvlad_normalize_bwd": [vp, vp, vp, i32, i32, i32, vp, vp],
+    "evc_nextvlad_gate_fwd": [vp, vp, i64, vp, vp],
+    "evc_nextvlad_gate_bwd": [vp, vp, vp, i64, vp, vp, vp, vp],
+    "evc_nextvlad_colsum": [vp, i64, i32, i32, vp, vp, i64, vp],
+    "evc_nextvlad_center_cast": [vp, i32, i32, vp, vp, vp],
+    "evc_nextvlad_bias_logits": [vp, vp, i32, i32, vp, vp, i32, vp],
+    "evc_nextvlad_wgrad_uncenter": [vp, vp, vp, i32, i32, vp, vp],
     "evc_dbof_workspace": [i32, i32, vp, vp, vp],
     "evc_dbof_gather": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp],
     "evc_bn_partials_reduce": [vp, i32, i32, vp, vp],

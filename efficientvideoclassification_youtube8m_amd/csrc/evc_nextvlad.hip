@@ -1,0 +1,537 @@
+// NeXtVLAD aggregation kernels (EXTENSION - the reference's NeXtVLADModel is an empty stub, cs/frame_level_models.py:349-355, so
+// there is no reference math; the binding definition is DESIGN.md 7.12, restated in float64 in tests/_nextvlad_ref.py and checked
+// against finite differences).  The GEMM-shaped parts of the tower (expansion, cluster / attention logits, hidden layer, context
+// gating, their gradients) run on the library's NT / TN kernels; these are the f32 pieces in between:
+//
+//   evc_nextvlad_assign_fwd/bwd      a[r,g,k] = softmax_k(cluster_bn(act)[r,g,:])[k] * sigmoid(att_logit[r,g]) and its reverse mode
+//   evc_nextvlad_aggregate_fwd/bwd   V[b,k,:] = sum_{s,g} a[b,s,g,k] * xe[b,s,g*D:(g+1)*D] - asum[b,k] * c2[k,:]; da, dxe from dV
+//   evc_nextvlad_normalize_fwd/bwd   U[b,k,:] = V[b,k,:] / max(|V[b,k,:]|, 1e-12)
+//   evc_nextvlad_gate_fwd/bwd        out = h * sigmoid(gl) (context gating)
+//   evc_nextvlad_colsum              out[c] = sum_r x[r][c] in a fixed order (the two bias gradients)
+//   evc_nextvlad_center_cast         bf16(xe - be): the centred operand of the cluster / attention products; with it
+//   evc_nextvlad_bias_logits         be.W in f32 (the products' bias) and evc_nextvlad_wgrad_uncenter (the rank-one gradient term)
+//
+// Layouts: sampled frames row-major, row b*S+s; xe [R][E] with group g in columns g*D .. g*D+D, so that one video's xe is a
+// contiguous [P][D] matrix X_b over the P = S*G (frame, group) pairs, and its assignment a [R][G][K] a contiguous [P][K] matrix
+// A_b.  The aggregation is then V_b = A_b^T X_b, and its reverse mode dX_b = A_b dV_b, dA_b = X_b dV_b^T - q_b: three small f32
+// products per video, all on nx_product_kernel below.  V / dV / U are [B][K][D] (cluster-major: towers.NeXtVladTower converts
+// to the TF order d*K+k in state_dict()).  Every sum runs in a fixed order (no atomics): two runs give the same bits.
+#include "evc_common.h"
+
+static inline bool nx_aligned16(const void* p) { return ((uintptr_t)p % 16) == 0; }
+static inline int nx_grid(long n) { long nb = (n + 255) / 256; return (int)(nb < 1 ? 1 : (nb < 8192 ? nb : 8192)); }
+
+// ---- assignment: one wave per (sampled frame, group) ----
+// y = cluster_bn(act)[row, g*K + k]; p = softmax_k(y) left in y[]; returns nothing, all lanes hold their y[i] for k = lane + 64 i
+__device__ __forceinline__ void nx_group_softmax(const float* __restrict__ act, long base, int col0, int K, int lane,
+                                                 const float* __restrict__ mean, const float* __restrict__ var,
+                                                 const float* __restrict__ gamma, const float* __restrict__ beta, float (&y)[16]) {
+  float mx = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int k = lane + 64 * i;
+    y[i] = -INFINITY;
+    if (k < K) {
+      const int c = col0 + k;
+      y[i] = (act[base + k] - mean[c]) * rsqrtf(var[c] + 1e-3f) * gamma[c] + beta[c];
+      mx = fmaxf(mx, y[i]);
+    }
+  }
+  mx = wave_max(mx);
+  float sum = 0.f;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int k = lane + 64 * i;
+    if (k < K) { y[i] = __expf(y[i] - mx); sum += y[i]; } else y[i] = 0.f;
+  }
+  const float inv = 1.0f / wave_sum(sum);
+#pragma unroll
+  for (int i = 0; i < 16; ++i) y[i] *= inv;
+}
+
+__global__ __launch_bounds__(256) void nextvlad_assign_fwd_kernel(const float* __restrict__ act, int R, int G, int K,
+                                                                  const float* __restrict__ mean, const float* __restrict__ var,
+                                                                  const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                  const float* __restrict__ attl, long ld_att,
+                                                                  const float* __restrict__ att_bias, float* __restrict__ a) {
+  const int lane = threadIdx.x & 63;
+  const long rg = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (rg >= (long)R * G) return;
+  const long row = rg / G;
+  const int g = (int)(rg % G);
+  float y[16];                                   // K <= 1024
+  nx_group_softmax(act, rg * K, g * K, K, lane, mean, var, gamma, beta, y);
+  const float att = sigmoidf_(attl[row * ld_att + g] + (att_bias ? att_bias[g] : 0.f));
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int k = lane + 64 * i;
+    if (k < K) a[rg * K + k] = y[i] * att;
+  }
+}
+extern "C" int evc_nextvlad_assign_fwd(const float* act, int R, int G, int K, const float* mean, const float* var, const float* gamma,
+                                       const float* beta, const float* att_logits, int64_t ld_att, const float* att_bias, float* a,
+                                       void* stream) {
+  EVC_REQUIRE(R > 0 && G > 0 && K > 0 && K <= 1024 && ld_att >= G && (long)R * G < (1L << 31), EVC_ERR_BAD_SHAPE,
+              "evc_nextvlad_assign_fwd: needs 1 <= clusters <= 1024, ld_att >= groups (R=%d G=%d K=%d ld_att=%ld)", R, G, K, (long)ld_att);
+  EVC_REQUIRE(act && mean && var && gamma && beta && att_logits && a, EVC_ERR_BAD_ARG, "evc_nextvlad_assign_fwd: NULL operand");
+  hipLaunchKernelGGL(nextvlad_assign_fwd_kernel, dim3((unsigned)(((long)R * G + 3) / 4)), dim3(256), 0, (hipStream_t)stream, act, R, G, K,
+                     mean, var, gamma, beta, att_logits, (long)ld_att, att_bias, a);
+  EVC_LAUNCH_CHECK();
+  return EVC_OK;
+}
+
+// dz = p * att * (da - sum_k p da), datt_logit = (sum_k p da) * att * (1 - att).  p is recomputed from act and the statistics
+// (a / att would divide by a sigmoid that may have underflowed).
+__global__ __launch_bounds__(256) void nextvlad_assign_bwd_kernel(const float* __restrict__ act, int R, int G, int K,
+                                                                  const float* __restrict__ mean, const float* __restrict__ var,
+                                                                  const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                  const float* __restrict__ attl, long ld_att,
+                                                                  const float* __restrict__ att_bias, const float* __restrict__ da,
+                                                                  float* __restrict__ dz, float* __restrict__ datt,
+                                                                  bf16_t* __restrict__ datt_bf, long ld_bf) {
+  const int lane = threadIdx.x & 63;
+  const long rg = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (rg >= (long)R * G) return;
+  const long row = rg / G;
+  const int g = (int)(rg % G);
+  float y[16];
+  nx_group_softmax(act, rg * K, g * K, K, lane, mean, var, gamma, beta, y);
+  float d[16];
+  float dot = 0.f;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int k = lane + 64 * i;
+    d[i] = (k < K) ? da[rg * K + k] : 0.f;
+    dot += y[i] * d[i];
+  }
+  dot = wave_sum(dot);
+  const float att = sigmoidf_(attl[row * ld_att + g] + (att_bias ? att_bias[g] : 0.f));
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int k = lane + 64 * i;
+    if (k < K) dz[rg * K + k] = y[i] * att * (d[i] - dot);
+  }
+  if (lane == 0) {
+    const float dl = dot * att * (1.0f - att);
+    datt[rg] = dl;
+    if (datt_bf) datt_bf[row * ld_bf + g] = f32_to_bf16(dl);
+  }
+}
+extern "C" int evc_nextvlad_assign_bwd(const float* act, int R, int G, int K, const float* mean, const float* var, const float* gamma,
+                                       const float* beta, const float* att_logits, int64_t ld_att, const float* att_bias, const float* da,
+                                       float* dz, float* datt_logit, evc_bf16* datt_logit_bf16, int64_t ld_bf16, void* stream) {
+  EVC_REQUIRE(R > 0 && G > 0 && K > 0 && K <= 1024 && ld_att >= G && (long)R * G < (1L << 31) && (!datt_logit_bf16 || ld_bf16 >= G),
+              EVC_ERR_BAD_SHAPE, "evc_nextvlad_assign_bwd: needs 1 <= clusters <= 1024, ld_att / ld_bf16 >= groups (R=%d G=%d K=%d)", R, G, K);
+  EVC_REQUIRE(act && mean && var && gamma && beta && att_logits && da && dz && datt_logit, EVC_ERR_BAD_ARG,
+              "evc_nextvlad_assign_bwd: NULL operand");
+  hipLaunchKernelGGL(nextvlad_assign_bwd_kernel, dim3((unsigned)(((long)R * G + 3) / 4)), dim3(256), 0, (hipStream_t)stream, act, R, G, K,
+                     mean, var, gamma, beta, att_logits, (long)ld_att, att_bias, da, dz, datt_logit, (bf16_t*)datt_logit_bf16, (long)ld_bf16);
+  EVC_LAUNCH_CHECK();
+  return EVC_OK;
+}
+
+// ---- the per-video f32 product  C_b[m][n] = sum_l T_b[l][m] * Bm_b[l][n]  behind the aggregation and its reverse mode.
+// grid (n tiles * m tiles, B).  A workgroup owns MT = 8 * (256 / DW) rows m and DW float4 columns n: thread t holds rows
+// mq*8 .. mq*8+8 (mq = t / DW) of float4 column t % DW in registers.  The contraction runs in passes of NX_LC rows l: the
+// [NX_LC][MT] slice of T is staged in LDS (row stride MT + 4 floats: 16-byte aligned rows; the transposed staging of MODE 1 / 2
+// writes with stride MT + 4 between lanes, a 4-way bank conflict on 1/33 of the inner loop's LDS traffic), then every thread
+// reads its 8 values of a row as two 16-byte LDS loads that are uniform over the DW lanes sharing mq (broadcast) and one
+// float4 of Bm from global memory (consecutive lanes, consecutive 16 bytes): 32 FMAs per 3 loads.
+//   MODE 0  aggregate forward  l = pair p, m = cluster, n = d:  T = A_b [P][K] (staged as is),       Bm = X_b [P][D]
+//   MODE 1  dxe                l = cluster, m = pair,   n = d:  T[l][m] = A_b[m][l] (transposed),    Bm = dV_b [K][D]
+//   MODE 2  da                 l = d,       m = pair,   n = k:  T[l][m] = X_b[m][l] (transposed),    Bm = dVt_b [D][Kp]
+static constexpr int NX_LC = 64;
+struct NxArgs {
+  const float* T; long t_batch; int t_ld;        // source of T: MODE 0 T[l*t_ld + m], MODE 1 / 2 T[m*t_ld + l]
+  const float* Bm; long b_batch; int b_ld;       // Bm[l*b_ld + n]
+  int L, M, N4;                                  // contraction length, rows, float4 columns
+  int DW, MT, ntiles;
+  float* C; long c_batch; int c_ld; int c_cols;  // C[m*c_ld + n], n < c_cols
+  const float* sub; long sub_batch;              // MODE 0: c2 [K][D] (sub_batch 0); MODE 2: q [B][K]
+  float* asum;                                   // MODE 0: [B][K]
+};
+template <int MODE>
+__global__ __launch_bounds__(256) void nx_product_kernel(const NxArgs p) {
+  extern __shared__ float tile[];                // [NX_LC][MT + 4]
+  __shared__ float sa[128];                      // MODE 0: column sums of T over all l (asum of this workgroup's clusters)
+  const int t = threadIdx.x;
+  const int b = blockIdx.y;
+  const int ntile = blockIdx.x % p.ntiles, mtile = blockIdx.x / p.ntiles;
+  const int MT = p.MT, TS = p.MT + 4, DW = p.DW;
+  const int m0 = mtile * MT;
+  const int n4 = ntile * DW + t % DW, mq = t / DW;
+  const bool active = n4 < p.N4;
+  const float* __restrict__ Tb = p.T + (long)b * p.t_batch;
+  const float* __restrict__ Bb = p.Bm + (long)b * p.b_batch + (long)n4 * 4;
+  float4 acc[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+  float colsum = 0.f;
+  for (int l0 = 0; l0 < p.L; l0 += NX_LC) {
+    const int lend = min(NX_LC, p.L - l0);
+    if (MODE == 0) {
+      for (int i = t; i < NX_LC * MT; i += 256) {
+        const int l = i / MT, m = i % MT;
+        tile[l * TS + m] = (l < lend && m0 + m < p.M) ? Tb[(long)(l0 + l) * p.t_ld + m0 + m] : 0.f;
+      }
+    } else {
+      for (int i = t; i < NX_LC * MT; i += 256) {
+        const int m = i / NX_LC, l = i % NX_LC;
+        tile[l * TS + m] = (l < lend && m0 + m < p.M) ? Tb[(long)(m0 + m) * p.t_ld + l0 + l] : 0.f;
+      }
+    }
+    __syncthreads();
+    if (MODE == 0 && t < MT) {
+      for (int l = 0; l < lend; ++l) colsum += tile[l * TS + t];
+    }
+    if (active) {
+      const float* tp = tile + mq * 8;
+      const float* bp = Bb + (long)l0 * p.b_ld;
+#pragma unroll 4
+      for (int l = 0; l < lend; ++l) {
+        const float4 x = *(const float4*)(bp + (long)l * p.b_ld);
+        const float4 a0 = *(const float4*)(tp + l * TS), a1 = *(const float4*)(tp + l * TS + 4);
+        const float w[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          acc[j].x += w[j] * x.x; acc[j].y += w[j] * x.y; acc[j].z += w[j] * x.z; acc[j].w += w[j] * x.w;
+        }
+      }
+    }
+    __syncthreads();
+  }
+  if (MODE == 0) {
+    if (t < MT) {
+      sa[t] = colsum;
+      if (ntile == 0 && m0 + t < p.M) p.asum[(long)b * p.M + m0 + t] = colsum;
+    }
+    __syncthreads();
+  }
+  if (!active) return;
+  float* __restrict__ Cb = p.C + (long)b * p.c_batch;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int m = m0 + mq * 8 + j;
+    if (m >= p.M) break;
+    float4 v = acc[j];
+    if (MODE == 0) {
+      const float s = sa[mq * 8 + j];
+      const float4 c = *(const float4*)(p.sub + (long)m * p.c_ld + n4 * 4);
+      v = make_float4(v.x - s * c.x, v.y - s * c.y, v.z - s * c.z, v.w - s * c.w);
+      *(float4*)(Cb + (long)m * p.c_ld + n4 * 4) = v;
+    } else if (MODE == 1) {
+      *(float4*)(Cb + (long)m * p.c_ld + n4 * 4) = v;
+    } else {
+      const float* __restrict__ q = p.sub + (long)b * p.sub_batch;
+      const int n = n4 * 4;
+      if ((p.c_cols & 3) == 0) {                 // (n4 < N4 = c_cols / 4: the whole float4 is inside the row)
+        const float4 qq = *(const float4*)(q + n);
+        *(float4*)(Cb + (long)m * p.c_ld + n) = make_float4(v.x - qq.x, v.y - qq.y, v.z - qq.z, v.w - qq.w);
+      } else {
+        const float vv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          if (n + c < p.c_cols) Cb[(long)m * p.c_ld + n + c] = vv[c] - q[n + c];
+      }
+    }
+  }
+}
+
+// tile shape: the DW in {16, 32, 64} (MT = 128, 64, 32) that wastes the fewest lanes / rows, among those that give the chip
+// two workgroups per CU where the shape allows it
+static void nx_pick(NxArgs& p, int B) {
+  double best = -1.0;
+  for (int dw = 16; dw <= 64; dw *= 2) {
+    const int mt = 8 * (256 / dw);
+    const int nt = ceil_div(p.N4, dw), mtl = ceil_div(p.M, mt);
+    const double blocks = (double)B * nt * mtl;
+    const double score = ((double)p.N4 / ((double)nt * dw)) * ((double)p.M / ((double)mtl * mt)) * (blocks < 512.0 ? blocks / 512.0 : 1.0);
+    if (score > best) { best = score; p.DW = dw; p.MT = mt; p.ntiles = nt; }
+  }
+}
+template <int MODE>
+static int nx_launch(NxArgs& p, int B, void* stream) {
+  nx_pick(p, B);
+  const int mtl = ceil_div(p.M, p.MT);
+  const size_t lds = (size_t)NX_LC * (p.MT + 4) * sizeof(float);       // <= 33792 bytes (+ 512 static)
+  hipLaunchKernelGGL(nx_product_kernel<MODE>, dim3(p.ntiles * mtl, B), dim3(256), lds, (hipStream_t)stream, p);
+  EVC_LAUNCH_CHECK();
+  return EVC_OK;
+}
+
+#define NX_AGG_SHAPE_OK (B > 0 && B <= 65535 && S > 0 && S <= 64 && G > 0 && (long)S * G <= 1024 && K > 0 && K <= 1024 && D > 0 && D % 4 == 0)
+
+extern "C" int evc_nextvlad_aggregate_fwd(const float* a, const float* xe, int B, int S, int G, int K, int D, const float* c2, float* V,
+                                          float* asum, void* stream) {
+  EVC_REQUIRE(NX_AGG_SHAPE_OK, EVC_ERR_BAD_SHAPE,
+              "evc_nextvlad_aggregate_fwd: needs S <= 64, S * G <= 1024, K <= 1024, D %% 4 == 0, B <= 65535 (B=%d S=%d G=%d K=%d D=%d)", B, S, G, K, D);
+  EVC_REQUIRE(a && xe && c2 && V && asum, EVC_ERR_BAD_ARG, "evc_nextvlad_aggregate_fwd: NULL operand");
+  EVC_REQUIRE(nx_aligned16(a) && nx_aligned16(xe) && nx_aligned16(c2) && nx_aligned16(V), EVC_ERR_BAD_ALIGN,
+              "evc_nextvlad_aggregate_fwd: a, xe, c2 and V must be 16-byte aligned (float4 access)");
+  const int P = S * G;
+  NxArgs p{};
+  p.T = a; p.t_batch = (long)P * K; p.t_ld = K;
+  p.Bm = xe; p.b_batch = (long)P * D; p.b_ld = D;
+  p.L = P; p.M = K; p.N4 = D / 4;
+  p.C = V; p.c_batch = (long)K * D; p.c_ld = D; p.c_cols = D;
+  p.sub = c2; p.sub_batch = 0; p.asum = asum;
+  return nx_launch<0>(p, B, stream);
+}
+
+// dVt[b][d][k] = dV[b][k][d] (k < K; zeros up to Kp = K rounded up to 4): the n-contiguous operand of the da product
+__global__ __launch_bounds__(256) void nextvlad_dvt_kernel(const float* __restrict__ dV, int K, int Kp, int D, float* __restrict__ dVt) {
+  __shared__ float tl[32][33];
+  const int b = blockIdx.z;
+  const int d0 = blockIdx.x * 32, k0 = blockIdx.y * 32;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  for (int i = ty; i < 32; i += 8) {
+    const int k = k0 + i, d = d0 + tx;
+    tl[i][tx] = (k < K && d < D) ? dV[((long)b * K + k) * D + d] : 0.f;
+  }
+  __syncthreads();
+  for (int i = ty; i < 32; i += 8) {
+    const int d = d0 + i, k = k0 + tx;
+    if (d < D && k < Kp) dVt[((long)b * D + d) * Kp + k] = tl[tx][i];
+  }
+}
+// q[b][k] = sum_d dV[b][k][d] * c2[k][d]: one wave per (video, cluster)
+__global__ __launch_bounds__(256) void nextvlad_q_kernel(const float* __restrict__ dV, const float* __restrict__ c2, long BK, int K, int D,
+                                                         float* __restrict__ q) {
+  const int lane = threadIdx.x & 63;
+  const long bk = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (bk >= BK) return;
+  const int k = (int)(bk % K);
+  float s = 0.f;
+  for (int d = lane; d < D; d += 64) s += dV[bk * D + d] * c2[(long)k * D + d];
+  s = wave_sum(s);
+  if (lane == 0) q[bk] = s;
+}
+
+// floats of scratch the backward entry needs (ops.nextvlad_aggregate_bwd_ws computes the same): dVt [B][D][Kp] and q [B][K]
+static inline int64_t evc_nextvlad_aggregate_bwd_ws(int B, int K, int D) {
+  return (int64_t)B * D * ((K + 3) / 4 * 4) + (int64_t)B * K;
+}
+
+extern "C" int evc_nextvlad_aggregate_bwd(const float* a, const float* xe, int B, int S, int G, int K, int D, const float* c2,
+                                          const float* dV, float* da, float* dxe, float* ws, int64_t ws_floats, void* stream) {
+  EVC_REQUIRE(NX_AGG_SHAPE_OK, EVC_ERR_BAD_SHAPE,
+              "evc_nextvlad_aggregate_bwd: needs S <= 64, S * G <= 1024, K <= 1024, D %% 4 == 0, B <= 65535 (B=%d S=%d G=%d K=%d D=%d)", B, S, G, K, D);
+  EVC_REQUIRE(a && xe && c2 && dV && da && dxe && ws, EVC_ERR_BAD_ARG, "evc_nextvlad_aggregate_bwd: NULL operand");
+  EVC_REQUIRE(nx_aligned16(a) && nx_aligned16(xe) && nx_aligned16(c2) && nx_aligned16(dV) && nx_aligned16(da) && nx_aligned16(dxe), EVC_ERR_BAD_ALIGN,
+              "evc_nextvlad_aggregate_bwd: a, xe, c2, dV, da and dxe must be 16-byte aligned (float4 access)");
+  EVC_REQUIRE(ws_floats >= evc_nextvlad_aggregate_bwd_ws(B, K, D) && ((uintptr_t)ws % 16) == 0, EVC_ERR_BAD_ARG,
+              "evc_nextvlad_aggregate_bwd: ws holds %ld floats, %ld needed (16-byte aligned)", (long)ws_floats,
+              (long)evc_nextvlad_aggregate_bwd_ws(B, K, D));
+  const int P = S * G, Kp = (K + 3) / 4 * 4;
+  float* dVt = ws;
+  float* q = ws + (long)B * D * Kp;              // (B * D * Kp is a multiple of 4: q stays 16-byte aligned)
+  hipLaunchKernelGGL(nextvlad_dvt_kernel, dim3(ceil_div(D, 32), ceil_div(Kp, 32), B), dim3(256), 0, (hipStream_t)stream, dV, K, Kp, D, dVt);
+  EVC_LAUNCH_CHECK();
+  hipLaunchKernelGGL(nextvlad_q_kernel, dim3((unsigned)(((long)B * K + 3) / 4)), dim3(256), 0, (hipStream_t)stream, dV, c2, (long)B * K, K, D, q);
+  EVC_LAUNCH_CHECK();
+  {                                              // dxe[b][p][d] = sum_k a[b][p][k] dV[b][k][d]   (written, not accumulated)
+    NxArgs p{};
+    p.T = a; p.t_batch = (long)P * K; p.t_ld = K;
+    p.Bm = dV; p.b_batch = (long)K * D; p.b_ld = D;
+    p.L = K; p.M = P; p.N4 = D / 4;
+    p.C = dxe; p.c_batch = (long)P * D; p.c_ld = D; p.c_cols = D;
+    const int rc = nx_launch<1>(p, B, stream);
+    if (rc) return rc;
+  }
+  {                                              // da[b][p][k] = sum_d xe[b][p][d] dV[b][k][d] - q[b][k]
+    NxArgs p{};
+    p.T = xe; p.t_batch = (long)P * D; p.t_ld = D;
+    p.Bm = dVt; p.b_batch = (long)D * Kp; p.b_ld = Kp;
+    p.L = D; p.M = P; p.N4 = Kp / 4;
+    p.C = da; p.c_batch = (long)P * K; p.c_ld = K; p.c_cols = K;
+    p.sub = q; p.sub_batch = K;
+    return nx_launch<2>(p, B, stream);
+  }
+}
+
+// ---- per-(video, cluster) l2 normalisation over D: one wave each.  n = max(|V|, 1e-12) is kept for the backward pass.
+__global__ __launch_bounds__(256) void nextvlad_normalize_fwd_kernel(const float* __restrict__ V, long BK, int D, float* __restrict__ U,
+                                                                     float* __restrict__ nrm) {
+  const int lane = threadIdx.x & 63;
+  const long bk = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (bk >= BK) return;
+  float s = 0.f;
+  for (int d = lane; d < D; d += 64) { const float v = V[bk * D + d]; s += v * v; }
+  const float n = fmaxf(sqrtf(wave_sum(s)), 1e-12f);
+  const float inv = 1.0f / n;
+  for (int d = lane; d < D; d += 64) U[bk * D + d] = V[bk * D + d] * inv;
+  if (lane == 0) nrm[bk] = n;
+}
+extern "C" int evc_nextvlad_normalize_fwd(const float* V, int B, int K, int D, float* U, float* norms, void* stream) {
+  EVC_REQUIRE(B > 0 && K > 0 && D > 0 && (long)B * K < (1L << 31), EVC_ERR_BAD_SHAPE, "evc_nextvlad_normalize_fwd: bad shape (B=%d K=%d D=%d)", B, K, D);
+  EVC_REQUIRE(V && U && norms, EVC_ERR_BAD_ARG, "evc_nextvlad_normalize_fwd: NULL operand");
+  hipLaunchKernelGGL(nextvlad_normalize_fwd_kernel, dim3((unsigned)(((long)B * K + 3) / 4)), dim3(256), 0, (hipStream_t)stream, V, (long)B * K, D, U, norms);
+  EVC_LAUNCH_CHECK();
+  return EVC_OK;
+}
+// dV = (dU - u (u . dU)) / n with u = V / n; where the clamp was active (|V| <= 1e-12, U = V / 1e-12) dV = dU / n
+__global__ __launch_bounds__(256) void nextvlad_normalize_bwd_kernel(const float* __restrict__ V, const float* __restrict__ nrm,
+                                                                     const float* __restrict__ dU, long BK, int D, float* __restrict__ dV) {
+  const int lane = threadIdx.x & 63;
+  const long bk = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (bk >= BK) return;
+  const float n = nrm[bk];
+  const float inv = 1.0f / n;
+  float s = 0.f;
+  for (int d = lane; d < D; d += 64) s += V[bk * D + d] * inv * dU[bk * D + d];
+  s = (n > 1e-12f) ? wave_sum(s) : 0.f;
+  for (int d = lane; d < D; d += 64) dV[bk * D + d] = (dU[bk * D + d] - V[bk * D + d] * inv * s) * inv;
+}
+extern "C" int evc_nextvlad_normalize_bwd(const float* V, const float* norms, const float* dU, int B, int K, int D, float* dV, void* stream) {
+  EVC_REQUIRE(B > 0 && K > 0 && D > 0 && (long)B * K < (1L << 31), EVC_ERR_BAD_SHAPE, "evc_nextvlad_normalize_bwd: bad shape (B=%d K=%d D=%d)", B, K, D);
+  EVC_REQUIRE(V && norms && dU && dV, EVC_ERR_BAD_ARG, "evc_nextvlad_normalize_bwd: NULL operand");
+  hipLaunchKernelGGL(nextvlad_normalize_bwd_kernel, dim3((unsigned)(((long)B * K + 3) / 4)), dim3(256), 0, (hipStream_t)stream, V, norms, dU, (long)B * K, D, dV);
+  EVC_LAUNCH_CHECK();
+  return EVC_OK;
+}
+
+// ---- context gating: out = h * sigmoid(gl);  dh = dout * gate (the direct path), dgl = dout * h * gate * (1 - gate)
+__global__ void nextvlad_gate_fwd_kernel(const float* __restrict__ h, const float* __restrict__ gl, long n, float* __restrict__ out) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) out[i] = h[i] * sigmoidf_(gl[i]);
+}
+extern "C" int evc_nextvlad_gate_fwd(const float* h, const float* gl, int64_t n, float* out, void* stream) {
+  EVC_REQUIRE(n > 0, EVC_ERR_BAD_SHAPE, "evc_nextvlad_gate_fwd: bad shape (n=%ld)", (long)n);
+  EVC_REQUIRE(h && gl && out, EVC_ERR_BAD_ARG, "evc_nextvlad_gate_fwd: NULL operand");
+  hipLaunchKernelGGL(nextvlad_gate_fwd_kernel, dim3(nx_grid(n)), dim3(256), 0, (hipStream_t)stream, h, gl, (long)n, out);
+  EVC_LAUNCH_CHECK();
+  return EVC_OK;
+}
+__global__ void nextvlad_gate_bwd_kernel(const float* __restrict__ h, const float* __restrict__ gl, const float* __restrict__ dout, long n,
+                                         float* __restrict__ dh, float* __restrict__ dgl, bf16_t* __restrict__ dgl_bf) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const float g = sigmoidf_(gl[i]), d = dout[i];
+    dh[i] = d * g;
+    const float dl = d * h[i] * g * (1.0f - g);
+    if (dgl) dgl[i] = dl;
+    if (dgl_bf) dgl_bf[i] = f32_to_bf16(dl);
+  }
+}
+extern "C" int evc_nextvlad_gate_bwd(const float* h, const float* gl, const float* dout, int64_t n, float* dh, float* dgl, evc_bf16* dgl_bf16,
+                                     void* stream) {
+  EVC_REQUIRE(n > 0, EVC_ERR_BAD_SHAPE, "evc_nextvlad_gate_bwd: bad shape (n=%ld)", (long)n);
+  EVC_REQUIRE(h && gl && dout && dh && (dgl || dgl_bf16), EVC_ERR_BAD_ARG, "evc_nextvlad_gate_bwd: NULL operand (dgl and dgl_bf16 may not both be NULL)");
+  hipLaunchKernelGGL(nextvlad_gate_bwd_kernel, dim3(nx_grid(n)), dim3(256), 0, (hipStream_t)stream, h, gl, dout, (long)n, dh, dgl, (bf16_t*)dgl_bf16);
+  EVC_LAUNCH_CHECK();
+  return EVC_OK;
+}
+
+// ---- the bf16 operand of the cluster / attention products, centred: xc = bf16(xe - be).  xe = r.We + be carries the expansion
+// bias into every row; rounded to bf16 as it stands, that constant costs 2^-9 of ITS magnitude in every element, although all it
+// adds to a logit is the per-column constant be.W, which evc_nextvlad_bias_logits computes in f32 and the product takes as its bias.
+__global__ void nextvlad_center_cast_kernel(const float* __restrict__ xe, const float* __restrict__ be, long n4, int E4,
+                                            uint32_t* __restrict__ out) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+    const float4 x = ((const float4*)xe)[i];
+    const float4 b = ((const float4*)be)[i % E4];
+    out[2 * i] = pack_bf16x2_hw(x.x - b.x, x.y - b.y);
+    out[2 * i + 1] = pack_bf16x2_hw(x.z - b.z, x.w - b.w);
+  }
+}
+extern "C" int evc_nextvlad_center_cast(const float* xe, int R, int E, const float* be, evc_bf16* out, void* stream) {
+  EVC_REQUIRE(R > 0 && E > 0 && E % 4 == 0, EVC_ERR_BAD_SHAPE, "evc_nextvlad_center_cast: needs E %% 4 == 0 (R=%d E=%d)", R, E);
+  EVC_REQUIRE(xe && be && out && ((uintptr_t)xe % 16) == 0 && ((uintptr_t)be % 16) == 0 && ((uintptr_t)out % 8) == 0, EVC_ERR_BAD_ARG,
+              "evc_nextvlad_center_cast: NULL or misaligned operand");
+  const long n4 = (long)R * (E / 4);
+  hipLaunchKernelGGL(nextvlad_center_cast_kernel, dim3(nx_grid(n4)), dim3(256), 0, (hipStream_t)stream, xe, be, n4, E / 4, (uint32_t*)out);
+  EVC_LAUNCH_CHECK();
+  return EVC_OK;
+}
+// out[n] = sum_e be[e] * W[n][e] (+ add[n]) for n < N, 0 for N <= n < n_out: one wave per output, lanes over e in a fixed order
+__global__ __launch_bounds__(256) void nextvlad_bias_logits_kernel(const float* __restrict__ be, const float* __restrict__ W, int N, int E,
+                                                                   const float* __restrict__ add, float* __restrict__ out, int n_out) {
+  const int lane = threadIdx.x & 63;
+  const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (n >= n_out) return;
+  float s = 0.f;
+  if (n < N) {
+    for (int e = lane; e < E; e += 64) s += be[e] * W[(long)n * E + e];
+    s = wave_sum(s) + (add ? add[n] : 0.f);
+  }
+  if (lane == 0) out[n] = s;
+}
+extern "C" int evc_nextvlad_bias_logits(const float* be, const float* W, int N, int E, const float* add, float* out, int n_out, void* stream) {
+  EVC_REQUIRE(N > 0 && E > 0 && n_out >= N, EVC_ERR_BAD_SHAPE, "evc_nextvlad_bias_logits: bad shape (N=%d E=%d n_out=%d)", N, E, n_out);
+  EVC_REQUIRE(be && W && out, EVC_ERR_BAD_ARG, "evc_nextvlad_bias_logits: NULL operand");
+  hipLaunchKernelGGL(nextvlad_bias_logits_kernel, dim3((n_out + 3) / 4), dim3(256), 0, (hipStream_t)stream, be, W, N, E, add, out, n_out);
+  EVC_LAUNCH_CHECK();
+  return EVC_OK;
+}
+// dW[g][e] = dWc[g][e] + du[g] * be[e]: a weight gradient contracted against the CENTRED operand (dWc = dlogit^T . (xe - be)) plus
+// the rank-one term the centring took out (du = column sums of dlogit)
+__global__ void nextvlad_wgrad_uncenter_kernel(const float* __restrict__ dWc, const float* __restrict__ du, const float* __restrict__ be,
+                                               long n, int E, float* __restrict__ dW) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
+    dW[i] = dWc[i] + du[i / E] * be[i % E];
+}
+extern "C" int evc_nextvlad_wgrad_uncenter(const float* dWc, const float* du, const float* be, int N, int E, float* dW, void* stream) {
+  EVC_REQUIRE(N > 0 && E > 0, EVC_ERR_BAD_SHAPE, "evc_nextvlad_wgrad_uncenter: bad shape (N=%d E=%d)", N, E);
+  EVC_REQUIRE(dWc && du && be && dW, EVC_ERR_BAD_ARG, "evc_nextvlad_wgrad_uncenter: NULL operand");
+  hipLaunchKernelGGL(nextvlad_wgrad_uncenter_kernel, dim3(nx_grid((long)N * E)), dim3(256), 0, (hipStream_t)stream, dWc, du, be, (long)N * E, E, dW);
+  EVC_LAUNCH_CHECK();
+  return EVC_OK;
+}
+
+// ---- out[c] = sum_r x[r][c], rows in a fixed order: a workgroup of 16 waves owns 64 columns, wave w adds rows w, w+16, ... and
+// the 16 partial rows are added in wave order (the bias gradients dbe = colsum(dxe), dba = colsum(datt_logit)).
+__global__ __launch_bounds__(1024) void nextvlad_colsum_kernel(const float* __restrict__ x, long ld, int R, int C, float* __restrict__ out) {
+  __shared__ float part[16][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int c = blockIdx.x * 64 + lane;
+  float s = 0.f;
+  if (c < C)
+    for (int r = wave; r < R; r += 16) s += x[(long)r * ld + c];
+  part[wave][lane] = s;
+  __syncthreads();
+  if (wave == 0 && c < C) {
+    float tsum = 0.f;
+#pragma unroll
+    for (int w = 0; w < 16; ++w) tsum += part[w][lane];
+    out[c] = tsum;
+  }
+}
+// Tall inputs: NX_CS_PARTS row ranges per 64 columns, so that the chip is filled, then the partial rows added in range order.
+static constexpr int NX_CS_PARTS = 32;
+__global__ __launch_bounds__(256) void nextvlad_colsum_part_kernel(const float* __restrict__ x, long ld, int R, int C, int rows_per_part,
+                                                                   float* __restrict__ ws) {
+  __shared__ float part[4][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int c = blockIdx.x * 64 + lane;
+  const int r0 = blockIdx.y * rows_per_part, r1 = min(R, r0 + rows_per_part);
+  float s = 0.f;
+  if (c < C)
+    for (int r = r0 + wave; r < r1; r += 4) s += x[(long)r * ld + c];
+  part[wave][lane] = s;
+  __syncthreads();
+  if (wave == 0 && c < C) ws[(long)blockIdx.y * C + c] = (part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]);
+}
+__global__ void nextvlad_colsum_finish_kernel(const float* __restrict__ ws, int C, float* __restrict__ out) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  float s = 0.f;
+#pragma unroll
+  for (int p = 0; p < NX_CS_PARTS; ++p) s += ws[(long)p * C + c];
+  out[c] = s;
+}
+// ws (may be NULL): NX_CS_PARTS * C floats of scratch; with it, inputs of 512 rows or more take the two-pass path
+extern "C" int evc_nextvlad_colsum(const float* x, int64_t ld, int R, int C, float* out, float* ws, int64_t ws_floats, void* stream) {
+  EVC_REQUIRE(R > 0 && C > 0 && ld >= C, EVC_ERR_BAD_SHAPE, "evc_nextvlad_colsum: bad shape (R=%d C=%d ld=%ld)", R, C, (long)ld);
+  EVC_REQUIRE(x && out, EVC_ERR_BAD_ARG, "evc_nextvlad_colsum: NULL operand");
+  if (ws && R >= 512) {
+    EVC_REQUIRE(ws_floats >= (int64_t)NX_CS_PARTS * C, EVC_ERR_BAD_ARG, "evc_nextvlad_colsum: ws holds %ld floats, %ld needed", (long)ws_floats,
+                (long)NX_CS_PARTS * C);
+    hipLaunchKernelGGL(nextvlad_colsum_part_kernel, dim3(ceil_div(C, 64), NX_CS_PARTS), dim3(256), 0, (hipStream_t)stream, x, (long)ld, R, C,
+                       ceil_div(R, NX_CS_PARTS), ws);
+    EVC_LAUNCH_CHECK();
+    hipLaunchKernelGGL(nextvlad_colsum_finish_kernel, dim3(ceil_div(C, 256)), dim3(256), 0, (hipStream_t)stream, ws, C, out);
+    EVC_LAUNCH_CHECK();
+    return EVC_OK;
+  }
+  hipLaunchKernelGGL(nextvlad_colsum_kernel, dim3(ceil_div(C, 64)), dim3(1024), 0, (hipStream_t)stream, x, (long)ld, R, C, out);
+  EVC_LAUNCH_CHECK();
+  return EVC_OK;
+}

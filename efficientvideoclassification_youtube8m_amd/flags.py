@@ -135,6 +135,11 @@ _define("precision", "bf16", str, "'bf16' (one bf16 MFMA product per forward con
         "'split' (split-bf16 operands, f32-operand accuracy, in every forward GEMM)")
 _define("netvlad_cluster_size", 64, int, "NetVLADModel (extension): number of clusters")
 _define("netvlad_hidden_size", 1024, int, "NetVLADModel (extension): width of the hidden layer after the aggregation")
+_define("nextvlad_cluster_size", 64, int, "NeXtVLADModel (extension): number of clusters")
+_define("nextvlad_hidden_size", 1024, int, "NeXtVLADModel (extension): width of the hidden layer after the aggregation")
+_define("nextvlad_groups", 8, int, "NeXtVLADModel (extension): number of groups the expanded frame is split into")
+_define("nextvlad_expansion", 2, int, "NeXtVLADModel (extension): expanded width = nextvlad_expansion x feature size")
+_define("nextvlad_gating_reduction", 8, int, "NeXtVLADModel (extension): context gating bottleneck = nextvlad_hidden_size / nextvlad_gating_reduction")
 _define("log_every", 1, int, "host metrics / logging period in iterations (the reference logs every step)")
 _define("metrics_on_device", False, _bool, "validate / eval_finetune: select what Hit@1 / PERR / GAP / mAP need from each batch on the device "
         "(ops.eval_select_rows) and fetch [B, top_k] + a few [B] vectors instead of the [B, 4716] predictions and labels; same metrics bit "

@@ -16,7 +16,7 @@ import torch
 from . import models, ops, video_level_models
 from .engine import HLstmTower
 from .flags import FLAGS
-from .towers import DbofGenericTower, DbofTower, LogisticTower, NetVladTower
+from .towers import DbofGenericTower, DbofTower, LogisticTower, NetVladTower, NeXtVladTower
 
 
 class FrameBatch(object):
@@ -183,10 +183,40 @@ class NetVLADModel(models.BaseModel):
 
 
 class NeXtVLADModel(models.BaseModel):
-    """Empty stub in the reference (cs/frame_level_models.py:349-355): returns None."""
+    """Empty stub in the reference (cs/frame_level_models.py:349-355: both methods `return`).  Here `create_model` builds the
+    NeXtVLAD aggregation tower (towers.NeXtVladTower) - an EXTENSION whose binding definition is DESIGN.md 7.12 (float64
+    restatement: tests/_nextvlad_ref.py), there being no reference math to match.  A call with `model_input is None` keeps
+    returning None, as the reference's stub does for every input; `create_model_inference` stays the stub."""
 
-    def create_model(self, model_input, vocab_size, num_frames, **unused_params):
-        return
+    def __init__(self):
+        self.towers = {}
+
+    def create_model(self, model_input, vocab_size, num_frames, iterations=None, cluster_size=None, hidden_size=None, groups=None,
+                     expansion=None, gating_reduction=None, is_training=True, **unused_params):
+        if model_input is None:
+            return                                                   # the reference's stub
+        iterations = iterations or FLAGS.iterations
+        cluster_size = cluster_size or FLAGS.nextvlad_cluster_size
+        hidden_size = hidden_size or FLAGS.nextvlad_hidden_size
+        groups = groups or FLAGS.nextvlad_groups
+        expansion = expansion or FLAGS.nextvlad_expansion
+        gating_reduction = gating_reduction or FLAGS.nextvlad_gating_reduction
+        _vl_check()
+        if not model_input.is_cuda:
+            raise ops._lib.EvcError("NeXtVLADModel needs a device tensor (got a CPU tensor); there is no CPU path")
+        scope = unused_params.get("scope", "model")
+        B, T, F = model_input.shape
+        tw = self.towers.get(scope)
+        if tw is None:
+            tw = self.towers[scope] = NeXtVladTower(B, T, F, vocab_size, iterations, cluster_size, hidden_size, groups, expansion,
+                                                    gating_reduction, FLAGS.moe_num_mixtures, device=model_input.device, training=True,
+                                                    scope=scope, seed=unused_params.get("seed", 0))
+        nf = num_frames.reshape(-1).to(torch.int32)
+        u = unused_params.get("uniform")
+        if u is None:
+            u = torch.rand((B, iterations), dtype=torch.float32, device=model_input.device)
+        return {"predictions": tw.forward(model_input.contiguous(), nf, u, normalize=unused_params.get("normalize_input", False),
+                                          is_training=is_training)}
 
     def create_model_inference(self, model_input, vocab_size, every_n, num_frames, **unused_params):
         return

@@ -1371,3 +1371,75 @@ def netvlad_normalize_fwd(V, B, K, F, n1, n2, Y_bf16, Y_f32=None):
 
 def netvlad_normalize_bwd(V, n1, n2, dY, B, K, F, dV):
     _lib.call("evc_netvlad_normalize_bwd", _p(V), _p(n1), _p(n2), _p(dY), B, K, F, _p(dV), _stream())
+
+
+# ---------------------------------------------------------------------------
+# NeXtVLAD aggregation (csrc/evc_nextvlad.hip; extension, see towers.NeXtVladTower and DESIGN.md 7.12)
+def nextvlad_assign_fwd(act, R, G, K, mean, var, gamma, beta, att_logits, a, att_bias=None):
+    """a [R,G,K] = softmax_k(cluster_bn(act)) * sigmoid(att_logits[:, :G] (+ att_bias)); att_logits f32 [R, ld >= G]."""
+    _lib.call("evc_nextvlad_assign_fwd", _p(act), R, G, K, _p(mean), _p(var), _p(gamma), _p(beta), _p(att_logits), att_logits.stride(0),
+              _p(att_bias), _p(a), _stream())
+
+
+def nextvlad_assign_bwd(act, R, G, K, mean, var, gamma, beta, att_logits, da, dz, datt_logit, att_bias=None, datt_logit_bf16=None):
+    """dz [R,G*K] and datt_logit [R,G] from da; the softmax is recomputed from act.  datt_logit_bf16 [R, ld >= G] bf16: a copy
+    as the operand of the attention weight-gradient products (its columns >= G are left alone)."""
+    _lib.call("evc_nextvlad_assign_bwd", _p(act), R, G, K, _p(mean), _p(var), _p(gamma), _p(beta), _p(att_logits), att_logits.stride(0),
+              _p(att_bias), _p(da), _p(dz), _p(datt_logit), _p(datt_logit_bf16),
+              datt_logit_bf16.stride(0) if datt_logit_bf16 is not None else 0, _stream())
+
+
+def nextvlad_aggregate_fwd(a, xe, B, S, G, K, D, c2, V, asum):
+    _lib.call("evc_nextvlad_aggregate_fwd", _p(a), _p(xe), B, S, G, K, D, _p(c2), _p(V), _p(asum), _stream())
+
+
+def nextvlad_aggregate_bwd_ws(B, K, D):
+    """Floats of scratch evc_nextvlad_aggregate_bwd needs: dV transposed [B][D][K rounded up to 4] and q [B][K]."""
+    return B * D * round_up(K, 4) + B * K
+
+
+def nextvlad_aggregate_bwd(a, xe, B, S, G, K, D, c2, dV, da, dxe, ws=None):
+    if ws is None:
+        ws = torch.empty(nextvlad_aggregate_bwd_ws(B, K, D), dtype=F32, device=da.device)
+    _lib.call("evc_nextvlad_aggregate_bwd", _p(a), _p(xe), B, S, G, K, D, _p(c2), _p(dV), _p(da), _p(dxe), _p(ws), ws.numel(), _stream())
+
+
+def nextvlad_normalize_fwd(V, B, K, D, U, norms):
+    _lib.call("evc_nextvlad_normalize_fwd", _p(V), B, K, D, _p(U), _p(norms), _stream())
+
+
+def nextvlad_normalize_bwd(V, norms, dU, B, K, D, dV):
+    _lib.call("evc_nextvlad_normalize_bwd", _p(V), _p(norms), _p(dU), B, K, D, _p(dV), _stream())
+
+
+def nextvlad_gate_fwd(h, gl, out):
+    _lib.call("evc_nextvlad_gate_fwd", _p(h), _p(gl), h.numel(), _p(out), _stream())
+
+
+def nextvlad_gate_bwd(h, gl, dout, dh, dgl=None, dgl_bf16=None):
+    _lib.call("evc_nextvlad_gate_bwd", _p(h), _p(gl), _p(dout), h.numel(), _p(dh), _p(dgl), _p(dgl_bf16), _stream())
+
+
+def nextvlad_colsum(x, R, C, out, ws=None):
+    """out[c] = sum_r x[r, c] (f32, fixed order).  Tall inputs go through 32 partial rows in `ws` (32 * C floats; from the
+    stream-aware caching allocator when not given)."""
+    if ws is None and R >= 512:
+        ws = torch.empty(32 * C, dtype=F32, device=x.device)
+    _lib.call("evc_nextvlad_colsum", _p(x), x.stride(0), R, C, _p(out), _p(ws), ws.numel() if ws is not None else 0, _stream())
+
+
+def nextvlad_center_cast(xe, R, E, be, out_bf16):
+    """out [R,E] bf16 = xe - be: the centred operand of the cluster / attention products (contiguous rows)."""
+    assert xe.is_contiguous() and out_bf16.is_contiguous() and out_bf16.dtype == BF16
+    _lib.call("evc_nextvlad_center_cast", _p(xe), R, E, _p(be), _p(out_bf16), _stream())
+
+
+def nextvlad_bias_logits(be, W, N, E, out, add=None):
+    """out[n] = be . W[n] (+ add[n]) for n < N, zeros up to out.numel(): the constant the expansion bias adds to every logit (f32)."""
+    assert W.is_contiguous() and W.dtype == F32
+    _lib.call("evc_nextvlad_bias_logits", _p(be), _p(W), N, E, _p(add), _p(out), out.numel(), _stream())
+
+
+def nextvlad_wgrad_uncenter(dWc, du, be, N, E, dW):
+    """dW [N,E] = dWc[:N] + du[:, None] * be[None, :] (the rank-one term a product against the centred operand leaves out)."""
+    _lib.call("evc_nextvlad_wgrad_uncenter", _p(dWc), _p(du), _p(be), N, E, _p(dW), _stream())

@@ -672,6 +672,270 @@ class NetVladTower(TowerBase):
         return self.moe.pred
 
 
+class NeXtVladTower(TowerBase):
+    """NeXtVLAD aggregation tower (Lin, Xiao, Fan 2018) - an EXTENSION: the reference ships NeXtVLADModel as an empty stub
+    (cs/frame_level_models.py:349-355), so there is no reference math; the binding definition is DESIGN.md 7.12, restated in
+    float64 in tests/_nextvlad_ref.py: sample S frames -> expansion (.We + be, E = expansion * F) -> per group g of D = E / G
+    columns: attention sigmoid(.Wa + ba) and softmax over K clusters of cluster_bn(.Wc) -> V[k] = sum_{s,g} a[s,g,k] (xe[s,g,:] -
+    c2[k]) -> l2 per cluster -> vlad_bn -> .Wh -> hidden1_bn -> context gating (h * sigmoid(relu6(gating_bn(h.Wg1)).Wg2)) -> MoE.
+    Two stated deviations from the paper's code: relu6 where it has relu (the fused batch-norm tail knows relu6 only) and no
+    dropout before the hidden layer.  GEMM-shaped parts on the library's NT / TN kernels (bf16 operands, f32 accumulation), the
+    f32 pieces in csrc/evc_nextvlad.hip.  V / U / Y and vlad_bn are kept cluster-major [K][D]; the TF order d*K + k of
+    vlad_bn/* and of hidden1_weights' rows is restored in state_dict()."""
+
+    PRECISIONS = ("bf16",)             # no split-bf16 forward (set_precision refuses anything else)
+
+    EW, EB, AW, AB = "expansion_weights", "expansion_biases", "attention_weights", "attention_biases"
+    CW, C2, HW, G1, G2 = "cluster_weights", "cluster_weights2", "hidden1_weights", "gating_weights_1", "gating_weights_2"
+    BNS = ("cluster_bn", "vlad_bn", "hidden1_bn", "gating_bn")
+    l2_names = (MoeHead.GATES, MoeHead.EXPERTS)
+    # all four batch-norms go through BatchNorm.backward: their gamma/beta gradients are global (all-reduced f64 sums)
+    global_grad_names = tuple("%s/%s" % (s_, v) for s_ in BNS for v in ("beta", "gamma"))
+    AP = 64                            # rows of the attention operand image / columns of the attention logits (one GEMM tile)
+
+    def __init__(self, batch_size, max_frames=300, feature_size=1152, vocab_size=4716, iterations=30, cluster_size=64,
+                 hidden_size=1024, groups=8, expansion=2, gating_reduction=8, num_mixtures=2, device="cuda:0", training=True,
+                 scope="model", seed=0, process_group=None):
+        self.device, self.training, self.scope, self.pg = torch.device(device), training, scope, process_group
+        self.T, self.F, self.V, self.S = max_frames, feature_size, vocab_size, iterations
+        self.Kc, self.Hd, self.Mx, self.G = cluster_size, hidden_size, num_mixtures, groups
+        if groups < 1 or expansion < 1 or gating_reduction < 1 or cluster_size < 1:
+            raise ValueError("groups=%d, expansion=%d, gating_reduction=%d, cluster_size=%d must all be >= 1"
+                             % (groups, expansion, gating_reduction, cluster_size))
+        F, K, H, G = feature_size, cluster_size, hidden_size, groups
+        E = self.E = expansion * F
+        if E % G:
+            raise ValueError("expanded width %d (expansion %d x %d features) is not a multiple of groups=%d" % (E, expansion, F, G))
+        D = self.D = E // G
+        if hidden_size % gating_reduction:
+            raise ValueError("hidden_size=%d is not a multiple of gating_reduction=%d" % (hidden_size, gating_reduction))
+        Hg = self.Hg = hidden_size // gating_reduction
+        for what, n in (("feature_size", F), ("expanded width", E), ("groups x cluster_size", G * K), ("cluster_size x group width", K * D),
+                        ("hidden_size", H), ("hidden_size / gating_reduction", Hg)):
+            if n % 64:
+                raise ValueError("%s = %d must be a multiple of 64 for the MFMA GEMM tiles" % (what, n))
+        if D % 4:
+            raise ValueError("group width %d (expanded width %d / groups %d) must be a multiple of 4 for the aggregation kernels" % (D, E, G))
+        if G > self.AP:
+            raise ValueError("groups=%d: the attention product holds at most %d groups" % (G, self.AP))
+        if K > 1024:
+            raise ValueError("cluster_size=%d: the assignment kernel holds at most 1024 clusters" % K)
+        if iterations > 64:
+            raise ValueError("iterations=%d: the aggregation kernels hold at most 64 sampled frames per video" % iterations)
+        if iterations * G > 1024:
+            raise ValueError("iterations x groups = %d: the aggregation kernels hold at most 1024 (frame, group) pairs per video" % (iterations * G))
+        shapes = OrderedDict()
+        shapes[self.EW] = (E, F)                                     # every 2-D weight is stored transposed [out][in]
+        shapes[self.EB] = (E,)
+        shapes[self.AW] = (G, E)
+        shapes[self.AB] = (G,)
+        shapes[self.CW] = (G * K, E)
+        shapes.update(BatchNorm.shapes("cluster_bn", G * K))
+        shapes[self.C2] = (K, D)                                     # centres [K][D] (tf: [D, K])
+        shapes.update(BatchNorm.shapes("vlad_bn", K * D))            # cluster-major k*D + d
+        shapes[self.HW] = (H, K * D)                                 # columns cluster-major
+        shapes.update(BatchNorm.shapes("hidden1_bn", H))
+        shapes[self.G1] = (Hg, H)
+        shapes.update(BatchNorm.shapes("gating_bn", Hg))
+        shapes[self.G2] = (H, Hg)
+        shapes.update(MoeHead.shapes(H, vocab_size, num_mixtures))
+        self.buffers = OrderedDict()
+        self._setup_store(shapes)
+        # the attention product has N = G columns, below the GEMM tiles' width: its forward operand is the first G rows of a
+        # zero-padded [AP][E] image (every writer of shadow_fwd - casts, the fused Adam pass - writes through the view)
+        self.att_img = torch.zeros((self.AP, E), dtype=BF16, device=self.device)
+        self.shadow_fwd[self.AW] = self.att_img[:G]
+        self.bn_cl = BatchNorm(self, "cluster_bn", G * K)
+        self.bn_v = BatchNorm(self, "vlad_bn", K * D)
+        self.bn_h = BatchNorm(self, "hidden1_bn", H)
+        self.bn_g = BatchNorm(self, "gating_bn", Hg)
+        self.moe = MoeHead(self, H, vocab_size, num_mixtures)
+        gen = torch.Generator(device="cpu")
+        gen.manual_seed(seed)
+        for k, shp in self.store.shapes.items():
+            p = self.store.p(k)
+            if k in (self.EW, self.AW, self.CW, self.G1, self.G2):
+                p.copy_(torch.randn(shp, generator=gen, dtype=F32) / math.sqrt(shp[1]))
+            elif k == self.C2:
+                p.copy_(torch.randn(shp, generator=gen, dtype=F32) / math.sqrt(D))
+            elif k == self.HW:
+                p.copy_(torch.randn(shp, generator=gen, dtype=F32) / math.sqrt(K))
+            elif len(shp) == 2:
+                lim = math.sqrt(6.0 / (shp[0] + shp[1]))
+                p.copy_((torch.rand(shp, generator=gen, dtype=F32) * 2 - 1) * lim)
+            elif k.endswith("/gamma"):
+                p.fill_(1.0)
+        self.refresh_shadows()
+        self._alloc(batch_size)
+
+    # TF order d*K + k  <->  internal cluster-major k*D + d: the rows of hidden1_weights [K*D, H] and every vlad_bn vector
+    def _tf_keys(self, prefix):
+        return ["%s/vlad_bn/%s" % (prefix, v) for v in ("beta", "gamma", "moving_mean", "moving_variance")]
+
+    def state_dict(self):
+        out = super().state_dict()
+        K, D, H = self.Kc, self.D, self.Hd
+        key = "%s/%s" % (self.scope, self.HW)
+        out[key] = out[key].view(K, D, H).permute(1, 0, 2).reshape(D * K, H).contiguous()
+        for key in self._tf_keys(self.scope):
+            out[key] = out[key].view(K, D).t().reshape(D * K).contiguous()
+        return out
+
+    def load_state_dict(self, sd, prefix=None):
+        prefix = self.scope if prefix is None else prefix
+        K, D, H = self.Kc, self.D, self.Hd
+        key = "%s/%s" % (prefix, self.HW)
+        if key not in sd:
+            raise KeyError("NeXtVladTower.load_state_dict: %r is not in the checkpoint (scope prefix %r; it holds e.g. %s)"
+                           % (key, prefix, sorted(sd)[:3]))
+        sd = dict(sd)
+        sd[key] = sd[key].view(D, K, H).permute(1, 0, 2).reshape(K * D, H).contiguous()
+        for key in self._tf_keys(prefix):
+            if key in sd:
+                sd[key] = sd[key].view(D, K).t().reshape(K * D).contiguous()
+        super().load_state_dict(sd, prefix)
+
+    def _alloc(self, B):
+        dev, F, S, K, H, G, E, D, Hg, AP = self.device, self.F, self.S, self.Kc, self.Hd, self.G, self.E, self.D, self.Hg, self.AP
+        self.B, self.R = B, B * S
+        if self.training and self.R % 32:
+            raise ValueError("batch_size x iterations = %d must be a multiple of 32 (row count of the TN weight-gradient products)" % self.R)
+        R = self.R
+        self.Bk = ops.round_up(B, 32)
+        self.r = torch.empty((R, F), dtype=F32, device=dev)
+        self.idx = torch.empty((B, S), dtype=torch.int32, device=dev)
+        self.r_bf = torch.empty((R, F), dtype=BF16, device=dev)
+        self.xe = torch.empty((R, E), dtype=F32, device=dev)
+        self.xe_bf = torch.empty((R, E), dtype=BF16, device=dev)
+        self.attl = torch.empty((R, AP), dtype=F32, device=dev)      # attention logits, biases included (columns >= G: zeros)
+        self.cbias = torch.empty((G * K,), dtype=F32, device=dev)    # be . Wc: what the expansion bias adds to every cluster logit
+        self.abias = torch.empty((AP,), dtype=F32, device=dev)       # be . Wa + ba (entries >= G: zeros)
+        self.act = torch.empty((R, G * K), dtype=F32, device=dev)
+        self.a = torch.empty((R, G * K), dtype=F32, device=dev)
+        self.asum = torch.empty((B, K), dtype=F32, device=dev)
+        self.Vv = torch.empty((B, K, D), dtype=F32, device=dev)
+        self.nrm = torch.empty((B, K), dtype=F32, device=dev)
+        self.U = torch.empty((B, K * D), dtype=F32, device=dev)
+        self.Y_bf = torch.zeros((self.Bk, K * D), dtype=BF16, device=dev)
+        self.hid = torch.empty((B, H), dtype=F32, device=dev)
+        self.h = torch.empty((B, H), dtype=F32, device=dev)
+        self.h_bf = torch.zeros((self.Bk, H), dtype=BF16, device=dev)
+        self.g1pre = torch.empty((B, Hg), dtype=F32, device=dev)
+        self.g1_bf = torch.zeros((self.Bk, Hg), dtype=BF16, device=dev)
+        self.gl = torch.empty((B, H), dtype=F32, device=dev)
+        self.out = torch.empty((B, H), dtype=F32, device=dev)
+        self.moe.alloc(B, self.training)
+        if self.training:
+            self.dh = torch.empty((B, H), dtype=F32, device=dev)
+            self.dgl_bf = torch.zeros((self.Bk, H), dtype=BF16, device=dev)
+            self.dg1 = torch.empty((B, Hg), dtype=F32, device=dev)
+            self.dg1pre_bf = torch.zeros((self.Bk, Hg), dtype=BF16, device=dev)
+            self.dhid_bf = torch.zeros((self.Bk, H), dtype=BF16, device=dev)
+            self.dY = torch.empty((B, K * D), dtype=F32, device=dev)
+            self.dU = torch.empty((B, K * D), dtype=F32, device=dev)
+            self.dV = torch.empty((B, K, D), dtype=F32, device=dev)
+            self.agg_ws = torch.empty(ops.nextvlad_aggregate_bwd_ws(B, K, D), dtype=F32, device=dev)
+            self.da = torch.empty((R, G * K), dtype=F32, device=dev)
+            self.dz = torch.empty((R, G * K), dtype=F32, device=dev)
+            self.dact_bf = torch.empty((R, G * K), dtype=BF16, device=dev)
+            self.datt = torch.empty((R, G), dtype=F32, device=dev)
+            self.datt_bf = torch.zeros((R, AP), dtype=BF16, device=dev)     # columns >= G stay zero
+            self.dxe = torch.empty((R, E), dtype=F32, device=dev)
+            self.dxe_bf = torch.empty((R, E), dtype=BF16, device=dev)
+            self.colsum_ws = torch.empty(32 * E, dtype=F32, device=dev)    # partial rows of the two bias-gradient column sums
+            self.dWa_pad = torch.empty((AP, E), dtype=F32, device=dev)      # the attention weight gradient on a whole tile of rows
+
+    def forward(self, x, num_frames, uniform, normalize=True, is_training=True):
+        """x [B,T,F] float32 or uint8 raw frames; uniform [B,S] f32 in [0,1): the frame-sampling draw."""
+        B = x.shape[0]
+        if B != self.B:
+            self._alloc(B)
+        F, S, K, H, R, G, E, D, Hg, AP = self.F, self.S, self.Kc, self.Hd, self.R, self.G, self.E, self.D, self.Hg, self.AP
+        st, bc, bv, bh, bg = self.store, self.bn_cl, self.bn_v, self.bn_h, self.bn_g
+        if self.precision != "bf16":
+            raise NotImplementedError("NeXtVladTower has no split-bf16 mode")
+        ops.sample_frames_gather(x, uniform, num_frames, self.r, self.idx, normalize=normalize)
+        ops.cast_bf16(self.r, self.r_bf)
+        ops.gemm_nt(self.r_bf, self.shadow_fwd[self.EW], R, E, F, self.xe, bias=st.p(self.EB))
+        # The bf16 operand of the two logit products is xe - be: the bias is the same in every row, so rounding it into the operand
+        # would spend bf16's 8 bits on a constant whose whole effect on a logit is the per-column constant be.W - that goes into the
+        # products as their f32 bias instead (and cluster_bn removes it again in training).  xe itself stays f32 for the aggregation.
+        ops.nextvlad_center_cast(self.xe, R, E, st.p(self.EB), self.xe_bf)
+        ops.nextvlad_bias_logits(st.p(self.EB), st.p(self.CW), G * K, E, self.cbias)
+        ops.nextvlad_bias_logits(st.p(self.EB), st.p(self.AW), G, E, self.abias, add=st.p(self.AB))
+        ops.gemm_nt(self.xe_bf, self.shadow_fwd[self.CW], R, G * K, E, self.act, bias=self.cbias)
+        ops.gemm_nt(self.xe_bf, self.att_img, R, AP, E, self.attl, bias=self.abias)
+        bc.stats(self.act, R, is_training)
+        ops.nextvlad_assign_fwd(self.act, R, G, K, bc.mean, bc.var, bc.gamma(), bc.beta(), self.attl, self.a)
+        ops.nextvlad_aggregate_fwd(self.a, self.xe, B, S, G, K, D, st.p(self.C2), self.Vv, self.asum)
+        ops.nextvlad_normalize_fwd(self.Vv, B, K, D, self.U, self.nrm)
+        bv.stats(self.U, B, is_training)
+        ops.bn_apply(self.U, B, K * D, bv.mean, bv.var, bv.gamma(), bv.beta(), False, y_bf16=self.Y_bf)
+        ops.gemm_nt(self.Y_bf, self.shadow_fwd[self.HW], B, H, K * D, self.hid)
+        bh.stats(self.hid, B, is_training)
+        ops.bn_apply(self.hid, B, H, bh.mean, bh.var, bh.gamma(), bh.beta(), False, y_f32=self.h, y_bf16=self.h_bf)
+        ops.gemm_nt(self.h_bf, self.shadow_fwd[self.G1], B, Hg, H, self.g1pre)
+        bg.stats(self.g1pre, B, is_training)
+        ops.bn_apply(self.g1pre, B, Hg, bg.mean, bg.var, bg.gamma(), bg.beta(), True, y_bf16=self.g1_bf)
+        ops.gemm_nt(self.g1_bf, self.shadow_fwd[self.G2], B, H, Hg, self.gl)
+        ops.nextvlad_gate_fwd(self.h, self.gl, self.out)
+        self._taped = self.training and is_training
+        return self.moe.forward(self.out)
+
+    def grad_stages(self):
+        moe = [MoeHead.GATES, MoeHead.EXPERTS, MoeHead.EBIAS]
+        hidden = [self.G2, "gating_bn/beta", "gating_bn/gamma", self.G1, "hidden1_bn/beta", "hidden1_bn/gamma", self.HW]
+        return moe, hidden, [k for k in self.names if k not in moe and k not in hidden]
+
+    def backward(self, dpred, on_moe_grads_ready=None, moe_weight_grads=True, on_stage=None):
+        assert self.training and self._taped, "backward needs a training-mode forward"
+        B, F, S, K, H, R, G, E, D, Hg, AP = self.B, self.F, self.S, self.Kc, self.Hd, self.R, self.G, self.E, self.D, self.Hg, self.AP
+        st, bc = self.store, self.bn_cl
+        dout = self.moe.backward(dpred, weight_grads=moe_weight_grads)
+        if on_moe_grads_ready is not None:
+            on_moe_grads_ready()
+        if on_stage is not None:
+            on_stage(0)
+        # context gating
+        ops.nextvlad_gate_bwd(self.h, self.gl, dout, self.dh, dgl_bf16=self.dgl_bf)
+        ops.gemm_tn(self.dgl_bf, self.g1_bf, H, Hg, self.Bk, st.g(self.G2))              # dWg2^T [H][Hg]
+        ops.gemm_nt(self.dgl_bf, self.shadow_bwd[self.G2], B, Hg, H, self.dg1)
+        self.bn_g.backward(self.g1pre, self.dg1, B, True, dx_bf16=self.dg1pre_bf)
+        ops.gemm_tn(self.dg1pre_bf, self.h_bf, Hg, H, self.Bk, st.g(self.G1))           # dWg1^T [Hg][H]
+        ops.gemm_nt(self.dg1pre_bf, self.shadow_bwd[self.G1], B, H, Hg, self.dh, accumulate=True)
+        # hidden layer
+        self.bn_h.backward(self.hid, self.dh, B, False, dx_bf16=self.dhid_bf)
+        ops.gemm_tn(self.dhid_bf, self.Y_bf, H, K * D, self.Bk, st.g(self.HW))          # dWh^T [H][K*D]
+        if on_stage is not None:
+            on_stage(1)
+        ops.gemm_nt(self.dhid_bf, self.shadow_bwd[self.HW], B, K * D, H, self.dY)
+        self.bn_v.backward(self.U, self.dY, B, False, dx_f32=self.dU)
+        ops.nextvlad_normalize_bwd(self.Vv, self.nrm, self.dU, B, K, D, self.dV)
+        ops.netvlad_dcenters(self.asum, self.dV, B, K, D, st.g(self.C2))                 # the same sum as NetVLAD's centres
+        ops.nextvlad_aggregate_bwd(self.a, self.xe, B, S, G, K, D, st.p(self.C2), self.dV, self.da, self.dxe, ws=self.agg_ws)
+        ops.nextvlad_assign_bwd(self.act, R, G, K, bc.mean, bc.var, bc.gamma(), bc.beta(), self.attl, self.da, self.dz, self.datt,
+                                datt_logit_bf16=self.datt_bf)
+        bc.backward(self.act, self.dz, R, False, dx_bf16=self.dact_bf)
+        # xe_bf is the CENTRED operand xe - be.  dWc = dact^T . xe = dact^T . (xe - be) + colsum(dact) (x) be, and the column sums of a
+        # training-mode batch-norm's input gradient are zero: the product against the centred operand is the whole gradient.
+        ops.gemm_tn(self.dact_bf, self.xe_bf, G * K, E, R, st.g(self.CW))               # dWc^T [G*K][E]
+        ops.gemm_nt(self.dact_bf, self.shadow_bwd[self.CW], R, E, G * K, self.dxe, accumulate=True)      # + dact . Wc^T
+        # the attention logits have no batch-norm behind them: dWa = datt^T . (xe - be) + dba (x) be, dba = colsum(datt)
+        ops.nextvlad_colsum(self.datt, R, G, st.g(self.AB), ws=self.colsum_ws)
+        ops.gemm_tn(self.datt_bf, self.xe_bf, AP, E, R, self.dWa_pad)                   # on a whole tile of rows, rows >= G are zero
+        ops.nextvlad_wgrad_uncenter(self.dWa_pad, st.g(self.AB), st.p(self.EB), G, E, st.g(self.AW))
+        ops.gemm_nt(self.datt_bf, self.shadow_bwd[self.AW], R, E, AP, self.dxe, accumulate=True)         # + datt . Wa^T
+        ops.nextvlad_colsum(self.dxe, R, E, st.g(self.EB), ws=self.colsum_ws)
+        ops.cast_bf16(self.dxe, self.dxe_bf)
+        ops.gemm_tn(self.dxe_bf, self.r_bf, E, F, R, st.g(self.EW))                     # dWe^T [E][F]
+        if on_stage is not None:
+            on_stage(2)
+
+    @property
+    def pred(self):
+        return self.moe.pred
+
+
 class LogisticTower(TowerBase):
     """FrameLevelLogisticModel: sigmoid(mean_frames(x) . W + b), with the
     reference's quirk that the sum runs over all (zero-padded) frames and is

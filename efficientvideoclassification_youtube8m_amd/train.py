@@ -41,7 +41,7 @@ import torch
 from . import eval_util, frame_level_models, losses, ops, readers, video_level_models
 from .distill import DistillGraph, EnsembleDistillGraph, OfflineDistillGraph, SerialStudentsGraph, SingleTowerGraph
 from .flags import FLAGS, GetListOfFeatureNamesAndSizes
-from .towers import DbofTower, LogisticTower, NetVladTower
+from .towers import DbofTower, LogisticTower, NetVladTower, NeXtVladTower
 
 NUM_CLASSES = 4716       # readers.YT8MFrameFeatureReader default num_classes (cs/readers.py:121)
 
@@ -54,7 +54,7 @@ def find_class_by_name(name, modules):
 
 def _apply_precision(tw):
     """--precision for the single-tower models: towers with a split-bf16 forward take it (DbofTower, LogisticTower); a tower
-    without one (NetVladTower) refuses anything but 'bf16' instead of silently ignoring the flag."""
+    without one (NetVladTower, NeXtVladTower) refuses anything but 'bf16' instead of silently ignoring the flag."""
     if FLAGS.precision != "bf16":
         if "high" not in getattr(tw, "PRECISIONS", ()):
             raise ValueError("--precision %s: %s has no such forward mode" % (FLAGS.precision, type(tw).__name__))
@@ -462,12 +462,17 @@ def build_graph(model, label_loss_fn, feature_size, batch_size, every_n, device,
                           FLAGS.netvlad_hidden_size, FLAGS.moe_num_mixtures, device=device, process_group=process_group)
         _apply_precision(tw)
         return SingleTowerGraph(tw, **common)
+    if isinstance(model, frame_level_models.NeXtVLADModel):         # extension (the reference's class is an empty stub)
+        tw = NeXtVladTower(batch_size, FLAGS.max_num_frames, feature_size, NUM_CLASSES, FLAGS.iterations, FLAGS.nextvlad_cluster_size,
+                           FLAGS.nextvlad_hidden_size, FLAGS.nextvlad_groups, FLAGS.nextvlad_expansion, FLAGS.nextvlad_gating_reduction,
+                           FLAGS.moe_num_mixtures, device=device, process_group=process_group)
+        _apply_precision(tw)
+        return SingleTowerGraph(tw, **common)
     if isinstance(model, frame_level_models.FrameLevelLogisticModel):
         tw = LogisticTower(batch_size, FLAGS.max_num_frames, feature_size, NUM_CLASSES, device=device)
         _apply_precision(tw)
         return SingleTowerGraph(tw, **common)
-    raise NotImplementedError("model %s has no training graph (NeXtVLAD is an empty stub in the reference too)"
-                              % type(model).__name__)
+    raise NotImplementedError("model %s has no training graph" % type(model).__name__)
 
 
 def synthetic_batches(batch_size, feature_size, device, videos_per_epoch, num_epochs, seed, drop_remainder=False):

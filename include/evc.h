@@ -846,6 +846,46 @@ int evc_netvlad_normalize_fwd(const float* V, int B, int K, int F, float* n1, fl
 int evc_netvlad_normalize_bwd(const float* V, const float* n1, const float* n2, const float* dY, int B, int K, int F, float* dV,
                               void* stream);
 
+/* ---- NeXtVLAD aggregation (EXTENSION: the reference's NeXtVLADModel is an empty stub, cs/frame_level_models.py:349-355; the
+ * binding definition is DESIGN.md 7.12, restated in float64 in tests/_nextvlad_ref.py).  csrc/evc_nextvlad.hip.
+ * Sizes: R = B*S sampled frames (row b*S+s), E = G*D expanded width, G groups of D columns, K clusters.  xe [R][E] f32 holds
+ * group g in columns g*D .. g*D+D; a / da / act / dz are [R][G][K] (= [R][G*K]); V / dV / U are [B][K][D] (cluster-major).
+ * All f32, every sum in a fixed order, no atomics: the same inputs give the same bits.  K <= 1024 everywhere. ------------- */
+/* a[r,g,k] = softmax_k(cluster_bn(act)[r,g,:])[k] * sigmoid(att_logits[r*ld_att + g] + att_bias[g]); att_bias may be NULL. */
+int evc_nextvlad_assign_fwd(const float* act, int R, int G, int K, const float* mean, const float* var, const float* gamma,
+                            const float* beta, const float* att_logits, int64_t ld_att, const float* att_bias, float* a, void* stream);
+/* With p = softmax_k(cluster_bn(act)) recomputed (never a / att), att as above:  dz = p * att * (da - sum_k p*da) [R][G*K],
+ * datt_logit[r*G+g] = (sum_k p*da) * att * (1-att); datt_logit_bf16 (may be NULL): the same at [r*ld_bf16 + g] as bf16. */
+int evc_nextvlad_assign_bwd(const float* act, int R, int G, int K, const float* mean, const float* var, const float* gamma,
+                            const float* beta, const float* att_logits, int64_t ld_att, const float* att_bias, const float* da,
+                            float* dz, float* datt_logit, evc_bf16* datt_logit_bf16, int64_t ld_bf16, void* stream);
+/* asum[b][k] = sum_{s,g} a[b,s,g,k];  V[b][k][d] = sum_{s,g} a[b,s,g,k] * xe[b,s,g*D+d] - asum[b][k] * c2[k][d].
+ * Needs S <= 64, S*G <= 1024, D % 4 == 0, B <= 65535 (EVC_ERR_BAD_SHAPE otherwise, nothing is launched). */
+int evc_nextvlad_aggregate_fwd(const float* a, const float* xe, int B, int S, int G, int K, int D, const float* c2, float* V,
+                               float* asum, void* stream);
+/* da[b,s,g,k] = sum_d dV[b][k][d] * (xe[b,s,g*D+d] - c2[k][d]);  dxe[b,s,g*D+d] = sum_k a[b,s,g,k] * dV[b][k][d] (written, not
+ * accumulated).  ws: B*D*Kp + B*K floats of 16-byte aligned scratch, Kp = K rounded up to 4.  Same shape limits as the forward.
+ * (dc2 = evc_netvlad_dcenters(asum, dV, B, K, D): the same sum.) */
+int evc_nextvlad_aggregate_bwd(const float* a, const float* xe, int B, int S, int G, int K, int D, const float* c2, const float* dV,
+                               float* da, float* dxe, float* ws, int64_t ws_floats, void* stream);
+/* U[b][k][:] = V[b][k][:] / n, n = norms[b][k] = max(|V[b][k][:]|, 1e-12);  dV = (dU - U (U . dU)) / n. */
+int evc_nextvlad_normalize_fwd(const float* V, int B, int K, int D, float* U, float* norms, void* stream);
+int evc_nextvlad_normalize_bwd(const float* V, const float* norms, const float* dU, int B, int K, int D, float* dV, void* stream);
+/* Context gating over n elements: out = h * sigmoid(gl);  dh = dout * gate, dgl = dout * h * gate * (1 - gate) (f32 and / or bf16). */
+int evc_nextvlad_gate_fwd(const float* h, const float* gl, int64_t n, float* out, void* stream);
+int evc_nextvlad_gate_bwd(const float* h, const float* gl, const float* dout, int64_t n, float* dh, float* dgl, evc_bf16* dgl_bf16,
+                          void* stream);
+/* The bf16 operand of the cluster / attention products, centred: out[r][e] = bf16(xe[r][e] - be[e]) (E % 4 == 0).  The constant
+ * the bias adds to every logit, out[n] = sum_e be[e]*W[n][e] (+ add[n]) for n < N and 0 for N <= n < n_out, goes into the
+ * product as its f32 bias.  A weight gradient contracted against the centred operand gets the rank-one term back:
+ * dW[n][e] = dWc[n][e] + du[n]*be[e], du = the column sums of the logit gradient. */
+int evc_nextvlad_center_cast(const float* xe, int R, int E, const float* be, evc_bf16* out, void* stream);
+int evc_nextvlad_bias_logits(const float* be, const float* W, int N, int E, const float* add, float* out, int n_out, void* stream);
+int evc_nextvlad_wgrad_uncenter(const float* dWc, const float* du, const float* be, int N, int E, float* dW, void* stream);
+/* out[c] = sum_r x[r*ld + c], rows added in a fixed order (bias gradients).  ws (may be NULL): 32 * C floats of scratch; with it,
+ * inputs of 512 rows or more are summed over 32 row ranges per 64 columns and the partial rows added in range order. */
+int evc_nextvlad_colsum(const float* x, int64_t ld, int R, int C, float* out, float* ws, int64_t ws_floats, void* stream);
+
 /* ---- one LSTM layer's train op in two launches (csrc/evc_optim.hip; a9: cs/train.py:329-334,413-418 + AdamOptimizer :241-242) ----
  * evc_sqnorm2_partials: part[0..1023] = per-block sums of squares of ga [na], part[1024] = sum of squares of gb [nb] (gb may be
  *   NULL with nb = 0); plain stores, fixed order.  part: 1025 floats.
