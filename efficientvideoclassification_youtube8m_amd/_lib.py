@@ -121,6 +121,9 @@ SIGNATURES = {
     "evc_nextvlad_assign_bwd": [vp, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp],
     "evc_nextvlad_aggregate_fwd": [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp],
     "evc_nextvlad_aggregate_bwd": [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp],
+    "evc_nextvlad_aggregate_packed_fwd": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp],
+    "evc_nextvlad_aggregate_packed_bwd": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp],
+    "evc_frames_gather_packed": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp],
     "evc_nextvlad_normalize_fwd": [vp, i32, i32, i32, vp, vp, vp],
     "evc_nextvlad_normalize_bwd": [vp, vp, vp, i32, i32, i32, vp, vp],
     "evc_nextvlad_gate_fwd": [vp, vp, i64, vp, vp],

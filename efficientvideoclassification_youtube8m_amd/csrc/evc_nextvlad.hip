@@ -5,6 +5,7 @@
 //
 //   evc_nextvlad_assign_fwd/bwd      a[r,g,k] = softmax_k(cluster_bn(act)[r,g,:])[k] * sigmoid(att_logit[r,g]) and its reverse mode
 //   evc_nextvlad_aggregate_fwd/bwd   V[b,k,:] = sum_{s,g} a[b,s,g,k] * xe[b,s,g*D:(g+1)*D] - asum[b,k] * c2[k,:]; da, dxe from dV
+//   evc_nextvlad_aggregate_packed_fwd/bwd, evc_frames_gather_packed   the same over a ragged, packed list of frames per video (7.13)
 //   evc_nextvlad_normalize_fwd/bwd   U[b,k,:] = V[b,k,:] / max(|V[b,k,:]|, 1e-12)
 //   evc_nextvlad_gate_fwd/bwd        out = h * sigmoid(gl) (context gating)
 //   evc_nextvlad_colsum              out[c] = sum_r x[r][c] in a fixed order (the two bias gradients)
@@ -149,8 +150,13 @@ struct NxArgs {
   float* C; long c_batch; int c_ld; int c_cols;  // C[m*c_ld + n], n < c_cols
   const float* sub; long sub_batch;              // MODE 0: c2 [K][D] (sub_batch 0); MODE 2: q [B][K]
   float* asum;                                   // MODE 0: [B][K]
+  const int* row_off; int G;                     // PACKED: first frame row of every video [B+1], groups (pairs per frame row)
 };
-template <int MODE>
+// PACKED (ragged videos): video b owns the pairs row_off[b]*G .. row_off[b+1]*G of the pair-major operands (T in
+// every mode, Bm in MODE 0, C in MODE 1 / 2) instead of a fixed batch stride, and its pair count P_b replaces L (MODE 0) or M
+// (MODE 1 / 2); the grid is sized for the longest video and a workgroup whose row tile lies beyond P_b leaves before the first
+// barrier (the condition is uniform over the workgroup).  Every element keeps the summation order of the fixed-length path.
+template <int MODE, bool PACKED = false>
 __global__ __launch_bounds__(256) void nx_product_kernel(const NxArgs p) {
   extern __shared__ float tile[];                // [NX_LC][MT + 4]
   __shared__ float sa[128];                      // MODE 0: column sums of T over all l (asum of this workgroup's clusters)
@@ -161,23 +167,33 @@ __global__ __launch_bounds__(256) void nx_product_kernel(const NxArgs p) {
   const int m0 = mtile * MT;
   const int n4 = ntile * DW + t % DW, mq = t / DW;
   const bool active = n4 < p.N4;
-  const float* __restrict__ Tb = p.T + (long)b * p.t_batch;
-  const float* __restrict__ Bb = p.Bm + (long)b * p.b_batch + (long)n4 * 4;
+  int L = p.L, M = p.M;
+  long t_base = (long)b * p.t_batch, b_base = (long)b * p.b_batch, c_base = (long)b * p.c_batch;
+  if (PACKED) {
+    const int r0 = p.row_off[b];
+    const long pair0 = (long)r0 * p.G;
+    const int Pb = (p.row_off[b + 1] - r0) * p.G;
+    t_base = pair0 * p.t_ld;
+    if (MODE == 0) { L = Pb; b_base = pair0 * p.b_ld; }
+    else { M = Pb; c_base = pair0 * p.c_ld; if (m0 >= M) return; }
+  }
+  const float* __restrict__ Tb = p.T + t_base;
+  const float* __restrict__ Bb = p.Bm + b_base + (long)n4 * 4;
   float4 acc[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) acc[j] = make_float4(0.f, 0.f, 0.f, 0.f);
   float colsum = 0.f;
-  for (int l0 = 0; l0 < p.L; l0 += NX_LC) {
-    const int lend = min(NX_LC, p.L - l0);
+  for (int l0 = 0; l0 < L; l0 += NX_LC) {
+    const int lend = min(NX_LC, L - l0);
     if (MODE == 0) {
       for (int i = t; i < NX_LC * MT; i += 256) {
         const int l = i / MT, m = i % MT;
-        tile[l * TS + m] = (l < lend && m0 + m < p.M) ? Tb[(long)(l0 + l) * p.t_ld + m0 + m] : 0.f;
+        tile[l * TS + m] = (l < lend && m0 + m < M) ? Tb[(long)(l0 + l) * p.t_ld + m0 + m] : 0.f;
       }
     } else {
       for (int i = t; i < NX_LC * MT; i += 256) {
         const int m = i / NX_LC, l = i % NX_LC;
-        tile[l * TS + m] = (l < lend && m0 + m < p.M) ? Tb[(long)(m0 + m) * p.t_ld + l0 + l] : 0.f;
+        tile[l * TS + m] = (l < lend && m0 + m < M) ? Tb[(long)(m0 + m) * p.t_ld + l0 + l] : 0.f;
       }
     }
     __syncthreads();
@@ -203,16 +219,16 @@ __global__ __launch_bounds__(256) void nx_product_kernel(const NxArgs p) {
   if (MODE == 0) {
     if (t < MT) {
       sa[t] = colsum;
-      if (ntile == 0 && m0 + t < p.M) p.asum[(long)b * p.M + m0 + t] = colsum;
+      if (ntile == 0 && m0 + t < M) p.asum[(long)b * M + m0 + t] = colsum;
     }
     __syncthreads();
   }
   if (!active) return;
-  float* __restrict__ Cb = p.C + (long)b * p.c_batch;
+  float* __restrict__ Cb = p.C + c_base;
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const int m = m0 + mq * 8 + j;
-    if (m >= p.M) break;
+    if (m >= M) break;
     float4 v = acc[j];
     if (MODE == 0) {
       const float s = sa[mq * 8 + j];
@@ -249,12 +265,12 @@ static void nx_pick(NxArgs& p, int B) {
     if (score > best) { best = score; p.DW = dw; p.MT = mt; p.ntiles = nt; }
   }
 }
-template <int MODE>
+template <int MODE, bool PACKED = false>
 static int nx_launch(NxArgs& p, int B, void* stream) {
   nx_pick(p, B);
   const int mtl = ceil_div(p.M, p.MT);
   const size_t lds = (size_t)NX_LC * (p.MT + 4) * sizeof(float);       // <= 33792 bytes (+ 512 static)
-  hipLaunchKernelGGL(nx_product_kernel<MODE>, dim3(p.ntiles * mtl, B), dim3(256), lds, (hipStream_t)stream, p);
+  hipLaunchKernelGGL((nx_product_kernel<MODE, PACKED>), dim3(p.ntiles * mtl, B), dim3(256), lds, (hipStream_t)stream, p);
   EVC_LAUNCH_CHECK();
   return EVC_OK;
 }
@@ -347,6 +363,139 @@ extern "C" int evc_nextvlad_aggregate_bwd(const float* a, const float* xe, int B
     p.sub = q; p.sub_batch = K;
     return nx_launch<2>(p, B, stream);
   }
+}
+
+// ---- ragged videos: video b owns the frame rows row_off[b] .. row_off[b+1] of a, xe, da, dxe, k_b of them in
+// time order (k_b = 0: none).  The same three products with a per-video length; B * K * D outputs and the scratch as above.
+#define NX_PACKED_SHAPE_OK                                                                                                          \
+  (B > 0 && B <= 65535 && T > 0 && G > 0 && (long)T * G < (1L << 31) && K > 0 && K <= 1024 && D > 0 && D % 4 == 0 && max_k >= 0 && \
+   max_k <= T && R >= max_k && (long)R <= (long)B * max_k && (long)R * G < (1L << 31))
+
+extern "C" int evc_nextvlad_aggregate_packed_fwd(const float* a, const float* xe, const int32_t* row_off, int B, int T, int G, int K, int D,
+                                                 int R, int max_k, const float* c2, float* V, float* asum, void* stream) {
+  EVC_REQUIRE(NX_PACKED_SHAPE_OK, EVC_ERR_BAD_SHAPE,
+              "evc_nextvlad_aggregate_packed_fwd: needs K <= 1024, D %% 4 == 0, B <= 65535, max_k <= T, max_k <= R <= B * max_k "
+              "(B=%d T=%d G=%d K=%d D=%d R=%d max_k=%d)", B, T, G, K, D, R, max_k);
+  EVC_REQUIRE(a && xe && row_off && c2 && V && asum, EVC_ERR_BAD_ARG, "evc_nextvlad_aggregate_packed_fwd: NULL operand");
+  EVC_REQUIRE(nx_aligned16(a) && nx_aligned16(xe) && nx_aligned16(c2) && nx_aligned16(V), EVC_ERR_BAD_ALIGN,
+              "evc_nextvlad_aggregate_packed_fwd: a, xe, c2 and V must be 16-byte aligned (float4 access)");
+  NxArgs p{};
+  p.T = a; p.t_ld = K;
+  p.Bm = xe; p.b_ld = D;
+  p.L = max_k * G; p.M = K; p.N4 = D / 4;        // (L is read per video in the kernel)
+  p.C = V; p.c_batch = (long)K * D; p.c_ld = D; p.c_cols = D;
+  p.sub = c2; p.sub_batch = 0; p.asum = asum;
+  p.row_off = row_off; p.G = G;
+  return nx_launch<0, true>(p, B, stream);
+}
+
+extern "C" int evc_nextvlad_aggregate_packed_bwd(const float* a, const float* xe, const int32_t* row_off, int B, int T, int G, int K, int D,
+                                                 int R, int max_k, const float* c2, const float* dV, float* da, float* dxe, float* ws,
+                                                 int64_t ws_floats, void* stream) {
+  EVC_REQUIRE(NX_PACKED_SHAPE_OK, EVC_ERR_BAD_SHAPE,
+              "evc_nextvlad_aggregate_packed_bwd: needs K <= 1024, D %% 4 == 0, B <= 65535, max_k <= T, max_k <= R <= B * max_k "
+              "(B=%d T=%d G=%d K=%d D=%d R=%d max_k=%d)", B, T, G, K, D, R, max_k);
+  EVC_REQUIRE(a && xe && row_off && c2 && dV && da && dxe && ws, EVC_ERR_BAD_ARG, "evc_nextvlad_aggregate_packed_bwd: NULL operand");
+  EVC_REQUIRE(nx_aligned16(a) && nx_aligned16(xe) && nx_aligned16(c2) && nx_aligned16(dV) && nx_aligned16(da) && nx_aligned16(dxe), EVC_ERR_BAD_ALIGN,
+              "evc_nextvlad_aggregate_packed_bwd: a, xe, c2, dV, da and dxe must be 16-byte aligned (float4 access)");
+  EVC_REQUIRE(ws_floats >= evc_nextvlad_aggregate_bwd_ws(B, K, D) && ((uintptr_t)ws % 16) == 0, EVC_ERR_BAD_ARG,
+              "evc_nextvlad_aggregate_packed_bwd: ws holds %ld floats, %ld needed (16-byte aligned)", (long)ws_floats,
+              (long)evc_nextvlad_aggregate_bwd_ws(B, K, D));
+  if (max_k == 0) return EVC_OK;                 // no video owns a row: nothing to write
+  const int Pmax = max_k * G, Kp = (K + 3) / 4 * 4;
+  float* dVt = ws;
+  float* q = ws + (long)B * D * Kp;
+  hipLaunchKernelGGL(nextvlad_dvt_kernel, dim3(ceil_div(D, 32), ceil_div(Kp, 32), B), dim3(256), 0, (hipStream_t)stream, dV, K, Kp, D, dVt);
+  EVC_LAUNCH_CHECK();
+  hipLaunchKernelGGL(nextvlad_q_kernel, dim3((unsigned)(((long)B * K + 3) / 4)), dim3(256), 0, (hipStream_t)stream, dV, c2, (long)B * K, K, D, q);
+  EVC_LAUNCH_CHECK();
+  {                                              // dxe rows of video b: A_b dV_b   (written, not accumulated)
+    NxArgs p{};
+    p.T = a; p.t_ld = K;
+    p.Bm = dV; p.b_batch = (long)K * D; p.b_ld = D;
+    p.L = K; p.M = Pmax; p.N4 = D / 4;           // (M sizes the grid; the kernel reads every video's own)
+    p.C = dxe; p.c_ld = D; p.c_cols = D;
+    p.row_off = row_off; p.G = G;
+    const int rc = nx_launch<1, true>(p, B, stream);
+    if (rc) return rc;
+  }
+  {                                              // da rows of video b: X_b dV_b^T - q_b
+    NxArgs p{};
+    p.T = xe; p.t_ld = D;
+    p.Bm = dVt; p.b_batch = (long)D * Kp; p.b_ld = Kp;
+    p.L = D; p.M = Pmax; p.N4 = Kp / 4;
+    p.C = da; p.c_ld = K; p.c_cols = K;
+    p.sub = q; p.sub_batch = K;
+    p.row_off = row_off; p.G = G;
+    return nx_launch<2, true>(p, B, stream);
+  }
+}
+
+// ---- the packed rows themselves: row row_off[b] + j is frame j * every_n of video b, dequantised / l2-normalised with the
+// arithmetic of sample_gather_kernel (evc_elementwise.hip) in the same order, so that one source frame gives the same bits through
+// either gather.  One wave per row; the row's video by a binary search of row_off (the last b with row_off[b] <= row: videos
+// without a row are stepped over).  Rows R .. Rp are zeros (the padding of the TN products' contraction), also in the bf16 copy.
+__global__ __launch_bounds__(256) void frames_gather_packed_kernel(const float* __restrict__ x, const uint8_t* __restrict__ xq,
+                                                                   const int* __restrict__ nfr, const int* __restrict__ row_off, int B,
+                                                                   int T, int F, int every_n, int R, int Rp, int normalize,
+                                                                   float* __restrict__ out, uint2* __restrict__ out_bf) {
+  const int lane = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= Rp) return;
+  const int F4 = F >> 2;
+  float4* dst = (float4*)(out + row * F);
+  uint2* dst_bf = out_bf ? out_bf + row * F4 : nullptr;
+  if (row >= R) {
+    for (int j = lane; j < F4; j += 64) {
+      dst[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (dst_bf) dst_bf[j] = make_uint2(0u, 0u);
+    }
+    return;
+  }
+  int b = 0, hi = B;
+  while (hi - b > 1) {
+    const int mid = (b + hi) >> 1;
+    if (row_off[mid] <= (int)row) b = mid; else hi = mid;
+  }
+  const int n = nfr[b];
+  long fr = (long)((int)row - row_off[b]) * every_n;
+  const int idx = fr < 0 ? 0 : (fr >= T ? T - 1 : (int)fr);
+  const bool padded = xq && idx >= n;            // uint8 input: frames >= num_frames are padding (zero after Dequantize)
+  auto load = [&](int j) {
+    if (padded) return make_float4(0.f, 0.f, 0.f, 0.f);
+    if (xq) {
+      const uchar4 q = ((const uchar4*)(xq + ((long)b * T + idx) * F))[j];
+      const float sc = 4.0f / 255.0f, bi = 4.0f / 512.0f - 2.0f;
+      return make_float4(q.x * sc + bi, q.y * sc + bi, q.z * sc + bi, q.w * sc + bi);
+    }
+    return ((const float4*)(x + ((long)b * T + idx) * F))[j];
+  };
+  float inv = 1.f;
+  if (normalize) {
+    float ss = 0.f;
+    for (int j = lane; j < F4; j += 64) { const float4 v = load(j); ss += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w; }
+    inv = rsqrtf(fmaxf(wave_sum(ss), 1e-12f));
+  }
+  for (int j = lane; j < F4; j += 64) {
+    float4 v = load(j); v.x *= inv; v.y *= inv; v.z *= inv; v.w *= inv; dst[j] = v;
+    if (dst_bf) dst_bf[j] = make_uint2(pack_bf16x2_hw(v.x, v.y), pack_bf16x2_hw(v.z, v.w));
+  }
+}
+extern "C" int evc_frames_gather_packed(const float* x, const uint8_t* x_u8, const int32_t* num_frames, const int32_t* row_off, int B, int T,
+                                        int F, int every_n, int R, int Rp, int normalize, float* out, evc_bf16* out_bf16, void* stream) {
+  EVC_REQUIRE(B > 0 && T > 0 && F > 0 && F % 4 == 0 && every_n >= 1 && R >= 0 && Rp >= R && Rp - R < 32 &&
+              (long)R <= (long)B * ((T + every_n - 1) / every_n), EVC_ERR_BAD_SHAPE,
+              "evc_frames_gather_packed: needs F %% 4 == 0, every_n >= 1, R <= B * ceil(T / every_n), R <= Rp < R + 32 "
+              "(B=%d T=%d F=%d every_n=%d R=%d Rp=%d)", B, T, F, every_n, R, Rp);
+  EVC_REQUIRE((x != nullptr) != (x_u8 != nullptr), EVC_ERR_BAD_ARG, "evc_frames_gather_packed: exactly one of x / x_u8");
+  EVC_REQUIRE(num_frames && row_off && out, EVC_ERR_BAD_ARG, "evc_frames_gather_packed: NULL operand");
+  EVC_REQUIRE(nx_aligned16(x) && ((uintptr_t)x_u8 % 4) == 0 && nx_aligned16(out) && ((uintptr_t)out_bf16 % 8) == 0, EVC_ERR_BAD_ALIGN,
+              "evc_frames_gather_packed: misaligned operand (float4 / uchar4 / 8-byte bf16 access)");
+  if (Rp == 0) return EVC_OK;
+  hipLaunchKernelGGL(frames_gather_packed_kernel, dim3((unsigned)((Rp + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, x_u8, num_frames, row_off,
+                     B, T, F, every_n, R, Rp, normalize, out, (uint2*)out_bf16);
+  EVC_LAUNCH_CHECK();
+  return EVC_OK;
 }
 
 // ---- per-(video, cluster) l2 normalisation over D: one wave each.  n = max(|V|, 1e-12) is kept for the backward pass.

@@ -1537,8 +1537,10 @@ class SingleTowerGraph(_StepGraph):
         """The dL/dpred buffer the last step filled, as {"teacher": ...} (the one tower).  For tests and debugging."""
         return {} if self._dp is None else {"teacher": self._dp}
 
-    def step(self, x_raw, labels_u8, num_frames, uniform=None, apply=True):
-        """x_raw [B,T,F] float32 or uint8 (as the reader delivers it: Dequantize is fused into the input kernels)."""
+    def step(self, x_raw, labels_u8, num_frames, uniform=None, apply=True, num_frames_host=None):
+        """x_raw [B,T,F] float32 or uint8 (as the reader delivers it: Dequantize is fused into the input kernels).
+        num_frames_host: the frame counts on the host, for a NeXtVladTower in grid mode (its packed rows are laid out from them
+        without a device sync; no draw is made in that mode)."""
         from .towers import DbofGenericTower, DbofTower, NetVladTower, NeXtVladTower
         B, V = labels_u8.shape
         if self._dp is None or self._dp.shape[0] != B:
@@ -1547,8 +1549,10 @@ class SingleTowerGraph(_StepGraph):
         if self.dp and B != tw.B:
             raise ValueError("data-parallel step on %d videos, the tower was built for %d per rank (ragged batches are not "
                              "allowed under data parallelism: drop the remainder)" % (B, tw.B))
-        if isinstance(tw, (DbofTower, NetVladTower, NeXtVladTower, DbofGenericTower)):
-            if uniform is None:      # (SampleRandomSequence draws one start per video: column 0 is used)
+        if isinstance(tw, NeXtVladTower) and tw.frames == "grid":
+            pred = tw.forward(x_raw, num_frames, num_frames_host=num_frames_host)
+        elif isinstance(tw, (DbofTower, NetVladTower, NeXtVladTower, DbofGenericTower)):
+            if uniform is None:     # (SampleRandomSequence draws one start per video: column 0 is used)
                 uniform = torch.rand((B, tw.S), dtype=F32, device=self.device)
             self.last_uniform = uniform              # the tf.random_uniform draw of this step (SampleRandomFrames)
             pred = tw.forward(x_raw, num_frames, uniform)

@@ -140,6 +140,9 @@ _define("nextvlad_hidden_size", 1024, int, "NeXtVLADModel (extension): width of 
 _define("nextvlad_groups", 8, int, "NeXtVLADModel (extension): number of groups the expanded frame is split into")
 _define("nextvlad_expansion", 2, int, "NeXtVLADModel (extension): expanded width = nextvlad_expansion x feature size")
 _define("nextvlad_gating_reduction", 8, int, "NeXtVLADModel (extension): context gating bottleneck = nextvlad_hidden_size / nextvlad_gating_reduction")
+_define("nextvlad_frames", "sampled", str, "NeXtVLADModel (extension): sampled (--iterations frames drawn per video and step) | grid (the frames "
+        "0, every_n, 2 every_n, ... of each video's real frames, a different number per video, packed without padding: --every_n 1 is every real "
+        "frame, the teacher's input; --every_n 10 or 30 the fewer-frames student's; --iterations is not read)")
 _define("log_every", 1, int, "host metrics / logging period in iterations (the reference logs every step)")
 _define("metrics_on_device", False, _bool, "validate / eval_finetune: select what Hit@1 / PERR / GAP / mAP need from each batch on the device "
         "(ops.eval_select_rows) and fetch [B, top_k] + a few [B] vectors instead of the [B, 4716] predictions and labels; same metrics bit "

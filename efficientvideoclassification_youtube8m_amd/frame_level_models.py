@@ -192,10 +192,12 @@ class NeXtVLADModel(models.BaseModel):
         self.towers = {}
 
     def create_model(self, model_input, vocab_size, num_frames, iterations=None, cluster_size=None, hidden_size=None, groups=None,
-                     expansion=None, gating_reduction=None, is_training=True, **unused_params):
+                     expansion=None, gating_reduction=None, is_training=True, frames=None, every_n=None, **unused_params):
         if model_input is None:
             return                                                   # the reference's stub
         iterations = iterations or FLAGS.iterations
+        frames = frames or FLAGS.nextvlad_frames                     # "grid": every every_n-th real frame, packed
+        every_n = every_n or FLAGS.every_n
         cluster_size = cluster_size or FLAGS.nextvlad_cluster_size
         hidden_size = hidden_size or FLAGS.nextvlad_hidden_size
         groups = groups or FLAGS.nextvlad_groups
@@ -210,8 +212,11 @@ class NeXtVLADModel(models.BaseModel):
         if tw is None:
             tw = self.towers[scope] = NeXtVladTower(B, T, F, vocab_size, iterations, cluster_size, hidden_size, groups, expansion,
                                                     gating_reduction, FLAGS.moe_num_mixtures, device=model_input.device, training=True,
-                                                    scope=scope, seed=unused_params.get("seed", 0))
+                                                    scope=scope, seed=unused_params.get("seed", 0), frames=frames, every_n=every_n)
         nf = num_frames.reshape(-1).to(torch.int32)
+        if tw.frames == "grid":                                      # no draw; the host frame counts lay out the packed rows
+            return {"predictions": tw.forward(model_input.contiguous(), nf, normalize=unused_params.get("normalize_input", False),
+                                              is_training=is_training, num_frames_host=unused_params.get("num_frames_host"))}
         u = unused_params.get("uniform")
         if u is None:
             u = torch.rand((B, iterations), dtype=torch.float32, device=model_input.device)

@@ -1404,6 +1404,61 @@ def nextvlad_aggregate_bwd(a, xe, B, S, G, K, D, c2, dV, da, dxe, ws=None):
     _lib.call("evc_nextvlad_aggregate_bwd", _p(a), _p(xe), B, S, G, K, D, _p(c2), _p(dV), _p(da), _p(dxe), _p(ws), ws.numel(), _stream())
 
 
+class GridPlan:
+    """Packed rows of a ragged batch, from the frame counts on the host: video b contributes the frames j * every_n,
+    j < k[b] = ceil(min(n_b, max_frames) / every_n) (n_b <= 0: none), as the rows row_off[b] .. row_off[b+1] in time order.
+    k, row_off: int32 numpy [B], [B+1]; R = row_off[B]; Rp = R rounded up to 32 (row count of the TN products); max_k = max_b k[b]."""
+
+    def __init__(self, num_frames_host, every_n, max_frames):
+        import numpy as np
+        every_n, max_frames = int(every_n), int(max_frames)
+        if every_n < 1 or every_n > max_frames:
+            raise ValueError("every_n=%d must lie in 1 .. max_num_frames=%d" % (every_n, max_frames))
+        n = np.clip(np.asarray(num_frames_host).reshape(-1).astype(np.int64), 0, max_frames)
+        k = (n + every_n - 1) // every_n
+        self.every_n, self.B = every_n, int(n.shape[0])
+        self.k = k.astype(np.int32)
+        self.row_off = np.zeros(self.B + 1, np.int32)
+        np.cumsum(k, out=self.row_off[1:])
+        self.R = int(self.row_off[-1])
+        self.Rp = round_up(self.R, 32)
+        self.max_k = int(k.max()) if self.B else 0
+
+
+def grid_capacity(B, max_frames, every_n):
+    """Rows the packed buffers of a batch of B videos are allocated for: every video at full length, rounded up to 32."""
+    return round_up(B * ((max_frames + every_n - 1) // every_n), 32)
+
+
+def frames_gather_packed(x, num_frames, row_off, every_n, R, Rp, out, out_bf16=None, normalize=False):
+    """out [>= Rp, F] f32 (and out_bf16, the same rows as bf16): row row_off[b] + j = frame j * every_n of video b with
+    sample_frames_gather's arithmetic; rows R .. Rp zeros.  row_off: device int32 [B+1] (GridPlan.row_off)."""
+    B, T, F = x.shape
+    is_u8 = x.dtype == torch.uint8
+    assert x.is_contiguous() and out.is_contiguous() and out.dtype == F32 and out.shape[0] >= Rp and out.shape[1] == F
+    assert out_bf16 is None or (out_bf16.is_contiguous() and out_bf16.dtype == BF16 and out_bf16.shape[0] >= Rp and out_bf16.shape[1] == F)
+    assert row_off.dtype == torch.int32 and row_off.numel() == B + 1 and num_frames.dtype == torch.int32 and num_frames.numel() == B
+    _lib.call("evc_frames_gather_packed", None if is_u8 else _p(x), _p(x) if is_u8 else None, _p(num_frames), _p(row_off), B, T, F, every_n, R, Rp,
+              1 if normalize else 0, _p(out), _p(out_bf16), _stream())
+
+
+def nextvlad_aggregate_packed_fwd(a, xe, row_off, B, T, G, K, D, R, max_k, c2, V, asum):
+    """nextvlad_aggregate_fwd over packed rows: video b's a / xe rows are row_off[b] .. row_off[b+1] (device int32 [B+1])."""
+    assert row_off.dtype == torch.int32 and row_off.numel() == B + 1
+    assert a.numel() >= R * G * K and xe.numel() >= R * G * D and V.numel() >= B * K * D and asum.numel() >= B * K
+    _lib.call("evc_nextvlad_aggregate_packed_fwd", _p(a), _p(xe), _p(row_off), B, T, G, K, D, R, max_k, _p(c2), _p(V), _p(asum), _stream())
+
+
+def nextvlad_aggregate_packed_bwd(a, xe, row_off, B, T, G, K, D, R, max_k, c2, dV, da, dxe, ws=None):
+    """nextvlad_aggregate_bwd over packed rows: the R live rows of da and dxe are written, nothing beyond them."""
+    assert row_off.dtype == torch.int32 and row_off.numel() == B + 1
+    assert a.numel() >= R * G * K and xe.numel() >= R * G * D and da.numel() >= R * G * K and dxe.numel() >= R * G * D and dV.numel() >= B * K * D
+    if ws is None:
+        ws = torch.empty(nextvlad_aggregate_bwd_ws(B, K, D), dtype=F32, device=da.device)
+    _lib.call("evc_nextvlad_aggregate_packed_bwd", _p(a), _p(xe), _p(row_off), B, T, G, K, D, R, max_k, _p(c2), _p(dV), _p(da), _p(dxe), _p(ws),
+              ws.numel(), _stream())
+
+
 def nextvlad_normalize_fwd(V, B, K, D, U, norms):
     _lib.call("evc_nextvlad_normalize_fwd", _p(V), B, K, D, _p(U), _p(norms), _stream())
 

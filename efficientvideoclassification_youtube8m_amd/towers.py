@@ -672,6 +672,23 @@ class NetVladTower(TowerBase):
         return self.moe.pred
 
 
+def check_nextvlad_frames(frames, every_n, max_frames, model=None, world=1, precision="bf16"):
+    """The combinations --nextvlad_frames / --every_n refuse, as ValueErrors that name the flags; touches no device."""
+    if frames not in NeXtVladTower.FRAME_MODES:
+        raise ValueError("--nextvlad_frames %r: one of %s" % (frames, "|".join(NeXtVladTower.FRAME_MODES)))
+    if frames != "grid":
+        return
+    if model is not None and model != "NeXtVLADModel":
+        raise ValueError("--nextvlad_frames grid is built for --model NeXtVLADModel, not %s" % model)
+    if every_n < 1 or every_n > max_frames:
+        raise ValueError("--nextvlad_frames grid: --every_n %d must lie in 1 .. --max_num_frames %d" % (every_n, max_frames))
+    if world > 1:
+        raise ValueError("--nextvlad_frames grid refuses a process group of %d ranks: ragged ranks hold different row counts and the "
+                         "batch-norm statistics assume equal ones; data parallelism is not built for this mode" % world)
+    if precision != "bf16":
+        raise ValueError("--nextvlad_frames grid: --precision %s is refused, the NeXtVLAD tower has no such forward mode (bf16 only)" % precision)
+
+
 class NeXtVladTower(TowerBase):
     """NeXtVLAD aggregation tower (Lin, Xiao, Fan 2018) - an EXTENSION: the reference ships NeXtVLADModel as an empty stub
     (cs/frame_level_models.py:349-355), so there is no reference math; the binding definition is DESIGN.md 7.12, restated in
@@ -681,9 +698,14 @@ class NeXtVladTower(TowerBase):
     Two stated deviations from the paper's code: relu6 where it has relu (the fused batch-norm tail knows relu6 only) and no
     dropout before the hidden layer.  GEMM-shaped parts on the library's NT / TN kernels (bf16 operands, f32 accumulation), the
     f32 pieces in csrc/evc_nextvlad.hip.  V / U / Y and vlad_bn are kept cluster-major [K][D]; the TF order d*K + k of
-    vlad_bn/* and of hidden1_weights' rows is restored in state_dict()."""
+    vlad_bn/* and of hidden1_weights' rows is restored in state_dict().
+
+    frames="grid" (DESIGN.md 7.13): instead of S drawn frames, video b contributes the frames j * every_n < min(n_b, T) - every real
+    frame at every_n = 1, the fewer-frames student's grid above - as a ragged list of rows packed back to back (ops.GridPlan);
+    padding frames are never computed.  Same weights and checkpoint names: a tower of either mode loads the other's checkpoint."""
 
     PRECISIONS = ("bf16",)             # no split-bf16 forward (set_precision refuses anything else)
+    FRAME_MODES = ("sampled", "grid")
 
     EW, EB, AW, AB = "expansion_weights", "expansion_biases", "attention_weights", "attention_biases"
     CW, C2, HW, G1, G2 = "cluster_weights", "cluster_weights2", "hidden1_weights", "gating_weights_1", "gating_weights_2"
@@ -695,7 +717,12 @@ class NeXtVladTower(TowerBase):
 
     def __init__(self, batch_size, max_frames=300, feature_size=1152, vocab_size=4716, iterations=30, cluster_size=64,
                  hidden_size=1024, groups=8, expansion=2, gating_reduction=8, num_mixtures=2, device="cuda:0", training=True,
-                 scope="model", seed=0, process_group=None):
+                 scope="model", seed=0, process_group=None, frames="sampled", every_n=1):
+        world = 1
+        if process_group is not None and torch.distributed.is_available() and torch.distributed.is_initialized():
+            world = torch.distributed.get_world_size(process_group)
+        check_nextvlad_frames(frames, every_n, max_frames, world=world)          # (before the device is touched)
+        self.frames, self.every_n = frames, int(every_n)
         self.device, self.training, self.scope, self.pg = torch.device(device), training, scope, process_group
         self.T, self.F, self.V, self.S = max_frames, feature_size, vocab_size, iterations
         self.Kc, self.Hd, self.Mx, self.G = cluster_size, hidden_size, num_mixtures, groups
@@ -720,9 +747,9 @@ class NeXtVladTower(TowerBase):
             raise ValueError("groups=%d: the attention product holds at most %d groups" % (G, self.AP))
         if K > 1024:
             raise ValueError("cluster_size=%d: the assignment kernel holds at most 1024 clusters" % K)
-        if iterations > 64:
+        if frames == "sampled" and iterations > 64:                  # (grid mode does not read iterations)
             raise ValueError("iterations=%d: the aggregation kernels hold at most 64 sampled frames per video" % iterations)
-        if iterations * G > 1024:
+        if frames == "sampled" and iterations * G > 1024:
             raise ValueError("iterations x groups = %d: the aggregation kernels hold at most 1024 (frame, group) pairs per video" % (iterations * G))
         shapes = OrderedDict()
         shapes[self.EW] = (E, F)                                     # every 2-D weight is stored transposed [out][in]
@@ -797,16 +824,28 @@ class NeXtVladTower(TowerBase):
 
     def _alloc(self, B):
         dev, F, S, K, H, G, E, D, Hg, AP = self.device, self.F, self.S, self.Kc, self.Hd, self.G, self.E, self.D, self.Hg, self.AP
-        self.B, self.R = B, B * S
-        if self.training and self.R % 32:
-            raise ValueError("batch_size x iterations = %d must be a multiple of 32 (row count of the TN weight-gradient products)" % self.R)
-        R = self.R
+        grid = self.frames == "grid"
+        if grid:
+            # every row buffer once, for every video at full length; a batch uses its first R (Rp in the TN products) rows.
+            # The bf16 operands of the TN products start as zeros: their rows R .. Rp are zeroed again at every step.
+            self.B, self.R, self.Rp, self.plan = B, 0, 0, None
+            R = ops.grid_capacity(B, self.T, self.every_n)
+            self.row_off = torch.zeros(B + 1, dtype=torch.int32, device=dev)
+            self._row_off_host = [torch.zeros(B + 1, dtype=torch.int32).pin_memory() for _ in range(2)]
+            self._row_off_done = [None, None]
+            self._uploads = 0
+        else:
+            self.B, self.R = B, B * S
+            if self.training and self.R % 32:
+                raise ValueError("batch_size x iterations = %d must be a multiple of 32 (row count of the TN weight-gradient products)" % self.R)
+            R = self.R
         self.Bk = ops.round_up(B, 32)
         self.r = torch.empty((R, F), dtype=F32, device=dev)
-        self.idx = torch.empty((B, S), dtype=torch.int32, device=dev)
-        self.r_bf = torch.empty((R, F), dtype=BF16, device=dev)
+        if not grid:
+            self.idx = torch.empty((B, S), dtype=torch.int32, device=dev)
+        self.r_bf = torch.zeros((R, F), dtype=BF16, device=dev) if grid else torch.empty((R, F), dtype=BF16, device=dev)
         self.xe = torch.empty((R, E), dtype=F32, device=dev)
-        self.xe_bf = torch.empty((R, E), dtype=BF16, device=dev)
+        self.xe_bf = torch.zeros((R, E), dtype=BF16, device=dev) if grid else torch.empty((R, E), dtype=BF16, device=dev)
         self.attl = torch.empty((R, AP), dtype=F32, device=dev)      # attention logits, biases included (columns >= G: zeros)
         self.cbias = torch.empty((G * K,), dtype=F32, device=dev)    # be . Wc: what the expansion bias adds to every cluster logit
         self.abias = torch.empty((AP,), dtype=F32, device=dev)       # be . Wa + ba (entries >= G: zeros)
@@ -837,37 +876,73 @@ class NeXtVladTower(TowerBase):
             self.agg_ws = torch.empty(ops.nextvlad_aggregate_bwd_ws(B, K, D), dtype=F32, device=dev)
             self.da = torch.empty((R, G * K), dtype=F32, device=dev)
             self.dz = torch.empty((R, G * K), dtype=F32, device=dev)
-            self.dact_bf = torch.empty((R, G * K), dtype=BF16, device=dev)
+            self.dact_bf = torch.zeros((R, G * K), dtype=BF16, device=dev) if grid else torch.empty((R, G * K), dtype=BF16, device=dev)
             self.datt = torch.empty((R, G), dtype=F32, device=dev)
             self.datt_bf = torch.zeros((R, AP), dtype=BF16, device=dev)     # columns >= G stay zero
             self.dxe = torch.empty((R, E), dtype=F32, device=dev)
-            self.dxe_bf = torch.empty((R, E), dtype=BF16, device=dev)
+            self.dxe_bf = torch.zeros((R, E), dtype=BF16, device=dev) if grid else torch.empty((R, E), dtype=BF16, device=dev)
             self.colsum_ws = torch.empty(32 * E, dtype=F32, device=dev)    # partial rows of the two bias-gradient column sums
             self.dWa_pad = torch.empty((AP, E), dtype=F32, device=dev)      # the attention weight gradient on a whole tile of rows
 
-    def forward(self, x, num_frames, uniform, normalize=True, is_training=True):
-        """x [B,T,F] float32 or uint8 raw frames; uniform [B,S] f32 in [0,1): the frame-sampling draw."""
+    def _plan_rows(self, num_frames, num_frames_host):
+        """Grid mode: this batch's packed layout from the HOST frame counts (launch sizes and offsets without a device sync);
+        row_off goes up through one of two pinned buffers, reused only once its earlier copy has completed."""
+        if num_frames_host is None:
+            num_frames_host = num_frames.cpu().numpy()       # an explicit device sync: callers that have the counts on the host pass them
+        plan = ops.GridPlan(num_frames_host, self.every_n, self.T)
+        if plan.B != self.B:
+            raise ValueError("num_frames_host holds %d videos, the batch %d" % (plan.B, self.B))
+        if plan.R == 0:
+            raise ValueError("--nextvlad_frames grid: no video of the batch has a frame")
+        slot = self._uploads % 2
+        self._uploads += 1
+        if self._row_off_done[slot] is not None:
+            self._row_off_done[slot].synchronize()
+        self._row_off_host[slot].copy_(torch.from_numpy(plan.row_off))
+        self.row_off.copy_(self._row_off_host[slot], non_blocking=True)
+        ev = self._row_off_done[slot] = torch.cuda.Event()
+        ev.record()
+        self.plan, self.R, self.Rp = plan, plan.R, plan.Rp
+        return plan
+
+    def forward(self, x, num_frames, uniform=None, normalize=True, is_training=True, num_frames_host=None):
+        """x [B,T,F] float32 or uint8 raw frames; uniform [B,S] f32 in [0,1): the frame-sampling draw (sampled mode; not read
+        in grid mode, which takes num_frames_host, the frame counts on the host, instead)."""
         B = x.shape[0]
         if B != self.B:
             self._alloc(B)
-        F, S, K, H, R, G, E, D, Hg, AP = self.F, self.S, self.Kc, self.Hd, self.R, self.G, self.E, self.D, self.Hg, self.AP
-        st, bc, bv, bh, bg = self.store, self.bn_cl, self.bn_v, self.bn_h, self.bn_g
         if self.precision != "bf16":
             raise NotImplementedError("NeXtVladTower has no split-bf16 mode")
-        ops.sample_frames_gather(x, uniform, num_frames, self.r, self.idx, normalize=normalize)
-        ops.cast_bf16(self.r, self.r_bf)
+        grid = self.frames == "grid"
+        F, S, K, H, G, E, D, Hg, AP = self.F, self.S, self.Kc, self.Hd, self.G, self.E, self.D, self.Hg, self.AP
+        st, bc, bv, bh, bg = self.store, self.bn_cl, self.bn_v, self.bn_h, self.bn_g
+        if grid:
+            if x.shape[1] != self.T:
+                raise ValueError("the batch holds %d frames per video, the tower was built for max_frames=%d" % (x.shape[1], self.T))
+            plan = self._plan_rows(num_frames, num_frames_host)
+            R, Rp = plan.R, plan.Rp
+            ops.frames_gather_packed(x, num_frames, self.row_off, self.every_n, R, Rp, self.r, self.r_bf, normalize=normalize)
+        else:
+            R = self.R
+            ops.sample_frames_gather(x, uniform, num_frames, self.r, self.idx, normalize=normalize)
+            ops.cast_bf16(self.r, self.r_bf)
         ops.gemm_nt(self.r_bf, self.shadow_fwd[self.EW], R, E, F, self.xe, bias=st.p(self.EB))
         # The bf16 operand of the two logit products is xe - be: the bias is the same in every row, so rounding it into the operand
         # would spend bf16's 8 bits on a constant whose whole effect on a logit is the per-column constant be.W - that goes into the
         # products as their f32 bias instead (and cluster_bn removes it again in training).  xe itself stays f32 for the aggregation.
         ops.nextvlad_center_cast(self.xe, R, E, st.p(self.EB), self.xe_bf)
+        if grid and Rp > R:
+            self.xe_bf[R:Rp].zero_()                         # (a longer earlier batch leaves stale rows there)
         ops.nextvlad_bias_logits(st.p(self.EB), st.p(self.CW), G * K, E, self.cbias)
         ops.nextvlad_bias_logits(st.p(self.EB), st.p(self.AW), G, E, self.abias, add=st.p(self.AB))
         ops.gemm_nt(self.xe_bf, self.shadow_fwd[self.CW], R, G * K, E, self.act, bias=self.cbias)
         ops.gemm_nt(self.xe_bf, self.att_img, R, AP, E, self.attl, bias=self.abias)
         bc.stats(self.act, R, is_training)
         ops.nextvlad_assign_fwd(self.act, R, G, K, bc.mean, bc.var, bc.gamma(), bc.beta(), self.attl, self.a)
-        ops.nextvlad_aggregate_fwd(self.a, self.xe, B, S, G, K, D, st.p(self.C2), self.Vv, self.asum)
+        if grid:
+            ops.nextvlad_aggregate_packed_fwd(self.a, self.xe, self.row_off, B, self.T, G, K, D, R, plan.max_k, st.p(self.C2), self.Vv, self.asum)
+        else:
+            ops.nextvlad_aggregate_fwd(self.a, self.xe, B, S, G, K, D, st.p(self.C2), self.Vv, self.asum)
         ops.nextvlad_normalize_fwd(self.Vv, B, K, D, self.U, self.nrm)
         bv.stats(self.U, B, is_training)
         ops.bn_apply(self.U, B, K * D, bv.mean, bv.var, bv.gamma(), bv.beta(), False, y_bf16=self.Y_bf)
@@ -891,6 +966,8 @@ class NeXtVladTower(TowerBase):
         assert self.training and self._taped, "backward needs a training-mode forward"
         B, F, S, K, H, R, G, E, D, Hg, AP = self.B, self.F, self.S, self.Kc, self.Hd, self.R, self.G, self.E, self.D, self.Hg, self.AP
         st, bc = self.store, self.bn_cl
+        grid = self.frames == "grid"
+        Rp = self.Rp if grid else R                          # row count of the TN products (grid: rows R .. Rp of their operands are zeros)
         dout = self.moe.backward(dpred, weight_grads=moe_weight_grads)
         if on_moe_grads_ready is not None:
             on_moe_grads_ready()
@@ -912,22 +989,31 @@ class NeXtVladTower(TowerBase):
         self.bn_v.backward(self.U, self.dY, B, False, dx_f32=self.dU)
         ops.nextvlad_normalize_bwd(self.Vv, self.nrm, self.dU, B, K, D, self.dV)
         ops.netvlad_dcenters(self.asum, self.dV, B, K, D, st.g(self.C2))                 # the same sum as NetVLAD's centres
-        ops.nextvlad_aggregate_bwd(self.a, self.xe, B, S, G, K, D, st.p(self.C2), self.dV, self.da, self.dxe, ws=self.agg_ws)
+        if grid:
+            ops.nextvlad_aggregate_packed_bwd(self.a, self.xe, self.row_off, B, self.T, G, K, D, R, self.plan.max_k, st.p(self.C2), self.dV,
+                                              self.da, self.dxe, ws=self.agg_ws)
+        else:
+            ops.nextvlad_aggregate_bwd(self.a, self.xe, B, S, G, K, D, st.p(self.C2), self.dV, self.da, self.dxe, ws=self.agg_ws)
         ops.nextvlad_assign_bwd(self.act, R, G, K, bc.mean, bc.var, bc.gamma(), bc.beta(), self.attl, self.da, self.dz, self.datt,
                                 datt_logit_bf16=self.datt_bf)
         bc.backward(self.act, self.dz, R, False, dx_bf16=self.dact_bf)
+        if grid and Rp > R:
+            self.dact_bf[R:Rp].zero_()
+            self.datt_bf[R:Rp].zero_()
         # xe_bf is the CENTRED operand xe - be.  dWc = dact^T . xe = dact^T . (xe - be) + colsum(dact) (x) be, and the column sums of a
         # training-mode batch-norm's input gradient are zero: the product against the centred operand is the whole gradient.
-        ops.gemm_tn(self.dact_bf, self.xe_bf, G * K, E, R, st.g(self.CW))               # dWc^T [G*K][E]
+        ops.gemm_tn(self.dact_bf, self.xe_bf, G * K, E, Rp, st.g(self.CW))               # dWc^T [G*K][E]
         ops.gemm_nt(self.dact_bf, self.shadow_bwd[self.CW], R, E, G * K, self.dxe, accumulate=True)      # + dact . Wc^T
         # the attention logits have no batch-norm behind them: dWa = datt^T . (xe - be) + dba (x) be, dba = colsum(datt)
         ops.nextvlad_colsum(self.datt, R, G, st.g(self.AB), ws=self.colsum_ws)
-        ops.gemm_tn(self.datt_bf, self.xe_bf, AP, E, R, self.dWa_pad)                   # on a whole tile of rows, rows >= G are zero
+        ops.gemm_tn(self.datt_bf, self.xe_bf, AP, E, Rp, self.dWa_pad)                   # on a whole tile of rows, rows >= G are zero
         ops.nextvlad_wgrad_uncenter(self.dWa_pad, st.g(self.AB), st.p(self.EB), G, E, st.g(self.AW))
         ops.gemm_nt(self.datt_bf, self.shadow_bwd[self.AW], R, E, AP, self.dxe, accumulate=True)         # + datt . Wa^T
         ops.nextvlad_colsum(self.dxe, R, E, st.g(self.EB), ws=self.colsum_ws)
-        ops.cast_bf16(self.dxe, self.dxe_bf)
-        ops.gemm_tn(self.dxe_bf, self.r_bf, E, F, R, st.g(self.EW))                     # dWe^T [E][F]
+        ops.cast_bf16(self.dxe[:R], self.dxe_bf[:R])
+        if grid and Rp > R:
+            self.dxe_bf[R:Rp].zero_()
+        ops.gemm_tn(self.dxe_bf, self.r_bf, E, F, Rp, st.g(self.EW))                     # dWe^T [E][F]
         if on_stage is not None:
             on_stage(2)
 

@@ -41,7 +41,7 @@ import torch
 from . import eval_util, frame_level_models, losses, ops, readers, video_level_models
 from .distill import DistillGraph, EnsembleDistillGraph, OfflineDistillGraph, SerialStudentsGraph, SingleTowerGraph
 from .flags import FLAGS, GetListOfFeatureNamesAndSizes
-from .towers import DbofTower, LogisticTower, NetVladTower, NeXtVladTower
+from .towers import DbofTower, LogisticTower, NetVladTower, NeXtVladTower, check_nextvlad_frames
 
 NUM_CLASSES = 4716       # readers.YT8MFrameFeatureReader default num_classes (cs/readers.py:121)
 
@@ -465,7 +465,8 @@ def build_graph(model, label_loss_fn, feature_size, batch_size, every_n, device,
     if isinstance(model, frame_level_models.NeXtVLADModel):         # extension (the reference's class is an empty stub)
         tw = NeXtVladTower(batch_size, FLAGS.max_num_frames, feature_size, NUM_CLASSES, FLAGS.iterations, FLAGS.nextvlad_cluster_size,
                            FLAGS.nextvlad_hidden_size, FLAGS.nextvlad_groups, FLAGS.nextvlad_expansion, FLAGS.nextvlad_gating_reduction,
-                           FLAGS.moe_num_mixtures, device=device, process_group=process_group)
+                           FLAGS.moe_num_mixtures, device=device, process_group=process_group, frames=FLAGS.nextvlad_frames,
+                           every_n=every_n)
         _apply_precision(tw)
         return SingleTowerGraph(tw, **common)
     if isinstance(model, frame_level_models.FrameLevelLogisticModel):
@@ -556,8 +557,10 @@ def save_checkpoint(graph, train_dir, rank):
     if isinstance(graph, OfflineDistillGraph) and getattr(graph, "teacher_record", None):    # metadata: trained against these prediction files
         sd["distill_mode"], sd["distill_losses"] = "offline", ",".join(graph.offline_losses)
         sd["distill_teacher_files"] = graph.teacher_record
+    if getattr(getattr(graph, "tower", None), "frames", None) == "grid":      # metadata: the frames this tower was trained on (--nextvlad_frames grid)
+        sd["nextvlad_frames"], sd["every_n"] = "grid", graph.tower.every_n
     fn = getattr(graph, "label_loss", None)
-    if fn is not None and not losses.is_default(fn):             # metadata: the --label_loss these weights were trained on (the default: no key)
+    if fn is not None and not losses.is_default(fn):            # metadata: the --label_loss these weights were trained on (the default: no key)
         sd["label_loss"] = type(fn).__name__
     for tw in (getattr(graph, "teacher", None), getattr(graph, "student", None), getattr(graph, "tower", None)):
         if tw is not None:
@@ -626,6 +629,7 @@ def main(argv=None):
     multi = serial_students(finetune, world)
     serial = check_serial_flags(finetune, world, students=multi)
     check_label_loss(find_class_by_name(FLAGS.label_loss, [losses])(), finetune)
+    check_nextvlad_frames(FLAGS.nextvlad_frames, FLAGS.every_n, FLAGS.max_num_frames, model=FLAGS.model, world=world, precision=FLAGS.precision)
     ens_sds = None
     if ens:
         # the teachers' checkpoints on the host, and - on resume - the recorded list against the flags: all before the device is touched
@@ -714,6 +718,7 @@ def main(argv=None):
     is_multi = isinstance(graph, SerialStudentsGraph)
     is_ens = isinstance(graph, EnsembleDistillGraph)
     is_distill = isinstance(graph, DistillGraph) or is_multi or is_ens
+    is_grid = getattr(getattr(graph, "tower", None), "frames", None) == "grid"     # --nextvlad_frames grid: the packed rows are laid out from n_host
     steps_per_it = 2 if is_distill and not is_multi and graph.mode == "teacher_student" else 1
     copy_stream = torch.cuda.Stream(device=device)
     host_bufs = {}                       # pinned staging, two alternating sets (one may still be read while the next fills)
@@ -794,7 +799,7 @@ def main(argv=None):
         if tables is not None:      # the teacher files' lists of exactly these videos: pinned staging, non_blocking copies on this stream
             out = graph.step(q, labels, n, num_frames_host=n_host, teacher_lists=tables.gather_device(LAST_BATCH["ids"], device))
         else:
-            out = graph.step(q, labels, n, num_frames_host=n_host) if is_distill else graph.step(q, labels, n)    # uint8 features: Dequantize is fused into every input kernel
+            out = graph.step(q, labels, n, num_frames_host=n_host) if is_distill or is_grid else graph.step(q, labels, n)    # uint8 features: Dequantize is fused into every input kernel
         it += 1
         graph.last_batch_ids = LAST_BATCH["ids"]
         logging_step = it % max(1, FLAGS.log_every) == 0

@@ -868,6 +868,21 @@ int evc_nextvlad_aggregate_fwd(const float* a, const float* xe, int B, int S, in
  * (dc2 = evc_netvlad_dcenters(asum, dV, B, K, D): the same sum.) */
 int evc_nextvlad_aggregate_bwd(const float* a, const float* xe, int B, int S, int G, int K, int D, const float* c2, const float* dV,
                                float* da, float* dxe, float* ws, int64_t ws_floats, void* stream);
+/* Ragged videos: video b owns the frame rows row_off[b] .. row_off[b+1] (device int32 [B+1], k_b of them in
+ * time order, k_b = 0 allowed: V[b] = 0, asum[b] = 0) of a, xe, da and dxe; R = row_off[B], max_k = max_b k_b (the host knows both:
+ * they size the launches).  The same sums in the same per-element order as the fixed-length entries, so equal lengths give their
+ * bits.  Needs K <= 1024, D % 4 == 0, B <= 65535, max_k <= T, max_k <= R <= B * max_k; ws as evc_nextvlad_aggregate_bwd. */
+int evc_nextvlad_aggregate_packed_fwd(const float* a, const float* xe, const int32_t* row_off, int B, int T, int G, int K, int D, int R,
+                                      int max_k, const float* c2, float* V, float* asum, void* stream);
+int evc_nextvlad_aggregate_packed_bwd(const float* a, const float* xe, const int32_t* row_off, int B, int T, int G, int K, int D, int R,
+                                      int max_k, const float* c2, const float* dV, float* da, float* dxe, float* ws, int64_t ws_floats,
+                                      void* stream);
+/* out[row_off[b] + j][:] = frame j * every_n of video b (x f32 or x_u8 [B][T][F], exactly one non-NULL; uint8 is dequantised as
+ * q * 4/255 + 4/512 - 2, a uint8 frame >= num_frames[b] reads as zeros), l2-normalised on request: the arithmetic of
+ * evc_sample_frames_gather, bit for bit.  Rows R .. Rp (Rp - R < 32) are written as zeros.  out_bf16 (may be NULL): the same rows
+ * as bf16.  F % 4 == 0. */
+int evc_frames_gather_packed(const float* x, const uint8_t* x_u8, const int32_t* num_frames, const int32_t* row_off, int B, int T, int F,
+                             int every_n, int R, int Rp, int normalize, float* out, evc_bf16* out_bf16, void* stream);
 /* U[b][k][:] = V[b][k][:] / n, n = norms[b][k] = max(|V[b][k][:]|, 1e-12);  dV = (dU - U (U . dU)) / n. */
 int evc_nextvlad_normalize_fwd(const float* V, int B, int K, int D, float* U, float* norms, void* stream);
 int evc_nextvlad_normalize_bwd(const float* V, const float* norms, const float* dU, int B, int K, int D, float* dV, void* stream);
