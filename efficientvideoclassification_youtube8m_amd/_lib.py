@@ -122,12 +122,14 @@ SIGNATURES = {
     "evc_nextvlad_aggregate_fwd": [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp],
     "evc_nextvlad_aggregate_bwd": [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp],
     "evc_nextvlad_aggregate_packed_fwd": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp],
+    "evc_nextvlad_aggregate_packed_fwd_mfma": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp],
     "evc_nextvlad_aggregate_packed_bwd": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp],
     "evc_frames_gather_packed": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp],
     "evc_nextvlad_normalize_fwd": [vp, i32, i32, i32, vp, vp, vp],
     "evc_nextvlad_normalize_bwd": [vp, vp, vp, i32, i32, i32, vp, vp],
     "evc_nextvlad_gate_fwd": [vp, vp, i64, vp, vp],
     "evc_nextvlad_gate_bwd": [vp, vp, vp, i64, vp, vp, vp, vp],
+    "evc_nextvlad_gate_bwd_add": [vp, vp, vp, vp, i64, vp, vp, vp, vp],
     "evc_nextvlad_colsum": [vp, i64, i32, i32, vp, vp, i64, vp],
     "evc_nextvlad_center_cast": [vp, i32, i32, vp, vp, vp],
     "evc_nextvlad_bias_logits": [vp, vp, i32, i32, vp, vp, i32, vp],

@@ -6,8 +6,9 @@
 //   evc_nextvlad_assign_fwd/bwd      a[r,g,k] = softmax_k(cluster_bn(act)[r,g,:])[k] * sigmoid(att_logit[r,g]) and its reverse mode
 //   evc_nextvlad_aggregate_fwd/bwd   V[b,k,:] = sum_{s,g} a[b,s,g,k] * xe[b,s,g*D:(g+1)*D] - asum[b,k] * c2[k,:]; da, dxe from dV
 //   evc_nextvlad_aggregate_packed_fwd/bwd, evc_frames_gather_packed   the same over a ragged, packed list of frames per video (7.13)
+//   evc_nextvlad_aggregate_packed_fwd_mfma   the packed forward on the f32 matrix cores, for forward-only towers: the same bits (7.14)
 //   evc_nextvlad_normalize_fwd/bwd   U[b,k,:] = V[b,k,:] / max(|V[b,k,:]|, 1e-12)
-//   evc_nextvlad_gate_fwd/bwd        out = h * sigmoid(gl) (context gating)
+//   evc_nextvlad_gate_fwd/bwd        out = h * sigmoid(gl) (context gating); _bwd_add: with a second gradient on out (7.14)
 //   evc_nextvlad_colsum              out[c] = sum_r x[r][c] in a fixed order (the two bias gradients)
 //   evc_nextvlad_center_cast         bf16(xe - be): the centred operand of the cluster / attention products; with it
 //   evc_nextvlad_bias_logits         be.W in f32 (the products' bias) and evc_nextvlad_wgrad_uncenter (the rank-one gradient term)
@@ -389,6 +390,109 @@ extern "C" int evc_nextvlad_aggregate_packed_fwd(const float* a, const float* xe
   return nx_launch<0, true>(p, B, stream);
 }
 
+// ---- the packed forward aggregation on the f32 matrix cores: V_b = A_b^T X_b - asum_b (x) c2 with
+// v_mfma_f32_32x32x2_f32, which is bit for bit a k-ordered fmaf chain - the chain nx_product_kernel<0, true> computes with
+// v_pk_fma_f32 - so this entry gives the bits of evc_nextvlad_aggregate_packed_fwd.  Forward only, mode 0 only (the frozen tower).
+// grid (n tiles * m tiles, B), 4 waves: a workgroup owns 128 clusters x 96 columns, wave w the clusters m0 = 32 w .. 32 w + 32 of it
+// and three 32 x 32 accumulators (the columns n0, n0 + 32, n0 + 64).  Both operands are read from global memory in the layout the
+// instruction wants - lane (i = lane & 31, kk = lane >> 5) holds a[pair l + kk][m0 + i] and xe[pair l + kk][n0 + 32 c + i], 32
+// consecutive floats per half-wave - so there is no LDS, no transpose and no barrier; the loads of the next NXM_U MFMA steps (2 NXM_U
+// pairs) are issued before the MFMAs of the current ones.  Every element is ONE chain over l = 0 .. L_b - 1 ascending from a zero
+// accumulator: successive MFMAs take (l, l + 1) as k = 0, 1 on the same accumulator, nothing is split over waves or workgroups.
+// Cluster rows >= K, columns >= D and the slot l + kk >= L_b are zeros by predicate in the operand (never loaded: no address at or
+// beyond the video's last pair is formed into a load, and 0 * NaN cannot enter).  asum[k]: lanes 0 .. 31 add a[l][k], then a[l+1][k]
+// (fetched from lane + 32), the sequential sum of the existing entry; the epilogue is fmaf(-asum, c2, acc).
+// gfx950: 66 VGPRs + 48 AGPRs (the three accumulators), 0 bytes of LDS, no scratch, no atomics (hipcc -O3).
+typedef float nx_f32x16 __attribute__((ext_vector_type(16)));
+static constexpr int NXM_U = 4;                  // MFMA steps (pairs of l) per load batch
+static constexpr int NXM_MT = 128, NXM_NT = 96;  // workgroup tile: clusters x columns
+__global__ __launch_bounds__(256) void nx_aggregate_mfma_kernel(const float* __restrict__ a, const float* __restrict__ xe,
+                                                                const int* __restrict__ row_off, int G, int K, int D, int ntiles,
+                                                                const float* __restrict__ c2, float* __restrict__ V,
+                                                                float* __restrict__ asum) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int b = blockIdx.y;
+  const int ntile = blockIdx.x % ntiles, mtile = blockIdx.x / ntiles;
+  const int m0 = mtile * NXM_MT + wave * 32;
+  if (m0 >= K) return;                           // (no barrier in this kernel)
+  const int n0 = ntile * NXM_NT;
+  const int i = lane & 31, kk = lane >> 5;
+  const int r0 = row_off[b];
+  const long pair0 = (long)r0 * G;
+  const int L = (row_off[b + 1] - r0) * G;
+  const int ncb = min(3, (D - n0 + 31) / 32);    // column blocks of this workgroup that hold a column < D (>= 1)
+  const bool mok = m0 + i < K;
+  const bool nok[3] = {n0 + i < D, n0 + 32 + i < D, n0 + 64 + i < D};
+  const float* __restrict__ ap = a + (pair0 + kk) * K + m0 + i;
+  const float* __restrict__ xp = xe + (pair0 + kk) * D + n0 + i;
+  nx_f32x16 acc[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[c][r] = 0.f;
+  float s = 0.f;
+  float ca[NXM_U], cx[NXM_U][3], na[NXM_U], nx[NXM_U][3];
+  auto load = [&](int l0, float (&va)[NXM_U], float (&vx)[NXM_U][3]) {
+#pragma unroll
+    for (int u = 0; u < NXM_U; ++u) {
+      const int l = l0 + 2 * u;
+      const bool lok = l + kk < L;
+      va[u] = (lok && mok) ? ap[(long)l * K] : 0.f;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) vx[u][c] = (lok && nok[c]) ? xp[(long)l * D + 32 * c] : 0.f;
+    }
+  };
+  load(0, ca, cx);
+  for (int l0 = 0; l0 < L; l0 += 2 * NXM_U) {
+    load(l0 + 2 * NXM_U, na, nx);                // (all zeros, nothing loaded, past the video's last pair)
+#pragma unroll
+    for (int u = 0; u < NXM_U; ++u) {
+      if (l0 + 2 * u < L) {                      // uniform over the wave
+        const float other = __shfl_xor(ca[u], 32);
+        s += ca[u];                              // lanes < 32: a[l][m0 + i], then a[l + 1][m0 + i] (0 when l + 1 = L)
+        s += other;
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+          if (c < ncb) acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(ca[u], cx[u][c], acc[c], 0, 0, 0);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < NXM_U; ++u) {
+      ca[u] = na[u];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) cx[u][c] = nx[u][c];
+    }
+  }
+  if (ntile == 0 && kk == 0 && mok) asum[(long)b * K + m0 + i] = s;
+  // C/D map of the 32 x 32 shapes: register r of lane (i, kk) is row (r & 3) + 8 (r >> 2) + 4 kk, column i
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int row = (r & 3) + 8 * (r >> 2) + 4 * kk;
+    const float sv = __shfl(s, row);             // asum of cluster m0 + row (lanes 0 .. 31 hold the sums)
+    const int m = m0 + row;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const int n = n0 + 32 * c + i;
+      if (c < ncb && m < K && n < D) V[((long)b * K + m) * D + n] = fmaf(-sv, c2[(long)m * D + n], acc[c][r]);
+    }
+  }
+}
+
+extern "C" int evc_nextvlad_aggregate_packed_fwd_mfma(const float* a, const float* xe, const int32_t* row_off, int B, int T, int G, int K,
+                                                      int D, int R, int max_k, const float* c2, float* V, float* asum, void* stream) {
+  EVC_REQUIRE(NX_PACKED_SHAPE_OK, EVC_ERR_BAD_SHAPE,
+              "evc_nextvlad_aggregate_packed_fwd_mfma: needs K <= 1024, D %% 4 == 0, B <= 65535, max_k <= T, max_k <= R <= B * max_k "
+              "(B=%d T=%d G=%d K=%d D=%d R=%d max_k=%d)", B, T, G, K, D, R, max_k);
+  EVC_REQUIRE(a && xe && row_off && c2 && V && asum, EVC_ERR_BAD_ARG, "evc_nextvlad_aggregate_packed_fwd_mfma: NULL operand");
+  EVC_REQUIRE(nx_aligned16(a) && nx_aligned16(xe) && nx_aligned16(c2) && nx_aligned16(V), EVC_ERR_BAD_ALIGN,
+              "evc_nextvlad_aggregate_packed_fwd_mfma: a, xe, c2 and V must be 16-byte aligned (as for evc_nextvlad_aggregate_packed_fwd)");
+  const int ntiles = ceil_div(D, NXM_NT), mtiles = ceil_div(K, NXM_MT);
+  hipLaunchKernelGGL(nx_aggregate_mfma_kernel, dim3(ntiles * mtiles, B), dim3(256), 0, (hipStream_t)stream, a, xe, row_off, G, K, D, ntiles, c2,
+                     V, asum);
+  EVC_LAUNCH_CHECK();
+  return EVC_OK;
+}
+
 extern "C" int evc_nextvlad_aggregate_packed_bwd(const float* a, const float* xe, const int32_t* row_off, int B, int T, int G, int K, int D,
                                                  int R, int max_k, const float* c2, const float* dV, float* da, float* dxe, float* ws,
                                                  int64_t ws_floats, void* stream) {
@@ -565,6 +669,32 @@ extern "C" int evc_nextvlad_gate_bwd(const float* h, const float* gl, const floa
   EVC_REQUIRE(n > 0, EVC_ERR_BAD_SHAPE, "evc_nextvlad_gate_bwd: bad shape (n=%ld)", (long)n);
   EVC_REQUIRE(h && gl && dout && dh && (dgl || dgl_bf16), EVC_ERR_BAD_ARG, "evc_nextvlad_gate_bwd: NULL operand (dgl and dgl_bf16 may not both be NULL)");
   hipLaunchKernelGGL(nextvlad_gate_bwd_kernel, dim3(nx_grid(n)), dim3(256), 0, (hipStream_t)stream, h, gl, dout, (long)n, dh, dgl, (bf16_t*)dgl_bf16);
+  EVC_LAUNCH_CHECK();
+  return EVC_OK;
+}
+
+// the same with a second incoming gradient (serial distillation: dL_REP/d out joins the MoE head's dout): d = dout + dout2, one f32
+// add in that order, then the formulas above unchanged.  dout2 == NULL: the bits of evc_nextvlad_gate_bwd.
+__global__ void nextvlad_gate_bwd_add_kernel(const float* __restrict__ h, const float* __restrict__ gl, const float* __restrict__ dout,
+                                             const float* __restrict__ dout2, long n, float* __restrict__ dh, float* __restrict__ dgl,
+                                             bf16_t* __restrict__ dgl_bf) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const float g = sigmoidf_(gl[i]);
+    float d = dout[i];
+    if (dout2) d = __fadd_rn(d, dout2[i]);
+    dh[i] = d * g;
+    const float dl = d * h[i] * g * (1.0f - g);
+    if (dgl) dgl[i] = dl;
+    if (dgl_bf) dgl_bf[i] = f32_to_bf16(dl);
+  }
+}
+extern "C" int evc_nextvlad_gate_bwd_add(const float* h, const float* gl, const float* dout, const float* dout2, int64_t n, float* dh,
+                                         float* dgl, evc_bf16* dgl_bf16, void* stream) {
+  EVC_REQUIRE(n > 0, EVC_ERR_BAD_SHAPE, "evc_nextvlad_gate_bwd_add: bad shape (n=%ld)", (long)n);
+  EVC_REQUIRE(h && gl && dout && dh && (dgl || dgl_bf16), EVC_ERR_BAD_ARG,
+              "evc_nextvlad_gate_bwd_add: NULL operand (dout2 may be NULL; dgl and dgl_bf16 may not both be)");
+  hipLaunchKernelGGL(nextvlad_gate_bwd_add_kernel, dim3(nx_grid(n)), dim3(256), 0, (hipStream_t)stream, h, gl, dout, dout2, (long)n, dh, dgl,
+                     (bf16_t*)dgl_bf16);
   EVC_LAUNCH_CHECK();
   return EVC_OK;
 }

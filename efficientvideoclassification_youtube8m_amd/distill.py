@@ -1600,3 +1600,128 @@ class SingleTowerGraph(_StepGraph):
                 tw.apply_gradients(lr, self.clip, l2c)
             self.global_step += 1
         return {"predictions": pred, "loss": self.losses[0], "global_step": self.global_step}
+
+
+def _world_of(process_group):
+    """Ranks of a process group without touching a device (None: the default group when one is initialised, else 1)."""
+    if process_group is not None and hasattr(process_group, "size"):
+        return int(process_group.size())
+    if torch.distributed.is_available() and torch.distributed.is_initialized():
+        return int(torch.distributed.get_world_size(process_group))
+    return 1
+
+
+class NeXtVladDistillGraph(_StepGraph):
+    """Serial distillation for the NeXtVLAD family: a grid student (frames j * every_n of every video, scope
+    'model_student') against a FROZEN grid teacher (every teacher_every_n-th real frame, scope 'model': forward only, batch norms on the
+    checkpoint's moving statistics, no gradient store / moments / tape, never written).  One step on one stream: teacher forward,
+    student forward, the loss section of DistillGraph's mode 'serial' (ops.distill_losses on the towers' gated hidden vectors and
+    predictions, the same scales), the student's backward with dL_REP/dstate joining the MoE head's gradient at `out`, and the update
+    exactly as SingleTowerGraph.step performs it; global_step += 1.  Reporting follows DistillGraph's serial mode (`out` keys,
+    LOSS_SLOTS, loss_report), so train's loop needs no special case.  Every refusal is a ValueError before the device is touched."""
+
+    LOSS_SLOTS = DistillGraph.LOSS_SLOTS
+    DISTILL_LOSSES = DistillGraph.DISTILL_LOSSES
+    mode = "serial"
+    student_sampling = "uniform"                 # (the grid is the uniform sub-sampling of the real frames; checkpoint metadata)
+    dp = False
+
+    def __init__(self, batch_size, every_n=10, teacher_every_n=1, feature_size=1152, vocab_size=4716, max_frames=300, cluster_size=64,
+                 hidden_size=1024, groups=8, expansion=2, gating_reduction=8, num_mixtures=2, base_learning_rate=0.001,
+                 learning_rate_decay=1.0, learning_rate_decay_examples=4000000, regularization_penalty=2.0, clip_gradient_norm=1.0,
+                 count_rep_twice=True, device="cuda:0", seed=7, process_group=None, precision="bf16", distill_losses=DISTILL_LOSSES,
+                 label_loss=None):
+        from .towers import NeXtVladTower, check_nextvlad_frames
+        self.world = _world_of(process_group)
+        if self.world > 1:
+            raise ValueError("NeXtVladDistillGraph is not data parallel (process group of %d ranks): train the student against the "
+                             "frozen teacher on one device" % self.world)
+        self.label_loss = _resolve_label_loss(label_loss, vocab_size)
+        if not losses_mod.is_default(self.label_loss):
+            raise ValueError("NeXtVladDistillGraph has CrossEntropyLoss built into its loss section (evc_distill_losses), not %s"
+                             % type(self.label_loss).__name__)
+        if precision != "bf16":
+            raise ValueError("NeXtVladDistillGraph: precision %r is refused, the NeXtVLAD tower has no such forward mode (bf16 only)" % (precision,))
+        self.distill_losses = check_distill_losses(distill_losses)
+        for n in (every_n, teacher_every_n):     # (ValueError naming --every_n and its range)
+            check_nextvlad_frames("grid", n, max_frames, world=self.world, precision=precision)
+        self.B, self.every_n, self.teacher_every_n, self.precision = batch_size, int(every_n), int(teacher_every_n), precision
+        self.lr0, self.lr_decay, self.lr_decay_examples = base_learning_rate, learning_rate_decay, learning_rate_decay_examples
+        self.reg_pen, self.clip, self.pg = regularization_penalty, clip_gradient_norm, process_group
+        self.rep_w = 2.0 if count_rep_twice else 1.0
+        self.device = torch.device(device)
+        self.global_step = 0
+        sizes = (batch_size, max_frames, feature_size, vocab_size, 30, cluster_size, hidden_size, groups, expansion, gating_reduction,
+                 num_mixtures)
+        self.teacher = NeXtVladTower(*sizes, device=device, training=False, scope="model", seed=seed, frames="grid",
+                                     every_n=self.teacher_every_n)
+        self.student = NeXtVladTower(*sizes, device=device, training=True, scope="model_student", seed=seed + 1, frames="grid",
+                                     every_n=self.every_n)
+        self.moe = self.student.moe
+        self.fused_moe_update = True
+        self.losses = torch.zeros(8, dtype=F32, device=self.device)
+        self._dp_s = self._ds_s = None
+
+    def _towers(self):
+        return [self.teacher, self.student]
+
+    def consolidate(self):
+        """Nothing is sharded on one rank (kept for train's checkpoint path)."""
+
+    def state_dict(self):
+        """Both scopes: model/* (the frozen teacher, the bits it was loaded with) and model_student/*."""
+        out = self.teacher.state_dict()
+        out.update(self.student.state_dict())
+        return out
+
+    def label_grads(self):
+        """The student's dL/dpred buffer of the last step (its L_CE and L_PRED gradient), as DistillGraph names it."""
+        return {} if self._dp_s is None else {"student": self._dp_s}
+
+    def state_grad(self):
+        """The dL_REP/dstate buffer of the last step (None before the first).  For tests and debugging."""
+        return self._ds_s
+
+    @property
+    def losses_for_report(self):
+        return self.losses
+
+    def loss_report(self, losses=None):
+        v = (self.losses if losses is None else losses).tolist()
+        return {k: v[i] for i, k in enumerate(self.LOSS_SLOTS)}
+
+    def step(self, x_raw, labels_u8, num_frames, apply=True, num_frames_host=None):
+        """x_raw [B,T,F] uint8 or float32, labels_u8 [B,V], num_frames [B] int32 (num_frames_host: the same counts on the host - both
+        towers lay their packed rows out from them; read back from the device when not given).  All launches on the caller's stream."""
+        B, V = labels_u8.shape
+        tt, ts = self.teacher, self.student
+        if num_frames_host is None:
+            num_frames_host = num_frames.cpu().numpy()
+        if self._dp_s is None or self._dp_s.shape[0] != B:
+            self._dp_s = torch.empty((B, V), dtype=F32, device=self.device)
+            self._ds_s = torch.empty((B, ts.Hd), dtype=F32, device=self.device)
+        t_pred = tt.forward(x_raw, num_frames, num_frames_host=num_frames_host, is_training=False)
+        s_pred = ts.forward(x_raw, num_frames, num_frames_host=num_frames_host)
+        on = self.distill_losses
+        self.losses.zero_()
+        ops.distill_losses(t_pred, tt.rowsum, s_pred, ts.rowsum, labels_u8, tt.state, ts.state, self.losses, self._dp_s, self._ds_s,
+                           g_ce=(1.0 / B) if "ce" in on else 0.0, g_kl=1.0 if "pred" in on else 0.0,
+                           g_rep=self.rep_w if "rep" in on else 0.0)
+        # the update of SingleTowerGraph.step on one rank: the MoE head's two matrices through the fused clip + Adam pass whenever
+        # the step applies (their gradient recomputed from its rank-B factors), the rest through clip_by_norm + TF-Adam
+        fuse = (apply and self.fused_moe_update and self.moe.can_fuse_update() and self.moe.prefer_fused_update(False)
+                and ts.precision == "bf16")
+        fused_names = (self.moe.GATES, self.moe.EXPERTS, self.moe.EBIAS) if fuse else ()
+        ts.backward(self._dp_s, moe_weight_grads=not fuse, dstate=self._ds_s)
+        if apply:
+            lr, l2c = self._lr_l2c(B)
+            if fuse:
+                ts.begin_update()
+                self.moe.fused_update(ts.adam_lr_t(lr), self.clip, l2c, dp=None)
+                ts.apply_group([k for k in ts.names if k not in fused_names], lr, self.clip, l2c)
+            else:
+                ts.apply_gradients(lr, self.clip, l2c)
+            self.global_step += 1
+        return dict(predictions=t_pred, teacher_state=tt.state, loss=self.losses[0], student_predictions=s_pred, student_state=ts.state,
+                    num_frames_student=torch.from_numpy(ts.plan.k), student_loss_state=self.losses[1], pred_loss=self.losses[2],
+                    student_label_loss=self.losses[3], global_step=self.global_step)

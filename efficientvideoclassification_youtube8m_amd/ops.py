@@ -1449,6 +1449,13 @@ def nextvlad_aggregate_packed_fwd(a, xe, row_off, B, T, G, K, D, R, max_k, c2, V
     _lib.call("evc_nextvlad_aggregate_packed_fwd", _p(a), _p(xe), _p(row_off), B, T, G, K, D, R, max_k, _p(c2), _p(V), _p(asum), _stream())
 
 
+def nextvlad_aggregate_packed_fwd_mfma(a, xe, row_off, B, T, G, K, D, R, max_k, c2, V, asum):
+    """nextvlad_aggregate_packed_fwd on the f32 matrix cores: same arguments, same bits; forward-only callers."""
+    assert row_off.dtype == torch.int32 and row_off.numel() == B + 1
+    assert a.numel() >= R * G * K and xe.numel() >= R * G * D and V.numel() >= B * K * D and asum.numel() >= B * K
+    _lib.call("evc_nextvlad_aggregate_packed_fwd_mfma", _p(a), _p(xe), _p(row_off), B, T, G, K, D, R, max_k, _p(c2), _p(V), _p(asum), _stream())
+
+
 def nextvlad_aggregate_packed_bwd(a, xe, row_off, B, T, G, K, D, R, max_k, c2, dV, da, dxe, ws=None):
     """nextvlad_aggregate_bwd over packed rows: the R live rows of da and dxe are written, nothing beyond them."""
     assert row_off.dtype == torch.int32 and row_off.numel() == B + 1
@@ -1473,6 +1480,12 @@ def nextvlad_gate_fwd(h, gl, out):
 
 def nextvlad_gate_bwd(h, gl, dout, dh, dgl=None, dgl_bf16=None):
     _lib.call("evc_nextvlad_gate_bwd", _p(h), _p(gl), _p(dout), h.numel(), _p(dh), _p(dgl), _p(dgl_bf16), _stream())
+
+
+def nextvlad_gate_bwd_add(h, gl, dout, dout2, dh, dgl=None, dgl_bf16=None):
+    """nextvlad_gate_bwd on the incoming gradient dout + dout2 (one f32 add; dout2 None: nextvlad_gate_bwd's bits)."""
+    assert dout2 is None or (dout2.numel() == h.numel() and dout2.dtype == F32 and dout2.is_contiguous())
+    _lib.call("evc_nextvlad_gate_bwd_add", _p(h), _p(gl), _p(dout), _p(dout2), h.numel(), _p(dh), _p(dgl), _p(dgl_bf16), _stream())
 
 
 def nextvlad_colsum(x, R, C, out, ws=None):

@@ -702,7 +702,12 @@ class NeXtVladTower(TowerBase):
 
     frames="grid" (DESIGN.md 7.13): instead of S drawn frames, video b contributes the frames j * every_n < min(n_b, T) - every real
     frame at every_n = 1, the fewer-frames student's grid above - as a ragged list of rows packed back to back (ops.GridPlan);
-    padding frames are never computed.  Same weights and checkpoint names: a tower of either mode loads the other's checkpoint."""
+    padding frames are never computed.  Same weights and checkpoint names: a tower of either mode loads the other's checkpoint.
+
+    Distillation: `state` is the gated hidden vector `out` [B, H], the representation L_REP is taken on, and
+    backward(dpred, dstate=...) adds a gradient on it to the MoE head's.  A forward-only grid tower (training=False: the frozen
+    teacher) keeps no gradient store or moments and aggregates on the f32 matrix cores (evc_nextvlad_aggregate_packed_fwd_mfma, the
+    bits of the entry the training towers call)."""
 
     PRECISIONS = ("bf16",)             # no split-bf16 forward (set_precision refuses anything else)
     FRAME_MODES = ("sampled", "grid")
@@ -751,21 +756,7 @@ class NeXtVladTower(TowerBase):
             raise ValueError("iterations=%d: the aggregation kernels hold at most 64 sampled frames per video" % iterations)
         if frames == "sampled" and iterations * G > 1024:
             raise ValueError("iterations x groups = %d: the aggregation kernels hold at most 1024 (frame, group) pairs per video" % (iterations * G))
-        shapes = OrderedDict()
-        shapes[self.EW] = (E, F)                                     # every 2-D weight is stored transposed [out][in]
-        shapes[self.EB] = (E,)
-        shapes[self.AW] = (G, E)
-        shapes[self.AB] = (G,)
-        shapes[self.CW] = (G * K, E)
-        shapes.update(BatchNorm.shapes("cluster_bn", G * K))
-        shapes[self.C2] = (K, D)                                     # centres [K][D] (tf: [D, K])
-        shapes.update(BatchNorm.shapes("vlad_bn", K * D))            # cluster-major k*D + d
-        shapes[self.HW] = (H, K * D)                                 # columns cluster-major
-        shapes.update(BatchNorm.shapes("hidden1_bn", H))
-        shapes[self.G1] = (Hg, H)
-        shapes.update(BatchNorm.shapes("gating_bn", Hg))
-        shapes[self.G2] = (H, Hg)
-        shapes.update(MoeHead.shapes(H, vocab_size, num_mixtures))
+        shapes = self.variable_shapes(F, vocab_size, K, H, G, expansion, gating_reduction, num_mixtures)
         self.buffers = OrderedDict()
         self._setup_store(shapes)
         # the attention product has N = G columns, below the GEMM tiles' width: its forward operand is the first G rows of a
@@ -793,7 +784,44 @@ class NeXtVladTower(TowerBase):
             elif k.endswith("/gamma"):
                 p.fill_(1.0)
         self.refresh_shadows()
+        if not training and frames == "grid":
+            self.store.drop_training_state()                         # forward only: the masters alone, as the frozen H-LSTM teacher
         self._alloc(batch_size)
+
+    @classmethod
+    def variable_shapes(cls, feature_size, vocab_size, cluster_size, hidden_size, groups, expansion, gating_reduction, num_mixtures):
+        """The trainable variables and their INTERNAL shapes, in store order, from the size flags alone (no device)."""
+        F, K, H, G = feature_size, cluster_size, hidden_size, groups
+        E = expansion * F
+        D, Hg = E // G, hidden_size // gating_reduction
+        shapes = OrderedDict()
+        shapes[cls.EW] = (E, F)                                      # every 2-D weight is stored transposed [out][in]
+        shapes[cls.EB] = (E,)
+        shapes[cls.AW] = (G, E)
+        shapes[cls.AB] = (G,)
+        shapes[cls.CW] = (G * K, E)
+        shapes.update(BatchNorm.shapes("cluster_bn", G * K))
+        shapes[cls.C2] = (K, D)                                      # centres [K][D] (tf: [D, K])
+        shapes.update(BatchNorm.shapes("vlad_bn", K * D))            # cluster-major k*D + d
+        shapes[cls.HW] = (H, K * D)                                  # columns cluster-major
+        shapes.update(BatchNorm.shapes("hidden1_bn", H))
+        shapes[cls.G1] = (Hg, H)
+        shapes.update(BatchNorm.shapes("gating_bn", Hg))
+        shapes[cls.G2] = (H, Hg)
+        shapes.update(MoeHead.shapes(H, vocab_size, num_mixtures))
+        return shapes
+
+    @classmethod
+    def checkpoint_shapes(cls, *sizes, **kw):
+        """What state_dict() holds for these size flags, without the scope prefix: every variable in its TF layout (2-D weights
+        [in][out]) and the batch norms' moving statistics.  For checking a checkpoint against the flags before a tower is built."""
+        out = OrderedDict()
+        for k, shp in cls.variable_shapes(*sizes, **kw).items():
+            out[k] = tuple(reversed(shp)) if len(shp) == 2 else tuple(shp)
+            if k.endswith("/gamma"):
+                for v in ("moving_mean", "moving_variance"):
+                    out[k[:-len("gamma")] + v] = tuple(shp)
+        return out
 
     # TF order d*K + k  <->  internal cluster-major k*D + d: the rows of hidden1_weights [K*D, H] and every vlad_bn vector
     def _tf_keys(self, prefix):
@@ -940,7 +968,8 @@ class NeXtVladTower(TowerBase):
         bc.stats(self.act, R, is_training)
         ops.nextvlad_assign_fwd(self.act, R, G, K, bc.mean, bc.var, bc.gamma(), bc.beta(), self.attl, self.a)
         if grid:
-            ops.nextvlad_aggregate_packed_fwd(self.a, self.xe, self.row_off, B, self.T, G, K, D, R, plan.max_k, st.p(self.C2), self.Vv, self.asum)
+            agg = ops.nextvlad_aggregate_packed_fwd if self.training else ops.nextvlad_aggregate_packed_fwd_mfma      # (the same bits)
+            agg(self.a, self.xe, self.row_off, B, self.T, G, K, D, R, plan.max_k, st.p(self.C2), self.Vv, self.asum)
         else:
             ops.nextvlad_aggregate_fwd(self.a, self.xe, B, S, G, K, D, st.p(self.C2), self.Vv, self.asum)
         ops.nextvlad_normalize_fwd(self.Vv, B, K, D, self.U, self.nrm)
@@ -962,7 +991,8 @@ class NeXtVladTower(TowerBase):
         hidden = [self.G2, "gating_bn/beta", "gating_bn/gamma", self.G1, "hidden1_bn/beta", "hidden1_bn/gamma", self.HW]
         return moe, hidden, [k for k in self.names if k not in moe and k not in hidden]
 
-    def backward(self, dpred, on_moe_grads_ready=None, moe_weight_grads=True, on_stage=None):
+    def backward(self, dpred, on_moe_grads_ready=None, moe_weight_grads=True, on_stage=None, dstate=None):
+        """dstate (None or [B, H] f32): a gradient on `state` itself, added to the MoE head's d(out) in the gate backward."""
         assert self.training and self._taped, "backward needs a training-mode forward"
         B, F, S, K, H, R, G, E, D, Hg, AP = self.B, self.F, self.S, self.Kc, self.Hd, self.R, self.G, self.E, self.D, self.Hg, self.AP
         st, bc = self.store, self.bn_cl
@@ -974,7 +1004,12 @@ class NeXtVladTower(TowerBase):
         if on_stage is not None:
             on_stage(0)
         # context gating
-        ops.nextvlad_gate_bwd(self.h, self.gl, dout, self.dh, dgl_bf16=self.dgl_bf)
+        if dstate is None:
+            ops.nextvlad_gate_bwd(self.h, self.gl, dout, self.dh, dgl_bf16=self.dgl_bf)
+        else:
+            if dstate.shape != self.out.shape:
+                raise ValueError("dstate %s: the state of this tower is %s" % (tuple(dstate.shape), tuple(self.out.shape)))
+            ops.nextvlad_gate_bwd_add(self.h, self.gl, dout, dstate, self.dh, dgl_bf16=self.dgl_bf)
         ops.gemm_tn(self.dgl_bf, self.g1_bf, H, Hg, self.Bk, st.g(self.G2))              # dWg2^T [H][Hg]
         ops.gemm_nt(self.dgl_bf, self.shadow_bwd[self.G2], B, Hg, H, self.dg1)
         self.bn_g.backward(self.g1pre, self.dg1, B, True, dx_bf16=self.dg1pre_bf)
@@ -1020,6 +1055,14 @@ class NeXtVladTower(TowerBase):
     @property
     def pred(self):
         return self.moe.pred
+
+    @property
+    def state(self):
+        return self.out
+
+    @property
+    def rowsum(self):
+        return self.moe.rowsum
 
 
 class LogisticTower(TowerBase):

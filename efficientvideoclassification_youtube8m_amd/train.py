@@ -24,6 +24,8 @@ small model, or a teacher next to the teaching assistants distilled from it (dis
 ``--teacher_preds_pattern GLOB`` trains the student ALONE against 1 .. 8 teacher prediction files (what inference --output_file writes):
 the train_finetune step with the loss section evc_distill_losses_sparse, no teacher tower in memory (distill.OfflineDistillGraph,
 DESIGN.md 7.11).
+``--model NeXtVLADModel --nextvlad_frames grid --every_n N --teacher_dir DIR`` trains a grid student against the frozen grid teacher of
+DIR's latest checkpoint, which runs on the frames its checkpoint records (distill.NeXtVladDistillGraph).
 Multi-GPU: launch with ``python -m torch.distributed.run --nproc-per-node N``;
 ``--gpu`` is then ignored in favour of LOCAL_RANK.
 """
@@ -39,7 +41,7 @@ import numpy as np
 import torch
 
 from . import eval_util, frame_level_models, losses, ops, readers, video_level_models
-from .distill import DistillGraph, EnsembleDistillGraph, OfflineDistillGraph, SerialStudentsGraph, SingleTowerGraph
+from .distill import DistillGraph, EnsembleDistillGraph, NeXtVladDistillGraph, OfflineDistillGraph, SerialStudentsGraph, SingleTowerGraph
 from .flags import FLAGS, GetListOfFeatureNamesAndSizes
 from .towers import DbofTower, LogisticTower, NetVladTower, NeXtVladTower, check_nextvlad_frames
 
@@ -371,6 +373,60 @@ def restore_serial_students(graph, cks):
         restore_checkpoint(graph.student_view(k, with_teacher=False), cks[k])
 
 
+def nextvlad_size_flags():
+    """The size flags of a NeXtVLAD tower, in the order of NeXtVladTower.variable_shapes (after the feature size and the classes)."""
+    return (FLAGS.nextvlad_cluster_size, FLAGS.nextvlad_hidden_size, FLAGS.nextvlad_groups, FLAGS.nextvlad_expansion,
+            FLAGS.nextvlad_gating_reduction, FLAGS.moe_num_mixtures)
+
+
+def check_nextvlad_distill_flags():
+    """--teacher_dir with --model NeXtVLADModel: the combinations it refuses, as ValueErrors that name the flags (no device).  Returns True
+    when the flags ask for it.  (--serial_student_dirs, --teacher_dirs and --teacher_preds_pattern refuse every model but
+    HierarchicalLstmModel themselves: they are not built for this family.  --teacher_only, --finetune, several ranks: check_serial_flags;
+    another --label_loss: check_label_loss; another --precision, --every_n out of range: check_nextvlad_frames.)"""
+    if not FLAGS.teacher_dir or FLAGS.model != "NeXtVLADModel":
+        return False
+    if FLAGS.nextvlad_frames != "grid":
+        raise ValueError("--teacher_dir %s with --model NeXtVLADModel and --nextvlad_frames %s: the student of this family is a grid tower "
+                         "(--nextvlad_frames grid --every_n N); distillation of sampled towers is not built" % (FLAGS.teacher_dir, FLAGS.nextvlad_frames))
+    return True
+
+
+def nextvlad_teacher_every_n(sd):
+    """The grid the model/* tower of the checkpoint dict ``sd`` runs on as a frozen teacher: the teacher_every_n a distillation
+    checkpoint records (its model/* IS such a teacher), else its every_n when it records nextvlad_frames == "grid", else 1 - a sampled
+    checkpoint, whose weights load into a grid tower, sees every real frame."""
+    if sd.get("nextvlad_frames") == "grid":
+        return int(sd["teacher_every_n"]) if "teacher_every_n" in sd else int(sd["every_n"])
+    return 1
+
+
+def check_nextvlad_teacher_shapes(sd, feature_size, what=""):
+    """model/* of the checkpoint dict ``sd`` against the size flags: ValueError naming the first missing or mismatching variable."""
+    want = NeXtVladTower.checkpoint_shapes(feature_size, NUM_CLASSES, *nextvlad_size_flags())
+    if not any(k.startswith("model/") and torch.is_tensor(v) for k, v in sd.items()):
+        raise ValueError("--teacher_dir %s: %s holds no model/* variables (not a teacher checkpoint)" % (FLAGS.teacher_dir, what))
+    for k, shp in want.items():
+        have = sd.get("model/" + k)
+        if not torch.is_tensor(have):
+            raise ValueError("--teacher_dir %s: %s holds no variable model/%s (not a NeXtVLADModel checkpoint)" % (FLAGS.teacher_dir, what, k))
+        if tuple(have.shape) != shp:
+            raise ValueError("--teacher_dir %s: model/%s of %s has shape %s, the size flags (--nextvlad_* / --feature_sizes / "
+                             "--moe_num_mixtures) give %s" % (FLAGS.teacher_dir, k, what, tuple(have.shape), shp))
+
+
+def nextvlad_distill_source(feature_size):
+    """The checkpoint the frozen NeXtVLAD teacher comes from, read on the host before the device is touched: --train_dir's latest on
+    resume, else --teacher_dir's.  Returns {"ck", "sd", "teacher_every_n", "resume"}."""
+    resume = None if FLAGS.start_new_model else latest_checkpoint(FLAGS.train_dir)
+    ck = resume or latest_checkpoint(FLAGS.teacher_dir)
+    if ck is None:
+        raise ValueError("--teacher_dir %s: no model.ckpt-*.pt checkpoint there" % FLAGS.teacher_dir)
+    sd = torch.load(ck, map_location="cpu")
+    check_nextvlad_teacher_shapes(sd, feature_size, os.path.basename(ck))
+    return dict(ck=ck, sd=sd, teacher_every_n=nextvlad_teacher_every_n(sd), resume=resume is not None)
+
+
 def load_frozen_teacher(graph, teacher_dir):
     """The model/* variables of latest_checkpoint(teacher_dir) into the serial graph's frozen teacher.  Returns the checkpoint's path."""
     ck = latest_checkpoint(teacher_dir)
@@ -397,7 +453,7 @@ def check_label_loss(label_loss_fn, finetune=False):
 
 
 def build_graph(model, label_loss_fn, feature_size, batch_size, every_n, device, finetune=False, process_group=None, students=_UNSET,
-                teachers=None, offline=None):
+                teachers=None, offline=None, teacher_every_n=1):
     """Equivalent of cs/train.py:185-427 (and cs/train_finetune.py:185-331 when
     finetune): returns the graph object whose ``step`` runs one iteration."""
     check_label_loss(label_loss_fn, finetune)
@@ -449,8 +505,20 @@ def build_graph(model, label_loss_fn, feature_size, batch_size, every_n, device,
                             lstm_cells=FLAGS.lstm_cells, lstm_layers=FLAGS.lstm_layers,
                             num_mixtures=FLAGS.moe_num_mixtures, device=device, precision=FLAGS.precision,
                             student_sampling=FLAGS.student_sampling, sampling_seed=FLAGS.student_sampling_seed, **common)
+    if FLAGS.teacher_dir and isinstance(model, frame_level_models.NeXtVLADModel):
+        # the grid student against the frozen grid teacher; teacher_every_n: nextvlad_teacher_every_n of its checkpoint
+        check_serial_flags(finetune)
+        check_nextvlad_distill_flags()
+        check_nextvlad_frames(FLAGS.nextvlad_frames, every_n, FLAGS.max_num_frames, model=FLAGS.model, precision=FLAGS.precision)
+        common.pop("label_loss", None)            # (refused above for anything but CrossEntropyLoss, which the loss kernel has built in)
+        cs, hs, g, ex, gr, mx = nextvlad_size_flags()
+        return NeXtVladDistillGraph(batch_size, every_n=every_n, teacher_every_n=teacher_every_n, feature_size=feature_size,
+                                    vocab_size=NUM_CLASSES, max_frames=FLAGS.max_num_frames, cluster_size=cs, hidden_size=hs, groups=g,
+                                    expansion=ex, gating_reduction=gr, num_mixtures=mx, device=device, precision=FLAGS.precision,
+                                    distill_losses=FLAGS.distill_losses, **common)
     if FLAGS.teacher_dir:
-        raise ValueError("--teacher_dir %s: serial distillation is built for HierarchicalLstmModel, not %s" % (FLAGS.teacher_dir, type(model).__name__))
+        raise ValueError("--teacher_dir %s: serial distillation is built for HierarchicalLstmModel and NeXtVLADModel, not %s" %
+                         (FLAGS.teacher_dir, type(model).__name__))
     if isinstance(model, frame_level_models.DbofModel):
         tw = DbofTower(batch_size, FLAGS.max_num_frames, feature_size, NUM_CLASSES, FLAGS.iterations,
                        FLAGS.dbof_cluster_size, FLAGS.dbof_hidden_size, FLAGS.moe_num_mixtures, device=device,
@@ -559,6 +627,8 @@ def save_checkpoint(graph, train_dir, rank):
         sd["distill_teacher_files"] = graph.teacher_record
     if getattr(getattr(graph, "tower", None), "frames", None) == "grid":      # metadata: the frames this tower was trained on (--nextvlad_frames grid)
         sd["nextvlad_frames"], sd["every_n"] = "grid", graph.tower.every_n
+    if isinstance(graph, NeXtVladDistillGraph):   # metadata: the student's grid and the one the frozen teacher in model/* runs on
+        sd["nextvlad_frames"], sd["every_n"], sd["teacher_every_n"] = "grid", graph.every_n, graph.teacher_every_n
     fn = getattr(graph, "label_loss", None)
     if fn is not None and not losses.is_default(fn):            # metadata: the --label_loss these weights were trained on (the default: no key)
         sd["label_loss"] = type(fn).__name__
@@ -629,7 +699,12 @@ def main(argv=None):
     multi = serial_students(finetune, world)
     serial = check_serial_flags(finetune, world, students=multi)
     check_label_loss(find_class_by_name(FLAGS.label_loss, [losses])(), finetune)
+    nx_distill = serial and check_nextvlad_distill_flags()
     check_nextvlad_frames(FLAGS.nextvlad_frames, FLAGS.every_n, FLAGS.max_num_frames, model=FLAGS.model, world=world, precision=FLAGS.precision)
+    nx_src = None
+    if nx_distill:
+        # the teacher's checkpoint on the host - its grid and its shapes against the size flags -, before the device is touched
+        nx_src = nextvlad_distill_source(sum(GetListOfFeatureNamesAndSizes(FLAGS.feature_names, FLAGS.feature_sizes)[1]))
     ens_sds = None
     if ens:
         # the teachers' checkpoints on the host, and - on resume - the recorded list against the flags: all before the device is touched
@@ -674,7 +749,7 @@ def main(argv=None):
     if FLAGS.optimizer != "AdamOptimizer":
         raise NotImplementedError("only AdamOptimizer (the reference default, cs/train.py:91) is built")
     graph = build_graph(model, label_loss_fn, feature_size, FLAGS.batch_size, FLAGS.every_n, device, finetune, students=multi, teachers=ens,
-                        offline=offline)
+                        offline=offline, teacher_every_n=nx_src["teacher_every_n"] if nx_src else 1)
     if offline:
         graph.teacher_record = offline_record(offline)
     logging.info("%s: Built graph.", task)
@@ -699,6 +774,14 @@ def main(argv=None):
                          "come from %s", task, FLAGS.teacher_dir, ck)
     if serial and ck is None and getattr(graph, "mode", None) == "serial":
         logging.info("%s: Frozen teacher from %s", task, load_frozen_teacher(graph, FLAGS.teacher_dir))
+    if nx_src is not None:
+        logging.info("%s: the frozen teacher runs on every %d-th real frame, the student on every %d-th", task, graph.teacher_every_n, graph.every_n)
+        if FLAGS.student_init_from_teacher and ck is not None:
+            logging.info("%s: --student_init_from_teacher is ignored on resume: the student comes from %s", task, ck)
+        elif FLAGS.student_init_from_teacher:
+            graph.student.load_state_dict(nx_src["sd"], prefix="model")
+            logging.info("%s: the new student starts from the teacher's weights and moving statistics (%s)", task, nx_src["ck"])
+        nx_src = None
     if ens:
         # entry 0 came with the student from --train_dir on resume (restore_checkpoint above); every other teacher from its directory
         graph.teacher_record = ens_record
@@ -717,8 +800,9 @@ def main(argv=None):
     start, last_save, it = time.time(), time.time(), 0
     is_multi = isinstance(graph, SerialStudentsGraph)
     is_ens = isinstance(graph, EnsembleDistillGraph)
-    is_distill = isinstance(graph, DistillGraph) or is_multi or is_ens
-    is_grid = getattr(getattr(graph, "tower", None), "frames", None) == "grid"     # --nextvlad_frames grid: the packed rows are laid out from n_host
+    is_distill = isinstance(graph, (DistillGraph, NeXtVladDistillGraph)) or is_multi or is_ens
+    # --nextvlad_frames grid (one tower, or the student and its frozen teacher): the packed rows are laid out from n_host
+    is_grid = getattr(getattr(graph, "tower", None), "frames", None) == "grid" or isinstance(graph, NeXtVladDistillGraph)
     steps_per_it = 2 if is_distill and not is_multi and graph.mode == "teacher_student" else 1
     copy_stream = torch.cuda.Stream(device=device)
     host_bufs = {}                       # pinned staging, two alternating sets (one may still be read while the next fills)

@@ -877,6 +877,11 @@ int evc_nextvlad_aggregate_packed_fwd(const float* a, const float* xe, const int
 int evc_nextvlad_aggregate_packed_bwd(const float* a, const float* xe, const int32_t* row_off, int B, int T, int G, int K, int D, int R,
                                       int max_k, const float* c2, const float* dV, float* da, float* dxe, float* ws, int64_t ws_floats,
                                       void* stream);
+/* evc_nextvlad_aggregate_packed_fwd on the f32 matrix cores (v_mfma_f32_32x32x2_f32): the same arguments, limits
+ * and - every element being one fmaf chain over the video's pairs in ascending order, the epilogue fmaf(-asum, c2, acc) - the same
+ * bits in V and asum.  Forward only; nothing outside a video's own rows is read. */
+int evc_nextvlad_aggregate_packed_fwd_mfma(const float* a, const float* xe, const int32_t* row_off, int B, int T, int G, int K, int D,
+                                           int R, int max_k, const float* c2, float* V, float* asum, void* stream);
 /* out[row_off[b] + j][:] = frame j * every_n of video b (x f32 or x_u8 [B][T][F], exactly one non-NULL; uint8 is dequantised as
  * q * 4/255 + 4/512 - 2, a uint8 frame >= num_frames[b] reads as zeros), l2-normalised on request: the arithmetic of
  * evc_sample_frames_gather, bit for bit.  Rows R .. Rp (Rp - R < 32) are written as zeros.  out_bf16 (may be NULL): the same rows
@@ -890,6 +895,10 @@ int evc_nextvlad_normalize_bwd(const float* V, const float* norms, const float* 
 int evc_nextvlad_gate_fwd(const float* h, const float* gl, int64_t n, float* out, void* stream);
 int evc_nextvlad_gate_bwd(const float* h, const float* gl, const float* dout, int64_t n, float* dh, float* dgl, evc_bf16* dgl_bf16,
                           void* stream);
+/* evc_nextvlad_gate_bwd with the incoming gradient dout[i] + dout2[i] (one f32 add, in that order; dout2 may be NULL: the bits of
+ * evc_nextvlad_gate_bwd).  Where a gradient on the gated vector itself (dL_REP/d out) joins the MoE head's. */
+int evc_nextvlad_gate_bwd_add(const float* h, const float* gl, const float* dout, const float* dout2, int64_t n, float* dh, float* dgl,
+                              evc_bf16* dgl_bf16, void* stream);
 /* The bf16 operand of the cluster / attention products, centred: out[r][e] = bf16(xe[r][e] - be[e]) (E % 4 == 0).  The constant
  * the bias adds to every logit, out[n] = sum_e be[e]*W[n][e] (+ add[n]) for n < N and 0 for N <= n < n_out, goes into the
  * product as its f32 bias.  A weight gradient contracted against the centred operand gets the rank-one term back:
