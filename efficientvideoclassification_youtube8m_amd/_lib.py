@@ -125,6 +125,8 @@ SIGNATURES = {
     "evc_nextvlad_aggregate_packed_fwd_mfma": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp],
     "evc_nextvlad_aggregate_packed_bwd": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp],
     "evc_frames_gather_packed": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp],
+    "evc_frames_gather_packed_sel": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp],
+    "evc_scatter_rows": [vp, i64, vp, i32, i32, i32, vp, i64, vp],
     "evc_nextvlad_normalize_fwd": [vp, i32, i32, i32, vp, vp, vp],
     "evc_nextvlad_normalize_bwd": [vp, vp, vp, i32, i32, i32, vp, vp],
     "evc_nextvlad_gate_fwd": [vp, vp, i64, vp, vp],

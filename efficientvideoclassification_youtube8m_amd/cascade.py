@@ -7,6 +7,9 @@ Rows of length 0 drop out of the input pass and of every L1 kernel (RowPlan.P = 
 the final state of rows no step touches.  What such a row's tower then predicts is never looked at: ops.cascade_confidence_rows copies
 into the merged matrix only the rows the stage ran.
 
+A NeXtVLAD stage (distill.NeXtVladEvalGraph) takes the same step: its settled rows leave the packed frame rows and - the
+graph serving only the videos that have a frame - everything behind the aggregation too.
+
 The gate is ops.cascade_confidence_rows + ops.cascade_pick_rows (csrc/evc_cascade.hip).  Its result has to reach the host, because the
 launch geometry of the next stage is host-side: one pinned copy and one wait per gate, timed as ``gate_wait_s``.
 
@@ -22,17 +25,22 @@ import numpy as np
 import torch
 
 from . import ops
-from .distill import EvalGraph, scored_sampling
+from .distill import member_graph, scored_sampling
 
 F32 = torch.float32
 
 
 def parse_stage(stage):
-    """(tower, every_n, student_sampling | None) of a ``stages`` entry (tower, every_n[, student_sampling])."""
+    """(tower, every_n, student_sampling | None) of a ``stages`` entry (tower, every_n[, student_sampling[, nextvlad]]); the fourth
+    element, the size keywords of a NeXtVLAD stage (distill.member_graph), is read by stage_family."""
     tower, every_n = stage[0], int(stage[1])
     if tower not in ("teacher", "student"):
         raise ValueError("CascadeGraph: tower %r (teacher | student)" % (tower,))
     return tower, every_n, (stage[2] if len(stage) > 2 else None)
+
+
+def stage_family(stage):
+    return "nextvlad" if len(stage) > 3 and stage[3] is not None else "hlstm"
 
 
 def check_gates(num_stages, confidence, thresholds, fractions, what="CascadeGraph"):
@@ -66,13 +74,14 @@ def stage_quota(n_active, fraction, batch_rows):
 
 
 def stage_bookkeeping(k, num_stages, active, num_frames_host, tower, every_n, threshold=None, fraction=None, max_frames=300,
-                      num_inputs_to_lstm=20, num_inputs_l1_student=5):
+                      num_inputs_to_lstm=20, num_inputs_l1_student=5, family="hlstm"):
     """Everything about stage k of a batch that is decided on the host.  active: None (stage 0: every row) or the bool / 0-1 vector [b] the
     gate before this stage returned; num_frames_host: the batch's ORIGINAL counts [b].  Returns a dict:
       run         False when no row is active: the stage's graph is not stepped and nothing is launched;
       rows        active rows;
       nh          int64 [b]: the host counts the stage's graph gets, where(active, num_frames_host, 0);
-      frames      frames the stage's tower consumes over its rows (ops.host_frame_counts: the teacher reads n, a student int(n / 300 * S));
+      frames      frames the stage's tower consumes over its rows (ops.host_frame_counts: the teacher reads n, a student int(n / 300 * S);
+                  family "nextvlad", either tower: the grid's ceil(min(n, max_frames) / every_n));
       gate        whether a gate follows (run, and k is not the last stage);
       threshold   the gate's threshold (+inf where only a fraction is given);
       max_rows    the gate's quota stage_quota(rows, fraction, b)."""
@@ -83,7 +92,9 @@ def stage_bookkeeping(k, num_stages, active, num_frames_host, tower, every_n, th
         raise ValueError("stage_bookkeeping: %d active flags for %d rows" % (act.shape[0], b))
     rows = int(act.sum())
     nh = np.where(act, nh0, 0).astype(np.int64)
-    if tower == "teacher":
+    if family == "nextvlad":
+        used = (np.clip(nh, 0, max_frames) + every_n - 1) // every_n             # (ops.GridPlan's k)
+    elif tower == "teacher":
         C = num_inputs_to_lstm
         used = ops.host_frame_counts(nh, 1, C, max_frames // C, max_frames)[0]
     else:
@@ -116,18 +127,17 @@ class CascadeGraph:
 
     def __init__(self, batch_size, stages, confidence="top1", thresholds=None, fractions=None, **kw):
         self.stages = [parse_stage(s) for s in stages]
+        self.families = [stage_family(s) for s in stages]
         self.thresholds, self.fractions = check_gates(len(self.stages), confidence, thresholds, fractions)
         self.confidence = confidence
         if batch_size > ops.CASCADE_MAX_ROWS:
             raise ValueError("CascadeGraph: batch_size %d (at most %d rows per gate)" % (batch_size, ops.CASCADE_MAX_ROWS))
         self.graphs = []
-        for tower, every_n, sampling in self.stages:
-            skw = dict(kw)
-            if sampling is not None:
-                skw["student_sampling"] = sampling
-            self.graphs.append(EvalGraph(batch_size, every_n=every_n, student_only=tower == "student", teacher_only=tower == "teacher", **skw))
+        for stage in stages:
+            self.graphs.append(member_graph(batch_size, stage, kw))
         g0 = self.graphs[0]
-        self.device, self.max_frames, self.C1, self.C2 = g0.device, g0.max_frames, g0.C1, g0.C2
+        self.device, self.max_frames = g0.device, g0.max_frames
+        self.C1, self.C2 = kw.get("num_inputs_to_lstm", 20), kw.get("num_inputs_l1_student", 5)     # (EvalGraph's defaults)
         self.stage_steps = [0] * len(self.stages)                        # how often each stage's graph was stepped
         self._pin_active = torch.empty(batch_size, dtype=torch.uint8, pin_memory=True)
         self._pin_count = torch.empty(1, dtype=torch.int32, pin_memory=True)
@@ -164,7 +174,7 @@ class CascadeGraph:
         for k, (g, (tower, every_n, _)) in enumerate(zip(self.graphs, self.stages)):
             book = stage_bookkeeping(k, K, active_host, nh0, tower, every_n, self.thresholds[k] if k < K - 1 else None,
                                      self.fractions[k] if (self.fractions is not None and k < K - 1) else None, self.max_frames, self.C1,
-                                     self.C2)
+                                     self.C2, family=self.families[k])
             if not book["run"]:
                 break                                                  # no row is active: nor will one be at any later stage
             out["stage_rows"][k], out["stage_frames"][k] = book["rows"], book["frames"]

@@ -6,6 +6,8 @@
 //   evc_nextvlad_assign_fwd/bwd      a[r,g,k] = softmax_k(cluster_bn(act)[r,g,:])[k] * sigmoid(att_logit[r,g]) and its reverse mode
 //   evc_nextvlad_aggregate_fwd/bwd   V[b,k,:] = sum_{s,g} a[b,s,g,k] * xe[b,s,g*D:(g+1)*D] - asum[b,k] * c2[k,:]; da, dxe from dV
 //   evc_nextvlad_aggregate_packed_fwd/bwd, evc_frames_gather_packed   the same over a ragged, packed list of frames per video (7.13)
+//   evc_frames_gather_packed_sel, evc_scatter_rows   serving a subset of the batch's videos: packed rows of the selected videos, and their
+//                                    result rows back to the batch's row numbers (7.15)
 //   evc_nextvlad_aggregate_packed_fwd_mfma   the packed forward on the f32 matrix cores, for forward-only towers: the same bits (7.14)
 //   evc_nextvlad_normalize_fwd/bwd   U[b,k,:] = V[b,k,:] / max(|V[b,k,:]|, 1e-12)
 //   evc_nextvlad_gate_fwd/bwd        out = h * sigmoid(gl) (context gating); _bwd_add: with a second gradient on out (7.14)
@@ -539,19 +541,23 @@ extern "C" int evc_nextvlad_aggregate_packed_bwd(const float* a, const float* xe
 // arithmetic of sample_gather_kernel (evc_elementwise.hip) in the same order, so that one source frame gives the same bits through
 // either gather.  One wave per row; the row's video by a binary search of row_off (the last b with row_off[b] <= row: videos
 // without a row are stepped over).  Rows R .. Rp are zeros (the padding of the TN products' contraction), also in the bf16 copy.
+// SEL (evc_frames_gather_packed_sel, 7.15): packed video j is source video sel[j] of the unchanged batch - B counts the packed videos,
+// nfr and x are indexed by the source video - and the f32 rows are optional (out NULL: the bf16 rows alone).
+template <bool SEL>
 __global__ __launch_bounds__(256) void frames_gather_packed_kernel(const float* __restrict__ x, const uint8_t* __restrict__ xq,
-                                                                   const int* __restrict__ nfr, const int* __restrict__ row_off, int B,
-                                                                   int T, int F, int every_n, int R, int Rp, int normalize,
-                                                                   float* __restrict__ out, uint2* __restrict__ out_bf) {
+                                                                   const int* __restrict__ nfr, const int* __restrict__ row_off,
+                                                                   const int* __restrict__ sel, int B, int T, int F, int every_n, int R,
+                                                                   int Rp, int normalize, float* __restrict__ out,
+                                                                   uint2* __restrict__ out_bf) {
   const int lane = threadIdx.x & 63;
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= Rp) return;
   const int F4 = F >> 2;
-  float4* dst = (float4*)(out + row * F);
+  float4* dst = (!SEL || out) ? (float4*)(out + row * F) : nullptr;
   uint2* dst_bf = out_bf ? out_bf + row * F4 : nullptr;
   if (row >= R) {
     for (int j = lane; j < F4; j += 64) {
-      dst[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (dst) dst[j] = make_float4(0.f, 0.f, 0.f, 0.f);
       if (dst_bf) dst_bf[j] = make_uint2(0u, 0u);
     }
     return;
@@ -561,8 +567,9 @@ __global__ __launch_bounds__(256) void frames_gather_packed_kernel(const float* 
     const int mid = (b + hi) >> 1;
     if (row_off[mid] <= (int)row) b = mid; else hi = mid;
   }
-  const int n = nfr[b];
   long fr = (long)((int)row - row_off[b]) * every_n;
+  if (SEL) b = sel[b];                           // from here on b is the source video
+  const int n = nfr[b];
   const int idx = fr < 0 ? 0 : (fr >= T ? T - 1 : (int)fr);
   const bool padded = xq && idx >= n;            // uint8 input: frames >= num_frames are padding (zero after Dequantize)
   auto load = [&](int j) {
@@ -581,7 +588,8 @@ __global__ __launch_bounds__(256) void frames_gather_packed_kernel(const float* 
     inv = rsqrtf(fmaxf(wave_sum(ss), 1e-12f));
   }
   for (int j = lane; j < F4; j += 64) {
-    float4 v = load(j); v.x *= inv; v.y *= inv; v.z *= inv; v.w *= inv; dst[j] = v;
+    float4 v = load(j); v.x *= inv; v.y *= inv; v.z *= inv; v.w *= inv;
+    if (dst) dst[j] = v;
     if (dst_bf) dst_bf[j] = make_uint2(pack_bf16x2_hw(v.x, v.y), pack_bf16x2_hw(v.z, v.w));
   }
 }
@@ -596,8 +604,54 @@ extern "C" int evc_frames_gather_packed(const float* x, const uint8_t* x_u8, con
   EVC_REQUIRE(nx_aligned16(x) && ((uintptr_t)x_u8 % 4) == 0 && nx_aligned16(out) && ((uintptr_t)out_bf16 % 8) == 0, EVC_ERR_BAD_ALIGN,
               "evc_frames_gather_packed: misaligned operand (float4 / uchar4 / 8-byte bf16 access)");
   if (Rp == 0) return EVC_OK;
-  hipLaunchKernelGGL(frames_gather_packed_kernel, dim3((unsigned)((Rp + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, x_u8, num_frames, row_off,
-                     B, T, F, every_n, R, Rp, normalize, out, (uint2*)out_bf16);
+  hipLaunchKernelGGL(frames_gather_packed_kernel<false>, dim3((unsigned)((Rp + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, x_u8, num_frames,
+                     row_off, nullptr, B, T, F, every_n, R, Rp, normalize, out, (uint2*)out_bf16);
+  EVC_LAUNCH_CHECK();
+  return EVC_OK;
+}
+extern "C" int evc_frames_gather_packed_sel(const float* x, const uint8_t* x_u8, const int32_t* num_frames, const int32_t* row_off,
+                                            const int32_t* sel, int B, int Bsel, int T, int F, int every_n, int R, int Rp, int normalize,
+                                            float* out, evc_bf16* out_bf16, void* stream) {
+  EVC_REQUIRE(B > 0 && Bsel > 0 && Bsel <= B && T > 0 && F > 0 && F % 4 == 0 && every_n >= 1 && R >= 0 && Rp >= R && Rp - R < 32 &&
+              (long)R <= (long)Bsel * ((T + every_n - 1) / every_n), EVC_ERR_BAD_SHAPE,
+              "evc_frames_gather_packed_sel: needs 1 <= Bsel <= B, F %% 4 == 0, every_n >= 1, R <= Bsel * ceil(T / every_n), R <= Rp < R + 32 "
+              "(B=%d Bsel=%d T=%d F=%d every_n=%d R=%d Rp=%d)", B, Bsel, T, F, every_n, R, Rp);
+  EVC_REQUIRE((x != nullptr) != (x_u8 != nullptr), EVC_ERR_BAD_ARG, "evc_frames_gather_packed_sel: exactly one of x / x_u8");
+  EVC_REQUIRE(num_frames && row_off && sel && (out || out_bf16), EVC_ERR_BAD_ARG,
+              "evc_frames_gather_packed_sel: NULL operand (num_frames, row_off, sel, and at least one of out / out_bf16)");
+  EVC_REQUIRE(nx_aligned16(x) && ((uintptr_t)x_u8 % 4) == 0 && nx_aligned16(out) && ((uintptr_t)out_bf16 % 8) == 0, EVC_ERR_BAD_ALIGN,
+              "evc_frames_gather_packed_sel: misaligned operand (float4 / uchar4 / 8-byte bf16 access)");
+  if (Rp == 0) return EVC_OK;
+  hipLaunchKernelGGL(frames_gather_packed_kernel<true>, dim3((unsigned)((Rp + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, x_u8, num_frames,
+                     row_off, sel, Bsel, T, F, every_n, R, Rp, normalize, out, (uint2*)out_bf16);
+  EVC_LAUNCH_CHECK();
+  return EVC_OK;
+}
+
+// ---- dst[sel[j]][:] = src[j][:] for the n rows of src (f32, C columns): one wave per row, float4 where both rows are 16-byte aligned
+// (C % 4 == 0 and aligned bases), scalar columns otherwise and for the tail.  Rows of dst that sel does not name are not touched.
+__global__ __launch_bounds__(256) void scatter_rows_kernel(const float* __restrict__ src, long ld_src, const int* __restrict__ sel, int n,
+                                                           int C, int vec, float* __restrict__ dst, long ld_dst) {
+  const int lane = threadIdx.x & 63;
+  const long j = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (j >= n) return;
+  const float* s = src + j * ld_src;
+  float* d = dst + (long)sel[j] * ld_dst;
+  const int C4 = vec ? (C >> 2) : 0;
+  for (int c = lane; c < C4; c += 64) ((float4*)d)[c] = ((const float4*)s)[c];
+  for (int c = (C4 << 2) + lane; c < C; c += 64) d[c] = s[c];
+}
+extern "C" int evc_scatter_rows(const float* src, int64_t ld_src, const int32_t* sel, int n, int rows_dst, int C, float* dst, int64_t ld_dst,
+                                void* stream) {
+  EVC_REQUIRE(n >= 0 && n <= rows_dst && C > 0 && ld_src >= C && ld_dst >= C, EVC_ERR_BAD_SHAPE,
+              "evc_scatter_rows: needs 0 <= n <= rows_dst, C > 0, row strides >= C (n=%d rows_dst=%d C=%d ld_src=%ld ld_dst=%ld)", n, rows_dst, C,
+              (long)ld_src, (long)ld_dst);
+  EVC_REQUIRE(src && sel && dst, EVC_ERR_BAD_ARG, "evc_scatter_rows: NULL operand");
+  EVC_REQUIRE(((uintptr_t)src % 4) == 0 && ((uintptr_t)dst % 4) == 0, EVC_ERR_BAD_ALIGN, "evc_scatter_rows: misaligned operand (f32 access)");
+  if (n == 0) return EVC_OK;
+  const int vec = nx_aligned16(src) && nx_aligned16(dst) && ld_src % 4 == 0 && ld_dst % 4 == 0;
+  hipLaunchKernelGGL(scatter_rows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, src, (long)ld_src, sel, n, C, vec, dst,
+                     (long)ld_dst);
   EVC_LAUNCH_CHECK();
   return EVC_OK;
 }

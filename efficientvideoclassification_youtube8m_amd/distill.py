@@ -1461,10 +1461,26 @@ class EvalGraph(_StepGraph):
         return dict(predictions=t_pred, teacher_state=t_state, teacher_predictions=t_pred)
 
 
+def member_graph(batch_size, member, kw):
+    """The forward-only graph of one ensemble member / cascade stage: ``member`` = (tower, every_n[, student_sampling[, nextvlad]]), kw =
+    EvalGraph's keywords.  Without a fourth element (or with None there) an EvalGraph that is teacher_only / student_only; with one - a
+    dict of NeXtVladEvalGraph's size keywords - a NeXtVladEvalGraph of that tower, which takes feature_size, vocab_size, max_frames,
+    num_mixtures, device, precision and label_loss from kw."""
+    tower, every_n = member[0], member[1]
+    if len(member) > 3 and member[3] is not None:
+        shared = {k: kw[k] for k in ("feature_size", "vocab_size", "max_frames", "num_mixtures", "device", "precision", "label_loss") if k in kw}
+        return NeXtVladEvalGraph(batch_size, tower=tower, every_n=every_n, student_sampling=member[2] or "uniform", **shared, **member[3])
+    mkw = dict(kw)
+    if len(member) > 2 and member[2] is not None:     # (tower, every_n, student_sampling): this member's own frame selection
+        mkw["student_sampling"] = member[2]
+    return EvalGraph(batch_size, every_n=every_n, student_only=tower == "student", teacher_only=tower == "teacher", **mkw)
+
+
 class EnsembleGraph:
     """N forward-only members for one input: each an EvalGraph that is ``teacher_only`` or ``student_only`` at its own every_n, all on
     one device with one --precision and one set of model sizes (``members``: list of (tower, every_n[, student_sampling]), tower
-    'teacher' | 'student'; the other arguments are EvalGraph's, student_sampling / sampling_seed among them).  step() runs every member on the same input tensors and returns their prediction tensors,
+    'teacher' | 'student'; the other arguments are EvalGraph's, student_sampling / sampling_seed among them); a member with a fourth
+    element is a NeXtVladEvalGraph (member_graph).  step() runs every member on the same input tensors and returns their prediction tensors,
     each the buffer of that member's own tower, so all of them are alive together for ops.ensemble_topk_rows."""
 
     def __init__(self, batch_size, members, **kw):
@@ -1475,10 +1491,7 @@ class EnsembleGraph:
             tower, every_n = member[0], member[1]
             if tower not in ("teacher", "student"):
                 raise ValueError("EnsembleGraph: tower %r (teacher | student)" % (tower,))
-            mkw = dict(kw)
-            if len(member) > 2:               # (tower, every_n, student_sampling): this member's own frame selection
-                mkw["student_sampling"] = member[2]
-            self.members.append(EvalGraph(batch_size, every_n=every_n, student_only=tower == "student", teacher_only=tower == "teacher", **mkw))
+            self.members.append(member_graph(batch_size, member, kw))
 
     def restore(self, state_dicts):
         """Each member restores its own checkpoint (the 11 variables of its tower by name)."""
@@ -1725,3 +1738,127 @@ class NeXtVladDistillGraph(_StepGraph):
         return dict(predictions=t_pred, teacher_state=tt.state, loss=self.losses[0], student_predictions=s_pred, student_state=ts.state,
                     num_frames_student=torch.from_numpy(ts.plan.k), student_loss_state=self.losses[1], pred_loss=self.losses[2],
                     student_label_loss=self.losses[3], global_step=self.global_step)
+
+
+def check_nextvlad_checkpoint(sd, scope, feature_size, vocab_size, sizes, what="the checkpoint"):
+    """The ``scope``/* variables of the checkpoint dict ``sd`` against the size flags (sizes: cluster_size, hidden_size, groups, expansion,
+    gating_reduction, num_mixtures), on the host: ValueError naming the first missing or mismatching variable and both shapes."""
+    from .towers import NeXtVladTower
+    for k, shp in NeXtVladTower.checkpoint_shapes(feature_size, vocab_size, *sizes).items():
+        have = sd.get("%s/%s" % (scope, k))
+        if not torch.is_tensor(have):
+            raise ValueError("%s holds no variable %s/%s (not a NeXtVLADModel checkpoint of that tower)" % (what, scope, k))
+        if tuple(have.shape) != shp:
+            raise ValueError("%s/%s of %s has shape %s, the size flags (--nextvlad_* / --feature_sizes / --moe_num_mixtures) give %s"
+                             % (scope, k, what, tuple(have.shape), shp))
+
+
+class NeXtVladEvalGraph(_StepGraph):
+    """Forward-only graph of the NeXtVLAD family with EvalGraph's interface: restore(state_dict) and
+    step(x_raw, labels_u8, num_frames, num_frames_host=None, keys=None) -> dict, so that EnsembleGraph, CascadeGraph, validate and inference
+    hold it where they hold an EvalGraph.  tower: 'teacher' (scope model, on every `every_n`-th real frame), 'student' (scope
+    model_student, the same) or 'both' (the student served at every_n, the teacher run too at teacher_every_n: validate's
+    student_state_loss).  The towers are forward-only grid towers (training=False: moving statistics, MFMA aggregation), bf16 only, on
+    the caller's stream.
+
+    compact: the towers run on the videos that have a frame.  sel = the ascending list of videos with num_frames_host > 0; when it is
+    shorter than the batch the towers serve those b' videos of the unchanged batch (NeXtVladTower.forward(sel=...)) and
+    ops.scatter_rows puts their rows back: predictions / states are [b, .] with zeros in the rows of videos without a frame.  With
+    compact=False such a video runs through the tower after the aggregation like any other (its V is zero) and its row holds what the
+    head makes of that.  The buffers are allocated once at batch_size: a shorter batch or a served subset allocates nothing."""
+
+    family = "nextvlad"
+    student_sampling = "uniform"
+
+    def __init__(self, batch_size, tower="teacher", every_n=1, teacher_every_n=1, feature_size=1152, vocab_size=4716, max_frames=300,
+                 cluster_size=64, hidden_size=1024, groups=8, expansion=2, gating_reduction=8, num_mixtures=2, device="cuda:0",
+                 precision="bf16", student_sampling="uniform", label_loss=None, compact=True, seed=7):
+        from .towers import NeXtVladTower, check_nextvlad_frames
+        if tower not in ("teacher", "student", "both"):
+            raise ValueError("NeXtVladEvalGraph: tower %r (teacher | student | both)" % (tower,))
+        if student_sampling != "uniform":
+            raise ValueError("--student_sampling %s with --model NeXtVLADModel: a grid tower reads every every_n-th real frame (uniform); "
+                             "the other selections are not built for this family" % (student_sampling,))
+        if precision != "bf16":
+            raise ValueError("--precision %s with --model NeXtVLADModel: the NeXtVLAD tower has no such forward mode (bf16 only)" % (precision,))
+        self.label_loss = _resolve_label_loss(label_loss, vocab_size)
+        grids = [every_n] + ([teacher_every_n] if tower == "both" else [])
+        for n in grids:
+            check_nextvlad_frames("grid", n, max_frames, precision=precision)
+        self.tower, self.every_n, self.teacher_every_n = tower, int(every_n), int(teacher_every_n if tower == "both" else every_n)
+        self.batch_size, self.max_frames, self.precision, self.compact = batch_size, max_frames, precision, bool(compact)
+        self.sizes = (cluster_size, hidden_size, groups, expansion, gating_reduction, num_mixtures)
+        self.F, self.V = feature_size, vocab_size
+        self.device = torch.device(device)
+        args = (batch_size, max_frames, feature_size, vocab_size, 30) + self.sizes
+        self.teacher = self.student = None
+        if tower != "student":
+            self.teacher = NeXtVladTower(*args, device=device, training=False, scope="model", seed=seed, frames="grid", every_n=self.teacher_every_n)
+        if tower != "teacher":
+            self.student = NeXtVladTower(*args, device=device, training=False, scope="model_student", seed=seed + 1, frames="grid",
+                                         every_n=self.every_n)
+        self.frames = FramePlan()                  # (no H-LSTM student: scored_sampling() is False for this member)
+        self.losses = torch.zeros(4, dtype=F32, device=self.device)
+        # what a compacted step hands out: [batch_size, .] once, rows of videos without a frame zero
+        self._wide = {}
+        if self.compact:
+            for name, tw in (("teacher", self.teacher), ("student", self.student)):
+                if tw is not None:
+                    self._wide[name] = (torch.zeros((batch_size, vocab_size), dtype=F32, device=self.device),
+                                        torch.zeros((batch_size, hidden_size), dtype=F32, device=self.device))
+
+    def _towers(self):
+        return [tw for tw in (self.teacher, self.student) if tw is not None]
+
+    def restore(self, state_dict):
+        """Each tower's variables and moving statistics by name, after the host check of their shapes against the graph's sizes."""
+        for tw in self._towers():
+            check_nextvlad_checkpoint(state_dict, tw.scope, self.F, self.V, self.sizes)
+            tw.load_state_dict(state_dict)
+
+    def _run(self, name, tw, x_raw, num_frames, nh, sel):
+        """(predictions [b, V], state [b, H]) of one tower for this batch; with sel, the rows of the other videos are zeros."""
+        pred = tw.forward(x_raw, num_frames, is_training=False, num_frames_host=nh, sel=sel)
+        if sel is None:
+            return pred, tw.state
+        b, n = x_raw.shape[0], int(sel.shape[0])
+        wide_pred, wide_state = (t[:b] for t in self._wide[name])
+        wide_pred.zero_()
+        wide_state.zero_()
+        ops.scatter_rows(pred, tw.sel[:n], wide_pred)
+        ops.scatter_rows(tw.state, tw.sel[:n], wide_state)
+        return wide_pred, wide_state
+
+    def step(self, x_raw, labels_u8, num_frames, num_frames_host=None, keys=None):
+        """x_raw [b, T, F] uint8 or float32, b <= batch_size; labels_u8 [b, V]; num_frames [b] int32 (num_frames_host: the same counts
+        on the host; read back from the device when not given).  keys is EvalGraph's argument and is not read."""
+        b = int(x_raw.shape[0])
+        if b > self.batch_size:
+            raise ValueError("NeXtVladEvalGraph: a batch of %d videos, the graph was built for %d" % (b, self.batch_size))
+        if num_frames_host is None:
+            num_frames_host = num_frames.cpu()
+        nh = np.asarray(num_frames_host, dtype=np.int64).reshape(-1)
+        sel = None
+        if self.compact:
+            have = np.flatnonzero(nh > 0)
+            if 0 < have.size < b:
+                sel = have.astype(np.int32)
+        out = {}
+        if self.teacher is not None:
+            t_pred, t_state = self._run("teacher", self.teacher, x_raw, num_frames, nh, sel)
+            out.update(teacher_predictions=t_pred, teacher_state=t_state)
+        if self.student is not None:
+            pred, s_state = self._run("student", self.student, x_raw, num_frames, nh, sel)
+            out["student_state"] = s_state
+        else:
+            pred = t_pred
+        served = self.student if self.student is not None else self.teacher
+        self.losses.zero_()
+        self.label_loss.fused(pred, labels_u8, self.losses[0:1])
+        if self.tower == "both":
+            ops.rep_loss(t_state, s_state, self.losses[1:2])
+            out["student_state_loss"] = self.losses[1]
+        k = np.zeros(b, np.int32)
+        k[sel if sel is not None else slice(None)] = served.plan.k
+        out.update(predictions=pred, loss=self.losses[0], student_label_loss=self.losses[0], num_frames=torch.from_numpy(k))
+        return out

@@ -641,8 +641,17 @@ class MoeHead:
             self.xT = torch.empty((K, self.Bp), dtype=BF16, device=dev)
             self.dx = torch.empty((B, K), dtype=F32, device=dev)
 
-    def forward(self, x):
+    def forward(self, x, rows=None):
+        """rows (bf16 mode only): the head of the first `rows` <= B rows of the allocated buffers (a served subset of the batch)."""
         tw, B, V, Mx, K = self.tw, self.B, self.V, self.Mx, self.K
+        if rows is not None:
+            if getattr(tw, "precision", "bf16") != "bf16" or not 0 < rows <= B:
+                raise ValueError("MoeHead.forward(rows=%r): needs the bf16 mode and 0 < rows <= %d" % (rows, B))
+            ops.cast_bf16(x, self.x_bf[:rows])
+            ops.gemm_nt(self.x_bf, tw.shadow_fwd[self.GATES], rows, V * (Mx + 1), K, self.gate_logits)
+            ops.gemm_nt(self.x_bf, tw.shadow_fwd[self.EXPERTS], rows, V * Mx, K, self.expert_logits, bias=tw.store.p(self.EBIAS))
+            ops.moe_tail_fwd(self.gate_logits, self.expert_logits, rows, V, Mx, self.pred, self.rowsum)
+            return self.pred
         if getattr(tw, "precision", "bf16") == "high" and self.GATES in getattr(tw, "shadow_w8", {}):
             # f16 product + both low-order corrections as e4m3 operands behind it in the same launch (ops.gemm_nt_f16_fp8)
             if not hasattr(self, "x_rows") or self.x_rows.shape[0] != B:

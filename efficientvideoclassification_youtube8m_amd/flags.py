@@ -143,6 +143,12 @@ _define("nextvlad_gating_reduction", 8, int, "NeXtVLADModel (extension): context
 _define("nextvlad_frames", "sampled", str, "NeXtVLADModel (extension): sampled (--iterations frames drawn per video and step) | grid (the frames "
         "0, every_n, 2 every_n, ... of each video's real frames, a different number per video, packed without padding: --every_n 1 is every real "
         "frame, the teacher's input; --every_n 10 or 30 the fewer-frames student's; --iterations is not read)")
+_define("nextvlad_serve_every_n", 0, int, "validate / inference with --model NeXtVLADModel (DESIGN.md 7.15): the grid the served tower runs "
+        "on, every N-th real frame; 0 = the grid its checkpoint records (model_student/*: every_n; model/*: the teacher's grid, 1 for a "
+        "--nextvlad_frames sampled checkpoint).  Another N than the recorded one is a legitimate experiment: the flag wins, with a warning")
+_define("serve_tower", "auto", str, "inference: auto|teacher|student - the tower of --train_dir's checkpoint that is served.  auto: for "
+        "HierarchicalLstmModel the tower its variables name (inference.serving_tower: model/* before model_student/*); for NeXtVLADModel "
+        "model_student/* when the checkpoint holds it (the student is what a --teacher_dir run produces), else model/*")
 _define("log_every", 1, int, "host metrics / logging period in iterations (the reference logs every step)")
 _define("metrics_on_device", False, _bool, "validate / eval_finetune: select what Hit@1 / PERR / GAP / mAP need from each batch on the device "
         "(ops.eval_select_rows) and fetch [B, top_k] + a few [B] vectors instead of the [B, 4716] predictions and labels; same metrics bit "
@@ -216,7 +222,9 @@ _define("ensemble_dirs", "", str, "comma separated checkpoint directories of the
         "combines and selects in one launch")
 _define("ensemble_towers", "", str, "one word per member from auto|teacher|student: auto = the tower the checkpoint's variables name "
         "(inference.serving_tower), student on a train.py checkpoint = its model_student/*; '' = auto for all")
-_define("ensemble_every_n", "", str, "one every_n per member (ignored for teachers); '' = --every_n for all")
+_define("ensemble_every_n", "", str, "one every_n per member (ignored for H-LSTM teachers); '' = --every_n for all.  A NeXtVLAD member (the "
+        "family is read from each member's own checkpoint; its sizes are the --nextvlad_* flags) runs on the grid its checkpoint records "
+        "when the list is not given or its entry is 0 or empty, as 10,,30")
 _define("ensemble_mode", "max", str, "max (per-class maximum, cs/max_ensemble.py) | mean (weighted mean)")
 _define("ensemble_weights", "", str, "comma separated weights, one per member and then one per --preds_pattern file; mean mode only; "
         "'' = 1 / (members + files) each")
@@ -229,7 +237,8 @@ _define("cascade_dirs", "", str, "comma separated checkpoint directories of the 
         "settled neighbours get num_frames = 0 and drop out of the row plans.  Under --precision split the row plans are off: the cascade "
         "is correct there but saves nothing.  Not with --ensemble_dirs or --preds_pattern; validate needs --run_once True")
 _define("cascade_towers", "", str, "one word per stage from auto|teacher|student, as --ensemble_towers; '' = auto for all")
-_define("cascade_every_n", "", str, "one every_n per stage (ignored for teachers); '' = --every_n for all")
+_define("cascade_every_n", "", str, "one every_n per stage (ignored for H-LSTM teachers); '' = --every_n for all; a NeXtVLAD stage: as "
+        "--ensemble_every_n (0 or an empty entry = the grid its checkpoint records)")
 _define("cascade_sampling", "", str, "one --student_sampling word per stage (ignored for teachers); '' = --student_sampling for all")
 _define("cascade_confidence", "", str, "top1 (the video's largest prediction) | margin (largest - second largest); '' = top1")
 _define("cascade_thresholds", "", str, "one value per gate (stages - 1): a video whose confidence is >= t_k is settled at stage k "

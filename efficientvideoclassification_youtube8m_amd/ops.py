@@ -1442,6 +1442,48 @@ def frames_gather_packed(x, num_frames, row_off, every_n, R, Rp, out, out_bf16=N
               1 if normalize else 0, _p(out), _p(out_bf16), _stream())
 
 
+def check_row_selection(sel, B):
+    """The host validation of a row selection before any launch reads it: ``sel`` (any integer sequence) must be strictly ascending and
+    lie in 0 .. B - 1, and not be empty.  Returns it as an int32 numpy array.  The kernels trust what this accepted."""
+    import numpy as np
+    s = np.asarray(sel)
+    if s.ndim != 1 or s.size == 0 or not np.issubdtype(s.dtype, np.integer):
+        raise ValueError("row selection: a non-empty 1-D integer sequence is needed (got shape %s, dtype %s)" % (s.shape, s.dtype))
+    s = s.astype(np.int64)
+    if s.min() < 0 or s.max() >= B:
+        raise ValueError("row selection: entries must lie in 0 .. %d (got %d .. %d)" % (B - 1, int(s.min()), int(s.max())))
+    bad = np.flatnonzero(np.diff(s) <= 0)
+    if bad.size:
+        i = int(bad[0]) + 1
+        raise ValueError("row selection: entries must be strictly ascending (entry %d is %d after %d)" % (i, int(s[i]), int(s[i - 1])))
+    return s.astype(np.int32)
+
+
+def frames_gather_packed_sel(x, num_frames, row_off, sel, every_n, R, Rp, out=None, out_bf16=None, normalize=False):
+    """frames_gather_packed for the videos sel[0 .. b') of the unchanged batch x [B, T, F]: packed video j is source
+    video sel[j].  row_off: device int32 [b' + 1] (GridPlan over the selected counts); sel: device int32 [b'], accepted by
+    check_row_selection on the host before this call.  out (f32) may be None: the bf16 rows alone."""
+    B, T, F = x.shape
+    bs = sel.numel()
+    is_u8 = x.dtype == torch.uint8
+    assert x.is_contiguous() and sel.dtype == torch.int32 and sel.is_contiguous()
+    assert out is None or (out.is_contiguous() and out.dtype == F32 and out.shape[0] >= Rp and out.shape[1] == F)
+    assert out_bf16 is None or (out_bf16.is_contiguous() and out_bf16.dtype == BF16 and out_bf16.shape[0] >= Rp and out_bf16.shape[1] == F)
+    assert row_off.dtype == torch.int32 and row_off.numel() == bs + 1 and num_frames.dtype == torch.int32 and num_frames.numel() == B
+    _lib.call("evc_frames_gather_packed_sel", None if is_u8 else _p(x), _p(x) if is_u8 else None, _p(num_frames), _p(row_off), _p(sel), B, bs,
+              T, F, every_n, R, Rp, 1 if normalize else 0, _p(out), _p(out_bf16), _stream())
+
+
+def scatter_rows(src, sel, dst):
+    """dst[sel[j]] = src[j] for the rows of src (2-D f32, rows contiguous, any row stride); the other rows of dst keep their contents.
+    sel: device int32 [src.shape[0]], accepted by check_row_selection(sel, dst.shape[0]) on the host before this call."""
+    assert src.dim() == 2 and dst.dim() == 2 and src.dtype == F32 and dst.dtype == F32 and src.shape[1] == dst.shape[1]
+    assert src.shape[1] <= 1 or (src.stride(1) == 1 and dst.stride(1) == 1)
+    assert sel.dtype == torch.int32 and sel.is_contiguous() and sel.numel() == src.shape[0] and src.shape[0] <= dst.shape[0]
+    _lib.call("evc_scatter_rows", _p(src), src.stride(0), _p(sel), src.shape[0], dst.shape[0], src.shape[1], _p(dst), dst.stride(0), _stream())
+    return dst
+
+
 def nextvlad_aggregate_packed_fwd(a, xe, row_off, B, T, G, K, D, R, max_k, c2, V, asum):
     """nextvlad_aggregate_fwd over packed rows: video b's a / xe rows are row_off[b] .. row_off[b+1] (device int32 [B+1])."""
     assert row_off.dtype == torch.int32 and row_off.numel() == B + 1

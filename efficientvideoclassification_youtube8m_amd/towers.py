@@ -9,6 +9,7 @@ from __future__ import annotations
 import math
 from collections import OrderedDict
 
+import numpy as np
 import torch
 
 from . import ops
@@ -860,6 +861,9 @@ class NeXtVladTower(TowerBase):
             R = ops.grid_capacity(B, self.T, self.every_n)
             self.row_off = torch.zeros(B + 1, dtype=torch.int32, device=dev)
             self._row_off_host = [torch.zeros(B + 1, dtype=torch.int32).pin_memory() for _ in range(2)]
+            if not self.training:                                    # a served subset of the batch's videos (forward(sel=...))
+                self.sel = torch.zeros(B, dtype=torch.int32, device=dev)
+                self._sel_host = [torch.zeros(B, dtype=torch.int32).pin_memory() for _ in range(2)]
             self._row_off_done = [None, None]
             self._uploads = 0
         else:
@@ -867,6 +871,7 @@ class NeXtVladTower(TowerBase):
             if self.training and self.R % 32:
                 raise ValueError("batch_size x iterations = %d must be a multiple of 32 (row count of the TN weight-gradient products)" % self.R)
             R = self.R
+        self.cap = B                                                 # videos the buffers hold (forward-only grid towers serve B <= cap)
         self.Bk = ops.round_up(B, 32)
         self.r = torch.empty((R, F), dtype=F32, device=dev)
         if not grid:
@@ -912,11 +917,14 @@ class NeXtVladTower(TowerBase):
             self.colsum_ws = torch.empty(32 * E, dtype=F32, device=dev)    # partial rows of the two bias-gradient column sums
             self.dWa_pad = torch.empty((AP, E), dtype=F32, device=dev)      # the attention weight gradient on a whole tile of rows
 
-    def _plan_rows(self, num_frames, num_frames_host):
+    def _plan_rows(self, num_frames, num_frames_host, sel=None):
         """Grid mode: this batch's packed layout from the HOST frame counts (launch sizes and offsets without a device sync);
-        row_off goes up through one of two pinned buffers, reused only once its earlier copy has completed."""
+        row_off goes up through one of two pinned buffers, reused only once its earlier copy has completed.  sel (int32 numpy,
+        accepted by ops.check_row_selection): the layout of those videos alone, and sel itself goes up the same way."""
         if num_frames_host is None:
             num_frames_host = num_frames.cpu().numpy()       # an explicit device sync: callers that have the counts on the host pass them
+        if sel is not None:
+            num_frames_host = np.asarray(num_frames_host).reshape(-1)[sel]
         plan = ops.GridPlan(num_frames_host, self.every_n, self.T)
         if plan.B != self.B:
             raise ValueError("num_frames_host holds %d videos, the batch %d" % (plan.B, self.B))
@@ -926,19 +934,35 @@ class NeXtVladTower(TowerBase):
         self._uploads += 1
         if self._row_off_done[slot] is not None:
             self._row_off_done[slot].synchronize()
-        self._row_off_host[slot].copy_(torch.from_numpy(plan.row_off))
-        self.row_off.copy_(self._row_off_host[slot], non_blocking=True)
+        B = plan.B
+        self._row_off_host[slot][:B + 1].copy_(torch.from_numpy(plan.row_off))
+        self.row_off[:B + 1].copy_(self._row_off_host[slot][:B + 1], non_blocking=True)
+        if sel is not None:
+            self._sel_host[slot][:B].copy_(torch.from_numpy(sel))
+            self.sel[:B].copy_(self._sel_host[slot][:B], non_blocking=True)
         ev = self._row_off_done[slot] = torch.cuda.Event()
         ev.record()
         self.plan, self.R, self.Rp = plan, plan.R, plan.Rp
         return plan
 
-    def forward(self, x, num_frames, uniform=None, normalize=True, is_training=True, num_frames_host=None):
+    def forward(self, x, num_frames, uniform=None, normalize=True, is_training=True, num_frames_host=None, sel=None):
         """x [B,T,F] float32 or uint8 raw frames; uniform [B,S] f32 in [0,1): the frame-sampling draw (sampled mode; not read
-        in grid mode, which takes num_frames_host, the frame counts on the host, instead)."""
+        in grid mode, which takes num_frames_host, the frame counts on the host, instead).
+        A forward-only grid tower keeps the buffers it allocated: a batch of fewer videos uses their first rows.  sel (such a tower
+        only): a strictly ascending host sequence of video numbers - the tower runs on those b' videos of the
+        unchanged batch alone, and pred / state hold b' rows, row j for video sel[j]."""
         B = x.shape[0]
+        serving = self.frames == "grid" and not self.training
+        if sel is not None:
+            if not serving:
+                raise ValueError("forward(sel=...) is built for forward-only grid towers (training=False, frames='grid')")
+            sel = ops.check_row_selection(sel, B)                    # (on the host, before any launch)
+            B = int(sel.shape[0])
         if B != self.B:
-            self._alloc(B)
+            if serving and B <= self.cap:
+                self.B = B
+            else:
+                self._alloc(B)
         if self.precision != "bf16":
             raise NotImplementedError("NeXtVladTower has no split-bf16 mode")
         grid = self.frames == "grid"
@@ -947,9 +971,13 @@ class NeXtVladTower(TowerBase):
         if grid:
             if x.shape[1] != self.T:
                 raise ValueError("the batch holds %d frames per video, the tower was built for max_frames=%d" % (x.shape[1], self.T))
-            plan = self._plan_rows(num_frames, num_frames_host)
+            plan = self._plan_rows(num_frames, num_frames_host, sel)
             R, Rp = plan.R, plan.Rp
-            ops.frames_gather_packed(x, num_frames, self.row_off, self.every_n, R, Rp, self.r, self.r_bf, normalize=normalize)
+            row_off = self.row_off[:B + 1]
+            if sel is None:
+                ops.frames_gather_packed(x, num_frames, row_off, self.every_n, R, Rp, self.r, self.r_bf, normalize=normalize)
+            else:                                                # (the forward reads the bf16 rows alone)
+                ops.frames_gather_packed_sel(x, num_frames, row_off, self.sel[:B], self.every_n, R, Rp, None, self.r_bf, normalize=normalize)
         else:
             R = self.R
             ops.sample_frames_gather(x, uniform, num_frames, self.r, self.idx, normalize=normalize)
@@ -969,7 +997,7 @@ class NeXtVladTower(TowerBase):
         ops.nextvlad_assign_fwd(self.act, R, G, K, bc.mean, bc.var, bc.gamma(), bc.beta(), self.attl, self.a)
         if grid:
             agg = ops.nextvlad_aggregate_packed_fwd if self.training else ops.nextvlad_aggregate_packed_fwd_mfma      # (the same bits)
-            agg(self.a, self.xe, self.row_off, B, self.T, G, K, D, R, plan.max_k, st.p(self.C2), self.Vv, self.asum)
+            agg(self.a, self.xe, row_off, B, self.T, G, K, D, R, plan.max_k, st.p(self.C2), self.Vv, self.asum)
         else:
             ops.nextvlad_aggregate_fwd(self.a, self.xe, B, S, G, K, D, st.p(self.C2), self.Vv, self.asum)
         ops.nextvlad_normalize_fwd(self.Vv, B, K, D, self.U, self.nrm)
@@ -982,9 +1010,11 @@ class NeXtVladTower(TowerBase):
         bg.stats(self.g1pre, B, is_training)
         ops.bn_apply(self.g1pre, B, Hg, bg.mean, bg.var, bg.gamma(), bg.beta(), True, y_bf16=self.g1_bf)
         ops.gemm_nt(self.g1_bf, self.shadow_fwd[self.G2], B, H, Hg, self.gl)
-        ops.nextvlad_gate_fwd(self.h, self.gl, self.out)
+        ops.nextvlad_gate_fwd(self.h[:B], self.gl[:B], self.out[:B])
         self._taped = self.training and is_training
-        return self.moe.forward(self.out)
+        if B == self.cap:
+            return self.moe.forward(self.out)
+        return self.moe.forward(self.out[:B], rows=B)[:B]         # (a forward-only grid tower on fewer videos than it was allocated for)
 
     def grad_stages(self):
         moe = [MoeHead.GATES, MoeHead.EXPERTS, MoeHead.EBIAS]
@@ -1054,15 +1084,15 @@ class NeXtVladTower(TowerBase):
 
     @property
     def pred(self):
-        return self.moe.pred
+        return self.moe.pred if self.B == self.cap else self.moe.pred[:self.B]
 
     @property
     def state(self):
-        return self.out
+        return self.out if self.B == self.cap else self.out[:self.B]
 
     @property
     def rowsum(self):
-        return self.moe.rowsum
+        return self.moe.rowsum if self.B == self.cap else self.moe.rowsum[:self.B]
 
 
 class LogisticTower(TowerBase):

@@ -25,6 +25,10 @@ no student_state_loss is reported and --train_dir only receives events.jsonl.
 --cascade_fractions, see inference.py; needs ``--run_once True``) evaluates a confidence cascade the same way: cascade.CascadeGraph merges
 each video's predictions from the last stage that ran it, loss and metrics are those of the merged predictions, and the share of the
 videos and the frames each stage read are logged and returned as ``cascade_stage_videos`` / ``cascade_stage_frames``.
+``--model NeXtVLADModel`` evaluates a NeXtVLAD checkpoint through distill.NeXtVladEvalGraph: a --teacher_dir checkpoint as
+teacher + student (the student's metrics, student_loss logged), a single-tower one as model/*, each tower on the grid its checkpoint
+records (--nextvlad_serve_every_n overrides); the graph is built for --train_dir's latest checkpoint, which must exist at the start.
+Ensemble members and cascade stages take their family from their own checkpoints, so H-LSTM and NeXtVLAD members mix.
 """
 from __future__ import annotations
 
@@ -55,8 +59,35 @@ def get_input_evaluation_tensors(reader, data_pattern, batch_size=1024, num_read
     return pipe
 
 
-def build_graph(reader, model, batch_size, device, student_only=False, label_loss=None):
-    """cs/validate.py:107-189 / cs/eval_finetune.py:108-175."""
+def nextvlad_source(reader, student_only=False):
+    """--model NeXtVLADModel: what is decided on the host, before the device is touched, from --train_dir's latest checkpoint - the graph
+    is built for the towers that checkpoint holds and the grids it records.  Returns {"ck", "sd", "tower", "every_n", "teacher_every_n"}:
+    tower 'both' for a distillation checkpoint (model/* and model_student/*: the student's metrics, student_state_loss logged),
+    'teacher' for a single-tower one; --nextvlad_serve_every_n overrides the served tower's grid."""
+    from . import inference
+    if student_only:
+        raise ValueError("eval_finetune with --model NeXtVLADModel: there is no convert / finetune step for this family, so no "
+                         "student-only checkpoint to evaluate; validate evaluates the student of a --teacher_dir run")
+    inference.check_nextvlad_serving_flags()
+    ck = latest_checkpoint(FLAGS.train_dir)
+    if ck is None:
+        raise IOError("unable to find a checkpoint at location: %s" % FLAGS.train_dir)
+    sd = torch.load(ck, map_location="cpu")
+    inference.check_model_family(sd, ck)
+    both = any(k.startswith("model_student/") and torch.is_tensor(v) for k, v in sd.items())
+    tower = "both" if both else inference.member_tower(sd, "teacher", ck)
+    every_n = inference.nextvlad_every_n(sd, "student" if both else "teacher", FLAGS.nextvlad_serve_every_n, ck)
+    inference.check_nextvlad_shapes(reader, sd, tower, ck)
+    return dict(ck=ck, sd=sd, tower=tower, every_n=every_n, teacher_every_n=inference.nextvlad_every_n(sd, "teacher"))
+
+
+def build_graph(reader, model, batch_size, device, student_only=False, label_loss=None, nextvlad=None):
+    """cs/validate.py:107-189 / cs/eval_finetune.py:108-175.  nextvlad: nextvlad_source() for --model NeXtVLADModel."""
+    if isinstance(model, frame_level_models.NeXtVLADModel):
+        from . import inference
+        src = nextvlad if nextvlad is not None else nextvlad_source(reader, student_only)
+        return inference.nextvlad_graph(reader, src["sd"], src["tower"], src["every_n"], batch_size, device, where=src["ck"],
+                                        teacher_every_n=src["teacher_every_n"], label_loss=label_loss)
     if not isinstance(model, frame_level_models.HierarchicalLstmModel):
         raise NotImplementedError("validate.py unpacks the H-LSTM (state, result) pair (cs/validate.py:150,157); "
                                   "model %s cannot be evaluated by the reference either" % type(model).__name__)
@@ -67,26 +98,28 @@ def build_graph(reader, model, batch_size, device, student_only=False, label_los
                      label_loss=label_loss)
 
 
-def build_ensemble(reader, model, spec, batch_size, device, label_loss=None):
-    """The members of an inference.ensemble_spec(), restored, behind one step() that returns their combination."""
+def build_ensemble(reader, model, spec, batch_size, device, label_loss=None, loaded=None):
+    """The members of an inference.ensemble_spec(), restored, behind one step() that returns their combination.  loaded: the result of
+    inference.load_members(spec) when the caller has read the checkpoints already (evaluate: before the device is touched)."""
     from . import inference
-    if not isinstance(model, frame_level_models.HierarchicalLstmModel):
-        raise NotImplementedError("an ensemble serves H-LSTM teacher / student towers; model %s has no path here" % type(model).__name__)
-    sds, members, _ = inference.load_members(spec)
-    graph = inference.build_ensemble_graph(reader, members, batch_size, device, spec["sampling"])
+    if not isinstance(model, (frame_level_models.HierarchicalLstmModel, frame_level_models.NeXtVLADModel)):
+        raise NotImplementedError("an ensemble serves H-LSTM and NeXtVLAD teacher / student towers; model %s has no path here" % type(model).__name__)
+    sds, members, _ = loaded if loaded is not None else inference.load_members(spec)
+    graph = inference.build_ensemble_graph(reader, members, batch_size, device, spec["sampling"], sds)
     graph.restore(sds)
     for d, tower, every_n in members:
         logging.info("ensemble member: the %s tower of %s%s", tower, d, " at every_n = %d" % every_n if tower == "student" else "")
     return _CombinedMembers(graph, spec, max(int(sd.get("global_step", 0)) for sd in sds), label_loss)
 
 
-def build_cascade(reader, model, spec, batch_size, device, label_loss=None):
-    """The stages of an inference.cascade_spec(), restored, behind one step() that returns the merged predictions."""
+def build_cascade(reader, model, spec, batch_size, device, label_loss=None, loaded=None):
+    """The stages of an inference.cascade_spec(), restored, behind one step() that returns the merged predictions.  loaded: as
+    build_ensemble."""
     from . import inference
-    if not isinstance(model, frame_level_models.HierarchicalLstmModel):
-        raise NotImplementedError("a cascade serves H-LSTM teacher / student towers; model %s has no path here" % type(model).__name__)
-    sds, members, _ = inference.load_members(spec)
-    graph = inference.build_cascade_graph(reader, members, batch_size, device, spec)
+    if not isinstance(model, (frame_level_models.HierarchicalLstmModel, frame_level_models.NeXtVLADModel)):
+        raise NotImplementedError("a cascade serves H-LSTM and NeXtVLAD teacher / student towers; model %s has no path here" % type(model).__name__)
+    sds, members, _ = loaded if loaded is not None else inference.load_members(spec)
+    graph = inference.build_cascade_graph(reader, members, batch_size, device, spec, sds)
     graph.restore(sds)
     inference.log_cascade_stages(spec, members)
     return _CascadeStages(graph, spec, max(int(sd.get("global_step", 0)) for sd in sds), label_loss)
@@ -188,9 +221,10 @@ def evaluation_loop(graph, reader, label_loss_fn, summary_writer, evl_metrics, l
         # forever - or ending a --run_once evaluation with no result and no failure - would hide it.
         logging.info("checkpoint %s disappeared before it could be loaded (%s); will look again.", ck, e)
         return last_global_step_val, None
+    from .inference import check_model_family, warn_sampling
+    check_model_family(sd, ck)
     graph.restore(sd)
     if graph.student is not None:
-        from .inference import warn_sampling
         warn_sampling(sd, FLAGS.student_sampling, ck)
     global_step_val = int(sd.get("global_step", 0))
     if global_step_val == last_global_step_val:
@@ -283,21 +317,36 @@ def evaluate(student_only=False, max_evals=None):
         raise ValueError("--cascade_dirs: evaluate a cascade with validate.py (each stage names its own tower)")
     if cascade is not None and cascade["stage_file"]:
         raise ValueError("--cascade_stage_file is written by inference.py only")
+    reader = get_reader()
+    model = find_class_by_name(FLAGS.model, [frame_level_models, video_level_models])()
+    nextvlad = loaded = None                     # the NeXtVLAD family's host checks, and every member's: before the device is touched
+    if isinstance(model, frame_level_models.NeXtVLADModel) and spec is None and cascade is None:
+        nextvlad = nextvlad_source(reader, student_only)
+    elif spec is not None or cascade is not None:
+        if isinstance(model, (frame_level_models.HierarchicalLstmModel, frame_level_models.NeXtVLADModel)):
+            from .inference import load_members
+            loaded = load_members(cascade if cascade is not None else spec)
+    elif isinstance(model, frame_level_models.HierarchicalLstmModel):
+        ck = latest_checkpoint(FLAGS.train_dir)                          # (a --model that is not this checkpoint's family: refused here)
+        if ck:
+            from .inference import check_model_family
+            try:
+                check_model_family(torch.load(ck, map_location="cpu"), ck)
+            except FileNotFoundError:
+                pass                                                     # replaced by the trainer meanwhile: evaluation_loop looks again
     device = "cuda:%d" % FLAGS.gpu
     torch.cuda.set_device(FLAGS.gpu)
     ops.check_device(FLAGS.gpu)
-    reader = get_reader()
-    model = find_class_by_name(FLAGS.model, [frame_level_models, video_level_models])()
     label_loss_fn = find_class_by_name(FLAGS.label_loss, [losses])()
     label_loss_fn.check(reader.num_classes)
     if FLAGS.eval_data_pattern == "":
         raise IOError("'eval_data_pattern' was not specified. Nothing to evaluate.")
     if cascade is not None:
-        graph = build_cascade(reader, model, cascade, FLAGS.batch_size, device, label_loss=label_loss_fn)
+        graph = build_cascade(reader, model, cascade, FLAGS.batch_size, device, label_loss=label_loss_fn, loaded=loaded)
     elif spec is None:
-        graph = build_graph(reader, model, FLAGS.batch_size, device, student_only, label_loss=label_loss_fn)
+        graph = build_graph(reader, model, FLAGS.batch_size, device, student_only, label_loss=label_loss_fn, nextvlad=nextvlad)
     else:
-        graph = build_ensemble(reader, model, spec, FLAGS.batch_size, device, label_loss=label_loss_fn)
+        graph = build_ensemble(reader, model, spec, FLAGS.batch_size, device, label_loss=label_loss_fn, loaded=loaded)
     logging.info("built evaluation graph")
     for tw in (graph.teacher, graph.student):
         if tw is not None:

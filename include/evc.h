@@ -888,6 +888,18 @@ int evc_nextvlad_aggregate_packed_fwd_mfma(const float* a, const float* xe, cons
  * as bf16.  F % 4 == 0. */
 int evc_frames_gather_packed(const float* x, const uint8_t* x_u8, const int32_t* num_frames, const int32_t* row_off, int B, int T, int F,
                              int every_n, int R, int Rp, int normalize, float* out, evc_bf16* out_bf16, void* stream);
+/* evc_frames_gather_packed over a subset of the batch's videos: packed video j < Bsel - the rows row_off[j] ..
+ * row_off[j+1], row_off int32 [Bsel + 1] - reads the frames and the count of source video sel[j] of the unchanged batch (x / x_u8
+ * [B][T][F], num_frames [B]; sel int32 [Bsel] on the device).  The same arithmetic, bit for bit; rows R .. Rp zeros.  out may be NULL
+ * (the bf16 rows alone), but not both outputs.  sel is NOT checked on the device: the caller guarantees 0 <= sel[j] < B (ops.py
+ * validates it on the host: strictly ascending, in range).  Bad shapes EVC_ERR_BAD_SHAPE, NULL operands EVC_ERR_BAD_ARG, no launch. */
+int evc_frames_gather_packed_sel(const float* x, const uint8_t* x_u8, const int32_t* num_frames, const int32_t* row_off, const int32_t* sel,
+                                 int B, int Bsel, int T, int F, int every_n, int R, int Rp, int normalize, float* out, evc_bf16* out_bf16,
+                                 void* stream);
+/* dst[sel[j]][0 .. C) = src[j][0 .. C) for j < n (f32; row strides ld_src / ld_dst in floats; float4 accesses where bases and strides
+ * allow, scalar otherwise and for the tail columns).  Every other row of dst is left untouched.  n <= rows_dst; n == 0 launches
+ * nothing.  sel (device int32 [n]) is NOT checked on the device: the caller guarantees distinct entries in 0 .. rows_dst - 1. */
+int evc_scatter_rows(const float* src, int64_t ld_src, const int32_t* sel, int n, int rows_dst, int C, float* dst, int64_t ld_dst, void* stream);
 /* U[b][k][:] = V[b][k][:] / n, n = norms[b][k] = max(|V[b][k][:]|, 1e-12);  dV = (dU - U (U . dU)) / n. */
 int evc_nextvlad_normalize_fwd(const float* V, int B, int K, int D, float* U, float* norms, void* stream);
 int evc_nextvlad_normalize_bwd(const float* V, const float* norms, const float* dU, int B, int K, int D, float* dV, void* stream);
