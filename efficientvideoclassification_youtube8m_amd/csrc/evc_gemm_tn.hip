@@ -1,4 +1,4 @@
-// TN products (weight gradients without transposes) and the fused MoE weight update (4.4b).
+// TN products (weight gradients without transposes, LAB_NOTEBOOK.md 4.2b) and the fused MoE weight update (4.4b).
 #include "gemm_shared.h"
 
 // ===========================================================================
@@ -83,76 +83,89 @@ __global__ __launch_bounds__(Cfg::NT) void gemm_tn_kernel(GemmOperandsT p, Store
   }
 }
 
-static int gemm_tn_impl(const evc_bf16* A, int64_t lda, const evc_bf16* B, int64_t ldb, int N1, const evc_bf16* B2, int64_t ldb2,
-                        int c_col2, float* C, int64_t ldc, int M, int N, int K, int row_interleave_H, int accumulate, void* stream,
-                        int slab_rows = 0, const int32_t* rows_per_slab = nullptr) {
+// ---- host side: every entry is its own refusals, then tn_operands, the tile / split choice, launch_tn ----
+// The refusals the product entries share, in the order every entry has made them, worded with the entry the caller used.  nslab: the K split of
+// the slab entries; slabs_ok: their slab image's rule.
+static int tn_args_ok(const char* entry, const void* A, int64_t lda, const void* B, int64_t ldb, int M, int N, int K, int row_interleave_H,
+                      int N1, const void* B2, int64_t ldb2, int c_col2, int nslab = 1, bool slabs_ok = true) {
   EVC_REQUIRE(M >= 8 && N >= 8 && K > 0 && M % 8 == 0 && N % 8 == 0 && K % 32 == 0, EVC_ERR_BAD_SHAPE,
-              "evc_gemm_tn: needs M %% 8 == 0, N %% 8 == 0, K %% 32 == 0 (M=%d N=%d K=%d)", M, N, K);
+              "%s: needs M %% 8 == 0, N %% 8 == 0, K %% 32 == 0 (M=%d N=%d K=%d)", entry, M, N, K);
+  EVC_REQUIRE(nslab >= 1 && nslab <= K / 32, EVC_ERR_BAD_SHAPE, "%s: needs 1 <= nslab <= K/32 (K=%d nslab=%d)", entry, K, nslab);
   EVC_REQUIRE(lda % 8 == 0 && ldb % 8 == 0 && ((uintptr_t)A % 16) == 0 && ((uintptr_t)B % 16) == 0, EVC_ERR_BAD_ALIGN,
-              "evc_gemm_tn: operands must be 16-byte aligned (lda=%ld ldb=%ld)", (long)lda, (long)ldb);
-  EVC_REQUIRE(row_interleave_H == 0 || M == 4 * row_interleave_H, EVC_ERR_BAD_SHAPE, "evc_gemm_tn: row_interleave_H needs M == 4*H");
+              "%s: operands must be 16-byte aligned (lda=%ld ldb=%ld)", entry, (long)lda, (long)ldb);
+  EVC_REQUIRE(slabs_ok, EVC_ERR_BAD_ALIGN, "%s: slabs == NULL or slab_stride < M * ldc", entry);
+  EVC_REQUIRE(row_interleave_H == 0 || M == 4 * row_interleave_H, EVC_ERR_BAD_SHAPE, "%s: row_interleave_H needs M == 4*H", entry);
   EVC_REQUIRE(!B2 || (N1 > 0 && N1 < N && N1 % 256 == 0 && ldb2 % 8 == 0 && ((uintptr_t)B2 % 16) == 0 && c_col2 >= N1), EVC_ERR_BAD_SHAPE,
-              "evc_gemm_tn2: N1=%d must be a multiple of 256 inside (0, N=%d), B2 16-byte aligned with ldb2 %% 8 == 0, c_col2=%d >= N1", N1, N, c_col2);
-  hipStream_t st = (hipStream_t)stream;
+              "%s: N1=%d must be a multiple of 256 inside (0, N=%d), B2 16-byte aligned with ldb2 %% 8 == 0, c_col2=%d >= N1", entry, N1, N, c_col2);
+  EVC_REQUIRE((long)ceil_div(K / 32, nslab) * (nslab - 1) < K / 32, EVC_ERR_BAD_SHAPE, "%s: nslab=%d leaves an empty slab at K=%d", entry, nslab, K);
+  return EVC_OK;
+}
+
+// operands of C = A^T . B over K rows, B2 != NULL: with a second column segment behind the first N1 columns
+static inline GemmOperandsT tn_operands(const evc_bf16* A, int64_t lda, const evc_bf16* B, int64_t ldb, int M, int N, int K,
+                                        int N1 = 0, const evc_bf16* B2 = nullptr, int64_t ldb2 = 0, int c_col2 = 0) {
   GemmOperandsT p{A, lda, B, ldb, M, N, K / 32};
   if (B2) { p.B2 = B2; p.ldb2 = ldb2; p.N1 = N1; p.c_col2 = c_col2; }
-  // live rows per time slab (evc_gemm_tn2_rows): the K walk covers ceil(rows / 32) steps of every slab.  More than 16 non-empty slabs, nothing
-  // dead or nothing live: the plain walk over all K rows (the dead rows of A are zeros: the same sums).
-  bool seg = false;
-  if (rows_per_slab && slab_rows > 0 && slab_rows % 32 == 0 && K % slab_rows == 0 && !evc_deterministic()) {
-    const int nslabs = K / slab_rows, slab_steps = slab_rows / 32;
-    int n = 0, total = 0;
-    // the segment walk indexes both operands by 32-bit BYTE offsets from their un-advanced bases (gemm_core_tn.h: (start + off) * 64 * ld): the
-    // last K row must stay below 4 GiB in the wider operand - beyond that the plain walk (which advances the base pointers per split) runs
-    const long ld_max = lda > ldb ? (long)lda : (long)ldb;
-    bool ok = (long)nslabs * slab_steps < 65536 && (long)K * (B2 && ldb2 > ld_max ? (long)ldb2 : ld_max) * 2 < (1L << 32);
-    for (int t = 0; t < nslabs && ok; ++t) {
-      int r = rows_per_slab[t] < 0 ? 0 : (rows_per_slab[t] > slab_rows ? slab_rows : rows_per_slab[t]);
-      const int steps = (r + 31) / 32;
-      if (steps == 0) continue;
-      if (n == 16) { ok = false; break; }
-      p.seg_start[n] = (unsigned short)(t * slab_steps); p.seg_len[n] = (unsigned short)steps;
-      ++n; total += steps;
-    }
-    if (ok && total > 0 && total < K / 32) { seg = true; p.nseg = n; p.nk = total; K = total * 32; }
+  return p;
+}
+
+// live rows per time slab (evc_gemm_tn2_rows): the K walk covers ceil(rows / 32) steps of every slab.  Fills p's segment table and sets p.nk to the
+// live steps; false with more than 16 non-empty slabs, nothing dead or nothing live: the plain walk over all K rows (the dead rows of A are
+// zeros: the same sums), which ignores what the table holds by then.
+static bool tn_live_segments(GemmOperandsT& p, int K, int slab_rows, const int32_t* rows_per_slab) {
+  if (slab_rows % 32 != 0 || K % slab_rows != 0) return false;
+  const int nslabs = K / slab_rows, slab_steps = slab_rows / 32;
+  // the segment walk indexes both operands by 32-bit BYTE offsets from their un-advanced bases (gemm_core_tn.h: (start + off) * 64 * ld): the
+  // last K row must stay below 4 GiB in the wider operand - beyond that the plain walk (which advances the base pointers per split) runs
+  const long ld_max = p.lda > p.ldb ? p.lda : p.ldb;
+  if ((long)nslabs * slab_steps >= 65536 || (long)K * (p.B2 && p.ldb2 > ld_max ? p.ldb2 : ld_max) * 2 >= (1L << 32)) return false;
+  int n = 0, total = 0;
+  for (int t = 0; t < nslabs; ++t) {
+    const int r = rows_per_slab[t] < 0 ? 0 : (rows_per_slab[t] > slab_rows ? slab_rows : rows_per_slab[t]);
+    const int steps = (r + 31) / 32;
+    if (steps == 0) continue;
+    if (n == 16) return false;
+    p.seg_start[n] = (unsigned short)(t * slab_steps); p.seg_len[n] = (unsigned short)steps;
+    ++n; total += steps;
   }
-  typedef TileCfg2<128, 1, 128, 2, 4, 5, true> CfgTn128;
+  if (total == 0 || total >= K / 32) return false;
+  p.nseg = n; p.nk = total;
+  return true;
+}
+
+// one launch of tm x tn tiles x s.splits K ranges; seg: on the kernel that walks p's live segments
+template <class Cfg>
+static int launch_tn(const GemmOperandsT& p, StoreParamsT s, bool seg, int tm, int tn, hipStream_t st) {
+  s.ksteps_per_split = ceil_div(p.nk, s.splits);
+  if (seg) launch_cfg<Cfg>(gemm_tn_kernel<Cfg, true>, tm * tn * s.splits, st, p, s, tm, tn);
+  else launch_cfg<Cfg>(gemm_tn_kernel<Cfg>, tm * tn * s.splits, st, p, s, tm, tn);
+  EVC_LAUNCH_CHECK();
+  return EVC_OK;
+}
+
+static int gemm_tn_impl(const char* entry, const evc_bf16* A, int64_t lda, const evc_bf16* B, int64_t ldb, int N1, const evc_bf16* B2, int64_t ldb2,
+                        int c_col2, float* C, int64_t ldc, int M, int N, int K, int row_interleave_H, int accumulate, void* stream,
+                        int slab_rows = 0, const int32_t* rows_per_slab = nullptr) {
+  EVC_TRY(tn_args_ok(entry, A, lda, B, ldb, M, N, K, row_interleave_H, N1, B2, ldb2, c_col2));
+  hipStream_t st = (hipStream_t)stream;
+  GemmOperandsT p = tn_operands(A, lda, B, ldb, M, N, K, N1, B2, ldb2, c_col2);
+  const bool seg = rows_per_slab && slab_rows > 0 && !evc_deterministic() && tn_live_segments(p, K, slab_rows, rows_per_slab);
+  K = p.nk * 32;                                 // (the live rows)
+  StoreParamsT s{C, ldc, M, N, row_interleave_H, accumulate, 1, 0, 0};
+  const int tm1 = ceil_div(M, 128), tn1 = ceil_div(N, 128);
   // short contractions (the student's L2: K = 5 x 256 rows) on 128x128 tiles without split-K: the atomic join of
   // 256x256 partial tiles costs more than the product itself there (81 -> 36 us at 4096 x 1024 x 1280); from
   // K ~ 5000 on the 256x256 split-K form is faster again (92 vs 99 us)
-  if (forced_tile() == 11 || (forced_tile() == 0 && K <= 2048 && (long)ceil_div(M, 128) * ceil_div(N, 128) >= 192)) {
-    const int tm1 = ceil_div(M, 128), tn1 = ceil_div(N, 128);
-    StoreParamsT s1{C, ldc, M, N, row_interleave_H, accumulate, 1, p.nk, 0};
-    if (seg) launch_cfg<CfgTn128>(gemm_tn_kernel<CfgTn128, true>, tm1 * tn1, st, p, s1, tm1, tn1);
-    else launch_cfg<CfgTn128>(gemm_tn_kernel<CfgTn128>, tm1 * tn1, st, p, s1, tm1, tn1);
-    EVC_LAUNCH_CHECK();
-    return EVC_OK;
-  }
+  const bool short128 = forced_tile() == 11 || (forced_tile() == 0 && K <= 2048 && (long)tm1 * tn1 >= 192);
   // a narrow strip (N <= 128: the last 128 input columns of an L1 layer-0 kernel gradient, see engine._wgrad_tn): 128x128 tiles,
   // K split until ~256 workgroups exist - a 256-column tile would do half of its MFMAs on columns that do not exist
-  if (forced_tile() == 0 && N <= 128 && !B2) {
-    const int tm1 = ceil_div(M, 128);
-    int splits = 256 / tm1;
-    if (splits > K / 1024) splits = K / 1024;
-    if (splits < 1 || evc_deterministic()) splits = 1;
-    while (splits > 1 && (long)ceil_div(p.nk, splits) * (splits - 1) >= p.nk) --splits;     // no empty split
-    StoreParamsT s1{C, ldc, M, N, row_interleave_H, accumulate, splits, ceil_div(p.nk, splits), 0};
-    if (splits > 1 && !accumulate) EVC_CHECK_HIP(hipMemset2DAsync(C, ldc * sizeof(float), 0, (size_t)N * sizeof(float), M, st));
-    if (seg) launch_cfg<CfgTn128>(gemm_tn_kernel<CfgTn128, true>, tm1 * splits, st, p, s1, tm1, 1);
-    else launch_cfg<CfgTn128>(gemm_tn_kernel<CfgTn128>, tm1 * splits, st, p, s1, tm1, 1);
-    EVC_LAUNCH_CHECK();
-    return EVC_OK;
-  }
-  const int tm = ceil_div(M, CfgPlainV2::BM), tn = ceil_div(N, CfgPlainV2::BU);
-  int splits = 256 / (tm * tn);
-  if (splits > K / 1024) splits = K / 1024;     // keep >= 32 K steps per split
-  if (splits < 1 || evc_deterministic()) splits = 1;
-  StoreParamsT s{C, ldc, M, N, row_interleave_H, accumulate, splits, ceil_div(p.nk, splits), 0};
-  if (splits > 1 && !accumulate) EVC_CHECK_HIP(hipMemset2DAsync(C, ldc * sizeof(float), 0, (size_t)N * sizeof(float), M, st));
-  if (seg) launch_cfg<CfgPlainV2>(gemm_tn_kernel<CfgPlainV2, true>, tm * tn * splits, st, p, s, tm, tn);
-  else launch_cfg<CfgPlainV2>(gemm_tn_kernel<CfgPlainV2>, tm * tn * splits, st, p, s, tm, tn);
-  EVC_LAUNCH_CHECK();
-  return EVC_OK;
+  const bool strip128 = !short128 && forced_tile() == 0 && N <= 128 && !B2;
+  const bool tile128 = short128 || strip128;
+  const int tm = tile128 ? tm1 : ceil_div(M, CfgPlainV2::BM), tn = short128 ? tn1 : strip128 ? 1 : ceil_div(N, CfgPlainV2::BU);
+  // K splits joined by atomics until ~256 workgroups exist, >= 32 K steps each; none with EVC_DETERMINISTIC
+  if (!short128 && !evc_deterministic()) s.splits = split_k(256 / (tm * tn), p.nk, 32);
+  if (s.splits > 1 && !accumulate) EVC_CHECK_HIP(hipMemset2DAsync(C, ldc * sizeof(float), 0, (size_t)N * sizeof(float), M, st));
+  return tile128 ? launch_tn<CfgTn128>(p, s, seg, tm, tn, st) : launch_tn<CfgPlainV2>(p, s, seg, tm, tn, st);
 }
 
 // evc_gemm_tn / evc_gemm_tn2 over TIME SLABS with a live prefix (round 5): the contraction index runs over K = nslabs * slab_rows rows, slab t
@@ -168,13 +181,13 @@ extern "C" int evc_gemm_tn2_rows(const evc_bf16* A, int64_t lda, const evc_bf16*
               "evc_gemm_tn2_rows: B1, N1, slab_rows, nslabs, rows_per_slab are required");
   EVC_REQUIRE(!B2 || N2 > 0, EVC_ERR_BAD_ARG, "evc_gemm_tn2_rows: N2=%d", N2);
   EVC_REQUIRE(!B2 || accumulate || c_col2 == N1, EVC_ERR_BAD_ARG, "evc_gemm_tn2_rows: segments that are not adjacent in C (c_col2=%d, N1=%d) need accumulate", c_col2, N1);
-  return gemm_tn_impl(A, lda, B1, ldb1, B2 ? N1 : 0, B2, ldb2, B2 ? c_col2 : 0, C, ldc, M, N1 + (B2 ? N2 : 0), slab_rows * nslabs, row_interleave_H, accumulate,
-                      stream, slab_rows, rows_per_slab);
+  return gemm_tn_impl("evc_gemm_tn2_rows", A, lda, B1, ldb1, B2 ? N1 : 0, B2, ldb2, B2 ? c_col2 : 0, C, ldc, M, N1 + (B2 ? N2 : 0), slab_rows * nslabs,
+                      row_interleave_H, accumulate, stream, slab_rows, rows_per_slab);
 }
 
 extern "C" int evc_gemm_tn(const evc_bf16* A, int64_t lda, const evc_bf16* B, int64_t ldb, float* C, int64_t ldc,
                            int M, int N, int K, int row_interleave_H, int accumulate, void* stream) {
-  return gemm_tn_impl(A, lda, B, ldb, 0, nullptr, 0, 0, C, ldc, M, N, K, row_interleave_H, accumulate, stream);
+  return gemm_tn_impl("evc_gemm_tn", A, lda, B, ldb, 0, nullptr, 0, 0, C, ldc, M, N, K, row_interleave_H, accumulate, stream);
 }
 
 extern "C" int evc_gemm_tn2(const evc_bf16* A, int64_t lda, const evc_bf16* B1, int64_t ldb1, int N1, const evc_bf16* B2, int64_t ldb2,
@@ -182,51 +195,31 @@ extern "C" int evc_gemm_tn2(const evc_bf16* A, int64_t lda, const evc_bf16* B1, 
   EVC_REQUIRE(B1 && B2 && N1 > 0 && N2 > 0, EVC_ERR_BAD_ARG, "evc_gemm_tn2: two column segments are required");
   EVC_REQUIRE(accumulate || c_col2 == N1, EVC_ERR_BAD_ARG, "evc_gemm_tn2: segments that are not adjacent in C (c_col2=%d, N1=%d) need accumulate "
               "(the split-K join adds into a C the caller has zeroed)", c_col2, N1);
-  return gemm_tn_impl(A, lda, B1, ldb1, N1, B2, ldb2, c_col2, C, ldc, M, N1 + N2, K, row_interleave_H, accumulate, stream);
-}
-
-// Split-K into slabs: slab s (s < nslab) = the partial product over K rows [s*ceil(K/32/nslab)*32, ...), stored plainly at
-// slabs + s*M*N (row stride N).  For products whose 256x256 tiles do not fill the chip and whose result is read once by a
-// pass that can add the slabs on the way (DBoF cluster-weight gradient: 8192 x 1152 x 16384 = 160 tiles): no atomics, no memset.
-extern "C" int evc_gemm_tn_slabs(const evc_bf16* A, int64_t lda, const evc_bf16* B, int64_t ldb, float* slabs, int M, int N, int K,
-                                 int nslab, void* stream) {
-  EVC_REQUIRE(M >= 8 && N >= 8 && K > 0 && M % 8 == 0 && N % 8 == 0 && K % 32 == 0 && nslab >= 1 && nslab <= K / 32, EVC_ERR_BAD_SHAPE,
-              "evc_gemm_tn_slabs: needs M %% 8 == 0, N %% 8 == 0, K %% 32 == 0, 1 <= nslab <= K/32 (M=%d N=%d K=%d nslab=%d)", M, N, K, nslab);
-  EVC_REQUIRE(lda % 8 == 0 && ldb % 8 == 0 && ((uintptr_t)A % 16) == 0 && ((uintptr_t)B % 16) == 0, EVC_ERR_BAD_ALIGN,
-              "evc_gemm_tn_slabs: operands must be 16-byte aligned (lda=%ld ldb=%ld)", (long)lda, (long)ldb);
-  GemmOperandsT p{A, lda, B, ldb, M, N, K / 32};
-  const int tm = ceil_div(M, CfgPlainV2::BM), tn = ceil_div(N, CfgPlainV2::BU);
-  const int per = ceil_div(p.nk, nslab);
-  EVC_REQUIRE((long)per * (nslab - 1) < p.nk, EVC_ERR_BAD_SHAPE, "evc_gemm_tn_slabs: nslab=%d leaves an empty slab at K=%d", nslab, K);
-  StoreParamsT s{slabs, N, M, N, 0, 0, nslab, per, (long)M * N};
-  launch_cfg<CfgPlainV2>(gemm_tn_kernel<CfgPlainV2>, tm * tn * nslab, (hipStream_t)stream, p, s, tm, tn);
-  EVC_LAUNCH_CHECK();
-  return EVC_OK;
+  return gemm_tn_impl("evc_gemm_tn2", A, lda, B1, ldb1, N1, B2, ldb2, c_col2, C, ldc, M, N1 + N2, K, row_interleave_H, accumulate, stream);
 }
 
 // Two column segments into slabs (EVC_DETERMINISTIC=1 weight gradients, round 5): evc_gemm_tn2's product with the K split stored as nslab plain partial
 // images instead of joined with atomics - slab s at slabs + s*slab_stride, each an [M][ldc] image like C (rows de-interleaved, the second segment
 // at column c_col2) - that evc_sum_slabs adds in slab order.  B2 == NULL: one segment of N1 columns.
+static int gemm_tn_slabs_impl(const char* entry, const evc_bf16* A, int64_t lda, const evc_bf16* B1, int64_t ldb1, int N1, const evc_bf16* B2, int64_t ldb2,
+                              int N2, int c_col2, float* slabs, int64_t ldc, int64_t slab_stride, int M, int K, int row_interleave_H, int nslab, void* stream) {
+  const int N = N1 + (B2 ? N2 : 0);
+  EVC_REQUIRE(N1 >= 8, EVC_ERR_BAD_SHAPE, "%s: N1=%d", entry, N1);
+  EVC_TRY(tn_args_ok(entry, A, lda, B1, ldb1, M, N, K, row_interleave_H, N1, B2, ldb2, c_col2, nslab, slabs && slab_stride >= (int64_t)M * ldc));
+  return launch_tn<CfgPlainV2>(tn_operands(A, lda, B1, ldb1, M, N, K, N1, B2, ldb2, c_col2), StoreParamsT{slabs, ldc, M, N, row_interleave_H, 0, nslab, 0, slab_stride},
+                               false, ceil_div(M, CfgPlainV2::BM), ceil_div(N, CfgPlainV2::BU), (hipStream_t)stream);
+}
 extern "C" int evc_gemm_tn2_slabs(const evc_bf16* A, int64_t lda, const evc_bf16* B1, int64_t ldb1, int N1, const evc_bf16* B2, int64_t ldb2,
                                   int N2, int c_col2, float* slabs, int64_t ldc, int64_t slab_stride, int M, int K, int row_interleave_H,
                                   int nslab, void* stream) {
-  const int N = N1 + (B2 ? N2 : 0);
-  EVC_REQUIRE(M >= 8 && N1 >= 8 && K > 0 && M % 8 == 0 && N % 8 == 0 && K % 32 == 0 && nslab >= 1 && nslab <= K / 32, EVC_ERR_BAD_SHAPE,
-              "evc_gemm_tn2_slabs: needs M %% 8 == 0, N %% 8 == 0, K %% 32 == 0, 1 <= nslab <= K/32 (M=%d N=%d K=%d nslab=%d)", M, N, K, nslab);
-  EVC_REQUIRE(lda % 8 == 0 && ldb1 % 8 == 0 && ((uintptr_t)A % 16) == 0 && ((uintptr_t)B1 % 16) == 0 && slabs && slab_stride >= (int64_t)M * ldc, EVC_ERR_BAD_ALIGN,
-              "evc_gemm_tn2_slabs: operands must be 16-byte aligned, slab_stride >= M * ldc");
-  EVC_REQUIRE(row_interleave_H == 0 || M == 4 * row_interleave_H, EVC_ERR_BAD_SHAPE, "evc_gemm_tn2_slabs: row_interleave_H needs M == 4*H");
-  EVC_REQUIRE(!B2 || (N1 % 256 == 0 && N2 > 0 && ldb2 % 8 == 0 && ((uintptr_t)B2 % 16) == 0 && c_col2 >= N1), EVC_ERR_BAD_SHAPE,
-              "evc_gemm_tn2_slabs: N1=%d must be a multiple of 256, B2 16-byte aligned with ldb2 %% 8 == 0, c_col2=%d >= N1", N1, c_col2);
-  GemmOperandsT p{A, lda, B1, ldb1, M, N, K / 32};
-  if (B2) { p.B2 = B2; p.ldb2 = ldb2; p.N1 = N1; p.c_col2 = c_col2; }
-  const int tm = ceil_div(M, CfgPlainV2::BM), tn = ceil_div(N, CfgPlainV2::BU);
-  const int per = ceil_div(p.nk, nslab);
-  EVC_REQUIRE((long)per * (nslab - 1) < p.nk, EVC_ERR_BAD_SHAPE, "evc_gemm_tn2_slabs: nslab=%d leaves an empty slab at K=%d", nslab, K);
-  StoreParamsT s{slabs, ldc, M, N, row_interleave_H, 0, nslab, per, slab_stride};
-  launch_cfg<CfgPlainV2>(gemm_tn_kernel<CfgPlainV2>, tm * tn * nslab, (hipStream_t)stream, p, s, tm, tn);
-  EVC_LAUNCH_CHECK();
-  return EVC_OK;
+  return gemm_tn_slabs_impl("evc_gemm_tn2_slabs", A, lda, B1, ldb1, N1, B2, ldb2, N2, c_col2, slabs, ldc, slab_stride, M, K, row_interleave_H, nslab, stream);
+}
+// Split-K into slabs: slab s (s < nslab) = the partial product over K rows [s*ceil(K/32/nslab)*32, ...), stored plainly at
+// slabs + s*M*N (row stride N).  For products whose 256x256 tiles do not fill the chip and whose result is read once by a
+// pass that can add the slabs on the way (DBoF cluster-weight gradient: 8192 x 1152 x 16384 = 160 tiles): no atomics, no memset.
+extern "C" int evc_gemm_tn_slabs(const evc_bf16* A, int64_t lda, const evc_bf16* B, int64_t ldb, float* slabs, int M, int N, int K,
+                                 int nslab, void* stream) {
+  return gemm_tn_slabs_impl("evc_gemm_tn_slabs", A, lda, B, ldb, N, nullptr, 0, 0, 0, slabs, N, (int64_t)M * N, M, K, 0, nslab, stream);
 }
 
 // C[r][c] (+)= sum over slabs s, in slab order, of slabs[s*slab_stride + r*ld + c] for r < M, c < N (N % 4 == 0, 16-byte aligned rows)

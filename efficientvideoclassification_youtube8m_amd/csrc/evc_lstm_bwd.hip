@@ -610,7 +610,7 @@ extern "C" int evc_lstm_layer_bwd(const evc_bf16* w_il, const int32_t* len, int 
     const int ma = Mt > 0 ? Mt : 1;
     for (int ci = 0; ci < 6; ++ci) {
       const int i = cand[ci];
-      const double c = tile_cost((long)ceil_div(ma, bm[i]) * ceil_div(H, bn[i]), bm[i], bn[i], 1, cf[i]);
+      const double c = tile_cost((long)ceil_div(ma, bm[i]) * ceil_div(H, bn[i]), bm[i], bn[i], cf[i]);
       if (c < bc) { bc = c; pick = i; }
     }
     if ((long)ceil_div(ma, 32) * ceil_div(H, 32) <= 512) pick = 5;   // M ~ batch: K split over the waves, a private LDS ring per wave

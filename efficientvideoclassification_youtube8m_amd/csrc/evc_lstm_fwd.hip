@@ -491,7 +491,6 @@ static inline void launch_lstm_fwd_pair(const FwdStep& a, const FwdStep& b, hipS
 }
 
 // ---- tile choice: two cost-model tables, one dispatcher each -----------------------------------------------------------------------------------
-template <class Cfg> struct TileTag { typedef Cfg type; };
 // the tiles lstm_fwd_walk2_kernel is built for
 template <class Cfg> struct is_walk2_tile {
   static constexpr bool value = std::is_same<Cfg, CfgLstmV3_256>::value || std::is_same<Cfg, CfgLstmV3_240>::value || std::is_same<Cfg, CfgLstmV3_224u>::value;
@@ -507,7 +506,7 @@ static inline int pick_fwd_tile(int rows, int H) {
   int best = 0;
   double bc = 1e300;
   for (int i = 0; i < NC; ++i) {
-    const double c = tile_cost((long)ceil_div(rows, bm[i]) * ceil_div(H, bu[i]), bm[i], bn[i], 1, cf[i]);
+    const double c = tile_cost((long)ceil_div(rows, bm[i]) * ceil_div(H, bu[i]), bm[i], bn[i], cf[i]);
     if (c < bc) { bc = c; best = i; }
   }
   const int f = forced_tile();        // debug: 1 -> 256, 2 -> v1 128, 3 -> v1 64, 4 -> 320, 5 -> 288, 6 -> 224, 7 -> 192, 8 -> 160, 9 -> v2 128, 10 -> v2 64, 11 -> 240
@@ -541,7 +540,7 @@ static inline int pick_fwd_tile_v3(int rows, int H) {
   int best = 0;
   double bc = 1e300;
   for (int i = 0; i < 5; ++i) {
-    const double c = tile_cost((long)ceil_div(rows, bm[i]) * ceil_div(H, 64), bm[i], 256, 1, cf[i]);
+    const double c = tile_cost((long)ceil_div(rows, bm[i]) * ceil_div(H, 64), bm[i], 256, cf[i]);
     if (c < bc) { bc = c; best = i; }
   }
   const int f = forced_tile();        // debug: 1 -> 256, 6 -> 224, 7 -> 192, 8 -> 160, 11 -> 240

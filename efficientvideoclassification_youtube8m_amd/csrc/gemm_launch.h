@@ -18,13 +18,13 @@ template <int a, int b, int c, int d, int e, int f, int g> struct is_v3<TileCfg3
 
 extern __shared__ __attribute__((aligned(16))) char lds_dyn[];
 
-// The ring loops address every LDS-DMA as base + 32-bit byte offset built from a 24-bit row index and a 24-bit row stride
-// (gemm_core_v2.h): an operand of `rows` rows with leading dimension `ld` (bf16 elements) must fit that.
-// the forward step's epilogue addresses its stores as base + 32-bit byte offset: gate records [rows][H] x 8 B, state rows (row_map is a
+// The forward step's epilogue addresses its stores as base + 32-bit byte offset: gate records [rows][H] x 8 B, state rows (row_map is a
 // permutation of [0, rows)) of ld_state floats, h rows of up to 3H bytes / 2H halfwords (the wide images)
 static inline bool fwd_tail_ok(long rows, long H, long ld_state) {
   return rows * H * 8 + 32 < (1L << 32) && rows * ld_state * 4 < (1L << 32);
 }
+// The ring loops address every LDS-DMA as base + 32-bit byte offset built from a 24-bit row index and a 24-bit row stride
+// (gemm_core_v2.h): an operand of `rows` rows with leading dimension `ld` (bf16 elements) must fit that.
 static inline bool ring_operand_ok(long rows, long ld) {
   return rows < (1L << 24) && ld * 2 < (1L << 24) && rows * ld * 2 < (1L << 32);
 }
@@ -66,7 +66,14 @@ static inline void launch_cfg(Kern kern, int grid, hipStream_t st, Args... args)
   }
 }
 
-// debug/benchmark override of the tile choice: EVC_FORCE_TILE = 1 (v2) | 2 (v1 128x128) | 3 (v1 64x64)
+// a tile type handed to a generic callable: f(TileTag<Cfg>()), typename decltype(tile)::type inside (with_nt_tile, with_fwd_tile)
+template <class Cfg> struct TileTag { typedef Cfg type; };
+
+// debug/benchmark override of the tile choice, EVC_FORCE_TILE (read once per process; 0 / unset: the choosers decide).  NT products (evc_gemm_nt
+// alone; NT_TILES in gemm_shared.h): 1 ring 256x256 | 2 v1 128x128 | 3 v1 64x64 | 4 ring 224x256 | 5 ring 128x128 | 6 ring 320x256 | 7 ring 160x128,
+// any other value: 3; a forced tile runs without K split, and the batch-row 256x64 tile and the two split-K tiles are chosen by shape only.  TN products:
+// 11 = 128x128 tiles without K split, any other value: 256x256 tiles with the usual K split.  LSTM steps: 1-11 as listed at pick_fwd_tile /
+// pick_fwd_tile_v3 (evc_lstm_fwd.hip), 1-7 at the BPTT step's pick (evc_lstm_bwd.hip).
 static inline int forced_tile() {
   static int v = -1;
   if (v < 0) { const char* e = getenv("EVC_FORCE_TILE"); v = e ? atoi(e) : 0; }

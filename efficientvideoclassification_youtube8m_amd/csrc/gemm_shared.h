@@ -26,9 +26,17 @@ template <class Cfg> static inline int kdiv() { return (is_v2<Cfg>::value && !is
 // Tile choice: a CU works through ceil(tiles/256) tiles (co-resident workgroups share its matrix
 // pipe, so residency does not shorten that), each costing area x a per-flop factor measured on
 // MI355X with scripts/gemm_bench.py (v2 ~1000 TF/s -> 1.0, v1 128x128 ~800 -> 1.3, v1 64x64 ~400 -> 2.6).
-static inline double tile_cost(long tiles, int bm, int bn, int /*occ*/, double c) {
+static inline double tile_cost(long tiles, int bm, int bn, double c) {
   const long per_cu = (tiles + 255) / 256;
   return (double)per_cu * bm * bn * c;
+}
+
+// K splits of a product of nk K steps: `want` of them, each at least min_steps long and none empty
+static inline int split_k(long want, int nk, int min_steps) {
+  int splits = (int)(want < nk / min_steps ? want : nk / min_steps);
+  if (splits < 1) splits = 1;
+  while (splits > 1 && (long)ceil_div(nk, splits) * (splits - 1) >= nk) --splits;
+  return splits;
 }
 
 // ===========================================================================
@@ -149,7 +157,64 @@ typedef TileCfg<32, 1, 32, 2, 2> CfgPlainTiny;    // 32x32: M ~ batch recurrent 
 typedef TileCfg2<256, 1, 256, 2, 4, 5, true> CfgPlainV2;   // 256x256, 8 waves (2x4), 128x64 per wave, 5-deep ring (160 KiB)
 typedef TileCfg2<320, 1, 256, 2, 4, 4, false> CfgPlainV2_320;  // 320 rows (4-deep ring, single fragment set): 5120 rows = 16 x 16 tiles, ONE round of 256 workgroups instead of 320 tiles
 typedef TileCfg2<128, 1, 128, 2, 4, 5, true> CfgTn128;     // 128x128 v2 tile (80 KB ring: two workgroups per CU)
+// the ring tiles on 64-wide K stages (the 224 / 256-row ones on two of them, the 128- and 64-column ones on four)
+typedef TileCfg3<256, 1, 256, 2, 4, 2> CfgRing256;
+typedef TileCfg3<224, 1, 256, 2, 4, 2> CfgRing224;
+typedef TileCfg3<160, 1, 128, 2, 4, 4> CfgRing160;
+typedef TileCfg3<128, 1, 128, 2, 4, 4> CfgRing128;
+typedef TileCfg3<256, 1, 64, 2, 4, 4> CfgRing256x64;       // batch rows: the [256][K] row operand is re-read from L2 by every workgroup
 // (256x128 tiles + split-K 2, to halve the re-reads of the [256][K] row operand: 80 vs 61 us at N = 14148 - not the bound)
+
+// The tiles of the NT products (evc_gemm.hip).  id: the EVC_FORCE_TILE value for 1-7 (forced_tile(), gemm_launch.h); the last three are
+// chosen by shape only.  cost: the per-flop factor of tile_cost().
+enum NtTileId { NT_RING256 = 1, NT_V1_128 = 2, NT_V1_64 = 3, NT_RING224 = 4, NT_RING128 = 5, NT_RING320 = 6, NT_RING160 = 7,
+                NT_ROWS256x64 = 12, NT_SPLIT128 = 13, NT_SPLIT256 = 14 };
+struct NtTile { int id; const char* name; int bm, bn; double cost; };
+constexpr NtTile NT_TILES[] = {
+    {NT_RING256, "ring 256x256", 256, 256, 1.0},
+    {NT_V1_128, "v1 128x128", 128, 128, 1.3},
+    {NT_V1_64, "v1 64x64", 64, 64, 2.6},
+    {NT_RING224, "ring 224x256", 224, 256, 1.01},      // e.g. 56 640 rows x 1024: 1012 tiles = 3.95 rounds instead of 888 = 3.47
+    {NT_RING128, "ring 128x128", 128, 128, 1.3},
+    {NT_RING320, "ring 320x256", 320, 256, 1.03},      // the L2 hoist / dX: 5120 x 4096 x 4096 = 16 x 16 tiles
+    {NT_RING160, "ring 160x128", 160, 128, 1.5},       // 1280 rows x 4096 columns (the student's L2 hoist / dX at batch 256) = 8 x 32 = 256 tiles, one round
+    {NT_ROWS256x64, "ring 256x64, batch rows", 256, 64, 0.0},      // (the last three are never costed)
+    {NT_SPLIT128, "ring 128x128 (32-wide stages), split K", 128, 128, 0.0},
+    {NT_SPLIT256, "ring 256x256 (32-wide stages), split K", 256, 256, 0.0},
+};
+constexpr const NtTile& nt_tile(int id) {
+  for (const NtTile& t : NT_TILES) if (t.id == id) return t;
+  return NT_TILES[2];
+}
+template <int ID, class Cfg> struct NtTileTag : TileTag<Cfg> {
+  static_assert(nt_tile(ID).id == ID && nt_tile(ID).bm == Cfg::BM && nt_tile(ID).bn == Cfg::BU, "NT_TILES row and tile type disagree");
+};
+// f(TileTag<Cfg>()) for the tile of an NT_TILES id, among the tiles the operand form is built on: bf16 (and split-bf16, the same kernels) all
+// ten, f16 the four ring tiles its chooser lists, f16 + e4m3 the two 64-wide-stage tiles of its two shapes.
+template <bool F16, bool FP8, class F>
+static inline auto with_nt_tile(int id, F&& f) {
+  if constexpr (FP8) {
+    return id == NT_ROWS256x64 ? f(NtTileTag<NT_ROWS256x64, CfgRing256x64>()) : f(NtTileTag<NT_RING256, CfgRing256>());
+  } else if constexpr (F16) {
+    if (id == NT_RING320) return f(NtTileTag<NT_RING320, CfgPlainV2_320>());
+    if (id == NT_RING256) return f(NtTileTag<NT_RING256, CfgRing256>());
+    if (id == NT_RING160) return f(NtTileTag<NT_RING160, CfgRing160>());
+    return f(NtTileTag<NT_RING128, CfgRing128>());
+  } else {
+    switch (id) {
+      case NT_ROWS256x64: return f(NtTileTag<NT_ROWS256x64, CfgRing256x64>());
+      case NT_SPLIT128: return f(NtTileTag<NT_SPLIT128, CfgTn128>());
+      case NT_SPLIT256: return f(NtTileTag<NT_SPLIT256, CfgPlainV2>());
+      case NT_RING128: return f(NtTileTag<NT_RING128, CfgRing128>());
+      case NT_RING224: return f(NtTileTag<NT_RING224, CfgRing224>());
+      case NT_RING320: return f(NtTileTag<NT_RING320, CfgPlainV2_320>());
+      case NT_RING256: return f(NtTileTag<NT_RING256, CfgRing256>());
+      case NT_RING160: return f(NtTileTag<NT_RING160, CfgRing160>());
+      case NT_V1_128: return f(NtTileTag<NT_V1_128, CfgPlainBig>());
+      default: return f(NtTileTag<NT_V1_64, CfgPlainSmall>());
+    }
+  }
+}
 
 __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) { return pack_bf16x2_hw(lo, hi); }
 

@@ -1,17 +1,11 @@
 // Recording stand-in for the HIP runtime, for scripts/fwd_launch_record.py: linked with a HOST-ONLY build of csrc/evc_lstm_fwd.hip in place of the
 // runtime, it writes every enqueue the forward entries make to the file named by SHIM_LOG - memsets, LDS attributes, the hoisted products and every
 // kernel launch with its geometry and each field of its GemmOperands / LstmFwdParams.  Nothing runs; no GPU is needed.
-#include "gemm_shared.h"
-#include <cstdio>
-#include <cstdarg>
-#include <map>
-#include <string>
+#include "launch_record_stubs.h"
 struct LstmFwdParamsX {      // the layout of LstmFwdParams (defined in evc_lstm_fwd.hip itself)
   const float* zx; long ldzx; const float* bias; const int* len; int t; float* c_state; float* h_state; long ld_state;
   bf16_t* hout; bf16_t* hout_lo; uint2* gates; bf16_t* c_hist; const int* row_map; int M, H; int h_wide;
 };
-static FILE* out() { static FILE* f = fopen(getenv("SHIM_LOG"), "w"); return f; }
-static std::map<const void*, std::string>& names() { static std::map<const void*, std::string> m; return m; }
 static void dump_p(const char* tag, const GemmOperands& p) {
   fprintf(out(), "  %s.p A1=%p lda1=%ld nk1=%d A2=%p lda2=%ld nk2=%d B=%p ldb=%ld gs=%ld M=%d Nu=%d A1lo=%p A2lo=%p Blo=%p B2=%p A3=%p lda3=%ld nk3=%d A4=%p lda4=%ld nk4=%d B8=%p ldb8=%ld s8=%d amax=%p a8=%d rs=%p ca=%p g2=%g gap=%ld\n",
           tag, (void*)p.A1, p.lda1, p.nk1, (void*)p.A2, p.lda2, p.nk2, (void*)p.B, p.ldb, p.group_stride, p.M, p.Nu, (void*)p.A1lo, (void*)p.A2lo, (void*)p.Blo, (void*)p.B2,
@@ -22,18 +16,7 @@ static void dump_e(const char* tag, const LstmFwdParamsX& e) {
           e.zx ? e.ldzx : -1L, (void*)e.bias, (void*)e.len, e.t, (void*)e.c_state, (void*)e.h_state, e.ld_state, (void*)e.hout, (void*)e.hout_lo, (void*)e.gates, (void*)e.c_hist,
           (void*)e.row_map, e.M, e.H, e.h_wide);
 }
-extern "C" {
-char __hip_fatbin[64];
-void** __hipRegisterFatBinary(const void*) { static void* h; return &h; }
-void __hipUnregisterFatBinary(void**) {}
-void __hipRegisterFunction(void**, const void* host, char*, const char* name, int, void*, void*, void*, void*, int*) { names()[host] = name; }
-void __hipRegisterVar(void**, void*, char*, const char*, int, size_t, int, int) {}
-static dim3 g_grid, g_block; static size_t g_sh; static hipStream_t g_st;
-hipError_t __hipPushCallConfiguration(dim3 g, dim3 b, size_t sh, hipStream_t st) { g_grid = g; g_block = b; g_sh = sh; g_st = st; return hipSuccess; }
-hipError_t __hipPopCallConfiguration(dim3* g, dim3* b, size_t* sh, hipStream_t* st) { *g = g_grid; *b = g_block; *sh = g_sh; *st = g_st; return hipSuccess; }
-hipError_t hipLaunchKernel(const void* f, dim3 g, dim3 b, void** a, size_t sh, hipStream_t st) {
-  const std::string& n = names()[f];
-  fprintf(out(), "launch %s grid=%u block=%u lds=%zu stream=%p\n", n.c_str(), g.x, b.x, sh, (void*)st);
+static void dump_launch_args(const std::string& n, void** a) {
   if (n.find("walk2") != std::string::npos) {
     const int tma = *(int*)a[2], tmb = *(int*)a[5];
     fprintf(out(), "  tiles_ma=%d tiles_mb=%d tiles_n=%d\n", tma, tmb, *(int*)a[6]);
@@ -46,20 +29,12 @@ hipError_t hipLaunchKernel(const void* f, dim3 g, dim3 b, void** a, size_t sh, h
     fprintf(out(), "  tiles_m=%d tiles_n=%d\n", *(int*)a[2], *(int*)a[3]);
     dump_p("s", *(GemmOperands*)a[0]); dump_e("s", *(LstmFwdParamsX*)a[1]);
   }
-  return hipSuccess;
 }
-hipError_t hipMemsetAsync(void* p, int v, size_t n, hipStream_t st) { fprintf(out(), "memset %p %d %zu\n", p, v, n); return hipSuccess; }
-hipError_t hipGetLastError() { return hipSuccess; }
-const char* hipGetErrorString(hipError_t) { return "?"; }
-hipError_t hipFuncSetAttribute(const void* f, hipFuncAttribute, int v) { fprintf(out(), "attr %s %d\n", names()[f].c_str(), v); return hipSuccess; }
+extern "C" {
 int evc_gemm_nt(const evc_bf16* A, int64_t lda, const evc_bf16* B, int64_t ldb, void* C, int64_t ldc, int M, int N, int K, const float* bias, int ob, int acc, void* st) {
   fprintf(out(), "evc_gemm_nt %p %ld %p %ld %p %ld %d %d %d %p %d %d\n", (void*)A, (long)lda, (void*)B, (long)ldb, C, (long)ldc, M, N, K, (void*)bias, ob, acc); return 0; }
 int evc_gemm_nt_split(const evc_bf16* A, int64_t lda, const evc_bf16* B, int64_t ldb, float* C, int64_t ldc, int M, int N, int K, const float* bias, void* st) {
   fprintf(out(), "evc_gemm_nt_split %p %ld %p %ld %p %ld %d %d %d %p\n", (void*)A, (long)lda, (void*)B, (long)ldb, (void*)C, (long)ldc, M, N, K, (void*)bias); return 0; }
-void shim_note(const char* s) { fprintf(out(), "%s\n", s); fflush(out()); }
 }
 int gemm_nt_f16(const evc_f16* A, int64_t lda, const evc_f16* B, int64_t ldb, float* C, int64_t ldc, int M, int N, int K, void* stream) {
   fprintf(out(), "gemm_nt_f16 %p %ld %p %ld %p %ld %d %d %d\n", (void*)A, (long)lda, (void*)B, (long)ldb, (void*)C, (long)ldc, M, N, K); return 0; }
-static char g_err[512];
-void evc_set_error(const char* fmt, ...) { va_list ap; va_start(ap, fmt); vsnprintf(g_err, sizeof g_err, fmt, ap); va_end(ap); }
-extern "C" const char* shim_err() { return g_err; }

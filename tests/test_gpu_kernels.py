@@ -40,7 +40,8 @@ def to_bf16(a):
 
 @pytest.mark.parametrize("M,N,K", [(128, 128, 64), (200, 300, 128), (512, 4096, 1024), (64, 64, 2176),
                                    (1, 5, 64), (1000, 130, 192), (4716, 64, 256),
-                                   (512, 300, 16384)])   # last: long K, few tiles -> split-K with f32 atomics
+                                   (512, 300, 16384),    # long K, few tiles -> split-K with f32 atomics on 128x128 tiles ...
+                                   (600, 264, 8192)])    # ... and, above 512 rows, on 256x256 tiles
 def test_gemm_nt(ops, M, N, K):
     rng = np.random.default_rng(M * 7 + N)
     A = bf16_round(rng.standard_normal((M, K)))
