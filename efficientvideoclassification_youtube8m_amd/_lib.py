@@ -136,6 +136,8 @@ SIGNATURES = {
     "evc_nextvlad_center_cast": [vp, i32, i32, vp, vp, vp],
     "evc_nextvlad_bias_logits": [vp, vp, i32, i32, vp, vp, i32, vp],
     "evc_nextvlad_wgrad_uncenter": [vp, vp, vp, i32, i32, vp, vp],
+    "evc_nextvlad_dropout_fwd": [vp, i32, i32, vp, vp, vp, vp, C.c_uint32, f32, C.c_uint32, C.c_uint32, C.c_uint64, vp, vp],
+    "evc_nextvlad_dropout_bwd": [vp, i32, i32, C.c_uint32, f32, C.c_uint32, C.c_uint32, C.c_uint64, vp],
     "evc_dbof_workspace": [i32, i32, vp, vp, vp],
     "evc_dbof_gather": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp],
     "evc_bn_partials_reduce": [vp, i32, i32, vp, vp],

@@ -14,6 +14,7 @@
 //   evc_nextvlad_colsum              out[c] = sum_r x[r][c] in a fixed order (the two bias gradients)
 //   evc_nextvlad_center_cast         bf16(xe - be): the centred operand of the cluster / attention products; with it
 //   evc_nextvlad_bias_logits         be.W in f32 (the products' bias) and evc_nextvlad_wgrad_uncenter (the rank-one gradient term)
+//   evc_nextvlad_dropout_fwd/bwd     dropout before the hidden layer: vlad_bn apply + stateless Philox mask + bf16 store; dY masked (7.17)
 //
 // Layouts: sampled frames row-major, row b*S+s; xe [R][E] with group g in columns g*D .. g*D+D, so that one video's xe is a
 // contiguous [P][D] matrix X_b over the P = S*G (frame, group) pairs, and its assignment a [R][G][K] a contiguous [P][K] matrix
@@ -865,6 +866,88 @@ extern "C" int evc_nextvlad_colsum(const float* x, int64_t ld, int R, int C, flo
     return EVC_OK;
   }
   hipLaunchKernelGGL(nextvlad_colsum_kernel, dim3(ceil_div(C, 64)), dim3(1024), 0, (hipStream_t)stream, x, (long)ld, R, C, out);
+  EVC_LAUNCH_CHECK();
+  return EVC_OK;
+}
+
+// ---- dropout before the hidden layer: Yd = Y * m / keep, m in {0, 1} a function of (seed, rank, step, element)
+// alone - a counter-based generator evaluated where the value is consumed, so the mask is never stored: the backward pass
+// regenerates it.  Element e = b*C + j of the [B][C] buffer (C = K*D, j = k*D + d: the INTERNAL cluster-major order) is lane
+// l = e & 3 of quad q = e >> 2; w = Philox4x32-10(counter (q_lo, q_hi, step_lo, step_hi), key (seed, rank))[l]; m = (w < T) as
+// unsigned 32-bit values, T = floor(keep * 2^32) from the host.  C % 4 == 0: a quad never straddles a row.
+// Philox4x32-10 (Salmon, Moraes, Dror, Shaw 2011): ten rounds of two 32 x 32 -> 64 bit multiplies, the key bumped by the Weyl
+// constants between rounds.
+__device__ __forceinline__ uint4 nx_philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+  constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t hi0 = __umulhi(M0, c0), lo0 = M0 * c0;
+    const uint32_t hi1 = __umulhi(M1, c2), lo1 = M1 * c2;
+    c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+    k0 += W0; k1 += W1;                          // (the bump after the tenth round is dead code)
+  }
+  return make_uint4(c0, c1, c2, c3);
+}
+__device__ __forceinline__ uint4 nx_dropout_words(long q, uint32_t seed, uint32_t rank, uint64_t step) {
+  return nx_philox4x32_10((uint32_t)q, (uint32_t)((uint64_t)q >> 32), (uint32_t)step, (uint32_t)(step >> 32), seed, rank);
+}
+
+// both launches are streaming passes: at most 2048 workgroups (8 per CU) and a grid-stride loop over the rest
+static inline int nx_drop_grid(long nq) { long nb = (nq + 255) / 256; return (int)(nb < 2048 ? nb : 2048); }
+
+// Y_bf16[e] = bf16(vlad_bn(U)[e] * scale) where kept, +0 where dropped: the batch-norm apply (the expression of bn_apply_kernel,
+// no relu6), the mask and the bf16 store (f32_to_bf16's conversion, two values at a time) in one pass.  One thread per quad and
+// iteration: one Philox call, 16-byte loads of U and of the four per-column vectors, one 8-byte store.
+__global__ __launch_bounds__(256) void nextvlad_dropout_fwd_kernel(const float4* __restrict__ U, long nq, uint32_t C4,
+                                                                   const float4* __restrict__ mean, const float4* __restrict__ var,
+                                                                   const float4* __restrict__ gamma, const float4* __restrict__ beta,
+                                                                   uint32_t T, float scale, uint32_t seed, uint32_t rank, uint64_t step,
+                                                                   uint2* __restrict__ Y) {
+  for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long)gridDim.x * blockDim.x) {
+    const uint32_t c4 = nq <= 0xffffffffL ? (uint32_t)q % C4 : (uint32_t)(q % C4);
+    const uint4 w = nx_dropout_words(q, seed, rank, step);
+    const float4 x = U[q], mu = mean[c4], va = var[c4], ga = gamma[c4], be = beta[c4];
+    const float y0 = ((x.x - mu.x) * rsqrtf(va.x + 1e-3f) * ga.x + be.x) * scale;
+    const float y1 = ((x.y - mu.y) * rsqrtf(va.y + 1e-3f) * ga.y + be.y) * scale;
+    const float y2 = ((x.z - mu.z) * rsqrtf(va.z + 1e-3f) * ga.z + be.z) * scale;
+    const float y3 = ((x.w - mu.w) * rsqrtf(va.w + 1e-3f) * ga.w + be.w) * scale;
+    Y[q] = make_uint2(pack_bf16x2_hw(w.x < T ? y0 : 0.f, w.y < T ? y1 : 0.f), pack_bf16x2_hw(w.z < T ? y2 : 0.f, w.w < T ? y3 : 0.f));
+  }
+}
+// dY[e] = m[e] ? dY[e] * scale : 0, in place: the same quads, the same words
+__global__ __launch_bounds__(256) void nextvlad_dropout_bwd_kernel(float4* __restrict__ dY, long nq, uint32_t T, float scale, uint32_t seed,
+                                                                   uint32_t rank, uint64_t step) {
+  for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long)gridDim.x * blockDim.x) {
+    const uint4 w = nx_dropout_words(q, seed, rank, step);
+    const float4 d = dY[q];
+    dY[q] = make_float4(w.x < T ? d.x * scale : 0.f, w.y < T ? d.y * scale : 0.f, w.z < T ? d.z * scale : 0.f, w.w < T ? d.w * scale : 0.f);
+  }
+}
+
+extern "C" int evc_nextvlad_dropout_fwd(const float* U, int B, int C, const float* mean, const float* var, const float* gamma,
+                                        const float* beta, uint32_t T, float scale, uint32_t seed, uint32_t rank, uint64_t step,
+                                        evc_bf16* Y_bf16, void* stream) {
+  EVC_REQUIRE(B > 0 && C > 0 && C % 4 == 0, EVC_ERR_BAD_SHAPE, "evc_nextvlad_dropout_fwd: needs B > 0, C %% 4 == 0 (B=%d C=%d)", B, C);
+  EVC_REQUIRE(T != 0, EVC_ERR_BAD_ARG, "evc_nextvlad_dropout_fwd: threshold 0 keeps nothing (the rate must be below 1)");
+  EVC_REQUIRE(U && mean && var && gamma && beta && Y_bf16, EVC_ERR_BAD_ARG, "evc_nextvlad_dropout_fwd: NULL operand");
+  EVC_REQUIRE(nx_aligned16(U) && nx_aligned16(mean) && nx_aligned16(var) && nx_aligned16(gamma) && nx_aligned16(beta) &&
+              ((uintptr_t)Y_bf16 % 8) == 0, EVC_ERR_BAD_ALIGN,
+              "evc_nextvlad_dropout_fwd: U and the four column vectors must be 16-byte aligned, Y_bf16 8-byte aligned");
+  const long nq = (long)B * (C / 4);
+  hipLaunchKernelGGL(nextvlad_dropout_fwd_kernel, dim3(nx_drop_grid(nq)), dim3(256), 0, (hipStream_t)stream, (const float4*)U, nq, (uint32_t)(C / 4),
+                     (const float4*)mean, (const float4*)var, (const float4*)gamma, (const float4*)beta, T, scale, seed, rank, step,
+                     (uint2*)Y_bf16);
+  EVC_LAUNCH_CHECK();
+  return EVC_OK;
+}
+extern "C" int evc_nextvlad_dropout_bwd(float* dY, int B, int C, uint32_t T, float scale, uint32_t seed, uint32_t rank, uint64_t step,
+                                        void* stream) {
+  EVC_REQUIRE(B > 0 && C > 0 && C % 4 == 0, EVC_ERR_BAD_SHAPE, "evc_nextvlad_dropout_bwd: needs B > 0, C %% 4 == 0 (B=%d C=%d)", B, C);
+  EVC_REQUIRE(T != 0, EVC_ERR_BAD_ARG, "evc_nextvlad_dropout_bwd: threshold 0 keeps nothing (the rate must be below 1)");
+  EVC_REQUIRE(dY, EVC_ERR_BAD_ARG, "evc_nextvlad_dropout_bwd: NULL operand");
+  EVC_REQUIRE(nx_aligned16(dY), EVC_ERR_BAD_ALIGN, "evc_nextvlad_dropout_bwd: dY must be 16-byte aligned (float4 access)");
+  const long nq = (long)B * (C / 4);
+  hipLaunchKernelGGL(nextvlad_dropout_bwd_kernel, dim3(nx_drop_grid(nq)), dim3(256), 0, (hipStream_t)stream, (float4*)dY, nq, T, scale, seed, rank, step);
   EVC_LAUNCH_CHECK();
   return EVC_OK;
 }

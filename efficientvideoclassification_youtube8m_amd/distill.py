@@ -1562,13 +1562,15 @@ class SingleTowerGraph(_StepGraph):
         if self.dp and B != tw.B:
             raise ValueError("data-parallel step on %d videos, the tower was built for %d per rank (ragged batches are not "
                              "allowed under data parallelism: drop the remainder)" % (B, tw.B))
+        # (a NeXtVLAD tower's dropout mask is a function of the step: a restored run draws the same masks)
+        kw = {"dropout_step": self.global_step} if isinstance(tw, NeXtVladTower) else {}
         if isinstance(tw, NeXtVladTower) and tw.frames == "grid":
-            pred = tw.forward(x_raw, num_frames, num_frames_host=num_frames_host)
+            pred = tw.forward(x_raw, num_frames, num_frames_host=num_frames_host, **kw)
         elif isinstance(tw, (DbofTower, NetVladTower, NeXtVladTower, DbofGenericTower)):
             if uniform is None:     # (SampleRandomSequence draws one start per video: column 0 is used)
                 uniform = torch.rand((B, tw.S), dtype=F32, device=self.device)
             self.last_uniform = uniform              # the tf.random_uniform draw of this step (SampleRandomFrames)
-            pred = tw.forward(x_raw, num_frames, uniform)
+            pred = tw.forward(x_raw, num_frames, uniform, **kw)
         else:
             pred = tw.forward(x_raw, num_frames)
         self.losses.zero_()
@@ -1631,7 +1633,9 @@ class NeXtVladDistillGraph(_StepGraph):
     student forward, the loss section of DistillGraph's mode 'serial' (ops.distill_losses on the towers' gated hidden vectors and
     predictions, the same scales), the student's backward with dL_REP/dstate joining the MoE head's gradient at `out`, and the update
     exactly as SingleTowerGraph.step performs it; global_step += 1.  Reporting follows DistillGraph's serial mode (`out` keys,
-    LOSS_SLOTS, loss_report), so train's loop needs no special case.  Every refusal is a ValueError before the device is touched."""
+    LOSS_SLOTS, loss_report), so train's loop needs no special case.  Every refusal is a ValueError before the device is touched.
+    dropout / dropout_seed: the STUDENT's drop rate before its hidden layer, its mask a function of global_step; the
+    frozen teacher never drops."""
 
     LOSS_SLOTS = DistillGraph.LOSS_SLOTS
     DISTILL_LOSSES = DistillGraph.DISTILL_LOSSES
@@ -1643,8 +1647,9 @@ class NeXtVladDistillGraph(_StepGraph):
                  hidden_size=1024, groups=8, expansion=2, gating_reduction=8, num_mixtures=2, base_learning_rate=0.001,
                  learning_rate_decay=1.0, learning_rate_decay_examples=4000000, regularization_penalty=2.0, clip_gradient_norm=1.0,
                  count_rep_twice=True, device="cuda:0", seed=7, process_group=None, precision="bf16", distill_losses=DISTILL_LOSSES,
-                 label_loss=None):
+                 label_loss=None, dropout=0.0, dropout_seed=0):
         from .towers import NeXtVladTower, check_nextvlad_frames
+        ops.check_dropout_rate(dropout)              # (before the device is touched; only the student drops)
         self.world = _world_of(process_group)
         if self.world > 1:
             raise ValueError("NeXtVladDistillGraph is not data parallel (process group of %d ranks): train the student against the "
@@ -1669,7 +1674,7 @@ class NeXtVladDistillGraph(_StepGraph):
         self.teacher = NeXtVladTower(*sizes, device=device, training=False, scope="model", seed=seed, frames="grid",
                                      every_n=self.teacher_every_n)
         self.student = NeXtVladTower(*sizes, device=device, training=True, scope="model_student", seed=seed + 1, frames="grid",
-                                     every_n=self.every_n)
+                                     every_n=self.every_n, dropout=dropout, dropout_seed=dropout_seed)
         self.moe = self.student.moe
         self.fused_moe_update = True
         self.losses = torch.zeros(8, dtype=F32, device=self.device)
@@ -1714,7 +1719,7 @@ class NeXtVladDistillGraph(_StepGraph):
             self._dp_s = torch.empty((B, V), dtype=F32, device=self.device)
             self._ds_s = torch.empty((B, ts.Hd), dtype=F32, device=self.device)
         t_pred = tt.forward(x_raw, num_frames, num_frames_host=num_frames_host, is_training=False)
-        s_pred = ts.forward(x_raw, num_frames, num_frames_host=num_frames_host)
+        s_pred = ts.forward(x_raw, num_frames, num_frames_host=num_frames_host, dropout_step=self.global_step)
         on = self.distill_losses
         self.losses.zero_()
         ops.distill_losses(t_pred, tt.rowsum, s_pred, ts.rowsum, labels_u8, tt.state, ts.state, self.losses, self._dp_s, self._ds_s,

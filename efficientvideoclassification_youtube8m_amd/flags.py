@@ -81,7 +81,9 @@ _define("every_n", 1, int)
 _define("label_loss", "CrossEntropyLoss", str)
 _define("label_loss_counts_file", "counts_tv", str, "CrossEntropyLossClassImbalance: the file of class counts, one integer per line, one line per "
         "class (the reference opens 'counts_tv' in the working directory, cs/losses.py:107)")
-_define("dropout", 0.5, float)
+_define("dropout", 0.5, float, "the reference's flag: a KEEP probability that cs/train.py hands to create_model, where its video-level "
+        "MLP models apply it and the frame-level models this project ports ignore it; nothing here reads it.  It is not "
+        "--nextvlad_dropout, the drop rate of the NeXtVLAD tower")
 _define("regularization_penalty", 2.0, float)
 _define("base_learning_rate", 0.001, float)
 _define("learning_rate_decay", 1.0, float)
@@ -143,6 +145,11 @@ _define("nextvlad_gating_reduction", 8, int, "NeXtVLADModel (extension): context
 _define("nextvlad_frames", "sampled", str, "NeXtVLADModel (extension): sampled (--iterations frames drawn per video and step) | grid (the frames "
         "0, every_n, 2 every_n, ... of each video's real frames, a different number per video, packed without padding: --every_n 1 is every real "
         "frame, the teacher's input; --every_n 10 or 30 the fewer-frames student's; --iterations is not read)")
+_define("nextvlad_dropout", 0.0, float, "NeXtVLADModel (extension, DESIGN.md 7.17): the DROP rate in [0, 1) applied to the hidden layer's "
+        "input in training (the paper trains with 0.5; 0 = off, the default).  The mask is a stateless function of "
+        "(--nextvlad_dropout_seed, data-parallel rank, global_step, element), generated on the device where it is consumed and never stored: "
+        "a run restored from a checkpoint continues with the masks an uninterrupted run would have drawn.  validate / inference never drop")
+_define("nextvlad_dropout_seed", 0, int, "NeXtVLADModel: the seed of the --nextvlad_dropout masks (a 32-bit key word)")
 _define("nextvlad_serve_every_n", 0, int, "validate / inference with --model NeXtVLADModel (DESIGN.md 7.15): the grid the served tower runs "
         "on, every N-th real frame; 0 = the grid its checkpoint records (model_student/*: every_n; model/*: the teacher's grid, 1 for a "
         "--nextvlad_frames sampled checkpoint).  Another N than the recorded one is a legitimate experiment: the flag wins, with a warning")

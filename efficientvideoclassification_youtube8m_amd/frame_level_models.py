@@ -192,7 +192,10 @@ class NeXtVLADModel(models.BaseModel):
         self.towers = {}
 
     def create_model(self, model_input, vocab_size, num_frames, iterations=None, cluster_size=None, hidden_size=None, groups=None,
-                     expansion=None, gating_reduction=None, is_training=True, frames=None, every_n=None, **unused_params):
+                     expansion=None, gating_reduction=None, is_training=True, frames=None, every_n=None, dropout=None, dropout_seed=None,
+                     dropout_step=0, **unused_params):
+        """dropout / dropout_seed (None: --nextvlad_dropout / --nextvlad_dropout_seed): the drop rate before the hidden layer in training
+        (DESIGN.md 7.17); dropout_step (a host integer) is the mask's step counter, the caller's global_step."""
         if model_input is None:
             return                                                   # the reference's stub
         iterations = iterations or FLAGS.iterations
@@ -203,6 +206,9 @@ class NeXtVLADModel(models.BaseModel):
         groups = groups or FLAGS.nextvlad_groups
         expansion = expansion or FLAGS.nextvlad_expansion
         gating_reduction = gating_reduction or FLAGS.nextvlad_gating_reduction
+        dropout = FLAGS.nextvlad_dropout if dropout is None else dropout
+        dropout_seed = FLAGS.nextvlad_dropout_seed if dropout_seed is None else dropout_seed
+        ops.check_dropout_rate(dropout, "--nextvlad_dropout")        # (before the device is touched)
         _vl_check()
         if not model_input.is_cuda:
             raise ops._lib.EvcError("NeXtVLADModel needs a device tensor (got a CPU tensor); there is no CPU path")
@@ -212,16 +218,18 @@ class NeXtVLADModel(models.BaseModel):
         if tw is None:
             tw = self.towers[scope] = NeXtVladTower(B, T, F, vocab_size, iterations, cluster_size, hidden_size, groups, expansion,
                                                     gating_reduction, FLAGS.moe_num_mixtures, device=model_input.device, training=True,
-                                                    scope=scope, seed=unused_params.get("seed", 0), frames=frames, every_n=every_n)
+                                                    scope=scope, seed=unused_params.get("seed", 0), frames=frames, every_n=every_n,
+                                                    dropout=dropout, dropout_seed=dropout_seed)
         nf = num_frames.reshape(-1).to(torch.int32)
         if tw.frames == "grid":                                      # no draw; the host frame counts lay out the packed rows
             return {"predictions": tw.forward(model_input.contiguous(), nf, normalize=unused_params.get("normalize_input", False),
-                                              is_training=is_training, num_frames_host=unused_params.get("num_frames_host"))}
+                                              is_training=is_training, num_frames_host=unused_params.get("num_frames_host"),
+                                              dropout_step=dropout_step)}
         u = unused_params.get("uniform")
         if u is None:
             u = torch.rand((B, iterations), dtype=torch.float32, device=model_input.device)
         return {"predictions": tw.forward(model_input.contiguous(), nf, u, normalize=unused_params.get("normalize_input", False),
-                                          is_training=is_training)}
+                                          is_training=is_training, dropout_step=dropout_step)}
 
     def create_model_inference(self, model_input, vocab_size, every_n, num_frames, **unused_params):
         return

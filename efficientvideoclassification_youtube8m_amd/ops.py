@@ -1550,6 +1550,40 @@ def nextvlad_bias_logits(be, W, N, E, out, add=None):
     _lib.call("evc_nextvlad_bias_logits", _p(be), _p(W), N, E, _p(add), _p(out), out.numel(), _stream())
 
 
+def check_dropout_rate(rate, what="dropout"):
+    """The DROP rate as a Python float; a value outside [0, 1) (or not a number) is a ValueError that names it."""
+    r = float(rate)
+    if not (0.0 <= r < 1.0):
+        raise ValueError("%s=%r: the drop rate must lie in [0, 1)" % (what, rate))
+    return r
+
+
+def dropout_threshold(keep):
+    """(T, scale) of the dropout entries for a keep probability in (0, 1]: T = floor(keep * 2^32) as a uint32 (an element is kept
+    iff its Philox word is below T; keep = 1 is refused, it has no such T - a rate of 0 launches nothing) and scale = float32(1 / keep)."""
+    import numpy as np
+    keep = float(keep)
+    T = int(keep * 4294967296.0) if 0.0 < keep < 1.0 else 0        # (the product is exact in float64; int() is floor here)
+    if not (0 < T <= 0xFFFFFFFF):
+        raise ValueError("dropout: keep probability %r has no 32-bit threshold (it must lie in (0, 1) and keep * 2^32 >= 1)" % keep)
+    return T, float(np.float32(1.0 / keep))
+
+
+def nextvlad_dropout_fwd(U, B, Cc, mean, var, gamma, beta, T, scale, seed, rank, step, y_bf16):
+    """y_bf16 [>= B, Cc] = bf16(vlad_bn(U) * scale) where kept, +0 where dropped: bn_apply, the stateless mask of
+    (seed, rank, step, element) and the bf16 store in one pass.  T, scale: dropout_threshold(keep)."""
+    assert U.is_contiguous() and U.dtype == F32 and U.numel() >= B * Cc
+    assert y_bf16.is_contiguous() and y_bf16.dtype == BF16 and y_bf16.numel() >= B * Cc
+    _lib.call("evc_nextvlad_dropout_fwd", _p(U), B, Cc, _p(mean), _p(var), _p(gamma), _p(beta), T, scale, seed & 0xFFFFFFFF,
+              rank & 0xFFFFFFFF, step & 0xFFFFFFFFFFFFFFFF, _p(y_bf16), _stream())
+
+
+def nextvlad_dropout_bwd(dY, B, Cc, T, scale, seed, rank, step):
+    """dY [B, Cc] f32 in place: dY * scale where the forward of the same (seed, rank, step) kept the element, 0 where it dropped it."""
+    assert dY.is_contiguous() and dY.dtype == F32 and dY.numel() >= B * Cc
+    _lib.call("evc_nextvlad_dropout_bwd", _p(dY), B, Cc, T, scale, seed & 0xFFFFFFFF, rank & 0xFFFFFFFF, step & 0xFFFFFFFFFFFFFFFF, _stream())
+
+
 def nextvlad_wgrad_uncenter(dWc, du, be, N, E, dW):
     """dW [N,E] = dWc[:N] + du[:, None] * be[None, :] (the rank-one term a product against the centred operand leaves out)."""
     _lib.call("evc_nextvlad_wgrad_uncenter", _p(dWc), _p(du), _p(be), N, E, _p(dW), _stream())

@@ -696,10 +696,10 @@ class NeXtVladTower(TowerBase):
     float64 in tests/_nextvlad_ref.py: sample S frames -> expansion (.We + be, E = expansion * F) -> per group g of D = E / G
     columns: attention sigmoid(.Wa + ba) and softmax over K clusters of cluster_bn(.Wc) -> V[k] = sum_{s,g} a[s,g,k] (xe[s,g,:] -
     c2[k]) -> l2 per cluster -> vlad_bn -> .Wh -> hidden1_bn -> context gating (h * sigmoid(relu6(gating_bn(h.Wg1)).Wg2)) -> MoE.
-    Two stated deviations from the paper's code: relu6 where it has relu (the fused batch-norm tail knows relu6 only) and no
-    dropout before the hidden layer.  GEMM-shaped parts on the library's NT / TN kernels (bf16 operands, f32 accumulation), the
-    f32 pieces in csrc/evc_nextvlad.hip.  V / U / Y and vlad_bn are kept cluster-major [K][D]; the TF order d*K + k of
-    vlad_bn/* and of hidden1_weights' rows is restored in state_dict().
+    One stated deviation from the paper's code: relu6 where it has relu (the fused batch-norm tail knows relu6 only).  GEMM-shaped
+    parts on the library's NT / TN kernels (bf16 operands, f32 accumulation), the f32 pieces in csrc/evc_nextvlad.hip.  V / U / Y
+    and vlad_bn are kept cluster-major [K][D]; the TF order d*K + k of vlad_bn/* and of hidden1_weights' rows is restored in
+    state_dict().
 
     frames="grid" (DESIGN.md 7.13): instead of S drawn frames, video b contributes the frames j * every_n < min(n_b, T) - every real
     frame at every_n = 1, the fewer-frames student's grid above - as a ragged list of rows packed back to back (ops.GridPlan);
@@ -708,7 +708,14 @@ class NeXtVladTower(TowerBase):
     Distillation: `state` is the gated hidden vector `out` [B, H], the representation L_REP is taken on, and
     backward(dpred, dstate=...) adds a gradient on it to the MoE head's.  A forward-only grid tower (training=False: the frozen
     teacher) keeps no gradient store or moments and aggregates on the f32 matrix cores (evc_nextvlad_aggregate_packed_fwd_mfma, the
-    bits of the entry the training towers call)."""
+    bits of the entry the training towers call).
+
+    Dropout: dropout = the DROP rate in [0, 1) on the hidden layer's operand in training-mode forwards of a training
+    tower, Yd = vlad_bn(U) * m / (1 - rate).  m is a stateless function of (dropout_seed, rank, dropout_step, element) evaluated inside
+    the kernel that writes Y_bf (ops.nextvlad_dropout_fwd, in place of that bn_apply) and again in backward (ops.nextvlad_dropout_bwd on
+    dY); no mask is stored.  rank is the data-parallel rank of the group the step reduces over - process_group, or the default group
+    when none is given, as train.main builds the tower - so ranks drop different elements.  At rate 0, with is_training=False or on
+    a forward-only tower the launches are the ones without the feature."""
 
     PRECISIONS = ("bf16",)             # no split-bf16 forward (set_precision refuses anything else)
     FRAME_MODES = ("sampled", "grid")
@@ -723,11 +730,19 @@ class NeXtVladTower(TowerBase):
 
     def __init__(self, batch_size, max_frames=300, feature_size=1152, vocab_size=4716, iterations=30, cluster_size=64,
                  hidden_size=1024, groups=8, expansion=2, gating_reduction=8, num_mixtures=2, device="cuda:0", training=True,
-                 scope="model", seed=0, process_group=None, frames="sampled", every_n=1):
+                 scope="model", seed=0, process_group=None, frames="sampled", every_n=1, dropout=0.0, dropout_seed=0):
         world = 1
         if process_group is not None and torch.distributed.is_available() and torch.distributed.is_initialized():
             world = torch.distributed.get_world_size(process_group)
         check_nextvlad_frames(frames, every_n, max_frames, world=world)          # (before the device is touched)
+        # The Philox key's rank: that of the group the step's reductions run over.  BatchNorm and GradReducer fall back to the DEFAULT
+        # group when process_group is None (train.main builds the tower that way under a launcher), so the rank does too.
+        rank = 0
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            rank = torch.distributed.get_rank(process_group)
+        self.dropout_seed, self.rank = int(dropout_seed), int(rank)
+        self.set_dropout(dropout)
+        self._drop = None                                                        # (T, scale, step) of the last forward that dropped
         self.frames, self.every_n = frames, int(every_n)
         self.device, self.training, self.scope, self.pg = torch.device(device), training, scope, process_group
         self.T, self.F, self.V, self.S = max_frames, feature_size, vocab_size, iterations
@@ -788,6 +803,12 @@ class NeXtVladTower(TowerBase):
         if not training and frames == "grid":
             self.store.drop_training_state()                         # forward only: the masters alone, as the frozen H-LSTM teacher
         self._alloc(batch_size)
+
+    def set_dropout(self, rate):
+        """The DROP rate in [0, 1) (a ValueError names any other value) and, from it, the constants of the two dropout entries: the
+        threshold T = floor(keep * 2^32) and the scale float32(1 / keep).  0: the feature makes no launch."""
+        self.dropout = ops.check_dropout_rate(rate)
+        self._drop_T, self._drop_scale = ops.dropout_threshold(1.0 - self.dropout) if self.dropout > 0.0 else (0, 1.0)
 
     @classmethod
     def variable_shapes(cls, feature_size, vocab_size, cluster_size, hidden_size, groups, expansion, gating_reduction, num_mixtures):
@@ -945,12 +966,14 @@ class NeXtVladTower(TowerBase):
         self.plan, self.R, self.Rp = plan, plan.R, plan.Rp
         return plan
 
-    def forward(self, x, num_frames, uniform=None, normalize=True, is_training=True, num_frames_host=None, sel=None):
+    def forward(self, x, num_frames, uniform=None, normalize=True, is_training=True, num_frames_host=None, sel=None, dropout_step=0):
         """x [B,T,F] float32 or uint8 raw frames; uniform [B,S] f32 in [0,1): the frame-sampling draw (sampled mode; not read
         in grid mode, which takes num_frames_host, the frame counts on the host, instead).
         A forward-only grid tower keeps the buffers it allocated: a batch of fewer videos uses their first rows.  sel (such a tower
         only): a strictly ascending host sequence of video numbers - the tower runs on those b' videos of the
-        unchanged batch alone, and pred / state hold b' rows, row j for video sel[j]."""
+        unchanged batch alone, and pred / state hold b' rows, row j for video sel[j].
+        dropout_step: the graph's global_step (a host integer), the counter of this forward's dropout mask; backward() regenerates the
+        mask from the step this forward used.  Not read at rate 0, with is_training=False or on a forward-only tower."""
         B = x.shape[0]
         serving = self.frames == "grid" and not self.training
         if sel is not None:
@@ -1002,7 +1025,13 @@ class NeXtVladTower(TowerBase):
             ops.nextvlad_aggregate_fwd(self.a, self.xe, B, S, G, K, D, st.p(self.C2), self.Vv, self.asum)
         ops.nextvlad_normalize_fwd(self.Vv, B, K, D, self.U, self.nrm)
         bv.stats(self.U, B, is_training)
-        ops.bn_apply(self.U, B, K * D, bv.mean, bv.var, bv.gamma(), bv.beta(), False, y_bf16=self.Y_bf)
+        self._drop = None
+        if self.dropout > 0.0 and self.training and is_training:
+            self._drop = (self._drop_T, self._drop_scale, int(dropout_step))
+            ops.nextvlad_dropout_fwd(self.U, B, K * D, bv.mean, bv.var, bv.gamma(), bv.beta(), *self._drop[:2], self.dropout_seed, self.rank,
+                                     self._drop[2], self.Y_bf)
+        else:
+            ops.bn_apply(self.U, B, K * D, bv.mean, bv.var, bv.gamma(), bv.beta(), False, y_bf16=self.Y_bf)
         ops.gemm_nt(self.Y_bf, self.shadow_fwd[self.HW], B, H, K * D, self.hid)
         bh.stats(self.hid, B, is_training)
         ops.bn_apply(self.hid, B, H, bh.mean, bh.var, bh.gamma(), bh.beta(), False, y_f32=self.h, y_bf16=self.h_bf)
@@ -1051,6 +1080,8 @@ class NeXtVladTower(TowerBase):
         if on_stage is not None:
             on_stage(1)
         ops.gemm_nt(self.dhid_bf, self.shadow_bwd[self.HW], B, K * D, H, self.dY)
+        if self._drop is not None:                           # dY = dYd * m / keep: the mask of this forward, regenerated
+            ops.nextvlad_dropout_bwd(self.dY, B, K * D, self._drop[0], self._drop[1], self.dropout_seed, self.rank, self._drop[2])
         self.bn_v.backward(self.U, self.dY, B, False, dx_f32=self.dU)
         ops.nextvlad_normalize_bwd(self.Vv, self.nrm, self.dU, B, K, D, self.dV)
         ops.netvlad_dcenters(self.asum, self.dV, B, K, D, st.g(self.C2))                 # the same sum as NetVLAD's centres

@@ -392,6 +392,24 @@ def check_nextvlad_distill_flags():
     return True
 
 
+def check_nextvlad_dropout_flags():
+    """--nextvlad_dropout: a drop rate outside [0, 1) and a non-zero rate with another --model are ValueErrors that name
+    the flags (no device).  Returns the rate.  (--dropout is the reference's unused keep-probability: not read.)"""
+    rate = ops.check_dropout_rate(FLAGS.nextvlad_dropout, "--nextvlad_dropout")
+    if rate > 0.0 and FLAGS.model != "NeXtVLADModel":
+        raise ValueError("--nextvlad_dropout %g with --model %s: the flag is the NeXtVLAD tower's drop rate before its hidden layer "
+                         "(--model NeXtVLADModel); no other model has dropout" % (rate, FLAGS.model))
+    return rate
+
+
+def nextvlad_dropout_metadata(graph):
+    """What a checkpoint records of --nextvlad_dropout: the rate and the seed of the tower that drops (the single tower, or the
+    distillation student), and nothing at rate 0.  validate / inference ignore both entries; the weights are the same either way."""
+    tw = getattr(graph, "student", None) if isinstance(graph, NeXtVladDistillGraph) else getattr(graph, "tower", None)
+    rate = float(getattr(tw, "dropout", 0.0) or 0.0)
+    return {"nextvlad_dropout": rate, "nextvlad_dropout_seed": int(tw.dropout_seed)} if rate > 0.0 else {}
+
+
 def nextvlad_teacher_every_n(sd):
     """The grid the model/* tower of the checkpoint dict ``sd`` runs on as a frozen teacher: the teacher_every_n a distillation
     checkpoint records (its model/* IS such a teacher), else its every_n when it records nextvlad_frames == "grid", else 1 - a sampled
@@ -515,7 +533,8 @@ def build_graph(model, label_loss_fn, feature_size, batch_size, every_n, device,
         return NeXtVladDistillGraph(batch_size, every_n=every_n, teacher_every_n=teacher_every_n, feature_size=feature_size,
                                     vocab_size=NUM_CLASSES, max_frames=FLAGS.max_num_frames, cluster_size=cs, hidden_size=hs, groups=g,
                                     expansion=ex, gating_reduction=gr, num_mixtures=mx, device=device, precision=FLAGS.precision,
-                                    distill_losses=FLAGS.distill_losses, **common)
+                                    distill_losses=FLAGS.distill_losses, dropout=check_nextvlad_dropout_flags(),
+                                    dropout_seed=FLAGS.nextvlad_dropout_seed, **common)
     if FLAGS.teacher_dir:
         raise ValueError("--teacher_dir %s: serial distillation is built for HierarchicalLstmModel and NeXtVLADModel, not %s" %
                          (FLAGS.teacher_dir, type(model).__name__))
@@ -534,7 +553,7 @@ def build_graph(model, label_loss_fn, feature_size, batch_size, every_n, device,
         tw = NeXtVladTower(batch_size, FLAGS.max_num_frames, feature_size, NUM_CLASSES, FLAGS.iterations, FLAGS.nextvlad_cluster_size,
                            FLAGS.nextvlad_hidden_size, FLAGS.nextvlad_groups, FLAGS.nextvlad_expansion, FLAGS.nextvlad_gating_reduction,
                            FLAGS.moe_num_mixtures, device=device, process_group=process_group, frames=FLAGS.nextvlad_frames,
-                           every_n=every_n)
+                           every_n=every_n, dropout=check_nextvlad_dropout_flags(), dropout_seed=FLAGS.nextvlad_dropout_seed)
         _apply_precision(tw)
         return SingleTowerGraph(tw, **common)
     if isinstance(model, frame_level_models.FrameLevelLogisticModel):
@@ -629,6 +648,7 @@ def save_checkpoint(graph, train_dir, rank):
         sd["nextvlad_frames"], sd["every_n"] = "grid", graph.tower.every_n
     if isinstance(graph, NeXtVladDistillGraph):   # metadata: the student's grid and the one the frozen teacher in model/* runs on
         sd["nextvlad_frames"], sd["every_n"], sd["teacher_every_n"] = "grid", graph.every_n, graph.teacher_every_n
+    sd.update(nextvlad_dropout_metadata(graph))   # metadata: --nextvlad_dropout and its seed, when the tower was trained with a non-zero rate
     fn = getattr(graph, "label_loss", None)
     if fn is not None and not losses.is_default(fn):            # metadata: the --label_loss these weights were trained on (the default: no key)
         sd["label_loss"] = type(fn).__name__
@@ -700,6 +720,7 @@ def main(argv=None):
     serial = check_serial_flags(finetune, world, students=multi)
     check_label_loss(find_class_by_name(FLAGS.label_loss, [losses])(), finetune)
     nx_distill = serial and check_nextvlad_distill_flags()
+    check_nextvlad_dropout_flags()
     check_nextvlad_frames(FLAGS.nextvlad_frames, FLAGS.every_n, FLAGS.max_num_frames, model=FLAGS.model, world=world, precision=FLAGS.precision)
     nx_src = None
     if nx_distill:

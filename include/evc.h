@@ -921,6 +921,18 @@ int evc_nextvlad_wgrad_uncenter(const float* dWc, const float* du, const float* 
 /* out[c] = sum_r x[r*ld + c], rows added in a fixed order (bias gradients).  ws (may be NULL): 32 * C floats of scratch; with it,
  * inputs of 512 rows or more are summed over 32 row ranges per 64 columns and the partial rows added in range order. */
 int evc_nextvlad_colsum(const float* x, int64_t ld, int R, int C, float* out, float* ws, int64_t ws_floats, void* stream);
+/* Dropout before the hidden layer, over the [B][C] buffers of the tower (C = K*D, internal cluster-major order).
+ * Element e = b*C + j is lane e & 3 of quad e >> 2; it is KEPT iff Philox4x32-10(counter (q_lo, q_hi, step_lo, step_hi),
+ * key (seed, rank))[e & 3] < T as unsigned 32-bit values, T = floor(keep * 2^32), scale = float32(1 / keep), both from the host.
+ * The mask is a function of (seed, rank, step, e) alone and is never stored: the backward entry regenerates it.
+ *   _fwd: Y_bf16[e] = bf16(((U[e] - mean[c]) * rsqrt(var[c] + 1e-3) * gamma[c] + beta[c]) * scale) where kept, +0 where dropped
+ *         (c = e % C; the expression of evc_bn_apply without relu6): batch-norm apply, mask and bf16 store in one pass.
+ *   _bwd: dY[e] = dY[e] * scale where kept (one f32 multiply), +0 where dropped, in place.
+ * Refused before any launch: B <= 0 or C % 4 != 0 (EVC_ERR_BAD_SHAPE), T == 0 or a NULL operand (EVC_ERR_BAD_ARG), f32 operands that
+ * are not 16-byte aligned or a Y_bf16 that is not 8-byte aligned (EVC_ERR_BAD_ALIGN).  No LDS, no atomics. */
+int evc_nextvlad_dropout_fwd(const float* U, int B, int C, const float* mean, const float* var, const float* gamma, const float* beta,
+                             uint32_t T, float scale, uint32_t seed, uint32_t rank, uint64_t step, evc_bf16* Y_bf16, void* stream);
+int evc_nextvlad_dropout_bwd(float* dY, int B, int C, uint32_t T, float scale, uint32_t seed, uint32_t rank, uint64_t step, void* stream);
 
 /* ---- one LSTM layer's train op in two launches (csrc/evc_optim.hip; a9: cs/train.py:329-334,413-418 + AdamOptimizer :241-242) ----
  * evc_sqnorm2_partials: part[0..1023] = per-block sums of squares of ga [na], part[1024] = sum of squares of gb [nb] (gb may be
