@@ -114,6 +114,8 @@ SIGNATURES = {
     "evc_netvlad_softmax_bwd": [vp, vp, i32, i32, vp, vp],
     "evc_netvlad_aggregate_fwd": [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
     "evc_netvlad_aggregate_bwd": [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "evc_netvlad_aggregate_packed_fwd": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
+    "evc_netvlad_aggregate_packed_bwd": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp],
     "evc_netvlad_dcenters": [vp, vp, i32, i32, i32, vp, vp],
     "evc_netvlad_normalize_fwd": [vp, i32, i32, i32, vp, vp, vp, vp, vp],
     "evc_netvlad_normalize_bwd": [vp, vp, vp, vp, i32, i32, i32, vp, vp],

@@ -1552,7 +1552,7 @@ class SingleTowerGraph(_StepGraph):
 
     def step(self, x_raw, labels_u8, num_frames, uniform=None, apply=True, num_frames_host=None):
         """x_raw [B,T,F] float32 or uint8 (as the reader delivers it: Dequantize is fused into the input kernels).
-        num_frames_host: the frame counts on the host, for a NeXtVladTower in grid mode (its packed rows are laid out from them
+        num_frames_host: the frame counts on the host, for a NeXtVladTower / NetVladTower in grid mode (its packed rows are laid out from them
         without a device sync; no draw is made in that mode)."""
         from .towers import DbofGenericTower, DbofTower, NetVladTower, NeXtVladTower
         B, V = labels_u8.shape
@@ -1564,7 +1564,7 @@ class SingleTowerGraph(_StepGraph):
                              "allowed under data parallelism: drop the remainder)" % (B, tw.B))
         # (a NeXtVLAD tower's dropout mask is a function of the step: a restored run draws the same masks)
         kw = {"dropout_step": self.global_step} if isinstance(tw, NeXtVladTower) else {}
-        if isinstance(tw, NeXtVladTower) and tw.frames == "grid":
+        if isinstance(tw, (NetVladTower, NeXtVladTower)) and tw.frames == "grid":
             pred = tw.forward(x_raw, num_frames, num_frames_host=num_frames_host, **kw)
         elif isinstance(tw, (DbofTower, NetVladTower, NeXtVladTower, DbofGenericTower)):
             if uniform is None:     # (SampleRandomSequence draws one start per video: column 0 is used)
@@ -1867,3 +1867,62 @@ class NeXtVladEvalGraph(_StepGraph):
         k[sel if sel is not None else slice(None)] = served.plan.k
         out.update(predictions=pred, loss=self.losses[0], student_label_loss=self.losses[0], num_frames=torch.from_numpy(k))
         return out
+
+
+def check_netvlad_checkpoint(sd, scope, feature_size, vocab_size, sizes, what="the checkpoint"):
+    """The ``scope``/* variables of the checkpoint dict ``sd`` against the size flags (sizes: cluster_size, hidden_size, num_mixtures), on
+    the host: ValueError naming the first missing or mismatching variable and both shapes."""
+    from .towers import NetVladTower
+    for k, shp in NetVladTower.checkpoint_shapes(feature_size, vocab_size, *sizes).items():
+        have = sd.get("%s/%s" % (scope, k))
+        if not torch.is_tensor(have):
+            raise ValueError("%s holds no variable %s/%s (not a NetVLADModel checkpoint)" % (what, scope, k))
+        if tuple(have.shape) != shp:
+            raise ValueError("%s/%s of %s has shape %s, the size flags (--netvlad_* / --feature_sizes / --moe_num_mixtures) give %s"
+                             % (scope, k, what, tuple(have.shape), shp))
+
+
+class NetVladEvalGraph(_StepGraph):
+    """Forward-only graph of the NetVLAD family with EvalGraph's interface: restore(state_dict) and
+    step(x_raw, labels_u8, num_frames, num_frames_host=None, keys=None) -> dict with predictions, loss, num_frames, so that validate
+    holds it where it holds an EvalGraph.  One forward-only grid tower, scope model, on every `every_n`-th real frame (training=False:
+    the moving statistics), bf16 only, on the caller's stream.  No row compaction: a video without a frame runs through the head with
+    V = 0 like any other and its row holds what the head makes of that.  The buffers are allocated once at batch_size: a shorter batch
+    allocates nothing."""
+
+    family = "netvlad"
+    student_sampling = "uniform"
+
+    def __init__(self, batch_size, every_n=1, feature_size=1152, vocab_size=4716, max_frames=300, cluster_size=64, hidden_size=1024,
+                 num_mixtures=2, device="cuda:0", precision="bf16", label_loss=None, seed=7):
+        from .towers import NetVladTower, check_netvlad_frames
+        check_netvlad_frames("grid", every_n, max_frames, precision=precision)       # (before the device is touched)
+        self.label_loss = _resolve_label_loss(label_loss, vocab_size)
+        self.every_n, self.batch_size, self.max_frames, self.precision = int(every_n), batch_size, max_frames, precision
+        self.sizes = (cluster_size, hidden_size, num_mixtures)
+        self.F, self.V = feature_size, vocab_size
+        self.device = torch.device(device)
+        self.teacher = NetVladTower(batch_size, max_frames, feature_size, vocab_size, 30, cluster_size, hidden_size, num_mixtures, device=device,
+                                    training=False, scope="model", seed=seed, frames="grid", every_n=self.every_n)
+        self.student = None
+        self.losses = torch.zeros(1, dtype=F32, device=self.device)
+
+    def restore(self, state_dict):
+        """The tower's variables and moving statistics by name, after the host check of their shapes against the graph's sizes."""
+        check_netvlad_checkpoint(state_dict, self.teacher.scope, self.F, self.V, self.sizes)
+        self.teacher.load_state_dict(state_dict)
+
+    def step(self, x_raw, labels_u8, num_frames, num_frames_host=None, keys=None):
+        """x_raw [b, T, F] uint8 or float32, b <= batch_size; labels_u8 [b, V]; num_frames [b] int32 (num_frames_host: the same counts
+        on the host; read back from the device when not given).  keys is EvalGraph's argument and is not read."""
+        b = int(x_raw.shape[0])
+        if b > self.batch_size:
+            raise ValueError("NetVladEvalGraph: a batch of %d videos, the graph was built for %d" % (b, self.batch_size))
+        if num_frames_host is None:
+            num_frames_host = num_frames.cpu()
+        nh = np.asarray(num_frames_host, dtype=np.int64).reshape(-1)
+        tw = self.teacher
+        pred = tw.forward(x_raw, num_frames, is_training=False, num_frames_host=nh)
+        self.losses.zero_()
+        self.label_loss.fused(pred, labels_u8, self.losses[0:1])
+        return dict(predictions=pred, loss=self.losses[0], num_frames=torch.from_numpy(tw.plan.k.copy()))

@@ -137,6 +137,12 @@ _define("precision", "bf16", str, "'bf16' (one bf16 MFMA product per forward con
         "'split' (split-bf16 operands, f32-operand accuracy, in every forward GEMM)")
 _define("netvlad_cluster_size", 64, int, "NetVLADModel (extension): number of clusters")
 _define("netvlad_hidden_size", 1024, int, "NetVLADModel (extension): width of the hidden layer after the aggregation")
+_define("netvlad_frames", "sampled", str, "NetVLADModel (extension, DESIGN.md 7.18): sampled (--iterations <= 64 frames drawn per video and "
+        "step) | grid (the frames 0, every_n, 2 every_n, ... of each video's real frames, a different number per video, packed without "
+        "padding: --every_n 1 is every real frame, the teacher's input; --every_n 10 or 30 the fewer-frames student's; --iterations is not read)")
+_define("netvlad_serve_every_n", 0, int, "validate with --model NetVLADModel (DESIGN.md 7.18): the grid the served tower runs on, every N-th "
+        "real frame; 0 = as the checkpoint records (its every_n for a --netvlad_frames grid checkpoint, 1 - every real frame - for a sampled "
+        "one).  Another N than the recorded one is a legitimate experiment: the flag wins, with a warning")
 _define("nextvlad_cluster_size", 64, int, "NeXtVLADModel (extension): number of clusters")
 _define("nextvlad_hidden_size", 1024, int, "NeXtVLADModel (extension): width of the hidden layer after the aggregation")
 _define("nextvlad_groups", 8, int, "NeXtVLADModel (extension): number of groups the expanded frame is split into")

@@ -159,8 +159,10 @@ class NetVLADModel(models.BaseModel):
         self.towers = {}
 
     def create_model(self, model_input, vocab_size, num_frames, iterations=None, cluster_size=None, hidden_size=None,
-                     is_training=True, **unused_params):
+                     is_training=True, frames=None, every_n=None, **unused_params):
         iterations = iterations or FLAGS.iterations
+        frames = frames or FLAGS.netvlad_frames                      # "grid": every every_n-th real frame, packed
+        every_n = every_n or FLAGS.every_n
         cluster_size = cluster_size or FLAGS.netvlad_cluster_size
         hidden_size = hidden_size or FLAGS.netvlad_hidden_size
         _vl_check()
@@ -170,8 +172,11 @@ class NetVLADModel(models.BaseModel):
         if tw is None:
             tw = self.towers[scope] = NetVladTower(B, T, F, vocab_size, iterations, cluster_size, hidden_size, FLAGS.moe_num_mixtures,
                                                    device=model_input.device, training=True, scope=scope,
-                                                   seed=unused_params.get("seed", 0))
+                                                   seed=unused_params.get("seed", 0), frames=frames, every_n=every_n)
         nf = num_frames.reshape(-1).to(torch.int32)
+        if tw.frames == "grid":                                      # no draw; the host frame counts lay out the packed rows
+            return {"predictions": tw.forward(model_input.contiguous(), nf, normalize=unused_params.get("normalize_input", False),
+                                              is_training=is_training, num_frames_host=unused_params.get("num_frames_host"))}
         u = unused_params.get("uniform")
         if u is None:
             u = torch.rand((B, iterations), dtype=torch.float32, device=model_input.device)

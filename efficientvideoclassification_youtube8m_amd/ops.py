@@ -1361,6 +1361,30 @@ def netvlad_aggregate_bwd(a, r, B, S, K, F, mean, var, gamma, beta, c2, dV, da, 
               _stream())
 
 
+def netvlad_aggregate_packed_fwd(a, r, row_off, B, T, K, F, R, max_k, mean, var, gamma, beta, c2, V, asum):
+    """netvlad_aggregate_fwd over packed rows: video b's a / r rows are row_off[b] .. row_off[b+1] (device int32 [B+1],
+    GridPlan.row_off), any number of them up to T; on the f32 matrix cores, for training and forward-only towers alike."""
+    assert row_off.dtype == torch.int32 and row_off.numel() == B + 1
+    assert a.numel() >= R * K and r.numel() >= R * F and V.numel() >= B * K * F and asum.numel() >= B * K
+    _lib.call("evc_netvlad_aggregate_packed_fwd", _p(a), _p(r), _p(row_off), B, T, K, F, R, max_k, _p(mean), _p(var), _p(gamma), _p(beta),
+              _p(c2), _p(V), _p(asum), _stream())
+
+
+def netvlad_aggregate_packed_bwd_ws(B, K, F):
+    """Floats of scratch evc_netvlad_aggregate_packed_bwd needs: dV transposed [B][F][K rounded up to 4] and q [B][K]."""
+    return B * F * round_up(K, 4) + B * K
+
+
+def netvlad_aggregate_packed_bwd(a, r, row_off, B, T, K, F, R, max_k, mean, var, gamma, beta, c2, dV, da, dx, ws=None):
+    """netvlad_aggregate_bwd over packed rows: the R live rows of da and dx are written, nothing beyond them."""
+    assert row_off.dtype == torch.int32 and row_off.numel() == B + 1
+    assert a.numel() >= R * K and r.numel() >= R * F and da.numel() >= R * K and dx.numel() >= R * F and dV.numel() >= B * K * F
+    if ws is None:
+        ws = torch.empty(netvlad_aggregate_packed_bwd_ws(B, K, F), dtype=F32, device=da.device)
+    _lib.call("evc_netvlad_aggregate_packed_bwd", _p(a), _p(r), _p(row_off), B, T, K, F, R, max_k, _p(mean), _p(var), _p(gamma), _p(beta),
+              _p(c2), _p(dV), _p(da), _p(dx), _p(ws), ws.numel(), _stream())
+
+
 def netvlad_dcenters(asum, dV, B, K, F, dc2):
     _lib.call("evc_netvlad_dcenters", _p(asum), _p(dV), B, K, F, _p(dc2), _stream())
 

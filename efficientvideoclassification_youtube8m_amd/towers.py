@@ -512,6 +512,35 @@ class DbofGenericTower(TowerBase):
         return self.moe.pred
 
 
+def _plan_grid_rows(tw, num_frames, num_frames_host, sel=None, flag="--nextvlad_frames"):
+    """Grid mode of a tower (NeXtVLAD, NetVLAD): this batch's packed layout from the HOST frame counts (launch sizes and offsets without
+    a device sync); row_off goes up through one of two pinned buffers, reused only once its earlier copy has completed.  sel (int32
+    numpy, accepted by ops.check_row_selection): the layout of those videos alone, and sel itself goes up the same way."""
+    if num_frames_host is None:
+        num_frames_host = num_frames.cpu().numpy()       # an explicit device sync: callers that have the counts on the host pass them
+    if sel is not None:
+        num_frames_host = np.asarray(num_frames_host).reshape(-1)[sel]
+    plan = ops.GridPlan(num_frames_host, tw.every_n, tw.T)
+    if plan.B != tw.B:
+        raise ValueError("num_frames_host holds %d videos, the batch %d" % (plan.B, tw.B))
+    if plan.R == 0:
+        raise ValueError("%s grid: no video of the batch has a frame" % flag)
+    slot = tw._uploads % 2
+    tw._uploads += 1
+    if tw._row_off_done[slot] is not None:
+        tw._row_off_done[slot].synchronize()
+    B = plan.B
+    tw._row_off_host[slot][:B + 1].copy_(torch.from_numpy(plan.row_off))
+    tw.row_off[:B + 1].copy_(tw._row_off_host[slot][:B + 1], non_blocking=True)
+    if sel is not None:
+        tw._sel_host[slot][:B].copy_(torch.from_numpy(sel))
+        tw.sel[:B].copy_(tw._sel_host[slot][:B], non_blocking=True)
+    ev = tw._row_off_done[slot] = torch.cuda.Event()
+    ev.record()
+    tw.plan, tw.R, tw.Rp = plan, plan.R, plan.Rp
+    return plan
+
+
 class NetVladTower(TowerBase):
     """NetVLAD aggregation tower - an EXTENSION: the reference announces NetVLAD / NeXtVLAD teacher-student variants
     (README.md:126-127) but ships empty stubs (cs/frame_level_models.py:341-355), so there is no reference math; the
@@ -519,9 +548,17 @@ class NetVladTower(TowerBase):
     DBoF tower): sample S frames -> input_bn -> .Wc -> cluster_bn -> softmax over K clusters -> V[k] = sum_s a[s,k] (x_s - c2[k])
     -> intra-normalise -> l2-normalise -> .Wh -> hidden1_bn -> relu6 -> MoE.
     GEMM-shaped parts on the library's NT / TN kernels, the f32 pieces in csrc/evc_netvlad.hip.  V / Y are kept
-    cluster-major [B][K][F]; hidden1_weights' TF row order f*K + k is restored in state_dict()."""
+    cluster-major [B][K][F]; hidden1_weights' TF row order f*K + k is restored in state_dict().
+
+    frames="grid" (DESIGN.md 7.18): instead of S drawn frames, video b contributes the frames j * every_n < min(n_b, T) - every real
+    frame at every_n = 1, the fewer-frames student's grid above - as a ragged list of rows packed back to back (ops.GridPlan), with
+    no limit on the rows of a video; padding frames are never computed.  The two batch-norms in front of the aggregation take their
+    statistics over the R live rows, the aggregation runs on evc_netvlad_aggregate_packed_fwd / _bwd.  Same weights and checkpoint
+    names: a tower of either mode loads the other's checkpoint.  A forward-only grid tower (training=False) keeps no gradient store
+    or moments, runs on the moving statistics and serves batches of up to batch_size videos in the buffers it allocated."""
 
     PRECISIONS = ("bf16",)             # no split-bf16 forward (set_precision refuses anything else)
+    FRAME_MODES = ("sampled", "grid")
 
     CW, C2, HW = "cluster_weights", "cluster_weights2", "hidden1_weights"
     l2_names = (MoeHead.GATES, MoeHead.EXPERTS)
@@ -529,23 +566,22 @@ class NetVladTower(TowerBase):
     global_grad_names = tuple("%s/%s" % (s_, v) for s_ in ("input_bn", "cluster_bn", "hidden1_bn") for v in ("beta", "gamma"))
 
     def __init__(self, batch_size, max_frames=300, feature_size=1152, vocab_size=4716, iterations=30, cluster_size=64,
-                 hidden_size=1024, num_mixtures=2, device="cuda:0", training=True, scope="model", seed=0, process_group=None):
+                 hidden_size=1024, num_mixtures=2, device="cuda:0", training=True, scope="model", seed=0, process_group=None,
+                 frames="sampled", every_n=1):
+        world = 1
+        if process_group is not None and torch.distributed.is_available() and torch.distributed.is_initialized():
+            world = torch.distributed.get_world_size(process_group)
+        check_netvlad_frames(frames, every_n, max_frames, world=world)           # (before the device is touched)
+        self.frames, self.every_n = frames, int(every_n)
         self.device, self.training, self.scope, self.pg = torch.device(device), training, scope, process_group
         self.T, self.F, self.V, self.S = max_frames, feature_size, vocab_size, iterations
         self.Kc, self.Hd, self.Mx = cluster_size, hidden_size, num_mixtures
         if feature_size % 64 or cluster_size % 64 or hidden_size % 64:
             raise ValueError("feature / cluster / hidden sizes must be multiples of 64 for the MFMA GEMM tiles")
-        if iterations > 64:
+        if frames == "sampled" and iterations > 64:                  # (grid mode does not read iterations)
             raise ValueError("iterations=%d: the aggregation kernel holds at most 64 sampled frames per video" % iterations)
         F, K, H = feature_size, cluster_size, hidden_size
-        shapes = OrderedDict()
-        shapes.update(BatchNorm.shapes("input_bn", F))
-        shapes[self.CW] = (K, F)                                     # stored transposed [K][F]
-        shapes.update(BatchNorm.shapes("cluster_bn", K))
-        shapes[self.C2] = (K, F)                                     # centres, stored [K][F] (tf: [1, F, K])
-        shapes[self.HW] = (H, K * F)                                 # stored transposed, columns cluster-major (k*F + f)
-        shapes.update(BatchNorm.shapes("hidden1_bn", H))
-        shapes.update(MoeHead.shapes(H, vocab_size, num_mixtures))
+        shapes = self.variable_shapes(F, vocab_size, K, H, num_mixtures)
         self.buffers = OrderedDict()
         self._setup_store(shapes)
         self.bn_in = BatchNorm(self, "input_bn", F)
@@ -566,7 +602,35 @@ class NetVladTower(TowerBase):
             elif k.endswith("/gamma"):
                 p.fill_(1.0)
         self.refresh_shadows()
+        if not training and frames == "grid":
+            self.store.drop_training_state()                         # forward only: the masters alone
         self._alloc(batch_size)
+
+    @classmethod
+    def variable_shapes(cls, feature_size, vocab_size, cluster_size, hidden_size, num_mixtures):
+        """The trainable variables and their INTERNAL shapes, in store order, from the size flags alone (no device)."""
+        F, K, H = feature_size, cluster_size, hidden_size
+        shapes = OrderedDict()
+        shapes.update(BatchNorm.shapes("input_bn", F))
+        shapes[cls.CW] = (K, F)                                      # stored transposed [K][F]
+        shapes.update(BatchNorm.shapes("cluster_bn", K))
+        shapes[cls.C2] = (K, F)                                      # centres, stored [K][F] (tf: [1, F, K])
+        shapes[cls.HW] = (H, K * F)                                  # stored transposed, columns cluster-major (k*F + f)
+        shapes.update(BatchNorm.shapes("hidden1_bn", H))
+        shapes.update(MoeHead.shapes(H, vocab_size, num_mixtures))
+        return shapes
+
+    @classmethod
+    def checkpoint_shapes(cls, *sizes, **kw):
+        """What state_dict() holds for these size flags, without the scope prefix: every variable in its TF layout (2-D weights
+        [in][out]) and the batch norms' moving statistics.  For checking a checkpoint against the flags before a tower is built."""
+        out = OrderedDict()
+        for k, shp in cls.variable_shapes(*sizes, **kw).items():
+            out[k] = tuple(reversed(shp)) if len(shp) == 2 else tuple(shp)
+            if k.endswith("/gamma"):
+                for v in ("moving_mean", "moving_variance"):
+                    out[k[:-len("gamma")] + v] = tuple(shp)
+        return out
 
     # hidden1_weights: TF layout [F*K, H] with row f*K + k  <->  internal [H][k*F + f]
     def state_dict(self):
@@ -588,14 +652,27 @@ class NetVladTower(TowerBase):
 
     def _alloc(self, B):
         dev, F, S, K, H = self.device, self.F, self.S, self.Kc, self.Hd
-        self.B, self.R = B, B * S
-        if self.training and self.R % 32:
-            raise ValueError("batch_size x iterations = %d must be a multiple of 32 (row count of the TN weight-gradient products)" % self.R)
-        R = self.R
+        grid = self.frames == "grid"
+        if grid:
+            # every row buffer once, for every video at full length; a batch uses its first R (Rp in the TN products) rows.
+            # The bf16 operands of the TN products start as zeros: their rows R .. Rp are zeroed again at every step.
+            self.B, self.R, self.Rp, self.plan = B, 0, 0, None
+            R = ops.grid_capacity(B, self.T, self.every_n)
+            self.row_off = torch.zeros(B + 1, dtype=torch.int32, device=dev)
+            self._row_off_host = [torch.zeros(B + 1, dtype=torch.int32).pin_memory() for _ in range(2)]
+            self._row_off_done = [None, None]
+            self._uploads = 0
+        else:
+            self.B, self.R = B, B * S
+            if self.training and self.R % 32:
+                raise ValueError("batch_size x iterations = %d must be a multiple of 32 (row count of the TN weight-gradient products)" % self.R)
+            R = self.R
+        self.cap = B                                                 # videos the buffers hold (forward-only grid towers serve B <= cap)
         self.Bk = ops.round_up(B, 32)
         self.r = torch.empty((R, F), dtype=F32, device=dev)
-        self.idx = torch.empty((B, S), dtype=torch.int32, device=dev)
-        self.r_bn = torch.empty((R, F), dtype=BF16, device=dev)
+        if not grid:
+            self.idx = torch.empty((B, S), dtype=torch.int32, device=dev)
+        self.r_bn = torch.zeros((R, F), dtype=BF16, device=dev) if grid else torch.empty((R, F), dtype=BF16, device=dev)
         self.act = torch.empty((R, K), dtype=F32, device=dev)
         self.a = torch.empty((R, K), dtype=F32, device=dev)
         self.asum = torch.empty((B, K), dtype=F32, device=dev)
@@ -613,30 +690,55 @@ class NetVladTower(TowerBase):
             self.da = torch.empty((R, K), dtype=F32, device=dev)
             self.dz = torch.empty((R, K), dtype=F32, device=dev)
             self.dx = torch.empty((R, F), dtype=F32, device=dev)
-            self.dact_bf = torch.empty((R, K), dtype=BF16, device=dev)
+            self.dact_bf = torch.zeros((R, K), dtype=BF16, device=dev) if grid else torch.empty((R, K), dtype=BF16, device=dev)
+            if grid:
+                self.agg_ws = torch.empty(ops.netvlad_aggregate_packed_bwd_ws(B, K, F), dtype=F32, device=dev)
 
-    def forward(self, x, num_frames, uniform, normalize=True, is_training=True):
-        """x [B,T,F] float32 or uint8 raw frames; uniform [B,S] f32 in [0,1): the frame-sampling draw."""
+    def forward(self, x, num_frames, uniform=None, normalize=True, is_training=True, num_frames_host=None):
+        """x [B,T,F] float32 or uint8 raw frames; uniform [B,S] f32 in [0,1): the frame-sampling draw (sampled mode; not read in grid
+        mode, which takes num_frames_host, the frame counts on the host, instead).  A forward-only grid tower keeps the buffers it
+        allocated: a batch of fewer videos uses their first rows."""
         B = x.shape[0]
+        grid = self.frames == "grid"
         if B != self.B:
-            self._alloc(B)
-        F, S, K, H, R = self.F, self.S, self.Kc, self.Hd, self.R
+            if grid and not self.training and B <= self.cap:
+                self.B = B
+            else:
+                self._alloc(B)
+        F, S, K, H = self.F, self.S, self.Kc, self.Hd
         st, bi, bc = self.store, self.bn_in, self.bn_cl
         if self.precision != "bf16":
             raise NotImplementedError("NetVladTower has no split-bf16 mode")
-        ops.sample_frames_gather(x, uniform, num_frames, self.r, self.idx, normalize=normalize)
+        if grid:
+            if x.shape[1] != self.T:
+                raise ValueError("the batch holds %d frames per video, the tower was built for max_frames=%d" % (x.shape[1], self.T))
+            plan = _plan_grid_rows(self, num_frames, num_frames_host, None, "--netvlad_frames")
+            R, Rp = plan.R, plan.Rp
+            row_off = self.row_off[:B + 1]
+            ops.frames_gather_packed(x, num_frames, row_off, self.every_n, R, Rp, self.r, normalize=normalize)
+        else:
+            R = self.R
+            ops.sample_frames_gather(x, uniform, num_frames, self.r, self.idx, normalize=normalize)
         bi.stats(self.r, R, is_training)
         ops.bn_apply(self.r, R, F, bi.mean, bi.var, bi.gamma(), bi.beta(), False, y_bf16=self.r_bn)
+        if grid and Rp > R:
+            self.r_bn[R:Rp].zero_()                          # (a longer earlier batch leaves stale rows there)
         ops.gemm_nt(self.r_bn, self.shadow_fwd[self.CW], R, K, F, self.act)
         bc.stats(self.act, R, is_training)
         ops.netvlad_softmax_fwd(self.act, R, K, bc.mean, bc.var, bc.gamma(), bc.beta(), self.a)
-        ops.netvlad_aggregate_fwd(self.a, self.r, B, S, K, F, bi.mean, bi.var, bi.gamma(), bi.beta(), st.p(self.C2), self.Vv, self.asum)
+        if grid:
+            ops.netvlad_aggregate_packed_fwd(self.a, self.r, row_off, B, self.T, K, F, R, plan.max_k, bi.mean, bi.var, bi.gamma(), bi.beta(),
+                                             st.p(self.C2), self.Vv, self.asum)
+        else:
+            ops.netvlad_aggregate_fwd(self.a, self.r, B, S, K, F, bi.mean, bi.var, bi.gamma(), bi.beta(), st.p(self.C2), self.Vv, self.asum)
         ops.netvlad_normalize_fwd(self.Vv, B, K, F, self.n1, self.n2, self.Y_bf)
         ops.gemm_nt(self.Y_bf, self.shadow_fwd[self.HW], B, H, K * F, self.hid)
         self.bn_h.stats(self.hid, B, is_training)
         ops.bn_apply(self.hid, B, H, self.bn_h.mean, self.bn_h.var, self.bn_h.gamma(), self.bn_h.beta(), True, y_f32=self.h6)
         self._taped = self.training and is_training
-        return self.moe.forward(self.h6)
+        if B == self.cap:
+            return self.moe.forward(self.h6)
+        return self.moe.forward(self.h6[:B], rows=B)[:B]      # (a forward-only grid tower on fewer videos than it was allocated for)
 
     def grad_stages(self):
         moe = [MoeHead.GATES, MoeHead.EXPERTS, MoeHead.EBIAS]
@@ -647,6 +749,8 @@ class NetVladTower(TowerBase):
         assert self.training and self._taped, "backward needs a training-mode forward"
         B, F, S, K, H, R = self.B, self.F, self.S, self.Kc, self.Hd, self.R
         st, bi = self.store, self.bn_in
+        grid = self.frames == "grid"
+        Rp = self.Rp if grid else R                          # row count of the TN product (grid: rows R .. Rp of its operands are zeros)
         dh6 = self.moe.backward(dpred, weight_grads=moe_weight_grads)
         if on_moe_grads_ready is not None:
             on_moe_grads_ready()
@@ -659,10 +763,16 @@ class NetVladTower(TowerBase):
         ops.gemm_nt(self.dhid_bf, self.shadow_bwd[self.HW], B, K * F, H, self.dY)
         ops.netvlad_normalize_bwd(self.Vv, self.n1, self.n2, self.dY, B, K, F, self.dV)
         ops.netvlad_dcenters(self.asum, self.dV, B, K, F, st.g(self.C2))
-        ops.netvlad_aggregate_bwd(self.a, self.r, B, S, K, F, bi.mean, bi.var, bi.gamma(), bi.beta(), st.p(self.C2), self.dV, self.da, self.dx)
+        if grid:
+            ops.netvlad_aggregate_packed_bwd(self.a, self.r, self.row_off[:B + 1], B, self.T, K, F, R, self.plan.max_k, bi.mean, bi.var, bi.gamma(),
+                                             bi.beta(), st.p(self.C2), self.dV, self.da, self.dx, ws=self.agg_ws)
+        else:
+            ops.netvlad_aggregate_bwd(self.a, self.r, B, S, K, F, bi.mean, bi.var, bi.gamma(), bi.beta(), st.p(self.C2), self.dV, self.da, self.dx)
         ops.netvlad_softmax_bwd(self.a, self.da, R, K, self.dz)
         self.bn_cl.backward(self.act, self.dz, R, False, dx_bf16=self.dact_bf)
-        ops.gemm_tn(self.dact_bf, self.r_bn, K, F, R, st.g(self.CW))                   # dWc^T [K][F]
+        if grid and Rp > R:
+            self.dact_bf[R:Rp].zero_()
+        ops.gemm_tn(self.dact_bf, self.r_bn, K, F, Rp, st.g(self.CW))                  # dWc^T [K][F]
         ops.gemm_nt(self.dact_bf, self.shadow_bwd[self.CW], R, F, K, self.dx, accumulate=True)   # + dact . Wc^T
         bi.backward(self.r, self.dx, R, False)
         if on_stage is not None:
@@ -670,7 +780,24 @@ class NetVladTower(TowerBase):
 
     @property
     def pred(self):
-        return self.moe.pred
+        return self.moe.pred if self.B == self.cap else self.moe.pred[:self.B]
+
+
+def check_netvlad_frames(frames, every_n, max_frames, model=None, world=1, precision="bf16"):
+    """The combinations --netvlad_frames / --every_n refuse, as ValueErrors that name the flags; touches no device."""
+    if frames not in NetVladTower.FRAME_MODES:
+        raise ValueError("--netvlad_frames %r: one of %s" % (frames, "|".join(NetVladTower.FRAME_MODES)))
+    if frames != "grid":
+        return
+    if model is not None and model != "NetVLADModel":
+        raise ValueError("--netvlad_frames grid is built for --model NetVLADModel, not %s" % model)
+    if every_n < 1 or every_n > max_frames:
+        raise ValueError("--netvlad_frames grid: --every_n %d must lie in 1 .. --max_num_frames %d" % (every_n, max_frames))
+    if world > 1:
+        raise ValueError("--netvlad_frames grid refuses a process group of %d ranks: ragged ranks hold different row counts and the "
+                         "batch-norm statistics assume equal ones; data parallelism is not built for this mode" % world)
+    if precision != "bf16":
+        raise ValueError("--netvlad_frames grid: --precision %s is refused, the NetVLAD tower has no such forward mode (bf16 only)" % precision)
 
 
 def check_nextvlad_frames(frames, every_n, max_frames, model=None, world=1, precision="bf16"):
@@ -939,32 +1066,8 @@ class NeXtVladTower(TowerBase):
             self.dWa_pad = torch.empty((AP, E), dtype=F32, device=dev)      # the attention weight gradient on a whole tile of rows
 
     def _plan_rows(self, num_frames, num_frames_host, sel=None):
-        """Grid mode: this batch's packed layout from the HOST frame counts (launch sizes and offsets without a device sync);
-        row_off goes up through one of two pinned buffers, reused only once its earlier copy has completed.  sel (int32 numpy,
-        accepted by ops.check_row_selection): the layout of those videos alone, and sel itself goes up the same way."""
-        if num_frames_host is None:
-            num_frames_host = num_frames.cpu().numpy()       # an explicit device sync: callers that have the counts on the host pass them
-        if sel is not None:
-            num_frames_host = np.asarray(num_frames_host).reshape(-1)[sel]
-        plan = ops.GridPlan(num_frames_host, self.every_n, self.T)
-        if plan.B != self.B:
-            raise ValueError("num_frames_host holds %d videos, the batch %d" % (plan.B, self.B))
-        if plan.R == 0:
-            raise ValueError("--nextvlad_frames grid: no video of the batch has a frame")
-        slot = self._uploads % 2
-        self._uploads += 1
-        if self._row_off_done[slot] is not None:
-            self._row_off_done[slot].synchronize()
-        B = plan.B
-        self._row_off_host[slot][:B + 1].copy_(torch.from_numpy(plan.row_off))
-        self.row_off[:B + 1].copy_(self._row_off_host[slot][:B + 1], non_blocking=True)
-        if sel is not None:
-            self._sel_host[slot][:B].copy_(torch.from_numpy(sel))
-            self.sel[:B].copy_(self._sel_host[slot][:B], non_blocking=True)
-        ev = self._row_off_done[slot] = torch.cuda.Event()
-        ev.record()
-        self.plan, self.R, self.Rp = plan, plan.R, plan.Rp
-        return plan
+        """Grid mode: this batch's packed layout from the HOST frame counts (_plan_grid_rows)."""
+        return _plan_grid_rows(self, num_frames, num_frames_host, sel, "--nextvlad_frames")
 
     def forward(self, x, num_frames, uniform=None, normalize=True, is_training=True, num_frames_host=None, sel=None, dropout_step=0):
         """x [B,T,F] float32 or uint8 raw frames; uniform [B,S] f32 in [0,1): the frame-sampling draw (sampled mode; not read

@@ -43,7 +43,7 @@ import torch
 from . import eval_util, frame_level_models, losses, ops, readers, video_level_models
 from .distill import DistillGraph, EnsembleDistillGraph, NeXtVladDistillGraph, OfflineDistillGraph, SerialStudentsGraph, SingleTowerGraph
 from .flags import FLAGS, GetListOfFeatureNamesAndSizes
-from .towers import DbofTower, LogisticTower, NetVladTower, NeXtVladTower, check_nextvlad_frames
+from .towers import DbofTower, LogisticTower, NetVladTower, NeXtVladTower, check_netvlad_frames, check_nextvlad_frames
 
 NUM_CLASSES = 4716       # readers.YT8MFrameFeatureReader default num_classes (cs/readers.py:121)
 
@@ -546,7 +546,8 @@ def build_graph(model, label_loss_fn, feature_size, batch_size, every_n, device,
         return SingleTowerGraph(tw, **common)
     if isinstance(model, frame_level_models.NetVLADModel):          # extension (the reference's class is an empty stub)
         tw = NetVladTower(batch_size, FLAGS.max_num_frames, feature_size, NUM_CLASSES, FLAGS.iterations, FLAGS.netvlad_cluster_size,
-                          FLAGS.netvlad_hidden_size, FLAGS.moe_num_mixtures, device=device, process_group=process_group)
+                          FLAGS.netvlad_hidden_size, FLAGS.moe_num_mixtures, device=device, process_group=process_group,
+                          frames=FLAGS.netvlad_frames, every_n=every_n)
         _apply_precision(tw)
         return SingleTowerGraph(tw, **common)
     if isinstance(model, frame_level_models.NeXtVLADModel):         # extension (the reference's class is an empty stub)
@@ -644,8 +645,8 @@ def save_checkpoint(graph, train_dir, rank):
     if isinstance(graph, OfflineDistillGraph) and getattr(graph, "teacher_record", None):    # metadata: trained against these prediction files
         sd["distill_mode"], sd["distill_losses"] = "offline", ",".join(graph.offline_losses)
         sd["distill_teacher_files"] = graph.teacher_record
-    if getattr(getattr(graph, "tower", None), "frames", None) == "grid":      # metadata: the frames this tower was trained on (--nextvlad_frames grid)
-        sd["nextvlad_frames"], sd["every_n"] = "grid", graph.tower.every_n
+    if getattr(getattr(graph, "tower", None), "frames", None) == "grid":      # metadata: the frames this tower was trained on (--nextvlad_frames / --netvlad_frames grid)
+        sd["netvlad_frames" if isinstance(graph.tower, NetVladTower) else "nextvlad_frames"], sd["every_n"] = "grid", graph.tower.every_n
     if isinstance(graph, NeXtVladDistillGraph):   # metadata: the student's grid and the one the frozen teacher in model/* runs on
         sd["nextvlad_frames"], sd["every_n"], sd["teacher_every_n"] = "grid", graph.every_n, graph.teacher_every_n
     sd.update(nextvlad_dropout_metadata(graph))   # metadata: --nextvlad_dropout and its seed, when the tower was trained with a non-zero rate
@@ -722,6 +723,7 @@ def main(argv=None):
     nx_distill = serial and check_nextvlad_distill_flags()
     check_nextvlad_dropout_flags()
     check_nextvlad_frames(FLAGS.nextvlad_frames, FLAGS.every_n, FLAGS.max_num_frames, model=FLAGS.model, world=world, precision=FLAGS.precision)
+    check_netvlad_frames(FLAGS.netvlad_frames, FLAGS.every_n, FLAGS.max_num_frames, model=FLAGS.model, world=world, precision=FLAGS.precision)
     nx_src = None
     if nx_distill:
         # the teacher's checkpoint on the host - its grid and its shapes against the size flags -, before the device is touched
@@ -822,7 +824,7 @@ def main(argv=None):
     is_multi = isinstance(graph, SerialStudentsGraph)
     is_ens = isinstance(graph, EnsembleDistillGraph)
     is_distill = isinstance(graph, (DistillGraph, NeXtVladDistillGraph)) or is_multi or is_ens
-    # --nextvlad_frames grid (one tower, or the student and its frozen teacher): the packed rows are laid out from n_host
+    # --nextvlad_frames / --netvlad_frames grid (one tower, or the student and its frozen teacher): the packed rows are laid out from n_host
     is_grid = getattr(getattr(graph, "tower", None), "frames", None) == "grid" or isinstance(graph, NeXtVladDistillGraph)
     steps_per_it = 2 if is_distill and not is_multi and graph.mode == "teacher_student" else 1
     copy_stream = torch.cuda.Stream(device=device)

@@ -29,6 +29,9 @@ videos and the frames each stage read are logged and returned as ``cascade_stage
 teacher + student (the student's metrics, student_loss logged), a single-tower one as model/*, each tower on the grid its checkpoint
 records (--nextvlad_serve_every_n overrides); the graph is built for --train_dir's latest checkpoint, which must exist at the start.
 Ensemble members and cascade stages take their family from their own checkpoints, so H-LSTM and NeXtVLAD members mix.
+``--model NetVLADModel`` evaluates a NetVLAD checkpoint through distill.NetVladEvalGraph: model/* as a forward-only grid
+tower on the grid the checkpoint records, every real frame for a --netvlad_frames sampled one (--netvlad_serve_every_n overrides); its
+variables are checked against the size flags on the host first.  No ensemble or cascade serves this family.
 """
 from __future__ import annotations
 
@@ -81,8 +84,47 @@ def nextvlad_source(reader, student_only=False):
     return dict(ck=ck, sd=sd, tower=tower, every_n=every_n, teacher_every_n=inference.nextvlad_every_n(sd, "teacher"))
 
 
-def build_graph(reader, model, batch_size, device, student_only=False, label_loss=None, nextvlad=None):
-    """cs/validate.py:107-189 / cs/eval_finetune.py:108-175.  nextvlad: nextvlad_source() for --model NeXtVLADModel."""
+def netvlad_every_n(state_dict, override=0, where="the checkpoint"):
+    """The grid a served NetVLAD tower runs on: the every_n of a --netvlad_frames grid checkpoint, every real frame (1) for a sampled one,
+    unless ``override`` (--netvlad_serve_every_n) > 0 names another, which wins with a warning."""
+    recorded = int(state_dict["every_n"]) if state_dict.get("netvlad_frames") == "grid" and "every_n" in state_dict else 1
+    if override and int(override) != recorded:
+        logging.warning("--netvlad_serve_every_n %d, but the tower of %s runs on every_n = %d there (the flag is used)", override, where, recorded)
+        return int(override)
+    return recorded
+
+
+def netvlad_source(reader, student_only=False):
+    """--model NetVLADModel: what is decided on the host, before the device is touched, from --train_dir's latest
+    checkpoint - its variables against the size flags, and the grid it records.  Returns {"ck", "sd", "every_n"}."""
+    from .distill import check_netvlad_checkpoint
+    if student_only:
+        raise ValueError("eval_finetune with --model NetVLADModel: there is no convert / finetune step for this family, so no "
+                         "student-only checkpoint to evaluate")
+    if FLAGS.precision != "bf16":
+        raise ValueError("--precision %s with --model NetVLADModel: the NetVLAD tower has no such forward mode (bf16 only)" % FLAGS.precision)
+    if FLAGS.netvlad_serve_every_n < 0 or FLAGS.netvlad_serve_every_n > FLAGS.max_num_frames:
+        raise ValueError("--netvlad_serve_every_n %d must lie in 0 .. --max_num_frames %d (0 = as the checkpoint records)"
+                         % (FLAGS.netvlad_serve_every_n, FLAGS.max_num_frames))
+    ck = latest_checkpoint(FLAGS.train_dir)
+    if ck is None:
+        raise IOError("unable to find a checkpoint at location: %s" % FLAGS.train_dir)
+    sd = torch.load(ck, map_location="cpu")
+    check_netvlad_checkpoint(sd, "model", sum(reader.feature_sizes), reader.num_classes,
+                             (FLAGS.netvlad_cluster_size, FLAGS.netvlad_hidden_size, FLAGS.moe_num_mixtures), ck)
+    return dict(ck=ck, sd=sd, every_n=netvlad_every_n(sd, FLAGS.netvlad_serve_every_n, ck))
+
+
+def build_graph(reader, model, batch_size, device, student_only=False, label_loss=None, nextvlad=None, netvlad=None):
+    """cs/validate.py:107-189 / cs/eval_finetune.py:108-175.  nextvlad: nextvlad_source() for --model NeXtVLADModel (DESIGN.md 7.15);
+    netvlad: netvlad_source() for --model NetVLADModel."""
+    if isinstance(model, frame_level_models.NetVLADModel):
+        from .distill import NetVladEvalGraph
+        src = netvlad if netvlad is not None else netvlad_source(reader, student_only)
+        return NetVladEvalGraph(batch_size, every_n=src["every_n"], feature_size=sum(reader.feature_sizes), vocab_size=reader.num_classes,
+                                max_frames=FLAGS.max_num_frames, cluster_size=FLAGS.netvlad_cluster_size,
+                                hidden_size=FLAGS.netvlad_hidden_size, num_mixtures=FLAGS.moe_num_mixtures, device=device,
+                                precision=FLAGS.precision, label_loss=label_loss)
     if isinstance(model, frame_level_models.NeXtVLADModel):
         from . import inference
         src = nextvlad if nextvlad is not None else nextvlad_source(reader, student_only)
@@ -222,7 +264,8 @@ def evaluation_loop(graph, reader, label_loss_fn, summary_writer, evl_metrics, l
         logging.info("checkpoint %s disappeared before it could be loaded (%s); will look again.", ck, e)
         return last_global_step_val, None
     from .inference import check_model_family, warn_sampling
-    check_model_family(sd, ck)
+    if getattr(graph, "family", None) != "netvlad":                      # (a NetVLAD graph's restore checks every variable's name and shape)
+        check_model_family(sd, ck)
     graph.restore(sd)
     if graph.student is not None:
         warn_sampling(sd, FLAGS.student_sampling, ck)
@@ -319,9 +362,11 @@ def evaluate(student_only=False, max_evals=None):
         raise ValueError("--cascade_stage_file is written by inference.py only")
     reader = get_reader()
     model = find_class_by_name(FLAGS.model, [frame_level_models, video_level_models])()
-    nextvlad = loaded = None                     # the NeXtVLAD family's host checks, and every member's: before the device is touched
+    nextvlad = netvlad = loaded = None           # the NeXtVLAD / NetVLAD family's host checks, and every member's: before the device is touched
     if isinstance(model, frame_level_models.NeXtVLADModel) and spec is None and cascade is None:
         nextvlad = nextvlad_source(reader, student_only)
+    elif isinstance(model, frame_level_models.NetVLADModel) and spec is None and cascade is None:
+        netvlad = netvlad_source(reader, student_only)
     elif spec is not None or cascade is not None:
         if isinstance(model, (frame_level_models.HierarchicalLstmModel, frame_level_models.NeXtVLADModel)):
             from .inference import load_members
@@ -344,7 +389,7 @@ def evaluate(student_only=False, max_evals=None):
     if cascade is not None:
         graph = build_cascade(reader, model, cascade, FLAGS.batch_size, device, label_loss=label_loss_fn, loaded=loaded)
     elif spec is None:
-        graph = build_graph(reader, model, FLAGS.batch_size, device, student_only, label_loss=label_loss_fn, nextvlad=nextvlad)
+        graph = build_graph(reader, model, FLAGS.batch_size, device, student_only, label_loss=label_loss_fn, nextvlad=nextvlad, netvlad=netvlad)
     else:
         graph = build_ensemble(reader, model, spec, FLAGS.batch_size, device, label_loss=label_loss_fn, loaded=loaded)
     logging.info("built evaluation graph")

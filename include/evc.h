@@ -845,6 +845,23 @@ int evc_netvlad_normalize_fwd(const float* V, int B, int K, int F, float* n1, fl
                               void* stream);
 int evc_netvlad_normalize_bwd(const float* V, const float* n1, const float* n2, const float* dY, int B, int K, int F, float* dV,
                               void* stream);
+/* Ragged videos: video b owns the frame rows row_off[b] .. row_off[b+1] (device int32 [B+1], L_b of them in time
+ * order, L_b = 0 allowed: V[b] = 0, asum[b] = 0 exactly) of a [R][K], r [R][F], da and dx; R = row_off[B], max_k = max_b L_b (the host
+ * knows both: they size the launches).  No limit on the frames of a video other than T.  With xb = (r - mean) * (rsqrtf(var + 1e-3f) *
+ * gamma) + beta, never stored:  asum[b][k] = sum_l a[l][k];  V[b][k][f] = sum_l a[l][k] * xb[l][f] - asum[b][k] * c2[k][f] on the f32
+ * matrix cores (v_mfma_f32_32x32x2_f32), every element one chain over the video's rows in ascending order, epilogue fmaf(-asum, c2, acc).
+ * Backward:  dx[l][f] = sum_k a[l][k] * dV[b][k][f] (a chain over k; written, not accumulated),  da[l][k] = sum_f dV[b][k][f] * xb[l][f]
+ * - q[b][k] (a chain over f), q[b][k] = sum_f dV[b][k][f] * c2[k][f].  ws: B*F*Kp + B*K floats of 16-byte aligned scratch, Kp = K
+ * rounded up to 4.  Fixed summation order, no atomics; rows >= R of da / dx are never written, rows >= R of a / r never read.
+ * Needs 0 < B <= 65535, 0 < K <= 1024, F % 4 == 0, 0 <= max_k <= T, max_k <= R <= B * max_k (EVC_ERR_BAD_SHAPE), non-NULL operands
+ * (EVC_ERR_BAD_ARG; a short or misaligned ws too), a, r, c2, V / dV, da, dx 16-byte aligned (EVC_ERR_BAD_ALIGN): nothing is launched
+ * otherwise.  (dc2 = evc_netvlad_dcenters(asum, dV, B, K, F) as for the fixed-length entries.) */
+int evc_netvlad_aggregate_packed_fwd(const float* a, const float* r, const int32_t* row_off, int B, int T, int K, int F, int R, int max_k,
+                                     const float* mean, const float* var, const float* gamma, const float* beta, const float* c2,
+                                     float* V, float* asum, void* stream);
+int evc_netvlad_aggregate_packed_bwd(const float* a, const float* r, const int32_t* row_off, int B, int T, int K, int F, int R, int max_k,
+                                     const float* mean, const float* var, const float* gamma, const float* beta, const float* c2,
+                                     const float* dV, float* da, float* dx, float* ws, int64_t ws_floats, void* stream);
 
 /* ---- NeXtVLAD aggregation (EXTENSION: the reference's NeXtVLADModel is an empty stub, cs/frame_level_models.py:349-355; the
  * binding definition is DESIGN.md 7.12, restated in float64 in tests/_nextvlad_ref.py).  csrc/evc_nextvlad.hip.
