@@ -25,6 +25,10 @@ SIGNATURES = {
     "evc_gemm_tn2": [vp, i64, vp, i64, i32, vp, i64, i32, i32, vp, i64, i32, i32, i32, i32, vp],
     "evc_gemm_tn2_rows": [vp, i64, vp, i64, i32, vp, i64, i32, i32, vp, i64, i32, i32, i32, vp, i32, i32, vp],
     "evc_gemm_tn2_slabs": [vp, i64, vp, i64, i32, vp, i64, i32, i32, vp, i64, i64, i32, i32, i32, i32, vp],
+    "evc_gemm_tn2_rows_skip": [vp, i64, vp, i64, i32, vp, i64, i32, i32, vp, i64, i32, i32, i32, vp, i32, i32, i32, vp],
+    "evc_gemm_tn_plan": [i64, i64, i32, i64, i32, i32, i32, i32, vp, i32, vp, vp, vp],
+    "evc_gemm_tn2_slabs_skip": [vp, i64, vp, i64, i32, vp, i64, i32, i32, vp, i64, i64, i32, i32, i32, i32, i32, vp],
+    "evc_fill_f32_cols": [vp, i64, i32, i32, f32, vp],
     "evc_sum_slabs": [vp, i64, i32, i32, i32, i64, vp, i64, i32, vp],
     "evc_colsum_bf16": [vp, i64, i32, i32, i32, vp, vp],
     "evc_colsum_bf16_det": [vp, i64, i32, i32, i32, vp, vp, i32, vp],
@@ -44,6 +48,7 @@ SIGNATURES = {
     "evc_cast_f32_to_fp8_lo": [vp, i64, i32, i32, i32, i32, i32, vp, i64, vp],
     "evc_cast_f32_to_fp8_lohi": [vp, i64, i32, i32, i32, i32, i32, vp, i64, vp],
     "evc_lstm_layer_bwd": [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "evc_lstm_layer_bwd_live": [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp],
     "evc_transpose_to_bf16": [vp, i32, i64, i32, i32, vp, i64, i32, i32, vp],
     "evc_cast_f32_to_bf16": [vp, i64, i32, i32, vp, i64, vp],
     "evc_cast_f32_to_f16": [vp, i64, i32, i32, vp, i64, vp],
@@ -164,6 +169,9 @@ SIGNATURES = {
     "evc_cascade_pick_rows": [vp, vp, vp, i32, f32, i32, vp, vp, vp, vp],
 }
 EXPORTS = tuple(SIGNATURES) + ("evc_version", "evc_last_error")
+# Entries that a library named by EVC_LIB may lack (a build of an older tree, for same-box A/B runs: DESIGN.md 9).  The in-tree library must have
+# them; a caller that can do without asks has() and takes the older entries' path.
+NEWER = ("evc_gemm_tn2_rows_skip", "evc_gemm_tn_plan", "evc_gemm_tn2_slabs_skip", "evc_fill_f32_cols", "evc_lstm_layer_bwd_live")
 
 _lib = None
 
@@ -187,6 +195,8 @@ def load():
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, args in SIGNATURES.items():
+        if name in NEWER and "EVC_LIB" in os.environ and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = C.c_int
@@ -196,6 +206,11 @@ def load():
     lib.evc_last_error.restype = C.c_char_p
     _lib = lib
     return lib
+
+
+def has(name):
+    """Whether the loaded library exports `name` (always true of the in-tree build; see NEWER)."""
+    return hasattr(load(), name)
 
 
 def call(name, *args):

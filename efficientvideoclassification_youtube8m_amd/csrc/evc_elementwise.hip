@@ -1960,6 +1960,24 @@ extern "C" int evc_fill_f32(float* p, int64_t n, float value, void* stream) {
   return EVC_OK;
 }
 
+// p[r*ld + c] = v for r < rows, c < cols: a column range of a row-major matrix (the columns of a weight gradient that a split-K launch joins
+// with atomics, engine.LstmStack._wgrad_tn), 16-byte stores (cols4 = cols / 4)
+__global__ void fill_cols_kernel(float* p, long ld, int rows, int cols4, float v) {
+  const long n = (long)rows * cols4, stride = (long)gridDim.x * blockDim.x;
+  const float4 v4 = make_float4(v, v, v, v);
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const long r = i / cols4, c = i - r * cols4;
+    *(float4*)(p + r * ld + c * 4) = v4;
+  }
+}
+extern "C" int evc_fill_f32_cols(float* p, int64_t ld, int rows, int cols, float value, void* stream) {
+  EVC_REQUIRE(p && rows > 0 && cols > 0 && cols % 4 == 0 && ld % 4 == 0 && ld >= cols && ((uintptr_t)p % 16) == 0, EVC_ERR_BAD_SHAPE,
+              "evc_fill_f32_cols: rows=%d cols=%d (%%4) ld=%ld (%%4, >= cols), 16-byte aligned", rows, cols, (long)ld);
+  hipLaunchKernelGGL(fill_cols_kernel, dim3(grid_for((long)rows * (cols / 4))), dim3(256), 0, (hipStream_t)stream, p, (long)ld, rows, cols / 4, value);
+  EVC_LAUNCH_CHECK();
+  return EVC_OK;
+}
+
 // ---------------------------------------------------------------------------
 // Measurement aid (scripts/dp_occupancy_sim.sh): a stand-in for a collective's kernel on a one-GPU box.  `blocks`
 // workgroups of `threads` threads, each holding `lds_bytes` of LDS, stay resident for `microseconds` (constant 100 MHz clock) and

@@ -9,6 +9,7 @@ struct StoreParamsT {
   int row_il_H;                   // > 0: row m = u*4+g of the product is stored at row g*H+u (gate de-interleave)
   int accumulate, splits, ksteps_per_split;
   long slab_stride;               // > 0: split s stores its partial tile plainly at C + s*slab_stride (no atomics; the caller sums the slabs)
+  int ksteps_per_split2;          // steps per split of the second column segment's tiles, which start at GemmOperandsT::k_skip2
 };
 
 template <class Cfg, bool SEG = false>
@@ -25,18 +26,22 @@ __global__ __launch_bounds__(Cfg::NT) void gemm_tn_kernel(GemmOperandsT p, Store
   const int m0 = tm * Cfg::BM;
   int n0 = tn * Cfg::BU;
   int nb = n0;                                                 // first column within the B segment this workgroup reads
+  int skip = 0, kps = s.ksteps_per_split;                      // this tile's first K step and its steps per split
   if (p.B2) {                                                  // two column segments (workgroup-uniform choice)
     if (n0 >= p.N1) {
       p.B = p.B2; p.ldb = p.ldb2; nb = n0 - p.N1; p.N = s.N - p.N1;
       s.N = p.c_col2 + p.N;                                    // the segment's columns in C: [c_col2, c_col2 + N2)
       n0 = p.c_col2 + nb;
+      skip = p.k_skip2; kps = s.ksteps_per_split2;             // the segment's own (shorter) walk, split evenly over ITS steps: no split is empty
     } else {
       p.N = s.N = p.N1;
     }
+  } else {
+    skip = p.k_skip2;                                          // one segment (the slab entries; the other entries drop the steps on the host)
   }
   if (SEG) {                                                   // K steps are counted over the LIVE steps of the segments (evc_gemm_tn2_rows)
-    int off = split * s.ksteps_per_split, sg = 0;
-    p.nk = min(s.ksteps_per_split, p.nk - off);
+    int off = skip + split * kps, sg = 0;
+    p.nk = min(kps, p.nk - off);
 #pragma unroll
     for (int i = 0; i < 15; ++i) {                             // (constant indices: the table stays in scalar registers)
       const bool adv = sg == i && i + 1 < p.nseg && off >= (int)p.seg_len[i];
@@ -44,11 +49,16 @@ __global__ __launch_bounds__(Cfg::NT) void gemm_tn_kernel(GemmOperandsT p, Store
       sg += adv ? 1 : 0;
     }
     p.seg0 = sg; p.seg_off0 = off;
-  } else if (s.splits > 1) {
-    const int k0 = split * s.ksteps_per_split;
+  } else if (s.splits > 1 || skip) {
+    // atomic joins: the tile's own steps [skip, nk) split evenly (kps of this segment).  Slabs (EVC_DETERMINISTIC): the ranges of the unskipped
+    // walk, the skipped steps cut off their front - every slab then holds the bits it held without the skip (the cut products are exact zeros;
+    // a range that is cut away whole stores zeros), and the fixed-order sum is bit-identical.
+    const bool slabs = s.slab_stride > 0;
+    const int k0 = slabs ? max(skip, split * s.ksteps_per_split) : skip + split * kps;
+    const int k1 = slabs ? min((split + 1) * s.ksteps_per_split, p.nk) : min(k0 + kps, p.nk);
     p.A += (long)k0 * 32 * p.lda;
     p.B += (long)k0 * 32 * p.ldb;
-    p.nk = min(s.ksteps_per_split, p.nk - k0);
+    p.nk = k1 - k0;
   }
   f32x4 acc[Cfg::MI][1][Cfg::NI];
   gemm_mainloop_tn<Cfg, true, TN_LOOP_MODE, SEG>(p, m0, nb, lds_dyn, acc);      // transposed accumulators: lane = one row, 4 consecutive columns
@@ -137,21 +147,48 @@ static bool tn_live_segments(GemmOperandsT& p, int K, int slab_rows, const int32
 template <class Cfg>
 static int launch_tn(const GemmOperandsT& p, StoreParamsT s, bool seg, int tm, int tn, hipStream_t st) {
   s.ksteps_per_split = ceil_div(p.nk, s.splits);
+  s.ksteps_per_split2 = p.k_skip2 && !s.slab_stride ? ceil_div(p.nk - p.k_skip2, s.splits) : s.ksteps_per_split;
   if (seg) launch_cfg<Cfg>(gemm_tn_kernel<Cfg, true>, tm * tn * s.splits, st, p, s, tm, tn);
   else launch_cfg<Cfg>(gemm_tn_kernel<Cfg>, tm * tn * s.splits, st, p, s, tm, tn);
   EVC_LAUNCH_CHECK();
   return EVC_OK;
 }
 
-static int gemm_tn_impl(const char* entry, const evc_bf16* A, int64_t lda, const evc_bf16* B, int64_t ldb, int N1, const evc_bf16* B2, int64_t ldb2,
-                        int c_col2, float* C, int64_t ldc, int M, int N, int K, int row_interleave_H, int accumulate, void* stream,
-                        int slab_rows = 0, const int32_t* rows_per_slab = nullptr) {
-  EVC_TRY(tn_args_ok(entry, A, lda, B, ldb, M, N, K, row_interleave_H, N1, B2, ldb2, c_col2));
-  hipStream_t st = (hipStream_t)stream;
-  GemmOperandsT p = tn_operands(A, lda, B, ldb, M, N, K, N1, B2, ldb2, c_col2);
-  const bool seg = rows_per_slab && slab_rows > 0 && !evc_deterministic() && tn_live_segments(p, K, slab_rows, rows_per_slab);
+// tile ids of the TN products, as EVC_FORCE_TILE names them
+enum TnTileId { TN_TILE_256 = 1, TN_TILE_128 = 11 };
+struct TnPlan { int tile, tm, tn, splits; bool seg; };
+
+// The plan of one product: tile, tile grid, K splits, and whether the K walk follows live segments.  A pure function of the shapes, the row table,
+// the skip and the two process-wide switches - evc_gemm_tn_plan answers with it, gemm_tn_impl launches by it.  Finishes p: segment table and live
+// step count, and the skip - k_skip leading K steps (of 32 operand rows) that the LAST column segment does not walk: as k_skip2 for the second of
+// two segments, by dropping the steps from a single segment's walk here.
+static TnPlan tn_plan(GemmOperandsT& p, int M, int N, int K, int slab_rows, const int32_t* rows_per_slab, int k_skip) {
+  TnPlan pl;
+  pl.seg = rows_per_slab && slab_rows > 0 && !evc_deterministic() && tn_live_segments(p, K, slab_rows, rows_per_slab);
   K = p.nk * 32;                                 // (the live rows)
-  StoreParamsT s{C, ldc, M, N, row_interleave_H, accumulate, 1, 0, 0};
+  int skip = k_skip;                             // ... in steps of the walk: the live steps below operand step k_skip
+  if (pl.seg) {
+    skip = 0;
+    for (int i = 0; i < p.nseg; ++i) skip += max(0, min((int)p.seg_len[i], k_skip - (int)p.seg_start[i]));
+  }
+  int nk_short = p.nk - skip;                    // the shorter walk: it decides the splits (>= 32 steps each in every tile)
+  if (p.B2) {
+    p.k_skip2 = skip;
+  } else if (skip) {
+    if (pl.seg) {
+      int i = 0, n = 0;
+      while (i < p.nseg && skip >= (int)p.seg_len[i]) skip -= p.seg_len[i++];
+      for (; i < p.nseg; ++i, ++n, skip = 0) {
+        p.seg_start[n] = (unsigned short)(p.seg_start[i] + skip); p.seg_len[n] = (unsigned short)(p.seg_len[i] - skip);
+      }
+      for (i = n; i < 16; ++i) p.seg_start[i] = p.seg_len[i] = 0;
+      p.nseg = n;
+    } else {
+      p.A += (long)skip * 32 * p.lda;
+      p.B += (long)skip * 32 * p.ldb;
+    }
+    p.nk = nk_short;
+  }
   const int tm1 = ceil_div(M, 128), tn1 = ceil_div(N, 128);
   // short contractions (the student's L2: K = 5 x 256 rows) on 128x128 tiles without split-K: the atomic join of
   // 256x256 partial tiles costs more than the product itself there (81 -> 36 us at 4096 x 1024 x 1280); from
@@ -159,13 +196,32 @@ static int gemm_tn_impl(const char* entry, const evc_bf16* A, int64_t lda, const
   const bool short128 = forced_tile() == 11 || (forced_tile() == 0 && K <= 2048 && (long)tm1 * tn1 >= 192);
   // a narrow strip (N <= 128: the last 128 input columns of an L1 layer-0 kernel gradient, see engine._wgrad_tn): 128x128 tiles,
   // K split until ~256 workgroups exist - a 256-column tile would do half of its MFMAs on columns that do not exist
-  const bool strip128 = !short128 && forced_tile() == 0 && N <= 128 && !B2;
+  const bool strip128 = !short128 && forced_tile() == 0 && N <= 128 && !p.B2;
   const bool tile128 = short128 || strip128;
   const int tm = tile128 ? tm1 : ceil_div(M, CfgPlainV2::BM), tn = short128 ? tn1 : strip128 ? 1 : ceil_div(N, CfgPlainV2::BU);
-  // K splits joined by atomics until ~256 workgroups exist, >= 32 K steps each; none with EVC_DETERMINISTIC
-  if (!short128 && !evc_deterministic()) s.splits = split_k(256 / (tm * tn), p.nk, 32);
+  // K splits joined by atomics until ~256 workgroups exist, >= 32 K steps each - counted on the shorter walk - and none empty in either
+  // walk; none with EVC_DETERMINISTIC
+  pl.splits = 1;
+  if (!short128 && !evc_deterministic()) {
+    pl.splits = split_k(256 / (tm * tn), nk_short, 32);
+    while (pl.splits > 1 && (long)ceil_div(p.nk, pl.splits) * (pl.splits - 1) >= p.nk) --pl.splits;
+  }
+  pl.tile = tile128 ? TN_TILE_128 : TN_TILE_256;
+  pl.tm = tm; pl.tn = tn;
+  return pl;
+}
+
+static int gemm_tn_impl(const char* entry, const evc_bf16* A, int64_t lda, const evc_bf16* B, int64_t ldb, int N1, const evc_bf16* B2, int64_t ldb2,
+                        int c_col2, float* C, int64_t ldc, int M, int N, int K, int row_interleave_H, int accumulate, void* stream,
+                        int slab_rows = 0, const int32_t* rows_per_slab = nullptr, int k_skip = 0) {
+  EVC_TRY(tn_args_ok(entry, A, lda, B, ldb, M, N, K, row_interleave_H, N1, B2, ldb2, c_col2));
+  EVC_REQUIRE(k_skip >= 0 && k_skip <= K / 32, EVC_ERR_BAD_ARG, "%s: k_skip=%d outside [0, K/32=%d]", entry, k_skip, K / 32);
+  hipStream_t st = (hipStream_t)stream;
+  GemmOperandsT p = tn_operands(A, lda, B, ldb, M, N, K, N1, B2, ldb2, c_col2);
+  const TnPlan pl = tn_plan(p, M, N, K, slab_rows, rows_per_slab, k_skip);
+  StoreParamsT s{C, ldc, M, N, row_interleave_H, accumulate, pl.splits, 0, 0};
   if (s.splits > 1 && !accumulate) EVC_CHECK_HIP(hipMemset2DAsync(C, ldc * sizeof(float), 0, (size_t)N * sizeof(float), M, st));
-  return tile128 ? launch_tn<CfgTn128>(p, s, seg, tm, tn, st) : launch_tn<CfgPlainV2>(p, s, seg, tm, tn, st);
+  return pl.tile == TN_TILE_128 ? launch_tn<CfgTn128>(p, s, pl.seg, pl.tm, pl.tn, st) : launch_tn<CfgPlainV2>(p, s, pl.seg, pl.tm, pl.tn, st);
 }
 
 // evc_gemm_tn / evc_gemm_tn2 over TIME SLABS with a live prefix (round 5): the contraction index runs over K = nslabs * slab_rows rows, slab t
@@ -185,6 +241,44 @@ extern "C" int evc_gemm_tn2_rows(const evc_bf16* A, int64_t lda, const evc_bf16*
                       row_interleave_H, accumulate, stream, slab_rows, rows_per_slab);
 }
 
+// The products of evc_gemm_tn / evc_gemm_tn2 / evc_gemm_tn2_rows with a SKIP: the last column segment (B2, or B1 when B2 == NULL) does not walk the
+// first k_skip K steps of 32 operand rows, because the caller knows those rows of it to be zeros (h_prev's slab 0 = h_-1 of the weight-gradient
+// products): the same sums without the products that add nothing.  rows_per_slab == NULL: the plain walk over all slab_rows * nslabs rows.
+static int tn_skip_args_ok(const char* entry, const void* B1, int N1, const void* B2, int N2, int c_col2, int slab_rows, int nslabs, int accumulate) {
+  EVC_REQUIRE(B1 && N1 > 0 && slab_rows > 0 && nslabs > 0 && (long)slab_rows * nslabs < (1L << 31), EVC_ERR_BAD_ARG, "%s: B1, N1, slab_rows, nslabs are required", entry);
+  EVC_REQUIRE(!B2 || N2 > 0, EVC_ERR_BAD_ARG, "%s: N2=%d", entry, N2);
+  EVC_REQUIRE(!B2 || accumulate || c_col2 == N1, EVC_ERR_BAD_ARG, "%s: segments that are not adjacent in C (c_col2=%d, N1=%d) need accumulate", entry, c_col2, N1);
+  return EVC_OK;
+}
+extern "C" int evc_gemm_tn2_rows_skip(const evc_bf16* A, int64_t lda, const evc_bf16* B1, int64_t ldb1, int N1, const evc_bf16* B2, int64_t ldb2,
+                                      int N2, int c_col2, float* C, int64_t ldc, int M, int slab_rows, int nslabs, const int32_t* rows_per_slab,
+                                      int k_skip, int row_interleave_H, int accumulate, void* stream) {
+  EVC_TRY(tn_skip_args_ok("evc_gemm_tn2_rows_skip", B1, N1, B2, N2, c_col2, slab_rows, nslabs, accumulate));
+  return gemm_tn_impl("evc_gemm_tn2_rows_skip", A, lda, B1, ldb1, B2 ? N1 : 0, B2, ldb2, B2 ? c_col2 : 0, C, ldc, M, N1 + (B2 ? N2 : 0), slab_rows * nslabs,
+                      row_interleave_H, accumulate, stream, slab_rows, rows_per_slab, k_skip);
+}
+
+// What evc_gemm_tn2_rows_skip (and, with k_skip = 0, evc_gemm_tn / evc_gemm_tn2 / evc_gemm_tn2_rows) would launch for these arguments: *tile = 1 (256 x 256)
+// or 11 (128 x 128), *splits = the K ranges joined by atomics, *live_walk = 1 when the K walk follows the live segments of rows_per_slab and reads no row
+// of a slab from round_up(rows, 32) on (0: the plain walk over every row).  splits == 1: one workgroup per tile - with accumulate = 0 the launch stores plainly and
+// is the sole writer of its columns, which the caller then need not zero.  The launch's own choice (tn_plan), asked without enqueueing anything.
+extern "C" int evc_gemm_tn_plan(int64_t lda, int64_t ldb1, int N1, int64_t ldb2, int N2, int M, int slab_rows, int nslabs, const int32_t* rows_per_slab,
+                                int k_skip, int* tile, int* splits, int* live_walk) {
+  EVC_REQUIRE(tile && splits && live_walk, EVC_ERR_BAD_ARG, "evc_gemm_tn_plan: tile, splits and live_walk are required");
+  const bf16_t* const some = (const bf16_t*)(uintptr_t)16;      // operands are never read here: an aligned stand-in address
+  const bf16_t* const B2 = N2 > 0 ? some : nullptr;
+  EVC_TRY(tn_skip_args_ok("evc_gemm_tn_plan", some, N1, B2, N2, N1, slab_rows, nslabs, 1));
+  const int N = N1 + (B2 ? N2 : 0), K = slab_rows * nslabs;
+  EVC_TRY(tn_args_ok("evc_gemm_tn_plan", some, lda, some, ldb1, M, N, K, 0, B2 ? N1 : 0, B2, ldb2, B2 ? N1 : 0));
+  EVC_REQUIRE(k_skip >= 0 && k_skip <= K / 32, EVC_ERR_BAD_ARG, "evc_gemm_tn_plan: k_skip=%d outside [0, K/32=%d]", k_skip, K / 32);
+  GemmOperandsT p = tn_operands(some, lda, some, ldb1, M, N, K, B2 ? N1 : 0, B2, ldb2, B2 ? N1 : 0);
+  const TnPlan pl = tn_plan(p, M, N, K, slab_rows, rows_per_slab, k_skip);
+  *tile = pl.tile;
+  *splits = pl.splits;
+  *live_walk = pl.seg ? 1 : 0;
+  return EVC_OK;
+}
+
 extern "C" int evc_gemm_tn(const evc_bf16* A, int64_t lda, const evc_bf16* B, int64_t ldb, float* C, int64_t ldc,
                            int M, int N, int K, int row_interleave_H, int accumulate, void* stream) {
   return gemm_tn_impl("evc_gemm_tn", A, lda, B, ldb, 0, nullptr, 0, 0, C, ldc, M, N, K, row_interleave_H, accumulate, stream);
@@ -202,12 +296,23 @@ extern "C" int evc_gemm_tn2(const evc_bf16* A, int64_t lda, const evc_bf16* B1, 
 // images instead of joined with atomics - slab s at slabs + s*slab_stride, each an [M][ldc] image like C (rows de-interleaved, the second segment
 // at column c_col2) - that evc_sum_slabs adds in slab order.  B2 == NULL: one segment of N1 columns.
 static int gemm_tn_slabs_impl(const char* entry, const evc_bf16* A, int64_t lda, const evc_bf16* B1, int64_t ldb1, int N1, const evc_bf16* B2, int64_t ldb2,
-                              int N2, int c_col2, float* slabs, int64_t ldc, int64_t slab_stride, int M, int K, int row_interleave_H, int nslab, void* stream) {
+                              int N2, int c_col2, float* slabs, int64_t ldc, int64_t slab_stride, int M, int K, int row_interleave_H, int nslab, void* stream,
+                              int k_skip = 0) {
   const int N = N1 + (B2 ? N2 : 0);
   EVC_REQUIRE(N1 >= 8, EVC_ERR_BAD_SHAPE, "%s: N1=%d", entry, N1);
   EVC_TRY(tn_args_ok(entry, A, lda, B1, ldb1, M, N, K, row_interleave_H, N1, B2, ldb2, c_col2, nslab, slabs && slab_stride >= (int64_t)M * ldc));
-  return launch_tn<CfgPlainV2>(tn_operands(A, lda, B1, ldb1, M, N, K, N1, B2, ldb2, c_col2), StoreParamsT{slabs, ldc, M, N, row_interleave_H, 0, nslab, 0, slab_stride},
+  // the last segment's walk without its first k_skip steps (see evc_gemm_tn2_rows_skip), the slab ranges unchanged (gemm_tn_kernel): same bits
+  EVC_REQUIRE(k_skip >= 0 && k_skip <= K / 32, EVC_ERR_BAD_ARG, "%s: k_skip=%d outside [0, K/32=%d]", entry, k_skip, K / 32);
+  GemmOperandsT p = tn_operands(A, lda, B1, ldb1, M, N, K, N1, B2, ldb2, c_col2);
+  p.k_skip2 = k_skip;
+  return launch_tn<CfgPlainV2>(p, StoreParamsT{slabs, ldc, M, N, row_interleave_H, 0, nslab, 0, slab_stride},
                                false, ceil_div(M, CfgPlainV2::BM), ceil_div(N, CfgPlainV2::BU), (hipStream_t)stream);
+}
+extern "C" int evc_gemm_tn2_slabs_skip(const evc_bf16* A, int64_t lda, const evc_bf16* B1, int64_t ldb1, int N1, const evc_bf16* B2, int64_t ldb2,
+                                       int N2, int c_col2, float* slabs, int64_t ldc, int64_t slab_stride, int M, int K, int k_skip, int row_interleave_H,
+                                       int nslab, void* stream) {
+  return gemm_tn_slabs_impl("evc_gemm_tn2_slabs_skip", A, lda, B1, ldb1, N1, B2, ldb2, N2, c_col2, slabs, ldc, slab_stride, M, K, row_interleave_H, nslab, stream,
+                            k_skip);
 }
 extern "C" int evc_gemm_tn2_slabs(const evc_bf16* A, int64_t lda, const evc_bf16* B1, int64_t ldb1, int N1, const evc_bf16* B2, int64_t ldb2,
                                   int N2, int c_col2, float* slabs, int64_t ldc, int64_t slab_stride, int M, int K, int row_interleave_H,

@@ -20,6 +20,8 @@ struct LstmBwdParams {
   int M, H;
   int fused_above;          // 1: the accumulator also holds the gradient from the layer above (second K segment, wavefront):
                             // at a row's last step the final-state gradient is ADDED to it instead of replacing it
+  int dead_unread = 0;      // 1: nothing reads the dz rows from round_up(m_active, 32) on (the weight-gradient products walk the live segments,
+                            // evc_gemm_tn2_rows; the rows of the hoisted dX product there are never loaded): tiles beyond them return at once
 };
 
 static inline int bwd_dc_bf16() {
@@ -118,6 +120,12 @@ __device__ __forceinline__ void lstm_bwd_finish(const LstmBwdParams& e, const in
   else *(float4*)(e.dc_ws + hu) = make_float4(dcn[0], dcn[1], dcn[2], dcn[3]);
   dzp[0] = make_uint4(dzr[0].x, dzr[0].y, dzr[1].x, dzr[1].y);
   dzp[1] = make_uint4(dzr[2].x, dzr[2].y, dzr[3].x, dzr[3].y);
+}
+
+// whether anything reads the dz rows of a tile that starts at row m0 >= m_active: always, unless the caller said otherwise (dead_unread) - then
+// only the rows up to the next multiple of 32, which the live-segment walk of the weight-gradient products still contracts
+__device__ __forceinline__ bool lstm_bwd_dead_tile_read(const LstmBwdParams& e, int m0) {
+  return !e.dead_unread || m0 < ((e.m_active + 31) & ~31);
 }
 
 // tiles entirely beyond the active prefix (row plan): dz = 0, no GEMM
@@ -317,7 +325,7 @@ __device__ __forceinline__ void lstm_bwd_step_body(const GemmOperands& p, const 
   tile_of(id, tiles_m, tiles_n, tm, tn);
   const int m0 = tm * Cfg::BM, u0 = tn * Cfg::BU;
   if (m0 >= e.m_active) {
-    lstm_bwd_zero_tile<Cfg::BM, Cfg::BU, Cfg::NT>(e, m0, u0);
+    if (lstm_bwd_dead_tile_read(e, m0)) lstm_bwd_zero_tile<Cfg::BM, Cfg::BU, Cfg::NT>(e, m0, u0);
     return;
   }
   f32x4 acc[Cfg::MI][1][Cfg::NI];
@@ -419,7 +427,7 @@ __device__ __forceinline__ void lstm_bwd_skinny_lds_body(const GemmOperands& p, 
   const int tm = id % tiles_m, tn = id / tiles_m;
   const int m0 = tm * 32, u0 = tn * 32;
   if (m0 >= e.m_active) {
-    lstm_bwd_zero_tile<32, 32, NT>(e, m0, u0);
+    if (lstm_bwd_dead_tile_read(e, m0)) lstm_bwd_zero_tile<32, 32, NT>(e, m0, u0);
     return;
   }
   const int lane = threadIdx.x & 63;
@@ -577,11 +585,11 @@ typedef TileCfg2<192, 1, 128, 2, 4, 5, true> CfgBwdV2_192;
 // (128x64 and 64x128 tiles at two workgroups per CU were measured: 84-86 us vs 69 us for 128x128 at ~3800 rows -
 // the extra L2->LDS traffic of the smaller tiles costs more than overlapping the epilogues gains)
 
-extern "C" int evc_lstm_layer_bwd(const evc_bf16* w_il, const int32_t* len, int T, int M, int Kin, int H,
-                                  const void* gates, const evc_bf16* c_all, const float* dS_c, const float* dS_h, int64_t ld_dS,
-                                  const evc_bf16* dh_above, float* dc_ws, evc_bf16* dz4, float* db,
-                                  const int32_t* row_map, const int32_t* rows_per_step, const evc_bf16* dz_above,
-                                  const evc_bf16* w_above, void* stream) {
+static int lstm_layer_bwd_impl(const evc_bf16* w_il, const int32_t* len, int T, int M, int Kin, int H,
+                               const void* gates, const evc_bf16* c_all, const float* dS_c, const float* dS_h, int64_t ld_dS,
+                               const evc_bf16* dh_above, float* dc_ws, evc_bf16* dz4, float* db,
+                               const int32_t* row_map, const int32_t* rows_per_step, const evc_bf16* dz_above,
+                               const evc_bf16* w_above, int dz_dead_unread, void* stream) {
   EVC_REQUIRE(T > 0 && M > 0 && H > 0 && Kin > 0 && H % 64 == 0, EVC_ERR_BAD_SHAPE, "evc_lstm_layer_bwd: bad shape");
   EVC_REQUIRE(ring_operand_ok(M, 4L * H) && ring_operand_ok(H, 4L * H), EVC_ERR_BAD_SHAPE,
               "evc_lstm_layer_bwd: a dz time slab spans 4 GiB or more (M=%d H=%d)", M, H);
@@ -639,6 +647,7 @@ extern "C" int evc_lstm_layer_bwd(const evc_bf16* w_il, const int32_t* len, int 
     e.dc_bf16 = bwd_dc_bf16();
     e.row_map = row_map; e.db = db; e.m_active = Mt;
     e.M = M; e.H = H; e.fused_above = dz_above ? 1 : 0;
+    e.dead_unread = dz_dead_unread;
     switch (pick) {
       case 0: launch_lstm_bwd<CfgBwdV2_192>(p, e, k1, st); break;
       case 1: launch_lstm_bwd<CfgBwdV2_160>(p, e, k1, st); break;
@@ -666,6 +675,27 @@ extern "C" int evc_lstm_layer_bwd(const evc_bf16* w_il, const int32_t* len, int 
   }
   EVC_LAUNCH_CHECK();
   return EVC_OK;
+}
+
+extern "C" int evc_lstm_layer_bwd(const evc_bf16* w_il, const int32_t* len, int T, int M, int Kin, int H,
+                                  const void* gates, const evc_bf16* c_all, const float* dS_c, const float* dS_h, int64_t ld_dS,
+                                  const evc_bf16* dh_above, float* dc_ws, evc_bf16* dz4, float* db,
+                                  const int32_t* row_map, const int32_t* rows_per_step, const evc_bf16* dz_above,
+                                  const evc_bf16* w_above, void* stream) {
+  return lstm_layer_bwd_impl(w_il, len, T, M, Kin, H, gates, c_all, dS_c, dS_h, ld_dS, dh_above, dc_ws, dz4, db, row_map, rows_per_step, dz_above, w_above, 0, stream);
+}
+// ... with the caller's word (dz_dead_unread = 1) that nothing reads slab t of dz from row round_up(rows_per_step[t], 32) on: step tiles that start
+// there return without zeroing them.  True of a row-planned level whose weight-gradient products walk the live segments (evc_gemm_tn_plan tells)
+// and whose dX is hoisted; not with dz_above (the fused walk adds the final-state gradient to an accumulator that contracted those rows).
+extern "C" int evc_lstm_layer_bwd_live(const evc_bf16* w_il, const int32_t* len, int T, int M, int Kin, int H,
+                                       const void* gates, const evc_bf16* c_all, const float* dS_c, const float* dS_h, int64_t ld_dS,
+                                       const evc_bf16* dh_above, float* dc_ws, evc_bf16* dz4, float* db,
+                                       const int32_t* row_map, const int32_t* rows_per_step, const evc_bf16* dz_above,
+                                       const evc_bf16* w_above, int dz_dead_unread, void* stream) {
+  EVC_REQUIRE(dz_dead_unread == 0 || (dz_dead_unread == 1 && rows_per_step && !dz_above), EVC_ERR_BAD_ARG,
+              "evc_lstm_layer_bwd_live: dz_dead_unread goes with rows_per_step and without dz_above");
+  return lstm_layer_bwd_impl(w_il, len, T, M, Kin, H, gates, c_all, dS_c, dS_h, ld_dS, dh_above, dc_ws, dz4, db, row_map, rows_per_step, dz_above, w_above,
+                             dz_dead_unread, stream);
 }
 
 // ===========================================================================

@@ -33,6 +33,9 @@ struct GemmOperandsT {
   // N1 is a multiple of the tile width, so a workgroup's columns lie in one segment (gemm_tn_kernel picks it)
   const bf16_t* B2 = nullptr; long ldb2 = 0; int N1 = 0;
   int c_col2 = 0;              // C column where the second segment's columns start (>= N1: the segments need not be adjacent in C)
+  // leading K steps that the SECOND segment's workgroups (every workgroup when there is one segment) do not walk (gemm_tn_kernel; counted in LIVE
+  // steps under the SEG walk): the rows of that operand there are zeros by construction (h_prev's slab 0 = h_-1), so their products add nothing
+  int k_skip2 = 0;
   // K as up to 16 SEGMENTS of live K steps (evc_gemm_tn2_rows, SEG loops only): the contraction index runs over time slabs of slab_rows rows of
   // which only a prefix is live (row plans: rows sorted by length) - segment i covers K steps [seg_start[i], seg_start[i] + seg_len[i]) of
   // the operands; nk then counts LIVE steps, and a workgroup's first step is step seg_off0 of segment seg0.
@@ -61,7 +64,7 @@ __device__ __forceinline__ void gemm_mainloop_tn(const GemmOperandsT& p, const i
 #pragma unroll
     for (int ni = 0; ni < Cfg::NI; ++ni) acc[mi][0][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int nk = p.nk;
-  if (nk == 0) return;
+  if (nk <= 0) return;                // (a second-segment tile whose whole walk is skipped: zeros)
 
   // ---- staging: chunk c = piece*64 + lane -> k row c / CPR, physical chunk c % CPR; piece q belongs to wave q % NPW ----
   constexpr bool PRODUCERS = (MODE & LOOP_PRODUCER) != 0 && Cfg::NT == 512;   // waves 0..3 (one per SIMD) issue all the LDS-DMA

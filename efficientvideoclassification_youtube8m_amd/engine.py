@@ -140,6 +140,12 @@ class LstmStack:
     # of 10.07-10.13 ms - a pair launch wants two 64 KB workgroups on every CU at once and waits longer for them beside the other streams' tiles
     # than two 256-workgroup launches do, and layer 1's weight gradients / update no longer run under layer 0's chain.  Off; the tests switch it on.
     small_pair = False
+    # weight gradients without the work their result does not need: the h-part's products skip slab 0 of h_prev (zeros), launches that do not
+    # split K store plainly into a gradient nobody zeroed, fills cover only what a split launch joins (profiles/wgrad_zero_work_ab.txt).  Off: one
+    # fill of the whole gradient and accumulate everywhere - the tests compare the two.
+    wgrad_zero_work = True
+    # row plans: BPTT step tiles beyond a slab's live rows stay unwritten where nothing reads them (backward_layers).  Off in the tests' reference runs.
+    bwd_skip_dead = True
     timing = None      # set to a list to collect (start event, end event, launches, algorithmic flops) per layer forward
     timing_bwd = None  # set to {"bwd_step": [], "dx_nt": [], "wgrad_tn": []} to collect the same per backward launch sequence
 
@@ -170,7 +176,15 @@ class LstmStack:
             n *= d
         return buf.view(-1)[:n].view(*shape)
 
+    _h0_zero = False   # slab 0 (h_-1) of every layer's h image holds zeros: set by forward(), read by the weight-gradient products' slab-0 skip
+
     def forward(self, x, lens, plan=None):
+        """_forward, and the note that every forward entry has zeroed slab 0 of the h images it was given (fwd_clear_h in evc_lstm_fwd.hip)."""
+        S = self._forward(x, lens, plan)
+        self._h0_zero = True
+        return S
+
+    def _forward(self, x, lens, plan=None):
         """x [T][M][Kin] bf16 time-major (or a (hi, lo) pair in "high" precision); lens [M] int32.
         plan: ops.RowPlan of this batch - x is then [T][plan.P][Kin] in slot order and every buffer of the
         stack is used with plan.P rows per time slab; the returned state is in the original row order.
@@ -421,35 +435,73 @@ class LstmStack:
             inp = self._hb[l][1:]
         return res
 
-    def _wgrad_tn(self, dz2, layer_in, h_prev, kin, rows, gW, live=None):
-        """gW [4H][kin+H] += dz^T . [layer_in | h_prev] (gate rows de-interleaved).  One launch over both column segments when
+    def _wgrad_tn(self, dz2, layer_in, h_prev, kin, rows, gW, live=None, k_skip=0, assign=False):
+        """gW [4H][kin+H] += dz^T . [layer_in | h_prev] (gate rows de-interleaved; assign: gW = ..., whatever it held).  One launch over both column segments when
         the input width allows it (kin == H, a multiple of 256: the upper layers): dz is read once and the launch has twice the
         tiles; two launches otherwise (layer 0 of the L1 stacks: 1152 + 1024 columns = 8.5 column tiles would leave half of
-        the chip idle in the second round)."""
+        the chip idle in the second round).
+        k_skip: leading K steps (32 rows) of h_prev that hold zeros (slab 0 = h_-1) - the h-part's column tiles do not walk them.
+        assign: gW needs no zeroing by the caller - every launch is asked for its plan first (ops.gemm_tn_plan); one that splits K joins its partial
+        tiles with atomics onto zeros filled here - the whole of gW in one contiguous fill when every launch splits, its own columns
+        otherwise - and one that does not split is the sole writer of its columns and stores them plainly (accumulate=False: no fill, no
+        read-modify-write)."""
         H = self.H
         n1 = kin // 256 * 256
         if ops.DETERMINISTIC and rows % 32 == 0 and kin % 8 == 0:
             # no atomics, K split kept (round 5): partial products into slabs, added in slab order (ops.gemm_tn_det) - round 4 ran these products
-            # as one workgroup per tile with the whole K (3.4 instead of 2.0 ms per step)
+            # as one workgroup per tile with the whole K (3.4 instead of 2.0 ms per step).  (assign: evc_sum_slabs stores every element, no fill.)
+            acc = not assign
             if n1 >= 256 and (kin == n1 or kin - n1 >= 8):
-                ops.gemm_tn_det(dz2, layer_in, 4 * H, n1, rows, gW, row_interleave_H=H, accumulate=True, ldc=kin + H, B2=h_prev, N2=H, c_col2=kin)
+                ops.gemm_tn_det(dz2, layer_in, 4 * H, n1, rows, gW, row_interleave_H=H, accumulate=acc, ldc=kin + H, B2=h_prev, N2=H, c_col2=kin, k_skip=k_skip)
                 if kin > n1:
-                    ops.gemm_tn_det(dz2, layer_in[:, n1:], 4 * H, kin - n1, rows, gW[:, n1:kin], row_interleave_H=H, accumulate=True, ldc=kin + H)
+                    ops.gemm_tn_det(dz2, layer_in[:, n1:], 4 * H, kin - n1, rows, gW[:, n1:kin], row_interleave_H=H, accumulate=acc, ldc=kin + H)
             else:
-                ops.gemm_tn_det(dz2, layer_in, 4 * H, kin, rows, gW, row_interleave_H=H, accumulate=True, ldc=kin + H)
-                ops.gemm_tn_det(dz2, h_prev, 4 * H, H, rows, gW[:, kin:], row_interleave_H=H, accumulate=True, ldc=kin + H)
+                ops.gemm_tn_det(dz2, layer_in, 4 * H, kin, rows, gW, row_interleave_H=H, accumulate=acc, ldc=kin + H)
+                ops.gemm_tn_det(dz2, h_prev, 4 * H, H, rows, gW[:, kin:], row_interleave_H=H, accumulate=acc, ldc=kin + H, k_skip=k_skip)
             return
+        lda, ldx, ldh, ldc = dz2.stride(0), layer_in.stride(0), h_prev.stride(0), kin + H
+        # the launches: (columns of gW as (first, end) ranges, plan arguments, launch)
         if kin == H and kin % 256 == 0:
-            ops.gemm_tn2(dz2, layer_in, kin, h_prev, H, 4 * H, rows, gW, row_interleave_H=H, accumulate=True, live_rows=live)
+            launches = [([(0, kin + H)], dict(N1=kin, ldb1=ldx, N2=H, ldb2=ldh, k_skip=k_skip),
+                         lambda acc: ops.gemm_tn2(dz2, layer_in, kin, h_prev, H, 4 * H, rows, gW, row_interleave_H=H, accumulate=acc, live_rows=live, k_skip=k_skip))]
         elif kin - n1 in (64, 128) and n1 >= H and rows >= 16384 and (n1 + H) % 2048 == 0:
             # layer 0 of the L1 stacks (1152 = 1024 + 128 input columns): the first 1024 input columns next to the h-part as one
             # 2048-column launch, the last 128 as a narrow strip of their own (1.0 + 0.13 ms against 0.75 + 0.6 ms)
-            ops.gemm_tn2(dz2, layer_in, n1, h_prev, H, 4 * H, rows, gW, row_interleave_H=H, accumulate=True, c_col2=kin, live_rows=live)
-            ops.gemm_tn(dz2, layer_in[:, n1:], 4 * H, kin - n1, rows, gW[:, n1:kin], row_interleave_H=H, lda=dz2.stride(0),
-                        ldb=layer_in.stride(0), ldc=kin + H, accumulate=True, live_rows=live)
+            launches = [([(0, n1), (kin, kin + H)], dict(N1=n1, ldb1=ldx, N2=H, ldb2=ldh, k_skip=k_skip),
+                         lambda acc: ops.gemm_tn2(dz2, layer_in, n1, h_prev, H, 4 * H, rows, gW, row_interleave_H=H, accumulate=acc, c_col2=kin, live_rows=live,
+                                                  k_skip=k_skip)),
+                        ([(n1, kin)], dict(N1=kin - n1, ldb1=ldx),
+                         lambda acc: ops.gemm_tn(dz2, layer_in[:, n1:], 4 * H, kin - n1, rows, gW[:, n1:kin], row_interleave_H=H, lda=lda, ldb=ldx, ldc=ldc,
+                                                 accumulate=acc, live_rows=live))]
         else:
-            ops.gemm_tn(dz2, layer_in, 4 * H, kin, rows, gW, row_interleave_H=H, ldc=kin + H, accumulate=True, live_rows=live)
-            ops.gemm_tn(dz2, h_prev, 4 * H, H, rows, gW[:, kin:], row_interleave_H=H, ldc=kin + H, accumulate=True, live_rows=live)
+            launches = [([(0, kin)], dict(N1=kin, ldb1=ldx),
+                         lambda acc: ops.gemm_tn(dz2, layer_in, 4 * H, kin, rows, gW, row_interleave_H=H, ldc=ldc, accumulate=acc, live_rows=live)),
+                        ([(kin, kin + H)], dict(N1=H, ldb1=ldh, k_skip=k_skip),
+                         lambda acc: ops.gemm_tn(dz2, h_prev, 4 * H, H, rows, gW[:, kin:], row_interleave_H=H, ldc=ldc, accumulate=acc, live_rows=live, k_skip=k_skip))]
+        if not assign or not ops.TN_PLAN:      # (no plan query: a library of an older tree, A/B runs through EVC_LIB) every launch accumulates
+            if assign:
+                ops.fill_f32(gW, 0.0)
+            for _, _, launch in launches:
+                launch(True)
+            return
+        # accumulate: a launch that splits K, or whose two segments lie apart in gW (the entries refuse those without accumulate, whatever the plan)
+        acc = [ops.gemm_tn_plan(4 * H, K=rows, lda=lda, live_rows=live, **plan)[1] > 1 or len(cols) > 1 for cols, plan, _ in launches]
+        if all(acc):
+            ops.fill_f32(gW, 0.0)
+        else:
+            for (cols, _, _), a in zip(launches, acc):
+                for c0, c1 in (cols if a else ()):
+                    ops.fill_f32_cols(gW[:, c0:c1], 0.0)
+        for (_, _, launch), a in zip(launches, acc):
+            launch(a)
+
+    def _h0_skip(self, l, h_prev, M):
+        """K steps (32 rows) at the start of h_prev = h image[:T] of layer l that are known zeros: slab 0 (M rows, h_-1), when the forward entry
+        cleared it - forward() of this object has run on this very buffer - and the slab is a whole number of steps."""
+        if not (self.wgrad_zero_work and self._h0_zero and ops.TN_PLAN and M % 32 == 0):
+            return 0
+        assert h_prev.data_ptr() == self.hbuf[l].data_ptr() and h_prev.stride(0) == self.H, "the skip is for the h image forward() cleared"
+        return M // 32
 
     def backward(self, dS, need_dx, aux=None, on_layer_grads=None):
         """backward_layers run to its end; returns dX (or None)."""
@@ -504,8 +556,9 @@ class LstmStack:
                     dz2 = dz[l].view(T * M, 4 * H)
                     layer_in = (self.x_in if l == 0 else self._hb[0][1:]).reshape(T * M, kin)
                     h_prev = self._hb[l][:T].reshape(T * M, H)
-                    ops.fill_f32(gW, 0.0)
-                    self._wgrad_tn(dz2, layer_in, h_prev, kin, T * M, gW)
+                    if not self.wgrad_zero_work:
+                        ops.fill_f32(gW, 0.0)
+                    self._wgrad_tn(dz2, layer_in, h_prev, kin, T * M, gW, k_skip=self._h0_skip(l, h_prev, M), assign=self.wgrad_zero_work)
                     if on_layer_grads is not None:
                         on_layer_grads(l)
             if need_dx:       # gradient wrt the stack's input (the L2 levels: it flows on into the L1 level's final states), from layer 0's dz alone
@@ -534,13 +587,18 @@ class LstmStack:
                 ops.fill_f32(gb, 0.0)
             fused = fuse_ok and self.bwd_fuse == "fused" and l + 1 < L
             rows = plan.rows if plan is not None else [M] * T
+            # row plans: step tiles beyond a slab's live rows (rounded up to 32) are left unwritten where nothing reads them - the weight-gradient
+            # products below take the live-segment walk (asked of the library with the level's widest operand rows; never under EVC_DETERMINISTIC)
+            # and dX is the hoisted product, whose rows there no step loads (the fused walk of layer l-1 would contract them)
+            dead_unread = bool(self.bwd_skip_dead and plan is not None and M % 32 == 0 and use_tn and not det and not (fuse_ok and self.bwd_fuse != "off") and ops.TN_PLAN
+                               and ops.gemm_tn_plan(4 * H, H, T * M, lda=4 * H, ldb1=max(kin, H), live_rows=(rows, M))[2])
             # BPTT step t contracts dh_t = dz_{t+1} . Wh^T over the rows live at t+1 (the last step has no recurrent product)
             with self._timed("bwd_step", sum(1 for r in rows if r > 0), sum(2.0 * r * H * 4 * H for r in rows[1:])):
                 ops.lstm_layer_bwd(w, self.lens, T, M, kin, H, self._v(self.gates[l], T, M, H, 2), self._v(self.c_all[l], T + 1, M, H),
                                    dS[:, (2 * l) * H:], dS[:, (2 * l + 1) * H:], 2 * L * H,
                                    dh_above, self._v(self.dc_ws, M, H), dz, plan=plan, db=None if det else gb,
                                    dz_above=self._v(self.dz[l + 1], T, M, 4 * H) if fused else None,
-                                   w_above=tw.shadow_bwd[self.names(l + 1)[0]] if fused else None)
+                                   w_above=tw.shadow_bwd[self.names(l + 1)[0]] if fused else None, dz_dead_unread=dead_unread)
             ops.mark("%s:%s_bptt%d_done" % (tw.scope, self.scope, l))
             dz2 = dz.view(T * M, 4 * H)
             # gradient wrt the layer input, all T at once (hoisted): dX = dz . Wx^T
@@ -572,12 +630,13 @@ class LstmStack:
                 if use_tn:
                     # "TN" products straight from the row-major activations (transpose reads in the kernel);
                     # the gate-interleaved rows of the product are stored in TF gate order.  The split-K partial
-                    # tiles are added with atomics: one contiguous fill of the whole gradient, then accumulate
-                    # (instead of a pitched 2-D memset inside each call).
-                    ops.fill_f32(gW, 0.0)
+                    # tiles are added with atomics onto zeros that _wgrad_tn fills (where a launch splits at all).
+                    if not self.wgrad_zero_work:
+                        ops.fill_f32(gW, 0.0)
                     # (flops of the LIVE rows: with a row plan the products skip each slab's dead rows, ops.gemm_tn(live_rows=...))
                     with self._timed("wgrad_tn", 1, 2.0 * (sum(rows) if plan is not None else T * M) * 4 * H * (kin + H), stream=side):
-                        self._wgrad_tn(dz2, layer_in, h_prev, kin, T * M, gW, live=(rows, M) if plan is not None and M % 32 == 0 else None)      # (plan.P = M when the stack has fewer rows than a multiple of 32)
+                        self._wgrad_tn(dz2, layer_in, h_prev, kin, T * M, gW, live=(rows, M) if plan is not None and M % 32 == 0 else None,      # (plan.P = M when the stack has fewer rows than a multiple of 32)
+                                       k_skip=self._h0_skip(l, h_prev, M), assign=self.wgrad_zero_work)
                 else:   # T*M not a multiple of 32: transposed copies + NT products
                     ops.transpose_to_bf16(dz2, T * M, 4 * H, self.dzT, KP, interleave_H=-H)
                     inT = self.xT[:kin]

@@ -95,23 +95,46 @@ def gemm_nt_sqnorm_ok(M, N, K):
     return M > 512 and N % 256 == 0 and K % 64 == 0 and K < 8192 and os.environ.get("EVC_FUSED_GRAD_NORM", "0") == "1"
 
 
-def gemm_tn(A, B, M, N, K, out, row_interleave_H=0, accumulate=False, lda=None, ldb=None, ldc=None, live_rows=None):
+def _tn_rows_args(live_rows, K, k_skip):
+    """(slab_rows, nslabs, rows table or None) of evc_gemm_tn2_rows_skip / evc_gemm_tn_plan: the live-row table, or K rows as one plain walk."""
+    if live_rows is not None:
+        return _slab_rows_arg(live_rows, K)
+    return K, 1, None
+
+
+def gemm_tn_plan(M, N1, K, lda, ldb1, N2=0, ldb2=0, live_rows=None, k_skip=0):
+    """(tile, splits, live_walk) that gemm_tn / gemm_tn2 would launch with for these shapes (evc_gemm_tn_plan: the launch's own choice, nothing
+    enqueued).  splits == 1: the launch stores each element of its columns once - accumulate=False needs no zeroed `out`.  live_walk: the K walk
+    follows live_rows and reads no dead row from the next multiple of 32 on."""
+    slab, ns, arr = _tn_rows_args(live_rows, K, k_skip)
+    tile, splits, walk = C.c_int(0), C.c_int(0), C.c_int(0)
+    _lib.call("evc_gemm_tn_plan", lda, ldb1, N1, ldb2, N2, M, slab, ns, arr, k_skip, C.byref(tile), C.byref(splits), C.byref(walk))
+    return tile.value, splits.value, bool(walk.value)
+
+
+def gemm_tn(A, B, M, N, K, out, row_interleave_H=0, accumulate=False, lda=None, ldb=None, ldc=None, live_rows=None, k_skip=0):
     """out[M,N] (+)= A[K,M]^T @ B[K,N] (both row-major over K), f32 out.  live_rows = (rows [T], slab_rows): K = T slabs of slab_rows rows
-    of which the first rows[t] are live (a row-planned level) - the dead rows are skipped (evc_gemm_tn2_rows)."""
+    of which the first rows[t] are live (a row-planned level) - the dead rows are skipped (evc_gemm_tn2_rows).  k_skip: the first k_skip * 32
+    rows of B are zeros and are not walked (evc_gemm_tn2_rows_skip)."""
     assert A.dtype == BF16 and B.dtype == BF16 and out.dtype == F32
+    lda, ldb, ldc = A.stride(0) if lda is None else lda, B.stride(0) if ldb is None else ldb, out.stride(0) if ldc is None else ldc
+    if k_skip:
+        slab, ns, arr = _tn_rows_args(live_rows, K, k_skip)
+        _lib.call("evc_gemm_tn2_rows_skip", _p(A), lda, _p(B), ldb, N, None, 0, 0, 0, _p(out), ldc, M, slab, ns, arr, k_skip, row_interleave_H,
+                  1 if accumulate else 0, _stream())
+        return out
     if live_rows is not None:
         slab, ns, arr = _slab_rows_arg(live_rows, K)
-        _lib.call("evc_gemm_tn2_rows", _p(A), A.stride(0) if lda is None else lda, _p(B), B.stride(0) if ldb is None else ldb, N, None, 0, 0, 0,
-                  _p(out), out.stride(0) if ldc is None else ldc, M, slab, ns, arr, row_interleave_H, 1 if accumulate else 0, _stream())
+        _lib.call("evc_gemm_tn2_rows", _p(A), lda, _p(B), ldb, N, None, 0, 0, 0, _p(out), ldc, M, slab, ns, arr, row_interleave_H, 1 if accumulate else 0, _stream())
         return out
-    _lib.call("evc_gemm_tn", _p(A), A.stride(0) if lda is None else lda, _p(B), B.stride(0) if ldb is None else ldb,
-              _p(out), out.stride(0) if ldc is None else ldc, M, N, K, row_interleave_H, 1 if accumulate else 0, _stream())
+    _lib.call("evc_gemm_tn", _p(A), lda, _p(B), ldb, _p(out), ldc, M, N, K, row_interleave_H, 1 if accumulate else 0, _stream())
     return out
 
 
-def gemm_tn_det(A, B, M, N, K, out, row_interleave_H=0, accumulate=False, ldc=None, B2=None, N2=0, c_col2=None):
+def gemm_tn_det(A, B, M, N, K, out, row_interleave_H=0, accumulate=False, ldc=None, B2=None, N2=0, c_col2=None, k_skip=0):
     """out[:, :N] (and out[:, c_col2:c_col2+N2] from B2) (+)= A^T @ B without atomics and with the K split kept (EVC_DETERMINISTIC=1): partial
-    products into slabs (evc_gemm_tn2_slabs), added in slab order (evc_sum_slabs).  Scratch from the stream-aware caching allocator."""
+    products into slabs (evc_gemm_tn2_slabs), added in slab order (evc_sum_slabs).  Scratch from the stream-aware caching allocator.
+    k_skip: the first k_skip * 32 rows of the last segment (B2, or B) are zeros and are not walked (evc_gemm_tn2_slabs_skip: same slabs, same bits)."""
     assert A.dtype == BF16 and B.dtype == BF16 and out.dtype == F32
     ldc = out.stride(0) if ldc is None else ldc
     ntot = (c_col2 + N2) if B2 is not None else N
@@ -120,24 +143,35 @@ def gemm_tn_det(A, B, M, N, K, out, row_interleave_H=0, accumulate=False, ldc=No
     while nslab > 1 and ((K // 32 + nslab - 1) // nslab) * (nslab - 1) >= K // 32:
         nslab -= 1
     ws = torch.empty((nslab, M, ntot), dtype=F32, device=out.device)
-    _lib.call("evc_gemm_tn2_slabs", _p(A), A.stride(0), _p(B), B.stride(0), N, _p(B2), B2.stride(0) if B2 is not None else 0, N2,
-              (c_col2 if c_col2 is not None else N), _p(ws), ntot, M * ntot, M, K, row_interleave_H, nslab, _stream())
+    args = (_p(A), A.stride(0), _p(B), B.stride(0), N, _p(B2), B2.stride(0) if B2 is not None else 0, N2,
+            (c_col2 if c_col2 is not None else N), _p(ws), ntot, M * ntot, M, K)
+    if k_skip:
+        _lib.call("evc_gemm_tn2_slabs_skip", *args, k_skip, row_interleave_H, nslab, _stream())
+    else:
+        _lib.call("evc_gemm_tn2_slabs", *args, row_interleave_H, nslab, _stream())
     for c0, w in ((0, N),) + (((c_col2, N2),) if B2 is not None else ()):
         _lib.call("evc_sum_slabs", _p(ws[0, :, c0:]), M * ntot, nslab, M, w, ntot, _p(out[:, c0:]), ldc, 1 if accumulate else 0, _stream())
     return out
 
 
-def gemm_tn2(A, B1, N1, B2, N2, M, K, out, row_interleave_H=0, accumulate=False, ldc=None, c_col2=None, live_rows=None):
+def gemm_tn2(A, B1, N1, B2, N2, M, K, out, row_interleave_H=0, accumulate=False, ldc=None, c_col2=None, live_rows=None, k_skip=0):
     """out[:, :N1] (+)= A[K,M]^T @ B1[K,N1], out[:, c_col2:c_col2+N2] (+)= A^T @ B2[K,N2] in one launch (N1 % 256 == 0;
-    c_col2 defaults to N1: adjacent segments).  live_rows: as in gemm_tn."""
+    c_col2 defaults to N1: adjacent segments).  live_rows: as in gemm_tn.  k_skip: the first k_skip * 32 rows of B2 are zeros and are not
+    walked (evc_gemm_tn2_rows_skip)."""
     assert A.dtype == BF16 and B1.dtype == BF16 and B2.dtype == BF16 and out.dtype == F32
+    ldc, c_col2 = out.stride(0) if ldc is None else ldc, N1 if c_col2 is None else c_col2
+    if k_skip:
+        slab, ns, arr = _tn_rows_args(live_rows, K, k_skip)
+        _lib.call("evc_gemm_tn2_rows_skip", _p(A), A.stride(0), _p(B1), B1.stride(0), N1, _p(B2), B2.stride(0), N2, c_col2, _p(out), ldc, M, slab, ns, arr, k_skip,
+                  row_interleave_H, 1 if accumulate else 0, _stream())
+        return out
     if live_rows is not None:
         slab, ns, arr = _slab_rows_arg(live_rows, K)
-        _lib.call("evc_gemm_tn2_rows", _p(A), A.stride(0), _p(B1), B1.stride(0), N1, _p(B2), B2.stride(0), N2, N1 if c_col2 is None else c_col2,
-                  _p(out), out.stride(0) if ldc is None else ldc, M, slab, ns, arr, row_interleave_H, 1 if accumulate else 0, _stream())
+        _lib.call("evc_gemm_tn2_rows", _p(A), A.stride(0), _p(B1), B1.stride(0), N1, _p(B2), B2.stride(0), N2, c_col2,
+                  _p(out), ldc, M, slab, ns, arr, row_interleave_H, 1 if accumulate else 0, _stream())
         return out
-    _lib.call("evc_gemm_tn2", _p(A), A.stride(0), _p(B1), B1.stride(0), N1, _p(B2), B2.stride(0), N2, N1 if c_col2 is None else c_col2,
-              _p(out), out.stride(0) if ldc is None else ldc, M, K, row_interleave_H, 1 if accumulate else 0, _stream())
+    _lib.call("evc_gemm_tn2", _p(A), A.stride(0), _p(B1), B1.stride(0), N1, _p(B2), B2.stride(0), N2, c_col2,
+              _p(out), ldc, M, K, row_interleave_H, 1 if accumulate else 0, _stream())
     return out
 
 
@@ -146,6 +180,27 @@ def fill_f32(t, value):
     assert t.dtype == F32 and t.is_contiguous()
     _lib.call("evc_fill_f32", _p(t), t.numel(), float(value), _stream())
 
+
+def fill_f32_cols(t, value):
+    """Fill of a column range t = m[:, c0:c1] of a row-major f32 matrix, in one kernel (evc_fill_f32_cols)."""
+    assert t.dtype == F32 and t.dim() == 2 and t.stride(1) == 1
+    _lib.call("evc_fill_f32_cols", _p(t), t.stride(0), t.shape[0], t.shape[1], float(value), _stream())
+
+
+class _Once:
+    """bool() of a question asked of the loaded library, on first use (importing this module must not load the library)."""
+
+    def __init__(self, ask):
+        self.ask, self.v = ask, None
+
+    def __bool__(self):
+        if self.v is None:
+            self.v = bool(self.ask())
+        return self.v
+
+
+# the TN products' plan query, skip entries and column fill: missing only from a library of an older tree named by EVC_LIB (_lib.NEWER)
+TN_PLAN = _Once(lambda: _lib.has("evc_gemm_tn_plan"))
 
 DETERMINISTIC = os.environ.get("EVC_DETERMINISTIC", "0") not in ("", "0")     # (the library reads the same variable: csrc/evc_common.h)
 
@@ -668,10 +723,16 @@ def lstm_layer_fwd_hp(x_lohi, wx_hilo, wh_hilo, bias, lens, T, M, Kin, H, zx_ws,
 
 
 def lstm_layer_bwd(w_il, lens, T, M, Kin, H, gates, c_all, dS_c, dS_h, ld_dS, dh_above, dc_ws, dz4, plan=None, db=None,
-                   dz_above=None, w_above=None):
+                   dz_above=None, w_above=None, dz_dead_unread=False):
     """db [4H] f32: the bias gradient is accumulated into it (zero it first) - no separate column-sum pass.
     dz_above / w_above (instead of dh_above): the upper layer's gate gradients and backward-layout kernel - its dX is
-    contracted inside this layer's steps."""
+    contracted inside this layer's steps.
+    dz_dead_unread (row plans): nothing reads slab t of dz4 from row round_up(plan.rows[t], 32) on - those tiles are left unwritten
+    (evc_lstm_layer_bwd_live)."""
+    if dz_dead_unread:
+        _lib.call("evc_lstm_layer_bwd_live", _p(w_il), _p(lens), T, M, Kin, H, _p(gates), _p(c_all), _p(dS_c), _p(dS_h), ld_dS,
+                  _p(dh_above), _p(dc_ws), _p(dz4), _p(db), *_plan_args(plan), _p(dz_above), _p(w_above), 1, _stream())
+        return
     _lib.call("evc_lstm_layer_bwd", _p(w_il), _p(lens), T, M, Kin, H, _p(gates), _p(c_all), _p(dS_c), _p(dS_h), ld_dS,
               _p(dh_above), _p(dc_ws), _p(dz4), _p(db), *_plan_args(plan), _p(dz_above), _p(w_above), _stream())
 

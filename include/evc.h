@@ -314,6 +314,14 @@ int evc_lstm_layer_bwd(const evc_bf16* w_il, const int32_t* len, int T, int M, i
                        const evc_bf16* dh_above, float* dc_ws, evc_bf16* dz4, float* db,
                        const int32_t* row_map, const int32_t* rows_per_step, const evc_bf16* dz_above,
                        const evc_bf16* w_above, void* stream);
+/* evc_lstm_layer_bwd with the caller's word (dz_dead_unread = 1; needs rows_per_step, no dz_above) that nothing reads slab t of dz4 from row
+ * round_up(rows_per_step[t], 32) on: step tiles that start there return without writing zeros.  It holds when the weight-gradient products of
+ * the level walk live segments (evc_gemm_tn_plan: live_walk) and dX is the hoisted product, whose rows there are never loaded. */
+int evc_lstm_layer_bwd_live(const evc_bf16* w_il, const int32_t* len, int T, int M, int Kin, int H,
+                       const void* gates, const evc_bf16* c_all, const float* dS_c, const float* dS_h, int64_t ld_dS,
+                       const evc_bf16* dh_above, float* dc_ws, evc_bf16* dz4, float* db,
+                       const int32_t* row_map, const int32_t* rows_per_step, const evc_bf16* dz_above,
+                       const evc_bf16* w_above, int dz_dead_unread, void* stream);
 
 /* ---- a5 + a8 + a9 fused: MoE weight update without materialising the gradient ----------------
  * d(loss)/dW of slim.fully_connected (cs/video_level_models.py:423-435) is dlogits^T . x over the batch rows:
@@ -806,6 +814,27 @@ int evc_gemm_tn2(const evc_bf16* A, int64_t lda, const evc_bf16* B1, int64_t ldb
 int evc_gemm_tn2_rows(const evc_bf16* A, int64_t lda, const evc_bf16* B1, int64_t ldb1, int N1, const evc_bf16* B2, int64_t ldb2,
                       int N2, int c_col2, float* C, int64_t ldc, int M, int slab_rows, int nslabs, const int32_t* rows_per_slab,
                       int row_interleave_H, int accumulate, void* stream);
+/* evc_gemm_tn / evc_gemm_tn2 / evc_gemm_tn2_rows with a skip: the LAST column segment (B2, or B1 when B2 == NULL) does not walk the first k_skip
+ * K steps of 32 operand rows, which the caller knows to be zeros in that operand - h_prev's slab 0 is h_-1 = 0 in the weight-gradient products
+ * dW^T = dz^T . [x | h_prev], so every h column tile otherwise contracts one time slab of zero products.  The same sums (the dropped products are
+ * exact zeros).  rows_per_slab == NULL: the plain walk over slab_rows * nslabs rows.  The K splits are chosen on the shorter walk (>= 32 steps per
+ * split in every tile) and each column segment's tiles split their own steps evenly: no split is empty. */
+int evc_gemm_tn2_rows_skip(const evc_bf16* A, int64_t lda, const evc_bf16* B1, int64_t ldb1, int N1, const evc_bf16* B2, int64_t ldb2,
+                           int N2, int c_col2, float* C, int64_t ldc, int M, int slab_rows, int nslabs, const int32_t* rows_per_slab,
+                           int k_skip, int row_interleave_H, int accumulate, void* stream);
+/* The plan evc_gemm_tn2_rows_skip follows for these arguments (k_skip = 0, rows_per_slab == NULL, N2 = 0: that of the entries without them), asked
+ * without a launch: *tile = 1 (256 x 256) or 11 (128 x 128), *splits = K ranges joined by atomics, *live_walk = 1 when the K walk follows the live
+ * segments of rows_per_slab - no row of slab t from round_up(rows_per_slab[t], 32) on is read - and 0 for the plain walk over every row.  With splits == 1 and accumulate = 0 the launch
+ * stores every element of its columns plainly and once - the caller need not zero them; with splits > 1 it adds into what C holds.  Depends on
+ * EVC_DETERMINISTIC and EVC_FORCE_TILE as the launch does. */
+int evc_gemm_tn_plan(int64_t lda, int64_t ldb1, int N1, int64_t ldb2, int N2, int M, int slab_rows, int nslabs, const int32_t* rows_per_slab,
+                     int k_skip, int* tile, int* splits, int* live_walk);
+/* evc_gemm_tn2_slabs with the skip of evc_gemm_tn2_rows_skip.  The slabs keep the K ranges of the product without the skip and the last segment's tiles
+ * cut the skipped steps off their front (a range cut away whole stores zeros): every slab holds the bits it would hold without the skip, so the
+ * fixed-order sum - the EVC_DETERMINISTIC weight gradient - does not change by one bit. */
+int evc_gemm_tn2_slabs_skip(const evc_bf16* A, int64_t lda, const evc_bf16* B1, int64_t ldb1, int N1, const evc_bf16* B2, int64_t ldb2,
+                            int N2, int c_col2, float* slabs, int64_t ldc, int64_t slab_stride, int M, int K, int k_skip, int row_interleave_H,
+                            int nslab, void* stream);
 /* evc_gemm_tn with the K range cut into nslab partial products stored plainly at slabs + s*M*N (no atomics). */
 int evc_gemm_tn_slabs(const evc_bf16* A, int64_t lda, const evc_bf16* B, int64_t ldb, float* slabs, int M, int N, int K,
                       int nslab, void* stream);
@@ -1131,6 +1160,8 @@ int evc_cascade_pick_rows(const float* conf, const uint8_t* active, const int32_
 
 /* utility: out[i] = value for n floats (avoids torch for tiny fills inside C loops) */
 int evc_fill_f32(float* p, int64_t n, float value, void* stream);
+/* p[r*ld + c] = value for r < rows, c < cols (cols, ld multiples of 4; 16-byte aligned): a column range of a row-major matrix in one kernel. */
+int evc_fill_f32_cols(float* p, int64_t ld, int rows, int cols, float value, void* stream);
 /* Measurement aid, not part of the path: `blocks` workgroups of `threads` threads with `lds_bytes` of LDS each stay resident for
  * `microseconds` - the footprint of a collective's kernel on the compute units, for the one-GPU stand-in runs of DESIGN.md 6.1. */
 int evc_debug_occupy(int blocks, int threads, int lds_bytes, double microseconds, void* stream);

@@ -3,7 +3,7 @@
 // LDS attributes and every kernel launch with its geometry and each field of its operand and store structs.  Nothing runs; no GPU is needed.
 #include "launch_record_stubs.h"
 struct StoreParamsTX {      // the layout of StoreParamsT (defined in evc_gemm_tn.hip itself)
-  float* C; long ldc; int M, N; int row_il_H; int accumulate, splits, ksteps_per_split; long slab_stride;
+  float* C; long ldc; int M, N; int row_il_H; int accumulate, splits, ksteps_per_split; long slab_stride; int ksteps_per_split2;
 };
 static void dump_launch_args(const std::string& n, void** a) {
   if (n.find("gemm_nt_kernel") != std::string::npos) {
@@ -24,6 +24,7 @@ static void dump_launch_args(const std::string& n, void** a) {
     for (int i = 0; i < 16; ++i) fprintf(out(), "%s%u+%u", i ? "," : "", (unsigned)p.seg_start[i], (unsigned)p.seg_len[i]);
     fprintf(out(), "\n  s C=%p ldc=%ld M=%d N=%d row_il_H=%d accumulate=%d splits=%d ksteps=%d slab_stride=%ld\n", (void*)s.C, s.ldc, s.M, s.N, s.row_il_H, s.accumulate, s.splits,
             s.ksteps_per_split, s.slab_stride);
+    if (p.k_skip2) fprintf(out(), "  k_skip2=%d ksteps2=%d\n", p.k_skip2, s.ksteps_per_split2);     // (only the launches that skip: logs of older trees stay comparable)
   } else if (n.find("sum_pairs_kernel") != std::string::npos) {
     fprintf(out(), "  part=%p n=%d sums=%p\n", *(void**)a[0], *(int*)a[1], *(void**)a[2]);
   } else if (n.find("sum_slabs_kernel") != std::string::npos) {
