@@ -107,6 +107,8 @@ SIGNATURES = {
     "evc_ema_update": [vp, vp, f32, i32, vp],
     "evc_bn_bwd_partial": [vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, i32, vp, vp],
     "evc_bn_bwd_finalize": [vp, vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp],
+    "evc_bn_bwd_partial_add": [vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, i32, vp, vp],
+    "evc_bn_bwd_finalize_add": [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp],
     "evc_bn_relu6_framepool_fwd": [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
     "evc_framepool_max_fwd": [vp, i32, i32, i32, vp, vp, vp, vp],
     "evc_framepool_max_bwd": [vp, vp, i32, i32, i32, vp, vp],
@@ -132,6 +134,7 @@ SIGNATURES = {
     "evc_nextvlad_aggregate_packed_fwd_mfma": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp],
     "evc_nextvlad_aggregate_packed_bwd": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp],
     "evc_frames_gather_packed": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp],
+    "evc_frames_gather_packed_bn": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp],
     "evc_frames_gather_packed_sel": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp],
     "evc_scatter_rows": [vp, i64, vp, i32, i32, i32, vp, i64, vp],
     "evc_nextvlad_normalize_fwd": [vp, i32, i32, i32, vp, vp, vp],

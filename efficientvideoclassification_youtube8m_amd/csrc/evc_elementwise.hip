@@ -1794,7 +1794,11 @@ __device__ __forceinline__ float routed_dy(const float* __restrict__ dy, const i
   const long b = r / S;
   return (am[b * C + c] == (int)(r % S)) ? dy[b * C + c] : 0.f;
 }
-__global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const float* __restrict__ x, const float* __restrict__ dy, int R, int C,
+// ADD (evc_bn_bwd_partial_add / _finalize_add): the incoming gradient is dy[i] + dy2[i], one f32 add in front of the
+// mask; the ADD = false instantiations are the code the plain entries always ran.
+template <bool ADD>
+__global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const float* __restrict__ x, const float* __restrict__ dy,
+                                                             const float* __restrict__ dy2, int R, int C,
                                                              const float* __restrict__ mean, const float* __restrict__ var,
                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
                                                              int relu6, const int* __restrict__ am, int S, double* __restrict__ ws) {
@@ -1808,6 +1812,7 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const float* __rest
       const long i = (long)r * C + c;
       const float xh = (x[i] - mu) * inv;
       float d = routed_dy(dy, am, S, r, c, C);
+      if constexpr (ADD) d = d + dy2[i];
       if (relu6) { const float y = xh * ga + be; if (!(y > 0.f && y < 6.f)) d = 0.f; }
       s += d; q += (double)d * xh;
     }
@@ -1819,7 +1824,8 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const float* __rest
     atomicAdd(&ws[C + c], sh[1][0][tx] + sh[1][1][tx] + sh[1][2][tx] + sh[1][3][tx]);
   }
 }
-__global__ void bn_bwd_final_kernel(const float* __restrict__ x, const float* __restrict__ dy, long n, int R, int C,
+template <bool ADD>
+__global__ void bn_bwd_final_kernel(const float* __restrict__ x, const float* __restrict__ dy, const float* __restrict__ dy2, long n, int R, int C,
                                     const float* __restrict__ mean, const float* __restrict__ var, const float* __restrict__ gamma,
                                     const float* __restrict__ beta, int relu6, const int* __restrict__ am, int S,
                                     const double* __restrict__ ws,
@@ -1830,6 +1836,7 @@ __global__ void bn_bwd_final_kernel(const float* __restrict__ x, const float* __
     const float inv = rsqrtf(var[c] + 1e-3f), ga = gamma[c];
     const float xh = (x[i] - mean[c]) * inv;
     float d = routed_dy(dy, am, S, i / C, c, C);
+    if constexpr (ADD) d = d + dy2[i];
     if (relu6) { const float y = xh * ga + beta[c]; if (!(y > 0.f && y < 6.f)) d = 0.f; }
     const float sd = (float)ws[c], sdx = (float)ws[C + c];
     // dx = gamma*inv/R * (R*d - sum(d) - xh*sum(d*xh))
@@ -1839,28 +1846,61 @@ __global__ void bn_bwd_final_kernel(const float* __restrict__ x, const float* __
     if (i < C) { if (dgamma) dgamma[i] = (float)ws[C + i]; if (dbeta) dbeta[i] = (float)ws[i]; }
   }
 }
-extern "C" int evc_bn_bwd_partial(const float* x, const float* dy, int R, int C, const float* mean, const float* var,
-                                  const float* gamma, const float* beta, int relu6, const int32_t* argmax, int S,
-                                  double* ws, void* stream) {
-  EVC_REQUIRE(R > 0 && C > 0 && ws && (!argmax || (S > 0 && R % S == 0)), EVC_ERR_BAD_SHAPE, "evc_bn_bwd_partial: bad args");
+static int bn_bwd_partial_launch(const char* who, const float* x, const float* dy, const float* dy2, int R, int C, const float* mean,
+                                 const float* var, const float* gamma, const float* beta, int relu6, const int32_t* argmax, int S,
+                                 double* ws, void* stream) {
+  EVC_REQUIRE(R > 0 && C > 0 && ws && (!argmax || (S > 0 && R % S == 0)), EVC_ERR_BAD_SHAPE, "%s: bad args", who);
+  EVC_REQUIRE(!dy2 || !argmax, EVC_ERR_BAD_ARG, "%s: dy2 with argmax (max-pool routing: dy is [R/S][C], dy2 [R][C])", who);
   hipStream_t st = (hipStream_t)stream;
   EVC_CHECK_HIP(hipMemsetAsync(ws, 0, sizeof(double) * 2 * C, st));
   int rs = R / 256; rs = rs < 1 ? 1 : (rs > 64 ? 64 : rs);
-  hipLaunchKernelGGL(bn_bwd_partial_kernel, dim3((C + 63) / 64, rs), dim3(256), 0, st, x, dy, R, C, mean, var, gamma, beta, relu6,
-                     argmax, S, ws);
+  if (dy2)
+    hipLaunchKernelGGL(bn_bwd_partial_kernel<true>, dim3((C + 63) / 64, rs), dim3(256), 0, st, x, dy, dy2, R, C, mean, var, gamma, beta,
+                       relu6, argmax, S, ws);
+  else
+    hipLaunchKernelGGL(bn_bwd_partial_kernel<false>, dim3((C + 63) / 64, rs), dim3(256), 0, st, x, dy, dy2, R, C, mean, var, gamma, beta,
+                       relu6, argmax, S, ws);
   EVC_LAUNCH_CHECK();
   return EVC_OK;
+}
+static int bn_bwd_finalize_launch(const char* who, const float* x, const float* dy, const float* dy2, int R, int R_total, int C,
+                                  const float* mean, const float* var, const float* gamma, const float* beta, int relu6,
+                                  const int32_t* argmax, int S, const double* ws, float* dx_f32, evc_bf16* dx_bf16, float* dgamma,
+                                  float* dbeta, void* stream) {
+  EVC_REQUIRE(R > 0 && C > 0 && ws && R_total >= R, EVC_ERR_BAD_SHAPE, "%s: bad args", who);
+  EVC_REQUIRE(!dy2 || !argmax, EVC_ERR_BAD_ARG, "%s: dy2 with argmax (max-pool routing: dy is [R/S][C], dy2 [R][C])", who);
+  const long n = (long)R * C;
+  if (dy2)
+    hipLaunchKernelGGL(bn_bwd_final_kernel<true>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, x, dy, dy2, n, R_total, C, mean,
+                       var, gamma, beta, relu6, argmax, S, ws, dx_f32, dx_bf16, dgamma, dbeta);
+  else
+    hipLaunchKernelGGL(bn_bwd_final_kernel<false>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, x, dy, dy2, n, R_total, C, mean,
+                       var, gamma, beta, relu6, argmax, S, ws, dx_f32, dx_bf16, dgamma, dbeta);
+  EVC_LAUNCH_CHECK();
+  return EVC_OK;
+}
+extern "C" int evc_bn_bwd_partial(const float* x, const float* dy, int R, int C, const float* mean, const float* var,
+                                  const float* gamma, const float* beta, int relu6, const int32_t* argmax, int S,
+                                  double* ws, void* stream) {
+  return bn_bwd_partial_launch("evc_bn_bwd_partial", x, dy, nullptr, R, C, mean, var, gamma, beta, relu6, argmax, S, ws, stream);
 }
 extern "C" int evc_bn_bwd_finalize(const float* x, const float* dy, int R, int R_total, int C, const float* mean,
                                    const float* var, const float* gamma, const float* beta, int relu6,
                                    const int32_t* argmax, int S, const double* ws, float* dx_f32, evc_bf16* dx_bf16,
                                    float* dgamma, float* dbeta, void* stream) {
-  EVC_REQUIRE(R > 0 && C > 0 && ws && R_total >= R, EVC_ERR_BAD_SHAPE, "evc_bn_bwd_finalize: bad args");
-  const long n = (long)R * C;
-  hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, x, dy, n, R_total, C, mean, var,
-                     gamma, beta, relu6, argmax, S, ws, dx_f32, dx_bf16, dgamma, dbeta);
-  EVC_LAUNCH_CHECK();
-  return EVC_OK;
+  return bn_bwd_finalize_launch("evc_bn_bwd_finalize", x, dy, nullptr, R, R_total, C, mean, var, gamma, beta, relu6, argmax, S, ws, dx_f32,
+                                dx_bf16, dgamma, dbeta, stream);
+}
+extern "C" int evc_bn_bwd_partial_add(const float* x, const float* dy, const float* dy2, int R, int C, const float* mean, const float* var,
+                                      const float* gamma, const float* beta, int relu6, const int32_t* argmax, int S, double* ws,
+                                      void* stream) {
+  return bn_bwd_partial_launch("evc_bn_bwd_partial_add", x, dy, dy2, R, C, mean, var, gamma, beta, relu6, argmax, S, ws, stream);
+}
+extern "C" int evc_bn_bwd_finalize_add(const float* x, const float* dy, const float* dy2, int R, int R_total, int C, const float* mean,
+                                       const float* var, const float* gamma, const float* beta, int relu6, const int32_t* argmax, int S,
+                                       const double* ws, float* dx_f32, evc_bf16* dx_bf16, float* dgamma, float* dbeta, void* stream) {
+  return bn_bwd_finalize_launch("evc_bn_bwd_finalize_add", x, dy, dy2, R, R_total, C, mean, var, gamma, beta, relu6, argmax, S, ws, dx_f32,
+                                dx_bf16, dgamma, dbeta, stream);
 }
 extern "C" int evc_bn_relu6_bwd(const float* x, const float* dy, int R, int C, const float* mean, const float* var,
                                 const float* gamma, const float* beta, int relu6, const int32_t* argmax, int S, double* ws,

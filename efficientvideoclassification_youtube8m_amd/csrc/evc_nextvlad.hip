@@ -610,6 +610,90 @@ extern "C" int evc_frames_gather_packed(const float* x, const uint8_t* x_u8, con
   EVC_LAUNCH_CHECK();
   return EVC_OK;
 }
+// ---- the input pass of a tower that knows its input batch-norm statistics before it sees the batch (a forward-only grid tower on its
+// moving statistics): the packed rows as frames_gather_packed_kernel<false> makes them - the same loads, sums and
+// products in the same order - and, from the registers that hold a row's quarter, its batch-normalised bf16 copy with
+// bn_apply_kernel's expression (evc_elementwise.hip), so that neither output differs from the two launches in a bit.  The product
+// v * inv is formed with contraction switched off (mul_rounded): the value that the batch norm reads is the f32 that is stored, never a
+// fused v * inv - mean, whose missing rounding moves one bf16 in ~45 000 (an intrinsic such as __fmul_rn does not stop the fusion).
+// One wave per row, 16-byte loads and stores (8 bytes for the bf16 quarter), the four per-column vectors as float4; no LDS, no atomics.
+__device__ __forceinline__ float mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__global__ __launch_bounds__(256) void frames_gather_packed_bn_kernel(const float* __restrict__ x, const uint8_t* __restrict__ xq,
+                                                                      const int* __restrict__ nfr, const int* __restrict__ row_off, int B,
+                                                                      int T, int F, int every_n, int R, int Rp, int normalize,
+                                                                      const float4* __restrict__ mean, const float4* __restrict__ var,
+                                                                      const float4* __restrict__ gamma, const float4* __restrict__ beta,
+                                                                      float* __restrict__ out, uint2* __restrict__ out_bn) {
+  const int lane = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= Rp) return;
+  const int F4 = F >> 2;
+  float4* dst = (float4*)(out + row * F);
+  uint2* dst_bn = out_bn + row * F4;
+  if (row >= R) {
+    for (int j = lane; j < F4; j += 64) {
+      dst[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+      dst_bn[j] = make_uint2(0u, 0u);
+    }
+    return;
+  }
+  int b = 0, hi = B;
+  while (hi - b > 1) {
+    const int mid = (b + hi) >> 1;
+    if (row_off[mid] <= (int)row) b = mid; else hi = mid;
+  }
+  const long fr = (long)((int)row - row_off[b]) * every_n;
+  const int n = nfr[b];
+  const int idx = fr < 0 ? 0 : (fr >= T ? T - 1 : (int)fr);
+  const bool padded = xq && idx >= n;            // uint8 input: frames >= num_frames are padding (zero after Dequantize)
+  auto load = [&](int j) {
+    if (padded) return make_float4(0.f, 0.f, 0.f, 0.f);
+    if (xq) {
+      const uchar4 q = ((const uchar4*)(xq + ((long)b * T + idx) * F))[j];
+      const float sc = 4.0f / 255.0f, bi = 4.0f / 512.0f - 2.0f;
+      return make_float4(q.x * sc + bi, q.y * sc + bi, q.z * sc + bi, q.w * sc + bi);
+    }
+    return ((const float4*)(x + ((long)b * T + idx) * F))[j];
+  };
+  float inv = 1.f;
+  if (normalize) {
+    float ss = 0.f;
+    for (int j = lane; j < F4; j += 64) { const float4 v = load(j); ss += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w; }
+    inv = rsqrtf(fmaxf(wave_sum(ss), 1e-12f));
+  }
+  auto bn = [](float r, float mu, float va, float ga, float be) { return (r - mu) * rsqrtf(va + 1e-3f) * ga + be; };
+  for (int j = lane; j < F4; j += 64) {
+    float4 v = load(j);
+    v.x = mul_rounded(v.x, inv); v.y = mul_rounded(v.y, inv); v.z = mul_rounded(v.z, inv); v.w = mul_rounded(v.w, inv);
+    dst[j] = v;
+    const float4 mu = mean[j], va = var[j], ga = gamma[j], be = beta[j];
+    dst_bn[j] = make_uint2(pack_bf16x2_hw(bn(v.x, mu.x, va.x, ga.x, be.x), bn(v.y, mu.y, va.y, ga.y, be.y)),
+                           pack_bf16x2_hw(bn(v.z, mu.z, va.z, ga.z, be.z), bn(v.w, mu.w, va.w, ga.w, be.w)));
+  }
+}
+extern "C" int evc_frames_gather_packed_bn(const float* x, const uint8_t* x_u8, const int32_t* num_frames, const int32_t* row_off, int B,
+                                           int T, int F, int every_n, int R, int Rp, int normalize, const float* mean, const float* var,
+                                           const float* gamma, const float* beta, float* out, evc_bf16* out_bn_bf16, void* stream) {
+  EVC_REQUIRE(B > 0 && T > 0 && F > 0 && F % 4 == 0 && every_n >= 1 && R >= 0 && Rp >= R && Rp - R < 32 &&
+              (long)R <= (long)B * ((T + every_n - 1) / every_n), EVC_ERR_BAD_SHAPE,
+              "evc_frames_gather_packed_bn: needs F %% 4 == 0, every_n >= 1, R <= B * ceil(T / every_n), R <= Rp < R + 32 "
+              "(B=%d T=%d F=%d every_n=%d R=%d Rp=%d)", B, T, F, every_n, R, Rp);
+  EVC_REQUIRE((x != nullptr) != (x_u8 != nullptr), EVC_ERR_BAD_ARG, "evc_frames_gather_packed_bn: exactly one of x / x_u8");
+  EVC_REQUIRE(num_frames && row_off && mean && var && gamma && beta && out && out_bn_bf16, EVC_ERR_BAD_ARG,
+              "evc_frames_gather_packed_bn: NULL operand");
+  EVC_REQUIRE(nx_aligned16(x) && ((uintptr_t)x_u8 % 4) == 0 && nx_aligned16(out) && ((uintptr_t)out_bn_bf16 % 8) == 0 && nx_aligned16(mean) &&
+              nx_aligned16(var) && nx_aligned16(gamma) && nx_aligned16(beta), EVC_ERR_BAD_ALIGN,
+              "evc_frames_gather_packed_bn: misaligned operand (float4 / uchar4 / 8-byte bf16 access)");
+  if (Rp == 0) return EVC_OK;
+  hipLaunchKernelGGL(frames_gather_packed_bn_kernel, dim3((unsigned)((Rp + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, x_u8, num_frames,
+                     row_off, B, T, F, every_n, R, Rp, normalize, (const float4*)mean, (const float4*)var, (const float4*)gamma,
+                     (const float4*)beta, out, (uint2*)out_bn_bf16);
+  EVC_LAUNCH_CHECK();
+  return EVC_OK;
+}
 extern "C" int evc_frames_gather_packed_sel(const float* x, const uint8_t* x_u8, const int32_t* num_frames, const int32_t* row_off,
                                             const int32_t* sel, int B, int Bsel, int T, int F, int every_n, int R, int Rp, int normalize,
                                             float* out, evc_bf16* out_bf16, void* stream) {

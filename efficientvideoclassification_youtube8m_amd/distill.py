@@ -1882,35 +1882,165 @@ def check_netvlad_checkpoint(sd, scope, feature_size, vocab_size, sizes, what="t
                              % (scope, k, what, tuple(have.shape), shp))
 
 
+class NetVladDistillGraph(_StepGraph):
+    """Serial distillation for the NetVLAD family, NeXtVladDistillGraph for this tower: a grid student (frames
+    j * every_n of every video, scope 'model_student') against a FROZEN grid teacher (every teacher_every_n-th real frame, scope
+    'model': forward only, batch norms on the checkpoint's moving statistics, no gradient store / moments / tape, never written).  One
+    step on one stream: teacher forward, student forward, the loss section of DistillGraph's mode 'serial' (ops.distill_losses on the
+    towers' h6 = relu6(hidden1_bn(hid)) and predictions, the same scales), the student's backward with dL_REP/dstate joining the MoE
+    head's gradient in front of hidden1_bn's relu6 mask, and the update exactly as SingleTowerGraph.step performs it; global_step += 1.
+    Reporting follows DistillGraph's serial mode (`out` keys, LOSS_SLOTS, loss_report), so train's loop needs no special case.  Every
+    refusal is a ValueError before the device is touched."""
+
+    LOSS_SLOTS = DistillGraph.LOSS_SLOTS
+    DISTILL_LOSSES = DistillGraph.DISTILL_LOSSES
+    mode = "serial"
+    student_sampling = "uniform"                 # (the grid is the uniform sub-sampling of the real frames; checkpoint metadata)
+    dp = False
+
+    def __init__(self, batch_size, every_n=10, teacher_every_n=1, feature_size=1152, vocab_size=4716, max_frames=300, cluster_size=64,
+                 hidden_size=1024, num_mixtures=2, base_learning_rate=0.001, learning_rate_decay=1.0,
+                 learning_rate_decay_examples=4000000, regularization_penalty=2.0, clip_gradient_norm=1.0, count_rep_twice=True,
+                 device="cuda:0", seed=7, process_group=None, precision="bf16", distill_losses=DISTILL_LOSSES, label_loss=None):
+        from .towers import NetVladTower, check_netvlad_frames
+        self.world = _world_of(process_group)
+        if self.world > 1:
+            raise ValueError("NetVladDistillGraph is not data parallel (process group of %d ranks): train the student against the "
+                             "frozen teacher on one device" % self.world)
+        self.label_loss = _resolve_label_loss(label_loss, vocab_size)
+        if not losses_mod.is_default(self.label_loss):
+            raise ValueError("NetVladDistillGraph has CrossEntropyLoss built into its loss section (evc_distill_losses), not %s"
+                             % type(self.label_loss).__name__)
+        if precision != "bf16":
+            raise ValueError("NetVladDistillGraph: precision %r is refused, the NetVLAD tower has no such forward mode (bf16 only)" % (precision,))
+        self.distill_losses = check_distill_losses(distill_losses)
+        for n in (every_n, teacher_every_n):     # (ValueError naming --every_n and its range)
+            check_netvlad_frames("grid", n, max_frames, world=self.world, precision=precision)
+        self.B, self.every_n, self.teacher_every_n, self.precision = batch_size, int(every_n), int(teacher_every_n), precision
+        self.lr0, self.lr_decay, self.lr_decay_examples = base_learning_rate, learning_rate_decay, learning_rate_decay_examples
+        self.reg_pen, self.clip, self.pg = regularization_penalty, clip_gradient_norm, process_group
+        self.rep_w = 2.0 if count_rep_twice else 1.0
+        self.device = torch.device(device)
+        self.global_step = 0
+        sizes = (batch_size, max_frames, feature_size, vocab_size, 30, cluster_size, hidden_size, num_mixtures)
+        self.teacher = NetVladTower(*sizes, device=device, training=False, scope="model", seed=seed, frames="grid",
+                                    every_n=self.teacher_every_n)
+        self.student = NetVladTower(*sizes, device=device, training=True, scope="model_student", seed=seed + 1, frames="grid",
+                                    every_n=self.every_n)
+        self.moe = self.student.moe
+        self.fused_moe_update = True
+        self.losses = torch.zeros(8, dtype=F32, device=self.device)
+        self._dp_s = self._ds_s = None
+
+    def _towers(self):
+        return [self.teacher, self.student]
+
+    def consolidate(self):
+        """Nothing is sharded on one rank (kept for train's checkpoint path)."""
+
+    def state_dict(self):
+        """Both scopes: model/* (the frozen teacher, the bits it was loaded with) and model_student/*."""
+        out = self.teacher.state_dict()
+        out.update(self.student.state_dict())
+        return out
+
+    def label_grads(self):
+        """The student's dL/dpred buffer of the last step (its L_CE and L_PRED gradient), as DistillGraph names it."""
+        return {} if self._dp_s is None else {"student": self._dp_s}
+
+    def state_grad(self):
+        """The dL_REP/dstate buffer of the last step (None before the first).  For tests and debugging."""
+        return self._ds_s
+
+    @property
+    def losses_for_report(self):
+        return self.losses
+
+    def loss_report(self, losses=None):
+        v = (self.losses if losses is None else losses).tolist()
+        return {k: v[i] for i, k in enumerate(self.LOSS_SLOTS)}
+
+    def step(self, x_raw, labels_u8, num_frames, apply=True, num_frames_host=None):
+        """x_raw [B,T,F] uint8 or float32, labels_u8 [B,V], num_frames [B] int32 (num_frames_host: the same counts on the host - both
+        towers lay their packed rows out from them; read back from the device when not given).  All launches on the caller's stream."""
+        B, V = labels_u8.shape
+        tt, ts = self.teacher, self.student
+        if num_frames_host is None:
+            num_frames_host = num_frames.cpu().numpy()
+        if self._dp_s is None or self._dp_s.shape[0] != B:
+            self._dp_s = torch.empty((B, V), dtype=F32, device=self.device)
+            self._ds_s = torch.empty((B, ts.Hd), dtype=F32, device=self.device)
+        t_pred = tt.forward(x_raw, num_frames, num_frames_host=num_frames_host, is_training=False)
+        s_pred = ts.forward(x_raw, num_frames, num_frames_host=num_frames_host)
+        on = self.distill_losses
+        self.losses.zero_()
+        ops.distill_losses(t_pred, tt.rowsum, s_pred, ts.rowsum, labels_u8, tt.state, ts.state, self.losses, self._dp_s, self._ds_s,
+                           g_ce=(1.0 / B) if "ce" in on else 0.0, g_kl=1.0 if "pred" in on else 0.0,
+                           g_rep=self.rep_w if "rep" in on else 0.0)
+        # the update of SingleTowerGraph.step on one rank: the MoE head's two matrices through the fused clip + Adam pass whenever
+        # the step applies (their gradient recomputed from its rank-B factors), the rest through clip_by_norm + TF-Adam
+        fuse = (apply and self.fused_moe_update and self.moe.can_fuse_update() and self.moe.prefer_fused_update(False)
+                and ts.precision == "bf16")
+        fused_names = (self.moe.GATES, self.moe.EXPERTS, self.moe.EBIAS) if fuse else ()
+        ts.backward(self._dp_s, moe_weight_grads=not fuse, dstate=self._ds_s)
+        if apply:
+            lr, l2c = self._lr_l2c(B)
+            if fuse:
+                ts.begin_update()
+                self.moe.fused_update(ts.adam_lr_t(lr), self.clip, l2c, dp=None)
+                ts.apply_group([k for k in ts.names if k not in fused_names], lr, self.clip, l2c)
+            else:
+                ts.apply_gradients(lr, self.clip, l2c)
+            self.global_step += 1
+        return dict(predictions=t_pred, teacher_state=tt.state, loss=self.losses[0], student_predictions=s_pred, student_state=ts.state,
+                    num_frames_student=torch.from_numpy(ts.plan.k), student_loss_state=self.losses[1], pred_loss=self.losses[2],
+                    student_label_loss=self.losses[3], global_step=self.global_step)
+
+
 class NetVladEvalGraph(_StepGraph):
-    """Forward-only graph of the NetVLAD family with EvalGraph's interface (DESIGN.md 7.18): restore(state_dict) and
+    """Forward-only graph of the NetVLAD family with EvalGraph's interface (DESIGN.md 7.18, 7.19): restore(state_dict) and
     step(x_raw, labels_u8, num_frames, num_frames_host=None, keys=None) -> dict with predictions, loss, num_frames, so that validate
-    holds it where it holds an EvalGraph.  One forward-only grid tower, scope model, on every `every_n`-th real frame (training=False:
-    the moving statistics), bf16 only, on the caller's stream.  No row compaction: a video without a frame runs through the head with
-    V = 0 like any other and its row holds what the head makes of that.  The buffers are allocated once at batch_size: a shorter batch
-    allocates nothing."""
+    holds it where it holds an EvalGraph.  tower: 'teacher' (scope model, on every `every_n`-th real frame), 'student' (scope
+    model_student, the same) or 'both' (the student served at every_n, the teacher run too at teacher_every_n: validate's
+    student_state_loss).  Forward-only grid towers (training=False: the moving statistics), bf16 only, on the caller's stream.  No row
+    compaction: a video without a frame runs through the head with V = 0 like any other and its row holds what the head makes of that.
+    The buffers are allocated once at batch_size: a shorter batch allocates nothing."""
 
     family = "netvlad"
     student_sampling = "uniform"
 
     def __init__(self, batch_size, every_n=1, feature_size=1152, vocab_size=4716, max_frames=300, cluster_size=64, hidden_size=1024,
-                 num_mixtures=2, device="cuda:0", precision="bf16", label_loss=None, seed=7):
+                 num_mixtures=2, device="cuda:0", precision="bf16", label_loss=None, seed=7, tower="teacher", teacher_every_n=1):
         from .towers import NetVladTower, check_netvlad_frames
-        check_netvlad_frames("grid", every_n, max_frames, precision=precision)       # (before the device is touched)
+        if tower not in ("teacher", "student", "both"):
+            raise ValueError("NetVladEvalGraph: tower %r (teacher | student | both)" % (tower,))
+        for n in [every_n] + ([teacher_every_n] if tower == "both" else []):
+            check_netvlad_frames("grid", n, max_frames, precision=precision)         # (before the device is touched)
         self.label_loss = _resolve_label_loss(label_loss, vocab_size)
-        self.every_n, self.batch_size, self.max_frames, self.precision = int(every_n), batch_size, max_frames, precision
+        self.tower, self.every_n, self.teacher_every_n = tower, int(every_n), int(teacher_every_n if tower == "both" else every_n)
+        self.batch_size, self.max_frames, self.precision = batch_size, max_frames, precision
         self.sizes = (cluster_size, hidden_size, num_mixtures)
         self.F, self.V = feature_size, vocab_size
         self.device = torch.device(device)
-        self.teacher = NetVladTower(batch_size, max_frames, feature_size, vocab_size, 30, cluster_size, hidden_size, num_mixtures, device=device,
-                                    training=False, scope="model", seed=seed, frames="grid", every_n=self.every_n)
-        self.student = None
-        self.losses = torch.zeros(1, dtype=F32, device=self.device)
+        args = (batch_size, max_frames, feature_size, vocab_size, 30, cluster_size, hidden_size, num_mixtures)
+        self.teacher = self.student = None
+        if tower != "student":
+            self.teacher = NetVladTower(*args, device=device, training=False, scope="model", seed=seed, frames="grid",
+                                        every_n=self.teacher_every_n)
+        if tower != "teacher":
+            self.student = NetVladTower(*args, device=device, training=False, scope="model_student", seed=seed + 1, frames="grid",
+                                        every_n=self.every_n)
+        self.losses = torch.zeros(2 if tower == "both" else 1, dtype=F32, device=self.device)
+
+    def _towers(self):
+        return [tw for tw in (self.teacher, self.student) if tw is not None]
 
     def restore(self, state_dict):
-        """The tower's variables and moving statistics by name, after the host check of their shapes against the graph's sizes."""
-        check_netvlad_checkpoint(state_dict, self.teacher.scope, self.F, self.V, self.sizes)
-        self.teacher.load_state_dict(state_dict)
+        """Each tower's variables and moving statistics by name, after the host check of their shapes against the graph's sizes."""
+        for tw in self._towers():
+            check_netvlad_checkpoint(state_dict, tw.scope, self.F, self.V, self.sizes)
+        for tw in self._towers():
+            tw.load_state_dict(state_dict)
 
     def step(self, x_raw, labels_u8, num_frames, num_frames_host=None, keys=None):
         """x_raw [b, T, F] uint8 or float32, b <= batch_size; labels_u8 [b, V]; num_frames [b] int32 (num_frames_host: the same counts
@@ -1921,8 +2051,20 @@ class NetVladEvalGraph(_StepGraph):
         if num_frames_host is None:
             num_frames_host = num_frames.cpu()
         nh = np.asarray(num_frames_host, dtype=np.int64).reshape(-1)
-        tw = self.teacher
-        pred = tw.forward(x_raw, num_frames, is_training=False, num_frames_host=nh)
+        out = {}
+        if self.teacher is not None:
+            pred = t_pred = self.teacher.forward(x_raw, num_frames, is_training=False, num_frames_host=nh)
+            if self.tower == "both":
+                out.update(teacher_predictions=t_pred, teacher_state=self.teacher.state)
+        if self.student is not None:
+            pred = self.student.forward(x_raw, num_frames, is_training=False, num_frames_host=nh)
+            out["student_state"] = self.student.state
+        served = self.student if self.student is not None else self.teacher
         self.losses.zero_()
         self.label_loss.fused(pred, labels_u8, self.losses[0:1])
-        return dict(predictions=pred, loss=self.losses[0], num_frames=torch.from_numpy(tw.plan.k.copy()))
+        if self.tower == "both":
+            ops.rep_loss(self.teacher.state, self.student.state, self.losses[1:2])
+            out["student_state_loss"] = self.losses[1]
+            out["student_label_loss"] = self.losses[0]
+        out.update(predictions=pred, loss=self.losses[0], num_frames=torch.from_numpy(served.plan.k.copy()))
+        return out

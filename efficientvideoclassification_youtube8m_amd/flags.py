@@ -181,15 +181,15 @@ _define("student_sampling", "uniform", _sampling, "uniform|first|middle|last|fir
 _define("student_sampling_seed", 0, int, "seed of --student_sampling random")
 _define("ensemble_sampling", "", str, "one --student_sampling word per member (ignored for teachers); '' = --student_sampling for all")
 # ---- serial distillation (train): the student against a finished, frozen teacher -----------------------------------------------------------
-_define("teacher_dir", "", str, "HierarchicalLstmModel (and NeXtVLADModel with --nextvlad_frames grid, DESIGN.md 7.14): directory of a finished teacher (train --teacher_only True, or any checkpoint with "
+_define("teacher_dir", "", str, "HierarchicalLstmModel (and NeXtVLADModel with --nextvlad_frames grid, DESIGN.md 7.14, NetVLADModel with --netvlad_frames grid, DESIGN.md 7.19): directory of a finished teacher (train --teacher_only True, or any checkpoint with "
         "model/* variables).  Set: the student is trained against that FROZEN teacher (the paper's Serial training; DistillGraph mode "
         "'serial'): the teacher runs forward only and is never written, one train op per iteration (global_step += 1); the checkpoint keeps "
         "model/* bit-identical to the source next to model_student/*.  On resume both towers come from --train_dir.  Not with "
         "--teacher_only, train_finetune or several ranks")
 _define("distill_losses", "rep,pred,ce", _distill_losses, "with --teacher_dir: which of L_REP, L_PRED, L_CE the student is trained on (comma "
         "list out of rep, pred, ce; the default is the reference's total, L_REP counted twice).  A loss left out is still computed and logged")
-_define("student_init_from_teacher", False, _bool, "--model NeXtVLADModel with --teacher_dir (the grid student against the frozen grid "
-        "teacher, distill.NeXtVladDistillGraph): True starts a NEW student from the teacher's weights and moving statistics instead of its own "
+_define("student_init_from_teacher", False, _bool, "--model NeXtVLADModel or NetVLADModel with --teacher_dir (the grid student against the frozen grid "
+        "teacher, distill.NeXtVladDistillGraph / NetVladDistillGraph): True starts a NEW student from the teacher's weights and moving statistics instead of its own "
         "seed; ignored (with a log line) on resume")
 # ---- serial distillation of several students against ONE forward of the frozen teacher per batch (train) ---------------------------------
 _define("serial_student_dirs", "", str, "with --teacher_dir: comma separated train directories, one per student (1 .. 8).  Set: all of them are "

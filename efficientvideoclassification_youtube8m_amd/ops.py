@@ -1305,6 +1305,19 @@ def bn_bwd_finalize(x, dy, R, R_total, Cc, mean, var, gamma, beta, relu6, ws, ar
               1 if relu6 else 0, _p(argmax), S, _p(ws), _p(dx_f32), _p(dx_bf16), _p(dgamma), _p(dbeta), _stream())
 
 
+def bn_bwd_partial_add(x, dy, dy2, R, Cc, mean, var, gamma, beta, relu6, ws, argmax=None, S=1):
+    """bn_bwd_partial on the gradient dy + dy2 (dy2 [R, Cc] f32 or None: the plain entry's launch and bits)."""
+    _lib.call("evc_bn_bwd_partial_add", _p(x), _p(dy), _p(dy2), R, Cc, _p(mean), _p(var), _p(gamma), _p(beta), 1 if relu6 else 0,
+              _p(argmax), S, _p(ws), _stream())
+
+
+def bn_bwd_finalize_add(x, dy, dy2, R, R_total, Cc, mean, var, gamma, beta, relu6, ws, argmax=None, S=1,
+                        dx_f32=None, dx_bf16=None, dgamma=None, dbeta=None):
+    """bn_bwd_finalize on the gradient dy + dy2, after bn_bwd_partial_add on the same pair."""
+    _lib.call("evc_bn_bwd_finalize_add", _p(x), _p(dy), _p(dy2), R, R_total, Cc, _p(mean), _p(var), _p(gamma), _p(beta),
+              1 if relu6 else 0, _p(argmax), S, _p(ws), _p(dx_f32), _p(dx_bf16), _p(dgamma), _p(dbeta), _stream())
+
+
 def bn_relu6_framepool_fwd(act, B, S, Cc, mean, var, gamma, beta, pooled_f32, pooled_bf16, argmax):
     _lib.call("evc_bn_relu6_framepool_fwd", _p(act), B, S, Cc, _p(mean), _p(var), _p(gamma), _p(beta), _p(pooled_f32),
               _p(pooled_bf16), _p(argmax), _stream())
@@ -1525,6 +1538,20 @@ def frames_gather_packed(x, num_frames, row_off, every_n, R, Rp, out, out_bf16=N
     assert row_off.dtype == torch.int32 and row_off.numel() == B + 1 and num_frames.dtype == torch.int32 and num_frames.numel() == B
     _lib.call("evc_frames_gather_packed", None if is_u8 else _p(x), _p(x) if is_u8 else None, _p(num_frames), _p(row_off), B, T, F, every_n, R, Rp,
               1 if normalize else 0, _p(out), _p(out_bf16), _stream())
+
+
+def frames_gather_packed_bn(x, num_frames, row_off, every_n, R, Rp, mean, var, gamma, beta, out, out_bn, normalize=False):
+    """frames_gather_packed and bn_apply(relu6=False, y_bf16=out_bn) behind it in one launch, for statistics known before the batch
+    (DESIGN.md 7.19): out [>= Rp, F] f32 and out_bn [>= Rp, F] bf16, bit for bit the two launches' outputs; rows R .. Rp zeros in both."""
+    B, T, F = x.shape
+    is_u8 = x.dtype == torch.uint8
+    assert x.is_contiguous() and out.is_contiguous() and out.dtype == F32 and out.shape[0] >= Rp and out.shape[1] == F
+    assert out_bn.is_contiguous() and out_bn.dtype == BF16 and out_bn.shape[0] >= Rp and out_bn.shape[1] == F
+    assert row_off.dtype == torch.int32 and row_off.numel() == B + 1 and num_frames.dtype == torch.int32 and num_frames.numel() == B
+    for v in (mean, var, gamma, beta):
+        assert v.dtype == F32 and v.numel() == F and v.is_contiguous()
+    _lib.call("evc_frames_gather_packed_bn", None if is_u8 else _p(x), _p(x) if is_u8 else None, _p(num_frames), _p(row_off), B, T, F, every_n,
+              R, Rp, 1 if normalize else 0, _p(mean), _p(var), _p(gamma), _p(beta), _p(out), _p(out_bn), _stream())
 
 
 def check_row_selection(sel, B):

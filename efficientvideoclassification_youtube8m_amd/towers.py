@@ -75,8 +75,17 @@ class BatchNorm:
         ops.ema_update(tw.buffers[self.scope + "/moving_mean"], self.mean)
         ops.ema_update(tw.buffers[self.scope + "/moving_variance"], self.var)
 
-    def backward(self, x, dy, R, relu6, argmax=None, S=1, dx_f32=None, dx_bf16=None):
+    def backward(self, x, dy, R, relu6, argmax=None, S=1, dx_f32=None, dx_bf16=None, dy2=None):
+        """dy2 (None or [R, C] f32): a second gradient on the layer's output, added to dy in front of the relu6 mask inside both
+        passes (evc_bn_bwd_partial_add / _finalize_add); None keeps the plain entries' calls."""
         tw = self.tw
+        if dy2 is not None:
+            ops.bn_bwd_partial_add(x, dy, dy2, R, self.C, self.mean, self.var, self.gamma(), self.beta(), relu6, self.ws, argmax, S)
+            _maybe_allreduce(self.ws, tw.pg)
+            ops.bn_bwd_finalize_add(x, dy, dy2, R, self.R_total, self.C, self.mean, self.var, self.gamma(), self.beta(), relu6,
+                                    self.ws, argmax, S, dx_f32, dx_bf16,
+                                    tw.store.g(self.scope + "/gamma"), tw.store.g(self.scope + "/beta"))
+            return
         ops.bn_bwd_partial(x, dy, R, self.C, self.mean, self.var, self.gamma(), self.beta(), relu6, self.ws, argmax, S)
         _maybe_allreduce(self.ws, tw.pg)
         ops.bn_bwd_finalize(x, dy, R, self.R_total, self.C, self.mean, self.var, self.gamma(), self.beta(), relu6,
@@ -555,10 +564,13 @@ class NetVladTower(TowerBase):
     no limit on the rows of a video; padding frames are never computed.  The two batch-norms in front of the aggregation take their
     statistics over the R live rows, the aggregation runs on evc_netvlad_aggregate_packed_fwd / _bwd.  Same weights and checkpoint
     names: a tower of either mode loads the other's checkpoint.  A forward-only grid tower (training=False) keeps no gradient store
-    or moments, runs on the moving statistics and serves batches of up to batch_size videos in the buffers it allocated."""
+    or moments, runs on the moving statistics and serves batches of up to batch_size videos in the buffers it allocated; its gather and
+    input_bn are one launch (evc_frames_gather_packed_bn).  `state` is h6 = relu6(hidden1_bn(hid)), what the MoE head
+    reads; backward(dstate=...) adds a gradient on it in front of that relu6's mask (serial distillation's L_REP)."""
 
     PRECISIONS = ("bf16",)             # no split-bf16 forward (set_precision refuses anything else)
     FRAME_MODES = ("sampled", "grid")
+    fused_input_pass = True            # forward-only grid towers: evc_frames_gather_packed_bn (False: the two launches, for A/B timing)
 
     CW, C2, HW = "cluster_weights", "cluster_weights2", "hidden1_weights"
     l2_names = (MoeHead.GATES, MoeHead.EXPERTS)
@@ -715,14 +727,23 @@ class NetVladTower(TowerBase):
             plan = _plan_grid_rows(self, num_frames, num_frames_host, None, "--netvlad_frames")
             R, Rp = plan.R, plan.Rp
             row_off = self.row_off[:B + 1]
+        # a forward-only grid tower knows input_bn's statistics before the batch (the moving ones): gather and batch norm in one
+        # launch, the same bits.  A training tower needs the batch statistics of r in between.
+        fused_in = grid and not self.training and not is_training and self.fused_input_pass
+        if fused_in:
+            bi.stats(None, R, False)
+            ops.frames_gather_packed_bn(x, num_frames, row_off, self.every_n, R, Rp, bi.mean, bi.var, bi.gamma(), bi.beta(), self.r, self.r_bn,
+                                        normalize=normalize)         # (rows R .. Rp of r_bn are zeros from the launch itself)
+        elif grid:
             ops.frames_gather_packed(x, num_frames, row_off, self.every_n, R, Rp, self.r, normalize=normalize)
         else:
             R = self.R
             ops.sample_frames_gather(x, uniform, num_frames, self.r, self.idx, normalize=normalize)
-        bi.stats(self.r, R, is_training)
-        ops.bn_apply(self.r, R, F, bi.mean, bi.var, bi.gamma(), bi.beta(), False, y_bf16=self.r_bn)
-        if grid and Rp > R:
-            self.r_bn[R:Rp].zero_()                          # (a longer earlier batch leaves stale rows there)
+        if not fused_in:
+            bi.stats(self.r, R, is_training)
+            ops.bn_apply(self.r, R, F, bi.mean, bi.var, bi.gamma(), bi.beta(), False, y_bf16=self.r_bn)
+            if grid and Rp > R:
+                self.r_bn[R:Rp].zero_()                      # (a longer earlier batch leaves stale rows there)
         ops.gemm_nt(self.r_bn, self.shadow_fwd[self.CW], R, K, F, self.act)
         bc.stats(self.act, R, is_training)
         ops.netvlad_softmax_fwd(self.act, R, K, bc.mean, bc.var, bc.gamma(), bc.beta(), self.a)
@@ -745,10 +766,14 @@ class NetVladTower(TowerBase):
         hidden = [self.HW, "hidden1_bn/beta", "hidden1_bn/gamma"]
         return moe, hidden, [k for k in self.names if k not in moe and k not in hidden]
 
-    def backward(self, dpred, on_moe_grads_ready=None, moe_weight_grads=True, on_stage=None):
+    def backward(self, dpred, on_moe_grads_ready=None, moe_weight_grads=True, on_stage=None, dstate=None):
+        """dstate (None or [B, H] f32): a gradient on `state` itself, added to the MoE head's d(h6) in front of the relu6 mask of
+        hidden1_bn's backward (BatchNorm.backward(dy2=...)); None keeps the plain launches."""
         assert self.training and self._taped, "backward needs a training-mode forward"
         B, F, S, K, H, R = self.B, self.F, self.S, self.Kc, self.Hd, self.R
         st, bi = self.store, self.bn_in
+        if dstate is not None and tuple(dstate.shape) != (B, H):
+            raise ValueError("dstate %s: the state of this tower is %s" % (tuple(dstate.shape), (B, H)))
         grid = self.frames == "grid"
         Rp = self.Rp if grid else R                          # row count of the TN product (grid: rows R .. Rp of its operands are zeros)
         dh6 = self.moe.backward(dpred, weight_grads=moe_weight_grads)
@@ -756,7 +781,10 @@ class NetVladTower(TowerBase):
             on_moe_grads_ready()
         if on_stage is not None:
             on_stage(0)
-        self.bn_h.backward(self.hid, dh6, B, True, dx_bf16=self.dhid_bf)
+        if dstate is None:
+            self.bn_h.backward(self.hid, dh6, B, True, dx_bf16=self.dhid_bf)
+        else:
+            self.bn_h.backward(self.hid, dh6, B, True, dx_bf16=self.dhid_bf, dy2=dstate)
         ops.gemm_tn(self.dhid_bf, self.Y_bf, H, K * F, self.Bk, st.g(self.HW))          # dWh^T [H][K*F]
         if on_stage is not None:
             on_stage(1)
@@ -781,6 +809,15 @@ class NetVladTower(TowerBase):
     @property
     def pred(self):
         return self.moe.pred if self.B == self.cap else self.moe.pred[:self.B]
+
+    @property
+    def state(self):
+        """The tower's representation, what its MoE head reads: h6 = relu6(hidden1_bn(hid)), [B, H] f32."""
+        return self.h6 if self.B == self.cap else self.h6[:self.B]
+
+    @property
+    def rowsum(self):
+        return self.moe.rowsum if self.B == self.cap else self.moe.rowsum[:self.B]
 
 
 def check_netvlad_frames(frames, every_n, max_frames, model=None, world=1, precision="bf16"):

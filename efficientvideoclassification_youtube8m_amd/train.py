@@ -25,7 +25,9 @@ small model, or a teacher next to the teaching assistants distilled from it (dis
 the train_finetune step with the loss section evc_distill_losses_sparse, no teacher tower in memory (distill.OfflineDistillGraph,
 DESIGN.md 7.11).
 ``--model NeXtVLADModel --nextvlad_frames grid --every_n N --teacher_dir DIR`` trains a grid student against the frozen grid teacher of
-DIR's latest checkpoint, which runs on the frames its checkpoint records (distill.NeXtVladDistillGraph).
+DIR's latest checkpoint, which runs on the frames its checkpoint records (distill.NeXtVladDistillGraph, DESIGN.md 7.14);
+``--model NetVLADModel --netvlad_frames grid --every_n N --teacher_dir DIR`` does the same for the NetVLAD family
+(distill.NetVladDistillGraph).
 Multi-GPU: launch with ``python -m torch.distributed.run --nproc-per-node N``;
 ``--gpu`` is then ignored in favour of LOCAL_RANK.
 """
@@ -41,7 +43,8 @@ import numpy as np
 import torch
 
 from . import eval_util, frame_level_models, losses, ops, readers, video_level_models
-from .distill import DistillGraph, EnsembleDistillGraph, NeXtVladDistillGraph, OfflineDistillGraph, SerialStudentsGraph, SingleTowerGraph
+from .distill import (DistillGraph, EnsembleDistillGraph, NetVladDistillGraph, NeXtVladDistillGraph, OfflineDistillGraph, SerialStudentsGraph,
+                      SingleTowerGraph)
 from .flags import FLAGS, GetListOfFeatureNamesAndSizes
 from .towers import DbofTower, LogisticTower, NetVladTower, NeXtVladTower, check_netvlad_frames, check_nextvlad_frames
 
@@ -445,6 +448,50 @@ def nextvlad_distill_source(feature_size):
     return dict(ck=ck, sd=sd, teacher_every_n=nextvlad_teacher_every_n(sd), resume=resume is not None)
 
 
+def netvlad_size_flags():
+    """The size flags of a NetVLAD tower, in the order of NetVladTower.variable_shapes (after the feature size and the classes)."""
+    return (FLAGS.netvlad_cluster_size, FLAGS.netvlad_hidden_size, FLAGS.moe_num_mixtures)
+
+
+def check_netvlad_distill_flags():
+    """--teacher_dir with --model NetVLADModel: the combinations it refuses, as ValueErrors that name the flags (no
+    device).  Returns True when the flags ask for it.  (--serial_student_dirs, --teacher_dirs and --teacher_preds_pattern refuse every
+    model but HierarchicalLstmModel themselves: they are not built for this family.  --teacher_only, --finetune, several ranks:
+    check_serial_flags; another --label_loss: check_label_loss; another --precision, --every_n out of range: check_netvlad_frames.)"""
+    if not FLAGS.teacher_dir or FLAGS.model != "NetVLADModel":
+        return False
+    if FLAGS.netvlad_frames != "grid":
+        raise ValueError("--teacher_dir %s with --model NetVLADModel and --netvlad_frames %s: the student of this family is a grid tower "
+                         "(--netvlad_frames grid --every_n N); distillation of sampled towers is not built" % (FLAGS.teacher_dir, FLAGS.netvlad_frames))
+    return True
+
+
+def netvlad_teacher_every_n(sd):
+    """The grid the model/* tower of the checkpoint dict ``sd`` runs on as a frozen teacher: the teacher_every_n a distillation
+    checkpoint records (its model/* IS such a teacher), else its every_n when it records netvlad_frames == "grid", else 1 - a sampled
+    checkpoint, whose weights load into a grid tower, sees every real frame."""
+    if sd.get("netvlad_frames") == "grid":
+        return int(sd["teacher_every_n"]) if "teacher_every_n" in sd else int(sd["every_n"])
+    return 1
+
+
+def netvlad_distill_source(feature_size):
+    """The checkpoint the frozen NetVLAD teacher comes from, read on the host before the device is touched: --train_dir's latest on
+    resume, else --teacher_dir's; its model/* variables against the size flags (distill.check_netvlad_checkpoint).  Returns {"ck", "sd",
+    "teacher_every_n", "resume"}."""
+    from .distill import check_netvlad_checkpoint
+    resume = None if FLAGS.start_new_model else latest_checkpoint(FLAGS.train_dir)
+    ck = resume or latest_checkpoint(FLAGS.teacher_dir)
+    if ck is None:
+        raise ValueError("--teacher_dir %s: no model.ckpt-*.pt checkpoint there" % FLAGS.teacher_dir)
+    sd = torch.load(ck, map_location="cpu")
+    what = "--teacher_dir %s: %s" % (FLAGS.teacher_dir, os.path.basename(ck))
+    if not any(k.startswith("model/") and torch.is_tensor(v) for k, v in sd.items()):
+        raise ValueError("%s holds no model/* variables (not a teacher checkpoint)" % what)
+    check_netvlad_checkpoint(sd, "model", feature_size, NUM_CLASSES, netvlad_size_flags(), what)
+    return dict(ck=ck, sd=sd, teacher_every_n=netvlad_teacher_every_n(sd), resume=resume is not None)
+
+
 def load_frozen_teacher(graph, teacher_dir):
     """The model/* variables of latest_checkpoint(teacher_dir) into the serial graph's frozen teacher.  Returns the checkpoint's path."""
     ck = latest_checkpoint(teacher_dir)
@@ -535,9 +582,19 @@ def build_graph(model, label_loss_fn, feature_size, batch_size, every_n, device,
                                     expansion=ex, gating_reduction=gr, num_mixtures=mx, device=device, precision=FLAGS.precision,
                                     distill_losses=FLAGS.distill_losses, dropout=check_nextvlad_dropout_flags(),
                                     dropout_seed=FLAGS.nextvlad_dropout_seed, **common)
+    if FLAGS.teacher_dir and isinstance(model, frame_level_models.NetVLADModel):
+        # the grid student against the frozen grid teacher; teacher_every_n: netvlad_teacher_every_n of its checkpoint
+        check_serial_flags(finetune)
+        check_netvlad_distill_flags()
+        check_netvlad_frames(FLAGS.netvlad_frames, every_n, FLAGS.max_num_frames, model=FLAGS.model, precision=FLAGS.precision)
+        common.pop("label_loss", None)            # (refused above for anything but CrossEntropyLoss, which the loss kernel has built in)
+        cs, hs, mx = netvlad_size_flags()
+        return NetVladDistillGraph(batch_size, every_n=every_n, teacher_every_n=teacher_every_n, feature_size=feature_size,
+                                   vocab_size=NUM_CLASSES, max_frames=FLAGS.max_num_frames, cluster_size=cs, hidden_size=hs,
+                                   num_mixtures=mx, device=device, precision=FLAGS.precision, distill_losses=FLAGS.distill_losses, **common)
     if FLAGS.teacher_dir:
-        raise ValueError("--teacher_dir %s: serial distillation is built for HierarchicalLstmModel and NeXtVLADModel, not %s" %
-                         (FLAGS.teacher_dir, type(model).__name__))
+        raise ValueError("--teacher_dir %s: serial distillation is built for HierarchicalLstmModel and NeXtVLADModel, not %s "
+                         "(and for NetVLADModel with --netvlad_frames grid)" % (FLAGS.teacher_dir, type(model).__name__))
     if isinstance(model, frame_level_models.DbofModel):
         tw = DbofTower(batch_size, FLAGS.max_num_frames, feature_size, NUM_CLASSES, FLAGS.iterations,
                        FLAGS.dbof_cluster_size, FLAGS.dbof_hidden_size, FLAGS.moe_num_mixtures, device=device,
@@ -649,6 +706,8 @@ def save_checkpoint(graph, train_dir, rank):
         sd["netvlad_frames" if isinstance(graph.tower, NetVladTower) else "nextvlad_frames"], sd["every_n"] = "grid", graph.tower.every_n
     if isinstance(graph, NeXtVladDistillGraph):   # metadata: the student's grid and the one the frozen teacher in model/* runs on
         sd["nextvlad_frames"], sd["every_n"], sd["teacher_every_n"] = "grid", graph.every_n, graph.teacher_every_n
+    if isinstance(graph, NetVladDistillGraph):    # the same for the NetVLAD family (distill_losses: recorded above, mode "serial")
+        sd["netvlad_frames"], sd["every_n"], sd["teacher_every_n"] = "grid", graph.every_n, graph.teacher_every_n
     sd.update(nextvlad_dropout_metadata(graph))   # metadata: --nextvlad_dropout and its seed, when the tower was trained with a non-zero rate
     fn = getattr(graph, "label_loss", None)
     if fn is not None and not losses.is_default(fn):            # metadata: the --label_loss these weights were trained on (the default: no key)
@@ -728,6 +787,8 @@ def main(argv=None):
     if nx_distill:
         # the teacher's checkpoint on the host - its grid and its shapes against the size flags -, before the device is touched
         nx_src = nextvlad_distill_source(sum(GetListOfFeatureNamesAndSizes(FLAGS.feature_names, FLAGS.feature_sizes)[1]))
+    elif serial and check_netvlad_distill_flags():
+        nx_src = netvlad_distill_source(sum(GetListOfFeatureNamesAndSizes(FLAGS.feature_names, FLAGS.feature_sizes)[1]))
     ens_sds = None
     if ens:
         # the teachers' checkpoints on the host, and - on resume - the recorded list against the flags: all before the device is touched
@@ -823,9 +884,9 @@ def main(argv=None):
     start, last_save, it = time.time(), time.time(), 0
     is_multi = isinstance(graph, SerialStudentsGraph)
     is_ens = isinstance(graph, EnsembleDistillGraph)
-    is_distill = isinstance(graph, (DistillGraph, NeXtVladDistillGraph)) or is_multi or is_ens
+    is_distill = isinstance(graph, (DistillGraph, NeXtVladDistillGraph, NetVladDistillGraph)) or is_multi or is_ens
     # --nextvlad_frames / --netvlad_frames grid (one tower, or the student and its frozen teacher): the packed rows are laid out from n_host
-    is_grid = getattr(getattr(graph, "tower", None), "frames", None) == "grid" or isinstance(graph, NeXtVladDistillGraph)
+    is_grid = getattr(getattr(graph, "tower", None), "frames", None) == "grid" or isinstance(graph, (NeXtVladDistillGraph, NetVladDistillGraph))
     steps_per_it = 2 if is_distill and not is_multi and graph.mode == "teacher_student" else 1
     copy_stream = torch.cuda.Stream(device=device)
     host_bufs = {}                       # pinned staging, two alternating sets (one may still be read while the next fills)

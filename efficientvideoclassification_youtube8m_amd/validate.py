@@ -31,7 +31,9 @@ records (--nextvlad_serve_every_n overrides); the graph is built for --train_dir
 Ensemble members and cascade stages take their family from their own checkpoints, so H-LSTM and NeXtVLAD members mix.
 ``--model NetVLADModel`` evaluates a NetVLAD checkpoint through distill.NetVladEvalGraph: model/* as a forward-only grid
 tower on the grid the checkpoint records, every real frame for a --netvlad_frames sampled one (--netvlad_serve_every_n overrides); its
-variables are checked against the size flags on the host first.  No ensemble or cascade serves this family.
+variables are checked against the size flags on the host first.  A --teacher_dir checkpoint of this family is evaluated
+as teacher + student: the student's metrics on the recorded every_n, student_loss logged against the teacher on the recorded
+teacher_every_n.  No ensemble or cascade serves this family.
 """
 from __future__ import annotations
 
@@ -96,7 +98,10 @@ def netvlad_every_n(state_dict, override=0, where="the checkpoint"):
 
 def netvlad_source(reader, student_only=False):
     """--model NetVLADModel: what is decided on the host, before the device is touched, from --train_dir's latest
-    checkpoint - its variables against the size flags, and the grid it records.  Returns {"ck", "sd", "every_n"}."""
+    checkpoint - its variables against the size flags, and the grid it records.  Returns {"ck", "sd", "tower", "every_n",
+    "teacher_every_n"}: tower 'both' for a distillation checkpoint (model/* and model_student/* - the student's metrics
+    at the recorded every_n, student_state_loss logged against the teacher at the recorded teacher_every_n), 'teacher' for a single-tower
+    one; --netvlad_serve_every_n overrides the served tower's grid only."""
     from .distill import check_netvlad_checkpoint
     if student_only:
         raise ValueError("eval_finetune with --model NetVLADModel: there is no convert / finetune step for this family, so no "
@@ -110,9 +115,13 @@ def netvlad_source(reader, student_only=False):
     if ck is None:
         raise IOError("unable to find a checkpoint at location: %s" % FLAGS.train_dir)
     sd = torch.load(ck, map_location="cpu")
-    check_netvlad_checkpoint(sd, "model", sum(reader.feature_sizes), reader.num_classes,
-                             (FLAGS.netvlad_cluster_size, FLAGS.netvlad_hidden_size, FLAGS.moe_num_mixtures), ck)
-    return dict(ck=ck, sd=sd, every_n=netvlad_every_n(sd, FLAGS.netvlad_serve_every_n, ck))
+    both = any(k.startswith("model_student/") and torch.is_tensor(v) for k, v in sd.items())
+    for scope in ("model", "model_student") if both else ("model",):
+        check_netvlad_checkpoint(sd, scope, sum(reader.feature_sizes), reader.num_classes,
+                                 (FLAGS.netvlad_cluster_size, FLAGS.netvlad_hidden_size, FLAGS.moe_num_mixtures), ck)
+    teacher_every_n = int(sd.get("teacher_every_n", 1)) if both else 1
+    return dict(ck=ck, sd=sd, tower="both" if both else "teacher", every_n=netvlad_every_n(sd, FLAGS.netvlad_serve_every_n, ck),
+                teacher_every_n=teacher_every_n)
 
 
 def build_graph(reader, model, batch_size, device, student_only=False, label_loss=None, nextvlad=None, netvlad=None):
@@ -124,7 +133,8 @@ def build_graph(reader, model, batch_size, device, student_only=False, label_los
         return NetVladEvalGraph(batch_size, every_n=src["every_n"], feature_size=sum(reader.feature_sizes), vocab_size=reader.num_classes,
                                 max_frames=FLAGS.max_num_frames, cluster_size=FLAGS.netvlad_cluster_size,
                                 hidden_size=FLAGS.netvlad_hidden_size, num_mixtures=FLAGS.moe_num_mixtures, device=device,
-                                precision=FLAGS.precision, label_loss=label_loss)
+                                precision=FLAGS.precision, label_loss=label_loss, tower=src.get("tower", "teacher"),
+                                teacher_every_n=src.get("teacher_every_n", 1))
     if isinstance(model, frame_level_models.NeXtVLADModel):
         from . import inference
         src = nextvlad if nextvlad is not None else nextvlad_source(reader, student_only)

@@ -703,6 +703,17 @@ int evc_bn_bwd_finalize(const float* x, const float* dy, int R, int R_total, int
                         const float* var, const float* gamma, const float* beta, int relu6,
                         const int32_t* argmax, int S, const double* ws, float* dx_f32, evc_bf16* dx_bf16,
                         float* dgamma, float* dbeta, void* stream);
+/* evc_bn_bwd_partial / evc_bn_bwd_finalize with the incoming gradient dy[i] + dy2[i] (dy2 [R][C]; one f32 add, in that order, in
+ * front of the relu6 mask, in both passes; everything behind it as above).  A second instantiation of the same two kernels: no extra
+ * pass or buffer.  dy2 == NULL: the launches and the bits of the plain entries.  dy2 with argmax (dy would be [R/S][C]) is
+ * EVC_ERR_BAD_ARG, nothing is launched.  Where a gradient on relu6(bn(x)) itself (dL_REP/dstate of a NetVLAD student)
+ * joins the one that arrives from the layer behind it. */
+int evc_bn_bwd_partial_add(const float* x, const float* dy, const float* dy2, int R, int C, const float* mean, const float* var,
+                           const float* gamma, const float* beta, int relu6, const int32_t* argmax, int S,
+                           double* ws /* 2*C, zeroed inside */, void* stream);
+int evc_bn_bwd_finalize_add(const float* x, const float* dy, const float* dy2, int R, int R_total, int C, const float* mean,
+                            const float* var, const float* gamma, const float* beta, int relu6, const int32_t* argmax, int S,
+                            const double* ws, float* dx_f32, evc_bf16* dx_bf16, float* dgamma, float* dbeta, void* stream);
 int evc_bn_relu6_bwd(const float* x, const float* dy, int R, int C, const float* mean, const float* var,
                      const float* gamma, const float* beta, int relu6, const int32_t* argmax, int S,
                      double* ws /* 2*C, zeroed inside */,
@@ -934,6 +945,14 @@ int evc_nextvlad_aggregate_packed_fwd_mfma(const float* a, const float* xe, cons
  * as bf16.  F % 4 == 0. */
 int evc_frames_gather_packed(const float* x, const uint8_t* x_u8, const int32_t* num_frames, const int32_t* row_off, int B, int T, int F,
                              int every_n, int R, int Rp, int normalize, float* out, evc_bf16* out_bf16, void* stream);
+/* evc_frames_gather_packed and the batch norm behind it in one launch, for a tower whose input statistics are known before the batch
+ * (the moving ones of a forward-only tower): out as above, and out_bn_bf16[row][f] =
+ * bf16((out[row][f] - mean[f]) * rsqrtf(var[f] + 1e-3f) * gamma[f] + beta[f]) with evc_bn_apply's expression - both outputs bit for
+ * bit those of evc_frames_gather_packed followed by evc_bn_apply(relu6 = 0).  Rows R .. Rp are zeros in BOTH outputs.  F % 4 == 0;
+ * x, out and the four vectors 16-byte aligned, x_u8 4-byte, out_bn_bf16 8-byte (EVC_ERR_BAD_ALIGN); every operand is required. */
+int evc_frames_gather_packed_bn(const float* x, const uint8_t* x_u8, const int32_t* num_frames, const int32_t* row_off, int B, int T, int F,
+                                int every_n, int R, int Rp, int normalize, const float* mean, const float* var, const float* gamma,
+                                const float* beta, float* out, evc_bf16* out_bn_bf16, void* stream);
 /* evc_frames_gather_packed over a subset of the batch's videos: packed video j < Bsel - the rows row_off[j] ..
  * row_off[j+1], row_off int32 [Bsel + 1] - reads the frames and the count of source video sel[j] of the unchanged batch (x / x_u8
  * [B][T][F], num_frames [B]; sel int32 [Bsel] on the device).  The same arithmetic, bit for bit; rows R .. Rp zeros.  out may be NULL
