@@ -43,7 +43,39 @@ struct GemmOperandsT {
   unsigned short seg_start[16] = {0}, seg_len[16] = {0};
 };
 
-__device__ __forceinline__ int tn_h(int row) { return (((row >> 3) & 1) << 2) | (row & 3); }
+__device__ __forceinline__ constexpr int tn_h(int row) { return (((row >> 3) & 1) << 2) | (row & 3); }
+
+// The transposing read as inline asm: through the builtin, hipcc's waitcnt pass sees an LDS read of unknown provenance
+// behind the LDS-DMA of the same K step and puts `s_waitcnt vmcnt(0)` in front of it - every K step then waited for the
+// DMA it had just issued (the whole ring's latency hiding gone; found in the ISA in round 2).  The asm has no memory
+// operand; its result is retired by the explicit lgkmcnt(0) of end_of_step() before the next step's MFMAs read it.
+// OFF: a compile-time byte offset in the instruction's 16-bit immediate - whatever of an address is constant costs no VALU add.
+template <int OFF>
+__device__ __forceinline__ s16x4 tn_tr(uint32_t lds_addr) {
+  static_assert(OFF >= 0 && OFF <= 0xffff, "ds_read offset: 16 bits");
+  s16x4 v;
+  if constexpr (OFF == 0) asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(lds_addr));
+  else asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(lds_addr), "n"(OFF));
+  return v;
+}
+
+// The LDS-DMA of the TN loop as a BUFFER load: address = descriptor base + per-lane offset (a VGPR that never changes) + the K walk in the
+// instruction's SCALAR offset, so a piece costs no VALU instruction (as a global load its 32-bit offset lane + walk was one v_add_u32 per
+// piece and K step on the staging waves).  Raw descriptor (stride 0) over the whole 32-bit offset range: the same 16 bytes per lane are read;
+// an offset beyond the range would read zeros instead of faulting.  (The host pass of hipcc has no buffer types: stubs there.)
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef __amdgpu_buffer_rsrc_t tn_rsrc_t;
+__device__ __forceinline__ tn_rsrc_t tn_make_rsrc(const void* base) {
+  return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, -1, 0x00020000);      // word 3, gfx9 raw buffer: 32-bit data format, no swizzle
+}
+__device__ __forceinline__ void tn_load_lds16(tn_rsrc_t r, char* lds_dst, uint32_t lane_off, uint32_t walk_off) {
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds_dst, 16, lane_off, walk_off, 0, 0);
+}
+#else
+struct tn_rsrc_t {};
+__device__ __forceinline__ tn_rsrc_t tn_make_rsrc(const void*) { return tn_rsrc_t{}; }
+__device__ __forceinline__ void tn_load_lds16(tn_rsrc_t, char*, uint32_t, uint32_t) {}
+#endif
 
 // SWAP = true issues the MFMA with the B fragment first: the accumulator tile is transposed - lane l holds
 // row (A column) m = l&15 and 4 consecutive columns n = (l>>4)*4 + reg (TileCoordsT) - so an epilogue that
@@ -63,7 +95,7 @@ __device__ __forceinline__ void gemm_mainloop_tn(const GemmOperandsT& p, const i
   for (int mi = 0; mi < Cfg::MI; ++mi)
 #pragma unroll
     for (int ni = 0; ni < Cfg::NI; ++ni) acc[mi][0][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int nk = p.nk;
+  const int nk = __builtin_amdgcn_readfirstlane(p.nk);   // (opaque: the caller's min() otherwise merges with the tail's into a VALU v_min3 per step)
   if (nk <= 0) return;                // (a second-segment tile whose whole walk is skipped: zeros)
 
   // ---- staging: chunk c = piece*64 + lane -> k row c / CPR, physical chunk c % CPR; piece q belongs to wave q % NPW ----
@@ -89,8 +121,7 @@ __device__ __forceinline__ void gemm_mainloop_tn(const GemmOperandsT& p, const i
     col = col + 8 <= p.N ? col : p.N - 8;
     b_vo[i] = (uint32_t)(((long)row * p.ldb + col) * 2);
   }
-  const char* const a_base = (const char*)p.A;
-  const char* const b_base = (const char*)p.B;
+  const tn_rsrc_t a_rsrc = tn_make_rsrc(p.A), b_rsrc = tn_make_rsrc(p.B);      // (tn_load_lds16: the K walk a_k / b_k is the scalar offset)
   const uint32_t a_step = (uint32_t)(64 * p.lda), b_step = (uint32_t)(64 * p.ldb);   // bytes per K step of 32 rows
   uint32_t a_k = 0, b_k = 0;
   int slot_issue = 0, slot_read = 0;
@@ -98,6 +129,8 @@ __device__ __forceinline__ void gemm_mainloop_tn(const GemmOperandsT& p, const i
   // SCALAR registers and is indexed by a chain of scalar selects - only when a segment ends (a uniform, rarely taken branch; a handful of
   // SALU instructions per step otherwise).  (A table in one vector register read with v_readlane was tried first: it was spilled, and its
   // reload inside the loop brought the `s_waitcnt vmcnt(0)` of DESIGN.md 4.2b back.)
+  // The readfirstlane at the set-up is what keeps them scalar: without it hipcc held the table, the segment index and with them a_k / b_k in
+  // vector registers and compiled the switch to v_cmp / v_cndmask chains (scripts/loop_mix.py shows it as VALU in the staging loops).
   uint32_t seg_e[16];
   int seg = 0, seg_left = 0;
   auto seg_entry = [&](int sidx) {
@@ -108,10 +141,10 @@ __device__ __forceinline__ void gemm_mainloop_tn(const GemmOperandsT& p, const i
   };
   if constexpr (SEG) {
 #pragma unroll
-    for (int i = 0; i < 16; ++i) seg_e[i] = ((uint32_t)p.seg_len[i] << 16) | (uint32_t)p.seg_start[i];
-    seg = p.seg0;
+    for (int i = 0; i < 16; ++i) seg_e[i] = __builtin_amdgcn_readfirstlane(((uint32_t)p.seg_len[i] << 16) | (uint32_t)p.seg_start[i]);
+    seg = __builtin_amdgcn_readfirstlane(p.seg0);
     const uint32_t e = seg_entry(seg);
-    seg_left = (int)(e >> 16) - p.seg_off0;
+    seg_left = __builtin_amdgcn_readfirstlane((int)(e >> 16) - p.seg_off0);
     a_k = ((e & 0xffffu) + (uint32_t)p.seg_off0) * a_step;
     b_k = ((e & 0xffffu) + (uint32_t)p.seg_off0) * b_step;
   }
@@ -119,8 +152,10 @@ __device__ __forceinline__ void gemm_mainloop_tn(const GemmOperandsT& p, const i
     if constexpr (SEG) {
       seg_left -= 1;
       if (__builtin_expect(seg_left == 0, 0)) {
+        uint32_t e = 0;                   // entry seg + 1, selected on seg itself (on seg + 1 hipcc forms the first compare from a VALU add's carry)
+#pragma unroll
+        for (int i = 1; i < 16; ++i) e = seg == i - 1 ? seg_e[i] : e;
         seg += 1;
-        const uint32_t e = seg_entry(seg);
         a_k = (e & 0xffffu) * a_step;
         b_k = (e & 0xffffu) * b_step;
         seg_left = (int)(e >> 16);
@@ -138,56 +173,54 @@ __device__ __forceinline__ void gemm_mainloop_tn(const GemmOperandsT& p, const i
     char* sbase = lds + slot_issue * Cfg::STAGE_BYTES;
 #pragma unroll
     for (int i = 0; i < ACH; ++i)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a_base + (a_vo[i] + a_k)),
-                                       (__attribute__((address_space(3))) void*)(sbase + ((wave % NPW) + i * NPW) * 1024), 16, 0, 0);
+      tn_load_lds16(a_rsrc, sbase + ((wave % NPW) + i * NPW) * 1024, a_vo[i], a_k);
 #pragma unroll
     for (int i = 0; i < BCH; ++i)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(b_base + (b_vo[i] + b_k)),
-                                       (__attribute__((address_space(3))) void*)(sbase + Cfg::A_BYTES + ((wave % NPW) + i * NPW) * 1024), 16, 0, 0);
+      tn_load_lds16(b_rsrc, sbase + Cfg::A_BYTES + ((wave % NPW) + i * NPW) * 1024, b_vo[i], b_k);
     advance();
     slot_issue = (slot_issue + 1 == Cfg::STAGES) ? 0 : slot_issue + 1;
   };
 
   // ---- fragment (transpose) read addresses within a stage ----
+  // One lane-offset register per fragment: the j = 0 address (B's with A_BYTES inside).  The j = 1 read is 4 k rows further on - r -> r + 4
+  // changes neither (r >> 3) & 1 nor r & 3, so tn_h(r) and with it the swizzled chunk stay - a constant 4 * ROWB bytes that rides in the
+  // read's 16-bit immediate (tn_tr<OFF>).  A K step then costs ONE VALU add per fragment (slot base + lane offset) instead of two to four.
   const int g = lane >> 4, q = (lane >> 2) & 3, pp = lane & 3;
-  int a_rd[Cfg::MI][2], b_rd[Cfg::NI][2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int r = 8 * g + 4 * j + q, hs = tn_h(r) << 1;
+  constexpr int A_J1 = 4 * AROWB, B_J1 = 4 * BROWB;
+  static_assert(tn_h(0) == tn_h(4) && tn_h(11) == tn_h(15), "j = 1 must keep the swizzle of j = 0");
+  static_assert(A_J1 % 8 == 0 && B_J1 % 8 == 0 && A_J1 <= 0xfff8 && B_J1 <= 0xfff8, "the j = 1 offset must fit the read's immediate");
+  uint32_t a_rd[Cfg::MI], b_rd[Cfg::NI];
+  {
+    const int r = 8 * g + q, hs = tn_h(r) << 1;
 #pragma unroll
     for (int mi = 0; mi < Cfg::MI; ++mi) {
       const int mc = wr * Cfg::WM + mi * 16;
-      a_rd[mi][j] = r * AROWB + ((((mc >> 3) + (pp >> 1)) ^ hs) << 4) + ((pp & 1) << 3);
+      a_rd[mi] = (uint32_t)(r * AROWB + ((((mc >> 3) + (pp >> 1)) ^ hs) << 4) + ((pp & 1) << 3));
     }
 #pragma unroll
     for (int ni = 0; ni < Cfg::NI; ++ni) {
       const int nc = wc * Cfg::WU + ni * 16;
-      b_rd[ni][j] = Cfg::A_BYTES + r * BROWB + ((((nc >> 3) + (pp >> 1)) ^ hs) << 4) + ((pp & 1) << 3);
+      b_rd[ni] = (uint32_t)(Cfg::A_BYTES + r * BROWB + ((((nc >> 3) + (pp >> 1)) ^ hs) << 4) + ((pp & 1) << 3));
     }
   }
-  // The transposing read as inline asm: through the builtin, hipcc's waitcnt pass sees an LDS read of unknown provenance
-  // behind the LDS-DMA of the same K step and puts `s_waitcnt vmcnt(0)` in front of it - every K step then waited for the
-  // DMA it had just issued (the whole ring's latency hiding gone; found in the ISA in round 2).  The asm has no memory
-  // operand; its result is retired by the explicit lgkmcnt(0) of end_of_step() before the next step's MFMAs read it.
-  auto tr = [&](const char* ptr) {
-    const uint32_t a = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) const char*)ptr);
-    s16x4 v;
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v) : "v"(a));
-    return v;
+  const uint32_t lds_rd = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) const char*)lds);    // the ring's LDS byte address
+  auto frag_a = [&](uint32_t sb, int mi) {      // both reads of a fragment from one address register: sb = byte address of the ring slot
+    const uint32_t a = sb + a_rd[mi];
+    const s16x4 lo = tn_tr<0>(a), hi = tn_tr<A_J1>(a);
+    return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+  };
+  auto frag_b = [&](uint32_t sb, int ni) {
+    const uint32_t a = sb + b_rd[ni];
+    const s16x4 lo = tn_tr<0>(a), hi = tn_tr<B_J1>(a);
+    return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
   };
   auto read_frags = [&](bf16x8 (&af)[Cfg::MI], bf16x8 (&bfr)[Cfg::NI]) {
-    const char* sb = lds + slot_read * Cfg::STAGE_BYTES;
+    const uint32_t sb = lds_rd + slot_read * Cfg::STAGE_BYTES;
     slot_read = (slot_read + 1 == Cfg::STAGES) ? 0 : slot_read + 1;
 #pragma unroll
-    for (int ni = 0; ni < Cfg::NI; ++ni) {
-      const s16x4 lo = tr(sb + b_rd[ni][0]), hi = tr(sb + b_rd[ni][1]);
-      bfr[ni] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    }
+    for (int ni = 0; ni < Cfg::NI; ++ni) bfr[ni] = frag_b(sb, ni);
 #pragma unroll
-    for (int mi = 0; mi < Cfg::MI; ++mi) {
-      const s16x4 lo = tr(sb + a_rd[mi][0]), hi = tr(sb + a_rd[mi][1]);
-      af[mi] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    }
+    for (int mi = 0; mi < Cfg::MI; ++mi) af[mi] = frag_a(sb, mi);
   };
   auto mfma_all = [&](const bf16x8 (&af)[Cfg::MI], const bf16x8 (&bfr)[Cfg::NI]) {
 #pragma unroll
@@ -230,7 +263,7 @@ __device__ __forceinline__ void gemm_mainloop_tn(const GemmOperandsT& p, const i
     if constexpr ((MODE & LOOP_NO_PRIO) == 0) __builtin_amdgcn_s_setprio(1);
     constexpr int NM = Cfg::MI * Cfg::NI, ND = PROD ? PER : 0, NF = Cfg::MI + Cfg::NI, NIT = ND + NF;
     char* sbase = lds + slot_issue * Cfg::STAGE_BYTES;
-    const char* sb = lds + slot_read * Cfg::STAGE_BYTES;
+    const uint32_t sb = lds_rd + slot_read * Cfg::STAGE_BYTES;
     slot_read = (slot_read + 1 == Cfg::STAGES) ? 0 : slot_read + 1;
 #pragma unroll
     for (int gi = 0; gi < NM; ++gi) {
@@ -238,19 +271,13 @@ __device__ __forceinline__ void gemm_mainloop_tn(const GemmOperandsT& p, const i
       for (int it = gi * NIT / NM; it < (gi + 1) * NIT / NM; ++it) {   // items of this group: LDS-DMA pieces first, then fragments
         if (it < ND) {
           if (it < ACH)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a_base + (a_vo[it] + a_k)),
-                                             (__attribute__((address_space(3))) void*)(sbase + ((wave % NPW) + it * NPW) * 1024), 16, 0, 0);
+            tn_load_lds16(a_rsrc, sbase + ((wave % NPW) + it * NPW) * 1024, a_vo[it], a_k);
           else
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(b_base + (b_vo[it - ACH] + b_k)),
-                                             (__attribute__((address_space(3))) void*)(sbase + Cfg::A_BYTES + ((wave % NPW) + (it - ACH) * NPW) * 1024), 16, 0, 0);
+            tn_load_lds16(b_rsrc, sbase + Cfg::A_BYTES + ((wave % NPW) + (it - ACH) * NPW) * 1024, b_vo[it - ACH], b_k);
         } else if (it - ND < Cfg::NI) {
-          const int f = it - ND;
-          const s16x4 lo = tr(sb + b_rd[f][0]), hi = tr(sb + b_rd[f][1]);
-          bfn[f] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+          bfn[it - ND] = frag_b(sb, it - ND);
         } else {
-          const int mi = it - ND - Cfg::NI;
-          const s16x4 lo = tr(sb + a_rd[mi][0]), hi = tr(sb + a_rd[mi][1]);
-          afn[mi] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+          afn[it - ND - Cfg::NI] = frag_a(sb, it - ND - Cfg::NI);
         }
       }
       const int mi = gi / Cfg::NI, ni = gi % Cfg::NI;
