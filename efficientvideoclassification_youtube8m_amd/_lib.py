@@ -136,6 +136,7 @@ SIGNATURES = {
     "evc_frames_gather_packed": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp],
     "evc_frames_gather_packed_bn": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp],
     "evc_frames_gather_packed_sel": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp],
+    "evc_frames_gather_packed_tab": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp],
     "evc_scatter_rows": [vp, i64, vp, i32, i32, i32, vp, i64, vp],
     "evc_nextvlad_normalize_fwd": [vp, i32, i32, i32, vp, vp, vp],
     "evc_nextvlad_normalize_bwd": [vp, vp, vp, i32, i32, i32, vp, vp],

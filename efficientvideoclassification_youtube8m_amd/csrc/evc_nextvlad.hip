@@ -8,6 +8,7 @@
 //   evc_nextvlad_aggregate_packed_fwd/bwd, evc_frames_gather_packed   the same over a ragged, packed list of frames per video (7.13)
 //   evc_frames_gather_packed_sel, evc_scatter_rows   serving a subset of the batch's videos: packed rows of the selected videos, and their
 //                                    result rows back to the batch's row numbers (7.15)
+//   evc_frames_gather_packed_tab     the packed rows of the frames a source-frame table names (--student_sampling on grid towers, 7.20)
 //   evc_nextvlad_aggregate_packed_fwd_mfma   the packed forward on the f32 matrix cores, for forward-only towers: the same bits (7.14)
 //   evc_nextvlad_normalize_fwd/bwd   U[b,k,:] = V[b,k,:] / max(|V[b,k,:]|, 1e-12)
 //   evc_nextvlad_gate_fwd/bwd        out = h * sigmoid(gl) (context gating); _bwd_add: with a second gradient on out (7.14)
@@ -709,6 +710,80 @@ extern "C" int evc_frames_gather_packed_sel(const float* x, const uint8_t* x_u8,
   if (Rp == 0) return EVC_OK;
   hipLaunchKernelGGL(frames_gather_packed_kernel<true>, dim3((unsigned)((Rp + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, x_u8, num_frames,
                      row_off, sel, Bsel, T, F, every_n, R, Rp, normalize, out, (uint2*)out_bf16);
+  EVC_LAUNCH_CHECK();
+  return EVC_OK;
+}
+// ---- the packed rows of frames that a table names (evc_frames_gather_packed_tab): row row_off[b] + j is frame
+// src[b][j] of video b, src [B][S] the source-frame table of evc_student_frame_select / _scored.  A kernel of its own next to
+// frames_gather_packed_kernel, whose instantiations stay what they were; the loads, sums and products are that kernel's in the same
+// order, so that a table holding j * every_n gives the grid gather's bits.  An entry outside 0 .. T - 1 (the tables' -1), a slot
+// j >= S (never read) and, for uint8 input, a frame >= num_frames[b] are exact zero rows and never an address.  Either output is
+// optional.  One wave per row, 16-byte loads and stores (8 bytes for the bf16 quarter); no LDS, no atomics.
+__global__ __launch_bounds__(256) void frames_gather_packed_tab_kernel(const float* __restrict__ x, const uint8_t* __restrict__ xq,
+                                                                       const int* __restrict__ nfr, const int* __restrict__ row_off,
+                                                                       const int* __restrict__ src, int B, int T, int F, int S, int R,
+                                                                       int Rp, int normalize, float* __restrict__ out,
+                                                                       uint2* __restrict__ out_bf) {
+  const int lane = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= Rp) return;
+  const int F4 = F >> 2;
+  float4* dst = out ? (float4*)(out + row * F) : nullptr;
+  uint2* dst_bf = out_bf ? out_bf + row * F4 : nullptr;
+  if (row >= R) {
+    for (int j = lane; j < F4; j += 64) {
+      if (dst) dst[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (dst_bf) dst_bf[j] = make_uint2(0u, 0u);
+    }
+    return;
+  }
+  int b = 0, hi = B;
+  while (hi - b > 1) {
+    const int mid = (b + hi) >> 1;
+    if (row_off[mid] <= (int)row) b = mid; else hi = mid;
+  }
+  const int slot = (int)row - row_off[b];
+  const int s = (slot >= 0 && slot < S) ? src[(long)b * S + slot] : -1;
+  const bool none = s < 0 || s >= T;
+  const int idx = none ? 0 : s;
+  const int n = nfr[b];
+  const bool padded = none || (xq && idx >= n);  // no frame, or uint8 padding (zero after Dequantize)
+  auto load = [&](int j) {
+    if (padded) return make_float4(0.f, 0.f, 0.f, 0.f);
+    if (xq) {
+      const uchar4 q = ((const uchar4*)(xq + ((long)b * T + idx) * F))[j];
+      const float sc = 4.0f / 255.0f, bi = 4.0f / 512.0f - 2.0f;
+      return make_float4(q.x * sc + bi, q.y * sc + bi, q.z * sc + bi, q.w * sc + bi);
+    }
+    return ((const float4*)(x + ((long)b * T + idx) * F))[j];
+  };
+  float inv = 1.f;
+  if (normalize) {
+    float ss = 0.f;
+    for (int j = lane; j < F4; j += 64) { const float4 v = load(j); ss += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w; }
+    inv = rsqrtf(fmaxf(wave_sum(ss), 1e-12f));
+  }
+  for (int j = lane; j < F4; j += 64) {
+    float4 v = load(j); v.x *= inv; v.y *= inv; v.z *= inv; v.w *= inv;
+    if (dst) dst[j] = v;
+    if (dst_bf) dst_bf[j] = make_uint2(pack_bf16x2_hw(v.x, v.y), pack_bf16x2_hw(v.z, v.w));
+  }
+}
+extern "C" int evc_frames_gather_packed_tab(const float* x, const uint8_t* x_u8, const int32_t* num_frames, const int32_t* row_off,
+                                            const int32_t* src, int B, int T, int F, int S, int R, int Rp, int normalize, float* out,
+                                            evc_bf16* out_bf16, void* stream) {
+  EVC_REQUIRE(B > 0 && T > 0 && F > 0 && F % 4 == 0 && S >= 1 && R >= 0 && Rp >= R && Rp - R < 32 && (long)R <= (long)B * S,
+              EVC_ERR_BAD_SHAPE, "evc_frames_gather_packed_tab: needs F %% 4 == 0, S >= 1, R <= B * S, R <= Rp < R + 32 "
+              "(B=%d T=%d F=%d S=%d R=%d Rp=%d)", B, T, F, S, R, Rp);
+  EVC_REQUIRE((x != nullptr) != (x_u8 != nullptr), EVC_ERR_BAD_ARG, "evc_frames_gather_packed_tab: exactly one of x / x_u8");
+  EVC_REQUIRE(num_frames && row_off && src && (out || out_bf16), EVC_ERR_BAD_ARG,
+              "evc_frames_gather_packed_tab: NULL operand (num_frames, row_off, src, and at least one of out / out_bf16)");
+  EVC_REQUIRE(nx_aligned16(x) && ((uintptr_t)x_u8 % 4) == 0 && nx_aligned16(out) && ((uintptr_t)out_bf16 % 8) == 0 &&
+              ((uintptr_t)src % 4) == 0 && ((uintptr_t)num_frames % 4) == 0 && ((uintptr_t)row_off % 4) == 0, EVC_ERR_BAD_ALIGN,
+              "evc_frames_gather_packed_tab: misaligned operand (float4 / uchar4 / 8-byte bf16 / int32 access)");
+  if (Rp == 0) return EVC_OK;
+  hipLaunchKernelGGL(frames_gather_packed_tab_kernel, dim3((unsigned)((Rp + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, x_u8, num_frames,
+                     row_off, src, B, T, F, S, R, Rp, normalize, out, (uint2*)out_bf16);
   EVC_LAUNCH_CHECK();
   return EVC_OK;
 }

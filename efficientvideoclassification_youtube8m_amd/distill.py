@@ -1564,6 +1564,8 @@ class SingleTowerGraph(_StepGraph):
                              "allowed under data parallelism: drop the remainder)" % (B, tw.B))
         # (a NeXtVLAD tower's dropout mask is a function of the step: a restored run draws the same masks)
         kw = {"dropout_step": self.global_step} if isinstance(tw, NeXtVladTower) else {}
+        if isinstance(tw, NetVladTower) and tw.sampling != "uniform":
+            kw = {"draw": self.global_step, "row0": 0}       # ("random" frames are a function of the step too)
         if isinstance(tw, (NetVladTower, NeXtVladTower)) and tw.frames == "grid":
             pred = tw.forward(x_raw, num_frames, num_frames_host=num_frames_host, **kw)
         elif isinstance(tw, (DbofTower, NetVladTower, NeXtVladTower, DbofGenericTower)):
@@ -1890,7 +1892,12 @@ class NetVladDistillGraph(_StepGraph):
     towers' h6 = relu6(hidden1_bn(hid)) and predictions, the same scales), the student's backward with dL_REP/dstate joining the MoE
     head's gradient in front of hidden1_bn's relu6 mask, and the update exactly as SingleTowerGraph.step performs it; global_step += 1.
     Reporting follows DistillGraph's serial mode (`out` keys, LOSS_SLOTS, loss_report), so train's loop needs no special case.  Every
-    refusal is a ValueError before the device is touched."""
+    refusal is a ValueError before the device is touched.
+
+    student_sampling / sampling_seed: the --student_sampling word of the STUDENT, "random" drawn with draw =
+    global_step and row0 = 0.  teacher_sampling / teacher_sampling_seed: what the frozen teacher's checkpoint records when that tower was
+    itself trained on selected frames; it runs on them with draw 0, as evaluation does.  Under a scored word the batch's
+    ops.frame_change_keys are computed once and handed to both towers."""
 
     LOSS_SLOTS = DistillGraph.LOSS_SLOTS
     DISTILL_LOSSES = DistillGraph.DISTILL_LOSSES
@@ -1901,8 +1908,11 @@ class NetVladDistillGraph(_StepGraph):
     def __init__(self, batch_size, every_n=10, teacher_every_n=1, feature_size=1152, vocab_size=4716, max_frames=300, cluster_size=64,
                  hidden_size=1024, num_mixtures=2, base_learning_rate=0.001, learning_rate_decay=1.0,
                  learning_rate_decay_examples=4000000, regularization_penalty=2.0, clip_gradient_norm=1.0, count_rep_twice=True,
-                 device="cuda:0", seed=7, process_group=None, precision="bf16", distill_losses=DISTILL_LOSSES, label_loss=None):
+                 device="cuda:0", seed=7, process_group=None, precision="bf16", distill_losses=DISTILL_LOSSES, label_loss=None,
+                 student_sampling="uniform", sampling_seed=0, teacher_sampling="uniform", teacher_sampling_seed=0):
         from .towers import NetVladTower, check_netvlad_frames
+        self.student_sampling, self.sampling_seed = ops.check_student_sampling(student_sampling, "--student_sampling"), int(sampling_seed)
+        self.teacher_sampling, self.teacher_sampling_seed = ops.check_student_sampling(teacher_sampling, "teacher_sampling"), int(teacher_sampling_seed)
         self.world = _world_of(process_group)
         if self.world > 1:
             raise ValueError("NetVladDistillGraph is not data parallel (process group of %d ranks): train the student against the "
@@ -1914,8 +1924,8 @@ class NetVladDistillGraph(_StepGraph):
         if precision != "bf16":
             raise ValueError("NetVladDistillGraph: precision %r is refused, the NetVLAD tower has no such forward mode (bf16 only)" % (precision,))
         self.distill_losses = check_distill_losses(distill_losses)
-        for n in (every_n, teacher_every_n):     # (ValueError naming --every_n and its range)
-            check_netvlad_frames("grid", n, max_frames, world=self.world, precision=precision)
+        for n, w in ((every_n, self.student_sampling), (teacher_every_n, self.teacher_sampling)):     # (ValueError naming --every_n and its range)
+            check_netvlad_frames("grid", n, max_frames, world=self.world, precision=precision, sampling=w)
         self.B, self.every_n, self.teacher_every_n, self.precision = batch_size, int(every_n), int(teacher_every_n), precision
         self.lr0, self.lr_decay, self.lr_decay_examples = base_learning_rate, learning_rate_decay, learning_rate_decay_examples
         self.reg_pen, self.clip, self.pg = regularization_penalty, clip_gradient_norm, process_group
@@ -1924,9 +1934,9 @@ class NetVladDistillGraph(_StepGraph):
         self.global_step = 0
         sizes = (batch_size, max_frames, feature_size, vocab_size, 30, cluster_size, hidden_size, num_mixtures)
         self.teacher = NetVladTower(*sizes, device=device, training=False, scope="model", seed=seed, frames="grid",
-                                    every_n=self.teacher_every_n)
+                                    every_n=self.teacher_every_n, sampling=self.teacher_sampling, sampling_seed=self.teacher_sampling_seed)
         self.student = NetVladTower(*sizes, device=device, training=True, scope="model_student", seed=seed + 1, frames="grid",
-                                    every_n=self.every_n)
+                                    every_n=self.every_n, sampling=self.student_sampling, sampling_seed=self.sampling_seed)
         self.moe = self.student.moe
         self.fused_moe_update = True
         self.losses = torch.zeros(8, dtype=F32, device=self.device)
@@ -1970,8 +1980,14 @@ class NetVladDistillGraph(_StepGraph):
         if self._dp_s is None or self._dp_s.shape[0] != B:
             self._dp_s = torch.empty((B, V), dtype=F32, device=self.device)
             self._ds_s = torch.empty((B, ts.Hd), dtype=F32, device=self.device)
-        t_pred = tt.forward(x_raw, num_frames, num_frames_host=num_frames_host, is_training=False)
-        s_pred = ts.forward(x_raw, num_frames, num_frames_host=num_frames_host)
+        tkw, skw = {}, {}
+        if self.student_sampling != "uniform" or self.teacher_sampling != "uniform":      # (uniform: today's calls)
+            scored = ops.STUDENT_SAMPLING_SCORED
+            keys = ops.frame_change_keys(x_raw, num_frames) if (self.student_sampling in scored or self.teacher_sampling in scored) else None
+            tkw = dict(keys=keys, draw=0, row0=0)
+            skw = dict(keys=keys, draw=self.global_step, row0=0)
+        t_pred = tt.forward(x_raw, num_frames, num_frames_host=num_frames_host, is_training=False, **tkw)
+        s_pred = ts.forward(x_raw, num_frames, num_frames_host=num_frames_host, **skw)
         on = self.distill_losses
         self.losses.zero_()
         ops.distill_losses(t_pred, tt.rowsum, s_pred, ts.rowsum, labels_u8, tt.state, ts.state, self.losses, self._dp_s, self._ds_s,
@@ -2004,18 +2020,27 @@ class NetVladEvalGraph(_StepGraph):
     model_student, the same) or 'both' (the student served at every_n, the teacher run too at teacher_every_n: validate's
     student_state_loss).  Forward-only grid towers (training=False: the moving statistics), bf16 only, on the caller's stream.  No row
     compaction: a video without a frame runs through the head with V = 0 like any other and its row holds what the head makes of that.
-    The buffers are allocated once at batch_size: a shorter batch allocates nothing."""
+    The buffers are allocated once at batch_size: a shorter batch allocates nothing.
+
+    student_sampling / sampling_seed: the --student_sampling word the SERVED tower runs on (the student, or the teacher
+    when it is the only tower), as EvalGraph serves its student on the flag; "random" is drawn with draw 0 and row0 0, the same frames
+    for the same batching.  With tower='both' the teacher runs on teacher_sampling / teacher_sampling_seed, what its checkpoint records."""
 
     family = "netvlad"
     student_sampling = "uniform"
 
     def __init__(self, batch_size, every_n=1, feature_size=1152, vocab_size=4716, max_frames=300, cluster_size=64, hidden_size=1024,
-                 num_mixtures=2, device="cuda:0", precision="bf16", label_loss=None, seed=7, tower="teacher", teacher_every_n=1):
+                 num_mixtures=2, device="cuda:0", precision="bf16", label_loss=None, seed=7, tower="teacher", teacher_every_n=1,
+                 student_sampling="uniform", sampling_seed=0, teacher_sampling="uniform", teacher_sampling_seed=0):
         from .towers import NetVladTower, check_netvlad_frames
         if tower not in ("teacher", "student", "both"):
             raise ValueError("NetVladEvalGraph: tower %r (teacher | student | both)" % (tower,))
-        for n in [every_n] + ([teacher_every_n] if tower == "both" else []):
-            check_netvlad_frames("grid", n, max_frames, precision=precision)         # (before the device is touched)
+        self.student_sampling, self.sampling_seed = ops.check_student_sampling(student_sampling, "--student_sampling"), int(sampling_seed)
+        if tower != "both":
+            teacher_sampling, teacher_sampling_seed = student_sampling, sampling_seed      # (the one tower is the served one)
+        self.teacher_sampling, self.teacher_sampling_seed = ops.check_student_sampling(teacher_sampling, "teacher_sampling"), int(teacher_sampling_seed)
+        for n, w in [(every_n, self.student_sampling)] + ([(teacher_every_n, self.teacher_sampling)] if tower == "both" else []):
+            check_netvlad_frames("grid", n, max_frames, precision=precision, sampling=w)         # (before the device is touched)
         self.label_loss = _resolve_label_loss(label_loss, vocab_size)
         self.tower, self.every_n, self.teacher_every_n = tower, int(every_n), int(teacher_every_n if tower == "both" else every_n)
         self.batch_size, self.max_frames, self.precision = batch_size, max_frames, precision
@@ -2026,10 +2051,10 @@ class NetVladEvalGraph(_StepGraph):
         self.teacher = self.student = None
         if tower != "student":
             self.teacher = NetVladTower(*args, device=device, training=False, scope="model", seed=seed, frames="grid",
-                                        every_n=self.teacher_every_n)
+                                        every_n=self.teacher_every_n, sampling=self.teacher_sampling, sampling_seed=self.teacher_sampling_seed)
         if tower != "teacher":
             self.student = NetVladTower(*args, device=device, training=False, scope="model_student", seed=seed + 1, frames="grid",
-                                        every_n=self.every_n)
+                                        every_n=self.every_n, sampling=self.student_sampling, sampling_seed=self.sampling_seed)
         self.losses = torch.zeros(2 if tower == "both" else 1, dtype=F32, device=self.device)
 
     def _towers(self):
@@ -2044,7 +2069,8 @@ class NetVladEvalGraph(_StepGraph):
 
     def step(self, x_raw, labels_u8, num_frames, num_frames_host=None, keys=None):
         """x_raw [b, T, F] uint8 or float32, b <= batch_size; labels_u8 [b, V]; num_frames [b] int32 (num_frames_host: the same counts
-        on the host; read back from the device when not given).  keys is EvalGraph's argument and is not read."""
+        on the host; read back from the device when not given).  keys is EvalGraph's argument: the batch's ops.frame_change_keys, read
+        under a scored word alone (computed here, once, when not given)."""
         b = int(x_raw.shape[0])
         if b > self.batch_size:
             raise ValueError("NetVladEvalGraph: a batch of %d videos, the graph was built for %d" % (b, self.batch_size))
@@ -2052,12 +2078,17 @@ class NetVladEvalGraph(_StepGraph):
             num_frames_host = num_frames.cpu()
         nh = np.asarray(num_frames_host, dtype=np.int64).reshape(-1)
         out = {}
+        kw = {}
+        if keys is None and any(tw.sampling in ops.STUDENT_SAMPLING_SCORED for tw in self._towers()):
+            keys = ops.frame_change_keys(x_raw, num_frames)
+        if any(tw.sampling != "uniform" for tw in self._towers()):
+            kw = dict(keys=keys, draw=0, row0=0)
         if self.teacher is not None:
-            pred = t_pred = self.teacher.forward(x_raw, num_frames, is_training=False, num_frames_host=nh)
+            pred = t_pred = self.teacher.forward(x_raw, num_frames, is_training=False, num_frames_host=nh, **kw)
             if self.tower == "both":
                 out.update(teacher_predictions=t_pred, teacher_state=self.teacher.state)
         if self.student is not None:
-            pred = self.student.forward(x_raw, num_frames, is_training=False, num_frames_host=nh)
+            pred = self.student.forward(x_raw, num_frames, is_training=False, num_frames_host=nh, **kw)
             out["student_state"] = self.student.state
         served = self.student if self.student is not None else self.teacher
         self.losses.zero_()

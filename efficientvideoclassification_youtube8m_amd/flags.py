@@ -177,7 +177,9 @@ _define("student_sampling", "uniform", _sampling, "uniform|first|middle|last|fir
         "segment_change choose by content: every raw frame is scored on the device by its squared change from the frame before it "
         "(ops.frame_change_keys; the first frame counts as the largest change), and the student sees the k frames of largest change, or of "
         "each of k equal segments of the video the one of largest change; both read every live frame of the batch once more.  Checkpoints "
-        "record the word; validate / inference warn when the flag disagrees with it, and the flag wins")
+        "record the word; validate / inference warn when the flag disagrees with it, and the flag wins.  --model NetVLADModel "
+        "--netvlad_frames grid: the tower - alone, as --teacher_dir's student, or served by validate - runs on the selected frames "
+        "(DESIGN.md 7.20); a sampled NetVLAD tower draws its frames, ignores the word and warns; NeXtVLADModel refuses the words")
 _define("student_sampling_seed", 0, int, "seed of --student_sampling random")
 _define("ensemble_sampling", "", str, "one --student_sampling word per member (ignored for teachers); '' = --student_sampling for all")
 # ---- serial distillation (train): the student against a finished, frozen teacher -----------------------------------------------------------

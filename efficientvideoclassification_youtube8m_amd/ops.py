@@ -1586,6 +1586,50 @@ def frames_gather_packed_sel(x, num_frames, row_off, sel, every_n, R, Rp, out=No
               T, F, every_n, R, Rp, 1 if normalize else 0, _p(out), _p(out_bf16), _stream())
 
 
+SELECT_MAX_T = 1024     # the frames per video the source-frame tables hold (evc_student_frame_select, evc_student_frame_select_scored)
+
+
+class SelectPlan:
+    """GridPlan's fields for the packed rows of frames a source-frame table names: video b contributes the k[b] frames in
+    the first k[b] slots of its table row, as the rows row_off[b] .. row_off[b+1].  The counts are the table kernels' own
+    (evc_student_frame_select, _scored; host_frame_counts(subsampled=True)): n_b clipped to 0 .. T, k[b] = trunc(float64(n_b) / T * S)
+    with S = T // every_n - the frames an H-LSTM student with the same word and every_n sees.  That can be one fewer than GridPlan's
+    ceil(n_b / every_n), and it is 0 for a video shorter than every_n.  B * S is at most grid_capacity(B, T, every_n)."""
+
+    def __init__(self, num_frames_host, every_n, max_frames):
+        import numpy as np
+        every_n, T = int(every_n), int(max_frames)
+        if every_n < 1 or every_n > T:
+            raise ValueError("every_n=%d must lie in 1 .. max_num_frames=%d" % (every_n, T))
+        if T > SELECT_MAX_T:
+            raise ValueError("max_num_frames=%d: the source-frame tables hold at most %d frames per video" % (T, SELECT_MAX_T))
+        self.S = T // every_n
+        n = np.clip(np.asarray(num_frames_host).reshape(-1).astype(np.int64), 0, T)
+        k = np.trunc(n.astype(np.float64) / float(T) * float(self.S)).astype(np.int64)
+        self.every_n, self.B = every_n, int(n.shape[0])
+        self.k = k.astype(np.int32)
+        self.row_off = np.zeros(self.B + 1, np.int32)
+        np.cumsum(k, out=self.row_off[1:])
+        self.R = int(self.row_off[-1])
+        self.Rp = round_up(self.R, 32)
+        self.max_k = int(k.max()) if self.B else 0
+
+
+def frames_gather_packed_tab(x, num_frames, row_off, src, R, Rp, out=None, out_bf16=None, normalize=False):
+    """frames_gather_packed on the frames a table names (evc_frames_gather_packed_tab): row row_off[b] + j = frame
+    src[b, j] of video b; src device int32 [B, S] (student_frame_select / student_frame_select_scored), an entry outside 0 .. T - 1
+    - and for uint8 input one >= num_frames[b] - a zero row.  row_off: device int32 [B+1] (SelectPlan.row_off).  out (f32) or out_bf16
+    may be None, not both; rows R .. Rp zeros."""
+    B, T, F = x.shape
+    is_u8 = x.dtype == torch.uint8
+    assert x.is_contiguous() and src.dtype == torch.int32 and src.is_contiguous() and src.dim() == 2 and src.shape[0] == B
+    assert out is None or (out.is_contiguous() and out.dtype == F32 and out.shape[0] >= Rp and out.shape[1] == F)
+    assert out_bf16 is None or (out_bf16.is_contiguous() and out_bf16.dtype == BF16 and out_bf16.shape[0] >= Rp and out_bf16.shape[1] == F)
+    assert row_off.dtype == torch.int32 and row_off.numel() == B + 1 and num_frames.dtype == torch.int32 and num_frames.numel() == B
+    _lib.call("evc_frames_gather_packed_tab", None if is_u8 else _p(x), _p(x) if is_u8 else None, _p(num_frames), _p(row_off), _p(src), B, T, F,
+              src.shape[1], R, Rp, 1 if normalize else 0, _p(out), _p(out_bf16), _stream())
+
+
 def scatter_rows(src, sel, dst):
     """dst[sel[j]] = src[j] for the rows of src (2-D f32, rows contiguous, any row stride); the other rows of dst keep their contents.
     sel: device int32 [src.shape[0]], accepted by check_row_selection(sel, dst.shape[0]) on the host before this call."""

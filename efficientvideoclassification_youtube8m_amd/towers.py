@@ -521,15 +521,16 @@ class DbofGenericTower(TowerBase):
         return self.moe.pred
 
 
-def _plan_grid_rows(tw, num_frames, num_frames_host, sel=None, flag="--nextvlad_frames"):
+def _plan_grid_rows(tw, num_frames, num_frames_host, sel=None, flag="--nextvlad_frames", select=False):
     """Grid mode of a tower (NeXtVLAD, NetVLAD): this batch's packed layout from the HOST frame counts (launch sizes and offsets without
     a device sync); row_off goes up through one of two pinned buffers, reused only once its earlier copy has completed.  sel (int32
-    numpy, accepted by ops.check_row_selection): the layout of those videos alone, and sel itself goes up the same way."""
+    numpy, accepted by ops.check_row_selection): the layout of those videos alone, and sel itself goes up the same way.  select: the
+    counts of a source-frame table (ops.SelectPlan) in place of the grid's."""
     if num_frames_host is None:
         num_frames_host = num_frames.cpu().numpy()       # an explicit device sync: callers that have the counts on the host pass them
     if sel is not None:
         num_frames_host = np.asarray(num_frames_host).reshape(-1)[sel]
-    plan = ops.GridPlan(num_frames_host, tw.every_n, tw.T)
+    plan = (ops.SelectPlan if select else ops.GridPlan)(num_frames_host, tw.every_n, tw.T)
     if plan.B != tw.B:
         raise ValueError("num_frames_host holds %d videos, the batch %d" % (plan.B, tw.B))
     if plan.R == 0:
@@ -566,11 +567,16 @@ class NetVladTower(TowerBase):
     names: a tower of either mode loads the other's checkpoint.  A forward-only grid tower (training=False) keeps no gradient store
     or moments, runs on the moving statistics and serves batches of up to batch_size videos in the buffers it allocated; its gather and
     input_bn are one launch (evc_frames_gather_packed_bn).  `state` is h6 = relu6(hidden1_bn(hid)), what the MoE head
-    reads; backward(dstate=...) adds a gradient on it in front of that relu6's mask (serial distillation's L_REP)."""
+    reads; backward(dstate=...) adds a gradient on it in front of that relu6's mask (serial distillation's L_REP).
+
+    sampling (grid mode): a word of ops.STUDENT_SAMPLING / STUDENT_SAMPLING_SCORED.  Off "uniform" video b contributes the
+    k_b = trunc(n_b / T * (T // every_n)) frames the word selects (ops.SelectPlan: the H-LSTM student's count, at most the grid's) - their
+    table built on the device per batch (kept as last_frame_table), one gather that reads it (evc_frames_gather_packed_tab), everything
+    behind the gather unchanged.  "random" draws from (sampling_seed, draw, row0 + b), forward's arguments."""
 
     PRECISIONS = ("bf16",)             # no split-bf16 forward (set_precision refuses anything else)
     FRAME_MODES = ("sampled", "grid")
-    fused_input_pass = True            # forward-only grid towers: evc_frames_gather_packed_bn (False: the two launches, for A/B timing)
+    fused_input_pass = True           # forward-only grid towers: evc_frames_gather_packed_bn (False: the two launches, for A/B timing)
 
     CW, C2, HW = "cluster_weights", "cluster_weights2", "hidden1_weights"
     l2_names = (MoeHead.GATES, MoeHead.EXPERTS)
@@ -579,12 +585,14 @@ class NetVladTower(TowerBase):
 
     def __init__(self, batch_size, max_frames=300, feature_size=1152, vocab_size=4716, iterations=30, cluster_size=64,
                  hidden_size=1024, num_mixtures=2, device="cuda:0", training=True, scope="model", seed=0, process_group=None,
-                 frames="sampled", every_n=1):
+                 frames="sampled", every_n=1, sampling="uniform", sampling_seed=0):
         world = 1
         if process_group is not None and torch.distributed.is_available() and torch.distributed.is_initialized():
             world = torch.distributed.get_world_size(process_group)
-        check_netvlad_frames(frames, every_n, max_frames, world=world)           # (before the device is touched)
+        check_netvlad_frames(frames, every_n, max_frames, world=world, sampling=sampling)   # (before the device is touched)
         self.frames, self.every_n = frames, int(every_n)
+        self.sampling, self.sampling_seed = sampling, int(sampling_seed)
+        self.last_frame_table = None       # the source-frame table of the last batch (sampling != "uniform"), for tests and diagnostics
         self.device, self.training, self.scope, self.pg = torch.device(device), training, scope, process_group
         self.T, self.F, self.V, self.S = max_frames, feature_size, vocab_size, iterations
         self.Kc, self.Hd, self.Mx = cluster_size, hidden_size, num_mixtures
@@ -706,12 +714,14 @@ class NetVladTower(TowerBase):
             if grid:
                 self.agg_ws = torch.empty(ops.netvlad_aggregate_packed_bwd_ws(B, K, F), dtype=F32, device=dev)
 
-    def forward(self, x, num_frames, uniform=None, normalize=True, is_training=True, num_frames_host=None):
+    def forward(self, x, num_frames, uniform=None, normalize=True, is_training=True, num_frames_host=None, keys=None, draw=0, row0=0):
         """x [B,T,F] float32 or uint8 raw frames; uniform [B,S] f32 in [0,1): the frame-sampling draw (sampled mode; not read in grid
         mode, which takes num_frames_host, the frame counts on the host, instead).  A forward-only grid tower keeps the buffers it
-        allocated: a batch of fewer videos uses their first rows."""
+        allocated: a batch of fewer videos uses their first rows.  keys / draw / row0 are read by a tower with a sampling word alone:
+        the batch's ops.frame_change_keys where the caller has them (scored words), and the draw of "random"."""
         B = x.shape[0]
         grid = self.frames == "grid"
+        select = grid and self.sampling != "uniform"
         if B != self.B:
             if grid and not self.training and B <= self.cap:
                 self.B = B
@@ -724,13 +734,25 @@ class NetVladTower(TowerBase):
         if grid:
             if x.shape[1] != self.T:
                 raise ValueError("the batch holds %d frames per video, the tower was built for max_frames=%d" % (x.shape[1], self.T))
-            plan = _plan_grid_rows(self, num_frames, num_frames_host, None, "--netvlad_frames")
+            if select:
+                # the frames of a --student_sampling word: their table on this stream, as distill.input_views builds it
+                if self.sampling in ops.STUDENT_SAMPLING_SCORED:
+                    if keys is None:
+                        keys = ops.frame_change_keys(x, num_frames)
+                    src = ops.student_frame_select_scored(num_frames, keys, self.T, self.every_n, self.sampling)
+                else:
+                    src = ops.student_frame_select(num_frames, self.T, self.every_n, self.sampling, seed=self.sampling_seed, draw=draw, row0=row0)
+                self.last_frame_table = src
+            plan = _plan_grid_rows(self, num_frames, num_frames_host, None, "--netvlad_frames", select=select)
             R, Rp = plan.R, plan.Rp
             row_off = self.row_off[:B + 1]
         # a forward-only grid tower knows input_bn's statistics before the batch (the moving ones): gather and batch norm in one
-        # launch, the same bits.  A training tower needs the batch statistics of r in between.
-        fused_in = grid and not self.training and not is_training and self.fused_input_pass
-        if fused_in:
+        # launch, the same bits.  A training tower needs the batch statistics of r in between; a tower on selected
+        # frames has a tenth of the rows and takes the two launches (7.20).
+        fused_in = grid and not select and not self.training and not is_training and self.fused_input_pass
+        if select:
+            ops.frames_gather_packed_tab(x, num_frames, row_off, src, R, Rp, self.r, normalize=normalize)
+        elif fused_in:
             bi.stats(None, R, False)
             ops.frames_gather_packed_bn(x, num_frames, row_off, self.every_n, R, Rp, bi.mean, bi.var, bi.gamma(), bi.beta(), self.r, self.r_bn,
                                         normalize=normalize)         # (rows R .. Rp of r_bn are zeros from the launch itself)
@@ -820,12 +842,19 @@ class NetVladTower(TowerBase):
         return self.moe.rowsum if self.B == self.cap else self.moe.rowsum[:self.B]
 
 
-def check_netvlad_frames(frames, every_n, max_frames, model=None, world=1, precision="bf16"):
-    """The combinations --netvlad_frames / --every_n refuse, as ValueErrors that name the flags; touches no device."""
+def check_netvlad_frames(frames, every_n, max_frames, model=None, world=1, precision="bf16", sampling="uniform"):
+    """The combinations --netvlad_frames / --every_n / --student_sampling refuse, as ValueErrors that name the
+    flags; touches no device."""
     if frames not in NetVladTower.FRAME_MODES:
         raise ValueError("--netvlad_frames %r: one of %s" % (frames, "|".join(NetVladTower.FRAME_MODES)))
+    ops.check_student_sampling(sampling, "--student_sampling")
     if frames != "grid":
+        if sampling != "uniform":
+            raise ValueError("--student_sampling %s selects among the rows of --netvlad_frames grid; a %s tower draws its frames" % (sampling, frames))
         return
+    if sampling != "uniform" and max_frames > ops.SELECT_MAX_T:
+        raise ValueError("--student_sampling %s: --max_num_frames %d is refused, the source-frame tables hold at most %d frames per video"
+                         % (sampling, max_frames, ops.SELECT_MAX_T))
     if model is not None and model != "NetVLADModel":
         raise ValueError("--netvlad_frames grid is built for --model NetVLADModel, not %s" % model)
     if every_n < 1 or every_n > max_frames:

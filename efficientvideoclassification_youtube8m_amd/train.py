@@ -27,7 +27,8 @@ DESIGN.md 7.11).
 ``--model NeXtVLADModel --nextvlad_frames grid --every_n N --teacher_dir DIR`` trains a grid student against the frozen grid teacher of
 DIR's latest checkpoint, which runs on the frames its checkpoint records (distill.NeXtVladDistillGraph, DESIGN.md 7.14);
 ``--model NetVLADModel --netvlad_frames grid --every_n N --teacher_dir DIR`` does the same for the NetVLAD family
-(distill.NetVladDistillGraph).
+(distill.NetVladDistillGraph).  With ``--student_sampling WORD`` a NetVLAD grid tower - alone or as that student - runs on
+the frames the word selects instead of the grid.
 Multi-GPU: launch with ``python -m torch.distributed.run --nproc-per-node N``;
 ``--gpu`` is then ignored in favour of LOCAL_RANK.
 """
@@ -466,6 +467,52 @@ def check_netvlad_distill_flags():
     return True
 
 
+def netvlad_sampling_word(warn=False):
+    """The --student_sampling word a NetVLAD tower is built with: the flag under --netvlad_frames grid, and "uniform"
+    for every other model.  A sampled tower draws its frames and has no rows to select among: it keeps running on drawn frames, and
+    ``warn`` logs that once, naming both flags."""
+    word = FLAGS.student_sampling
+    if FLAGS.model != "NetVLADModel" or word == "uniform":
+        return "uniform"
+    if FLAGS.netvlad_frames != "grid":
+        if warn:
+            logging.warning("--student_sampling %s is not used with --netvlad_frames %s: the tower draws --iterations %d frames per video; "
+                            "the word selects among the rows of --netvlad_frames grid", word, FLAGS.netvlad_frames, FLAGS.iterations)
+        return "uniform"
+    return word
+
+
+def netvlad_sampling_metadata(graph):
+    """The checkpoint keys of a NetVLAD tower trained on selected frames: student_sampling for the one tower of a
+    SingleTowerGraph (a distillation graph's student word is recorded with every student's), student_sampling_seed under "random", and
+    teacher_sampling[_seed] when the frozen teacher of a distillation runs on a word itself.  "uniform" adds no key."""
+    out = {}
+    tw = getattr(graph, "tower", None)
+    if isinstance(tw, NetVladTower) and tw.sampling != "uniform":
+        out["student_sampling"] = tw.sampling
+        if tw.sampling == "random":
+            out["student_sampling_seed"] = tw.sampling_seed
+    if isinstance(graph, NetVladDistillGraph):
+        if graph.student_sampling == "random":
+            out["student_sampling_seed"] = graph.sampling_seed
+        if graph.teacher_sampling != "uniform":
+            out["teacher_sampling"] = graph.teacher_sampling
+            if graph.teacher_sampling == "random":
+                out["teacher_sampling_seed"] = graph.teacher_sampling_seed
+    return out
+
+
+def netvlad_teacher_sampling(sd):
+    """(word, seed) the model/* tower of the checkpoint dict ``sd`` runs on as a frozen teacher: the teacher_sampling a distillation
+    checkpoint records (its model/* IS such a teacher), else the student_sampling a grid tower trained alone records; "uniform" without
+    either."""
+    if sd.get("netvlad_frames") != "grid":
+        return "uniform", 0
+    if "teacher_every_n" in sd:
+        return sd.get("teacher_sampling", "uniform"), int(sd.get("teacher_sampling_seed", 0))
+    return sd.get("student_sampling", "uniform"), int(sd.get("student_sampling_seed", 0))
+
+
 def netvlad_teacher_every_n(sd):
     """The grid the model/* tower of the checkpoint dict ``sd`` runs on as a frozen teacher: the teacher_every_n a distillation
     checkpoint records (its model/* IS such a teacher), else its every_n when it records netvlad_frames == "grid", else 1 - a sampled
@@ -489,7 +536,8 @@ def netvlad_distill_source(feature_size):
     if not any(k.startswith("model/") and torch.is_tensor(v) for k, v in sd.items()):
         raise ValueError("%s holds no model/* variables (not a teacher checkpoint)" % what)
     check_netvlad_checkpoint(sd, "model", feature_size, NUM_CLASSES, netvlad_size_flags(), what)
-    return dict(ck=ck, sd=sd, teacher_every_n=netvlad_teacher_every_n(sd), resume=resume is not None)
+    return dict(ck=ck, sd=sd, teacher_every_n=netvlad_teacher_every_n(sd), resume=resume is not None,
+                teacher_sampling=netvlad_teacher_sampling(sd))
 
 
 def load_frozen_teacher(graph, teacher_dir):
@@ -518,7 +566,7 @@ def check_label_loss(label_loss_fn, finetune=False):
 
 
 def build_graph(model, label_loss_fn, feature_size, batch_size, every_n, device, finetune=False, process_group=None, students=_UNSET,
-                teachers=None, offline=None, teacher_every_n=1):
+                teachers=None, offline=None, teacher_every_n=1, teacher_sampling=("uniform", 0)):
     """Equivalent of cs/train.py:185-427 (and cs/train_finetune.py:185-331 when
     finetune): returns the graph object whose ``step`` runs one iteration."""
     check_label_loss(label_loss_fn, finetune)
@@ -586,9 +634,13 @@ def build_graph(model, label_loss_fn, feature_size, batch_size, every_n, device,
         # the grid student against the frozen grid teacher; teacher_every_n: netvlad_teacher_every_n of its checkpoint
         check_serial_flags(finetune)
         check_netvlad_distill_flags()
-        check_netvlad_frames(FLAGS.netvlad_frames, every_n, FLAGS.max_num_frames, model=FLAGS.model, precision=FLAGS.precision)
+        check_netvlad_frames(FLAGS.netvlad_frames, every_n, FLAGS.max_num_frames, model=FLAGS.model, precision=FLAGS.precision,
+                             sampling=netvlad_sampling_word())
         common.pop("label_loss", None)            # (refused above for anything but CrossEntropyLoss, which the loss kernel has built in)
         cs, hs, mx = netvlad_size_flags()
+        if netvlad_sampling_word() != "uniform" or teacher_sampling[0] != "uniform":      # (uniform: the call of 7.19)
+            common.update(student_sampling=netvlad_sampling_word(), sampling_seed=FLAGS.student_sampling_seed,
+                          teacher_sampling=teacher_sampling[0], teacher_sampling_seed=teacher_sampling[1])
         return NetVladDistillGraph(batch_size, every_n=every_n, teacher_every_n=teacher_every_n, feature_size=feature_size,
                                    vocab_size=NUM_CLASSES, max_frames=FLAGS.max_num_frames, cluster_size=cs, hidden_size=hs,
                                    num_mixtures=mx, device=device, precision=FLAGS.precision, distill_losses=FLAGS.distill_losses, **common)
@@ -604,7 +656,8 @@ def build_graph(model, label_loss_fn, feature_size, batch_size, every_n, device,
     if isinstance(model, frame_level_models.NetVLADModel):          # extension (the reference's class is an empty stub)
         tw = NetVladTower(batch_size, FLAGS.max_num_frames, feature_size, NUM_CLASSES, FLAGS.iterations, FLAGS.netvlad_cluster_size,
                           FLAGS.netvlad_hidden_size, FLAGS.moe_num_mixtures, device=device, process_group=process_group,
-                          frames=FLAGS.netvlad_frames, every_n=every_n)
+                          frames=FLAGS.netvlad_frames, every_n=every_n, sampling=netvlad_sampling_word(warn=True),
+                          sampling_seed=FLAGS.student_sampling_seed)
         _apply_precision(tw)
         return SingleTowerGraph(tw, **common)
     if isinstance(model, frame_level_models.NeXtVLADModel):         # extension (the reference's class is an empty stub)
@@ -708,6 +761,7 @@ def save_checkpoint(graph, train_dir, rank):
         sd["nextvlad_frames"], sd["every_n"], sd["teacher_every_n"] = "grid", graph.every_n, graph.teacher_every_n
     if isinstance(graph, NetVladDistillGraph):    # the same for the NetVLAD family (distill_losses: recorded above, mode "serial")
         sd["netvlad_frames"], sd["every_n"], sd["teacher_every_n"] = "grid", graph.every_n, graph.teacher_every_n
+    sd.update(netvlad_sampling_metadata(graph))   # metadata: the --student_sampling word of a NetVLAD tower off the uniform grid
     sd.update(nextvlad_dropout_metadata(graph))   # metadata: --nextvlad_dropout and its seed, when the tower was trained with a non-zero rate
     fn = getattr(graph, "label_loss", None)
     if fn is not None and not losses.is_default(fn):            # metadata: the --label_loss these weights were trained on (the default: no key)
@@ -782,7 +836,8 @@ def main(argv=None):
     nx_distill = serial and check_nextvlad_distill_flags()
     check_nextvlad_dropout_flags()
     check_nextvlad_frames(FLAGS.nextvlad_frames, FLAGS.every_n, FLAGS.max_num_frames, model=FLAGS.model, world=world, precision=FLAGS.precision)
-    check_netvlad_frames(FLAGS.netvlad_frames, FLAGS.every_n, FLAGS.max_num_frames, model=FLAGS.model, world=world, precision=FLAGS.precision)
+    check_netvlad_frames(FLAGS.netvlad_frames, FLAGS.every_n, FLAGS.max_num_frames, model=FLAGS.model, world=world, precision=FLAGS.precision,
+                         sampling=netvlad_sampling_word())
     nx_src = None
     if nx_distill:
         # the teacher's checkpoint on the host - its grid and its shapes against the size flags -, before the device is touched
@@ -833,7 +888,8 @@ def main(argv=None):
     if FLAGS.optimizer != "AdamOptimizer":
         raise NotImplementedError("only AdamOptimizer (the reference default, cs/train.py:91) is built")
     graph = build_graph(model, label_loss_fn, feature_size, FLAGS.batch_size, FLAGS.every_n, device, finetune, students=multi, teachers=ens,
-                        offline=offline, teacher_every_n=nx_src["teacher_every_n"] if nx_src else 1)
+                        offline=offline, teacher_every_n=nx_src["teacher_every_n"] if nx_src else 1,
+                        teacher_sampling=(nx_src or {}).get("teacher_sampling", ("uniform", 0)))
     if offline:
         graph.teacher_record = offline_record(offline)
     logging.info("%s: Built graph.", task)

@@ -33,7 +33,9 @@ Ensemble members and cascade stages take their family from their own checkpoints
 tower on the grid the checkpoint records, every real frame for a --netvlad_frames sampled one (--netvlad_serve_every_n overrides); its
 variables are checked against the size flags on the host first.  A --teacher_dir checkpoint of this family is evaluated
 as teacher + student: the student's metrics on the recorded every_n, student_loss logged against the teacher on the recorded
-teacher_every_n.  No ensemble or cascade serves this family.
+teacher_every_n.  --student_sampling WORD serves the served tower on the frames that word selects (a warning when the
+checkpoint records another word), the teacher next to a served student stays on its recorded frames.  No ensemble or cascade serves this
+family.
 """
 from __future__ import annotations
 
@@ -120,8 +122,10 @@ def netvlad_source(reader, student_only=False):
         check_netvlad_checkpoint(sd, scope, sum(reader.feature_sizes), reader.num_classes,
                                  (FLAGS.netvlad_cluster_size, FLAGS.netvlad_hidden_size, FLAGS.moe_num_mixtures), ck)
     teacher_every_n = int(sd.get("teacher_every_n", 1)) if both else 1
+    #  the served tower runs on --student_sampling; the teacher next to a served student stays on what the checkpoint records
+    teacher_sampling = (sd.get("teacher_sampling", "uniform"), int(sd.get("teacher_sampling_seed", 0))) if both else ("uniform", 0)
     return dict(ck=ck, sd=sd, tower="both" if both else "teacher", every_n=netvlad_every_n(sd, FLAGS.netvlad_serve_every_n, ck),
-                teacher_every_n=teacher_every_n)
+                teacher_every_n=teacher_every_n, teacher_sampling=teacher_sampling)
 
 
 def build_graph(reader, model, batch_size, device, student_only=False, label_loss=None, nextvlad=None, netvlad=None):
@@ -134,7 +138,9 @@ def build_graph(reader, model, batch_size, device, student_only=False, label_los
                                 max_frames=FLAGS.max_num_frames, cluster_size=FLAGS.netvlad_cluster_size,
                                 hidden_size=FLAGS.netvlad_hidden_size, num_mixtures=FLAGS.moe_num_mixtures, device=device,
                                 precision=FLAGS.precision, label_loss=label_loss, tower=src.get("tower", "teacher"),
-                                teacher_every_n=src.get("teacher_every_n", 1))
+                                teacher_every_n=src.get("teacher_every_n", 1), student_sampling=FLAGS.student_sampling,
+                                sampling_seed=FLAGS.student_sampling_seed, teacher_sampling=src.get("teacher_sampling", ("uniform", 0))[0],
+                                teacher_sampling_seed=src.get("teacher_sampling", ("uniform", 0))[1])
     if isinstance(model, frame_level_models.NeXtVLADModel):
         from . import inference
         src = nextvlad if nextvlad is not None else nextvlad_source(reader, student_only)
@@ -277,7 +283,7 @@ def evaluation_loop(graph, reader, label_loss_fn, summary_writer, evl_metrics, l
     if getattr(graph, "family", None) != "netvlad":                      # (a NetVLAD graph's restore checks every variable's name and shape)
         check_model_family(sd, ck)
     graph.restore(sd)
-    if graph.student is not None:
+    if graph.student is not None or getattr(graph, "family", None) == "netvlad":      # (a NetVLAD tower trained alone records its word too)
         warn_sampling(sd, FLAGS.student_sampling, ck)
     global_step_val = int(sd.get("global_step", 0))
     if global_step_val == last_global_step_val:

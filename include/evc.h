@@ -961,6 +961,18 @@ int evc_frames_gather_packed_bn(const float* x, const uint8_t* x_u8, const int32
 int evc_frames_gather_packed_sel(const float* x, const uint8_t* x_u8, const int32_t* num_frames, const int32_t* row_off, const int32_t* sel,
                                  int B, int Bsel, int T, int F, int every_n, int R, int Rp, int normalize, float* out, evc_bf16* out_bf16,
                                  void* stream);
+/* evc_frames_gather_packed on the frames a table names: out[row_off[b] + j][:] = frame src[b * S + j] of video b, src
+ * int32 [B][S] on the device - the table evc_student_frame_select / evc_student_frame_select_scored write, S = T / every_n there; this
+ * entry takes no every_n.  The arithmetic and its order are evc_frames_gather_packed's: a table holding j * every_n gives that entry's
+ * bits.  An entry < 0 or >= T is an exact zero row in both outputs and is never used as an address; for uint8 input an entry >=
+ * num_frames[b] is a zero row too.  row_off[b+1] - row_off[b] <= S is the caller's responsibility (ops.SelectPlan counts what the
+ * table kernels count: k_b = trunc(float64(n_b) / T * S), n_b clipped to 0 .. T); src is never read at j >= S all the same, such a row
+ * is zeros.  Rows R .. Rp (Rp - R < 32) are zeros, nothing at or beyond Rp is written.  out or out_bf16 may be NULL, not both.
+ * EVC_ERR_BAD_SHAPE: F % 4 != 0, S < 1, R > B * S, Rp < R, Rp - R >= 32.  EVC_ERR_BAD_ARG: NULL num_frames / row_off / src, both
+ * outputs NULL, not exactly one of x / x_u8.  EVC_ERR_BAD_ALIGN: x, out 16-byte, out_bf16 8-byte, x_u8, src and the other int32
+ * operands 4-byte.  All before any launch. */
+int evc_frames_gather_packed_tab(const float* x, const uint8_t* x_u8, const int32_t* num_frames, const int32_t* row_off, const int32_t* src,
+                                 int B, int T, int F, int S, int R, int Rp, int normalize, float* out, evc_bf16* out_bf16, void* stream);
 /* dst[sel[j]][0 .. C) = src[j][0 .. C) for j < n (f32; row strides ld_src / ld_dst in floats; float4 accesses where bases and strides
  * allow, scalar otherwise and for the tail columns).  Every other row of dst is left untouched.  n <= rows_dst; n == 0 launches
  * nothing.  sel (device int32 [n]) is NOT checked on the device: the caller guarantees distinct entries in 0 .. rows_dst - 1. */
