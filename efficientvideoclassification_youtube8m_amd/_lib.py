@@ -109,6 +109,9 @@ SIGNATURES = {
     "evc_bn_bwd_finalize": [vp, vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp],
     "evc_bn_bwd_partial_add": [vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, i32, vp, vp],
     "evc_bn_bwd_finalize_add": [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp],
+    "evc_bn_gate_fwd": [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp],
+    "evc_bn_gate_bwd_partial": [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp],
+    "evc_bn_gate_bwd_finalize": [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "evc_bn_relu6_framepool_fwd": [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
     "evc_framepool_max_fwd": [vp, i32, i32, i32, vp, vp, vp, vp],
     "evc_framepool_max_bwd": [vp, vp, i32, i32, i32, vp, vp],

@@ -1910,6 +1910,128 @@ extern "C" int evc_bn_relu6_bwd(const float* x, const float* dy, int R, int C, c
   return evc_bn_bwd_finalize(x, dy, R, R, C, mean, var, gamma, beta, relu6, argmax, S, ws, dx_f32, dx_bf16, dgamma, dbeta, stream);
 }
 
+// ---- context gate behind a batch norm (NetVLAD's gating_bn): out = h * sigmoid(bn(gl)).  The chain these entries replace is
+// evc_bn_apply(gl -> gn), evc_nextvlad_gate_fwd(h, gn), evc_nextvlad_gate_bwd_add(h, gn, d, d2 -> dh, dgn), evc_bn_bwd_partial / _finalize(gl, dgn);
+// they give its bits without gn, g or dgn in memory.  gn is bn_apply_kernel's expression, xh * ga + be with xh = (x - mu) * inv, which is also how
+// bn_bwd_partial_kernel spells it.  dgn is an f32 the chain STORES before the batch norm's backward reads it, so it is formed with contraction
+// switched off (gate_dy): left to the compiler, d - sd / R in the finalize pass would take the last product as an fma operand, unrounded.
+__device__ __forceinline__ float gate_dy(float e, float h, float g) {
+#pragma clang fp contract(off)
+  return e * h * g * (1.0f - g);
+}
+__device__ __forceinline__ float bn_gate_out(float x, float h, float mu, float va, float ga, float be) {
+  return h * sigmoidf_((x - mu) * rsqrtf(va + 1e-3f) * ga + be);
+}
+__global__ void bn_gate_fwd_kernel(const float* __restrict__ gl, const float* __restrict__ h, long n, int C, const float* __restrict__ mean,
+                                   const float* __restrict__ var, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                   float* __restrict__ out) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const int c = (int)(i % C);
+    out[i] = bn_gate_out(gl[i], h[i], mean[c], var[c], gamma[c], beta[c]);
+  }
+}
+// C % 4 == 0 and every base 16-byte aligned: one quad per thread and iteration, the four per-column vectors as float4
+__global__ void bn_gate_fwd_vec4_kernel(const float4* __restrict__ gl, const float4* __restrict__ h, long n4, int C4, const float4* __restrict__ mean,
+                                        const float4* __restrict__ var, const float4* __restrict__ gamma, const float4* __restrict__ beta,
+                                        float4* __restrict__ out) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+    const int c = (int)(i % C4);
+    const float4 x = gl[i], hh = h[i], mu = mean[c], va = var[c], ga = gamma[c], be = beta[c];
+    float4 o;
+    o.x = bn_gate_out(x.x, hh.x, mu.x, va.x, ga.x, be.x);
+    o.y = bn_gate_out(x.y, hh.y, mu.y, va.y, ga.y, be.y);
+    o.z = bn_gate_out(x.z, hh.z, mu.z, va.z, ga.z, be.z);
+    o.w = bn_gate_out(x.w, hh.w, mu.w, va.w, ga.w, be.w);
+    out[i] = o;
+  }
+}
+static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+extern "C" int evc_bn_gate_fwd(const float* gl, const float* h, int R, int C, const float* mean, const float* var, const float* gamma,
+                               const float* beta, float* out, void* stream) {
+  EVC_REQUIRE(R > 0 && C > 0, EVC_ERR_BAD_SHAPE, "evc_bn_gate_fwd: bad shape (R=%d C=%d)", R, C);
+  EVC_REQUIRE(gl && h && mean && var && gamma && beta && out, EVC_ERR_BAD_ARG, "evc_bn_gate_fwd: NULL operand");
+  const long n = (long)R * C;
+  if (C % 4 == 0 && aligned16(gl) && aligned16(h) && aligned16(mean) && aligned16(var) && aligned16(gamma) && aligned16(beta) && aligned16(out))
+    hipLaunchKernelGGL(bn_gate_fwd_vec4_kernel, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, (const float4*)gl, (const float4*)h, n / 4,
+                       C / 4, (const float4*)mean, (const float4*)var, (const float4*)gamma, (const float4*)beta, (float4*)out);
+  else
+    hipLaunchKernelGGL(bn_gate_fwd_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, gl, h, n, C, mean, var, gamma, beta, out);
+  EVC_LAUNCH_CHECK();
+  return EVC_OK;
+}
+// bn_bwd_partial_kernel<false>'s grid, loop and summation order (relu6 = 0, no argmax) on dy = e * h * g * (1 - g), e = d (+ d2); stores dh = e * g
+__global__ __launch_bounds__(256) void bn_gate_bwd_partial_kernel(const float* __restrict__ gl, const float* __restrict__ h, const float* __restrict__ d,
+                                                                  const float* __restrict__ d2, int R, int C, const float* __restrict__ mean,
+                                                                  const float* __restrict__ var, const float* __restrict__ gamma,
+                                                                  const float* __restrict__ beta, double* __restrict__ ws, float* __restrict__ dh) {
+  __shared__ double sh[2][4][64];
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const int c = blockIdx.x * 64 + tx;
+  double s = 0.0, q = 0.0;
+  if (c < C) {
+    const float mu = mean[c], inv = rsqrtf(var[c] + 1e-3f), ga = gamma[c], be = beta[c];
+    for (int r = blockIdx.y * 4 + ty; r < R; r += gridDim.y * 4) {
+      const long i = (long)r * C + c;
+      const float xh = (gl[i] - mu) * inv;
+      const float g = sigmoidf_(xh * ga + be);
+      float e = d[i];
+      if (d2) e = __fadd_rn(e, d2[i]);
+      dh[i] = e * g;
+      const float dy = gate_dy(e, h[i], g);
+      s += dy; q += (double)dy * xh;
+    }
+  }
+  sh[0][ty][tx] = s; sh[1][ty][tx] = q;
+  __syncthreads();
+  if (ty == 0 && c < C) {
+    atomicAdd(&ws[c], sh[0][0][tx] + sh[0][1][tx] + sh[0][2][tx] + sh[0][3][tx]);
+    atomicAdd(&ws[C + c], sh[1][0][tx] + sh[1][1][tx] + sh[1][2][tx] + sh[1][3][tx]);
+  }
+}
+__global__ void bn_gate_bwd_final_kernel(const float* __restrict__ gl, const float* __restrict__ h, const float* __restrict__ d,
+                                         const float* __restrict__ d2, long n, int R, int C, const float* __restrict__ mean,
+                                         const float* __restrict__ var, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                         const double* __restrict__ ws, float* __restrict__ dxf, bf16_t* __restrict__ dxb,
+                                         float* __restrict__ dgamma, float* __restrict__ dbeta) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const int c = (int)(i % C);
+    const float inv = rsqrtf(var[c] + 1e-3f), ga = gamma[c];
+    const float xh = (gl[i] - mean[c]) * inv;
+    const float g = sigmoidf_(xh * ga + beta[c]);
+    float e = d[i];
+    if (d2) e = __fadd_rn(e, d2[i]);
+    const float dy = gate_dy(e, h[i], g);
+    const float sd = (float)ws[c], sdx = (float)ws[C + c];
+    const float dx = ga * inv * (dy - sd / R - xh * sdx / R);
+    if (dxf) dxf[i] = dx;
+    if (dxb) dxb[i] = f32_to_bf16(dx);
+    if (i < C) { if (dgamma) dgamma[i] = (float)ws[C + i]; if (dbeta) dbeta[i] = (float)ws[i]; }
+  }
+}
+extern "C" int evc_bn_gate_bwd_partial(const float* gl, const float* h, const float* d, const float* d2, int R, int C, const float* mean,
+                                       const float* var, const float* gamma, const float* beta, double* ws, float* dh, void* stream) {
+  EVC_REQUIRE(R > 0 && C > 0, EVC_ERR_BAD_SHAPE, "evc_bn_gate_bwd_partial: bad shape (R=%d C=%d)", R, C);
+  EVC_REQUIRE(gl && h && d && mean && var && gamma && beta && ws && dh, EVC_ERR_BAD_ARG, "evc_bn_gate_bwd_partial: NULL operand (d2 may be NULL)");
+  hipStream_t st = (hipStream_t)stream;
+  EVC_CHECK_HIP(hipMemsetAsync(ws, 0, sizeof(double) * 2 * C, st));
+  int rs = R / 256; rs = rs < 1 ? 1 : (rs > 64 ? 64 : rs);
+  hipLaunchKernelGGL(bn_gate_bwd_partial_kernel, dim3((C + 63) / 64, rs), dim3(256), 0, st, gl, h, d, d2, R, C, mean, var, gamma, beta, ws, dh);
+  EVC_LAUNCH_CHECK();
+  return EVC_OK;
+}
+extern "C" int evc_bn_gate_bwd_finalize(const float* gl, const float* h, const float* d, const float* d2, int R, int R_total, int C,
+                                        const float* mean, const float* var, const float* gamma, const float* beta, const double* ws,
+                                        float* dgl_f32, evc_bf16* dgl_bf16, float* dgamma, float* dbeta, void* stream) {
+  EVC_REQUIRE(R > 0 && C > 0 && R_total >= R, EVC_ERR_BAD_SHAPE, "evc_bn_gate_bwd_finalize: bad shape (R=%d R_total=%d C=%d)", R, R_total, C);
+  EVC_REQUIRE(gl && h && d && mean && var && gamma && beta && ws, EVC_ERR_BAD_ARG,
+              "evc_bn_gate_bwd_finalize: NULL operand (d2 and each output may be NULL)");
+  const long n = (long)R * C;
+  hipLaunchKernelGGL(bn_gate_bwd_final_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, gl, h, d, d2, n, R_total, C, mean, var, gamma,
+                     beta, ws, dgl_f32, (bf16_t*)dgl_bf16, dgamma, dbeta);
+  EVC_LAUNCH_CHECK();
+  return EVC_OK;
+}
+
 // fused cluster_bn + relu6 + FramePooling('max'): act [B][S][C] f32 -> pooled [B][C]
 __global__ __launch_bounds__(256) void bn_relu6_pool_kernel(const float* __restrict__ act, int S, int C,
                                                             const float* __restrict__ mean, const float* __restrict__ var,

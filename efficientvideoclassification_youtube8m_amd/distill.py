@@ -1871,11 +1871,22 @@ class NeXtVladEvalGraph(_StepGraph):
         return out
 
 
-def check_netvlad_checkpoint(sd, scope, feature_size, vocab_size, sizes, what="the checkpoint"):
+def netvlad_checkpoint_gating(sd, scope):
+    """Whether the ``scope``/* tower of the checkpoint dict ``sd`` has the context gate: it holds <scope>/gating_weights."""
+    return torch.is_tensor(sd.get("%s/gating_weights" % scope))
+
+
+def check_netvlad_checkpoint(sd, scope, feature_size, vocab_size, sizes, what="the checkpoint", gating=False):
     """The ``scope``/* variables of the checkpoint dict ``sd`` against the size flags (sizes: cluster_size, hidden_size, num_mixtures), on
-    the host: ValueError naming the first missing or mismatching variable and both shapes."""
+    the host: ValueError naming the first missing or mismatching variable and both shapes.  gating: whether the caller's tower has the
+    context gate (--netvlad_gating); a checkpoint that disagrees is a ValueError naming the flag and the variable found or missing."""
     from .towers import NetVladTower
-    for k, shp in NetVladTower.checkpoint_shapes(feature_size, vocab_size, *sizes).items():
+    gw = "%s/%s" % (scope, NetVladTower.GW)
+    if netvlad_checkpoint_gating(sd, scope) != bool(gating):
+        if gating:
+            raise ValueError("--netvlad_gating True, but %s holds no variable %s (a tower trained without the context gate)" % (what, gw))
+        raise ValueError("--netvlad_gating False, but %s holds the variable %s (a tower trained with the context gate)" % (what, gw))
+    for k, shp in NetVladTower.checkpoint_shapes(feature_size, vocab_size, *sizes, gating=bool(gating)).items():
         have = sd.get("%s/%s" % (scope, k))
         if not torch.is_tensor(have):
             raise ValueError("%s holds no variable %s/%s (not a NetVLADModel checkpoint)" % (what, scope, k))
@@ -1897,7 +1908,10 @@ class NetVladDistillGraph(_StepGraph):
     student_sampling / sampling_seed: the --student_sampling word of the STUDENT, "random" drawn with draw =
     global_step and row0 = 0.  teacher_sampling / teacher_sampling_seed: what the frozen teacher's checkpoint records when that tower was
     itself trained on selected frames; it runs on them with draw 0, as evaluation does.  Under a scored word the batch's
-    ops.frame_change_keys are computed once and handed to both towers."""
+    ops.frame_change_keys are computed once and handed to both towers.
+
+    gating / teacher_gating: the context gate of the student (--netvlad_gating) and of the frozen teacher (what its
+    checkpoint holds).  They may differ: both states are [B, H], and L_REP and dstate are on `state`, the gated vector where there is a gate."""
 
     LOSS_SLOTS = DistillGraph.LOSS_SLOTS
     DISTILL_LOSSES = DistillGraph.DISTILL_LOSSES
@@ -1909,10 +1923,12 @@ class NetVladDistillGraph(_StepGraph):
                  hidden_size=1024, num_mixtures=2, base_learning_rate=0.001, learning_rate_decay=1.0,
                  learning_rate_decay_examples=4000000, regularization_penalty=2.0, clip_gradient_norm=1.0, count_rep_twice=True,
                  device="cuda:0", seed=7, process_group=None, precision="bf16", distill_losses=DISTILL_LOSSES, label_loss=None,
-                 student_sampling="uniform", sampling_seed=0, teacher_sampling="uniform", teacher_sampling_seed=0):
+                 student_sampling="uniform", sampling_seed=0, teacher_sampling="uniform", teacher_sampling_seed=0, gating=False,
+                 teacher_gating=False):
         from .towers import NetVladTower, check_netvlad_frames
         self.student_sampling, self.sampling_seed = ops.check_student_sampling(student_sampling, "--student_sampling"), int(sampling_seed)
         self.teacher_sampling, self.teacher_sampling_seed = ops.check_student_sampling(teacher_sampling, "teacher_sampling"), int(teacher_sampling_seed)
+        self.gating, self.teacher_gating = bool(gating), bool(teacher_gating)
         self.world = _world_of(process_group)
         if self.world > 1:
             raise ValueError("NetVladDistillGraph is not data parallel (process group of %d ranks): train the student against the "
@@ -1934,9 +1950,10 @@ class NetVladDistillGraph(_StepGraph):
         self.global_step = 0
         sizes = (batch_size, max_frames, feature_size, vocab_size, 30, cluster_size, hidden_size, num_mixtures)
         self.teacher = NetVladTower(*sizes, device=device, training=False, scope="model", seed=seed, frames="grid",
-                                    every_n=self.teacher_every_n, sampling=self.teacher_sampling, sampling_seed=self.teacher_sampling_seed)
+                                    every_n=self.teacher_every_n, sampling=self.teacher_sampling, sampling_seed=self.teacher_sampling_seed,
+                                    gating=self.teacher_gating)
         self.student = NetVladTower(*sizes, device=device, training=True, scope="model_student", seed=seed + 1, frames="grid",
-                                    every_n=self.every_n, sampling=self.student_sampling, sampling_seed=self.sampling_seed)
+                                    every_n=self.every_n, sampling=self.student_sampling, sampling_seed=self.sampling_seed, gating=self.gating)
         self.moe = self.student.moe
         self.fused_moe_update = True
         self.losses = torch.zeros(8, dtype=F32, device=self.device)
@@ -2024,17 +2041,24 @@ class NetVladEvalGraph(_StepGraph):
 
     student_sampling / sampling_seed: the --student_sampling word the SERVED tower runs on (the student, or the teacher
     when it is the only tower), as EvalGraph serves its student on the flag; "random" is drawn with draw 0 and row0 0, the same frames
-    for the same batching.  With tower='both' the teacher runs on teacher_sampling / teacher_sampling_seed, what its checkpoint records."""
+    for the same batching.  With tower='both' the teacher runs on teacher_sampling / teacher_sampling_seed, what its checkpoint records.
+
+    gating / teacher_gating: the context gate of the served tower and, with tower='both', of the teacher - what the
+    checkpoint's own variables say (validate.netvlad_source), never the flag."""
 
     family = "netvlad"
     student_sampling = "uniform"
 
     def __init__(self, batch_size, every_n=1, feature_size=1152, vocab_size=4716, max_frames=300, cluster_size=64, hidden_size=1024,
                  num_mixtures=2, device="cuda:0", precision="bf16", label_loss=None, seed=7, tower="teacher", teacher_every_n=1,
-                 student_sampling="uniform", sampling_seed=0, teacher_sampling="uniform", teacher_sampling_seed=0):
+                 student_sampling="uniform", sampling_seed=0, teacher_sampling="uniform", teacher_sampling_seed=0, gating=False,
+                 teacher_gating=False):
         from .towers import NetVladTower, check_netvlad_frames
         if tower not in ("teacher", "student", "both"):
             raise ValueError("NetVladEvalGraph: tower %r (teacher | student | both)" % (tower,))
+        if tower != "both":
+            teacher_gating = gating                                   # (the one tower is the served one)
+        self.gating, self.teacher_gating = bool(gating), bool(teacher_gating)
         self.student_sampling, self.sampling_seed = ops.check_student_sampling(student_sampling, "--student_sampling"), int(sampling_seed)
         if tower != "both":
             teacher_sampling, teacher_sampling_seed = student_sampling, sampling_seed      # (the one tower is the served one)
@@ -2051,10 +2075,12 @@ class NetVladEvalGraph(_StepGraph):
         self.teacher = self.student = None
         if tower != "student":
             self.teacher = NetVladTower(*args, device=device, training=False, scope="model", seed=seed, frames="grid",
-                                        every_n=self.teacher_every_n, sampling=self.teacher_sampling, sampling_seed=self.teacher_sampling_seed)
+                                        every_n=self.teacher_every_n, sampling=self.teacher_sampling, sampling_seed=self.teacher_sampling_seed,
+                                        gating=self.teacher_gating)
         if tower != "teacher":
             self.student = NetVladTower(*args, device=device, training=False, scope="model_student", seed=seed + 1, frames="grid",
-                                        every_n=self.every_n, sampling=self.student_sampling, sampling_seed=self.sampling_seed)
+                                        every_n=self.every_n, sampling=self.student_sampling, sampling_seed=self.sampling_seed,
+                                        gating=self.gating)
         self.losses = torch.zeros(2 if tower == "both" else 1, dtype=F32, device=self.device)
 
     def _towers(self):
@@ -2063,7 +2089,7 @@ class NetVladEvalGraph(_StepGraph):
     def restore(self, state_dict):
         """Each tower's variables and moving statistics by name, after the host check of their shapes against the graph's sizes."""
         for tw in self._towers():
-            check_netvlad_checkpoint(state_dict, tw.scope, self.F, self.V, self.sizes)
+            check_netvlad_checkpoint(state_dict, tw.scope, self.F, self.V, self.sizes, gating=tw.gating)
         for tw in self._towers():
             tw.load_state_dict(state_dict)
 

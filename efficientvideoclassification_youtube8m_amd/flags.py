@@ -140,6 +140,9 @@ _define("netvlad_hidden_size", 1024, int, "NetVLADModel (extension): width of th
 _define("netvlad_frames", "sampled", str, "NetVLADModel (extension, DESIGN.md 7.18): sampled (--iterations <= 64 frames drawn per video and "
         "step) | grid (the frames 0, every_n, 2 every_n, ... of each video's real frames, a different number per video, packed without "
         "padding: --every_n 1 is every real frame, the teacher's input; --every_n 10 or 30 the fewer-frames student's; --iterations is not read)")
+_define("netvlad_gating", False, _bool, "NetVLADModel (extension, DESIGN.md 7.21): the context gate of 'Learnable pooling with Context Gating' "
+        "between the hidden layer and the MoE head, state = h6 * sigmoid(gating_bn(h6 . gating_weights)), in both --netvlad_frames modes; "
+        "with --teacher_dir it is the student's gate (the frozen teacher's is read from its checkpoint).  One rank only")
 _define("netvlad_serve_every_n", 0, int, "validate with --model NetVLADModel (DESIGN.md 7.18): the grid the served tower runs on, every N-th "
         "real frame; 0 = as the checkpoint records (its every_n for a --netvlad_frames grid checkpoint, 1 - every real frame - for a sampled "
         "one).  Another N than the recorded one is a legitimate experiment: the flag wins, with a warning")

@@ -172,7 +172,8 @@ class NetVLADModel(models.BaseModel):
         if tw is None:
             tw = self.towers[scope] = NetVladTower(B, T, F, vocab_size, iterations, cluster_size, hidden_size, FLAGS.moe_num_mixtures,
                                                    device=model_input.device, training=True, scope=scope,
-                                                   seed=unused_params.get("seed", 0), frames=frames, every_n=every_n)
+                                                   seed=unused_params.get("seed", 0), frames=frames, every_n=every_n,
+                                                   gating=FLAGS.netvlad_gating)
         nf = num_frames.reshape(-1).to(torch.int32)
         if tw.frames == "grid":                                      # no draw; the host frame counts lay out the packed rows
             return {"predictions": tw.forward(model_input.contiguous(), nf, normalize=unused_params.get("normalize_input", False),

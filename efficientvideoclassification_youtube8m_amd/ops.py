@@ -1318,6 +1318,22 @@ def bn_bwd_finalize_add(x, dy, dy2, R, R_total, Cc, mean, var, gamma, beta, relu
               1 if relu6 else 0, _p(argmax), S, _p(ws), _p(dx_f32), _p(dx_bf16), _p(dgamma), _p(dbeta), _stream())
 
 
+def bn_gate_fwd(gl, h, R, Cc, mean, var, gamma, beta, out):
+    """out = h * sigmoid(bn(gl)): bn_apply and nextvlad_gate_fwd in one pass, their bits."""
+    _lib.call("evc_bn_gate_fwd", _p(gl), _p(h), R, Cc, _p(mean), _p(var), _p(gamma), _p(beta), _p(out), _stream())
+
+
+def bn_gate_bwd_partial(gl, h, d, d2, R, Cc, mean, var, gamma, beta, ws, dh):
+    """bn_bwd_partial on dy = e * h * g * (1 - g), e = d (+ d2, None allowed), g recomputed from gl; stores dh = e * g."""
+    _lib.call("evc_bn_gate_bwd_partial", _p(gl), _p(h), _p(d), _p(d2), R, Cc, _p(mean), _p(var), _p(gamma), _p(beta), _p(ws), _p(dh), _stream())
+
+
+def bn_gate_bwd_finalize(gl, h, d, d2, R, R_total, Cc, mean, var, gamma, beta, ws, dgl_f32=None, dgl_bf16=None, dgamma=None, dbeta=None):
+    """bn_bwd_finalize on the same dy, after bn_gate_bwd_partial on the same operands."""
+    _lib.call("evc_bn_gate_bwd_finalize", _p(gl), _p(h), _p(d), _p(d2), R, R_total, Cc, _p(mean), _p(var), _p(gamma), _p(beta), _p(ws),
+              _p(dgl_f32), _p(dgl_bf16), _p(dgamma), _p(dbeta), _stream())
+
+
 def bn_relu6_framepool_fwd(act, B, S, Cc, mean, var, gamma, beta, pooled_f32, pooled_bf16, argmax):
     _lib.call("evc_bn_relu6_framepool_fwd", _p(act), B, S, Cc, _p(mean), _p(var), _p(gamma), _p(beta), _p(pooled_f32),
               _p(pooled_bf16), _p(argmax), _stream())

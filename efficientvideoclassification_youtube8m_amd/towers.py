@@ -569,6 +569,13 @@ class NetVladTower(TowerBase):
     input_bn are one launch (evc_frames_gather_packed_bn).  `state` is h6 = relu6(hidden1_bn(hid)), what the MoE head
     reads; backward(dstate=...) adds a gradient on it in front of that relu6's mask (serial distillation's L_REP).
 
+    gating=True (--netvlad_gating): the paper's context gate between the hidden layer and the classifier, in both frame modes:
+    gl = bf16(h6) . gating_weights, state = h6 * sigmoid(gating_bn(gl)); the MoE head reads `state`, and so does L_REP.  Five more variables
+    (gating_weights [H, H] and gating_bn's four), stored after hidden1_bn's; none is in l2_names.  The gate is evc_bn_gate_fwd and
+    evc_bn_gate_bwd_partial / _finalize (fused_gate = False: the chain of older entries they replace, the same bits).  In the backward pass
+    the head's gradient and dstate meet inside the gate, and hidden1_bn receives the gate's two gradients on h6 (the direct one and the one
+    through gating_weights) as its dy / dy2.  One rank only.  Off, the tower has no such variable and issues the launches it always did.
+
     sampling (grid mode): a word of ops.STUDENT_SAMPLING / STUDENT_SAMPLING_SCORED.  Off "uniform" video b contributes the
     k_b = trunc(n_b / T * (T // every_n)) frames the word selects (ops.SelectPlan: the H-LSTM student's count, at most the grid's) - their
     table built on the device per batch (kept as last_frame_table), one gather that reads it (evc_frames_gather_packed_tab), everything
@@ -577,19 +584,23 @@ class NetVladTower(TowerBase):
     PRECISIONS = ("bf16",)             # no split-bf16 forward (set_precision refuses anything else)
     FRAME_MODES = ("sampled", "grid")
     fused_input_pass = True           # forward-only grid towers: evc_frames_gather_packed_bn (False: the two launches, for A/B timing)
+    fused_gate = True                 # gating: evc_bn_gate_fwd / _bwd_* (False: bn_apply, nextvlad_gate_*, bn_bwd_* one after another; same bits)
 
-    CW, C2, HW = "cluster_weights", "cluster_weights2", "hidden1_weights"
+    CW, C2, HW, GW = "cluster_weights", "cluster_weights2", "hidden1_weights", "gating_weights"
     l2_names = (MoeHead.GATES, MoeHead.EXPERTS)
     # all three batch-norms go through BatchNorm.backward: their gamma/beta gradients are global (all-reduced f64 sums)
+    # (a tower with the gate adds gating_bn's pair to its own copy)
     global_grad_names = tuple("%s/%s" % (s_, v) for s_ in ("input_bn", "cluster_bn", "hidden1_bn") for v in ("beta", "gamma"))
 
     def __init__(self, batch_size, max_frames=300, feature_size=1152, vocab_size=4716, iterations=30, cluster_size=64,
                  hidden_size=1024, num_mixtures=2, device="cuda:0", training=True, scope="model", seed=0, process_group=None,
-                 frames="sampled", every_n=1, sampling="uniform", sampling_seed=0):
+                 frames="sampled", every_n=1, sampling="uniform", sampling_seed=0, gating=False):
         world = 1
         if process_group is not None and torch.distributed.is_available() and torch.distributed.is_initialized():
             world = torch.distributed.get_world_size(process_group)
         check_netvlad_frames(frames, every_n, max_frames, world=world, sampling=sampling)   # (before the device is touched)
+        check_netvlad_gating(gating, world)
+        self.gating = bool(gating)
         self.frames, self.every_n = frames, int(every_n)
         self.sampling, self.sampling_seed = sampling, int(sampling_seed)
         self.last_frame_table = None       # the source-frame table of the last batch (sampling != "uniform"), for tests and diagnostics
@@ -601,12 +612,15 @@ class NetVladTower(TowerBase):
         if frames == "sampled" and iterations > 64:                  # (grid mode does not read iterations)
             raise ValueError("iterations=%d: the aggregation kernel holds at most 64 sampled frames per video" % iterations)
         F, K, H = feature_size, cluster_size, hidden_size
-        shapes = self.variable_shapes(F, vocab_size, K, H, num_mixtures)
+        shapes = self.variable_shapes(F, vocab_size, K, H, num_mixtures, gating=self.gating)
         self.buffers = OrderedDict()
         self._setup_store(shapes)
         self.bn_in = BatchNorm(self, "input_bn", F)
         self.bn_cl = BatchNorm(self, "cluster_bn", K)
         self.bn_h = BatchNorm(self, "hidden1_bn", H)
+        if self.gating:
+            self.bn_g = BatchNorm(self, "gating_bn", H)
+            self.global_grad_names = type(self).global_grad_names + ("gating_bn/beta", "gating_bn/gamma")
         self.moe = MoeHead(self, H, vocab_size, num_mixtures)
         gen = torch.Generator(device="cpu")
         gen.manual_seed(seed)
@@ -616,19 +630,24 @@ class NetVladTower(TowerBase):
                 p.copy_(torch.randn(shp, generator=gen, dtype=F32) / math.sqrt(F))
             elif k == self.HW:
                 p.copy_(torch.randn(shp, generator=gen, dtype=F32) / math.sqrt(K))
+            elif k == self.GW:
+                continue                                             # drawn behind every other variable, below
             elif len(shp) == 2:
                 lim = math.sqrt(6.0 / (shp[0] + shp[1]))
                 p.copy_((torch.rand(shp, generator=gen, dtype=F32) * 2 - 1) * lim)
             elif k.endswith("/gamma"):
                 p.fill_(1.0)
+        if self.gating:                                              # (after the others: the draws of a tower without the gate keep their values)
+            self.store.p(self.GW).copy_(torch.randn((H, H), generator=gen, dtype=F32) / math.sqrt(H))
         self.refresh_shadows()
         if not training and frames == "grid":
             self.store.drop_training_state()                         # forward only: the masters alone
         self._alloc(batch_size)
 
     @classmethod
-    def variable_shapes(cls, feature_size, vocab_size, cluster_size, hidden_size, num_mixtures):
-        """The trainable variables and their INTERNAL shapes, in store order, from the size flags alone (no device)."""
+    def variable_shapes(cls, feature_size, vocab_size, cluster_size, hidden_size, num_mixtures, gating=False):
+        """The trainable variables and their INTERNAL shapes, in store order, from the size flags alone (no device).  gating: with the
+        context gate's variables behind hidden1_bn's."""
         F, K, H = feature_size, cluster_size, hidden_size
         shapes = OrderedDict()
         shapes.update(BatchNorm.shapes("input_bn", F))
@@ -637,13 +656,17 @@ class NetVladTower(TowerBase):
         shapes[cls.C2] = (K, F)                                      # centres, stored [K][F] (tf: [1, F, K])
         shapes[cls.HW] = (H, K * F)                                  # stored transposed, columns cluster-major (k*F + f)
         shapes.update(BatchNorm.shapes("hidden1_bn", H))
+        if gating:
+            shapes[cls.GW] = (H, H)                                  # stored transposed [out][in]
+            shapes.update(BatchNorm.shapes("gating_bn", H))
         shapes.update(MoeHead.shapes(H, vocab_size, num_mixtures))
         return shapes
 
     @classmethod
     def checkpoint_shapes(cls, *sizes, **kw):
         """What state_dict() holds for these size flags, without the scope prefix: every variable in its TF layout (2-D weights
-        [in][out]) and the batch norms' moving statistics.  For checking a checkpoint against the flags before a tower is built."""
+        [in][out]) and the batch norms' moving statistics.  For checking a checkpoint against the flags before a tower is built.
+        gating=True: with the context gate's names."""
         out = OrderedDict()
         for k, shp in cls.variable_shapes(*sizes, **kw).items():
             out[k] = tuple(reversed(shp)) if len(shp) == 2 else tuple(shp)
@@ -702,8 +725,20 @@ class NetVladTower(TowerBase):
         self.Y_bf = torch.zeros((self.Bk, K * F), dtype=BF16, device=dev)
         self.hid = torch.empty((B, H), dtype=F32, device=dev)
         self.h6 = torch.empty((B, H), dtype=F32, device=dev)
+        if self.gating:
+            self.h6_bf = torch.zeros((self.Bk, H), dtype=BF16, device=dev)      # (rows B .. Bk stay zeros: an operand of the TN product)
+            self.gl = torch.empty((B, H), dtype=F32, device=dev)
+            self.gated = torch.empty((B, H), dtype=F32, device=dev)
+            if not self.fused_gate:
+                self.gn = torch.empty((B, H), dtype=F32, device=dev)
         self.moe.alloc(B, self.training)
         if self.training:
+            if self.gating:
+                self.dgl_bf = torch.zeros((self.Bk, H), dtype=BF16, device=dev)
+                self.dh6_via = torch.empty((B, H), dtype=F32, device=dev)
+                self.dh6_direct = torch.empty((B, H), dtype=F32, device=dev)
+                if not self.fused_gate:
+                    self.dgn = torch.empty((B, H), dtype=F32, device=dev)
             self.dhid_bf = torch.zeros((self.Bk, H), dtype=BF16, device=dev)
             self.dY = torch.empty((B, K * F), dtype=F32, device=dev)
             self.dV = torch.empty((B, K, F), dtype=F32, device=dev)
@@ -777,16 +812,47 @@ class NetVladTower(TowerBase):
         ops.netvlad_normalize_fwd(self.Vv, B, K, F, self.n1, self.n2, self.Y_bf)
         ops.gemm_nt(self.Y_bf, self.shadow_fwd[self.HW], B, H, K * F, self.hid)
         self.bn_h.stats(self.hid, B, is_training)
-        ops.bn_apply(self.hid, B, H, self.bn_h.mean, self.bn_h.var, self.bn_h.gamma(), self.bn_h.beta(), True, y_f32=self.h6)
+        if not self.gating:
+            ops.bn_apply(self.hid, B, H, self.bn_h.mean, self.bn_h.var, self.bn_h.gamma(), self.bn_h.beta(), True, y_f32=self.h6)
+            head_in = self.h6
+        else:
+            bg = self.bn_g
+            ops.bn_apply(self.hid, B, H, self.bn_h.mean, self.bn_h.var, self.bn_h.gamma(), self.bn_h.beta(), True, y_f32=self.h6, y_bf16=self.h6_bf)
+            ops.gemm_nt(self.h6_bf, self.shadow_fwd[self.GW], B, H, H, self.gl)
+            bg.stats(self.gl, B, is_training)
+            if self.fused_gate:
+                ops.bn_gate_fwd(self.gl, self.h6, B, H, bg.mean, bg.var, bg.gamma(), bg.beta(), self.gated)
+            else:
+                ops.bn_apply(self.gl, B, H, bg.mean, bg.var, bg.gamma(), bg.beta(), False, y_f32=self.gn)
+                ops.nextvlad_gate_fwd(self.h6[:B], self.gn[:B], self.gated[:B])
+            head_in = self.gated
         self._taped = self.training and is_training
         if B == self.cap:
-            return self.moe.forward(self.h6)
-        return self.moe.forward(self.h6[:B], rows=B)[:B]      # (a forward-only grid tower on fewer videos than it was allocated for)
+            return self.moe.forward(head_in)
+        return self.moe.forward(head_in[:B], rows=B)[:B]      # (a forward-only grid tower on fewer videos than it was allocated for)
 
     def grad_stages(self):
         moe = [MoeHead.GATES, MoeHead.EXPERTS, MoeHead.EBIAS]
         hidden = [self.HW, "hidden1_bn/beta", "hidden1_bn/gamma"]
+        if self.gating:
+            hidden += [self.GW, "gating_bn/beta", "gating_bn/gamma"]
         return moe, hidden, [k for k in self.names if k not in moe and k not in hidden]
+
+    def _gate_backward(self, e, dstate):
+        """The context gate's backward; e (+ dstate) is the gradient on `state`.  Leaves dh6_direct = e * g and dh6_via = dgl_bf . Wg^T,
+        hidden1_bn's dy / dy2, and the gradients of gating_weights and gating_bn."""
+        B, H, st, bg = self.B, self.Hd, self.store, self.bn_g
+        stats = (bg.mean, bg.var, bg.gamma(), bg.beta())
+        dgamma, dbeta = st.g("gating_bn/gamma"), st.g("gating_bn/beta")
+        if self.fused_gate:
+            ops.bn_gate_bwd_partial(self.gl, self.h6, e, dstate, B, H, *stats, bg.ws, self.dh6_direct)
+            ops.bn_gate_bwd_finalize(self.gl, self.h6, e, dstate, B, bg.R_total, H, *stats, bg.ws, dgl_bf16=self.dgl_bf, dgamma=dgamma, dbeta=dbeta)
+        else:
+            ops.nextvlad_gate_bwd_add(self.h6, self.gn, e, dstate, self.dh6_direct, dgl=self.dgn)
+            ops.bn_bwd_partial(self.gl, self.dgn, B, H, *stats, False, bg.ws)
+            ops.bn_bwd_finalize(self.gl, self.dgn, B, bg.R_total, H, *stats, False, bg.ws, dx_bf16=self.dgl_bf, dgamma=dgamma, dbeta=dbeta)
+        ops.gemm_tn(self.dgl_bf, self.h6_bf, H, H, self.Bk, st.g(self.GW))                # dWg^T [out][in] = dgl^T . h6
+        ops.gemm_nt(self.dgl_bf, self.shadow_bwd[self.GW], B, H, H, self.dh6_via)
 
     def backward(self, dpred, on_moe_grads_ready=None, moe_weight_grads=True, on_stage=None, dstate=None):
         """dstate (None or [B, H] f32): a gradient on `state` itself, added to the MoE head's d(h6) in front of the relu6 mask of
@@ -803,7 +869,10 @@ class NetVladTower(TowerBase):
             on_moe_grads_ready()
         if on_stage is not None:
             on_stage(0)
-        if dstate is None:
+        if self.gating:
+            self._gate_backward(dh6, dstate)
+            self.bn_h.backward(self.hid, self.dh6_direct, B, True, dx_bf16=self.dhid_bf, dy2=self.dh6_via)
+        elif dstate is None:
             self.bn_h.backward(self.hid, dh6, B, True, dx_bf16=self.dhid_bf)
         else:
             self.bn_h.backward(self.hid, dh6, B, True, dx_bf16=self.dhid_bf, dy2=dstate)
@@ -834,12 +903,21 @@ class NetVladTower(TowerBase):
 
     @property
     def state(self):
-        """The tower's representation, what its MoE head reads: h6 = relu6(hidden1_bn(hid)), [B, H] f32."""
-        return self.h6 if self.B == self.cap else self.h6[:self.B]
+        """The tower's representation, what its MoE head reads, [B, H] f32: h6 = relu6(hidden1_bn(hid)), or with the gate
+        h6 * sigmoid(gating_bn(bf16(h6) . gating_weights))."""
+        s_ = self.gated if self.gating else self.h6
+        return s_ if self.B == self.cap else s_[:self.B]
 
     @property
     def rowsum(self):
         return self.moe.rowsum if self.B == self.cap else self.moe.rowsum[:self.B]
+
+
+def check_netvlad_gating(gating, world=1):
+    """--netvlad_gating on more than one rank is refused; touches no device."""
+    if gating and world > 1:
+        raise ValueError("--netvlad_gating True refuses a process group of %d ranks: data parallelism is not built for the context gate "
+                         "(gating_bn's statistics and gating_weights' gradient stay on one rank)" % world)
 
 
 def check_netvlad_frames(frames, every_n, max_frames, model=None, world=1, precision="bf16", sampling="uniform"):

@@ -47,7 +47,7 @@ from . import eval_util, frame_level_models, losses, ops, readers, video_level_m
 from .distill import (DistillGraph, EnsembleDistillGraph, NetVladDistillGraph, NeXtVladDistillGraph, OfflineDistillGraph, SerialStudentsGraph,
                       SingleTowerGraph)
 from .flags import FLAGS, GetListOfFeatureNamesAndSizes
-from .towers import DbofTower, LogisticTower, NetVladTower, NeXtVladTower, check_netvlad_frames, check_nextvlad_frames
+from .towers import DbofTower, LogisticTower, NetVladTower, NeXtVladTower, check_netvlad_frames, check_netvlad_gating, check_nextvlad_frames
 
 NUM_CLASSES = 4716       # readers.YT8MFrameFeatureReader default num_classes (cs/readers.py:121)
 
@@ -502,6 +502,43 @@ def netvlad_sampling_metadata(graph):
     return out
 
 
+def netvlad_gating_metadata(graph):
+    """The checkpoint keys of the NetVLAD context gate, only when true: netvlad_gating for the one tower of a
+    SingleTowerGraph or the student of a distillation, teacher_netvlad_gating for its frozen teacher."""
+    out = {}
+    tw = getattr(graph, "tower", None)
+    if isinstance(tw, NetVladTower) and tw.gating:
+        out["netvlad_gating"] = True
+    if isinstance(graph, NetVladDistillGraph):
+        if graph.gating:
+            out["netvlad_gating"] = True
+        if graph.teacher_gating:
+            out["teacher_netvlad_gating"] = True
+    return out
+
+
+def check_netvlad_gating_checkpoint(sd, scope, what):
+    """--netvlad_gating against the ``scope``/* tower of a checkpoint that training resumes from: a ValueError naming the flag and the
+    variable found or missing when they disagree (no device)."""
+    from .distill import netvlad_checkpoint_gating
+    have, key = netvlad_checkpoint_gating(sd, scope), "%s/%s" % (scope, NetVladTower.GW)
+    if have and not FLAGS.netvlad_gating:
+        raise ValueError("--netvlad_gating False, but %s holds the variable %s: resume it with --netvlad_gating True" % (what, key))
+    if FLAGS.netvlad_gating and not have:
+        raise ValueError("--netvlad_gating True, but %s holds no variable %s: it was trained without the context gate" % (what, key))
+
+
+def check_netvlad_gating_flags(world=1, serial=False):
+    """--netvlad_gating before the device is touched: refused on several ranks; on resume of a NetVLAD tower trained alone, the flag
+    against --train_dir's latest checkpoint (a distillation's resume is checked by netvlad_distill_source)."""
+    if FLAGS.model != "NetVLADModel":
+        return
+    check_netvlad_gating(FLAGS.netvlad_gating, world)
+    ck = None if (FLAGS.start_new_model or serial) else latest_checkpoint(FLAGS.train_dir)
+    if ck is not None:
+        check_netvlad_gating_checkpoint(torch.load(ck, map_location="cpu"), "model", "--train_dir %s: %s" % (FLAGS.train_dir, os.path.basename(ck)))
+
+
 def netvlad_teacher_sampling(sd):
     """(word, seed) the model/* tower of the checkpoint dict ``sd`` runs on as a frozen teacher: the teacher_sampling a distillation
     checkpoint records (its model/* IS such a teacher), else the student_sampling a grid tower trained alone records; "uniform" without
@@ -525,8 +562,10 @@ def netvlad_teacher_every_n(sd):
 def netvlad_distill_source(feature_size):
     """The checkpoint the frozen NetVLAD teacher comes from, read on the host before the device is touched: --train_dir's latest on
     resume, else --teacher_dir's; its model/* variables against the size flags (distill.check_netvlad_checkpoint).  Returns {"ck", "sd",
-    "teacher_every_n", "resume"}."""
-    from .distill import check_netvlad_checkpoint
+    "teacher_every_n", "resume", "teacher_sampling", "teacher_gating"}.  teacher_gating: whether model/* holds the context gate's
+    variables - the frozen teacher is built as its checkpoint says, the student as --netvlad_gating says; on resume the
+    flag must agree with model_student/*, and --student_init_from_teacher needs the two gates to agree."""
+    from .distill import check_netvlad_checkpoint, netvlad_checkpoint_gating
     resume = None if FLAGS.start_new_model else latest_checkpoint(FLAGS.train_dir)
     ck = resume or latest_checkpoint(FLAGS.teacher_dir)
     if ck is None:
@@ -535,9 +574,15 @@ def netvlad_distill_source(feature_size):
     what = "--teacher_dir %s: %s" % (FLAGS.teacher_dir, os.path.basename(ck))
     if not any(k.startswith("model/") and torch.is_tensor(v) for k, v in sd.items()):
         raise ValueError("%s holds no model/* variables (not a teacher checkpoint)" % what)
-    check_netvlad_checkpoint(sd, "model", feature_size, NUM_CLASSES, netvlad_size_flags(), what)
+    teacher_gating = netvlad_checkpoint_gating(sd, "model")
+    check_netvlad_checkpoint(sd, "model", feature_size, NUM_CLASSES, netvlad_size_flags(), what, gating=teacher_gating)
+    if resume is not None:
+        check_netvlad_gating_checkpoint(sd, "model_student", "--train_dir %s: %s" % (FLAGS.train_dir, os.path.basename(ck)))
+    elif FLAGS.student_init_from_teacher and teacher_gating != bool(FLAGS.netvlad_gating):
+        raise ValueError("--student_init_from_teacher True with --netvlad_gating %s: the teacher of %s was trained %s the context gate, "
+                         "its variables do not fill this student" % (FLAGS.netvlad_gating, what, "with" if teacher_gating else "without"))
     return dict(ck=ck, sd=sd, teacher_every_n=netvlad_teacher_every_n(sd), resume=resume is not None,
-                teacher_sampling=netvlad_teacher_sampling(sd))
+                teacher_sampling=netvlad_teacher_sampling(sd), teacher_gating=teacher_gating)
 
 
 def load_frozen_teacher(graph, teacher_dir):
@@ -566,7 +611,7 @@ def check_label_loss(label_loss_fn, finetune=False):
 
 
 def build_graph(model, label_loss_fn, feature_size, batch_size, every_n, device, finetune=False, process_group=None, students=_UNSET,
-                teachers=None, offline=None, teacher_every_n=1, teacher_sampling=("uniform", 0)):
+                teachers=None, offline=None, teacher_every_n=1, teacher_sampling=("uniform", 0), teacher_gating=False):
     """Equivalent of cs/train.py:185-427 (and cs/train_finetune.py:185-331 when
     finetune): returns the graph object whose ``step`` runs one iteration."""
     check_label_loss(label_loss_fn, finetune)
@@ -641,6 +686,8 @@ def build_graph(model, label_loss_fn, feature_size, batch_size, every_n, device,
         if netvlad_sampling_word() != "uniform" or teacher_sampling[0] != "uniform":      # (uniform: the call of 7.19)
             common.update(student_sampling=netvlad_sampling_word(), sampling_seed=FLAGS.student_sampling_seed,
                           teacher_sampling=teacher_sampling[0], teacher_sampling_seed=teacher_sampling[1])
+        if FLAGS.netvlad_gating or teacher_gating:                   # (neither: the call of 7.19)
+            common.update(gating=FLAGS.netvlad_gating, teacher_gating=teacher_gating)
         return NetVladDistillGraph(batch_size, every_n=every_n, teacher_every_n=teacher_every_n, feature_size=feature_size,
                                    vocab_size=NUM_CLASSES, max_frames=FLAGS.max_num_frames, cluster_size=cs, hidden_size=hs,
                                    num_mixtures=mx, device=device, precision=FLAGS.precision, distill_losses=FLAGS.distill_losses, **common)
@@ -657,7 +704,7 @@ def build_graph(model, label_loss_fn, feature_size, batch_size, every_n, device,
         tw = NetVladTower(batch_size, FLAGS.max_num_frames, feature_size, NUM_CLASSES, FLAGS.iterations, FLAGS.netvlad_cluster_size,
                           FLAGS.netvlad_hidden_size, FLAGS.moe_num_mixtures, device=device, process_group=process_group,
                           frames=FLAGS.netvlad_frames, every_n=every_n, sampling=netvlad_sampling_word(warn=True),
-                          sampling_seed=FLAGS.student_sampling_seed)
+                          sampling_seed=FLAGS.student_sampling_seed, gating=FLAGS.netvlad_gating)
         _apply_precision(tw)
         return SingleTowerGraph(tw, **common)
     if isinstance(model, frame_level_models.NeXtVLADModel):         # extension (the reference's class is an empty stub)
@@ -762,6 +809,7 @@ def save_checkpoint(graph, train_dir, rank):
     if isinstance(graph, NetVladDistillGraph):    # the same for the NetVLAD family (distill_losses: recorded above, mode "serial")
         sd["netvlad_frames"], sd["every_n"], sd["teacher_every_n"] = "grid", graph.every_n, graph.teacher_every_n
     sd.update(netvlad_sampling_metadata(graph))   # metadata: the --student_sampling word of a NetVLAD tower off the uniform grid
+    sd.update(netvlad_gating_metadata(graph))     # metadata: --netvlad_gating of the tower / student and the frozen teacher's gate, when true
     sd.update(nextvlad_dropout_metadata(graph))   # metadata: --nextvlad_dropout and its seed, when the tower was trained with a non-zero rate
     fn = getattr(graph, "label_loss", None)
     if fn is not None and not losses.is_default(fn):            # metadata: the --label_loss these weights were trained on (the default: no key)
@@ -838,6 +886,7 @@ def main(argv=None):
     check_nextvlad_frames(FLAGS.nextvlad_frames, FLAGS.every_n, FLAGS.max_num_frames, model=FLAGS.model, world=world, precision=FLAGS.precision)
     check_netvlad_frames(FLAGS.netvlad_frames, FLAGS.every_n, FLAGS.max_num_frames, model=FLAGS.model, world=world, precision=FLAGS.precision,
                          sampling=netvlad_sampling_word())
+    check_netvlad_gating_flags(world, serial=bool(serial))
     nx_src = None
     if nx_distill:
         # the teacher's checkpoint on the host - its grid and its shapes against the size flags -, before the device is touched
@@ -889,7 +938,8 @@ def main(argv=None):
         raise NotImplementedError("only AdamOptimizer (the reference default, cs/train.py:91) is built")
     graph = build_graph(model, label_loss_fn, feature_size, FLAGS.batch_size, FLAGS.every_n, device, finetune, students=multi, teachers=ens,
                         offline=offline, teacher_every_n=nx_src["teacher_every_n"] if nx_src else 1,
-                        teacher_sampling=(nx_src or {}).get("teacher_sampling", ("uniform", 0)))
+                        teacher_sampling=(nx_src or {}).get("teacher_sampling", ("uniform", 0)),
+                        teacher_gating=(nx_src or {}).get("teacher_gating", False))
     if offline:
         graph.teacher_record = offline_record(offline)
     logging.info("%s: Built graph.", task)

@@ -103,8 +103,10 @@ def netvlad_source(reader, student_only=False):
     checkpoint - its variables against the size flags, and the grid it records.  Returns {"ck", "sd", "tower", "every_n",
     "teacher_every_n"}: tower 'both' for a distillation checkpoint (model/* and model_student/* - the student's metrics
     at the recorded every_n, student_state_loss logged against the teacher at the recorded teacher_every_n), 'teacher' for a single-tower
-    one; --netvlad_serve_every_n overrides the served tower's grid only."""
-    from .distill import check_netvlad_checkpoint
+    one; --netvlad_serve_every_n overrides the served tower's grid only.  "gating" / "teacher_gating" (DESIGN.md 7.21): the context gate of
+    the served tower and of the teacher next to a served student, each read from its scope's own variables; --netvlad_gating is not
+    consulted, a flag that disagrees with the served tower is logged as a warning."""
+    from .distill import check_netvlad_checkpoint, netvlad_checkpoint_gating
     if student_only:
         raise ValueError("eval_finetune with --model NetVLADModel: there is no convert / finetune step for this family, so no "
                          "student-only checkpoint to evaluate")
@@ -118,14 +120,20 @@ def netvlad_source(reader, student_only=False):
         raise IOError("unable to find a checkpoint at location: %s" % FLAGS.train_dir)
     sd = torch.load(ck, map_location="cpu")
     both = any(k.startswith("model_student/") and torch.is_tensor(v) for k, v in sd.items())
+    gates = {}
     for scope in ("model", "model_student") if both else ("model",):
+        gates[scope] = netvlad_checkpoint_gating(sd, scope)
         check_netvlad_checkpoint(sd, scope, sum(reader.feature_sizes), reader.num_classes,
-                                 (FLAGS.netvlad_cluster_size, FLAGS.netvlad_hidden_size, FLAGS.moe_num_mixtures), ck)
+                                 (FLAGS.netvlad_cluster_size, FLAGS.netvlad_hidden_size, FLAGS.moe_num_mixtures), ck, gating=gates[scope])
+    gating = gates["model_student" if both else "model"]
+    if bool(FLAGS.netvlad_gating) != gating:
+        logging.warning("--netvlad_gating %s, but the served tower of %s was trained %s the context gate (the checkpoint's variables are used)",
+                        FLAGS.netvlad_gating, ck, "with" if gating else "without")
     teacher_every_n = int(sd.get("teacher_every_n", 1)) if both else 1
     #  the served tower runs on --student_sampling; the teacher next to a served student stays on what the checkpoint records
     teacher_sampling = (sd.get("teacher_sampling", "uniform"), int(sd.get("teacher_sampling_seed", 0))) if both else ("uniform", 0)
     return dict(ck=ck, sd=sd, tower="both" if both else "teacher", every_n=netvlad_every_n(sd, FLAGS.netvlad_serve_every_n, ck),
-                teacher_every_n=teacher_every_n, teacher_sampling=teacher_sampling)
+                teacher_every_n=teacher_every_n, teacher_sampling=teacher_sampling, gating=gating, teacher_gating=gates["model"])
 
 
 def build_graph(reader, model, batch_size, device, student_only=False, label_loss=None, nextvlad=None, netvlad=None):
@@ -140,7 +148,8 @@ def build_graph(reader, model, batch_size, device, student_only=False, label_los
                                 precision=FLAGS.precision, label_loss=label_loss, tower=src.get("tower", "teacher"),
                                 teacher_every_n=src.get("teacher_every_n", 1), student_sampling=FLAGS.student_sampling,
                                 sampling_seed=FLAGS.student_sampling_seed, teacher_sampling=src.get("teacher_sampling", ("uniform", 0))[0],
-                                teacher_sampling_seed=src.get("teacher_sampling", ("uniform", 0))[1])
+                                teacher_sampling_seed=src.get("teacher_sampling", ("uniform", 0))[1], gating=src.get("gating", False),
+                                teacher_gating=src.get("teacher_gating", False))
     if isinstance(model, frame_level_models.NeXtVLADModel):
         from . import inference
         src = nextvlad if nextvlad is not None else nextvlad_source(reader, student_only)

@@ -718,6 +718,23 @@ int evc_bn_relu6_bwd(const float* x, const float* dy, int R, int C, const float*
                      const float* gamma, const float* beta, int relu6, const int32_t* argmax, int S,
                      double* ws /* 2*C, zeroed inside */,
                      float* dx_f32, evc_bf16* dx_bf16, float* dgamma, float* dbeta, void* stream);
+/* Context gate behind a batch norm (NetVLAD's gating_bn), gl / h / d / d2 / out / dh [R][C] f32:
+ *   _fwd:          out = h * sigmoid(bn(gl)), bn = evc_bn_apply's expression without relu6; one pass, 16-byte accesses when C % 4 == 0 and
+ *                  every base is 16-byte aligned, scalar otherwise.
+ *   _bwd_partial:  evc_bn_bwd_partial (relu6 = 0, no argmax) on dy = e * h * g * (1 - g), e = d or d + d2 (one f32 add, in that order),
+ *                  g = sigmoid(bn(gl)) recomputed; also stores dh = e * g, the gradient on h through the product.
+ *   _bwd_finalize: evc_bn_bwd_finalize on the same dy -> dgl f32 / bf16, dgamma, dbeta (each output may be NULL).
+ * The bits of evc_bn_apply, evc_nextvlad_gate_fwd, evc_nextvlad_gate_bwd_add and evc_bn_bwd_partial / _finalize run one after another,
+ * with neither bn(gl), g nor dy in memory.  d2 may be NULL.  Refused before any launch: R < 1, C < 1, R_total < R (EVC_ERR_BAD_SHAPE),
+ * any other NULL operand (EVC_ERR_BAD_ARG). */
+int evc_bn_gate_fwd(const float* gl, const float* h, int R, int C, const float* mean, const float* var, const float* gamma,
+                    const float* beta, float* out, void* stream);
+int evc_bn_gate_bwd_partial(const float* gl, const float* h, const float* d, const float* d2, int R, int C, const float* mean,
+                            const float* var, const float* gamma, const float* beta, double* ws /* 2*C, zeroed inside */, float* dh,
+                            void* stream);
+int evc_bn_gate_bwd_finalize(const float* gl, const float* h, const float* d, const float* d2, int R, int R_total, int C,
+                             const float* mean, const float* var, const float* gamma, const float* beta, const double* ws,
+                             float* dgl_f32, evc_bf16* dgl_bf16, float* dgamma, float* dbeta, void* stream);
 /* cluster_bn + relu6 + FramePooling('max') in one pass over act [B][S][C] (cs/frame_level_models.py:149-167). */
 int evc_bn_relu6_framepool_fwd(const float* act, int B, int S, int C, const float* mean, const float* var,
                                const float* gamma, const float* beta, float* pooled_f32, evc_bf16* pooled_bf16,
