@@ -7,7 +7,7 @@ Rows of length 0 drop out of the input pass and of every L1 kernel (RowPlan.P = 
 the final state of rows no step touches.  What such a row's tower then predicts is never looked at: ops.cascade_confidence_rows copies
 into the merged matrix only the rows the stage ran.
 
-A NeXtVLAD stage (distill.NeXtVladEvalGraph) takes the same step: its settled rows leave the packed frame rows and - the
+A NeXtVLAD stage (vlad_graphs.NeXtVladEvalGraph) takes the same step: its settled rows leave the packed frame rows and - the
 graph serving only the videos that have a frame - everything behind the aggregation too.
 
 The gate is ops.cascade_confidence_rows + ops.cascade_pick_rows (csrc/evc_cascade.hip).  Its result has to reach the host, because the

@@ -467,6 +467,30 @@ class _StepGraph:
         return (exponential_decay(self.lr0, self.global_step, batch_size * self.world, self.lr_decay_examples, self.lr_decay),
                 self.reg_pen * 1e-8)
 
+    def _fuse_moe_update(self, apply, moe, precision, dp=False):
+        """(fuse, fused_names) of a single-tower step (SingleTowerGraph, vlad_graphs.GridDistillGraph): whether its update takes the MoE
+        head's two matrices through MoeHead's fused clip + Adam pass (their gradient recomputed from its rank-B factors) - whenever the step
+        also applies -, and the variables that pass updates (the bias gradient comes from the same factors).  dp: data parallel."""
+        fuse = bool(apply and self.fused_moe_update and moe is not None and moe.can_fuse_update() and moe.prefer_fused_update(dp)
+                    and precision == "bf16")
+        return fuse, ((moe.GATES, moe.EXPERTS, moe.EBIAS) if fuse else ())
+
+    def _update_tower(self, tw, moe, B, fuse, fused_names, route_rs=False, dp=None):
+        """The train op of a single-tower step behind tw.backward: the fused MoE update (route_rs: on the owners' slabs of a bf16
+        reduce-scatter) and clip_by_norm + TF-Adam on the tower's other variables, or the latter on all of them; global_step += 1.
+        dp: the GradReducer of a data-parallel step, None on one rank."""
+        lr, l2c = self._lr_l2c(B)
+        if fuse:
+            tw.begin_update()
+            if route_rs:
+                moe.sharded_update(tw.adam_lr_t(lr), self.clip, l2c, dp)
+            else:
+                moe.fused_update(tw.adam_lr_t(lr), self.clip, l2c, dp=dp)
+            tw.apply_group([k for k in tw.names if k not in fused_names], lr, self.clip, l2c)
+        else:
+            tw.apply_gradients(lr, self.clip, l2c)
+        self.global_step += 1
+
     def _on_main(self, inputs, num_frames_host, body):
         """Runs ``body(host frame counts)`` on the graph's own main stream, ordered after the caller's current stream on entry
         and before it on exit (so callers see ordinary single-stream semantics).  ``inputs``: the caller's tensors the step reads
@@ -1468,6 +1492,7 @@ def member_graph(batch_size, member, kw):
     num_mixtures, device, precision and label_loss from kw."""
     tower, every_n = member[0], member[1]
     if len(member) > 3 and member[3] is not None:
+        from .vlad_graphs import NeXtVladEvalGraph
         shared = {k: kw[k] for k in ("feature_size", "vocab_size", "max_frames", "num_mixtures", "device", "precision", "label_loss") if k in kw}
         return NeXtVladEvalGraph(batch_size, tower=tower, every_n=every_n, student_sampling=member[2] or "uniform", **shared, **member[3])
     mkw = dict(kw)
@@ -1554,7 +1579,6 @@ class SingleTowerGraph(_StepGraph):
         """x_raw [B,T,F] float32 or uint8 (as the reader delivers it: Dequantize is fused into the input kernels).
         num_frames_host: the frame counts on the host, for a NeXtVladTower / NetVladTower in grid mode (its packed rows are laid out from them
         without a device sync; no draw is made in that mode)."""
-        from .towers import DbofGenericTower, DbofTower, NetVladTower, NeXtVladTower
         B, V = labels_u8.shape
         if self._dp is None or self._dp.shape[0] != B:
             self._dp = torch.empty((B, V), dtype=F32, device=self.device)
@@ -1562,13 +1586,10 @@ class SingleTowerGraph(_StepGraph):
         if self.dp and B != tw.B:
             raise ValueError("data-parallel step on %d videos, the tower was built for %d per rank (ragged batches are not "
                              "allowed under data parallelism: drop the remainder)" % (B, tw.B))
-        # (a NeXtVLAD tower's dropout mask is a function of the step: a restored run draws the same masks)
-        kw = {"dropout_step": self.global_step} if isinstance(tw, NeXtVladTower) else {}
-        if isinstance(tw, NetVladTower) and tw.sampling != "uniform":
-            kw = {"draw": self.global_step, "row0": 0}       # ("random" frames are a function of the step too)
-        if isinstance(tw, (NetVladTower, NeXtVladTower)) and tw.frames == "grid":
+        kw = tw.step_kwargs(self.global_step)        # (what the tower's forward derives from the step: a dropout mask, "random" frames)
+        if tw.frames == "grid":
             pred = tw.forward(x_raw, num_frames, num_frames_host=num_frames_host, **kw)
-        elif isinstance(tw, (DbofTower, NetVladTower, NeXtVladTower, DbofGenericTower)):
+        elif tw.takes_uniform_draw:
             if uniform is None:     # (SampleRandomSequence draws one start per video: column 0 is used)
                 uniform = torch.rand((B, tw.S), dtype=F32, device=self.device)
             self.last_uniform = uniform              # the tf.random_uniform draw of this step (SampleRandomFrames)
@@ -1577,9 +1598,7 @@ class SingleTowerGraph(_StepGraph):
             pred = tw.forward(x_raw, num_frames)
         self.losses.zero_()
         self.label_loss.fused(pred, labels_u8, self.losses[0:1], self._dp, grad_scale=1.0 / (B * self.world))
-        fuse = (apply and self.fused_moe_update and self.moe is not None and self.moe.can_fuse_update()
-                and self.moe.prefer_fused_update(self.dp)
-                and tw.precision == "bf16")
+        fuse, fused_names = self._fuse_moe_update(apply, self.moe, tw.precision, self.dp)
         if self.moe is not None and not fuse and getattr(self.moe, "_stale", False):
             raise RuntimeError("the MoE weights are sharded over the ranks (fused data-parallel update); call consolidate() "
                                "on every rank before a step that does not apply through it")
@@ -1588,8 +1607,7 @@ class SingleTowerGraph(_StepGraph):
         route_rs = bool(fuse and self.dp and self.moe.dp_route(self.reducer.shard_world) == "reduce_scatter")
         main = torch.cuda.current_stream(self.device)
         stages = tw.grad_stages()
-        fused_names = (self.moe.GATES, self.moe.EXPERTS, self.moe.EBIAS) if fuse else ()    # (the bias gradient comes from the same factors)
-        skip = tuple(getattr(tw, "global_grad_names", ())) + fused_names
+        skip =tuple(getattr(tw, "global_grad_names", ())) + fused_names
 
         def on_stage(i):
             # data parallel: SUM of this stage's per-rank gradients on the side stream, in stream order behind the kernels
@@ -1605,523 +1623,18 @@ class SingleTowerGraph(_StepGraph):
         if self.dp:
             main.wait_stream(self._aux)
         if apply:
-            lr, l2c = self._lr_l2c(B)
-            if fuse:
-                tw.begin_update()
-                if route_rs:
-                    self.moe.sharded_update(tw.adam_lr_t(lr), self.clip, l2c, self.reducer)
-                else:
-                    self.moe.fused_update(tw.adam_lr_t(lr), self.clip, l2c, dp=self.reducer if self.dp else None)
-                tw.apply_group([k for k in tw.names if k not in fused_names], lr, self.clip, l2c)
-            else:
-                tw.apply_gradients(lr, self.clip, l2c)
-            self.global_step += 1
+            self._update_tower(tw, self.moe, B, fuse, fused_names, route_rs, self.reducer if self.dp else None)
         return {"predictions": pred, "loss": self.losses[0], "global_step": self.global_step}
 
 
-def _world_of(process_group):
-    """Ranks of a process group without touching a device (None: the default group when one is initialised, else 1)."""
-    if process_group is not None and hasattr(process_group, "size"):
-        return int(process_group.size())
-    if torch.distributed.is_available() and torch.distributed.is_initialized():
-        return int(torch.distributed.get_world_size(process_group))
-    return 1
+# The VLAD families' graphs and checkpoint checks live in vlad_graphs (which builds on this module); their public names stay importable
+# from here.
+_VLAD_GRAPHS = ("GridDistillGraph", "GridEvalGraph", "NeXtVladDistillGraph", "NetVladDistillGraph", "NeXtVladEvalGraph", "NetVladEvalGraph",
+                "check_vlad_checkpoint", "check_nextvlad_checkpoint", "check_netvlad_checkpoint", "netvlad_checkpoint_gating")
 
 
-class NeXtVladDistillGraph(_StepGraph):
-    """Serial distillation for the NeXtVLAD family: a grid student (frames j * every_n of every video, scope
-    'model_student') against a FROZEN grid teacher (every teacher_every_n-th real frame, scope 'model': forward only, batch norms on the
-    checkpoint's moving statistics, no gradient store / moments / tape, never written).  One step on one stream: teacher forward,
-    student forward, the loss section of DistillGraph's mode 'serial' (ops.distill_losses on the towers' gated hidden vectors and
-    predictions, the same scales), the student's backward with dL_REP/dstate joining the MoE head's gradient at `out`, and the update
-    exactly as SingleTowerGraph.step performs it; global_step += 1.  Reporting follows DistillGraph's serial mode (`out` keys,
-    LOSS_SLOTS, loss_report), so train's loop needs no special case.  Every refusal is a ValueError before the device is touched.
-    dropout / dropout_seed: the STUDENT's drop rate before its hidden layer, its mask a function of global_step; the
-    frozen teacher never drops."""
-
-    LOSS_SLOTS = DistillGraph.LOSS_SLOTS
-    DISTILL_LOSSES = DistillGraph.DISTILL_LOSSES
-    mode = "serial"
-    student_sampling = "uniform"                 # (the grid is the uniform sub-sampling of the real frames; checkpoint metadata)
-    dp = False
-
-    def __init__(self, batch_size, every_n=10, teacher_every_n=1, feature_size=1152, vocab_size=4716, max_frames=300, cluster_size=64,
-                 hidden_size=1024, groups=8, expansion=2, gating_reduction=8, num_mixtures=2, base_learning_rate=0.001,
-                 learning_rate_decay=1.0, learning_rate_decay_examples=4000000, regularization_penalty=2.0, clip_gradient_norm=1.0,
-                 count_rep_twice=True, device="cuda:0", seed=7, process_group=None, precision="bf16", distill_losses=DISTILL_LOSSES,
-                 label_loss=None, dropout=0.0, dropout_seed=0):
-        from .towers import NeXtVladTower, check_nextvlad_frames
-        ops.check_dropout_rate(dropout)              # (before the device is touched; only the student drops, DESIGN.md 7.17)
-        self.world = _world_of(process_group)
-        if self.world > 1:
-            raise ValueError("NeXtVladDistillGraph is not data parallel (process group of %d ranks): train the student against the "
-                             "frozen teacher on one device" % self.world)
-        self.label_loss = _resolve_label_loss(label_loss, vocab_size)
-        if not losses_mod.is_default(self.label_loss):
-            raise ValueError("NeXtVladDistillGraph has CrossEntropyLoss built into its loss section (evc_distill_losses), not %s"
-                             % type(self.label_loss).__name__)
-        if precision != "bf16":
-            raise ValueError("NeXtVladDistillGraph: precision %r is refused, the NeXtVLAD tower has no such forward mode (bf16 only)" % (precision,))
-        self.distill_losses = check_distill_losses(distill_losses)
-        for n in (every_n, teacher_every_n):     # (ValueError naming --every_n and its range)
-            check_nextvlad_frames("grid", n, max_frames, world=self.world, precision=precision)
-        self.B, self.every_n, self.teacher_every_n, self.precision = batch_size, int(every_n), int(teacher_every_n), precision
-        self.lr0, self.lr_decay, self.lr_decay_examples = base_learning_rate, learning_rate_decay, learning_rate_decay_examples
-        self.reg_pen, self.clip, self.pg = regularization_penalty, clip_gradient_norm, process_group
-        self.rep_w = 2.0 if count_rep_twice else 1.0
-        self.device = torch.device(device)
-        self.global_step = 0
-        sizes = (batch_size, max_frames, feature_size, vocab_size, 30, cluster_size, hidden_size, groups, expansion, gating_reduction,
-                 num_mixtures)
-        self.teacher = NeXtVladTower(*sizes, device=device, training=False, scope="model", seed=seed, frames="grid",
-                                     every_n=self.teacher_every_n)
-        self.student = NeXtVladTower(*sizes, device=device, training=True, scope="model_student", seed=seed + 1, frames="grid",
-                                     every_n=self.every_n, dropout=dropout, dropout_seed=dropout_seed)
-        self.moe = self.student.moe
-        self.fused_moe_update = True
-        self.losses = torch.zeros(8, dtype=F32, device=self.device)
-        self._dp_s = self._ds_s = None
-
-    def _towers(self):
-        return [self.teacher, self.student]
-
-    def consolidate(self):
-        """Nothing is sharded on one rank (kept for train's checkpoint path)."""
-
-    def state_dict(self):
-        """Both scopes: model/* (the frozen teacher, the bits it was loaded with) and model_student/*."""
-        out = self.teacher.state_dict()
-        out.update(self.student.state_dict())
-        return out
-
-    def label_grads(self):
-        """The student's dL/dpred buffer of the last step (its L_CE and L_PRED gradient), as DistillGraph names it."""
-        return {} if self._dp_s is None else {"student": self._dp_s}
-
-    def state_grad(self):
-        """The dL_REP/dstate buffer of the last step (None before the first).  For tests and debugging."""
-        return self._ds_s
-
-    @property
-    def losses_for_report(self):
-        return self.losses
-
-    def loss_report(self, losses=None):
-        v = (self.losses if losses is None else losses).tolist()
-        return {k: v[i] for i, k in enumerate(self.LOSS_SLOTS)}
-
-    def step(self, x_raw, labels_u8, num_frames, apply=True, num_frames_host=None):
-        """x_raw [B,T,F] uint8 or float32, labels_u8 [B,V], num_frames [B] int32 (num_frames_host: the same counts on the host - both
-        towers lay their packed rows out from them; read back from the device when not given).  All launches on the caller's stream."""
-        B, V = labels_u8.shape
-        tt, ts = self.teacher, self.student
-        if num_frames_host is None:
-            num_frames_host = num_frames.cpu().numpy()
-        if self._dp_s is None or self._dp_s.shape[0] != B:
-            self._dp_s = torch.empty((B, V), dtype=F32, device=self.device)
-            self._ds_s = torch.empty((B, ts.Hd), dtype=F32, device=self.device)
-        t_pred = tt.forward(x_raw, num_frames, num_frames_host=num_frames_host, is_training=False)
-        s_pred = ts.forward(x_raw, num_frames, num_frames_host=num_frames_host, dropout_step=self.global_step)
-        on = self.distill_losses
-        self.losses.zero_()
-        ops.distill_losses(t_pred, tt.rowsum, s_pred, ts.rowsum, labels_u8, tt.state, ts.state, self.losses, self._dp_s, self._ds_s,
-                           g_ce=(1.0 / B) if "ce" in on else 0.0, g_kl=1.0 if "pred" in on else 0.0,
-                           g_rep=self.rep_w if "rep" in on else 0.0)
-        # the update of SingleTowerGraph.step on one rank: the MoE head's two matrices through the fused clip + Adam pass whenever
-        # the step applies (their gradient recomputed from its rank-B factors), the rest through clip_by_norm + TF-Adam
-        fuse = (apply and self.fused_moe_update and self.moe.can_fuse_update() and self.moe.prefer_fused_update(False)
-                and ts.precision == "bf16")
-        fused_names = (self.moe.GATES, self.moe.EXPERTS, self.moe.EBIAS) if fuse else ()
-        ts.backward(self._dp_s, moe_weight_grads=not fuse, dstate=self._ds_s)
-        if apply:
-            lr, l2c = self._lr_l2c(B)
-            if fuse:
-                ts.begin_update()
-                self.moe.fused_update(ts.adam_lr_t(lr), self.clip, l2c, dp=None)
-                ts.apply_group([k for k in ts.names if k not in fused_names], lr, self.clip, l2c)
-            else:
-                ts.apply_gradients(lr, self.clip, l2c)
-            self.global_step += 1
-        return dict(predictions=t_pred, teacher_state=tt.state, loss=self.losses[0], student_predictions=s_pred, student_state=ts.state,
-                    num_frames_student=torch.from_numpy(ts.plan.k), student_loss_state=self.losses[1], pred_loss=self.losses[2],
-                    student_label_loss=self.losses[3], global_step=self.global_step)
-
-
-def check_nextvlad_checkpoint(sd, scope, feature_size, vocab_size, sizes, what="the checkpoint"):
-    """The ``scope``/* variables of the checkpoint dict ``sd`` against the size flags (sizes: cluster_size, hidden_size, groups, expansion,
-    gating_reduction, num_mixtures), on the host: ValueError naming the first missing or mismatching variable and both shapes."""
-    from .towers import NeXtVladTower
-    for k, shp in NeXtVladTower.checkpoint_shapes(feature_size, vocab_size, *sizes).items():
-        have = sd.get("%s/%s" % (scope, k))
-        if not torch.is_tensor(have):
-            raise ValueError("%s holds no variable %s/%s (not a NeXtVLADModel checkpoint of that tower)" % (what, scope, k))
-        if tuple(have.shape) != shp:
-            raise ValueError("%s/%s of %s has shape %s, the size flags (--nextvlad_* / --feature_sizes / --moe_num_mixtures) give %s"
-                             % (scope, k, what, tuple(have.shape), shp))
-
-
-class NeXtVladEvalGraph(_StepGraph):
-    """Forward-only graph of the NeXtVLAD family with EvalGraph's interface: restore(state_dict) and
-    step(x_raw, labels_u8, num_frames, num_frames_host=None, keys=None) -> dict, so that EnsembleGraph, CascadeGraph, validate and inference
-    hold it where they hold an EvalGraph.  tower: 'teacher' (scope model, on every `every_n`-th real frame), 'student' (scope
-    model_student, the same) or 'both' (the student served at every_n, the teacher run too at teacher_every_n: validate's
-    student_state_loss).  The towers are forward-only grid towers (training=False: moving statistics, MFMA aggregation), bf16 only, on
-    the caller's stream.
-
-    compact: the towers run on the videos that have a frame.  sel = the ascending list of videos with num_frames_host > 0; when it is
-    shorter than the batch the towers serve those b' videos of the unchanged batch (NeXtVladTower.forward(sel=...)) and
-    ops.scatter_rows puts their rows back: predictions / states are [b, .] with zeros in the rows of videos without a frame.  With
-    compact=False such a video runs through the tower after the aggregation like any other (its V is zero) and its row holds what the
-    head makes of that.  The buffers are allocated once at batch_size: a shorter batch or a served subset allocates nothing."""
-
-    family = "nextvlad"
-    student_sampling = "uniform"
-
-    def __init__(self, batch_size, tower="teacher", every_n=1, teacher_every_n=1, feature_size=1152, vocab_size=4716, max_frames=300,
-                 cluster_size=64, hidden_size=1024, groups=8, expansion=2, gating_reduction=8, num_mixtures=2, device="cuda:0",
-                 precision="bf16", student_sampling="uniform", label_loss=None, compact=True, seed=7):
-        from .towers import NeXtVladTower, check_nextvlad_frames
-        if tower not in ("teacher", "student", "both"):
-            raise ValueError("NeXtVladEvalGraph: tower %r (teacher | student | both)" % (tower,))
-        if student_sampling != "uniform":
-            raise ValueError("--student_sampling %s with --model NeXtVLADModel: a grid tower reads every every_n-th real frame (uniform); "
-                             "the other selections are not built for this family" % (student_sampling,))
-        if precision != "bf16":
-            raise ValueError("--precision %s with --model NeXtVLADModel: the NeXtVLAD tower has no such forward mode (bf16 only)" % (precision,))
-        self.label_loss = _resolve_label_loss(label_loss, vocab_size)
-        grids = [every_n] + ([teacher_every_n] if tower == "both" else [])
-        for n in grids:
-            check_nextvlad_frames("grid", n, max_frames, precision=precision)
-        self.tower, self.every_n, self.teacher_every_n = tower, int(every_n), int(teacher_every_n if tower == "both" else every_n)
-        self.batch_size, self.max_frames, self.precision, self.compact = batch_size, max_frames, precision, bool(compact)
-        self.sizes = (cluster_size, hidden_size, groups, expansion, gating_reduction, num_mixtures)
-        self.F, self.V = feature_size, vocab_size
-        self.device = torch.device(device)
-        args = (batch_size, max_frames, feature_size, vocab_size, 30) + self.sizes
-        self.teacher = self.student = None
-        if tower != "student":
-            self.teacher = NeXtVladTower(*args, device=device, training=False, scope="model", seed=seed, frames="grid", every_n=self.teacher_every_n)
-        if tower != "teacher":
-            self.student = NeXtVladTower(*args, device=device, training=False, scope="model_student", seed=seed + 1, frames="grid",
-                                         every_n=self.every_n)
-        self.frames = FramePlan()                  # (no H-LSTM student: scored_sampling() is False for this member)
-        self.losses = torch.zeros(4, dtype=F32, device=self.device)
-        # what a compacted step hands out: [batch_size, .] once, rows of videos without a frame zero
-        self._wide = {}
-        if self.compact:
-            for name, tw in (("teacher", self.teacher), ("student", self.student)):
-                if tw is not None:
-                    self._wide[name] = (torch.zeros((batch_size, vocab_size), dtype=F32, device=self.device),
-                                        torch.zeros((batch_size, hidden_size), dtype=F32, device=self.device))
-
-    def _towers(self):
-        return [tw for tw in (self.teacher, self.student) if tw is not None]
-
-    def restore(self, state_dict):
-        """Each tower's variables and moving statistics by name, after the host check of their shapes against the graph's sizes."""
-        for tw in self._towers():
-            check_nextvlad_checkpoint(state_dict, tw.scope, self.F, self.V, self.sizes)
-            tw.load_state_dict(state_dict)
-
-    def _run(self, name, tw, x_raw, num_frames, nh, sel):
-        """(predictions [b, V], state [b, H]) of one tower for this batch; with sel, the rows of the other videos are zeros."""
-        pred = tw.forward(x_raw, num_frames, is_training=False, num_frames_host=nh, sel=sel)
-        if sel is None:
-            return pred, tw.state
-        b, n = x_raw.shape[0], int(sel.shape[0])
-        wide_pred, wide_state = (t[:b] for t in self._wide[name])
-        wide_pred.zero_()
-        wide_state.zero_()
-        ops.scatter_rows(pred, tw.sel[:n], wide_pred)
-        ops.scatter_rows(tw.state, tw.sel[:n], wide_state)
-        return wide_pred, wide_state
-
-    def step(self, x_raw, labels_u8, num_frames, num_frames_host=None, keys=None):
-        """x_raw [b, T, F] uint8 or float32, b <= batch_size; labels_u8 [b, V]; num_frames [b] int32 (num_frames_host: the same counts
-        on the host; read back from the device when not given).  keys is EvalGraph's argument and is not read."""
-        b = int(x_raw.shape[0])
-        if b > self.batch_size:
-            raise ValueError("NeXtVladEvalGraph: a batch of %d videos, the graph was built for %d" % (b, self.batch_size))
-        if num_frames_host is None:
-            num_frames_host = num_frames.cpu()
-        nh = np.asarray(num_frames_host, dtype=np.int64).reshape(-1)
-        sel = None
-        if self.compact:
-            have = np.flatnonzero(nh > 0)
-            if 0 < have.size < b:
-                sel = have.astype(np.int32)
-        out = {}
-        if self.teacher is not None:
-            t_pred, t_state = self._run("teacher", self.teacher, x_raw, num_frames, nh, sel)
-            out.update(teacher_predictions=t_pred, teacher_state=t_state)
-        if self.student is not None:
-            pred, s_state = self._run("student", self.student, x_raw, num_frames, nh, sel)
-            out["student_state"] = s_state
-        else:
-            pred = t_pred
-        served = self.student if self.student is not None else self.teacher
-        self.losses.zero_()
-        self.label_loss.fused(pred, labels_u8, self.losses[0:1])
-        if self.tower == "both":
-            ops.rep_loss(t_state, s_state, self.losses[1:2])
-            out["student_state_loss"] = self.losses[1]
-        k = np.zeros(b, np.int32)
-        k[sel if sel is not None else slice(None)] = served.plan.k
-        out.update(predictions=pred, loss=self.losses[0], student_label_loss=self.losses[0], num_frames=torch.from_numpy(k))
-        return out
-
-
-def netvlad_checkpoint_gating(sd, scope):
-    """Whether the ``scope``/* tower of the checkpoint dict ``sd`` has the context gate: it holds <scope>/gating_weights."""
-    return torch.is_tensor(sd.get("%s/gating_weights" % scope))
-
-
-def check_netvlad_checkpoint(sd, scope, feature_size, vocab_size, sizes, what="the checkpoint", gating=False):
-    """The ``scope``/* variables of the checkpoint dict ``sd`` against the size flags (sizes: cluster_size, hidden_size, num_mixtures), on
-    the host: ValueError naming the first missing or mismatching variable and both shapes.  gating: whether the caller's tower has the
-    context gate (--netvlad_gating); a checkpoint that disagrees is a ValueError naming the flag and the variable found or missing."""
-    from .towers import NetVladTower
-    gw = "%s/%s" % (scope, NetVladTower.GW)
-    if netvlad_checkpoint_gating(sd, scope) != bool(gating):
-        if gating:
-            raise ValueError("--netvlad_gating True, but %s holds no variable %s (a tower trained without the context gate)" % (what, gw))
-        raise ValueError("--netvlad_gating False, but %s holds the variable %s (a tower trained with the context gate)" % (what, gw))
-    for k, shp in NetVladTower.checkpoint_shapes(feature_size, vocab_size, *sizes, gating=bool(gating)).items():
-        have = sd.get("%s/%s" % (scope, k))
-        if not torch.is_tensor(have):
-            raise ValueError("%s holds no variable %s/%s (not a NetVLADModel checkpoint)" % (what, scope, k))
-        if tuple(have.shape) != shp:
-            raise ValueError("%s/%s of %s has shape %s, the size flags (--netvlad_* / --feature_sizes / --moe_num_mixtures) give %s"
-                             % (scope, k, what, tuple(have.shape), shp))
-
-
-class NetVladDistillGraph(_StepGraph):
-    """Serial distillation for the NetVLAD family, NeXtVladDistillGraph for this tower: a grid student (frames
-    j * every_n of every video, scope 'model_student') against a FROZEN grid teacher (every teacher_every_n-th real frame, scope
-    'model': forward only, batch norms on the checkpoint's moving statistics, no gradient store / moments / tape, never written).  One
-    step on one stream: teacher forward, student forward, the loss section of DistillGraph's mode 'serial' (ops.distill_losses on the
-    towers' h6 = relu6(hidden1_bn(hid)) and predictions, the same scales), the student's backward with dL_REP/dstate joining the MoE
-    head's gradient in front of hidden1_bn's relu6 mask, and the update exactly as SingleTowerGraph.step performs it; global_step += 1.
-    Reporting follows DistillGraph's serial mode (`out` keys, LOSS_SLOTS, loss_report), so train's loop needs no special case.  Every
-    refusal is a ValueError before the device is touched.
-
-    student_sampling / sampling_seed: the --student_sampling word of the STUDENT, "random" drawn with draw =
-    global_step and row0 = 0.  teacher_sampling / teacher_sampling_seed: what the frozen teacher's checkpoint records when that tower was
-    itself trained on selected frames; it runs on them with draw 0, as evaluation does.  Under a scored word the batch's
-    ops.frame_change_keys are computed once and handed to both towers.
-
-    gating / teacher_gating: the context gate of the student (--netvlad_gating) and of the frozen teacher (what its
-    checkpoint holds).  They may differ: both states are [B, H], and L_REP and dstate are on `state`, the gated vector where there is a gate."""
-
-    LOSS_SLOTS = DistillGraph.LOSS_SLOTS
-    DISTILL_LOSSES = DistillGraph.DISTILL_LOSSES
-    mode = "serial"
-    student_sampling = "uniform"                 # (the grid is the uniform sub-sampling of the real frames; checkpoint metadata)
-    dp = False
-
-    def __init__(self, batch_size, every_n=10, teacher_every_n=1, feature_size=1152, vocab_size=4716, max_frames=300, cluster_size=64,
-                 hidden_size=1024, num_mixtures=2, base_learning_rate=0.001, learning_rate_decay=1.0,
-                 learning_rate_decay_examples=4000000, regularization_penalty=2.0, clip_gradient_norm=1.0, count_rep_twice=True,
-                 device="cuda:0", seed=7, process_group=None, precision="bf16", distill_losses=DISTILL_LOSSES, label_loss=None,
-                 student_sampling="uniform", sampling_seed=0, teacher_sampling="uniform", teacher_sampling_seed=0, gating=False,
-                 teacher_gating=False):
-        from .towers import NetVladTower, check_netvlad_frames
-        self.student_sampling, self.sampling_seed = ops.check_student_sampling(student_sampling, "--student_sampling"), int(sampling_seed)
-        self.teacher_sampling, self.teacher_sampling_seed = ops.check_student_sampling(teacher_sampling, "teacher_sampling"), int(teacher_sampling_seed)
-        self.gating, self.teacher_gating = bool(gating), bool(teacher_gating)
-        self.world = _world_of(process_group)
-        if self.world > 1:
-            raise ValueError("NetVladDistillGraph is not data parallel (process group of %d ranks): train the student against the "
-                             "frozen teacher on one device" % self.world)
-        self.label_loss = _resolve_label_loss(label_loss, vocab_size)
-        if not losses_mod.is_default(self.label_loss):
-            raise ValueError("NetVladDistillGraph has CrossEntropyLoss built into its loss section (evc_distill_losses), not %s"
-                             % type(self.label_loss).__name__)
-        if precision != "bf16":
-            raise ValueError("NetVladDistillGraph: precision %r is refused, the NetVLAD tower has no such forward mode (bf16 only)" % (precision,))
-        self.distill_losses = check_distill_losses(distill_losses)
-        for n, w in ((every_n, self.student_sampling), (teacher_every_n, self.teacher_sampling)):     # (ValueError naming --every_n and its range)
-            check_netvlad_frames("grid", n, max_frames, world=self.world, precision=precision, sampling=w)
-        self.B, self.every_n, self.teacher_every_n, self.precision = batch_size, int(every_n), int(teacher_every_n), precision
-        self.lr0, self.lr_decay, self.lr_decay_examples = base_learning_rate, learning_rate_decay, learning_rate_decay_examples
-        self.reg_pen, self.clip, self.pg = regularization_penalty, clip_gradient_norm, process_group
-        self.rep_w = 2.0 if count_rep_twice else 1.0
-        self.device = torch.device(device)
-        self.global_step = 0
-        sizes = (batch_size, max_frames, feature_size, vocab_size, 30, cluster_size, hidden_size, num_mixtures)
-        self.teacher = NetVladTower(*sizes, device=device, training=False, scope="model", seed=seed, frames="grid",
-                                    every_n=self.teacher_every_n, sampling=self.teacher_sampling, sampling_seed=self.teacher_sampling_seed,
-                                    gating=self.teacher_gating)
-        self.student = NetVladTower(*sizes, device=device, training=True, scope="model_student", seed=seed + 1, frames="grid",
-                                    every_n=self.every_n, sampling=self.student_sampling, sampling_seed=self.sampling_seed, gating=self.gating)
-        self.moe = self.student.moe
-        self.fused_moe_update = True
-        self.losses = torch.zeros(8, dtype=F32, device=self.device)
-        self._dp_s = self._ds_s = None
-
-    def _towers(self):
-        return [self.teacher, self.student]
-
-    def consolidate(self):
-        """Nothing is sharded on one rank (kept for train's checkpoint path)."""
-
-    def state_dict(self):
-        """Both scopes: model/* (the frozen teacher, the bits it was loaded with) and model_student/*."""
-        out = self.teacher.state_dict()
-        out.update(self.student.state_dict())
-        return out
-
-    def label_grads(self):
-        """The student's dL/dpred buffer of the last step (its L_CE and L_PRED gradient), as DistillGraph names it."""
-        return {} if self._dp_s is None else {"student": self._dp_s}
-
-    def state_grad(self):
-        """The dL_REP/dstate buffer of the last step (None before the first).  For tests and debugging."""
-        return self._ds_s
-
-    @property
-    def losses_for_report(self):
-        return self.losses
-
-    def loss_report(self, losses=None):
-        v = (self.losses if losses is None else losses).tolist()
-        return {k: v[i] for i, k in enumerate(self.LOSS_SLOTS)}
-
-    def step(self, x_raw, labels_u8, num_frames, apply=True, num_frames_host=None):
-        """x_raw [B,T,F] uint8 or float32, labels_u8 [B,V], num_frames [B] int32 (num_frames_host: the same counts on the host - both
-        towers lay their packed rows out from them; read back from the device when not given).  All launches on the caller's stream."""
-        B, V = labels_u8.shape
-        tt, ts = self.teacher, self.student
-        if num_frames_host is None:
-            num_frames_host = num_frames.cpu().numpy()
-        if self._dp_s is None or self._dp_s.shape[0] != B:
-            self._dp_s = torch.empty((B, V), dtype=F32, device=self.device)
-            self._ds_s = torch.empty((B, ts.Hd), dtype=F32, device=self.device)
-        tkw, skw = {}, {}
-        if self.student_sampling != "uniform" or self.teacher_sampling != "uniform":      # (DESIGN.md 7.20; uniform: today's calls)
-            scored = ops.STUDENT_SAMPLING_SCORED
-            keys = ops.frame_change_keys(x_raw, num_frames) if (self.student_sampling in scored or self.teacher_sampling in scored) else None
-            tkw = dict(keys=keys, draw=0, row0=0)
-            skw = dict(keys=keys, draw=self.global_step, row0=0)
-        t_pred = tt.forward(x_raw, num_frames, num_frames_host=num_frames_host, is_training=False, **tkw)
-        s_pred = ts.forward(x_raw, num_frames, num_frames_host=num_frames_host, **skw)
-        on = self.distill_losses
-        self.losses.zero_()
-        ops.distill_losses(t_pred, tt.rowsum, s_pred, ts.rowsum, labels_u8, tt.state, ts.state, self.losses, self._dp_s, self._ds_s,
-                           g_ce=(1.0 / B) if "ce" in on else 0.0, g_kl=1.0 if "pred" in on else 0.0,
-                           g_rep=self.rep_w if "rep" in on else 0.0)
-        # the update of SingleTowerGraph.step on one rank: the MoE head's two matrices through the fused clip + Adam pass whenever
-        # the step applies (their gradient recomputed from its rank-B factors), the rest through clip_by_norm + TF-Adam
-        fuse = (apply and self.fused_moe_update and self.moe.can_fuse_update() and self.moe.prefer_fused_update(False)
-                and ts.precision == "bf16")
-        fused_names = (self.moe.GATES, self.moe.EXPERTS, self.moe.EBIAS) if fuse else ()
-        ts.backward(self._dp_s, moe_weight_grads=not fuse, dstate=self._ds_s)
-        if apply:
-            lr, l2c = self._lr_l2c(B)
-            if fuse:
-                ts.begin_update()
-                self.moe.fused_update(ts.adam_lr_t(lr), self.clip, l2c, dp=None)
-                ts.apply_group([k for k in ts.names if k not in fused_names], lr, self.clip, l2c)
-            else:
-                ts.apply_gradients(lr, self.clip, l2c)
-            self.global_step += 1
-        return dict(predictions=t_pred, teacher_state=tt.state, loss=self.losses[0], student_predictions=s_pred, student_state=ts.state,
-                    num_frames_student=torch.from_numpy(ts.plan.k), student_loss_state=self.losses[1], pred_loss=self.losses[2],
-                    student_label_loss=self.losses[3], global_step=self.global_step)
-
-
-class NetVladEvalGraph(_StepGraph):
-    """Forward-only graph of the NetVLAD family with EvalGraph's interface: restore(state_dict) and
-    step(x_raw, labels_u8, num_frames, num_frames_host=None, keys=None) -> dict with predictions, loss, num_frames, so that validate
-    holds it where it holds an EvalGraph.  tower: 'teacher' (scope model, on every `every_n`-th real frame), 'student' (scope
-    model_student, the same) or 'both' (the student served at every_n, the teacher run too at teacher_every_n: validate's
-    student_state_loss).  Forward-only grid towers (training=False: the moving statistics), bf16 only, on the caller's stream.  No row
-    compaction: a video without a frame runs through the head with V = 0 like any other and its row holds what the head makes of that.
-    The buffers are allocated once at batch_size: a shorter batch allocates nothing.
-
-    student_sampling / sampling_seed: the --student_sampling word the SERVED tower runs on (the student, or the teacher
-    when it is the only tower), as EvalGraph serves its student on the flag; "random" is drawn with draw 0 and row0 0, the same frames
-    for the same batching.  With tower='both' the teacher runs on teacher_sampling / teacher_sampling_seed, what its checkpoint records.
-
-    gating / teacher_gating: the context gate of the served tower and, with tower='both', of the teacher - what the
-    checkpoint's own variables say (validate.netvlad_source), never the flag."""
-
-    family = "netvlad"
-    student_sampling = "uniform"
-
-    def __init__(self, batch_size, every_n=1, feature_size=1152, vocab_size=4716, max_frames=300, cluster_size=64, hidden_size=1024,
-                 num_mixtures=2, device="cuda:0", precision="bf16", label_loss=None, seed=7, tower="teacher", teacher_every_n=1,
-                 student_sampling="uniform", sampling_seed=0, teacher_sampling="uniform", teacher_sampling_seed=0, gating=False,
-                 teacher_gating=False):
-        from .towers import NetVladTower, check_netvlad_frames
-        if tower not in ("teacher", "student", "both"):
-            raise ValueError("NetVladEvalGraph: tower %r (teacher | student | both)" % (tower,))
-        if tower != "both":
-            teacher_gating = gating                                   # (the one tower is the served one)
-        self.gating, self.teacher_gating = bool(gating), bool(teacher_gating)
-        self.student_sampling, self.sampling_seed = ops.check_student_sampling(student_sampling, "--student_sampling"), int(sampling_seed)
-        if tower != "both":
-            teacher_sampling, teacher_sampling_seed = student_sampling, sampling_seed      # (the one tower is the served one)
-        self.teacher_sampling, self.teacher_sampling_seed = ops.check_student_sampling(teacher_sampling, "teacher_sampling"), int(teacher_sampling_seed)
-        for n, w in [(every_n, self.student_sampling)] + ([(teacher_every_n, self.teacher_sampling)] if tower == "both" else []):
-            check_netvlad_frames("grid", n, max_frames, precision=precision, sampling=w)         # (before the device is touched)
-        self.label_loss = _resolve_label_loss(label_loss, vocab_size)
-        self.tower, self.every_n, self.teacher_every_n = tower, int(every_n), int(teacher_every_n if tower == "both" else every_n)
-        self.batch_size, self.max_frames, self.precision = batch_size, max_frames, precision
-        self.sizes = (cluster_size, hidden_size, num_mixtures)
-        self.F, self.V = feature_size, vocab_size
-        self.device = torch.device(device)
-        args = (batch_size, max_frames, feature_size, vocab_size, 30, cluster_size, hidden_size, num_mixtures)
-        self.teacher = self.student = None
-        if tower != "student":
-            self.teacher = NetVladTower(*args, device=device, training=False, scope="model", seed=seed, frames="grid",
-                                        every_n=self.teacher_every_n, sampling=self.teacher_sampling, sampling_seed=self.teacher_sampling_seed,
-                                        gating=self.teacher_gating)
-        if tower != "teacher":
-            self.student = NetVladTower(*args, device=device, training=False, scope="model_student", seed=seed + 1, frames="grid",
-                                        every_n=self.every_n, sampling=self.student_sampling, sampling_seed=self.sampling_seed,
-                                        gating=self.gating)
-        self.losses = torch.zeros(2 if tower == "both" else 1, dtype=F32, device=self.device)
-
-    def _towers(self):
-        return [tw for tw in (self.teacher, self.student) if tw is not None]
-
-    def restore(self, state_dict):
-        """Each tower's variables and moving statistics by name, after the host check of their shapes against the graph's sizes."""
-        for tw in self._towers():
-            check_netvlad_checkpoint(state_dict, tw.scope, self.F, self.V, self.sizes, gating=tw.gating)
-        for tw in self._towers():
-            tw.load_state_dict(state_dict)
-
-    def step(self, x_raw, labels_u8, num_frames, num_frames_host=None, keys=None):
-        """x_raw [b, T, F] uint8 or float32, b <= batch_size; labels_u8 [b, V]; num_frames [b] int32 (num_frames_host: the same counts
-        on the host; read back from the device when not given).  keys is EvalGraph's argument: the batch's ops.frame_change_keys, read
-        under a scored word alone (computed here, once, when not given)."""
-        b = int(x_raw.shape[0])
-        if b > self.batch_size:
-            raise ValueError("NetVladEvalGraph: a batch of %d videos, the graph was built for %d" % (b, self.batch_size))
-        if num_frames_host is None:
-            num_frames_host = num_frames.cpu()
-        nh = np.asarray(num_frames_host, dtype=np.int64).reshape(-1)
-        out = {}
-        kw = {}
-        if keys is None and any(tw.sampling in ops.STUDENT_SAMPLING_SCORED for tw in self._towers()):
-            keys = ops.frame_change_keys(x_raw, num_frames)
-        if any(tw.sampling != "uniform" for tw in self._towers()):
-            kw = dict(keys=keys, draw=0, row0=0)
-        if self.teacher is not None:
-            pred = t_pred = self.teacher.forward(x_raw, num_frames, is_training=False, num_frames_host=nh, **kw)
-            if self.tower == "both":
-                out.update(teacher_predictions=t_pred, teacher_state=self.teacher.state)
-        if self.student is not None:
-            pred = self.student.forward(x_raw, num_frames, is_training=False, num_frames_host=nh, **kw)
-            out["student_state"] = self.student.state
-        served = self.student if self.student is not None else self.teacher
-        self.losses.zero_()
-        self.label_loss.fused(pred, labels_u8, self.losses[0:1])
-        if self.tower == "both":
-            ops.rep_loss(self.teacher.state, self.student.state, self.losses[1:2])
-            out["student_state_loss"] = self.losses[1]
-            out["student_label_loss"] = self.losses[0]
-        out.update(predictions=pred, loss=self.losses[0], num_frames=torch.from_numpy(served.plan.k.copy()))
-        return out
+def __getattr__(name):
+    if name in _VLAD_GRAPHS:
+        from . import vlad_graphs
+        return getattr(vlad_graphs, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

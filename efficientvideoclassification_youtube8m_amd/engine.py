@@ -1032,6 +1032,12 @@ class TowerBase:
     """Parameter store + bf16 shadows + per-tensor clip / TF-Adam shared by all model towers."""
 
     l2_names = ()
+    frames = None                 # "grid": forward lays its packed rows out from num_frames_host (the VLAD towers' --*_frames grid)
+    takes_uniform_draw = False    # forward(x, num_frames, uniform): the tower samples its frames from a [B, S] draw of the step
+
+    def step_kwargs(self, global_step):
+        """forward's keywords that are a function of the training step (a dropout mask's counter, the draw of "random" frames)."""
+        return {}
 
     def _setup_store(self, shapes, transposed_2d=True):
         self.store = ParamStore(shapes, self.device)

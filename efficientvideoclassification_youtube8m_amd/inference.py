@@ -36,7 +36,7 @@ row being that of the last stage that ran it.  ``--cascade_stage_file`` records 
         --cascade_dirs "./model_every30_finetune/,./model_train/" --cascade_every_n "30,1" --cascade_thresholds 0.9 --cascade_fractions 0.3
 
 NeXtVLAD checkpoints (an addition): ``--model NeXtVLADModel`` serves a grid tower of --train_dir's checkpoint through
-distill.NeXtVladEvalGraph - ``--serve_tower`` auto (model_student/* when the checkpoint holds it, else model/*) | teacher | student, on
+vlad_graphs.NeXtVladEvalGraph - ``--serve_tower`` auto (model_student/* when the checkpoint holds it, else model/*) | teacher | student, on
 the grid the checkpoint records unless ``--nextvlad_serve_every_n`` names another.  The family of every ensemble member and cascade
 stage is read from its own checkpoint (checkpoint_family), so H-LSTM and NeXtVLAD members mix; NeXtVLAD members take their sizes from
 the --nextvlad_* flags and an every_n entry of 0 or '' means "as recorded".
@@ -52,9 +52,10 @@ import numpy as np
 import torch
 
 from . import frame_level_models, ops, readers, utils, video_level_models
-from .distill import EnsembleGraph, EvalGraph, NeXtVladEvalGraph, check_nextvlad_checkpoint
+from .distill import EnsembleGraph, EvalGraph
 from .flags import FLAGS
 from .train import NUM_CLASSES, find_class_by_name, get_reader, latest_checkpoint, nextvlad_size_flags, nextvlad_teacher_every_n
+from .vlad_graphs import NeXtVladEvalGraph, check_nextvlad_checkpoint
 
 HEADER = "VideoId,LabelConfidencePairs\n"
 

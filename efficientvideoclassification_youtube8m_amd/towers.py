@@ -110,6 +110,7 @@ class DbofTower(TowerBase):
     # gradients that the batch-norm backward passes already leave summed over the ranks (SyncBN: all-reduced f64 sums): not
     # part of the gradient all-reduce.  (input_bn's come from the rank's own G = dact^T . xhat and ARE all-reduced.)
     global_grad_names = tuple("%s/%s" % (s, v) for s in ("cluster_bn", "hidden1_bn") for v in ("beta", "gamma"))
+    takes_uniform_draw = True
     timing = None      # bench.py: set to a list to collect (start, end) events around the cluster GEMM launches
 
     def __init__(self, batch_size, max_frames=300, feature_size=1152, vocab_size=4716, iterations=30,
@@ -352,6 +353,7 @@ class DbofGenericTower(TowerBase):
     mode inside north_star's 1e-3; the backward products stay bf16 as in every mode."""
 
     CW, CB, HW, HB = "cluster_weights", "cluster_biases", "hidden1_weights", "hidden1_biases"
+    takes_uniform_draw = True
     l2_names = (MoeHead.GATES, MoeHead.EXPERTS)
 
     def __init__(self, batch_size, max_frames=300, feature_size=1152, vocab_size=4716, iterations=30, cluster_size=8192,
@@ -521,37 +523,113 @@ class DbofGenericTower(TowerBase):
         return self.moe.pred
 
 
-def _plan_grid_rows(tw, num_frames, num_frames_host, sel=None, flag="--nextvlad_frames", select=False):
-    """Grid mode of a tower (NeXtVLAD, NetVLAD): this batch's packed layout from the HOST frame counts (launch sizes and offsets without
-    a device sync); row_off goes up through one of two pinned buffers, reused only once its earlier copy has completed.  sel (int32
-    numpy, accepted by ops.check_row_selection): the layout of those videos alone, and sel itself goes up the same way.  select: the
-    counts of a source-frame table (ops.SelectPlan) in place of the grid's."""
-    if num_frames_host is None:
-        num_frames_host = num_frames.cpu().numpy()       # an explicit device sync: callers that have the counts on the host pass them
-    if sel is not None:
-        num_frames_host = np.asarray(num_frames_host).reshape(-1)[sel]
-    plan = (ops.SelectPlan if select else ops.GridPlan)(num_frames_host, tw.every_n, tw.T)
-    if plan.B != tw.B:
-        raise ValueError("num_frames_host holds %d videos, the batch %d" % (plan.B, tw.B))
-    if plan.R == 0:
-        raise ValueError("%s grid: no video of the batch has a frame" % flag)
-    slot = tw._uploads % 2
-    tw._uploads += 1
-    if tw._row_off_done[slot] is not None:
-        tw._row_off_done[slot].synchronize()
-    B = plan.B
-    tw._row_off_host[slot][:B + 1].copy_(torch.from_numpy(plan.row_off))
-    tw.row_off[:B + 1].copy_(tw._row_off_host[slot][:B + 1], non_blocking=True)
-    if sel is not None:
-        tw._sel_host[slot][:B].copy_(torch.from_numpy(sel))
-        tw.sel[:B].copy_(tw._sel_host[slot][:B], non_blocking=True)
-    ev = tw._row_off_done[slot] = torch.cuda.Event()
-    ev.record()
-    tw.plan, tw.R, tw.Rp = plan, plan.R, plan.Rp
-    return plan
+class VladTower(TowerBase):
+    """What the two VLAD towers (NetVLAD, NeXtVLAD) share: the check of a checkpoint's shapes, the row bookkeeping of both frame modes, the
+    packed layout of grid mode and the views of a forward-only grid tower that serves fewer videos than it was allocated for.  A family
+    names itself in FAMILY / MODEL / FLAG (the prefix of its flags) and NOT_A_CHECKPOINT (vlad_graphs.check_vlad_checkpoint's clause)."""
+
+    PRECISIONS = ("bf16",)             # no split-bf16 forward (set_precision refuses anything else)
+    FRAME_MODES = ("sampled", "grid")
+    takes_uniform_draw = property(lambda self: self.frames != "grid")
+
+    @classmethod
+    def checkpoint_shapes(cls, *sizes, **kw):
+        """What state_dict() holds for these size flags, without the scope prefix: every variable in its TF layout (2-D weights
+        [in][out]) and the batch norms' moving statistics.  For checking a checkpoint against the flags before a tower is built.
+        Keywords are variable_shapes' (NetVLAD: gating=True, with the context gate's names)."""
+        out = OrderedDict()
+        for k, shp in cls.variable_shapes(*sizes, **kw).items():
+            out[k] = tuple(reversed(shp)) if len(shp) == 2 else tuple(shp)
+            if k.endswith("/gamma"):
+                for v in ("moving_mean", "moving_variance"):
+                    out[k[:-len("gamma")] + v] = tuple(shp)
+        return out
+
+    def _alloc_rows(self, B, with_sel=False):
+        """The bookkeeping in front of _alloc's buffer list; returns the rows of the row buffers.  Grid mode: every row buffer once, for
+        every video at full length - a batch uses its first R (Rp in the TN products) rows -, and row_off with its two pinned staging
+        buffers (with_sel: the same for sel, a served subset of the batch's videos)."""
+        dev = self.device
+        if self.frames == "grid":
+            self.B, self.R, self.Rp, self.plan = B, 0, 0, None
+            R = ops.grid_capacity(B, self.T, self.every_n)
+            self.row_off = torch.zeros(B + 1, dtype=torch.int32, device=dev)
+            self._row_off_host = [torch.zeros(B + 1, dtype=torch.int32).pin_memory() for _ in range(2)]
+            if with_sel:
+                self.sel = torch.zeros(B, dtype=torch.int32, device=dev)
+                self._sel_host = [torch.zeros(B, dtype=torch.int32).pin_memory() for _ in range(2)]
+            self._row_off_done = [None, None]
+            self._uploads = 0
+        else:
+            self.B, self.R = B, B * self.S
+            if self.training and self.R % 32:
+                raise ValueError("batch_size x iterations = %d must be a multiple of 32 (row count of the TN weight-gradient products)" % self.R)
+            R = self.R
+        self.cap = B                                                 # videos the buffers hold (forward-only grid towers serve B <= cap)
+        self.Bk = ops.round_up(B, 32)
+        return R
+
+    def _fit_batch(self, B):
+        """A batch of B videos: a forward-only grid tower keeps the buffers it allocated when they hold it, every other case allocates."""
+        if B != self.B:
+            if self.frames == "grid" and not self.training and B <= self.cap:
+                self.B = B
+            else:
+                self._alloc(B)
+
+    def _plan_grid_rows(self, num_frames, num_frames_host, sel=None, select=False):
+        """Grid mode: this batch's packed layout from the HOST frame counts (launch sizes and offsets without a device sync); row_off goes
+        up through one of two pinned buffers, reused only once its earlier copy has completed.  sel (int32 numpy, accepted by
+        ops.check_row_selection): the layout of those videos alone, and sel itself goes up the same way.  select: the counts of a
+        source-frame table (ops.SelectPlan) in place of the grid's."""
+        if num_frames_host is None:
+            num_frames_host = num_frames.cpu().numpy()       # an explicit device sync: callers that have the counts on the host pass them
+        if sel is not None:
+            num_frames_host = np.asarray(num_frames_host).reshape(-1)[sel]
+        plan = (ops.SelectPlan if select else ops.GridPlan)(num_frames_host, self.every_n, self.T)
+        if plan.B != self.B:
+            raise ValueError("num_frames_host holds %d videos, the batch %d" % (plan.B, self.B))
+        if plan.R == 0:
+            raise ValueError("%s_frames grid: no video of the batch has a frame" % self.FLAG)
+        slot = self._uploads % 2
+        self._uploads += 1
+        if self._row_off_done[slot] is not None:
+            self._row_off_done[slot].synchronize()
+        B = plan.B
+        self._row_off_host[slot][:B + 1].copy_(torch.from_numpy(plan.row_off))
+        self.row_off[:B + 1].copy_(self._row_off_host[slot][:B + 1], non_blocking=True)
+        if sel is not None:
+            self._sel_host[slot][:B].copy_(torch.from_numpy(sel))
+            self.sel[:B].copy_(self._sel_host[slot][:B], non_blocking=True)
+        ev = self._row_off_done[slot] = torch.cuda.Event()
+        ev.record()
+        self.plan, self.R, self.Rp = plan, plan.R, plan.Rp
+        return plan
+
+    def _live(self, t):
+        """The rows of a [cap, .] buffer that belong to this batch."""
+        return t if self.B == self.cap else t[:self.B]
+
+    pred = property(lambda self: self._live(self.moe.pred))
+    rowsum = property(lambda self: self._live(self.moe.rowsum))
 
 
-class NetVladTower(TowerBase):
+def check_grid_frames(tower_cls, frames, every_n, max_frames, model, world, precision):
+    """What --nextvlad_frames / --netvlad_frames grid refuse with --every_n, the model, the ranks and --precision, as ValueErrors that name
+    the family's flag; touches no device."""
+    flag, name = tower_cls.FLAG + "_frames", tower_cls.FAMILY
+    if model is not None and model != tower_cls.MODEL:
+        raise ValueError("%s grid is built for --model %s, not %s" % (flag, tower_cls.MODEL, model))
+    if every_n < 1 or every_n > max_frames:
+        raise ValueError("%s grid: --every_n %d must lie in 1 .. --max_num_frames %d" % (flag, every_n, max_frames))
+    if world > 1:
+        raise ValueError("%s grid refuses a process group of %d ranks: ragged ranks hold different row counts and the "
+                         "batch-norm statistics assume equal ones; data parallelism is not built for this mode" % (flag, world))
+    if precision != "bf16":
+        raise ValueError("%s grid: --precision %s is refused, the %s tower has no such forward mode (bf16 only)" % (flag, precision, name))
+
+
+class NetVladTower(VladTower):
     """NetVLAD aggregation tower - an EXTENSION: the reference announces NetVLAD / NeXtVLAD teacher-student variants
     (README.md:126-127) but ships empty stubs (cs/frame_level_models.py:341-355), so there is no reference math; the
     definition is oracle/model_math.py::netvlad_fwd ("Learnable pooling with Context Gating" NetVLAD in the frame of the
@@ -581,8 +659,7 @@ class NetVladTower(TowerBase):
     table built on the device per batch (kept as last_frame_table), one gather that reads it (evc_frames_gather_packed_tab), everything
     behind the gather unchanged.  "random" draws from (sampling_seed, draw, row0 + b), forward's arguments."""
 
-    PRECISIONS = ("bf16",)             # no split-bf16 forward (set_precision refuses anything else)
-    FRAME_MODES = ("sampled", "grid")
+    FAMILY, MODEL, FLAG, NOT_A_CHECKPOINT = "NetVLAD", "NetVLADModel", "--netvlad", "not a NetVLADModel checkpoint"
     fused_input_pass = True           # forward-only grid towers: evc_frames_gather_packed_bn (False: the two launches, for A/B timing)
     fused_gate = True                 # gating: evc_bn_gate_fwd / _bwd_* (False: bn_apply, nextvlad_gate_*, bn_bwd_* one after another; same bits)
 
@@ -662,19 +739,6 @@ class NetVladTower(TowerBase):
         shapes.update(MoeHead.shapes(H, vocab_size, num_mixtures))
         return shapes
 
-    @classmethod
-    def checkpoint_shapes(cls, *sizes, **kw):
-        """What state_dict() holds for these size flags, without the scope prefix: every variable in its TF layout (2-D weights
-        [in][out]) and the batch norms' moving statistics.  For checking a checkpoint against the flags before a tower is built.
-        gating=True: with the context gate's names."""
-        out = OrderedDict()
-        for k, shp in cls.variable_shapes(*sizes, **kw).items():
-            out[k] = tuple(reversed(shp)) if len(shp) == 2 else tuple(shp)
-            if k.endswith("/gamma"):
-                for v in ("moving_mean", "moving_variance"):
-                    out[k[:-len("gamma")] + v] = tuple(shp)
-        return out
-
     # hidden1_weights: TF layout [F*K, H] with row f*K + k  <->  internal [H][k*F + f]
     def state_dict(self):
         out = super().state_dict()
@@ -696,22 +760,7 @@ class NetVladTower(TowerBase):
     def _alloc(self, B):
         dev, F, S, K, H = self.device, self.F, self.S, self.Kc, self.Hd
         grid = self.frames == "grid"
-        if grid:
-            # every row buffer once, for every video at full length; a batch uses its first R (Rp in the TN products) rows.
-            # The bf16 operands of the TN products start as zeros: their rows R .. Rp are zeroed again at every step.
-            self.B, self.R, self.Rp, self.plan = B, 0, 0, None
-            R = ops.grid_capacity(B, self.T, self.every_n)
-            self.row_off = torch.zeros(B + 1, dtype=torch.int32, device=dev)
-            self._row_off_host = [torch.zeros(B + 1, dtype=torch.int32).pin_memory() for _ in range(2)]
-            self._row_off_done = [None, None]
-            self._uploads = 0
-        else:
-            self.B, self.R = B, B * S
-            if self.training and self.R % 32:
-                raise ValueError("batch_size x iterations = %d must be a multiple of 32 (row count of the TN weight-gradient products)" % self.R)
-            R = self.R
-        self.cap = B                                                 # videos the buffers hold (forward-only grid towers serve B <= cap)
-        self.Bk = ops.round_up(B, 32)
+        R = self._alloc_rows(B)          # (grid: the bf16 operands of the TN products start as zeros; their rows R .. Rp are zeroed again at every step)
         self.r = torch.empty((R, F), dtype=F32, device=dev)
         if not grid:
             self.idx = torch.empty((B, S), dtype=torch.int32, device=dev)
@@ -757,11 +806,7 @@ class NetVladTower(TowerBase):
         B = x.shape[0]
         grid = self.frames == "grid"
         select = grid and self.sampling != "uniform"
-        if B != self.B:
-            if grid and not self.training and B <= self.cap:
-                self.B = B
-            else:
-                self._alloc(B)
+        self._fit_batch(B)
         F, S, K, H = self.F, self.S, self.Kc, self.Hd
         st, bi, bc = self.store, self.bn_in, self.bn_cl
         if self.precision != "bf16":
@@ -778,7 +823,7 @@ class NetVladTower(TowerBase):
                 else:
                     src = ops.student_frame_select(num_frames, self.T, self.every_n, self.sampling, seed=self.sampling_seed, draw=draw, row0=row0)
                 self.last_frame_table = src
-            plan = _plan_grid_rows(self, num_frames, num_frames_host, None, "--netvlad_frames", select=select)
+            plan = self._plan_grid_rows(num_frames, num_frames_host, select=select)
             R, Rp = plan.R, plan.Rp
             row_off = self.row_off[:B + 1]
         # a forward-only grid tower knows input_bn's statistics before the batch (the moving ones): gather and batch norm in one
@@ -897,20 +942,15 @@ class NetVladTower(TowerBase):
         if on_stage is not None:
             on_stage(2)
 
-    @property
-    def pred(self):
-        return self.moe.pred if self.B == self.cap else self.moe.pred[:self.B]
+    def step_kwargs(self, global_step):
+        """("random" frames are a function of the step too)"""
+        return {"draw": global_step, "row0": 0} if self.sampling != "uniform" else {}
 
     @property
     def state(self):
         """The tower's representation, what its MoE head reads, [B, H] f32: h6 = relu6(hidden1_bn(hid)), or with the gate
         h6 * sigmoid(gating_bn(bf16(h6) . gating_weights))."""
-        s_ = self.gated if self.gating else self.h6
-        return s_ if self.B == self.cap else s_[:self.B]
-
-    @property
-    def rowsum(self):
-        return self.moe.rowsum if self.B == self.cap else self.moe.rowsum[:self.B]
+        return self._live(self.gated if self.gating else self.h6)
 
 
 def check_netvlad_gating(gating, world=1):
@@ -933,15 +973,7 @@ def check_netvlad_frames(frames, every_n, max_frames, model=None, world=1, preci
     if sampling != "uniform" and max_frames > ops.SELECT_MAX_T:
         raise ValueError("--student_sampling %s: --max_num_frames %d is refused, the source-frame tables hold at most %d frames per video"
                          % (sampling, max_frames, ops.SELECT_MAX_T))
-    if model is not None and model != "NetVLADModel":
-        raise ValueError("--netvlad_frames grid is built for --model NetVLADModel, not %s" % model)
-    if every_n < 1 or every_n > max_frames:
-        raise ValueError("--netvlad_frames grid: --every_n %d must lie in 1 .. --max_num_frames %d" % (every_n, max_frames))
-    if world > 1:
-        raise ValueError("--netvlad_frames grid refuses a process group of %d ranks: ragged ranks hold different row counts and the "
-                         "batch-norm statistics assume equal ones; data parallelism is not built for this mode" % world)
-    if precision != "bf16":
-        raise ValueError("--netvlad_frames grid: --precision %s is refused, the NetVLAD tower has no such forward mode (bf16 only)" % precision)
+    check_grid_frames(NetVladTower, frames, every_n, max_frames, model, world, precision)
 
 
 def check_nextvlad_frames(frames, every_n, max_frames, model=None, world=1, precision="bf16"):
@@ -950,18 +982,10 @@ def check_nextvlad_frames(frames, every_n, max_frames, model=None, world=1, prec
         raise ValueError("--nextvlad_frames %r: one of %s" % (frames, "|".join(NeXtVladTower.FRAME_MODES)))
     if frames != "grid":
         return
-    if model is not None and model != "NeXtVLADModel":
-        raise ValueError("--nextvlad_frames grid is built for --model NeXtVLADModel, not %s" % model)
-    if every_n < 1 or every_n > max_frames:
-        raise ValueError("--nextvlad_frames grid: --every_n %d must lie in 1 .. --max_num_frames %d" % (every_n, max_frames))
-    if world > 1:
-        raise ValueError("--nextvlad_frames grid refuses a process group of %d ranks: ragged ranks hold different row counts and the "
-                         "batch-norm statistics assume equal ones; data parallelism is not built for this mode" % world)
-    if precision != "bf16":
-        raise ValueError("--nextvlad_frames grid: --precision %s is refused, the NeXtVLAD tower has no such forward mode (bf16 only)" % precision)
+    check_grid_frames(NeXtVladTower, frames, every_n, max_frames, model, world, precision)
 
 
-class NeXtVladTower(TowerBase):
+class NeXtVladTower(VladTower):
     """NeXtVLAD aggregation tower (Lin, Xiao, Fan 2018) - an EXTENSION: the reference ships NeXtVLADModel as an empty stub
     (cs/frame_level_models.py:349-355), so there is no reference math; the binding definition is DESIGN.md 7.12, restated in
     float64 in tests/_nextvlad_ref.py: sample S frames -> expansion (.We + be, E = expansion * F) -> per group g of D = E / G
@@ -988,8 +1012,7 @@ class NeXtVladTower(TowerBase):
     when none is given, as train.main builds the tower - so ranks drop different elements.  At rate 0, with is_training=False or on
     a forward-only tower the launches are the ones without the feature."""
 
-    PRECISIONS = ("bf16",)             # no split-bf16 forward (set_precision refuses anything else)
-    FRAME_MODES = ("sampled", "grid")
+    FAMILY, MODEL, FLAG, NOT_A_CHECKPOINT = "NeXtVLAD", "NeXtVLADModel", "--nextvlad", "not a NeXtVLADModel checkpoint of that tower"
 
     EW, EB, AW, AB = "expansion_weights", "expansion_biases", "attention_weights", "attention_biases"
     CW, C2, HW, G1, G2 = "cluster_weights", "cluster_weights2", "hidden1_weights", "gating_weights_1", "gating_weights_2"
@@ -1104,18 +1127,6 @@ class NeXtVladTower(TowerBase):
         shapes.update(MoeHead.shapes(H, vocab_size, num_mixtures))
         return shapes
 
-    @classmethod
-    def checkpoint_shapes(cls, *sizes, **kw):
-        """What state_dict() holds for these size flags, without the scope prefix: every variable in its TF layout (2-D weights
-        [in][out]) and the batch norms' moving statistics.  For checking a checkpoint against the flags before a tower is built."""
-        out = OrderedDict()
-        for k, shp in cls.variable_shapes(*sizes, **kw).items():
-            out[k] = tuple(reversed(shp)) if len(shp) == 2 else tuple(shp)
-            if k.endswith("/gamma"):
-                for v in ("moving_mean", "moving_variance"):
-                    out[k[:-len("gamma")] + v] = tuple(shp)
-        return out
-
     # TF order d*K + k  <->  internal cluster-major k*D + d: the rows of hidden1_weights [K*D, H] and every vlad_bn vector
     def _tf_keys(self, prefix):
         return ["%s/vlad_bn/%s" % (prefix, v) for v in ("beta", "gamma", "moving_mean", "moving_variance")]
@@ -1146,25 +1157,9 @@ class NeXtVladTower(TowerBase):
     def _alloc(self, B):
         dev, F, S, K, H, G, E, D, Hg, AP = self.device, self.F, self.S, self.Kc, self.Hd, self.G, self.E, self.D, self.Hg, self.AP
         grid = self.frames == "grid"
-        if grid:
-            # every row buffer once, for every video at full length; a batch uses its first R (Rp in the TN products) rows.
-            # The bf16 operands of the TN products start as zeros: their rows R .. Rp are zeroed again at every step.
-            self.B, self.R, self.Rp, self.plan = B, 0, 0, None
-            R = ops.grid_capacity(B, self.T, self.every_n)
-            self.row_off = torch.zeros(B + 1, dtype=torch.int32, device=dev)
-            self._row_off_host = [torch.zeros(B + 1, dtype=torch.int32).pin_memory() for _ in range(2)]
-            if not self.training:                                    # a served subset of the batch's videos (forward(sel=...))
-                self.sel = torch.zeros(B, dtype=torch.int32, device=dev)
-                self._sel_host = [torch.zeros(B, dtype=torch.int32).pin_memory() for _ in range(2)]
-            self._row_off_done = [None, None]
-            self._uploads = 0
-        else:
-            self.B, self.R = B, B * S
-            if self.training and self.R % 32:
-                raise ValueError("batch_size x iterations = %d must be a multiple of 32 (row count of the TN weight-gradient products)" % self.R)
-            R = self.R
-        self.cap = B                                                 # videos the buffers hold (forward-only grid towers serve B <= cap)
-        self.Bk = ops.round_up(B, 32)
+        # (grid: the bf16 operands of the TN products start as zeros; their rows R .. Rp are zeroed again at every step.  A forward-only
+        # tower can serve a subset of the batch's videos, forward(sel=...))
+        R = self._alloc_rows(B, with_sel=not self.training)
         self.r = torch.empty((R, F), dtype=F32, device=dev)
         if not grid:
             self.idx = torch.empty((B, S), dtype=torch.int32, device=dev)
@@ -1209,10 +1204,6 @@ class NeXtVladTower(TowerBase):
             self.colsum_ws = torch.empty(32 * E, dtype=F32, device=dev)    # partial rows of the two bias-gradient column sums
             self.dWa_pad = torch.empty((AP, E), dtype=F32, device=dev)      # the attention weight gradient on a whole tile of rows
 
-    def _plan_rows(self, num_frames, num_frames_host, sel=None):
-        """Grid mode: this batch's packed layout from the HOST frame counts (_plan_grid_rows)."""
-        return _plan_grid_rows(self, num_frames, num_frames_host, sel, "--nextvlad_frames")
-
     def forward(self, x, num_frames, uniform=None, normalize=True, is_training=True, num_frames_host=None, sel=None, dropout_step=0):
         """x [B,T,F] float32 or uint8 raw frames; uniform [B,S] f32 in [0,1): the frame-sampling draw (sampled mode; not read
         in grid mode, which takes num_frames_host, the frame counts on the host, instead).
@@ -1228,11 +1219,7 @@ class NeXtVladTower(TowerBase):
                 raise ValueError("forward(sel=...) is built for forward-only grid towers (training=False, frames='grid')")
             sel = ops.check_row_selection(sel, B)                    # (on the host, before any launch)
             B = int(sel.shape[0])
-        if B != self.B:
-            if serving and B <= self.cap:
-                self.B = B
-            else:
-                self._alloc(B)
+        self._fit_batch(B)
         if self.precision != "bf16":
             raise NotImplementedError("NeXtVladTower has no split-bf16 mode")
         grid = self.frames == "grid"
@@ -1241,7 +1228,7 @@ class NeXtVladTower(TowerBase):
         if grid:
             if x.shape[1] != self.T:
                 raise ValueError("the batch holds %d frames per video, the tower was built for max_frames=%d" % (x.shape[1], self.T))
-            plan = self._plan_rows(num_frames, num_frames_host, sel)
+            plan = self._plan_grid_rows(num_frames, num_frames_host, sel)
             R, Rp = plan.R, plan.Rp
             row_off = self.row_off[:B + 1]
             if sel is None:
@@ -1360,17 +1347,11 @@ class NeXtVladTower(TowerBase):
         if on_stage is not None:
             on_stage(2)
 
-    @property
-    def pred(self):
-        return self.moe.pred if self.B == self.cap else self.moe.pred[:self.B]
+    def step_kwargs(self, global_step):
+        """(the dropout mask is a function of the step: a restored run draws the same masks)"""
+        return {"dropout_step": global_step}
 
-    @property
-    def state(self):
-        return self.out if self.B == self.cap else self.out[:self.B]
-
-    @property
-    def rowsum(self):
-        return self.moe.rowsum if self.B == self.cap else self.moe.rowsum[:self.B]
+    state = property(lambda self: self._live(self.out))
 
 
 class LogisticTower(TowerBase):

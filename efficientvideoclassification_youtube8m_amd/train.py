@@ -25,9 +25,9 @@ small model, or a teacher next to the teaching assistants distilled from it (dis
 the train_finetune step with the loss section evc_distill_losses_sparse, no teacher tower in memory (distill.OfflineDistillGraph,
 DESIGN.md 7.11).
 ``--model NeXtVLADModel --nextvlad_frames grid --every_n N --teacher_dir DIR`` trains a grid student against the frozen grid teacher of
-DIR's latest checkpoint, which runs on the frames its checkpoint records (distill.NeXtVladDistillGraph, DESIGN.md 7.14);
+DIR's latest checkpoint, which runs on the frames its checkpoint records (vlad_graphs.NeXtVladDistillGraph, DESIGN.md 7.14);
 ``--model NetVLADModel --netvlad_frames grid --every_n N --teacher_dir DIR`` does the same for the NetVLAD family
-(distill.NetVladDistillGraph).  With ``--student_sampling WORD`` a NetVLAD grid tower - alone or as that student - runs on
+(vlad_graphs.NetVladDistillGraph).  With ``--student_sampling WORD`` a NetVLAD grid tower - alone or as that student - runs on
 the frames the word selects instead of the grid.
 Multi-GPU: launch with ``python -m torch.distributed.run --nproc-per-node N``;
 ``--gpu`` is then ignored in favour of LOCAL_RANK.
@@ -44,10 +44,11 @@ import numpy as np
 import torch
 
 from . import eval_util, frame_level_models, losses, ops, readers, video_level_models
-from .distill import (DistillGraph, EnsembleDistillGraph, NetVladDistillGraph, NeXtVladDistillGraph, OfflineDistillGraph, SerialStudentsGraph,
-                      SingleTowerGraph)
+from .distill import DistillGraph, EnsembleDistillGraph, OfflineDistillGraph, SerialStudentsGraph, SingleTowerGraph
 from .flags import FLAGS, GetListOfFeatureNamesAndSizes
 from .towers import DbofTower, LogisticTower, NetVladTower, NeXtVladTower, check_netvlad_frames, check_netvlad_gating, check_nextvlad_frames
+from .vlad_graphs import (GridDistillGraph, NetVladDistillGraph, NeXtVladDistillGraph, check_netvlad_checkpoint, check_vlad_checkpoint,
+                          netvlad_checkpoint_gating)
 
 NUM_CLASSES = 4716       # readers.YT8MFrameFeatureReader default num_classes (cs/readers.py:121)
 
@@ -383,17 +384,35 @@ def nextvlad_size_flags():
             FLAGS.nextvlad_gating_reduction, FLAGS.moe_num_mixtures)
 
 
-def check_nextvlad_distill_flags():
-    """--teacher_dir with --model NeXtVLADModel: the combinations it refuses, as ValueErrors that name the flags (no device).  Returns True
-    when the flags ask for it.  (--serial_student_dirs, --teacher_dirs and --teacher_preds_pattern refuse every model but
-    HierarchicalLstmModel themselves: they are not built for this family.  --teacher_only, --finetune, several ranks: check_serial_flags;
-    another --label_loss: check_label_loss; another --precision, --every_n out of range: check_nextvlad_frames.)"""
-    if not FLAGS.teacher_dir or FLAGS.model != "NeXtVLADModel":
-        return False
-    if FLAGS.nextvlad_frames != "grid":
-        raise ValueError("--teacher_dir %s with --model NeXtVLADModel and --nextvlad_frames %s: the student of this family is a grid tower "
-                         "(--nextvlad_frames grid --every_n N); distillation of sampled towers is not built" % (FLAGS.teacher_dir, FLAGS.nextvlad_frames))
-    return True
+def netvlad_size_flags():
+    """The size flags of a NetVLAD tower, in the order of NetVladTower.variable_shapes (after the feature size and the classes)."""
+    return (FLAGS.netvlad_cluster_size, FLAGS.netvlad_hidden_size, FLAGS.moe_num_mixtures)
+
+
+def frames_key(fam):
+    """'nextvlad_frames' | 'netvlad_frames': the family's frames flag without its dashes, which is also its checkpoint key."""
+    return fam["tower"].FLAG[2:] + "_frames"
+
+
+def check_vlad_distill_flags(model=None):
+    """--teacher_dir with a VLAD --model (``model``: that one alone): the combinations it refuses, as ValueErrors that name the flags (no
+    device).  Returns the family (VLAD_FAMILIES) when the flags ask for it, else None.  (--serial_student_dirs, --teacher_dirs and
+    --teacher_preds_pattern refuse every model but HierarchicalLstmModel themselves: they are not built for these families.
+    --teacher_only, --finetune, several ranks: check_serial_flags; another --label_loss: check_label_loss; another --precision,
+    --every_n out of range: the family's check_frames.)"""
+    fam = VLAD_FAMILIES.get(FLAGS.model)
+    if not FLAGS.teacher_dir or fam is None or model not in (None, FLAGS.model):
+        return None
+    key = frames_key(fam)
+    if getattr(FLAGS, key) != "grid":
+        raise ValueError("--teacher_dir %s with --model %s and --%s %s: the student of this family is a grid tower "
+                         "(--%s grid --every_n N); distillation of sampled towers is not built"
+                         % (FLAGS.teacher_dir, FLAGS.model, key, getattr(FLAGS, key), key))
+    return fam
+
+
+def check_netvlad_distill_flags():
+    return check_vlad_distill_flags("NetVLADModel") is not None
 
 
 def check_nextvlad_dropout_flags():
@@ -414,57 +433,57 @@ def nextvlad_dropout_metadata(graph):
     return {"nextvlad_dropout": rate, "nextvlad_dropout_seed": int(tw.dropout_seed)} if rate > 0.0 else {}
 
 
-def nextvlad_teacher_every_n(sd):
-    """The grid the model/* tower of the checkpoint dict ``sd`` runs on as a frozen teacher: the teacher_every_n a distillation
-    checkpoint records (its model/* IS such a teacher), else its every_n when it records nextvlad_frames == "grid", else 1 - a sampled
-    checkpoint, whose weights load into a grid tower, sees every real frame."""
-    if sd.get("nextvlad_frames") == "grid":
+def vlad_teacher_every_n(sd, key):
+    """The grid the model/* tower of the checkpoint dict ``sd`` runs on as a frozen teacher (key: the family's frames_key): the
+    teacher_every_n a distillation checkpoint records (its model/* IS such a teacher), else its every_n when it records <key> == "grid",
+    else 1 - a sampled checkpoint, whose weights load into a grid tower, sees every real frame."""
+    if sd.get(key) == "grid":
         return int(sd["teacher_every_n"]) if "teacher_every_n" in sd else int(sd["every_n"])
     return 1
 
 
+nextvlad_teacher_every_n = lambda sd: vlad_teacher_every_n(sd, "nextvlad_frames")
+netvlad_teacher_every_n = lambda sd: vlad_teacher_every_n(sd, "netvlad_frames")
+
+
 def check_nextvlad_teacher_shapes(sd, feature_size, what=""):
     """model/* of the checkpoint dict ``sd`` against the size flags: ValueError naming the first missing or mismatching variable."""
-    want = NeXtVladTower.checkpoint_shapes(feature_size, NUM_CLASSES, *nextvlad_size_flags())
+    prefix = "--teacher_dir %s: " % FLAGS.teacher_dir
     if not any(k.startswith("model/") and torch.is_tensor(v) for k, v in sd.items()):
-        raise ValueError("--teacher_dir %s: %s holds no model/* variables (not a teacher checkpoint)" % (FLAGS.teacher_dir, what))
-    for k, shp in want.items():
-        have = sd.get("model/" + k)
-        if not torch.is_tensor(have):
-            raise ValueError("--teacher_dir %s: %s holds no variable model/%s (not a NeXtVLADModel checkpoint)" % (FLAGS.teacher_dir, what, k))
-        if tuple(have.shape) != shp:
-            raise ValueError("--teacher_dir %s: model/%s of %s has shape %s, the size flags (--nextvlad_* / --feature_sizes / "
-                             "--moe_num_mixtures) give %s" % (FLAGS.teacher_dir, k, what, tuple(have.shape), shp))
+        raise ValueError("%s%s holds no model/* variables (not a teacher checkpoint)" % (prefix, what))
+    check_vlad_checkpoint(NeXtVladTower, sd, "model", feature_size, NUM_CLASSES, nextvlad_size_flags(), what, prefix=prefix,
+                          clause="not a NeXtVLADModel checkpoint")
 
 
-def nextvlad_distill_source(feature_size):
-    """The checkpoint the frozen NeXtVLAD teacher comes from, read on the host before the device is touched: --train_dir's latest on
-    resume, else --teacher_dir's.  Returns {"ck", "sd", "teacher_every_n", "resume"}."""
+def vlad_distill_source(fam, feature_size):
+    """The checkpoint the frozen teacher of a VLAD family comes from, read on the host before the device is touched: --train_dir's latest
+    on resume, else --teacher_dir's; its model/* variables against the size flags.  Returns {"ck", "sd", "teacher_every_n", "resume"};
+    NetVLAD adds "teacher_sampling" and "teacher_gating".  teacher_gating: whether model/* holds the context gate's variables (DESIGN.md
+    7.21) - the frozen teacher is built as its checkpoint says, the student as --netvlad_gating says; on resume the flag must agree with
+    model_student/*, and --student_init_from_teacher needs the two gates to agree."""
     resume = None if FLAGS.start_new_model else latest_checkpoint(FLAGS.train_dir)
     ck = resume or latest_checkpoint(FLAGS.teacher_dir)
     if ck is None:
         raise ValueError("--teacher_dir %s: no model.ckpt-*.pt checkpoint there" % FLAGS.teacher_dir)
     sd = torch.load(ck, map_location="cpu")
-    check_nextvlad_teacher_shapes(sd, feature_size, os.path.basename(ck))
-    return dict(ck=ck, sd=sd, teacher_every_n=nextvlad_teacher_every_n(sd), resume=resume is not None)
+    src = lambda: dict(ck=ck, sd=sd, teacher_every_n=vlad_teacher_every_n(sd, frames_key(fam)), resume=resume is not None)
+    if fam["tower"] is NeXtVladTower:
+        check_nextvlad_teacher_shapes(sd, feature_size, os.path.basename(ck))
+        return src()
+    what = "--teacher_dir %s: %s" % (FLAGS.teacher_dir, os.path.basename(ck))
+    if not any(k.startswith("model/") and torch.is_tensor(v) for k, v in sd.items()):
+        raise ValueError("%s holds no model/* variables (not a teacher checkpoint)" % what)
+    teacher_gating = netvlad_checkpoint_gating(sd, "model")
+    check_netvlad_checkpoint(sd, "model", feature_size, NUM_CLASSES, netvlad_size_flags(), what, gating=teacher_gating)
+    if resume is not None:
+        check_netvlad_gating_checkpoint(sd, "model_student", "--train_dir %s: %s" % (FLAGS.train_dir, os.path.basename(ck)))
+    elif FLAGS.student_init_from_teacher and teacher_gating != bool(FLAGS.netvlad_gating):
+        raise ValueError("--student_init_from_teacher True with --netvlad_gating %s: the teacher of %s was trained %s the context gate, "
+                         "its variables do not fill this student" % (FLAGS.netvlad_gating, what, "with" if teacher_gating else "without"))
+    return dict(src(), teacher_sampling=netvlad_teacher_sampling(sd), teacher_gating=teacher_gating)
 
 
-def netvlad_size_flags():
-    """The size flags of a NetVLAD tower, in the order of NetVladTower.variable_shapes (after the feature size and the classes)."""
-    return (FLAGS.netvlad_cluster_size, FLAGS.netvlad_hidden_size, FLAGS.moe_num_mixtures)
-
-
-def check_netvlad_distill_flags():
-    """--teacher_dir with --model NetVLADModel: the combinations it refuses, as ValueErrors that name the flags (no
-    device).  Returns True when the flags ask for it.  (--serial_student_dirs, --teacher_dirs and --teacher_preds_pattern refuse every
-    model but HierarchicalLstmModel themselves: they are not built for this family.  --teacher_only, --finetune, several ranks:
-    check_serial_flags; another --label_loss: check_label_loss; another --precision, --every_n out of range: check_netvlad_frames.)"""
-    if not FLAGS.teacher_dir or FLAGS.model != "NetVLADModel":
-        return False
-    if FLAGS.netvlad_frames != "grid":
-        raise ValueError("--teacher_dir %s with --model NetVLADModel and --netvlad_frames %s: the student of this family is a grid tower "
-                         "(--netvlad_frames grid --every_n N); distillation of sampled towers is not built" % (FLAGS.teacher_dir, FLAGS.netvlad_frames))
-    return True
+netvlad_distill_source = lambda feature_size: vlad_distill_source(VLAD_FAMILIES["NetVLADModel"], feature_size)
 
 
 def netvlad_sampling_word(warn=False):
@@ -520,7 +539,6 @@ def netvlad_gating_metadata(graph):
 def check_netvlad_gating_checkpoint(sd, scope, what):
     """--netvlad_gating against the ``scope``/* tower of a checkpoint that training resumes from: a ValueError naming the flag and the
     variable found or missing when they disagree (no device)."""
-    from .distill import netvlad_checkpoint_gating
     have, key = netvlad_checkpoint_gating(sd, scope), "%s/%s" % (scope, NetVladTower.GW)
     if have and not FLAGS.netvlad_gating:
         raise ValueError("--netvlad_gating False, but %s holds the variable %s: resume it with --netvlad_gating True" % (what, key))
@@ -530,7 +548,7 @@ def check_netvlad_gating_checkpoint(sd, scope, what):
 
 def check_netvlad_gating_flags(world=1, serial=False):
     """--netvlad_gating before the device is touched: refused on several ranks; on resume of a NetVLAD tower trained alone, the flag
-    against --train_dir's latest checkpoint (a distillation's resume is checked by netvlad_distill_source)."""
+    against --train_dir's latest checkpoint (a distillation's resume is checked by vlad_distill_source)."""
     if FLAGS.model != "NetVLADModel":
         return
     check_netvlad_gating(FLAGS.netvlad_gating, world)
@@ -550,39 +568,34 @@ def netvlad_teacher_sampling(sd):
     return sd.get("student_sampling", "uniform"), int(sd.get("student_sampling_seed", 0))
 
 
-def netvlad_teacher_every_n(sd):
-    """The grid the model/* tower of the checkpoint dict ``sd`` runs on as a frozen teacher: the teacher_every_n a distillation
-    checkpoint records (its model/* IS such a teacher), else its every_n when it records netvlad_frames == "grid", else 1 - a sampled
-    checkpoint, whose weights load into a grid tower, sees every real frame."""
-    if sd.get("netvlad_frames") == "grid":
-        return int(sd["teacher_every_n"]) if "teacher_every_n" in sd else int(sd["every_n"])
-    return 1
+def nextvlad_distill_kw(teacher_sampling, teacher_gating):
+    """NeXtVladDistillGraph's own keywords from the flags: the student's dropout."""
+    return dict(dropout=check_nextvlad_dropout_flags(), dropout_seed=FLAGS.nextvlad_dropout_seed)
 
 
-def netvlad_distill_source(feature_size):
-    """The checkpoint the frozen NetVLAD teacher comes from, read on the host before the device is touched: --train_dir's latest on
-    resume, else --teacher_dir's; its model/* variables against the size flags (distill.check_netvlad_checkpoint).  Returns {"ck", "sd",
-    "teacher_every_n", "resume", "teacher_sampling", "teacher_gating"}.  teacher_gating: whether model/* holds the context gate's
-    variables - the frozen teacher is built as its checkpoint says, the student as --netvlad_gating says; on resume the
-    flag must agree with model_student/*, and --student_init_from_teacher needs the two gates to agree."""
-    from .distill import check_netvlad_checkpoint, netvlad_checkpoint_gating
-    resume = None if FLAGS.start_new_model else latest_checkpoint(FLAGS.train_dir)
-    ck = resume or latest_checkpoint(FLAGS.teacher_dir)
-    if ck is None:
-        raise ValueError("--teacher_dir %s: no model.ckpt-*.pt checkpoint there" % FLAGS.teacher_dir)
-    sd = torch.load(ck, map_location="cpu")
-    what = "--teacher_dir %s: %s" % (FLAGS.teacher_dir, os.path.basename(ck))
-    if not any(k.startswith("model/") and torch.is_tensor(v) for k, v in sd.items()):
-        raise ValueError("%s holds no model/* variables (not a teacher checkpoint)" % what)
-    teacher_gating = netvlad_checkpoint_gating(sd, "model")
-    check_netvlad_checkpoint(sd, "model", feature_size, NUM_CLASSES, netvlad_size_flags(), what, gating=teacher_gating)
-    if resume is not None:
-        check_netvlad_gating_checkpoint(sd, "model_student", "--train_dir %s: %s" % (FLAGS.train_dir, os.path.basename(ck)))
-    elif FLAGS.student_init_from_teacher and teacher_gating != bool(FLAGS.netvlad_gating):
-        raise ValueError("--student_init_from_teacher True with --netvlad_gating %s: the teacher of %s was trained %s the context gate, "
-                         "its variables do not fill this student" % (FLAGS.netvlad_gating, what, "with" if teacher_gating else "without"))
-    return dict(ck=ck, sd=sd, teacher_every_n=netvlad_teacher_every_n(sd), resume=resume is not None,
-                teacher_sampling=netvlad_teacher_sampling(sd), teacher_gating=teacher_gating)
+def netvlad_distill_kw(teacher_sampling, teacher_gating):
+    """NetVladDistillGraph's own keywords from the flags and the teacher's checkpoint (vlad_distill_source): the sampling words (DESIGN.md
+    7.20) and the context gates (7.21), each pair only off its default - the call of 7.19 otherwise."""
+    kw = {}
+    if netvlad_sampling_word() != "uniform" or teacher_sampling[0] != "uniform":
+        kw.update(student_sampling=netvlad_sampling_word(), sampling_seed=FLAGS.student_sampling_seed,
+                  teacher_sampling=teacher_sampling[0], teacher_sampling_seed=teacher_sampling[1])
+    if FLAGS.netvlad_gating or teacher_gating:
+        kw.update(gating=FLAGS.netvlad_gating, teacher_gating=teacher_gating)
+    return kw
+
+
+# The VLAD families by --model name (DESIGN.md 7.22): what train reads of a family beyond its tower class (the tower names its model, its
+# flag prefix - the --<prefix>_frames flag, the <prefix>_frames checkpoint key - and its messages itself).  check_frames_kw / distill_kw:
+# the family's own step behind the shared part.  A third family is one more entry.
+VLAD_FAMILIES = {
+    "NeXtVLADModel": dict(tower=NeXtVladTower, distill_graph=NeXtVladDistillGraph, size_flags=nextvlad_size_flags,
+                          size_names=("cluster_size", "hidden_size", "groups", "expansion", "gating_reduction", "num_mixtures"),
+                          check_frames=check_nextvlad_frames, check_frames_kw=lambda: {}, distill_kw=nextvlad_distill_kw),
+    "NetVLADModel": dict(tower=NetVladTower, distill_graph=NetVladDistillGraph, size_flags=netvlad_size_flags,
+                         size_names=("cluster_size", "hidden_size", "num_mixtures"), check_frames=check_netvlad_frames,
+                         check_frames_kw=lambda: dict(sampling=netvlad_sampling_word()), distill_kw=netvlad_distill_kw),
+}
 
 
 def load_frozen_teacher(graph, teacher_dir):
@@ -663,34 +676,20 @@ def build_graph(model, label_loss_fn, feature_size, batch_size, every_n, device,
                             lstm_cells=FLAGS.lstm_cells, lstm_layers=FLAGS.lstm_layers,
                             num_mixtures=FLAGS.moe_num_mixtures, device=device, precision=FLAGS.precision,
                             student_sampling=FLAGS.student_sampling, sampling_seed=FLAGS.student_sampling_seed, **common)
-    if FLAGS.teacher_dir and isinstance(model, frame_level_models.NeXtVLADModel):
-        # the grid student against the frozen grid teacher; teacher_every_n: nextvlad_teacher_every_n of its checkpoint
+    fam = next((f for name, f in VLAD_FAMILIES.items() if isinstance(model, getattr(frame_level_models, name))), None)
+    if FLAGS.teacher_dir and fam is not None:
+        # the grid student against the frozen grid teacher; teacher_every_n / teacher_sampling / teacher_gating:
+        # what vlad_distill_source reads of the teacher's checkpoint
         check_serial_flags(finetune)
-        check_nextvlad_distill_flags()
-        check_nextvlad_frames(FLAGS.nextvlad_frames, every_n, FLAGS.max_num_frames, model=FLAGS.model, precision=FLAGS.precision)
+        check_vlad_distill_flags()
+        fam["check_frames"](getattr(FLAGS, frames_key(fam)), every_n, FLAGS.max_num_frames, model=FLAGS.model, precision=FLAGS.precision,
+                            **fam["check_frames_kw"]())
         common.pop("label_loss", None)            # (refused above for anything but CrossEntropyLoss, which the loss kernel has built in)
-        cs, hs, g, ex, gr, mx = nextvlad_size_flags()
-        return NeXtVladDistillGraph(batch_size, every_n=every_n, teacher_every_n=teacher_every_n, feature_size=feature_size,
-                                    vocab_size=NUM_CLASSES, max_frames=FLAGS.max_num_frames, cluster_size=cs, hidden_size=hs, groups=g,
-                                    expansion=ex, gating_reduction=gr, num_mixtures=mx, device=device, precision=FLAGS.precision,
-                                    distill_losses=FLAGS.distill_losses, dropout=check_nextvlad_dropout_flags(),
-                                    dropout_seed=FLAGS.nextvlad_dropout_seed, **common)
-    if FLAGS.teacher_dir and isinstance(model, frame_level_models.NetVLADModel):
-        # the grid student against the frozen grid teacher; teacher_every_n: netvlad_teacher_every_n of its checkpoint
-        check_serial_flags(finetune)
-        check_netvlad_distill_flags()
-        check_netvlad_frames(FLAGS.netvlad_frames, every_n, FLAGS.max_num_frames, model=FLAGS.model, precision=FLAGS.precision,
-                             sampling=netvlad_sampling_word())
-        common.pop("label_loss", None)            # (refused above for anything but CrossEntropyLoss, which the loss kernel has built in)
-        cs, hs, mx = netvlad_size_flags()
-        if netvlad_sampling_word() != "uniform" or teacher_sampling[0] != "uniform":      # (uniform: the call of 7.19)
-            common.update(student_sampling=netvlad_sampling_word(), sampling_seed=FLAGS.student_sampling_seed,
-                          teacher_sampling=teacher_sampling[0], teacher_sampling_seed=teacher_sampling[1])
-        if FLAGS.netvlad_gating or teacher_gating:                   # (neither: the call of 7.19)
-            common.update(gating=FLAGS.netvlad_gating, teacher_gating=teacher_gating)
-        return NetVladDistillGraph(batch_size, every_n=every_n, teacher_every_n=teacher_every_n, feature_size=feature_size,
-                                   vocab_size=NUM_CLASSES, max_frames=FLAGS.max_num_frames, cluster_size=cs, hidden_size=hs,
-                                   num_mixtures=mx, device=device, precision=FLAGS.precision, distill_losses=FLAGS.distill_losses, **common)
+        common.update(zip(fam["size_names"], fam["size_flags"]()))
+        common.update(fam["distill_kw"](teacher_sampling, teacher_gating))
+        return fam["distill_graph"](batch_size, every_n=every_n, teacher_every_n=teacher_every_n, feature_size=feature_size,
+                                    vocab_size=NUM_CLASSES, max_frames=FLAGS.max_num_frames, device=device, precision=FLAGS.precision,
+                                    distill_losses=FLAGS.distill_losses, **common)
     if FLAGS.teacher_dir:
         raise ValueError("--teacher_dir %s: serial distillation is built for HierarchicalLstmModel and NeXtVLADModel, not %s "
                          "(and for NetVLADModel with --netvlad_frames grid)" % (FLAGS.teacher_dir, type(model).__name__))
@@ -803,11 +802,9 @@ def save_checkpoint(graph, train_dir, rank):
         sd["distill_mode"], sd["distill_losses"] = "offline", ",".join(graph.offline_losses)
         sd["distill_teacher_files"] = graph.teacher_record
     if getattr(getattr(graph, "tower", None), "frames", None) == "grid":      # metadata: the frames this tower was trained on (--nextvlad_frames / --netvlad_frames grid)
-        sd["netvlad_frames" if isinstance(graph.tower, NetVladTower) else "nextvlad_frames"], sd["every_n"] = "grid", graph.tower.every_n
-    if isinstance(graph, NeXtVladDistillGraph):   # metadata: the student's grid and the one the frozen teacher in model/* runs on
-        sd["nextvlad_frames"], sd["every_n"], sd["teacher_every_n"] = "grid", graph.every_n, graph.teacher_every_n
-    if isinstance(graph, NetVladDistillGraph):    # the same for the NetVLAD family (distill_losses: recorded above, mode "serial")
-        sd["netvlad_frames"], sd["every_n"], sd["teacher_every_n"] = "grid", graph.every_n, graph.teacher_every_n
+        sd[type(graph.tower).FLAG[2:] + "_frames"], sd["every_n"] = "grid", graph.tower.every_n
+    if isinstance(graph, GridDistillGraph):       # metadata: the student's grid and the one the frozen teacher in model/* runs on
+        sd[graph.tower_cls.FLAG[2:] + "_frames"], sd["every_n"], sd["teacher_every_n"] = "grid", graph.every_n, graph.teacher_every_n
     sd.update(netvlad_sampling_metadata(graph))   # metadata: the --student_sampling word of a NetVLAD tower off the uniform grid
     sd.update(netvlad_gating_metadata(graph))     # metadata: --netvlad_gating of the tower / student and the frozen teacher's gate, when true
     sd.update(nextvlad_dropout_metadata(graph))   # metadata: --nextvlad_dropout and its seed, when the tower was trained with a non-zero rate
@@ -881,18 +878,18 @@ def main(argv=None):
     multi = serial_students(finetune, world)
     serial = check_serial_flags(finetune, world, students=multi)
     check_label_loss(find_class_by_name(FLAGS.label_loss, [losses])(), finetune)
-    nx_distill = serial and check_nextvlad_distill_flags()
+    vlad_fam = check_vlad_distill_flags("NeXtVLADModel") if serial else None
     check_nextvlad_dropout_flags()
     check_nextvlad_frames(FLAGS.nextvlad_frames, FLAGS.every_n, FLAGS.max_num_frames, model=FLAGS.model, world=world, precision=FLAGS.precision)
     check_netvlad_frames(FLAGS.netvlad_frames, FLAGS.every_n, FLAGS.max_num_frames, model=FLAGS.model, world=world, precision=FLAGS.precision,
                          sampling=netvlad_sampling_word())
     check_netvlad_gating_flags(world, serial=bool(serial))
     nx_src = None
-    if nx_distill:
+    if serial and vlad_fam is None:
+        vlad_fam = check_vlad_distill_flags("NetVLADModel")      # (this family's refusal has always come behind the flag checks above)
+    if vlad_fam is not None:
         # the teacher's checkpoint on the host - its grid and its shapes against the size flags -, before the device is touched
-        nx_src = nextvlad_distill_source(sum(GetListOfFeatureNamesAndSizes(FLAGS.feature_names, FLAGS.feature_sizes)[1]))
-    elif serial and check_netvlad_distill_flags():
-        nx_src = netvlad_distill_source(sum(GetListOfFeatureNamesAndSizes(FLAGS.feature_names, FLAGS.feature_sizes)[1]))
+        nx_src = vlad_distill_source(vlad_fam, sum(GetListOfFeatureNamesAndSizes(FLAGS.feature_names, FLAGS.feature_sizes)[1]))
     ens_sds = None
     if ens:
         # the teachers' checkpoints on the host, and - on resume - the recorded list against the flags: all before the device is touched
@@ -990,9 +987,9 @@ def main(argv=None):
     start, last_save, it = time.time(), time.time(), 0
     is_multi = isinstance(graph, SerialStudentsGraph)
     is_ens = isinstance(graph, EnsembleDistillGraph)
-    is_distill = isinstance(graph, (DistillGraph, NeXtVladDistillGraph, NetVladDistillGraph)) or is_multi or is_ens
+    is_distill = isinstance(graph, (DistillGraph, GridDistillGraph)) or is_multi or is_ens
     # --nextvlad_frames / --netvlad_frames grid (one tower, or the student and its frozen teacher): the packed rows are laid out from n_host
-    is_grid = getattr(getattr(graph, "tower", None), "frames", None) == "grid" or isinstance(graph, (NeXtVladDistillGraph, NetVladDistillGraph))
+    is_grid = getattr(getattr(graph, "tower", None), "frames", None) == "grid" or isinstance(graph, GridDistillGraph)
     steps_per_it = 2 if is_distill and not is_multi and graph.mode == "teacher_student" else 1
     copy_stream = torch.cuda.Stream(device=device)
     host_bufs = {}                       # pinned staging, two alternating sets (one may still be read while the next fills)

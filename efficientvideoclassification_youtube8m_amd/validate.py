@@ -25,11 +25,11 @@ no student_state_loss is reported and --train_dir only receives events.jsonl.
 --cascade_fractions, see inference.py; needs ``--run_once True``) evaluates a confidence cascade the same way: cascade.CascadeGraph merges
 each video's predictions from the last stage that ran it, loss and metrics are those of the merged predictions, and the share of the
 videos and the frames each stage read are logged and returned as ``cascade_stage_videos`` / ``cascade_stage_frames``.
-``--model NeXtVLADModel`` evaluates a NeXtVLAD checkpoint through distill.NeXtVladEvalGraph: a --teacher_dir checkpoint as
+``--model NeXtVLADModel`` evaluates a NeXtVLAD checkpoint through vlad_graphs.NeXtVladEvalGraph: a --teacher_dir checkpoint as
 teacher + student (the student's metrics, student_loss logged), a single-tower one as model/*, each tower on the grid its checkpoint
 records (--nextvlad_serve_every_n overrides); the graph is built for --train_dir's latest checkpoint, which must exist at the start.
 Ensemble members and cascade stages take their family from their own checkpoints, so H-LSTM and NeXtVLAD members mix.
-``--model NetVLADModel`` evaluates a NetVLAD checkpoint through distill.NetVladEvalGraph: model/* as a forward-only grid
+``--model NetVLADModel`` evaluates a NetVLAD checkpoint through vlad_graphs.NetVladEvalGraph: model/* as a forward-only grid
 tower on the grid the checkpoint records, every real frame for a --netvlad_frames sampled one (--netvlad_serve_every_n overrides); its
 variables are checked against the size flags on the host first.  A --teacher_dir checkpoint of this family is evaluated
 as teacher + student: the student's metrics on the recorded every_n, student_loss logged against the teacher on the recorded
@@ -106,7 +106,7 @@ def netvlad_source(reader, student_only=False):
     one; --netvlad_serve_every_n overrides the served tower's grid only.  "gating" / "teacher_gating" (DESIGN.md 7.21): the context gate of
     the served tower and of the teacher next to a served student, each read from its scope's own variables; --netvlad_gating is not
     consulted, a flag that disagrees with the served tower is logged as a warning."""
-    from .distill import check_netvlad_checkpoint, netvlad_checkpoint_gating
+    from .vlad_graphs import check_netvlad_checkpoint, netvlad_checkpoint_gating
     if student_only:
         raise ValueError("eval_finetune with --model NetVLADModel: there is no convert / finetune step for this family, so no "
                          "student-only checkpoint to evaluate")
@@ -140,7 +140,7 @@ def build_graph(reader, model, batch_size, device, student_only=False, label_los
     """cs/validate.py:107-189 / cs/eval_finetune.py:108-175.  nextvlad: nextvlad_source() for --model NeXtVLADModel (DESIGN.md 7.15);
     netvlad: netvlad_source() for --model NetVLADModel."""
     if isinstance(model, frame_level_models.NetVLADModel):
-        from .distill import NetVladEvalGraph
+        from .vlad_graphs import NetVladEvalGraph
         src = netvlad if netvlad is not None else netvlad_source(reader, student_only)
         return NetVladEvalGraph(batch_size, every_n=src["every_n"], feature_size=sum(reader.feature_sizes), vocab_size=reader.num_classes,
                                 max_frames=FLAGS.max_num_frames, cluster_size=FLAGS.netvlad_cluster_size,
