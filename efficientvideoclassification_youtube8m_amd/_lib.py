@@ -20,6 +20,8 @@ SIGNATURES = {
     "evc_sort_rows_by_len": [vp, i32, i32, vp, vp, vp, vp],
     "evc_frame_counts": [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp],
     "evc_gemm_nt": [vp, i64, vp, i64, vp, i64, i32, i32, i32, vp, i32, i32, vp],
+    "evc_gemm_kn": [vp, i64, vp, i64, i32, i32, vp, i64, vp, i64, i32, i32, vp, i64, i32, i32, vp, i32, i32, i32, vp],
+    "evc_gemm_kn_plan": [i32, i32, i32, i32, vp],
     "evc_gemm_nt_sqnorm": [vp, i64, vp, i64, vp, i64, i32, i32, i32, vp, f32, vp, vp, i64, vp],
     "evc_gemm_tn": [vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, i32, vp],
     "evc_gemm_tn2": [vp, i64, vp, i64, i32, vp, i64, i32, i32, vp, i64, i32, i32, i32, i32, vp],
@@ -178,7 +180,8 @@ SIGNATURES = {
 EXPORTS = tuple(SIGNATURES) + ("evc_version", "evc_last_error")
 # Entries that a library named by EVC_LIB may lack (a build of an older tree, for same-box A/B runs: DESIGN.md 9).  The in-tree library must have
 # them; a caller that can do without asks has() and takes the older entries' path.
-NEWER = ("evc_gemm_tn2_rows_skip", "evc_gemm_tn_plan", "evc_gemm_tn2_slabs_skip", "evc_fill_f32_cols", "evc_lstm_layer_bwd_live")
+NEWER = ("evc_gemm_tn2_rows_skip", "evc_gemm_tn_plan", "evc_gemm_tn2_slabs_skip", "evc_fill_f32_cols", "evc_lstm_layer_bwd_live", "evc_gemm_kn",
+         "evc_gemm_kn_plan")
 
 _lib = None
 

@@ -7,7 +7,7 @@ OUT="${EVC_OUT:-$HERE/../libevc_hip.so}"
 OBJ="${EVC_OBJ_DIR:-$HERE/build}"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=default -Wno-unused-result"
-SRCS="evc_gemm evc_gemm_tn evc_lstm_fwd evc_lstm_bwd evc_elementwise evc_dbof evc_netvlad evc_nextvlad evc_moe_norms evc_optim evc_topk evc_frame_select evc_distill_multi evc_distill_ensemble evc_distill_sparse evc_label_loss evc_frame_change evc_cascade"
+SRCS="evc_gemm evc_gemm_kn evc_gemm_tn evc_lstm_fwd evc_lstm_bwd evc_elementwise evc_dbof evc_netvlad evc_nextvlad evc_moe_norms evc_optim evc_topk evc_frame_select evc_distill_multi evc_distill_ensemble evc_distill_sparse evc_label_loss evc_frame_change evc_cascade"
 mkdir -p "$OBJ"
 # a stale object is only reused when neither its source nor any header changed (and the extra flags are the same)
 STAMP="$(cat "$HERE"/*.h "$HERE/../../include/evc.h" | md5sum | cut -d' ' -f1)-$(echo "$FLAGS $*" | md5sum | cut -d' ' -f1)"

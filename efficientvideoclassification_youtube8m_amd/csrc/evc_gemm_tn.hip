@@ -374,7 +374,7 @@ extern "C" int evc_sum_slabs(const float* slabs, int64_t slab_stride, int nslab,
 struct MoeUpdateParams {
   float* p; float* m; float* v;        // [V][K] f32, row stride K
   bf16_t* p_bf16;                      // forward shadow [V][K], or NULL (round 5: a "high" tower's forward reads the f16 + e4m3 images, not this one)
-  bf16_t* pT_bf16; long ldT;           // transposed shadow [K][ldT], ldT >= V
+  bf16_t* pT_bf16; long ldT;           // transposed shadow [K][ldT], ldT >= V, or NULL (plain bf16 form: the backward reads p_bf16)
   bf16_t* p_wide;                      // or NULL: wide split-bf16 image [V][2K] = [hi | lo] of the new weights (the "split" forward's operand)
   bf16_t* p_f16; uint8_t* p_fp8;       // or NULL: IEEE f16 image [V][K] and e4m3 image [V][2K] = [e4m3((w - f16(w)) lo_scale) | e4m3(w hi_scale)] of the
   float lo_scale, hi_scale;            // new weights (the "high" forward's operands: evc_gemm_nt_f16_fp8)
@@ -556,8 +556,10 @@ __global__ __launch_bounds__(Cfg::NT, 2) void moe_update_kernel(GemmOperandsT p,
                                         pack_bf16x2_hw(pn[2] - bf16_to_f32(pb[2]), pn[3] - bf16_to_f32(pb[3])));
         }
       }
+      if (u.pT_bf16) {                                 // (kernel-uniform)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) tile[(rcol + r) * TP + vl] = pb[r];
+        for (int r = 0; r < 4; ++r) tile[(rcol + r) * TP + vl] = pb[r];
+      }
     }
     __syncthreads();                                   // gbuf holds the new weights of this wave row, the transpose image its columns
     if (u.wsq_partial && wr == h) {                    // (kernel-uniform / wave-uniform)
@@ -579,8 +581,10 @@ __global__ __launch_bounds__(Cfg::NT, 2) void moe_update_kernel(GemmOperandsT p,
   // rows k of the transposed shadow: 4 bf16 per lane, BM/4 lanes per row (256 contiguous bytes), 64/(BM/4) rows per wave-instruction
   constexpr int TLPR = Cfg::BM / 4, RPW = 64 / TLPR;
   static_assert(TLPR <= 64 && 64 % TLPR == 0, "row of the transposed image must fit a wave");
+  // (pT_bf16 == NULL: a caller whose backward reads the forward image - evc_gemm_kn - keeps no transposed shadow; this phase and the LDS
+  //  image behind it are skipped, 2 of the pass's 30 bytes per parameter: profiles/moe_head_fwd_image_ab.txt)
   const int v4 = m0 + (lane % TLPR) * 4;
-  for (int kl = wave * RPW + lane / TLPR; kl < Cfg::BU; kl += (Cfg::NT / 64) * RPW) {
+  for (int kl = wave * RPW + lane / TLPR; u.pT_bf16 && kl < Cfg::BU; kl += (Cfg::NT / 64) * RPW) {
     const int k = n0 + kl;
     if (k >= K || v4 >= u.V) continue;                 // V % 4 == 0: a lane's 4 rows are all valid or all not
     const uint32_t* src = (const uint32_t*)(tile + kl * TP + (lane % TLPR) * 4);     // (4-byte aligned: TP is not a multiple of 4)
@@ -654,10 +658,12 @@ static int moe_grad_update_impl(const evc_bf16* dlogits, int64_t ld_dlogits, con
   EVC_REQUIRE(rows > 0 && rows % 32 == 0 && V > 0 && V % 4 == 0 && K > 0 && K % 8 == 0, EVC_ERR_BAD_SHAPE,
               "evc_moe_grad_update: rows=%d (%%32), V=%d (%%4), K=%d (%%8)", rows, V, K);
   EVC_REQUIRE(phase >= 0 && phase <= 2, EVC_ERR_BAD_ARG, "evc_moe_grad_update_phase: phase=%d (0 both, 1 norms, 2 update)", phase);
-  EVC_REQUIRE(ld_dlogits % 8 == 0 && ld_dlogits >= V && ldx % 8 == 0 && ldT % 4 == 0 && ldT >= V &&
+  EVC_REQUIRE(ld_dlogits % 8 == 0 && ld_dlogits >= V && ldx % 8 == 0 && (!pT_bf16 || (ldT % 4 == 0 && ldT >= V)) &&
               ((uintptr_t)dlogits % 16) == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)p % 16) == 0 && ((uintptr_t)m % 16) == 0 &&
               ((uintptr_t)v % 16) == 0 && ((uintptr_t)p_bf16 % 8) == 0 && ((uintptr_t)pT_bf16 % 8) == 0, EVC_ERR_BAD_ALIGN,
               "evc_moe_grad_update: operand alignment / leading dimensions");
+  EVC_REQUIRE(pT_bf16 || (p_bf16 && !p_wide && !p_f16), EVC_ERR_BAD_ARG,
+              "evc_moe_grad_update: pT_bf16 == NULL needs the plain bf16 form (p_bf16 written, no wide / f16 + e4m3 images)");
   hipStream_t st = (hipStream_t)stream;
   // 128x128 tiles, two workgroups per CU: the kernel is a stream over W, m, v with an 8-step GEMM in front - what
   // counts is how many epilogue loads are in flight per CU (256x256 tiles, one workgroup per CU: 3.4 TB/s)

@@ -699,6 +699,32 @@ class MoeHead:
             self.delT = torch.empty((V * Mx, self.Bp), dtype=BF16, device=dev)
             self.xT = torch.empty((K, self.Bp), dtype=BF16, device=dev)
             self.dx = torch.empty((B, K), dtype=F32, device=dev)
+        self.sync_bwd_images()
+
+    # bf16 precision, one process, B <= 256: backward contracts the FORWARD weight image (ops.gemm_kn), the tower keeps no transposed image
+    # of the two weight matrices (386 MB at the reference sizes) and the fused update writes none (28 instead of 30 bytes per parameter:
+    # profiles/moe_head_fwd_image_ab.txt).  False (set before the tower is built, or followed by sync_bwd_images()): the transposed image and
+    # ops.gemm_nt - the tests and A/B runs compare the two.  "high" / "split" towers (their update writes no bf16 forward image), heads of
+    # more than 256 rows and sharded heads (shard(): the data-parallel routes) keep the transposed image.
+    dx_fwd_image = True
+    dx_one_launch = True      # gates and experts parts of dX as the two K segments of one launch (False, or EVC_DETERMINISTIC: one launch each)
+
+    def sync_bwd_images(self):
+        """Makes the tower's shadow_bwd hold the two weight matrices' transposed images exactly when backward() reads them.  Their presence
+        in that dict is what every path goes by (backward, the updates, refresh_shadows): a path that needs an image that is not kept fails
+        on the missing key instead of reading a stale one."""
+        tw = self.tw
+        if not hasattr(self, "B") or not hasattr(tw, "shadow_bwd"):
+            return
+        fwd = bool(self.dx_fwd_image and getattr(tw, "precision", "bf16") == "bf16" and self.B <= 256 and self.K % 8 == 0 and ops.GEMM_KN)
+        for name in (self.GATES, self.EXPERTS):
+            if fwd:
+                tw.shadow_bwd.pop(name, None)
+            elif name not in tw.shadow_bwd:
+                p = tw.store.p(name)
+                sb = torch.zeros((p.shape[1], ops.round_up(p.shape[0], 64)), dtype=BF16, device=p.device)
+                ops.transpose_to_bf16(p, p.shape[0], p.shape[1], sb, sb.shape[1])
+                tw.shadow_bwd[name] = sb
 
     def forward(self, x, rows=None):
         """rows (bf16 mode only): the head of the first `rows` <= B rows of the allocated buffers (a served subset of the batch)."""
@@ -881,6 +907,8 @@ class MoeHead:
         world*slab rows so that equal slabs can be all-gathered in place) is complete on every rank."""
         tw = self.tw
         self.world, self.rank, self.slab, self._stale = world, rank, {}, False
+        self.dx_fwd_image = False                 # the sharded routes transpose the gathered rows: they keep the transposed images
+        self.sync_bwd_images()
         for name, Vn in ((self.GATES, self.V * (self.Mx + 1)), (self.EXPERTS, self.V * self.Mx)):
             tiles = (Vn + 127) // 128
             slab = (tiles + world - 1) // world * 128
@@ -958,11 +986,11 @@ class MoeHead:
                     logits = self.gate_logits if i == 0 else self.expert_logits
                     ops.moe_grad_norms(self.gram_a, Sa, self.gram_x, Sx, rows, dlog, logits,
                                        None if i == 0 else st.p(self.EBIAS), self.B, Vn, l2, self.wsq[i], self.norm_part, tw.sums[idx[name]])
-                    ops.moe_grad_update_apply(dlog, x, rows, Vn, K, pw, mw, vw, pfwd, tw.shadow_bwd[name], l2,
+                    ops.moe_grad_update_apply(dlog, x, rows, Vn, K, pw, mw, vw, pfwd, tw.shadow_bwd.get(name), l2,
                                               tw.sums[idx[name]], self.partial_ws, clip_norm, lr_t, self.wsq[i], beta1, beta2, eps,
                                               p_wide=wide, p_f16=w16, p_fp8=w8)
                 else:
-                    ops.moe_grad_update(dlog, x, rows, Vn, K, pw, mw, vw, pfwd, tw.shadow_bwd[name], l2,
+                    ops.moe_grad_update(dlog, x, rows, Vn, K, pw, mw, vw, pfwd, tw.shadow_bwd.get(name), l2,
                                         tw.sums[idx[name]], self.partial_ws, clip_norm, lr_t, beta1, beta2, eps, p_wide=wide, p_f16=w16, p_fp8=w8)
                     self._wsq_valid[0 if name == self.GATES else 1] = False      # this matrix's carried |W|^2 is stale now
                 refreshed_wide = refreshed_wide or wide is not None or w16 is not None
@@ -1001,12 +1029,21 @@ class MoeHead:
         tw, B, V, Mx, K = self.tw, self.B, self.V, self.Mx, self.K
         ops.moe_tail_bwd(self.gate_logits, self.expert_logits, dpred, B, V, Mx, self.dgl, self.del_)
         V3p, V2p = self.dgl.shape[1], self.del_.shape[1]
-        if dx_init is None:
-            ops.gemm_nt(self.dgl, tw.shadow_bwd[self.GATES], B, K, V3p, self.dx)
-        else:
+        if dx_init is not None:
             self.dx.copy_(dx_init)
-            ops.gemm_nt(self.dgl, tw.shadow_bwd[self.GATES], B, K, V3p, self.dx, accumulate=True)
-        ops.gemm_nt(self.del_, tw.shadow_bwd[self.EXPERTS], B, K, V2p, self.dx, accumulate=True)
+        if self.GATES not in tw.shadow_bwd:
+            # dX = dlogits . W contracts the rows of the FORWARD image [V][K] (ops.gemm_kn; sync_bwd_images): the factors' zero pad columns
+            # meet copies of the image's last row.  One launch with the experts part as the second K segment, or - the sum order of the
+            # transposed-image path, bit for bit when K is not split: EVC_DETERMINISTIC - one launch per matrix.
+            Wg, We, acc = tw.shadow_fwd[self.GATES], tw.shadow_fwd[self.EXPERTS], dx_init is not None
+            if self.dx_one_launch and not ops.DETERMINISTIC:
+                ops.gemm_kn(self.dgl, Wg, B, K, V3p, self.dx, A2=self.del_, B2=We, K2=V2p, accumulate=acc, b_rows=V * (Mx + 1), b_rows2=V * Mx)
+            else:
+                ops.gemm_kn(self.dgl, Wg, B, K, V3p, self.dx, accumulate=acc, b_rows=V * (Mx + 1))
+                ops.gemm_kn(self.del_, We, B, K, V2p, self.dx, accumulate=True, b_rows=V * Mx)
+        else:
+            ops.gemm_nt(self.dgl, tw.shadow_bwd[self.GATES], B, K, V3p, self.dx, accumulate=dx_init is not None)
+            ops.gemm_nt(self.del_, tw.shadow_bwd[self.EXPERTS], B, K, V2p, self.dx, accumulate=True)
         if not weight_grads:
             return self.dx
         Bp = self.Bp
@@ -1028,6 +1065,25 @@ class MoeHead:
         return self.dx
 
 
+class _BwdImages(dict):
+    """tower.shadow_bwd: weight name -> the RESIDENT transposed bf16 image [cols][round_up(rows, 64)] the backward products read.  The two
+    matrices of a MoE head that contracts its forward image have no resident entry (MoeHead.sync_bwd_images): `in` and .get() say so, and
+    every engine path goes by them.  Indexing one of the two anyway - a test or a tool that inspects the image - returns a fresh transpose
+    of the current forward image; it is not kept, so nothing can read a stale one."""
+
+    def __init__(self, tower):
+        super().__init__()
+        self._tower = tower
+
+    def __missing__(self, k):
+        fwd = self._tower.shadow_fwd.get(k) if k in (MoeHead.GATES, MoeHead.EXPERTS) else None
+        if fwd is None:
+            raise KeyError(k)
+        sb = torch.zeros((fwd.shape[1], ops.round_up(fwd.shape[0], 64)), dtype=BF16, device=fwd.device)
+        ops.transpose_to_bf16(fwd, fwd.shape[0], fwd.shape[1], sb, sb.shape[1])
+        return sb
+
+
 class TowerBase:
     """Parameter store + bf16 shadows + per-tensor clip / TF-Adam shared by all model towers."""
 
@@ -1042,7 +1098,7 @@ class TowerBase:
     def _setup_store(self, shapes, transposed_2d=True):
         self.store = ParamStore(shapes, self.device)
         self.names = list(shapes.keys())
-        self.shadow_fwd, self.shadow_bwd = {}, {}
+        self.shadow_fwd, self.shadow_bwd = {}, _BwdImages(self)
         for k, shp in shapes.items():
             if len(shp) == 2:
                 self.shadow_fwd[k] = torch.zeros(shp, dtype=BF16, device=self.device)
@@ -1088,6 +1144,7 @@ class TowerBase:
     def refresh_shadows(self, fwd=True):
         if getattr(self, "moe", None) is not None:
             self.moe.invalidate_norm_cache()             # (called whenever the f32 masters were written from outside)
+            self.moe.sync_bwd_images()                   # (set_precision: a "high" / "split" head reads the transposed images, a bf16 one need not)
         for k in self.shadow_fwd:
             p = self.store.p(k)
             if self.precision != "bf16":
@@ -1095,7 +1152,9 @@ class TowerBase:
                 self._refresh_high(k)
             elif fwd:
                 ops.cast_bf16(p, self.shadow_fwd[k])
-            sb = self.shadow_bwd[k]
+            sb = self.shadow_bwd.get(k)
+            if sb is None:                               # (a MoE head that contracts the forward image: MoeHead.sync_bwd_images)
+                continue
             il = p.shape[0] // 4 if k.endswith("basic_lstm_cell/kernel") else 0     # LSTM: gate-interleaved 4H axis
             ops.transpose_to_bf16(p, p.shape[0], p.shape[1], sb, sb.shape[1], interleave_H=il)
 

@@ -62,6 +62,24 @@ def gemm_nt(A, B, M, N, K, out, bias=None, accumulate=False, lda=None, ldb=None,
     return out
 
 
+def gemm_kn(A, B, M, N, K, out, A2=None, B2=None, K2=0, bias=None, accumulate=False, splits=0, b_rows=0, b_rows2=0, lda=None, ldb=None, ldc=None):
+    """out[M,N] (+)= A[M,K] @ B[K,N] (+ A2[M,K2] @ B2[K2,N]) (+ bias): B bf16 with the CONTRACTION index as its row (evc_gemm_kn; M <= 256).
+    b_rows (0: K): the rows B really has - the rows up to K are read as its last row, A's columns there must be zero.  splits: 0 = by shape
+    (gemm_kn_splits), else forced."""
+    assert A.dtype == BF16 and B.dtype == BF16 and (A2 is None) == (B2 is None) == (K2 == 0)
+    _lib.call("evc_gemm_kn", _p(A), A.stride(0) if lda is None else lda, _p(B), B.stride(0) if ldb is None else ldb, K, b_rows,
+              _p(A2), A2.stride(0) if A2 is not None else 0, _p(B2), B2.stride(0) if B2 is not None else 0, K2, b_rows2,
+              _p(out), out.stride(0) if ldc is None else ldc, M, N, _p(bias), 1 if out.dtype == BF16 else 0, 1 if accumulate else 0, splits, _stream())
+    return out
+
+
+def gemm_kn_splits(N, K, K2=0, out_bf16=False):
+    """K splits evc_gemm_kn takes by itself for this shape in this process (no GPU needed)."""
+    s = C.c_int(0)
+    _lib.call("evc_gemm_kn_plan", N, K, K2, 1 if out_bf16 else 0, C.byref(s))
+    return s.value
+
+
 def _slab_rows_arg(live_rows, K):
     """(slab_rows, nslabs, host int32 array) of evc_gemm_tn2_rows from live_rows = (rows per slab [T], rows of one slab)."""
     rows, slab = live_rows
@@ -201,6 +219,7 @@ class _Once:
 
 # the TN products' plan query, skip entries and column fill: missing only from a library of an older tree named by EVC_LIB (_lib.NEWER)
 TN_PLAN = _Once(lambda: _lib.has("evc_gemm_tn_plan"))
+GEMM_KN = _Once(lambda: _lib.has("evc_gemm_kn"))      # the K-major-B product (the MoE head's dX from the forward weight image), likewise
 
 DETERMINISTIC = os.environ.get("EVC_DETERMINISTIC", "0") not in ("", "0")     # (the library reads the same variable: csrc/evc_common.h)
 
@@ -925,6 +944,10 @@ def moe_tail_bwd(gate_logits, expert_logits, dpred, B, V, M, dgate, dexpert):
               _p(dexpert), dexpert.stride(0), _stream())
 
 
+def _ld_or_0(t):
+    return t.stride(0) if t is not None else 0
+
+
 def moe_grad_update(dlogits, x, rows, V, K, p, m, v, p_bf16, pT_bf16, l2_coeff, sums, partial_ws, clip_norm, lr_t,
                     beta1=0.9, beta2=0.999, eps=1e-8, phase=0, p_wide=None, p_f16=None, p_fp8=None):
     """Fused weight-gradient + per-tensor clip + TF-Adam of one MoE weight matrix (evc_moe_grad_update); phase 1 / 2:
@@ -937,11 +960,11 @@ def moe_grad_update(dlogits, x, rows, V, K, p, m, v, p_bf16, pT_bf16, l2_coeff, 
         if p_f16 is not None:
             assert p_f16.dtype == F16 and p_f16.shape == (V, K) and p_fp8.dtype == torch.uint8 and p_fp8.shape == (V, 2 * K) and p_f16.is_contiguous() and p_fp8.is_contiguous()
         _lib.call("evc_moe_grad_update_wide", _p(dlogits), dlogits.stride(0), _p(x), x.stride(0), rows, V, K, _p(p), _p(m), _p(v),
-                  _p(p_bf16), _p(pT_bf16), pT_bf16.stride(0), _p(p_wide), _p(p_f16), _p(p_fp8), FP8_MOE["w_lo_exp"], FP8_MOE["w_hi_exp"],
+                  _p(p_bf16), _p(pT_bf16), _ld_or_0(pT_bf16), _p(p_wide), _p(p_f16), _p(p_fp8), FP8_MOE["w_lo_exp"], FP8_MOE["w_hi_exp"],
                   l2_coeff, _p(sums), _p(partial_ws), clip_norm, lr_t, beta1, beta2, eps, _stream())
         return
     _lib.call("evc_moe_grad_update_phase", _p(dlogits), dlogits.stride(0), _p(x), x.stride(0), rows, V, K, _p(p), _p(m), _p(v),
-              _p(p_bf16), _p(pT_bf16), pT_bf16.stride(0), l2_coeff, _p(sums), _p(partial_ws), clip_norm, lr_t, beta1, beta2, eps,
+              _p(p_bf16), _p(pT_bf16), _ld_or_0(pT_bf16), l2_coeff, _p(sums), _p(partial_ws), clip_norm, lr_t, beta1, beta2, eps,
               phase, _stream())
 
 
@@ -964,7 +987,7 @@ def moe_grad_update_apply(dlogits, x, rows, V, K, p, m, v, p_bf16, pT_bf16, l2_c
     """The update pass of evc_moe_grad_update alone (clip scale from sums[0]) + wsq_out[0] = sum of the new weights squared."""
     assert (p_f16 is None) == (p_fp8 is None)
     _lib.call("evc_moe_grad_update_apply", _p(dlogits), dlogits.stride(0), _p(x), x.stride(0), rows, V, K, _p(p), _p(m), _p(v),
-              _p(p_bf16), _p(pT_bf16), pT_bf16.stride(0), _p(p_wide), _p(p_f16), _p(p_fp8), FP8_MOE["w_lo_exp"], FP8_MOE["w_hi_exp"],
+              _p(p_bf16), _p(pT_bf16), _ld_or_0(pT_bf16), _p(p_wide), _p(p_f16), _p(p_fp8), FP8_MOE["w_lo_exp"], FP8_MOE["w_hi_exp"],
               l2_coeff, _p(sums), _p(partial_ws), clip_norm, lr_t, beta1, beta2, eps, _p(wsq_out), _stream())
 
 

@@ -110,6 +110,21 @@ int evc_frame_counts(const int32_t* num_frames, int B, int every_n, int subsampl
  * K % 64 == 0.  bias may be NULL. */
 int evc_gemm_nt(const evc_bf16* A, int64_t lda, const evc_bf16* B, int64_t ldb, void* C, int64_t ldc,
                 int M, int N, int K, const float* bias, int out_bf16, int accumulate, void* stream);
+/* K-major-B product (an addition, no existing entry changed): C[M,N] (+)= A1[M,K1] . B1[K1,N] (+ A2[M,K2] . B2[K2,N]) (+ bias[N]), B with the
+ * CONTRACTION index as its row (N contiguous) - the MoE head's dX = dlogits . W on the forward weight image [V][K] (csrc/evc_gemm_kn.hip).
+ * bias, out_bf16, accumulate as evc_gemm_nt.  With equal K splits the result has the bits of evc_gemm_nt on a transposed copy of B.
+ *   b_rows1 / b_rows2 (0: K1 / K2): the rows B1 / B2 really have; the rows from there up to K are read as the last row, and A's columns there
+ *   must be zero (factor images padded with zero columns).  K2 == 0: one segment, A2 / B2 ignored.
+ *   splits: 0 = chosen as evc_gemm_nt does for its batch-row tile (1 under EVC_DETERMINISTIC or for a bf16 output; evc_gemm_kn_plan tells),
+ *   n > 1 forces n K splits joined by f32 atomics into a C that is zeroed first unless accumulate.
+ * Refused before anything is enqueued: a NULL operand, K2 > 0 without A2 / B2, out_bf16 with accumulate or with splits > 1, a split count
+ *   that leaves a split empty (EVC_ERR_BAD_ARG); M > 256 (only the batch-row tile is built), K1 / K2 / N not multiples of 8, b_rows outside
+ *   1 .. K, a leading dimension shorter than its row, an operand of 4 GiB or more (EVC_ERR_BAD_SHAPE); pointers not 16-byte aligned or
+ *   lda / ldb not multiples of 8 (EVC_ERR_BAD_ALIGN). */
+int evc_gemm_kn(const evc_bf16* A1, int64_t lda1, const evc_bf16* B1, int64_t ldb1, int K1, int b_rows1,
+                const evc_bf16* A2, int64_t lda2, const evc_bf16* B2, int64_t ldb2, int K2, int b_rows2,
+                void* C, int64_t ldc, int M, int N, const float* bias, int out_bf16, int accumulate, int splits, void* stream);
+int evc_gemm_kn_plan(int N, int K1, int K2, int out_bf16, int* splits);
 /* evc_gemm_nt (plain f32 output, no bias) + evc_grad_sqnorm in one pass (round 6): sums[0] += sum of (C + l2_coeff * P)^2 and sums[1] += sum of P^2 over the
  * product's elements (what evc_grad_sqnorm leaves), from the tiles' stores (P [M][N] f32 laid out as C; NULL with l2_coeff 0).  The MoE weight gradient that is materialised at 1024 rows
  * (cs/train.py:329-334 clip_by_norm of `MatMul(transpose_a=True)`, cs/video_level_models.py:423-435) needs no separate norm pass.  M > 512,
@@ -334,7 +349,10 @@ int evc_lstm_layer_bwd_live(const evc_bf16* w_il, const int32_t* len, int T, int
  *   under data parallelism rows = world x batch: the all-gathered factors replace the gradient all-reduce.
  *   partial_ws: 2 * ceil(V/128) * ceil(K/128) floats of scratch.  V % 4 == 0, K % 8 == 0.
  *   p_bf16 may be NULL (here and in the _wide / _phase / _apply forms): the forward shadow is then not written - a caller whose forward
- *   reads other operand images of W (the f16 + e4m3 images of _wide) saves 2 of the 34 bytes per parameter. */
+ *   reads other operand images of W (the f16 + e4m3 images of _wide) saves 2 of the 34 bytes per parameter.
+ *   pT_bf16 may be NULL (all forms, plain bf16 only: p_bf16 given, no _wide images; EVC_ERR_BAD_ARG otherwise; ldT is then ignored): the
+ *   transposed shadow is not written - a caller whose backward contracts p_bf16 itself (evc_gemm_kn) saves 2 of the 30 bytes per parameter.
+ *   p, m, v, p_bf16 and wsq_out get the same bits either way. */
 int evc_moe_grad_update(const evc_bf16* dlogits, int64_t ld_dlogits, const evc_bf16* x, int64_t ldx, int rows,
                         int V, int K, float* p, float* m, float* v, evc_bf16* p_bf16, evc_bf16* pT_bf16, int64_t ldT,
                         float l2_coeff, float* sums, float* partial_ws, float clip_norm, float lr_t,
